@@ -7,13 +7,18 @@ collective (weak scaling).  Rank 0 prints ONE JSON line.
 
 `value` (--workload auto) is BASELINE.json's config 3 as written: surface projection (sp.py:17-85) -> U-Net segmentation
 (pl.py:124-199: prepare, network, threshold / closing / erosion / boundary, two-valued watershed) -> cell tables
-(ti.py:880-909).  The classical variant of the same frame (projection -> watershed_segmentation (bim.py:446-476) -> cell
-tables) is timed in the same process and reported under "classical" (`--workload classical` makes it the headline).
-Both legs also report `value_with_pcie`: the same steps with every frame uploaded from pinned host memory and the
+(ti.py:880-909).  With --full, the classical variant of the same frame (projection -> watershed_segmentation (bim.py:446-476)
+-> cell tables) is timed in the same process and reported under "classical" (`--workload classical` makes it the headline),
+and both legs also report `value_with_pcie`: the same steps with every frame uploaded from pinned host memory and the
 projection + label map fetched back, i.e. what the drop-in functions (host arrays in and out) sustain.
 
 `python bench.py --gpus N` without a launcher environment starts N ranks itself (one process per GPU, RCCL process group
 on 127.0.0.1) and fails if fewer than N devices are visible; under torchrun it is one of the ranks.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps and the result line.  `--full` adds
+everything else the benchmark measures: the CPU baseline, the secondary leg, the per-kernel event repeat and isolated pass
+(kernel table, rooflines), the PCIe-inclusive repeat, the U-Net arithmetic modes and the label parity record.
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import ctypes
@@ -27,6 +32,7 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
+T_START = time.perf_counter()
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_VALU_PEAK_TF = 78.6   # MI355X datasheet FP64 vector (spec)
 FP32_VALU_PEAK_TF = 157.3  # MI355X_MICROARCH.md: FP32 vector (pure FMA stream; the passes' add+fma mix sustains 104-109)
@@ -274,6 +280,38 @@ def label_parity_record(cpu, Y, X, Z, device_index):
     return out
 
 
+DUMP_SAMPLE = 1 << 21          # elements kept of a larger output array
+DUMP_BUDGET = 64 << 20         # bytes written by --dump-outputs at most
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every output array as `path`/<name>.npy in float64 (integers are exact there).  An array of more than
+    DUMP_SAMPLE elements is represented by the elements at DUMP_SAMPLE flat indices drawn from np.random.default_rng(0) and
+    sorted: the same indices for the same size in every run, so two builds can be compared output for output."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        out[name] = a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BUDGET:
+        raise RuntimeError("bench.py: the outputs take %d bytes, more than --dump-outputs writes (%d)" % (total, DUMP_BUDGET))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def table_arrays(tables):
+    """The numeric arrays of a cell table (dict), as cells_<key>.  The neighbour pairs are a set whose order follows the
+    device's atomics from run to run: they are given sorted by row."""
+    out = {"cells_" + k: v for k, v in tables.items() if isinstance(v, np.ndarray) and v.dtype.kind in "biuf"}
+    pairs = out.get("cells_pairs")
+    if pairs is not None and pairs.ndim == 2 and len(pairs):
+        out["cells_pairs"] = pairs[np.lexsort(pairs.T[::-1])]
+    return out
+
+
 # ---- --gpus N without a launcher: this process starts the N ranks ------------------------------------------------------------
 def launch_ranks(args, argv):
     """Starts N = --gpus child processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT, as torchrun would)
@@ -383,6 +421,8 @@ def bench_movie(args, rank, local_rank, world, dist, torch):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:       # the movie's last frame: its cell table and its track ids
+        dump_outputs(args.dump_outputs, dict(table_arrays(tabs[-1]), track_ids=ids[-1]))
     if rank == 0:
         n_tracks = int(max(i.max() for i in ids))
         print(json.dumps({
@@ -421,6 +461,12 @@ def main():
     ap.add_argument("--inflight", type=int, default=4,
                     help="frames in flight per GPU: host threads, each with its own HIP stream and workspaces (the library "
                          "is re-entrant per thread, like the reference's Qt workers); frames are independent units")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: CPU baseline, secondary leg, per-kernel events and "
+                         "rooflines, PCIe-inclusive repeat, U-Net arithmetic modes, label parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64; "
+                         "at most 64 MB: arrays of more than %d elements as a fixed seeded sample)" % DUMP_SAMPLE)
     args = ap.parse_args()
     workload = "unet" if args.workload == "auto" else args.workload
     if args.steps is None:
@@ -445,10 +491,28 @@ def main():
 
     # CPU baseline first: its child processes are started before this process initialises the GPU
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and workload != "movie":
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and workload != "movie":
         cpu = cpu_baseline_record(Y, X, Z, workload)
         if workload == "unet" and not args.no_secondary:
             cpu["classical"] = cpu_baseline_record(Y, X, Z, "classical")
+
+    # the synthetic frames (two distinct frames per rank, alternated) are generated on a host thread while torch and the device
+    # come up: numpy's Poisson draws, most of the generator's time, release the GIL
+    import threading
+    made = {}
+    frames_thread = None
+    if workload != "movie":
+        from tissue_image_processing_amd import synthetic
+
+        def make_frames():
+            try:
+                s = synthetic.make_stack(Z, Y, X, seed=100 + rank)
+                made["frames"] = (s, np.ascontiguousarray(s[:, :, :, ::-1]))
+            except BaseException as e:
+                made["error"] = e
+
+        frames_thread = threading.Thread(target=make_frames, daemon=True)     # (daemon: a run that fails early does not wait)
+        frames_thread.start()
 
     # MIOpen's exhaustive find ran its naive reference convolutions for ~3 minutes per process (profiles/r02e_*): the fast
     # find mode picks the same implicit-GEMM solvers in seconds
@@ -487,12 +551,15 @@ def main():
     lib = _lib.lib()
     from tissue_image_processing_amd import prediction_local as plm
 
-    # synthetic frames, resident in HBM before the timed region (two distinct frames per rank, alternated)
-    import threading
-    st = synthetic.make_stack(Z, Y, X, seed=100 + rank)
-    st_flip = np.ascontiguousarray(st[:, :, :, ::-1])
-    host_frames = [torch.from_numpy(st).pin_memory(), torch.from_numpy(st_flip).pin_memory()]   # the PCIe leg uploads these
+    # synthetic frames, resident in HBM before the timed region
+    frames_thread.join()
+    if "error" in made:
+        raise made["error"]
+    st, st_flip = made.pop("frames")
+    with_pcie = args.full and not args.no_pcie_leg
+    host_frames = [torch.from_numpy(st).pin_memory(), torch.from_numpy(st_flip).pin_memory()] if with_pcie else None   # the PCIe leg uploads these
     steps_lock = threading.Lock()
+    dump_step = [None]       # index of the timed step whose outputs --dump-outputs keeps (None: outside the timed region)
 
     class Worker(object):
         """One frame in flight: own thread, own HIP stream / workspace pool (tip_init per thread), own torch stream for the
@@ -509,6 +576,8 @@ def main():
             self.unet_ms = []
             self.pcie = False
             self.diag = []           # U-Net leg: (watershed flags, markers) of every step since the last reset
+            self.kept = None         # --dump-outputs: the dump step's output tensors (U-Net) / True, until fetched
+            self.outputs = None
             self.thread = threading.Thread(target=self.run, daemon=True)
             self.thread.start()
             self.wait()  # wait for setup
@@ -540,9 +609,9 @@ def main():
                 pj = self.pipe._proj_t
                 padded, _ = self.predictor.prepare_image(torch.stack([pj[1].T, pj[0].T]))
                 self.predictor.model.calibrate_head(padded, 0.5)
-            # pinned landing buffers of the PCIe leg: the projection (C, Y, X) float64 and the label map int32
-            self.out_proj = torch.empty((C, Y, X), dtype=torch.float64).pin_memory()
-            self.out_lab = torch.empty((Y, X), dtype=torch.int32).pin_memory()
+            if with_pcie:        # pinned landing buffers of the PCIe leg: the projection (C, Y, X) float64 and the label map int32
+                self.out_proj = torch.empty((C, Y, X), dtype=torch.float64).pin_memory()
+                self.out_lab = torch.empty((Y, X), dtype=torch.int32).pin_memory()
             self.done.release()
             while True:
                 self.todo.acquire()
@@ -566,6 +635,9 @@ def main():
                     self.pcie = bool(arg)
                 elif kind == "diag":
                     self.diag = []
+                elif kind == "outputs":
+                    self.outputs = self.fetch_outputs() if self.kept is not None else None
+                    self.kept = None
                 elif kind == "prof":
                     if arg == "on":
                         _lib.prof_reset()
@@ -593,17 +665,37 @@ def main():
                 pipe.cell_tables()
                 lab_ptr = pipe.d_labels.ptr
             elif self.workload == "unet":
-                lab, _ = pipe.segment_unet(self.predictor)
+                lab, hc = pipe.segment_unet(self.predictor)
                 if getattr(self.predictor.model, "last_mode", None) != unet_mode:       # a silent fall-back to MIOpen must not be timed under this label
                     raise RuntimeError("the U-Net step ran in mode %r, the bench line says %r" % (getattr(self.predictor.model, "last_mode", None), unet_mode))
                 self.diag.append((int(self.predictor.last_flags), int(self.predictor.last_markers)))
                 pipe.cell_tables(labels_ptr=lab.data_ptr(), shape=(X, Y))
                 lab_ptr = lab.data_ptr()
+                if i == dump_step[0]:
+                    self.kept = (lab, hc)
+            elif i == dump_step[0]:
+                self.kept = True
             if self.pcie:        # what the drop-in functions hand back: the (C, Y, X) float64 projection and the int32 label map
                 _lib.check(lib.tip_memcpy_d2h(ctypes.c_void_p(self.out_proj.data_ptr()), _lib.dptr(pipe.d_proj.ptr),
                                               ctypes.c_size_t(C * Y * X * 8)))
                 if lab_ptr is not None:
                     _lib.check(lib.tip_memcpy_d2h(ctypes.c_void_p(self.out_lab.data_ptr()), _lib.dptr(lab_ptr), ctypes.c_size_t(Y * X * 4)))
+
+        def fetch_outputs(self):
+            """What a caller of the timed path receives from the kept step (its buffers are not written again before this
+            runs): the projection (C, Y, X) float64; the z-map (projection workload); the label map int32 and the cell tables
+            (classical); the label map int32 (X, Y), the HC map float64 and the cell tables (U-Net)."""
+            proj, zmap = self.pipe.fetch_projection()
+            out = {"projection": proj}
+            if self.workload == "projection":
+                out["zmap"] = zmap
+            elif self.workload == "classical":
+                out["labels"] = self.pipe.fetch_labels()
+            else:
+                out["labels"], out["hc"] = (t.cpu().numpy() for t in self.kept)
+            if self.workload != "projection":
+                out.update(table_arrays(self.pipe.tables))
+            return out
 
         def submit(self, job):
             self.jobs.append(job)
@@ -631,10 +723,10 @@ def main():
                 "serial_finish_pixels": int(sum(f >> _lib.WS_FLAG_COUNT_SHIFT for f in fl)),
                 "markers_min": int(min(m for _, m in d)), "markers_max": int(max(m for _, m in d))}
 
-    def run_leg(workload, nthreads, steps, warmup, pcie_steps):
-        """warmup untimed steps, then exactly `steps` timed steps between barriers; the same steps again with per-kernel
-        events; an isolated pass (ONE frame in flight) whose per-kernel HIP-event durations feed the roofline; and the
-        PCIe-inclusive repeat."""
+    def run_leg(workload, nthreads, steps, warmup, pcie_steps, full, dump=False):
+        """warmup untimed steps, then exactly `steps` timed steps between barriers (dump: the outputs of the last one are
+        fetched right after them); with `full`, the same steps again with per-kernel events, an isolated pass (ONE frame in
+        flight) whose per-kernel HIP-event durations feed the roofline, and the PCIe-inclusive repeat."""
         workers = [Worker(w, workload) for w in range(nthreads)]
 
         def run_steps(n, ws=workers):
@@ -652,7 +744,7 @@ def main():
 
         def progress(msg):          # (stderr: a long U-Net leg must not look hung to whoever watches the run)
             if rank == 0:
-                print("bench[%s]: %s" % (workload, msg), file=sys.stderr, flush=True)
+                print("bench[%s] %.1f s: %s" % (workload, time.perf_counter() - T_START, msg), file=sys.stderr, flush=True)
 
         diag = {}
         progress("warm-up (%d frames in flight)" % nthreads)
@@ -664,12 +756,28 @@ def main():
         # The timed region runs the product path as a caller would: no per-kernel events (two hipEventRecord per launch cost
         # the four-frame pipeline 3-5 % of its rate).  The same K steps are then repeated with the events on -- same threads,
         # same frames in flight -- for `roofline_timed_region`.
+        dump_step[0] = steps - 1 if dump else None
         t0 = time.perf_counter()
         run_steps(steps)
         barrier()
         elapsed = time.perf_counter() - t0
+        dump_step[0] = None
         diag["timed"] = diag_summary(workers)
         all_workers(("diag", None))
+        outputs = None
+        if dump:
+            all_workers(("outputs", None))
+            outputs = [w.outputs for w in workers if w.outputs is not None][0]
+        res = dict(workload=workload, elapsed=elapsed, nthreads=nthreads, steps=steps, warmup=warmup, diag=diag, outputs=outputs,
+                   full=full)
+        if not full:
+            progress("%.2f frames/s" % (steps / elapsed))
+            all_workers(None)
+            if use_dist:
+                t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                res["elapsed"] = float(t[0].item())
+            return res
         progress("%.2f frames/s; the same steps again with per-kernel events" % (steps / elapsed))
         all_workers(("prof", "on"))
         barrier()
@@ -709,9 +817,9 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t[0].item())
             pcie_elapsed = float(t[1].item()) if pcie_steps else None
-        return dict(workload=workload, elapsed=elapsed, elapsed_events=elapsed_events, timed=timed_reports, iso=iso_report,
-                    iso_steps=iso_steps, unet_ms=unet_ms, iso_unet_ms=iso_unet_ms, nthreads=nthreads, steps=steps, warmup=warmup,
-                    pcie_steps=pcie_steps, pcie_elapsed=pcie_elapsed, diag=diag)
+        res.update(elapsed=elapsed, elapsed_events=elapsed_events, timed=timed_reports, iso=iso_report, iso_steps=iso_steps,
+                   unet_ms=unet_ms, iso_unet_ms=iso_unet_ms, pcie_steps=pcie_steps, pcie_elapsed=pcie_elapsed)
+        return res
 
     def merge(reports):
         rep = {}
@@ -854,17 +962,20 @@ def main():
 
     pcie_steps = 0 if args.no_pcie_leg else None
     main_pcie = pcie_steps if pcie_steps is not None else (6 if workload == "unet" else 24)
-    leg = run_leg(workload, threads_for(workload, args.steps), args.steps, args.warmup, main_pcie)
+    leg = run_leg(workload, threads_for(workload, args.steps), args.steps, args.warmup, main_pcie, args.full,
+                  dump=bool(args.dump_outputs) and rank == 0)
     second = None
-    if not args.no_secondary and workload in ("unet", "classical"):
+    if args.full and not args.no_secondary and workload in ("unet", "classical"):
         wl2 = "classical" if workload == "unet" else "unet"
         st2 = args.secondary_steps or (64 if wl2 == "classical" else 9)
         second = run_leg(wl2, threads_for(wl2, st2), st2, 8 if wl2 == "classical" else 3,
-                         pcie_steps if pcie_steps is not None else (24 if wl2 == "classical" else 6))
+                         pcie_steps if pcie_steps is not None else (24 if wl2 == "classical" else 6), True)
     del st, st_flip
     unet_modes = None
-    if rank == 0 and workload == "unet" and unet_mode != "miopen" and os.environ.get("TIP_BENCH_NO_MODES") != "1":
+    if args.full and rank == 0 and workload == "unet" and unet_mode != "miopen" and os.environ.get("TIP_BENCH_NO_MODES") != "1":
         unet_modes = unet_modes_record()
+    if leg["outputs"] is not None:
+        dump_outputs(args.dump_outputs, leg["outputs"])
 
     def leg_object(lg):
         """Everything one leg measured, as a JSON object."""
@@ -873,7 +984,12 @@ def main():
         o = {"workload": "%dx%dx%d_c%d_u16:%s" % (Y, X, Z, C, wl_names[wl]), "value": world * lg["steps"] / el, "unit": "frames/s",
              "steps": lg["steps"], "warmup": lg["warmup"], "ms_per_step": 1e3 * el / lg["steps"],
              "dtype": "f64" if wl != "unet" else plm.unet_arithmetic()["dtype"], "frames_in_flight_per_gpu": lg["nthreads"],
-             "includes_h2d_upload": False, "kernels": kernel_table(lg["iso"], lg["iso_steps"])}
+             "includes_h2d_upload": False}
+        if not lg["full"]:
+            if wl == "unet":
+                o["watershed_diagnostics"] = lg["diag"]
+            return o
+        o["kernels"] = kernel_table(lg["iso"], lg["iso_steps"])
         if lg["pcie_elapsed"]:
             o["value_with_pcie"] = world * lg["pcie_steps"] / lg["pcie_elapsed"]
             o["with_pcie"] = {"value": o["value_with_pcie"], "unit": "frames/s", "steps": lg["pcie_steps"], "includes_h2d_upload": True,
@@ -941,10 +1057,11 @@ def main():
                                                               "concurrent (TISSUE_HIP_UNET_SERIAL=0)" if os.environ.get("TISSUE_HIP_UNET_SERIAL", "1") == "0"
                                                               else "one after the other on the device, other frames' projections / tails beside them"),
                        "parallelism": "frame-sharded dp%d, no data-path collective" % world},
-            "value_with_pcie": head.get("value_with_pcie"), "with_pcie": head.get("with_pcie"),
-            "roofline": head["roofline"], "roofline_timed_region": head["roofline_timed_region"], "roofline_valu": head["roofline_valu"],
-            "kernels": head["kernels"],
         }
+        if args.full:
+            out.update({"value_with_pcie": head.get("value_with_pcie"), "with_pcie": head.get("with_pcie"), "roofline": head["roofline"],
+                        "roofline_timed_region": head["roofline_timed_region"], "roofline_valu": head["roofline_valu"],
+                        "kernels": head["kernels"]})
         for k in ("roofline_library_kernel", "watershed_diagnostics"):
             if k in head:
                 out[k] = head[k]

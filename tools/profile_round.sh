@@ -13,24 +13,24 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 hb=$!
 trap "kill $hb 2>/dev/null" EXIT
 # classical leg, one frame in flight: per-kernel durations that must agree with bench.py's HIP-event figures
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/s1 -o s1 -- python3 bench.py --workload classical --inflight 1 --no-cpu-baseline --no-secondary-leg --no-pcie-leg > $out/${tag}_bench_classical_inflight1_profiled.json 2> $out/s1.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/s1 -o s1 -- python3 bench.py --full --workload classical --inflight 1 --no-cpu-baseline --no-secondary-leg --no-pcie-leg > $out/${tag}_bench_classical_inflight1_profiled.json 2> $out/s1.err || exit 1
 echo "stats classical inflight 1 done"
 # the default command (headline = U-Net leg, classical leg secondary), shortened
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/s3 -o s3 -- python3 bench.py --no-cpu-baseline --steps 6 --secondary-steps 32 > $out/${tag}_bench_default_profiled.json 2> $out/s3.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/s3 -o s3 -- python3 bench.py --full --no-cpu-baseline --steps 6 --secondary-steps 32 > $out/${tag}_bench_default_profiled.json 2> $out/s3.err || exit 1
 echo "stats default done"
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pf -o pf -- python3 bench.py --workload classical --steps 3 --warmup 1 --inflight 1 --no-cpu-baseline --no-secondary-leg --no-pcie-leg > $out/pf.json 2> $out/pf.err || exit 1
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pf -o pf -- python3 bench.py --full --workload classical --steps 3 --warmup 1 --inflight 1 --no-cpu-baseline --no-secondary-leg --no-pcie-leg > $out/pf.json 2> $out/pf.err || exit 1
 echo "pmc fetch done"
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pw -o pw -- python3 bench.py --workload classical --steps 3 --warmup 1 --inflight 1 --no-cpu-baseline --no-secondary-leg --no-pcie-leg > $out/pw.json 2> $out/pw.err || exit 1
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pw -o pw -- python3 bench.py --full --workload classical --steps 3 --warmup 1 --inflight 1 --no-cpu-baseline --no-secondary-leg --no-pcie-leg > $out/pw.json 2> $out/pw.err || exit 1
 echo "pmc write done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/su -o su -- python3 bench.py --workload unet --steps 6 --warmup 3 --no-cpu-baseline --no-secondary-leg > $out/${tag}_bench_unet_profiled.json 2> $out/su.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/su -o su -- python3 bench.py --full --workload unet --steps 6 --warmup 3 --no-cpu-baseline --no-secondary-leg > $out/${tag}_bench_unet_profiled.json 2> $out/su.err || exit 1
 echo "stats unet done"
-rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU --output-format csv -d $out/pm -o pm -- python3 bench.py --workload unet --steps 2 --warmup 1 --inflight 1 --no-cpu-baseline --no-secondary-leg --no-pcie-leg > $out/pm.json 2> $out/pm.err || exit 1
+rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU --output-format csv -d $out/pm -o pm -- python3 bench.py --full --workload unet --steps 2 --warmup 1 --inflight 1 --no-cpu-baseline --no-secondary-leg --no-pcie-leg > $out/pm.json 2> $out/pm.err || exit 1
 echo "pmc mfma done"
 # HBM traffic of the network's kernels (the headline's dominant kernel group): one forward pass per launch of tools/unet_layers.py
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/uf -o uf -- python3 tools/unet_layers.py 2048 > $out/uf.log 2> $out/uf.err || exit 1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/uw -o uw -- python3 tools/unet_layers.py 2048 > $out/uw.log 2> $out/uw.err || exit 1
 echo "pmc unet traffic done"
-rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU --output-format csv -d $out/ps -o ps -- python3 bench.py --workload projection --steps 3 --warmup 1 --inflight 1 --no-cpu-baseline --no-pcie-leg > $out/ps.json 2> $out/ps.err || exit 1
+rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU --output-format csv -d $out/ps -o ps -- python3 bench.py --full --workload projection --steps 3 --warmup 1 --inflight 1 --no-cpu-baseline --no-pcie-leg > $out/ps.json 2> $out/ps.err || exit 1
 echo "pmc mfma (score passes) done"
 cp $(find $out/s1 -name "*kernel_stats.csv" | head -1) $out/${tag}_kernel_stats_inflight1.csv
 cp $(find $out/s3 -name "*kernel_stats.csv" | head -1) $out/${tag}_kernel_stats_default.csv
