@@ -59,7 +59,7 @@ TIP_API int tip_sync(void);                       /* wait for this thread's stre
 /* Tuning and test hooks, process-wide.  The library reads the TIP_* environment variables ONCE (at first use) and   */
 /* never again; afterwards a hook changes only through this call.  value NULL or "" restores the default.           */
 /*   TIP_WS_TIES = exact | fast          tie policy of the watershed (default exact, see below)                      */
-/*   TIP_WS_TILE, TIP_WS_OPEN = a,b, TIP_WS_CERT_FROM, TIP_WS_NO_SKIP, TIP_WS_LDS_PAD   tile flavour / schedule       */
+/*   TIP_WS_OPEN = a,b, TIP_WS_NO_SKIP                                                 tile schedule                 */
 /*   TIP_WS_DEBUG, TIP_WS_NO_ENDGAME, TIP_WS_NO_WIDE                                   counters / stall machinery    */
 /*   TIP_PROJECT_EXACT_SCORE, TIP_PROJECT_GENERIC, TIP_PROJECT_UNFUSED_PREBLUR, TIP_PROJECT_UNFUSED_MASK,            */
 /*   TIP_PROJECT_DEBUG, TIP_FAST_CFG = y,x, TIP_MFMA_BLOCKS_PER_CU                     projection kernel selection   */

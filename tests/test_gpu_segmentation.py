@@ -348,23 +348,24 @@ def test_watershed_vs_oracle_synthetic_frame(env):
     assert mism == 0
 
 
-def test_watershed_tile_flavours_and_openings_agree(env):
-    """The tile kernel's selectable flavours (TIP_WS_TILE: interior-only / evaluated margins, event-driven list or not, 8-,
-    16-, 32-pixel tiles) and openings (TIP_WS_OPEN) only change the schedule of certified decisions: every one of them gives
-    the oracle's labels."""
+def test_watershed_tile_openings_agree(env):
+    """The openings of the tile schedule (TIP_WS_OPEN: tile launches before / after the early endgame) and the re-run of
+    stuck tiles (TIP_WS_NO_SKIP) only change the schedule of certified decisions: every one of them gives the oracle's
+    labels.  The tile-flavour hooks of the sweep that chose the shipped kernel are gone."""
     bim, _, _, orc = env
     from tissue_image_processing_amd import synthetic, _segmentation as seg, _lib
     from tissue_image_processing_amd import surface_projection as sp
     st = synthetic.make_stack(8, 300, 340, seed=35)
     proj = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False)
     ref = orc.watershed_segmentation(proj[0], 0.03, 3, 3)
-    for variant, opening in (("0", "10,8"), ("4", "6,6"), ("5", "8,6"), ("6", "6,6"), ("9", "3,2"), ("12", "12,9"), ("14", "1,1"),
-                             ("15", "8,6")):
-        with _lib.tuning(TIP_WS_TILE=variant, TIP_WS_OPEN=opening):
+    for opening in ("10,8", "6,6", "8,6", "3,2", "12,9", "1,1"):
+        with _lib.tuning(TIP_WS_OPEN=opening):
             out = seg.watershed_segmentation(proj[0], 0.03, 3, 3)
-        assert int((out != ref).sum()) == 0, (variant, opening)
+        assert int((out != ref).sum()) == 0, opening
     with _lib.tuning(TIP_WS_NO_SKIP="1"):                     # stuck tiles re-run on every wake-up
         assert int((seg.watershed_segmentation(proj[0], 0.03, 3, 3) != ref).sum()) == 0
+    with pytest.raises(ValueError):
+        _lib.set_tuning("TIP_WS_TILE", "0")
 
 
 def test_headline_frame_segmentation_and_tables_bit_exact(env):

@@ -156,11 +156,8 @@ bool tuning_assign(Tuning &t, const char *name, const char *value)
         if (unset) t.ws_ties = def.ws_ties;
         else t.ws_ties = (!strcmp(value, "fast") || !strcmp(value, "0")) ? 0 : 1;
     }
-    else if (n == "TIP_WS_TILE") num(t.ws_tile, def.ws_tile);
     else if (n == "TIP_WS_OPEN") pair(t.ws_open_a, t.ws_open_b, def.ws_open_a, def.ws_open_b);
-    else if (n == "TIP_WS_CERT_FROM") num(t.ws_cert_from, def.ws_cert_from);
     else if (n == "TIP_WS_NO_SKIP") flag(t.ws_no_skip, 0);
-    else if (n == "TIP_WS_LDS_PAD") num(t.ws_lds_pad, 0);
     else if (n == "TIP_WS_DEBUG") flag(t.ws_debug, 0);
     else if (n == "TIP_WS_NO_ENDGAME") flag(t.ws_no_endgame, 0);
     else if (n == "TIP_WS_NO_WIDE") flag(t.ws_no_wide, 0);
@@ -182,8 +179,8 @@ bool tuning_assign(Tuning &t, const char *name, const char *value)
     return true;
 }
 
-const char *const TUNING_NAMES[] = {"TIP_WS_TIES", "TIP_WS_TILE", "TIP_WS_OPEN", "TIP_WS_CERT_FROM", "TIP_WS_NO_SKIP", "TIP_WS_LDS_PAD",
-                                    "TIP_WS_DEBUG", "TIP_WS_NO_ENDGAME", "TIP_WS_NO_WIDE", "TIP_MFMA_BLOCKS_PER_CU", "TIP_PROJECT_GENERIC",
+const char *const TUNING_NAMES[] = {"TIP_WS_TIES", "TIP_WS_OPEN", "TIP_WS_NO_SKIP", "TIP_WS_DEBUG", "TIP_WS_NO_ENDGAME", "TIP_WS_NO_WIDE",
+                                    "TIP_MFMA_BLOCKS_PER_CU", "TIP_PROJECT_GENERIC",
                                     "TIP_PROJECT_UNFUSED_PREBLUR", "TIP_PROJECT_UNFUSED_MASK", "TIP_PROJECT_EXACT_SCORE", "TIP_PROJECT_DEBUG",
                                     "TIP_FAST_CFG", "TIP_UNET_TILE8", "TIP_UNET_TAIL_UNFUSED", "TIP_UNET_XCD_MAP", "TIP_UNET_SPB", "TIP_UF_ONE_LEVEL", "TIP_MB_SMALL", "TIP_MB_BATCH"};
 

@@ -56,11 +56,8 @@ void prof_end();
 // changed afterwards only through tip_set_tuning(): entry points read plain ints, never the environment.
 struct Tuning {
     int ws_ties = 1;            // TIP_WS_TIES: 1 = exact (serial (value, age) replay on tie landscapes), 0 = fast (device order)
-    int ws_tile = -1;           // TIP_WS_TILE: everyday tile flavour (-1: the built-in default)
     int ws_open_a = -1, ws_open_b = -1;   // TIP_WS_OPEN=a,b
-    int ws_cert_from = -1;      // TIP_WS_CERT_FROM
     int ws_no_skip = 0;         // TIP_WS_NO_SKIP
-    int ws_lds_pad = 0;         // TIP_WS_LDS_PAD
     int ws_debug = 0;           // TIP_WS_DEBUG
     int ws_no_endgame = 0, ws_no_wide = 0;   // TIP_WS_NO_ENDGAME / TIP_WS_NO_WIDE (exercise the stall machinery)
     int mfma_blocks_per_cu = 2; // TIP_MFMA_BLOCKS_PER_CU
