@@ -62,7 +62,7 @@ TIP_API int tip_sync(void);                       /* wait for this thread's stre
 /*   TIP_WS_OPEN = a,b, TIP_WS_NO_SKIP                                                 tile schedule                 */
 /*   TIP_WS_DEBUG, TIP_WS_NO_ENDGAME, TIP_WS_NO_WIDE                                   counters / stall machinery    */
 /*   TIP_PROJECT_EXACT_SCORE, TIP_PROJECT_GENERIC, TIP_PROJECT_UNFUSED_PREBLUR, TIP_PROJECT_UNFUSED_MASK,            */
-/*   TIP_PROJECT_DEBUG, TIP_FAST_CFG = y,x, TIP_MFMA_BLOCKS_PER_CU                     projection kernel selection   */
+/*   TIP_PROJECT_DEBUG                                                                 projection kernel selection   */
 /*   TIP_UNET_TILE8 = -1|0|1, TIP_UNET_SPB = 1|2|3, TIP_UNET_XCD_MAP = 0|1             U-Net convolution schedule    */
 /*   TIP_UNET_TAIL_UNFUSED                                                            tail morphology as separate launches */
 /*   TIP_MB_SMALL = pixels, TIP_MB_BATCH = generations                                 two-valued flood: one-workgroup  */

@@ -61,3 +61,38 @@ def test_host_axis_logic():
     assert out.shape == (2, 3, 7, 5) and order == (1, 0, 3, 2)     # reference order is C,(Z),X,Y (bim.py:219-226)
     out, order = put_channel_axis_first(a, "CZYX")                 # C already first: untouched (bim.py:216 `> 0`)
     assert out is a and tuple(order) == (0, 1, 2, 3)
+
+
+PROJECTION_HOOKS = ("TIP_PROJECT_EXACT_SCORE", "TIP_PROJECT_GENERIC", "TIP_PROJECT_UNFUSED_PREBLUR", "TIP_PROJECT_UNFUSED_MASK",
+                    "TIP_PROJECT_DEBUG")
+
+
+def test_retired_score_pass_hooks_are_unknown():
+    """The float32 / VALU score-pass flavours are gone, and with them their hooks (tip_set_tuning touches no device)."""
+    from tissue_image_processing_amd import _lib
+    with pytest.raises(ValueError):
+        _lib.set_tuning("TIP_FAST_CFG", "5,5")
+    with pytest.raises(ValueError):
+        _lib.set_tuning("TIP_MFMA_BLOCKS_PER_CU", "1")
+
+
+@pytest.mark.parametrize("name", PROJECTION_HOOKS)
+def test_projection_hooks_are_accepted(name):
+    from tissue_image_processing_amd import _lib
+    try:
+        _lib.set_tuning(name, "1")
+    finally:
+        _lib.set_tuning(name, None)
+
+
+def test_tests_switch_hooks_through_the_library():
+    """The library reads the TIP_* environment once per process: a hook set in the environment after the first call never
+    reaches it, and the test would compare the default path with itself.  Tests switch hooks with _lib.tuning."""
+    pat = re.compile(r"""(setenv|setdefault)\(\s*["']TIP_|os\.environ\[\s*["']TIP_\w*["']\s*\]\s*=(?!=)""")
+    tests = os.path.join(ROOT, "tests")
+    hits = []
+    for f in sorted(os.listdir(tests)):
+        if f.endswith(".py"):
+            with open(os.path.join(tests, f)) as fh:
+                hits += ["%s:%d: %s" % (f, i, line.strip()) for i, line in enumerate(fh, 1) if pat.search(line)]
+    assert not hits, "hooks switched through the environment:\n" + "\n".join(hits)

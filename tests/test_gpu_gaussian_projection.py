@@ -171,23 +171,22 @@ def test_projection_errors(mods):
         sp.time_point_surface_projection(st2, "CZYX", 0, airyscan=False, atoh_shift=1)
 
 
-def test_projection_full_size_properties(mods, monkeypatch):
+def test_projection_full_size_properties(mods):
     """At BASELINE full size (2048x2048x30, C=2), size-independent properties (the bit-for-bit comparison with the
     oracle at this size is test_projection_headline_frame_vs_oracle): z-map range, projection >= 0, bounded by the
     per-pixel z-max of the stack, certified == all-exact argmax, and invariance of the z-map under a global intensity
     scaling of the non-reference channel."""
     _, sp, _ = mods
-    from tissue_image_processing_amd import synthetic
+    from tissue_image_processing_amd import _lib, synthetic
     st = synthetic.make_stack(30, 2048, 2048, seed=1)
     proj, zmap = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True)
     assert proj.shape == (2, 2048, 2048) and zmap.shape == (2048, 2048)
     assert zmap.min() >= 0 and zmap.max() < 30
     assert (proj >= 0).all()
     assert (proj <= st.max(axis=1).astype(np.float64) + 1e-9).all()
-    # certified (fast float32 score + exact fix-up) argmax == the all-exact float64 score path, at full size
-    monkeypatch.setenv("TIP_PROJECT_EXACT_SCORE", "1")
-    proj_e, zmap_e = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True)
-    monkeypatch.delenv("TIP_PROJECT_EXACT_SCORE")
+    # certified (fp16 score tiles + exact fix-up) argmax == the all-exact float64 score path, at full size
+    with _lib.tuning(TIP_PROJECT_EXACT_SCORE="1"):
+        proj_e, zmap_e = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True)
     assert int((zmap != zmap_e).sum()) == 0
     np.testing.assert_array_equal(proj, proj_e)
     st2 = st.copy()
@@ -197,28 +196,26 @@ def test_projection_full_size_properties(mods, monkeypatch):
     np.testing.assert_array_equal(proj[0], proj2[0])
 
 
-def test_projection_fast_path_equals_generic_path(mods, monkeypatch):
+def test_projection_fast_path_equals_generic_path(mods):
     """Register-sliding / sparse-mask kernels are the same arithmetic as the generic kernels: bit-identical output."""
     _, sp, _ = mods
-    from tissue_image_processing_amd import synthetic
+    from tissue_image_processing_amd import _lib, synthetic
     for shape, seed in [((9, 200, 264), 1), ((5, 77, 136), 2), ((30, 128, 512), 3)]:
         st = synthetic.make_stack(*shape, seed=seed)
         st[1, :, :10, :] = 0
-        monkeypatch.delenv("TIP_PROJECT_GENERIC", raising=False)
         p_fast, z_fast = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True, atoh_shift=-1)
-        monkeypatch.setenv("TIP_PROJECT_GENERIC", "1")
-        p_gen, z_gen = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True, atoh_shift=-1)
-        monkeypatch.delenv("TIP_PROJECT_GENERIC", raising=False)
+        with _lib.tuning(TIP_PROJECT_GENERIC="1"):
+            p_gen, z_gen = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True, atoh_shift=-1)
         np.testing.assert_array_equal(z_fast, z_gen)
         np.testing.assert_array_equal(p_fast, p_gen)
 
 
-def test_fused_mask_kernel_equals_separate_kernels(mods, monkeypatch):
+def test_fused_mask_kernel_equals_separate_kernels(mods):
     """k_mask_wmax_fused (y pass + x pass of the blurred one-hot mask + weighted z-max in one kernel, the mask volume never
     written) against the separate sparse kernels: bit-identical, with airyscan offset, three channels, a shifted second
     mask, frames that are not multiples of the tile and a rough z-map (random planes: wide z ranges per tile)."""
     _, sp, _ = mods
-    from tissue_image_processing_amd import synthetic
+    from tissue_image_processing_amd import _lib, synthetic
     rng = np.random.default_rng(4)
     cases = [(synthetic.make_stack(9, 200, 264, seed=1), dict(airyscan=False, atoh_shift=-1)),
              (synthetic.make_stack(12, 77, 136, seed=2, channels=3, offset=10000), dict(airyscan=True, atoh_shift=0)),
@@ -226,23 +223,20 @@ def test_fused_mask_kernel_equals_separate_kernels(mods, monkeypatch):
              (rng.integers(0, 4000, (2, 16, 90, 300)).astype(np.uint16), dict(airyscan=False, atoh_shift=0))]
     for st, kw in cases:
         try:
-            monkeypatch.delenv("TIP_PROJECT_UNFUSED_MASK", raising=False)
             p_f, z_f = sp.time_point_surface_projection(st, "CZYX", 0, z_map=True, **kw)
-            monkeypatch.setenv("TIP_PROJECT_UNFUSED_MASK", "1")
-            p_s, z_s = sp.time_point_surface_projection(st, "CZYX", 0, z_map=True, **kw)
+            with _lib.tuning(TIP_PROJECT_UNFUSED_MASK="1"):
+                p_s, z_s = sp.time_point_surface_projection(st, "CZYX", 0, z_map=True, **kw)
         except IndexError:
             continue      # (a shifted plane fell off the stack: the reference's IndexError, both paths)
-        finally:
-            monkeypatch.delenv("TIP_PROJECT_UNFUSED_MASK", raising=False)
         np.testing.assert_array_equal(z_f, z_s)
         np.testing.assert_array_equal(p_f, p_s)
 
 
-def test_fused_preblur_kernel_equals_separate_kernels(mods, monkeypatch):
+def test_fused_preblur_kernel_equals_separate_kernels(mods):
     """k_preblur_fused (uint16 -> z 0.5 -> y 1 -> x 1 -> z 0.5 in one kernel) against the four separate register-sliding
     kernels: identical z-maps and projections, incl. few planes (Z = 1, 2, 3), ragged frames, the airyscan offset."""
     _, sp, _ = mods
-    from tissue_image_processing_amd import synthetic
+    from tissue_image_processing_amd import _lib, synthetic
     rng = np.random.default_rng(6)
     cases = [(synthetic.make_stack(9, 200, 264, seed=1), dict(airyscan=False)),
              (synthetic.make_stack(12, 77, 136, seed=2, channels=3, offset=10000), dict(airyscan=True)),
@@ -252,20 +246,18 @@ def test_fused_preblur_kernel_equals_separate_kernels(mods, monkeypatch):
              (rng.integers(0, 4000, (1, 3, 64, 128)).astype(np.uint16), dict(airyscan=False)),
              (rng.integers(0, 60000, (2, 5, 31, 12)).astype(np.uint16), dict(airyscan=True))]
     for st, kw in cases:
-        monkeypatch.delenv("TIP_PROJECT_UNFUSED_PREBLUR", raising=False)
         p_f, z_f = sp.time_point_surface_projection(st, "CZYX", 0, z_map=True, **kw)
-        monkeypatch.setenv("TIP_PROJECT_UNFUSED_PREBLUR", "1")
-        p_s, z_s = sp.time_point_surface_projection(st, "CZYX", 0, z_map=True, **kw)
-        monkeypatch.delenv("TIP_PROJECT_UNFUSED_PREBLUR", raising=False)
+        with _lib.tuning(TIP_PROJECT_UNFUSED_PREBLUR="1"):
+            p_s, z_s = sp.time_point_surface_projection(st, "CZYX", 0, z_map=True, **kw)
         np.testing.assert_array_equal(z_f, z_s)
         np.testing.assert_array_equal(p_f, p_s)
 
 
-def test_certified_argmax_equals_exact_score_path(mods, monkeypatch):
-    """The fast float32 score passes + certification + exact fix-up give the same z-map as the exact float64 passes,
+def test_certified_argmax_equals_exact_score_path(mods):
+    """The fp16 score passes + certification + exact fix-up give the same z-map as the exact float64 passes,
     including on data built to make neighbouring planes nearly tie."""
     _, sp, _ = mods
-    from tissue_image_processing_amd import synthetic
+    from tissue_image_processing_amd import _lib, synthetic
     rng = np.random.default_rng(9)
     cases = [synthetic.make_stack(12, 300, 328, seed=11), synthetic.make_stack(30, 256, 256, seed=12)]
     tie = np.zeros((2, 6, 160, 200), np.uint16)            # identical planes -> exact ties everywhere
@@ -273,11 +265,9 @@ def test_certified_argmax_equals_exact_score_path(mods, monkeypatch):
     tie[0, 3, 80:, :] += 1                                  # and a one-count edge on plane 3
     cases.append(tie)
     for st in cases:
-        monkeypatch.delenv("TIP_PROJECT_EXACT_SCORE", raising=False)
         p_c, z_c = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True)
-        monkeypatch.setenv("TIP_PROJECT_EXACT_SCORE", "1")
-        p_e, z_e = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True)
-        monkeypatch.delenv("TIP_PROJECT_EXACT_SCORE", raising=False)
+        with _lib.tuning(TIP_PROJECT_EXACT_SCORE="1"):
+            p_e, z_e = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True)
         assert int((z_c != z_e).sum()) == 0
         np.testing.assert_array_equal(p_c, p_e)
 
@@ -311,26 +301,18 @@ def test_projection_headline_frame_vs_oracle(mods):
     np.testing.assert_array_equal(proj, rproj)
 
 
-def test_every_fast_pass_variant_gives_the_same_zmap(mods, monkeypatch):
-    """The approximate sigma-30 score comes from the matrix-core kernels by default (k_corr_long_mfma for y,
-    k_corr_long_mfma2 for x); the tuning hook selects the other variants (both MFMA kernels on both axes, the packed and
-    the scalar VALU kernels).  Certification makes the z-map independent of which variant produced the score: all equal
-    the all-exact float64 path, on a frame whose extents are not multiples of the tiles (ragged edge tiles, more tiles
-    than persistent blocks)."""
+def test_score_pass_zmap_equals_exact_path_ragged(mods):
+    """The certified z-map (fp16 score tiles + certification + exact fix-up) equals the all-exact float64 path's on frames
+    whose extents are not multiples of the tiles (ragged edge tiles in both passes)."""
     _, sp, _ = mods
-    from tissue_image_processing_amd import synthetic
+    from tissue_image_processing_amd import _lib, synthetic
     for shape, seed in [((12, 515, 777), 77), ((30, 1100, 1300), 78)]:
         st = synthetic.make_stack(*shape, seed=seed)
-        monkeypatch.setenv("TIP_PROJECT_EXACT_SCORE", "1")
-        proj_e, zmap_e = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True)
-        monkeypatch.delenv("TIP_PROJECT_EXACT_SCORE")
-        for cfg in (None, "5,5", "3,4", "3,3", "4,4", "4,3", "5,4", "11616,11616", "1616,1616"):      # (5: the fp16 tiles, the default)
-            if cfg:
-                monkeypatch.setenv("TIP_FAST_CFG", cfg)
-            proj, zmap = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True)
-            monkeypatch.delenv("TIP_FAST_CFG", raising=False)
-            assert int((zmap != zmap_e).sum()) == 0, cfg
-            np.testing.assert_array_equal(proj, proj_e)
+        with _lib.tuning(TIP_PROJECT_EXACT_SCORE="1"):
+            proj_e, zmap_e = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True)
+        proj, zmap = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=False, z_map=True)
+        assert int((zmap != zmap_e).sum()) == 0
+        np.testing.assert_array_equal(proj, proj_e)
 
 
 def _gauss30():
@@ -440,11 +422,12 @@ def test_f16_score_pass_error_bound(axis):
     assert flag.value & 8
 
 
-def test_black_background_zmap_is_exact(mods, monkeypatch):
+def test_black_background_zmap_is_exact(mods):
     """airyscan=True subtracts 10000 and clamps: large exactly-zero regions with blurred fringes of every magnitude around the signal.
     The fp16 score tiles keep the certification meaningful there (relative accuracy down to 2^-36 of the clip value, zero scores only
     from zero inputs): the z-map equals the all-exact path's."""
     _, sp, _ = mods
+    from tissue_image_processing_amd import _lib
     rng = np.random.default_rng(12)
     Z, Y, X = 9, 600, 700
     st = np.full((2, Z, Y, X), 9000, np.uint16)                  # below the airyscan offset: zero after the subtraction
@@ -453,9 +436,8 @@ def test_black_background_zmap_is_exact(mods, monkeypatch):
         st[:, z, y:y + 12, x:x + 12] = 10000 + rng.integers(50, 4000, (2, 12, 12))
         if z + 1 < Z:
             st[:, z + 1, y:y + 12, x:x + 12] = 10000 + rng.integers(50, 4000, (2, 12, 12))
-    monkeypatch.setenv("TIP_PROJECT_EXACT_SCORE", "1")
-    proj_e, zmap_e = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=True, z_map=True)
-    monkeypatch.delenv("TIP_PROJECT_EXACT_SCORE")
+    with _lib.tuning(TIP_PROJECT_EXACT_SCORE="1"):
+        proj_e, zmap_e = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=True, z_map=True)
     proj, zmap = sp.time_point_surface_projection(st[None], "TCZYX", 0, airyscan=True, z_map=True)
     assert int((zmap != zmap_e).sum()) == 0
     np.testing.assert_array_equal(proj, proj_e)

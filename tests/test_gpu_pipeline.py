@@ -84,7 +84,6 @@ def test_config5_frame_4096x4096x60():
     """BASELINE config 5's frame size on one GPU (the frame and its workspaces fit HBM many times over): certified z-map ==
     exact-score z-map at full size, projection and labels of a crop-sized sub-problem against the oracle, and
     size-independent properties of the full-size outputs (label map vs its own cell tables)."""
-    import os
     from oracle import oracle as orc
     from tissue_image_processing_amd import synthetic, _lib
     from tissue_image_processing_amd.pipeline import FramePipeline
@@ -98,12 +97,9 @@ def test_config5_frame_4096x4096x60():
     d = pipe.upload_stack(st)
     pipe.project(d)
     proj, zmap = pipe.fetch_projection()
-    os.environ["TIP_PROJECT_EXACT_SCORE"] = "1"
-    try:
+    with _lib.tuning(TIP_PROJECT_EXACT_SCORE="1"):
         pipe.project(d)
         proj_x, zmap_x = pipe.fetch_projection()
-    finally:
-        del os.environ["TIP_PROJECT_EXACT_SCORE"]
     assert int((zmap != zmap_x).sum()) == 0
     np.testing.assert_array_equal(proj, proj_x)
     assert zmap.min() >= 0 and zmap.max() < Z

@@ -161,13 +161,11 @@ bool tuning_assign(Tuning &t, const char *name, const char *value)
     else if (n == "TIP_WS_DEBUG") flag(t.ws_debug, 0);
     else if (n == "TIP_WS_NO_ENDGAME") flag(t.ws_no_endgame, 0);
     else if (n == "TIP_WS_NO_WIDE") flag(t.ws_no_wide, 0);
-    else if (n == "TIP_MFMA_BLOCKS_PER_CU") { num(t.mfma_blocks_per_cu, def.mfma_blocks_per_cu); t.mfma_blocks_per_cu = std::max(1, std::min(2, t.mfma_blocks_per_cu)); }
     else if (n == "TIP_PROJECT_GENERIC") flag(t.project_generic, 0);
     else if (n == "TIP_PROJECT_UNFUSED_PREBLUR") flag(t.project_unfused_preblur, 0);
     else if (n == "TIP_PROJECT_UNFUSED_MASK") flag(t.project_unfused_mask, 0);
     else if (n == "TIP_PROJECT_EXACT_SCORE") flag(t.project_exact_score, 0);
     else if (n == "TIP_PROJECT_DEBUG") flag(t.project_debug, 0);
-    else if (n == "TIP_FAST_CFG") pair(t.fast_cfg_y, t.fast_cfg_x, def.fast_cfg_y, def.fast_cfg_x);
     else if (n == "TIP_UNET_TILE8") num(t.unet_tile8, def.unet_tile8);
     else if (n == "TIP_UF_ONE_LEVEL") flag(t.uf_one_level, 0);
     else if (n == "TIP_UNET_SPB") num(t.unet_spb, def.unet_spb);
@@ -180,9 +178,8 @@ bool tuning_assign(Tuning &t, const char *name, const char *value)
 }
 
 const char *const TUNING_NAMES[] = {"TIP_WS_TIES", "TIP_WS_OPEN", "TIP_WS_NO_SKIP", "TIP_WS_DEBUG", "TIP_WS_NO_ENDGAME", "TIP_WS_NO_WIDE",
-                                    "TIP_MFMA_BLOCKS_PER_CU", "TIP_PROJECT_GENERIC",
-                                    "TIP_PROJECT_UNFUSED_PREBLUR", "TIP_PROJECT_UNFUSED_MASK", "TIP_PROJECT_EXACT_SCORE", "TIP_PROJECT_DEBUG",
-                                    "TIP_FAST_CFG", "TIP_UNET_TILE8", "TIP_UNET_TAIL_UNFUSED", "TIP_UNET_XCD_MAP", "TIP_UNET_SPB", "TIP_UF_ONE_LEVEL", "TIP_MB_SMALL", "TIP_MB_BATCH"};
+                                    "TIP_PROJECT_GENERIC", "TIP_PROJECT_UNFUSED_PREBLUR", "TIP_PROJECT_UNFUSED_MASK",
+                                    "TIP_PROJECT_EXACT_SCORE", "TIP_PROJECT_DEBUG", "TIP_UNET_TILE8", "TIP_UNET_TAIL_UNFUSED", "TIP_UNET_XCD_MAP", "TIP_UNET_SPB", "TIP_UF_ONE_LEVEL", "TIP_MB_SMALL", "TIP_MB_BATCH"};
 
 void tuning_from_env()
 {

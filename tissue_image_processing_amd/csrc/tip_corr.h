@@ -154,173 +154,4 @@ __global__ void __launch_bounds__(256) k_corr_long_f32(const float *__restrict__
     }
 }
 
-// ---- fast (NOT bit-exact) long pass for the certified argmax: float32 math, FMA allowed -----------------------------------
-// Same tiling as k_corr_long_f32; every lane slides R = 2H outputs.
-//   VAR 1 (default): outputs j and j+H share one register pair,
-//       acc[j] = pk_fma(L[j] + Rr[j], {w, w}, acc[j]),   L[j] = {x[j-d], x[j+H-d]},  Rr[j] = {x[j+d], x[j+H+d]}
-//     = one v_pk_add_f32 + one v_pk_fma_f32 per TWO outputs and tap.  Pairing outputs H apart (not neighbours) makes the
-//     window slide a pure renaming of whole pairs (L[j] <- L[j+1]); the one new pair per side and tap is read from LDS
-//     through a volatile pointer -- otherwise the compiler notices that half of it is already in a register and assembles
-//     the pair with v_mov, which costs as much as the arithmetic it saves.  Needs radius % H == 0.
-//   VAR 0: scalar v_add_f32 + v_fmac_f32 per output and tap (any radius).  VOP2 float32 on VGPR operands issues about
-//     twice as fast as the packed instructions (tools/ubench/valu_rate.hip: 109 vs 104 TFLOP/s for this add+fma mix), so
-//     the two variants run within a few percent of each other.
-// Error vs the exact pass: every term is non-negative.  The taps are summed in partial sums of at most FAST_SEG taps
-// that are flushed into a running total, so a term sees at most FAST_SEG + 1 FMA roundings (its partial sum, the centre
-// term included), one tap rounding, one pair-sum rounding and at most ceil(r / 8) + 1 roundings of the running total:
-//     |fast - exact| <= ((1+u)^(FAST_SEG + 3 + ceil(r/8) + 1) - 1) * exact,   u = 2^-24
-// i.e. 35 u for r = 120 and 36 u at the largest radius (a single running sum would be 123 u); see k_argmax_certify for
-// how the bound is used.
-constexpr int FAST_SEG = 16;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-template <int AXIS, int TO, int NW, int R, int VAR, int REM = 0>
-__global__ void __launch_bounds__(NW * 64) k_corr_long_fast(const float *__restrict__ in, float *__restrict__ out, int Z, int Y, int X,
-                                                        TapsF taps)
-{
-    extern __shared__ __attribute__((aligned(16))) float tile[];
-    constexpr int LS = AXIS == 1 ? 64 : 65;
-    const int r = taps.n >> 1;
-    const int npos = TO + 2 * r;
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int z = blockIdx.z;
-    const int len = AXIS == 1 ? Y : X;
-    const int nlines = AXIS == 1 ? X : Y;
-    const int p0 = blockIdx.y * TO;
-    const int l0 = blockIdx.x * 64;
-    const float *src = in + (long)z * Y * X;
-    float *dst = out + (long)z * Y * X;
-    // taps live in LDS: scalar loads in the tap loop would share lgkmcnt with the window reads and force a full
-    // drain (s_waitcnt lgkmcnt(0)) at every use; LDS broadcasts return in order and pipeline with them
-    __shared__ __attribute__((aligned(16))) float wl[256];
-    for (int i = threadIdx.x; i < 256; i += NW * 64) wl[i] = taps.w[i];
-    stage_tile<AXIS, NW>(tile, src, npos, p0 - r, l0, Y, X, lane, wave);
-    __syncthreads();
-    const int line = l0 + lane;
-    constexpr int PER_WAVE = TO / NW;
-    static_assert(PER_WAVE % R == 0, "outputs per wave must be a multiple of the group size");
-    constexpr bool STAGED = AXIS == 2 && PER_WAVE == R;  // x pass: results go back through LDS for coalesced row stores
-    for (int g = 0; g < PER_WAVE / R; ++g) {
-        const int o0 = wave * PER_WAVE + g * R;
-        const bool active = p0 + o0 < len;  // wave-uniform
-        if (!STAGED && !active) break;
-        const float *ctr = tile + (r + o0) * LS + lane;
-        typedef __attribute__((address_space(3))) const volatile float *lds_cvf32;   // (a plain volatile pointer decays to flat loads)
-        constexpr int H = R / 2;
-        float res[R];
-        if (active) {
-            const float wc = wl[r];
-            if constexpr (VAR == 0) {   // scalar: one v_add_f32 + one v_fmac_f32 per output and tap
-                float acc[R], L[R], Rr[R];
-#pragma unroll
-                for (int i = 0; i < R; ++i) {
-                    acc[i] = ctr[i * LS] * wc;
-                    L[i] = ctr[(i - r) * LS];
-                    Rr[i] = ctr[(i + r) * LS];
-                }
-                float tot[R];
-#pragma unroll
-                for (int i = 0; i < R; ++i) tot[i] = 0.f;
-                int seg = 0;
-#pragma unroll R
-                for (int d = r; d >= 1; --d) {
-                    const float w = wl[r - d];
-#pragma unroll
-                    for (int i = 0; i < R; ++i) acc[i] = __builtin_fmaf(L[i] + Rr[i], w, acc[i]);
-#pragma unroll
-                    for (int i = 0; i < R - 1; ++i) L[i] = L[i + 1];
-                    L[R - 1] = ctr[(R - d) * LS];
-#pragma unroll
-                    for (int i = R - 1; i > 0; --i) Rr[i] = Rr[i - 1];
-                    Rr[0] = ctr[(d - 1) * LS];
-                    if (++seg == FAST_SEG) {   // short partial sums: see the error bound above k_argmax_certify
-                        seg = 0;
-#pragma unroll
-                        for (int i = 0; i < R; ++i) { tot[i] += acc[i]; acc[i] = 0.f; }
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < R; ++i) res[i] = tot[i] + acc[i];
-            } else {
-                static_assert(H <= FAST_SEG, "partial sums must stay within the certified bound");
-                f32x2 acc[H], L[H], Rr[H], tot[H];
-#pragma unroll
-                for (int j = 0; j < H; ++j) {
-                    tot[j] = f32x2{0.f, 0.f};
-                    acc[j] = f32x2{ctr[j * LS], ctr[(j + H) * LS]} * wc;
-                    L[j] = f32x2{ctr[(j - r) * LS], ctr[(j + H - r) * LS]};
-                    Rr[j] = f32x2{ctr[(j + r) * LS], ctr[(j + H + r) * LS]};
-                }
-                // H taps per trip, written as a constant-trip inner loop (the radius must be a multiple of H: checked by
-                // the launcher) so that it is fully unrolled and the window rotation is pure renaming
-                for (int db = r; db >= H; db -= H) {
-#pragma unroll
-                    for (int kk = 0; kk < H; ++kk) {
-                        const int d = db - kk;
-                        const float w = wl[r - d];
-#pragma unroll
-                        for (int j = 0; j < H; ++j) acc[j] = __builtin_elementwise_fma(L[j] + Rr[j], f32x2{w, w}, acc[j]);
-#pragma unroll
-                        for (int j = 0; j < H - 1; ++j) L[j] = L[j + 1];
-#pragma unroll
-                        for (int j = H - 1; j > 0; --j) Rr[j] = Rr[j - 1];
-                        // volatile LDS reads: never merged with, or replaced by copies of, words already in registers
-                        // (same-run A/B on MI355X: this 0.80 ms per pass, "laundered" non-volatile pointers 0.865 ms,
-                        // the scalar variant 0.845 / 0.885 ms)
-                        lds_cvf32 q = (lds_cvf32)ctr;
-                        L[H - 1] = f32x2{q[(H - d) * LS], q[(2 * H - d) * LS]};
-                        Rr[0] = f32x2{q[(d - 1) * LS], q[(H + d - 1) * LS]};
-                    }
-                    // short partial sums (H <= FAST_SEG taps each): see the error bound above k_argmax_certify
-#pragma unroll
-                    for (int j = 0; j < H; ++j) { tot[j] += acc[j]; acc[j] = f32x2{0.f, 0.f}; }
-                }
-                if constexpr (REM > 0) {   // radius % H == REM: the last REM taps (d = REM .. 1), one more short partial sum
-#pragma unroll
-                    for (int kk = 0; kk < REM; ++kk) {
-                        const int d = REM - kk;
-                        const float w = wl[r - d];
-#pragma unroll
-                        for (int j = 0; j < H; ++j) acc[j] = __builtin_elementwise_fma(L[j] + Rr[j], f32x2{w, w}, acc[j]);
-#pragma unroll
-                        for (int j = 0; j < H - 1; ++j) L[j] = L[j + 1];
-#pragma unroll
-                        for (int j = H - 1; j > 0; --j) Rr[j] = Rr[j - 1];
-                        lds_cvf32 q = (lds_cvf32)ctr;
-                        L[H - 1] = f32x2{q[(H - d) * LS], q[(2 * H - d) * LS]};
-                        Rr[0] = f32x2{q[(d - 1) * LS], q[(H + d - 1) * LS]};
-                    }
-#pragma unroll
-                    for (int j = 0; j < H; ++j) tot[j] += acc[j];
-                }
-#pragma unroll
-                for (int j = 0; j < H; ++j) { res[j] = tot[j].x; res[j + H] = tot[j].y; }
-            }
-        }
-        if (STAGED) {
-            constexpr int OS = TO + 1;  // odd row stride: lane-major writes and row-major reads are both conflict-free
-            __syncthreads();            // every wave has finished reading the input tile
-            if (active) {
-#pragma unroll
-                for (int i = 0; i < R; ++i) tile[lane * OS + o0 + i] = res[i];
-            }
-            __syncthreads();
-            for (int l = wave; l < 64; l += NW) {
-                const int yy = l0 + l;
-                if (yy >= Y) break;
-                for (int p = lane; p < TO; p += 64)
-                    if (p0 + p < X) dst[(long)yy * X + p0 + p] = tile[l * OS + p];
-            }
-        } else if (line < nlines) {
-#pragma unroll
-            for (int i = 0; i < R; ++i) {
-                const int pp = p0 + o0 + i;
-                if (AXIS == 1) { if (pp < Y) dst[(long)pp * X + line] = res[i]; }
-                else { if (pp < X) dst[(long)line * X + pp] = res[i]; }
-            }
-        }
-    }
-}
-
 }  // namespace tip

@@ -1,8 +1,9 @@
 // tip_corr_f16.h -- the sigma-30 score passes (certified-argmax path) on the 16-bit matrix cores with SPLIT float32 operands.
 //
-// The passes are arithmetic-bound (241 taps per voxel), and gfx950's float32-input MFMA runs at the float32 VECTOR rate (the round-2/3
-// kernels of tip_corr_mfma*.h: 0.67-0.74 ms per pass at 65 % of that 157 TFLOP/s peak).  The fp16 MFMA is sixteen times faster, and the
-// score only feeds an argmax whose error bars are certified afterwards (k_argmax_certify), so the same banded-Toeplitz product
+// The passes are arithmetic-bound (241 taps per voxel), and gfx950's float32-input MFMA runs at the float32 VECTOR rate (the float32
+// MFMA kernels that came before, last present in commit c2e281b: 0.67-0.74 ms per pass at 65 % of that 157 TFLOP/s peak).  The fp16
+// MFMA is sixteen times faster, and the score only feeds an argmax whose error bars are certified afterwards (k_argmax_certify), so
+// the same banded-Toeplitz product
 //     Out(32 x 32) = W(32 x K) In(K x 32),   K = 32 + 2 r positions,   W[o][kk] = w(|kk - o - r|)
 // is formed from fp16 PIECES of power-of-two-scaled values with float32 accumulation (the U-Net's f16x3 arithmetic, tip_unet_conv.h):
 //     sample  a s = hi + 2^-11 lo',  hi = fp16(a s),  lo' = fp16((a s - hi) 2^11)      (s = 2^k puts the clip value in [2^13, 2^14))

@@ -60,10 +60,8 @@ struct Tuning {
     int ws_no_skip = 0;         // TIP_WS_NO_SKIP
     int ws_debug = 0;           // TIP_WS_DEBUG
     int ws_no_endgame = 0, ws_no_wide = 0;   // TIP_WS_NO_ENDGAME / TIP_WS_NO_WIDE (exercise the stall machinery)
-    int mfma_blocks_per_cu = 2; // TIP_MFMA_BLOCKS_PER_CU
     int project_generic = 0, project_unfused_preblur = 0, project_unfused_mask = 0;
     int project_exact_score = 0, project_debug = 0;
-    int fast_cfg_y = -1, fast_cfg_x = -1;    // TIP_FAST_CFG=y,x
     int unet_tail_unfused = 0;  // TIP_UNET_TAIL_UNFUSED: the tail's morphology as separate rank-filter launches (tests)
     int unet_xcd_map = 1;       // TIP_UNET_XCD_MAP: the channel blocks of one pixel tile side by side on one XCD (0: all workgroups in flight on one channel block)
     int unet_spb = 3;           // TIP_UNET_SPB: steps per barrier of the 3x3 16-row convolution kernel (1, 2 or 3)

@@ -9,7 +9,7 @@
 //   P8  per-channel max_z(image * mask) -> float64 (sp.py:72-81)    x pass fused with the weighted z-max
 #include "tip_slide.h"
 #include "tip_preblur.h"
-#include "tip_corr_mfma2.h"
+#include "tip_corr.h"
 #include "tip_corr_f16.h"
 #include <atomic>
 #include "tip_manifold.h"
@@ -543,18 +543,6 @@ __global__ void __launch_bounds__(256) k_mask_wmax_fused(const float *__restrict
     }
 }
 
-// Configuration of the fast sigma-30 passes: 3 / 4 = the matrix-core kernels (tip_corr_mfma.h / tip_corr_mfma2.h), else
-// variant * 10000 + (waves per block) * 100 + (outputs per lane and group) of the VALU kernel k_corr_long_fast.
-// Measured on the 2048 x 2048 x 30 frame, one frame in flight, y / x pass: VALU 0.79 / 0.81 ms, 3: 0.67 / 0.69 ms,
-// 4: 0.76 / 0.69 ms; whole classical pipeline 155 / 166.6 / 169.4 frames/s for (VALU, VALU) / (3, 3) / (3, 4), and
-// 242.7 / 249.8 / 252.2 with four frames in flight.
-#ifndef FAST_CFG_Y
-#define FAST_CFG_Y 5
-#endif
-#ifndef FAST_CFG_X
-#define FAST_CFG_X 5
-#endif
-
 static int cu_count()
 {
     static int cus = 0;          // (same device model on every GPU of a node; a benign race writes the same value)
@@ -565,70 +553,12 @@ static int cu_count()
     return cus;
 }
 
-template <int AXIS, int NW, int R, int VAR, int REM = 0>
-static int launch_fast_cfg(const float *in, float *out, int Zs, int Y, int X, const TapsF &t)
-{
-    const int r = t.n >> 1;
-    if (VAR != 0 && r % (R / 2) != REM) return fail(TIP_ERR_ARG, "fast pass: radius %d mod %d is not %d", r, R / 2, REM);
-    const size_t lds = (size_t)(256 + 2 * r) * (AXIS == 1 ? 64 : 65) * sizeof(float);
-    auto k = k_corr_long_fast<AXIS, 256, NW, R, VAR, REM>;
-    TIP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const dim3 grid = AXIS == 1 ? dim3(cdiv(X, 64), cdiv(Y, 256), Zs) : dim3(cdiv(Y, 64), cdiv(X, 256), Zs);
-    TIP_LAUNCH(AXIS == 1 ? "score_fast_y" : "score_fast_x", k, grid, dim3(NW * 64), lds, in, out, Zs, Y, X, t);
-    return TIP_OK;
-}
-
-// the same pass on the matrix cores (tip_corr_mfma.h)
-template <int AXIS>
-static int launch_mfma(const float *in, float *out, int Zs, int Y, int X, const TapsF &t)
-{
-    const int r = t.n >> 1;
-    if (r < 1 || r > 127 || (16 + r) % MF_SEG) return fail(TIP_ERR_ARG, "mfma pass: radius %d (16 + r must be a multiple of %d)", r, MF_SEG);
-    const int npos = MF_TO + 2 * r;
-    const size_t lds = AXIS == 1 ? (size_t)npos * MF_LN * sizeof(float)
-                                 : (size_t)MF_LN * (npos + 1 + (npos & 1)) * sizeof(float);
-    auto k = k_corr_long_mfma<AXIS>;
-    TIP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int tiles_pos = cdiv(AXIS == 1 ? Y : X, MF_TO), tiles_ln = cdiv(AXIS == 1 ? X : Y, MF_LN);
-    const int ntiles = tiles_pos * tiles_ln * Zs;
-    const int cus = cu_count();
-    const int per_cu = tuning().mfma_blocks_per_cu;
-    const int blocks = std::min(ntiles, per_cu * cus);  // persistent blocks, two per CU (LDS: 64 KB each); tuning hook: one
-    TIP_LAUNCH(AXIS == 1 ? "score_fast_y" : "score_fast_x", k, dim3(blocks), dim3(MF_NW * 64), lds, in, out, Zs, Y, X, t, ntiles,
-               tiles_pos, tiles_ln);
-    return TIP_OK;
-}
-
-// ... with asynchronous global -> LDS copies and one double-buffered persistent block per CU (tip_corr_mfma2.h)
-template <int AXIS>
-static int launch_mfma2(const float *in, float *out, int Zs, int Y, int X, const TapsF &t)
-{
-    const int r = t.n >> 1;
-    if (r < 8 || r > 120 || r % MF_SEG) return fail(TIP_ERR_ARG, "mfma pass: radius %d (a multiple of %d in [8, 120])", r, MF_SEG);
-    const int npos = MF_TO + 2 * r;
-    const int pitch = 513;                                // AXIS 2: 512 copied positions per line; odd: ds_read_b32 / ds_read2_b32 bank
-                                                          // on (address / 4) mod 32 within each 32-lane half, and a half holds the
-                                                          // 32 lines of one position (pitch 514 made lines l and l + 16 collide)
-    const int bufsz = AXIS == 1 ? npos * MF_LN : MF_LN * pitch;
-    const size_t lds = ((size_t)2 * bufsz + 2 * 127 + 64 + 64) * sizeof(float);   // + padded kernel + sink
-    if (lds > 160 * 1024) return fail(TIP_ERR_ARG, "mfma pass: tile buffers exceed the LDS");
-    auto k = k_corr_long_mfma2<AXIS>;
-    TIP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int tiles_pos = cdiv(AXIS == 1 ? Y : X, MF_TO), tiles_ln = cdiv(AXIS == 1 ? X : Y, MF_LN);
-    const long nt = (long)tiles_pos * tiles_ln * Zs;
-    if (nt > 0x7fffffffL - 4096) return fail(TIP_ERR_ARG, "mfma pass: too many tiles");
-    const int ntiles = (int)nt;
-    const int cus = cu_count();
-    const int blocks = std::min(ntiles, cus);             // persistent blocks, one per CU (two 62 KB tile buffers each)
-    TIP_LAUNCH(AXIS == 1 ? "score_fast_y" : "score_fast_x", k, dim3(blocks), dim3(MF_NW * 64), lds, in, out, Zs, Y, X, t, ntiles,
-               tiles_pos, tiles_ln, pitch, bufsz);
-    return TIP_OK;
-}
-
-// ... on the fp16 matrix cores with split operands (tip_corr_f16.h): radius 120 (sigma 30), data bounded by the clip value
+// The sigma-30 score pass of the certified argmax on the fp16 matrix cores with split operands (tip_corr_f16.h): radius 120
+// (241 taps) only, data bounded by the clip value; err bit 8 (range_flag) reports a sample beyond that range.
 template <int AXIS>
 static int launch_f16(const float *in, float *out, int Zs, int Y, int X, const TapsF &t, const ClipInfo *clip, int *range_flag)
 {
+    if (t.n != 241 || !clip || !range_flag) return fail(TIP_ERR_ARG, "f16 score pass: %d taps (241 only) or no clip value / range flag", t.n);
     constexpr int R8 = 15, NPOS = HF_TO + 16 * R8, PITCH = ((NPOS / 8) | 1) * 8, WROWS = 2 * (R8 + 2) + 3;
     const size_t lds = (size_t)2 * HF_LN * PITCH * 2 + (size_t)2 * WROWS * 8 * 16;
     auto k = k_corr_long_f16<AXIS, R8>;
@@ -647,40 +577,19 @@ static int launch_f16(const float *in, float *out, int Zs, int Y, int X, const T
     return TIP_OK;
 }
 
-template <int AXIS>
-static int launch_fast(int cfg, const float *in, float *out, int Zs, int Y, int X, const TapsF &t, const ClipInfo *clip = nullptr,
-                       int *range_flag = nullptr)
-{
-    const int r = t.n >> 1;
-    if (cfg == 5 && (r != 120 || !clip || !range_flag)) cfg = AXIS == 1 ? 3 : 4;          // the fp16 tiles: sigma 30 on clipped data only
-    if (cfg == 5) return launch_f16<AXIS>(in, out, Zs, Y, X, t, clip, range_flag);
-    if ((cfg == 3 || cfg == 4) && (r < 8 || r > 120 || r % MF_SEG)) cfg = 11616;   // the MFMA tiles need radius % 8 == 0 (sigma 30: 120)
-    if (cfg == 3) return launch_mfma<AXIS>(in, out, Zs, Y, X, t);
-    if (cfg == 4) return launch_mfma2<AXIS>(in, out, Zs, Y, X, t);
-    if (cfg == 10832 && r % 16 != 0 && r % 16 != 8) cfg = 11616;   // 32 outputs per lane: radius % 16 must be 0 or 8
-    if (cfg / 10000 == 1 && cfg != 10832 && (r % 8)) cfg -= 10000;  // the packed variant needs radius % H == 0
-    switch (cfg) {   // variant * 10000 + waves * 100 + outputs per lane
-    case 1616: return launch_fast_cfg<AXIS, 16, 16, 0>(in, out, Zs, Y, X, t);
-    case 11616: return launch_fast_cfg<AXIS, 16, 16, 1>(in, out, Zs, Y, X, t);
-    case 10832:   // 8 waves, 32 outputs per lane: half the LDS window reads per output, 2 waves per SIMD
-        return r % 16 == 0 ? launch_fast_cfg<AXIS, 8, 32, 1, 0>(in, out, Zs, Y, X, t) : launch_fast_cfg<AXIS, 8, 32, 1, 8>(in, out, Zs, Y, X, t);
-    default: return fail(TIP_ERR_ARG, "unknown fast-pass configuration %d", cfg);
-    }
-}
-
 // ---- certified argmax --------------------------------------------------------------------------------------------------
 // The sigma-30 score is used for ONE thing: chosen_z = argmax_z(score) (sp.py:55-61).  So the score itself need not be
-// exact -- only the argmax must be.  The fast passes (k_corr_long_fast) give S~ with |S~ - S| <= EPS * S for the exact
-// float32 score S: each fast pass is within a = (1+u)^36 - 1 of the real-number sum (short partial sums, see tip_corr.h)
-// and scipy's pass within 1.0001u of it (u = 2^-24, all terms non-negative), two passes compose to 2a + 2.1u < 74.2u;
-// EPS = 96u leaves 29 % headroom.  (With one running sum per output a was 123u and EPS 320u: the uncertified pixels --
+// exact -- only the argmax must be.  The fp16 score passes (k_corr_long_f16) give S~ with |S~ - S| <= EPS * S + ABS for the
+// exact float32 score S.  By the bound in the header of tip_corr_f16.h (u = 2^-24, all samples and taps non-negative), each pass is
+// within 38.2u relative (plus 2^-35 / s absolute) of the real-number sum and scipy's pass within 1.0001u of it; two passes compose
+// to < 79u relative and < clip 2^-47 absolute.  EPS = 96u leaves 21 % headroom on the relative part.  (The uncertified pixels --
 // and the cost of the exact fix-up -- scale with EPS.)
 // A pixel is certified when its best fast score beats every other plane by more than both error bars; the few that
 // are not (top two planes closer than ~1.2e-5 relative: the lines where the surface crosses between planes) are
 // recomputed in exact scipy arithmetic from the z-passed volume, for the candidate planes only.
 #define CERT_EPS (96.0f * 5.9604644775390625e-8f)
-// absolute part of the fast passes' error: none for the float32 tiles (relative down to underflow); the fp16 tiles keep 22 bits
-// relative down to 2^-36 of the clip value and are off by at most clip 2^-47 below that (tip_corr_f16.h) -- 2^-44 here
+// ABS: the fp16 tiles keep 22 bits relative down to 2^-36 of the clip value and are off by at most clip 2^-47 below that
+// (tip_corr_f16.h) -- clip 2^-44 here, a factor 8 of headroom
 __device__ __forceinline__ float cert_abs(const ClipInfo *clip)
 {
     return (clip && clip->has) ? clip->p95 * 5.684341886080802e-14f + 1e-30f : 1e-30f;
@@ -1154,15 +1063,11 @@ int project_dev(const uint16_t *czyx, int C, int Z, int Y, int X, int zlo, int z
         TapsF f30;
         f30.n = k30.n;
         for (int i = 0; i < 256; ++i) f30.w[i] = (float)k30.w[i];
-        const int r = k30.n >> 1;
-        {   // fast y pass B -> A, fast x pass A -> D   (B, the exact z-passed volume, is kept for the exact fix-up)
-            int cy = FAST_CFG_Y, cx = FAST_CFG_X;
-            if (tuning().fast_cfg_y >= 0) { cy = tuning().fast_cfg_y; cx = tuning().fast_cfg_x >= 0 ? tuning().fast_cfg_x : cx; }  // tuning hook TIP_FAST_CFG: NW*100+NP per pass
-            // (the fp16 tiles, cfg 5, take the clip value: their samples are scaled into fp16's range by it, and the volume B --
-            //  convex combinations of clipped voxels -- is bounded by it; err bit 8 would report a sample beyond that range)
-            if ((rc = launch_fast<1>(cy, (const float *)B, A, Zs, Y, X, f30, clip, err))) return rc;
-            if ((rc = launch_fast<2>(cx, (const float *)A, D, Zs, Y, X, f30, clip, err))) return rc;
-        }
+        // fast y pass B -> A, fast x pass A -> D   (B, the exact z-passed volume, is kept for the exact fix-up).  The fp16 tiles
+        // take the clip value: their samples are scaled into fp16's range by it, and the volume B -- convex combinations of
+        // clipped voxels -- is bounded by it; err bit 8 would report a sample beyond that range.
+        if ((rc = launch_f16<1>((const float *)B, A, Zs, Y, X, f30, clip, err))) return rc;
+        if ((rc = launch_f16<2>((const float *)A, D, Zs, Y, X, f30, clip, err))) return rc;
         TIP_HIP(hipMemsetAsync(uncn, 0, sizeof(int), c.stream));
         TIP_LAUNCH("argmax_certify", k_argmax_certify, dim3(cdiv(cdiv(P, 4), 256)), dim3(256), 0, (const float *)D, Zs, P, bestz, unc, uncn,
                    (const ClipInfo *)clip);
