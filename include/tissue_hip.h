@@ -311,6 +311,19 @@ TIP_API int tip_phase_correlation(const void *ref, const void *mov, int dtype, i
 TIP_API int tip_phase_correlation_dev(const void *ref, const void *mov, int dtype, int y, int x, int upsample,
                                       int64_t *out4_host);
 
+/* ---- PIV drift: skimage.registration.optical_flow_tvl1(ref, mov, attachment, tightness, num_warp, num_iter, tol) --- */
+/* (ti.py:2061-2070 track_cells_iterator(use_piv=True)); scikit-image 0.18.3, 2-D, float32, prefilter=False.           */
+/* dtype: 0 float32, 1 float64, 3 uint16, 4 uint8 (integers scaled to [0, 1] like skimage's _convert); y, x >= 2.       */
+/* flow_out: (2, y, x) float32, row displacement then column displacement.  warps_per_level: the warps each pyramid    */
+/* level ran, coarse to fine (skimage's early stop), `cap` entries (at most 10 levels).  The _dev variant takes device */
+/* ref / mov / flow_out; warps_per_level stays a host array there, and when it is not NULL the call waits for the      */
+/* stream (without it the call is asynchronous like every _dev entry).                                                */
+TIP_API int tip_optical_flow_tvl1(const void *ref, const void *mov, int dtype, int y, int x, float attachment, float tightness,
+                                  int num_warp, int num_iter, double tol, float *flow_out, int32_t *warps_per_level, int cap);
+TIP_API int tip_optical_flow_tvl1_dev(const void *ref, const void *mov, int dtype, int y, int x, float attachment,
+                                      float tightness, int num_warp, int num_iter, double tol, float *flow_out,
+                                      int32_t *warps_per_level, int cap);
+
 #ifdef __cplusplus
 }
 #endif

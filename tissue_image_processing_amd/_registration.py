@@ -145,3 +145,77 @@ def sample_local_drift(drifts, rows, cols):
         cnt[inside] += 1
     with np.errstate(invalid="ignore", divide="ignore"):
         return sx / cnt, sy / cnt
+
+
+# ---- PIV drift (ti.py:2061-2070): TV-L1 optical flow between two frames -------------------------------------------------
+_OF_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.uint16): 3, np.dtype(np.uint8): 4}
+
+
+def _of_args(reference_image, moving_image, prefilter, dtype):
+    a = np.asarray(reference_image)
+    b = np.asarray(moving_image)
+    if a.shape != b.shape:
+        raise ValueError("Input images should have the same shape")
+    if np.dtype(dtype).char not in 'efdg':
+        raise ValueError("Only floating point data type are valid for optical flow")
+    if prefilter:
+        raise NotImplementedError("optical_flow_tvl1: prefilter=True is not supported on MI355X (the reference never passes it)")
+    if np.dtype(dtype) != np.float32:
+        raise NotImplementedError("optical_flow_tvl1: only dtype=float32 (the reference's default)")
+    if a.ndim != 2:
+        raise NotImplementedError("optical_flow_tvl1: 2-D frames only")
+    if a.dtype not in _OF_DTYPES:
+        a = a.astype(np.float64)
+    if b.dtype not in _OF_DTYPES:
+        b = b.astype(np.float64)
+    if a.dtype != b.dtype:            # each frame converts on its own (skimage's _convert); float64 keeps both exact
+        a = a.astype(np.float32) if a.dtype.kind == "f" else _to_unit_f32(a)
+        b = b.astype(np.float32) if b.dtype.kind == "f" else _to_unit_f32(b)
+    if min(a.shape) < 2:
+        raise ValueError("optical_flow_tvl1: frames need at least 2 rows and 2 columns (np.gradient)")
+    return np.ascontiguousarray(a), np.ascontiguousarray(b)
+
+
+def _to_unit_f32(img):
+    return np.multiply(img, 1.0 / np.iinfo(img.dtype).max, dtype=np.float32)
+
+
+def optical_flow_tvl1(reference_image, moving_image, *, attachment=15, tightness=0.3, num_warp=5, num_iter=10, tol=1e-4,
+                      prefilter=False, dtype=np.float32):
+    """skimage.registration.optical_flow_tvl1 (0.18.3) on MI355X: the (2, M, N) float32 flow, row displacement first.
+    prefilter=True, float64 flows and 3-D frames are not supported (NotImplementedError); the reference uses none of them."""
+    flow, _ = optical_flow_tvl1_levels(reference_image, moving_image, attachment=attachment, tightness=tightness,
+                                       num_warp=num_warp, num_iter=num_iter, tol=tol, prefilter=prefilter, dtype=dtype)
+    return flow
+
+
+def optical_flow_tvl1_levels(reference_image, moving_image, *, attachment=15, tightness=0.3, num_warp=5, num_iter=10,
+                             tol=1e-4, prefilter=False, dtype=np.float32):
+    """optical_flow_tvl1 that also returns the warps each pyramid level ran (coarse to fine)."""
+    a, b = _of_args(reference_image, moving_image, prefilter, dtype)
+    flow = np.empty((2,) + a.shape, np.float32)
+    warps = np.zeros(10, np.int32)
+    _lib.check(_lib.lib().tip_optical_flow_tvl1(_lib.ptr(a), _lib.ptr(b), _OF_DTYPES[a.dtype], a.shape[0], a.shape[1],
+                                                ctypes.c_float(attachment), ctypes.c_float(tightness), int(num_warp),
+                                                int(num_iter), ctypes.c_double(tol), _lib.ptr(flow), _lib.ptr(warps), 10))
+    return flow, [int(w) for w in warps[:pyramid_levels(a.shape)]]
+
+
+def pyramid_levels(shape):
+    """Levels of skimage's get_pyramid(downscale=2, nlevel=10, min_size=16)."""
+    n, m = 1, min(shape)
+    while n < 10 and m > 32:
+        shape = tuple((s + 1) // 2 for s in shape)
+        m = min(shape)
+        n += 1
+    return n
+
+
+def optical_flow_tvl1_dev(ref_ptr, mov_ptr, ny, nx, flow_ptr, dtype="float32", attachment=15, tightness=0.3, num_warp=5,
+                          num_iter=10, tol=1e-4):
+    """The same on device-resident (ny, nx) frames; the (2, ny, nx) float32 flow goes to the device address flow_ptr.
+    Asynchronous on the calling thread's stream."""
+    dt = {"float32": 0, "float64": 1, "uint16": 3, "uint8": 4}[dtype]
+    _lib.check(_lib.lib().tip_optical_flow_tvl1_dev(_lib.dptr(ref_ptr), _lib.dptr(mov_ptr), dt, int(ny), int(nx),
+                                                    ctypes.c_float(attachment), ctypes.c_float(tightness), int(num_warp),
+                                                    int(num_iter), ctypes.c_double(tol), _lib.dptr(flow_ptr), None, 0))

@@ -389,8 +389,6 @@ class TissueHipMixin(object):
         """ti.py:2037-2113, the label-lookup tracker: the previous frame's centroids (drift-corrected) are looked up in
         the current frame's 3x3-max-filtered label map, ids propagate one-to-one, unmatched cells get fresh ids.
         Generator yielding the frame numbers it finished, like the reference."""
-        if use_piv:
-            raise NotImplementedError("optical-flow (PIV) drift is out of scope (SURVEY.md 8f)")
         from .movie import assign_track_ids
         last = self.number_of_frames if final_frame == -1 else final_frame
         table = self.get_cells_info(initial_frame)
@@ -410,7 +408,9 @@ class TissueHipMixin(object):
                     self.drifts[frame - 1, :] = np.nan
                     refresh_next = True
                 continue
-            if reuse_drifts and not refresh_next:
+            if use_piv and images is not None:
+                dx, dy = self._piv_drift(images, prev, frame, image_in_memory)
+            elif reuse_drifts and not refresh_next:
                 dy, dx = self.drifts[frame - 1, 0], self.drifts[frame - 1, 1]
             else:
                 dy, dx = self.update_drift(frame, prev["frame"], images=images, image_in_memory=image_in_memory)
@@ -436,6 +436,23 @@ class TissueHipMixin(object):
                         ids=ids, empty=table.empty_cell.to_numpy(), frame=frame)
             yield frame
         return 0
+
+    @staticmethod
+    def _piv_drift(images, prev, frame, image_in_memory):
+        """ti.py:2061-2070: the TV-L1 flow from the previous frame to this one, sampled at the previous centroids exactly as
+        upstream indexes it -- transposed, the row flow at (row = round(cx), col = round(cy)), numpy rules included (half to
+        even, negative indices wrap, an index past the end raises IndexError).  Returns (drift_x, drift_y) per cell;
+        self.drifts is not written."""
+        from ._registration import optical_flow_tvl1
+        last_image = images[prev["frame"] - 1]
+        current_image = images[frame - 1]
+        if not image_in_memory:
+            last_image = last_image.compute()
+            current_image = current_image.compute()
+        piv_x, piv_y = optical_flow_tvl1(np.asarray(last_image), np.asarray(current_image))
+        rows = np.round(prev["cx"]).astype(int)
+        cols = np.round(prev["cy"]).astype(int)
+        return piv_x[rows, cols], piv_y[rows, cols]
 
     # ---- T1 -------------------------------------------------------------------------------------------------
     @staticmethod
