@@ -323,6 +323,23 @@ TIP_API int tip_optical_flow_tvl1(const void *ref, const void *mov, int dtype, i
 TIP_API int tip_optical_flow_tvl1_dev(const void *ref, const void *mov, int dtype, int y, int x, float attachment,
                                       float tightness, int num_warp, int num_iter, double tol, float *flow_out,
                                       int32_t *warps_per_level, int cap);
+/* The PIV step of the sharded movie tracker (movie.process_movie(use_piv=True); ti.py:2061-2106, frame t against t-1):  */
+/* the flow above from prev_plane to cur_plane -- DEVICE (y, x) float64 reference-channel projections, each truncated to  */
+/* uint16 first (astype, as the GUI loads the movie) and then scaled like dtype 3 -- sampled at the n rows of frame t-1's  */
+/* table with upstream's transposed indexing: rows = round(cx), cols = round(cy) (half to even; an index in [-size, 0)    */
+/* wraps), cx -= flow_row[rows, cols], cy -= flow_col[rows, cols] in float64; then hit_host[i] = maximum_filter(labels,    */
+/* (3,3), 'constant') at (round(cy), round(cx)), -1 outside the frame or where present_host[i] == 0.  labels is a DEVICE */
+/* int32 map; cy/cx/present/hit are host arrays.  An index that numpy would reject gives TIP_ERR_INDEX with numpy's text */
+/* ("index I is out of bounds for axis A with size S", the first failing row, axis 0 before axis 1).  The flow stays in  */
+/* the workspace unless flow_dev (device, (2, y, x) float32) is given; with n == 0 and no flow_dev nothing is computed.  */
+/* Waits for the stream when n > 0.                                                                                      */
+TIP_API int tip_piv_lookup_max3_i32_dev(const double *prev_plane, const double *cur_plane, const int32_t *labels, int y, int x,
+                                        const double *cy_host, const double *cx_host, const uint8_t *present_host, int64_t n,
+                                        float attachment, float tightness, int num_warp, int num_iter, double tol,
+                                        float *flow_dev, int32_t *hit_host);
+/* Its sampling-and-lookup step alone on a given DEVICE (2, y, x) float32 flow (same rules, same errors; waits).          */
+TIP_API int tip_piv_sample_max3_i32_dev(const float *flow, const int32_t *labels, int y, int x, const double *cy_host,
+                                        const double *cx_host, const uint8_t *present_host, int64_t n, int32_t *hit_host);
 
 #ifdef __cplusplus
 }

@@ -219,3 +219,38 @@ def optical_flow_tvl1_dev(ref_ptr, mov_ptr, ny, nx, flow_ptr, dtype="float32", a
     _lib.check(_lib.lib().tip_optical_flow_tvl1_dev(_lib.dptr(ref_ptr), _lib.dptr(mov_ptr), dt, int(ny), int(nx),
                                                     ctypes.c_float(attachment), ctypes.c_float(tightness), int(num_warp),
                                                     int(num_iter), ctypes.c_double(tol), _lib.dptr(flow_ptr), None, 0))
+
+
+# ---- PIV step of the sharded movie tracker (movie.process_movie(use_piv=True); ti.py:2061-2106) ---------------------------
+def _piv_rows(prev_table):
+    cy = np.ascontiguousarray(prev_table["cy"], dtype=np.float64)
+    cx = np.ascontiguousarray(prev_table["cx"], dtype=np.float64)
+    present = np.ascontiguousarray(np.asarray(prev_table["area"]) > 0, dtype=np.uint8)
+    if not (cy.shape == cx.shape == present.shape) or cy.ndim != 1:
+        raise ValueError("piv lookup: cy, cx and area must be 1-D arrays of one length")
+    return cy, cx, present
+
+
+def piv_lookup_dev(prev_ptr, cur_ptr, labels_ptr, ny, nx, prev_table, flow_ptr=None, attachment=15, tightness=0.3,
+                   num_warp=5, num_iter=10, tol=1e-4):
+    """tip_piv_lookup_max3_i32_dev: the TV-L1 flow between two device-resident float64 (ny, nx) planes (frame t-1, frame t;
+    each truncated to uint16 first, as the GUI loads the movie), sampled at the rows of frame t-1's table (dict with cy, cx,
+    area) with upstream's transposed indexing, and frame t's 3x3-max-filtered device label map looked up at the moved
+    centroids.  Returns int32 hits (-1: outside the frame or an absent row); raises IndexError where numpy would.
+    flow_ptr: a device (2, ny, nx) float32 buffer that receives the flow (default: it stays in the library's workspace)."""
+    cy, cx, present = _piv_rows(prev_table)
+    hit = np.empty(cy.shape, np.int32)
+    _lib.check(_lib.lib().tip_piv_lookup_max3_i32_dev(
+        _lib.dptr(prev_ptr), _lib.dptr(cur_ptr), _lib.dptr(labels_ptr), int(ny), int(nx), _lib.ptr(cy), _lib.ptr(cx),
+        _lib.ptr(present), ctypes.c_int64(cy.size), ctypes.c_float(attachment), ctypes.c_float(tightness), int(num_warp),
+        int(num_iter), ctypes.c_double(tol), None if flow_ptr is None else _lib.dptr(flow_ptr), _lib.ptr(hit)))
+    return hit
+
+
+def piv_sample_dev(flow_ptr, labels_ptr, ny, nx, prev_table):
+    """tip_piv_sample_max3_i32_dev: piv_lookup_dev's sampling and look-up on a given device (2, ny, nx) float32 flow."""
+    cy, cx, present = _piv_rows(prev_table)
+    hit = np.empty(cy.shape, np.int32)
+    _lib.check(_lib.lib().tip_piv_sample_max3_i32_dev(_lib.dptr(flow_ptr), _lib.dptr(labels_ptr), int(ny), int(nx), _lib.ptr(cy),
+                                                      _lib.ptr(cx), _lib.ptr(present), ctypes.c_int64(cy.size), _lib.ptr(hit)))
+    return hit

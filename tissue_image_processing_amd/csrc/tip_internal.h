@@ -106,4 +106,11 @@ struct TapsF {   // float32 copy for the certified fast score passes
 int make_taps(Taps &t, const double *w, int n);  // validates odd + symmetric (scipy's symmetric branch)
 int libm_taps(double sigma, double truncate, double *w, int cap);
 
+// tip_optflow.hip: the TV-L1 flow on device planes, asynchronous unless warps_host is given; returns the pyramid's level
+// count or an error code.  dtype: the public codes of tip_optical_flow_tvl1 or OF_F64_AS_U16, a float64 plane truncated to
+// uint16 and then scaled as code 3 (tip_piv.hip: the projection as the GUI tracks it) -- one read of each plane.
+constexpr int OF_F64_AS_U16 = 5;
+int optical_flow_tvl1_dev(const void *ref, const void *mov, int dtype, int y, int x, float attachment, float tightness,
+                          int num_warp, int num_iter, double tol, float *flow_out, int32_t *warps_host, int cap);
+
 }  // namespace tip

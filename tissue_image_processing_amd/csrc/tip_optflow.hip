@@ -28,6 +28,13 @@ __global__ void __launch_bounds__(256) k_of_convert(const void *__restrict__ src
     if (dtype == 0) v = ((const float *)src)[i];
     else if (dtype == 1) v = (float)((const double *)src)[i];
     else if (dtype == 3) v = (float)((const uint16_t *)src)[i] * (float)(1.0 / 65535.0);   // np.multiply(img, 1/imax, dtype=float32)
+    else if (dtype == OF_F64_AS_U16) {
+        // a float64 plane as the GUI loads it: astype(uint16) first (truncation; outside [0, 65535] the x86 cast's int32
+        // wrap, NaN and values past int32 give 0), then as code 3
+        const double d = trunc(((const double *)src)[i]);
+        const uint16_t u = (d >= -2147483648.0 && d <= 2147483647.0) ? (uint16_t)(int32_t)d : (uint16_t)0;
+        v = (float)u * (float)(1.0 / 65535.0);
+    }
     else v = (float)((const uint8_t *)src)[i] * (float)(1.0 / 255.0);
     dst[i] = v;
 }
@@ -283,8 +290,8 @@ struct Level { int H, W; float *ref, *mov; };
 
 }  // namespace
 
-// ref, mov: device (y, x) planes of `dtype` (0 f32, 1 f64, 3 u16, 4 u8); flow_out: device (2, y, x) float32;
-// warps_host: NULL or a host array of `cap` ints (then the call waits for the stream)
+// ref, mov: device (y, x) planes of `dtype` (0 f32, 1 f64, 3 u16, 4 u8, or the internal OF_F64_AS_U16); flow_out: device
+// (2, y, x) float32; warps_host: NULL or a host array of `cap` ints (then the call waits for the stream)
 int optical_flow_tvl1_dev(const void *ref, const void *mov, int dtype, int y, int x, float attachment, float tightness,
                           int num_warp, int num_iter, double tol, float *flow_out, int32_t *warps_host, int cap)
 {
@@ -292,7 +299,7 @@ int optical_flow_tvl1_dev(const void *ref, const void *mov, int dtype, int y, in
     if (!c.stream) return TIP_ERR_HIP;
     if (!ref || !mov || !flow_out) return fail(TIP_ERR_ARG, "tip_optical_flow_tvl1: null pointer");
     if (y < 2 || x < 2) return fail(TIP_ERR_ARG, "tip_optical_flow_tvl1: frames need at least 2 rows and 2 columns (got %dx%d)", y, x);
-    if (dtype != 0 && dtype != 1 && dtype != 3 && dtype != 4)
+    if (dtype != 0 && dtype != 1 && dtype != 3 && dtype != 4 && dtype != OF_F64_AS_U16)
         return fail(TIP_ERR_ARG, "tip_optical_flow_tvl1: dtype %d (0 f32, 1 f64, 3 u16, 4 u8)", dtype);
     // get_pyramid(downscale=2, nlevel=10, min_size=16): reduce while min(shape) > 32
     Level lv[OF_MAX_LEVELS];
@@ -420,6 +427,7 @@ extern "C" {
 int tip_optical_flow_tvl1_dev(const void *ref, const void *mov, int dtype, int y, int x, float attachment, float tightness,
                               int num_warp, int num_iter, double tol, float *flow_out, int32_t *warps_per_level, int cap)
 {
+    if (dtype == OF_F64_AS_U16) return fail(TIP_ERR_ARG, "tip_optical_flow_tvl1: dtype %d (0 f32, 1 f64, 3 u16, 4 u8)", dtype);
     int rc = optical_flow_tvl1_dev(ref, mov, dtype, y, x, attachment, tightness, num_warp, num_iter, tol, flow_out,
                                    warps_per_level, cap);
     return rc < 0 ? rc : TIP_OK;
@@ -431,6 +439,7 @@ int tip_optical_flow_tvl1(const void *ref, const void *mov, int dtype, int y, in
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
     if (!ref || !mov || !flow_out || y < 2 || x < 2) return fail(TIP_ERR_ARG, "tip_optical_flow_tvl1: bad arguments");
+    if (dtype == OF_F64_AS_U16) return fail(TIP_ERR_ARG, "tip_optical_flow_tvl1: dtype %d (0 f32, 1 f64, 3 u16, 4 u8)", dtype);
     const size_t es = dtype == 1 ? 8 : (dtype == 0 ? 4 : (dtype == 3 ? 2 : 1));
     const size_t bytes = (size_t)y * x * es;
     WsGuard ws;

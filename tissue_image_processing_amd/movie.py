@@ -15,6 +15,11 @@ sharded driver as well: the owner of frame t needs frame t-1's reference-channel
 xGMI, all pairs at once) -- and runs the phase correlation next to its own plane.  `stitcher="linker"` replaces the
 label-lookup tracker by the trackpy-model linker (ti.py:1881-1933, linking.FrameLinker) on rank 0.
 
+With `use_piv=True` the same plane exchange feeds the tracker's PIV mode (ti.py:2061-2106) instead: the owner of frame t
+runs the TV-L1 flow from frame t-1's plane to its own (both truncated to uint16 first, as the GUI loads the movie), samples
+it at frame t-1's centroids with upstream's transposed indexing and looks the moved centroids up in its label map -- one
+device call per frame (tip_piv_lookup_max3_i32_dev), the flow never leaves the GPU.  Drifts are not written.
+
 `backend` supplies the per-frame compute so the same driver runs on GPUs (GpuFrameBackend) and, for the
 multi-process CPU tests, on a stand-in backend with the gloo process group.
 """
@@ -194,6 +199,19 @@ class GpuFrameBackend(object):
         from . import _lib
         return torch.empty((self.Y, self.X), dtype=torch.float64, device=torch.device("cuda", _lib.device_for_thread() or 0))
 
+    def piv_lookup(self, t, prev_plane, prev_table):
+        """The PIV step of the tracker for frame t (ti.py:2061-2106): TV-L1 flow from frame t-1's reference-channel plane
+        (prev_plane, received from the neighbour rank) to frame t's, both truncated to uint16 on the device; frame t-1's
+        centroids (prev_table: area, cy, cx) moved by the flow sampled as upstream samples it (row flow at (round(cx),
+        round(cy)), numpy's wrap and IndexError rules) and looked up in frame t's 3x3-max-filtered label map.  Returns int32
+        hits (-1: outside the frame or an absent row); raises IndexError where upstream's numpy indexing would."""
+        import torch
+        from ._registration import piv_lookup_dev
+        if not self.keep_planes:
+            raise ValueError("piv_lookup needs the reference-channel planes: GpuFrameBackend(..., keep_planes=True)")
+        torch.cuda.current_stream(prev_plane.device).synchronize()      # the received plane is complete
+        return piv_lookup_dev(prev_plane.data_ptr(), self.planes[t].data_ptr(), self.labels[t].ptr, self.Y, self.X, prev_table)
+
     def drift(self, t, prev_plane):
         """(row shift, column shift) that registers frame t onto frame t-1: Tissue.update_drift without a stage table
         (ti.py:1982-2035 -> calculate_refine_drift with a zero coarse shift -> phase_cross_correlation(upsample 100))."""
@@ -323,11 +341,33 @@ def link_ids(tables, drifts):
     return out
 
 
+def _first_piv_failure(failed, rank, world, dist, device):
+    """all-gather of every rank's first failing PIV frame this round ((frame, kind) or (-1, 0); kind 1: IndexError, 2: other)
+    -> the lowest failing frame over all ranks as (frame, kind, owner rank), or None."""
+    import torch
+    if world == 1:
+        return failed + (rank,) if failed[0] >= 0 else None
+    mine = torch.tensor(list(failed), dtype=torch.int64, device=device)
+    allv = [torch.zeros(2, dtype=torch.int64, device=device) for _ in range(world)]
+    dist.all_gather(allv, mine)
+    hits = [(int(v[0]), int(v[1]), r) for r, v in enumerate(allv) if int(v[0]) >= 0]
+    return min(hits) if hits else None
+
+
 def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, device="cpu", drifts=None,
-                  estimate_drift=False, stitcher="lookup", block_frames=None):
+                  estimate_drift=False, stitcher="lookup", block_frames=None, use_piv=False):
     """Runs the sharded pipeline.  frame_source(t) -> uint16 stack (or whatever backend.process_frame takes).
     Returns on rank 0: (tables per frame, track ids per frame); on other ranks (None, None).  tables[t]["drift"] holds
     the (row, column) drift used between frames t-1 and t (estimated by frame t's owner when estimate_drift).
+
+    use_piv=True: the tracker's PIV mode (Tissue.track_cells_iterator(use_piv=True), ti.py:2061-2106).  Planes are exchanged
+    as for estimate_drift, and the owner of frame t >= 1 calls backend.piv_lookup(t, plane of frame t-1, table of frame t-1)
+    instead of shifting the centroids by a drift and calling backend.lookup; tables[t]["drift"] keeps the `drifts` row given.
+    It needs a backend with planes (GpuFrameBackend(keep_planes=True)) and the "lookup" stitcher, and excludes
+    estimate_drift (ValueError).  Upstream's transposed sampling makes only square frames safe: where its numpy indexing
+    raises, every rank raises IndexError for the lowest failing frame of that round -- each rank first takes part in the
+    round's small all-gather of failures and joins its worker thread, so no collective is left waiting and no further
+    round starts.
 
     The movie is worked off in ROUNDS of `block_frames` frames per rank (round k = global frames [k B W, (k+1) B W)): while
     the workers compute round k+1, this thread runs round k's exchange -- planes to the neighbour rank, drift, all-gather of
@@ -338,6 +378,13 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
     import threading
     if stitcher not in ("lookup", "linker"):
         raise ValueError("stitcher must be 'lookup' or 'linker'")
+    if use_piv:
+        if estimate_drift:
+            raise ValueError("use_piv and estimate_drift are two drift sources: pass one of them")
+        if stitcher != "lookup":
+            raise ValueError("use_piv needs stitcher='lookup' (the reference's trackpy linker has no PIV mode)")
+        if not hasattr(backend, "piv_lookup") or not getattr(backend, "keep_planes", True):
+            raise ValueError("use_piv needs a backend with the reference-channel planes (GpuFrameBackend(keep_planes=True))")
     if drifts is None:
         drifts = np.zeros((n_frames, 2))
     drifts = np.array(drifts, dtype=np.float64)
@@ -369,10 +416,11 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
             worker = threading.Thread(target=compute, args=(rounds[k + 1], results[k + 1]))
             worker.start()
         lo, hi = k * per_round, min(n_frames, (k + 1) * per_round)
-        if estimate_drift:
+        if estimate_drift or use_piv:
             sends = [t for t in mine if t + 1 < n_frames]
             recvs = [t for t in range(lo, hi) if t % world == (rank - 1) % world and t + 1 < n_frames]
             held_planes.update(exchange_planes(n_frames, sends, recvs, backend, rank, world, dist))
+        if estimate_drift:
             for t in mine:
                 if t >= 1:
                     drifts[t] = backend.drift(t, held_planes.pop(t))
@@ -399,16 +447,33 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
         if stitcher == "linker":
             continue
         # 2. owners look the previous frame's centroids up in their resident label maps
-        my_lookups = {}
+        my_lookups, failed, error = {}, (-1, 0), None
         for t in mine:
             if t == 0:
                 continue
             prev = tables[t - 1]
-            cy = prev["cy"] - tables[t]["drift"][0]
-            cx = prev["cx"] - tables[t]["drift"][1]
-            qy, qx = np.round(cy).astype(np.int64), np.round(cx).astype(np.int64)
-            res = backend.lookup(t, qy, qx)
+            if use_piv:
+                try:
+                    res = backend.piv_lookup(t, held_planes.pop(t), prev)
+                except Exception as e:            # the round's collectives still run: every rank learns of it below
+                    failed, error = (t, 1 if isinstance(e, IndexError) else 2), e
+                    break
+            else:
+                cy = prev["cy"] - tables[t]["drift"][0]
+                cx = prev["cx"] - tables[t]["drift"][1]
+                qy, qx = np.round(cy).astype(np.int64), np.round(cx).astype(np.int64)
+                res = backend.lookup(t, qy, qx)
             my_lookups[t] = np.where(prev["area"] > 0, res, -1)   # absent rows never match (empty_cell / zero-area rows)
+        if use_piv:
+            first = _first_piv_failure(failed, rank, world, dist, device)
+            if first is not None:
+                worker.join()                     # (round k+1's frames: nothing is left running)
+                t_bad, kind, owner = first
+                if owner == rank and t_bad == failed[0]:
+                    raise error
+                if kind == 1:
+                    raise IndexError("use_piv: frame %d's flow sampling is out of bounds on rank %d" % (t_bad, owner))
+                raise RuntimeError("use_piv: frame %d's PIV look-up failed on rank %d" % (t_bad, owner))
         # 3. gather to rank 0
         if world > 1:
             flat = []
