@@ -287,6 +287,17 @@ TIP_API int tip_neighbor_pairs_i32_dev(const int32_t *labels, int y, int x, int3
 /* and the statistic is taken over the whole frame (np.percentile(img, 99), ti.py:2371).                               */
 TIP_API int tip_label_order_stats_f64(const int32_t *labels, const double *img, int y, int x, int nlab, const int64_t *ranks,
                                       double *lo, double *hi);
+/* calc_cell_types (ti.py:2338-2408) of one frame on DEVICE buffers, asynchronous on the calling thread's stream: labels     */
+/* (int32) 1..n and the marker plane (float64, same orientation).  Per row l = label - 1 (n rows): out_type = 1 << type_index */
+/* when np.percentile(marker[cell], 100 * q_over_100) > threshold * np.percentile(marker, 99) (and, peak_window_size > 0,   */
+/* the cell holds a local maximum of the sigma-7 blur under maximum_filter(size=peak_window_size); label 1 never does), else */
+/* 0; out_valid = min_cell_area * mean(area) < area < max_cell_area * mean(area) over all n rows; out_mean = intensity mean */
+/* (NaN for absent labels).  out_type_map (uint8, y x x): the row's type where valid, 255 elsewhere and on label 0.          */
+/* peak_taps: scipy's sigma-7 Gaussian taps (host array, read during the call), used when peak_window_size > 0.             */
+TIP_API int tip_cell_types_i32_dev(const int32_t *labels, const double *marker, int y, int x, int n, double q_over_100,
+                                   double threshold, int peak_window_size, const double *peak_taps, int n_peak_taps,
+                                   int type_index, double min_cell_area, double max_cell_area, uint8_t *out_type,
+                                   uint8_t *out_valid, double *out_mean, uint8_t *out_type_map);
 /* Contact lengths (ti.py:1844-1872, 4073-4094): for every ordered label pair (hi > lo >= 1) the number of pixels whose  */
 /* 4-neighbour maximum of the labels is hi and whose 4-neighbour minimum of the labels with zeros replaced by `big`    */
 /* (= max label + 1, ti.py:4081) is lo; filters as scipy's with the cross footprint and mode='constant'.  pairs: (hi, */

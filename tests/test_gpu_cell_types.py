@@ -1,0 +1,232 @@
+"""GPU: cell typing on the device (tip_cell_types_i32_dev, FramePipeline.cell_types, GpuFrameBackend(cell_types=...)) equals
+Tissue.calc_cell_types on a fresh table (the mixin, golden-pinned in test_gpu_segmentation.py), and the sharded movie driver
+carries the types without touching the tracks."""
+import os
+import socket
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def mixin_types(labels, marker, threshold, percentage, window, min_cell_area=0.1, max_cell_area=10):
+    """set_labels + calculate_frame_cellinfo + calc_cell_types("HC") on a fresh Tissue -> (type, valid, mean, type map)."""
+    from tissue_image_processing_amd import tissue_info as ti
+    t = ti.Tissue(1, max_cell_area=max_cell_area, min_cell_area=min_cell_area)
+    t.set_labels(1, np.asarray(labels).copy(), reset_data=True)
+    t.calculate_frame_cellinfo(1)
+    t.calc_cell_types(marker, 1, "HC", threshold, percentage, window)
+    ci = t.get_cells_info(1)
+    return (ci["type"].to_numpy().astype(np.uint8), ci["valid"].to_numpy().astype(np.uint8),
+            ci["mean_intensity_HC"].to_numpy().astype(np.float64), np.asarray(t.get_cell_types(1)))
+
+
+def device_types(labels, marker, threshold, percentage, window, type_index=0, min_cell_area=0.1, max_cell_area=10, n=None):
+    """The entry on uploaded copies of labels / marker -> (type, valid, mean, type map)."""
+    from tissue_image_processing_amd import _lib, _segmentation as seg
+    from tissue_image_processing_amd.basic_image_manipulations import gaussian_taps
+    lab = np.ascontiguousarray(labels, np.int32)
+    mk = np.ascontiguousarray(marker, np.float64)
+    Y, X = lab.shape
+    n = int(lab.max()) if n is None else n
+    d_lab = _lib.DeviceBuffer(lab.nbytes).upload(lab)
+    d_mk = _lib.DeviceBuffer(mk.nbytes).upload(mk)
+    d_rows = _lib.DeviceBuffer(10 * max(n, 1))
+    d_map = _lib.DeviceBuffer(Y * X)
+    seg.cell_types_dev(d_lab.ptr, d_mk.ptr, Y, X, n, percentage, threshold, window, gaussian_taps(7.0), type_index,
+                       min_cell_area, max_cell_area, d_rows.ptr + 8 * n, d_rows.ptr + 9 * n, d_rows.ptr, d_map.ptr)
+    blob = d_rows.download((10 * n,), np.uint8)
+    return blob[8 * n:9 * n].copy(), blob[9 * n:].copy(), blob[:8 * n].view(np.float64), d_map.download((Y, X), np.uint8)
+
+
+def assert_same_types(got, want):
+    typ, valid, mean, tmap = got
+    wtyp, wvalid, wmean, wmap = want
+    np.testing.assert_array_equal(typ, wtyp)
+    np.testing.assert_array_equal(valid, wvalid)
+    np.testing.assert_allclose(mean, wmean, rtol=1e-12)          # (float64 atomics in the intensity sums; NaN where absent)
+    assert np.array_equal(np.isnan(mean), np.isnan(wmean))
+    np.testing.assert_array_equal(tmap, wmap)
+
+
+def random_frame(seed, Y=120, X=150):
+    """Blocky cells (absent labels, single-pixel labels, background) and a marker with a smooth part, integer ties,
+    negative values and -0.0 patches."""
+    rng = np.random.default_rng(seed)
+    coarse = rng.integers(1, 160, (Y // 6 + 1, X // 6 + 1))
+    lab = np.kron(coarse, np.ones((6, 6), np.int64))[:Y, :X].astype(np.int32)
+    lab[rng.random(lab.shape) < 0.05] = 0                          # background specks
+    lab[lab == 17] = 0                                             # label 17 absent
+    lab[lab == 42] = 0                                             # ... and 42
+    for k, (y, x) in enumerate(((3, 4), (50, 60), (Y - 1, X - 1))):
+        lab[y, x] = 170 + k                                        # single-pixel labels
+    smooth = np.kron(rng.normal(0, 30, (Y // 10 + 1, X // 10 + 1)), np.ones((10, 10)))[:Y, :X]
+    marker = np.round(smooth + rng.normal(0, 5, (Y, X)))          # integers: heavy ties, both signs
+    marker[10:30, 20:70] = -0.0
+    marker[lab == 0] = 0.0
+    return lab, marker
+
+
+def test_entry_equals_mixin_on_golden(golden):
+    g = golden("celltypes")
+    lab, inten = g["labels"], g["intensity"]
+    for thr, pct, win in ((0.5, 90, 0), (0.03, 3, 3), (0.1, 90, 7)):
+        assert_same_types(device_types(lab, inten, thr, pct, win), mixin_types(lab, inten, thr, pct, win))
+    # the C5 golden itself: positives are the cells whose 10th percentile exceeds 0.5 x p99
+    typ = device_types(lab, inten, 0.5, 90, 0)[0]
+    np.testing.assert_array_equal(typ == 1, g["p10"] > 0.5 * g["p99"])
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_entry_equals_mixin_grid(seed):
+    lab, marker = random_frame(seed)
+    seen = set()
+    for thr in (0.03, 0.5):
+        for pct in (3, 90):
+            for win in (0, 3, 7):
+                got = device_types(lab, marker, thr, pct, win)
+                assert_same_types(got, mixin_types(lab, marker, thr, pct, win))
+                seen.update(np.unique(got[0]).tolist())
+    assert seen == {0, 1}                                          # both outcomes occur in the grid
+
+
+def test_label_one_never_holds_a_peak():
+    """Upstream drops row 0 from the labels with a local maximum (ti.py:2377): label 1, the brightest cell and the one
+    holding the frame's maximum, is positive without the peak test and negative with it."""
+    from tissue_image_processing_amd import tissue_info as ti
+    lab, marker = random_frame(5)
+    lab[lab == 1] = 0
+    lab[40:80, 50:100] = 1
+    yy, xx = np.mgrid[:lab.shape[0], :lab.shape[1]]
+    marker = marker + 500.0 * np.exp(-((yy - 60.0) ** 2 + (xx - 75.0) ** 2) / 2000.0)
+    assert ti.find_local_maxima(marker, window_size=3)[lab == 1].any()
+    for win in (0, 3):
+        got, want = device_types(lab, marker, 0.03, 90, win), mixin_types(lab, marker, 0.03, 90, win)
+        assert_same_types(got, want)
+        assert got[0][0] == (1 if win == 0 else 0)
+
+
+def test_entry_options_and_arguments():
+    lab, marker = random_frame(3)
+    got = device_types(lab, marker, 0.5, 90, 3, type_index=2, min_cell_area=0.5, max_cell_area=2)
+    want = mixin_types(lab, marker, 0.5, 90, 3, min_cell_area=0.5, max_cell_area=2)
+    assert_same_types((got[0] >> 2,) + got[1:3] + (np.where(got[3] == 255, 255, got[3] >> 2),), want)
+    assert set(np.unique(got[0]).tolist()) <= {0, 4}
+    empty = device_types(np.zeros_like(lab), marker, 0.5, 90, 0, n=0)
+    assert (empty[3] == 255).all()
+    with pytest.raises(ValueError):
+        device_types(lab, marker, 0.5, 120, 0)                     # percentile -20
+    with pytest.raises(ValueError):
+        device_types(lab, marker, 0.5, 90, 0, type_index=8)
+    with pytest.raises(ValueError):
+        device_types(lab, marker, 0.5, 90, 40)                     # window above the rank filter's 31
+
+
+def _hc_of_labels(labels, sites, is_hc):
+    """Per label: the generator's is_hc of the site that owns most of its pixels."""
+    from tissue_image_processing_amd import synthetic
+    _, _, owner = synthetic._two_nearest(sites, *labels.shape)
+    n = int(labels.max())
+    votes = np.bincount(labels.ravel(), weights=is_hc[owner].ravel().astype(np.float64), minlength=n + 1)[1:]
+    area = np.bincount(labels.ravel(), minlength=n + 1)[1:]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return votes / area > 0.5
+
+
+def test_frame_pipeline_equals_mixin():
+    from tissue_image_processing_amd import synthetic
+    from tissue_image_processing_amd.pipeline import FramePipeline
+    Z, Y, X = 8, 192, 256
+    sites, is_hc = synthetic.make_sites(Y, X, 21)
+    stack = synthetic.make_stack(Z, Y, X, seed=21, sites=sites, is_hc=is_hc)
+    pipe = FramePipeline(2, Z, Y, X, reference_channel=0, airyscan=False)
+    d = pipe.upload_stack(stack)
+    pipe.project(d)
+    pipe.segment(0)
+    n = pipe.cell_tables()["area"].size
+    labels, marker = pipe.fetch_labels(), pipe.fetch_projection()[0][1]
+    assert n == int(labels.max())
+    for thr, pct, win in ((0.1, 90, 0), (0.03, 3, 3)):
+        rows = pipe.cell_types(atoh_channel=1, threshold=thr, percentage_above_threshold=pct, peak_window_size=win)
+        got = (rows["type"], rows["valid"], rows["mean_intensity"], pipe.fetch_cell_types())
+        assert_same_types(got, mixin_types(labels, marker, thr, pct, win))
+    rows = pipe.cell_types(threshold=0.1, percentage_above_threshold=90)
+    sel = rows["valid"] == 1
+    agree = np.mean((rows["type"][sel] == 1) == _hc_of_labels(labels, sites, is_hc)[sel])
+    print("valid cells typed as the generator's HC / SC: %.3f of %d" % (agree, sel.sum()))
+    assert agree > 0.8
+
+
+def _movie(T=5, Z=6, Y=128, X=160):
+    from tissue_image_processing_amd import synthetic
+    sites_t, is_hc = synthetic.make_movie_sites(Y, X, T, seed=9)
+    return [synthetic.make_stack(Z, Y, X, seed=90 + t, sites=sites_t[t], is_hc=is_hc) for t in range(T)], (Z, Y, X)
+
+
+@pytest.mark.parametrize("inflight", [1, 3])
+def test_process_movie_types_equal_mixin(inflight):
+    from tissue_image_processing_amd import movie
+    from tissue_image_processing_amd.pipeline import FramePipeline
+    stacks, (Z, Y, X) = _movie()
+    T = len(stacks)
+    opts = dict(atoh_channel=1, threshold=0.03, percentage_above_threshold=3, peak_window_size=3)
+    drifts = np.zeros((T, 2))
+    drifts[1:] = (-0.5, 0.3)
+    plain = movie.GpuFrameBackend(2, Z, Y, X, device=0, inflight=inflight)
+    tabs_plain, ids_plain = movie.process_movie(T, lambda t: stacks[t], plain, 0, 1, None, "cpu", drifts)
+    plain.close()
+    typed = movie.GpuFrameBackend(2, Z, Y, X, device=0, inflight=inflight, cell_types=opts)
+    tabs, ids = movie.process_movie(T, lambda t: stacks[t], typed, 0, 1, None, "cpu", drifts)
+    pipe = FramePipeline(2, Z, Y, X, reference_channel=0, airyscan=False)
+    for t in range(T):
+        np.testing.assert_array_equal(ids[t], ids_plain[t])
+        labels = typed.labels[t].download((Y, X), np.int32)
+        d = pipe.upload_stack(stacks[t])
+        pipe.project(d)
+        marker = pipe.fetch_projection()[0][1]
+        want = mixin_types(labels, marker, 0.03, 3, 3)
+        assert_same_types((tabs[t]["type"], tabs[t]["valid"], tabs[t]["mean_intensity"], typed.fetch_cell_types(t)), want)
+        assert tabs[t]["type"].dtype == np.uint8 and tabs[t]["valid"].dtype == np.uint8
+        assert sorted(tabs_plain[t]) == ["area", "cx", "cy", "drift"]
+        np.testing.assert_array_equal(tabs[t]["area"], tabs_plain[t]["area"])
+    typed.close()
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _run(world, out):
+    port = _free_port()
+    procs = []
+    for r in range(world):
+        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                   LOCAL_RANK="0")
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_gpu_movie_celltypes_worker.py"), out],
+                                      env=env))
+    for p in procs:
+        assert p.wait(timeout=600) == 0
+
+
+def test_two_processes_equal_one(tmp_path):
+    o1, o2 = str(tmp_path / "w1.npz"), str(tmp_path / "w2.npz")
+    _run(1, o1)
+    _run(2, o2)
+    a, b = np.load(o1), np.load(o2)
+    maps1 = np.load(o1 + ".rank0.npz")
+    maps2 = dict(np.load(o2 + ".rank0.npz"))
+    maps2.update(np.load(o2 + ".rank1.npz"))
+    T = int(a["n"])
+    for t in range(T):
+        for k in ("ids", "area", "type", "valid"):
+            np.testing.assert_array_equal(a["%s_%d" % (k, t)], b["%s_%d" % (k, t)])
+        np.testing.assert_allclose(a["mean_intensity_%d" % t], b["mean_intensity_%d" % t], rtol=1e-12)
+        np.testing.assert_array_equal(maps1["map_%d" % t], maps2["map_%d" % t])

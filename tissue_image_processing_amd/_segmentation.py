@@ -234,3 +234,17 @@ def percentile_frame(img, q):
     lo, hi = label_order_stats(None, img.reshape(1, -1) if img.ndim != 2 else img, 1, np.array([prev], np.int64))
     hi = hi if prev + 1 <= n - 1 else lo
     return float(_lerp_percentile(lo, hi, gamma)[0])
+
+
+def cell_types_dev(labels_ptr, marker_ptr, y, x, n, percentage_above_threshold, threshold, peak_window_size, peak_taps,
+                   type_index, min_cell_area, max_cell_area, out_type_ptr, out_valid_ptr, out_mean_ptr, out_type_map_ptr):
+    """calc_cell_types of one frame on device buffers (tip_cell_types_i32_dev), asynchronous on the calling thread's stream.
+    Pointers are device addresses: labels int32 (y, x) 1..n, marker float64 (y, x); per row (n) type / valid uint8 and mean
+    float64, and the uint8 (y, x) type map.  peak_taps: the sigma-7 taps (host float64 array) when peak_window_size > 0."""
+    taps = None if not peak_window_size else np.ascontiguousarray(peak_taps, dtype=np.float64)
+    q_over_100 = (100 - percentage_above_threshold) / 100.0      # percentile_per_label's q / 100.0, q = 100 - p
+    _lib.check(_lib.lib().tip_cell_types_i32_dev(
+        _lib.dptr(labels_ptr), _lib.dptr(marker_ptr), int(y), int(x), int(n), ctypes.c_double(q_over_100),
+        ctypes.c_double(threshold), int(peak_window_size), _lib.ptr(taps), 0 if taps is None else int(taps.size), int(type_index),
+        ctypes.c_double(min_cell_area), ctypes.c_double(max_cell_area), _lib.dptr(out_type_ptr or 0), _lib.dptr(out_valid_ptr or 0),
+        _lib.dptr(out_mean_ptr or 0), _lib.dptr(out_type_map_ptr)))

@@ -6,7 +6,8 @@
 //   every label is found digit by digit: 8 passes over the pixels, each histogramming one byte of the keys that still
 //   match the label's prefix (256 bins per label), each followed by a per-label pick of the bin that holds rank k.  The
 //   (k+1)-th statistic is the same key when that key occurs often enough, else the smallest larger key (one more pass).
-//   The interpolation stays on the host (numpy's arithmetic, a few thousand values).
+//   The interpolation stays on the host (numpy's arithmetic, a few thousand values) behind tip_label_order_stats_f64;
+//   tip_celltypes.hip runs the same select on device-resident ranks (order_stats_dev) and interpolates on the device.
 #include "tip_internal.h"
 
 namespace tip {
@@ -115,8 +116,38 @@ __global__ void __launch_bounds__(256) k_sel_emit(const unsigned long long *__re
     hi[l] = room[l] > 0 ? a : (above[l] == ~0ULL ? a : sel_dec(above[l]));
 }
 
+// The select on device-resident ranks, asynchronous on the context stream: rank[l] (consumed: it ends as the rank inside the
+// selected key) and rank0[l] (kept) hold the 0-based rank asked of label l + 1, < 0 for an absent label; lo / hi are device
+// arrays of nlab values (see label_order_stats_dev).  labels == nullptr: nlab must be 1 (the whole frame).
+int order_stats_dev(const int32_t *labels, const double *img, long n, int nlab, long long *rank, const long long *rank0, double *lo,
+                    double *hi)
+{
+    if (!img || !rank || !rank0 || !lo || !hi || n < 1 || nlab < 1) return fail(TIP_ERR_ARG, "order_stats: bad arguments");
+    if (!labels && nlab != 1) return fail(TIP_ERR_ARG, "order_stats: whole-frame mode takes one rank");
+    WsGuard ws;
+    unsigned int *hist = ws.get<unsigned int>((size_t)nlab * 256);
+    unsigned long long *prefix = ws.get<unsigned long long>(nlab), *above = ws.get<unsigned long long>(nlab);
+    long long *room = ws.get<long long>(nlab);
+    if (!hist || !prefix || !above || !room) return TIP_ERR_NOMEM;
+    hipStream_t s = ctx().stream;
+    TIP_HIP(hipMemsetAsync(hist, 0, (size_t)nlab * 256 * 4, s));
+    TIP_HIP(hipMemsetAsync(prefix, 0, (size_t)nlab * 8, s));
+    TIP_HIP(hipMemsetAsync(above, 0xff, (size_t)nlab * 8, s));
+    TIP_HIP(hipMemsetAsync(room, 0, (size_t)nlab * 8, s));
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        TIP_LAUNCH("sel_hist", k_sel_hist, dim3(cdiv(n, 256 * 8)), dim3(256), 0, labels, img, n, nlab, (const unsigned long long *)prefix, shift,
+                   hist);
+        TIP_LAUNCH("sel_pick", k_sel_pick, dim3(cdiv(nlab, 256)), dim3(256), 0, hist, rank, prefix, shift, nlab, room);
+    }
+    TIP_LAUNCH("sel_next", k_sel_next, dim3(cdiv(n, 256)), dim3(256), 0, labels, img, n, nlab, (const unsigned long long *)prefix, above);
+    TIP_LAUNCH("sel_emit", k_sel_emit, dim3(cdiv(nlab, 256)), dim3(256), 0, (const unsigned long long *)prefix, (const unsigned long long *)above,
+               (const long long *)room, rank0, nlab, lo, hi);
+    return TIP_OK;
+}
+
 // lo[l] = value of rank ranks[l] (0-based) among the pixels of label l + 1, hi[l] = value of rank ranks[l] + 1 (= lo when
-// there is none); ranks[l] < 0: label absent.  labels == nullptr: nlab must be 1 (the whole frame).
+// there is none); ranks[l] < 0: label absent.  labels == nullptr: nlab must be 1 (the whole frame).  Host ranks in, host
+// values out (synchronises).
 int label_order_stats_dev(const int32_t *labels, const double *img, long n, int nlab, const long long *ranks_host, double *lo_host,
                           double *hi_host)
 {
@@ -125,26 +156,14 @@ int label_order_stats_dev(const int32_t *labels, const double *img, long n, int 
     if (!img || !ranks_host || !lo_host || !hi_host || n < 1 || nlab < 1) return fail(TIP_ERR_ARG, "order_stats: bad arguments");
     if (!labels && nlab != 1) return fail(TIP_ERR_ARG, "order_stats: whole-frame mode takes one rank");
     WsGuard ws;
-    unsigned int *hist = ws.get<unsigned int>((size_t)nlab * 256);
-    unsigned long long *prefix = ws.get<unsigned long long>(nlab), *above = ws.get<unsigned long long>(nlab);
-    long long *rank = ws.get<long long>(nlab), *rank0 = ws.get<long long>(nlab), *room = ws.get<long long>(nlab);
+    long long *rank = ws.get<long long>(nlab), *rank0 = ws.get<long long>(nlab);
     double *lo = ws.get<double>(nlab), *hi = ws.get<double>(nlab);
-    if (!hist || !prefix || !above || !rank || !rank0 || !room || !lo || !hi) return TIP_ERR_NOMEM;
+    if (!rank || !rank0 || !lo || !hi) return TIP_ERR_NOMEM;
     hipStream_t s = c.stream;
-    TIP_HIP(hipMemsetAsync(hist, 0, (size_t)nlab * 256 * 4, s));
-    TIP_HIP(hipMemsetAsync(prefix, 0, (size_t)nlab * 8, s));
-    TIP_HIP(hipMemsetAsync(above, 0xff, (size_t)nlab * 8, s));
-    TIP_HIP(hipMemsetAsync(room, 0, (size_t)nlab * 8, s));
     TIP_HIP(hipMemcpyAsync(rank, ranks_host, (size_t)nlab * 8, hipMemcpyHostToDevice, s));
     TIP_HIP(hipMemcpyAsync(rank0, ranks_host, (size_t)nlab * 8, hipMemcpyHostToDevice, s));
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        TIP_LAUNCH("sel_hist", k_sel_hist, dim3(cdiv(n, 256 * 8)), dim3(256), 0, labels, img, n, nlab, (const unsigned long long *)prefix, shift,
-                   hist);
-        TIP_LAUNCH("sel_pick", k_sel_pick, dim3(cdiv(nlab, 256)), dim3(256), 0, hist, rank, prefix, shift, nlab, room);
-    }
-    TIP_LAUNCH("sel_next", k_sel_next, dim3(cdiv(n, 256)), dim3(256), 0, labels, img, n, nlab, (const unsigned long long *)prefix, above);
-    TIP_LAUNCH("sel_emit", k_sel_emit, dim3(cdiv(nlab, 256)), dim3(256), 0, (const unsigned long long *)prefix, (const unsigned long long *)above,
-               (const long long *)room, (const long long *)rank0, nlab, lo, hi);
+    const int rc = order_stats_dev(labels, img, n, nlab, rank, rank0, lo, hi);
+    if (rc) return rc;
     TIP_HIP(hipMemcpyAsync(lo_host, lo, (size_t)nlab * 8, hipMemcpyDeviceToHost, s));
     TIP_HIP(hipMemcpyAsync(hi_host, hi, (size_t)nlab * 8, hipMemcpyDeviceToHost, s));
     TIP_HIP(hipStreamSynchronize(s));

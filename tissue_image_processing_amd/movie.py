@@ -20,6 +20,11 @@ runs the TV-L1 flow from frame t-1's plane to its own (both truncated to uint16 
 it at frame t-1's centroids with upstream's transposed indexing and looks the moved centroids up in its label map -- one
 device call per frame (tip_piv_lookup_max3_i32_dev), the flow never leaves the GPU.  Drifts are not written.
 
+With `GpuFrameBackend(cell_types=...)` the owner of frame t also classifies its cells as calc_cell_types does (ti.py:2338-2408)
+on the resident labels and Atoh-channel projection (one device call, tip_cell_types_i32_dev): the per-row columns type, valid
+and mean_intensity, named in the backend's `extra_columns`, travel with the centroid tables, and the type map stays on the
+owner GPU next to the label map.
+
 `backend` supplies the per-frame compute so the same driver runs on GPUs (GpuFrameBackend) and, for the
 multi-process CPU tests, on a stand-in backend with the gloo process group.
 """
@@ -93,10 +98,22 @@ class GpuFrameBackend(object):
     frame: the int32 label map (tracker look-ups) and, when drift is estimated, the reference channel's projection plane
     -- both kept with device-to-device copies.  The planes are torch tensors so that RCCL can send them as they are."""
 
-    def __init__(self, C, Z, Y, X, device=None, keep_planes=False, inflight=1, **kw):
+    CELL_TYPE_COLUMNS = (("type", np.uint8), ("valid", np.uint8), ("mean_intensity", np.float64))
+    CELL_TYPE_OPTIONS = ("atoh_channel", "threshold", "percentage_above_threshold", "peak_window_size", "type_index",
+                         "min_cell_area", "max_cell_area")
+
+    def __init__(self, C, Z, Y, X, device=None, keep_planes=False, inflight=1, cell_types=None, **kw):
         from .pipeline import FramePipeline
         from . import _lib
         self._shape, self._kw = (C, Z, Y, X), kw
+        # cell_types: None, or FramePipeline.cell_types' keyword arguments (atoh_channel, threshold, percentage_above_threshold,
+        # peak_window_size, type_index, min_cell_area, max_cell_area) -- every frame is then typed on the device after its
+        # cell tables, its dict gains the per-row columns below and its type map stays resident (fetch_cell_types)
+        self.cell_types = None if cell_types is None else dict(cell_types)
+        unknown = set(self.cell_types or ()) - set(self.CELL_TYPE_OPTIONS)
+        if unknown:
+            raise ValueError("cell_types: unknown option(s) %s (known: %s)" % (sorted(unknown), ", ".join(self.CELL_TYPE_OPTIONS)))
+        self.extra_columns = self.CELL_TYPE_COLUMNS if cell_types is not None else ()
         self.device = device
         self.pipe = FramePipeline(C, Z, Y, X, device=device, **kw)
         if device is None:
@@ -106,6 +123,7 @@ class GpuFrameBackend(object):
         self.inflight = max(1, int(inflight))
         self.labels = {}   # frame -> DeviceBuffer (int32 label map)
         self.planes = {}   # frame -> torch tensor (Y, X) float64 on this GPU
+        self.type_maps = {}   # frame -> DeviceBuffer (uint8 type map), with cell_types
         self._workers = []  # persistent worker threads (process_frames)
 
     def process_frame(self, t, stack_u16):
@@ -179,7 +197,16 @@ class GpuFrameBackend(object):
         with np.errstate(invalid="ignore", divide="ignore"):
             cy = tab["sumy"] / area
             cx = tab["sumx"] / area
-        return dict(area=tab["area"], cy=np.where(area > 0, cy, 0.0), cx=np.where(area > 0, cx, 0.0))
+        out = dict(area=tab["area"], cy=np.where(area > 0, cy, 0.0), cx=np.where(area > 0, cx, 0.0))
+        if self.cell_types is not None:
+            tmap = _lib.DeviceBuffer(self.Y * self.X)      # the frame's type map is painted straight into its own buffer
+            out.update(p.cell_types(n=tab["area"].size, type_map_ptr=tmap.ptr, **self.cell_types))   # (synchronises)
+            self.type_maps[t] = tmap
+        return out
+
+    def fetch_cell_types(self, t):
+        """Frame t's type map (uint8 (Y, X): a valid cell's type, 255 on invalid cells and label 0), downloaded."""
+        return self.type_maps[t].download((self.Y, self.X), np.uint8)
 
     def lookup(self, t, qy, qx):
         from . import _lib
@@ -358,7 +385,9 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
                   estimate_drift=False, stitcher="lookup", block_frames=None, use_piv=False):
     """Runs the sharded pipeline.  frame_source(t) -> uint16 stack (or whatever backend.process_frame takes).
     Returns on rank 0: (tables per frame, track ids per frame); on other ranks (None, None).  tables[t]["drift"] holds
-    the (row, column) drift used between frames t-1 and t (estimated by frame t's owner when estimate_drift).
+    the (row, column) drift used between frames t-1 and t (estimated by frame t's owner when estimate_drift).  A backend
+    with `extra_columns` ((name, dtype) pairs, e.g. GpuFrameBackend(cell_types=...)'s type / valid / mean_intensity) has
+    those per-row columns carried to rank 0's tables too, at any world size; without them the exchange is unchanged.
 
     use_piv=True: the tracker's PIV mode (Tissue.track_cells_iterator(use_piv=True), ti.py:2061-2106).  Planes are exchanged
     as for estimate_drift, and the owner of frame t >= 1 calls backend.piv_lookup(t, plane of frame t-1, table of frame t-1)
@@ -388,6 +417,7 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
     if drifts is None:
         drifts = np.zeros((n_frames, 2))
     drifts = np.array(drifts, dtype=np.float64)
+    extra = tuple(getattr(backend, "extra_columns", ()))      # further per-row columns every frame's dict carries
     per_round = (int(block_frames) if block_frames else max(1, -(-n_frames // world))) * world
     n_rounds = max(1, -(-n_frames // per_round))
     rounds = [[t for t in range(k * per_round, min(n_frames, (k + 1) * per_round)) if t % world == rank] for k in range(n_rounds)]
@@ -433,6 +463,7 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
                 tb = local[t]
                 payload += [np.array([t, tb["area"].size, tb["drift"][0], tb["drift"][1]], np.float64),
                             tb["area"].astype(np.float64), tb["cy"], tb["cx"]]
+                payload += [np.asarray(tb[name], np.float64) for name, _ in extra]
             for flat in _all_gather_arrays(payload, dist, world, device):
                 pos = 0
                 while pos < flat.size:
@@ -442,6 +473,9 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
                     tables[t] = dict(area=flat[pos:pos + n].astype(np.int64), cy=flat[pos + n:pos + 2 * n],
                                      cx=flat[pos + 2 * n:pos + 3 * n], drift=drift_t)
                     pos += 3 * n
+                    for name, dtype in extra:
+                        tables[t][name] = flat[pos:pos + n].astype(dtype)
+                        pos += n
         else:
             tables.update({t: local[t] for t in mine})
         if stitcher == "linker":

@@ -116,6 +116,41 @@ class FramePipeline:
             pc=i64[7 * n:10 * n].reshape(n, 3), pairs=blob[80 * n:].view(np.int32).reshape(npair, 2))
         return self.tables
 
+    def cell_types(self, atoh_channel=1, threshold=0.1, percentage_above_threshold=90, peak_window_size=0, type_index=0,
+                   min_cell_area=0.1, max_cell_area=10, n=None, type_map_ptr=None):
+        """C5 (Tissue.calc_cell_types, ti.py:2338-2408, on a fresh table) on the resident label map with the resident projection
+        of `atoh_channel` as the marker: one device call (tip_cell_types_i32_dev).  The type map stays resident in
+        self.d_types (uint8 (Y, X): a valid cell's type, 255 elsewhere), or in the device buffer at type_map_ptr; the per-row
+        arrays over labels 1..n (n: the last watershed's label count by default) -- type (uint8, 1 << type_index or 0), valid
+        (uint8) and mean_intensity (float64, NaN for absent labels) -- come back in one copy, which also completes the map."""
+        if not 0 <= atoh_channel < self.C:
+            raise ValueError("atoh_channel %d: the projection has %d channels" % (atoh_channel, self.C))
+        P = self.Y * self.X
+        n = int(self.lib.tip_last_watershed_labels()) if n is None else int(n)
+        if type_map_ptr is None:
+            if getattr(self, "d_types", None) is None:
+                self.d_types = _lib.DeviceBuffer(P)
+            type_map_ptr = self.d_types.ptr
+        # ONE device block [mean n | type n | valid n] so that the rows come back in a single device-to-host copy
+        if getattr(self, "_ct", None) is None or self._ct[0] < n:
+            cap = max(1024, int(n * 1.5))
+            self._ct = (cap, _lib.DeviceBuffer(cap * 10))
+        d_rows = self._ct[1].ptr
+        if peak_window_size and getattr(self, "t7", None) is None:
+            self.t7 = gaussian_taps(7.0)           # find_local_maxima's blur (ti.py:141-144)
+        from ._segmentation import cell_types_dev
+        cell_types_dev(self.d_labels.ptr, self.d_proj.ptr + atoh_channel * P * 8, self.Y, self.X, n, percentage_above_threshold,
+                       threshold, peak_window_size, getattr(self, "t7", None), type_index, min_cell_area, max_cell_area,
+                       d_rows + 8 * n, d_rows + 9 * n, d_rows, type_map_ptr)
+        if n <= 0:
+            self.sync()
+            return dict(type=np.zeros(0, np.uint8), valid=np.zeros(0, np.uint8), mean_intensity=np.zeros(0, np.float64))
+        blob = self._ct[1].download((10 * n,), np.uint8)
+        return dict(type=blob[8 * n:9 * n].copy(), valid=blob[9 * n:].copy(), mean_intensity=blob[:8 * n].view(np.float64))
+
+    def fetch_cell_types(self):
+        return self.d_types.download((self.Y, self.X), np.uint8)
+
     def sync(self):
         _lib.check(self.lib.tip_sync())
 
