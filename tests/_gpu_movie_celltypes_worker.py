@@ -9,13 +9,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def main():
-    import torch.distributed as dist
+def run(out_path, rank, world, dist):
     from tissue_image_processing_amd import movie, synthetic
-    out_path = sys.argv[1]
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    if world > 1:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
     Z, Y, X, T = 6, 128, 160, 5
     sites_t, is_hc = synthetic.make_movie_sites(Y, X, T, seed=8)
     stacks = [synthetic.make_stack(Z, Y, X, seed=80 + t, sites=sites_t[t], is_hc=is_hc) for t in range(T)]
@@ -23,8 +18,7 @@ def main():
     backend = movie.GpuFrameBackend(2, Z, Y, X, device=0, inflight=2, cell_types=opts)
     drifts = np.zeros((T, 2))
     drifts[1:] = (-0.5, 0.3)
-    tabs, ids = movie.process_movie(T, lambda t: stacks[t], backend, rank, world, dist if world > 1 else None, "cpu", drifts,
-                                    block_frames=1)
+    tabs, ids = movie.process_movie(T, lambda t: stacks[t], backend, rank, world, dist, "cpu", drifts, block_frames=1)
     np.savez(out_path + ".rank%d.npz" % rank, **{"map_%d" % t: backend.fetch_cell_types(t) for t in backend.type_maps})
     backend.close()
     if rank == 0:
@@ -34,10 +28,9 @@ def main():
             for k in ("area", "type", "valid", "mean_intensity"):
                 out["%s_%d" % (k, t)] = tabs[t][k]
         np.savez(out_path, **out)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
-    main()
+    from gloo_launch import gloo_group
+    with gloo_group(single=False) as (rank, world, dist):
+        run(sys.argv[1], rank, world, dist)

@@ -42,34 +42,25 @@ def synthetic_movie(Y, X, T, Z=6, seed=7):
     return [synthetic.make_stack(Z, Y, X, seed=10 * seed + t, sites=sites_t[t], is_hc=is_hc) for t in range(T)]
 
 
-def main():
-    import torch.distributed as dist
+def run(out_path, mode, rank, world, dist):
     from tissue_image_processing_amd import movie
-    out_path, mode = sys.argv[1], sys.argv[2]
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    if world > 1:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    d = dist if world > 1 else None
     Z, T = 6, 4
     Y, X = (256, 256) if mode == "square" else (128, 256)      # non-square: rows < columns, cells right of row index 127
     stacks = synthetic_movie(Y, X, T, Z)
     backend = movie.GpuFrameBackend(2, Z, Y, X, device=0, keep_planes=True, inflight=2)
     try:
-        tabs, ids = movie.process_movie(T, lambda t: stacks[t], backend, rank, world, d, "cpu", block_frames=1, use_piv=True)
-    except IndexError as e:
-        with open("%s.rank%d.err" % (out_path, rank), "w") as f:
-            f.write(str(e))
+        tabs, ids = movie.process_movie(T, lambda t: stacks[t], backend, rank, world, dist, "cpu", block_frames=1, use_piv=True)
+    finally:
         backend.close()
-        if world > 1:
-            dist.destroy_process_group()
-        return
     if rank == 0:
         np.savez(out_path, n=T, **{"ids_%d" % t: ids[t] for t in range(T)}, **{"area_%d" % t: tabs[t]["area"] for t in range(T)})
-    backend.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
-    main()
+    from gloo_launch import gloo_group
+    try:
+        with gloo_group(single=False) as (rank, world, dist):
+            run(sys.argv[1], sys.argv[2], rank, world, dist)
+    except IndexError as e:      # (the group is gone by now, without a barrier)
+        with open("%s.rank%s.err" % (sys.argv[1], os.environ["RANK"]), "w") as f:
+            f.write(str(e))

@@ -1,108 +1,30 @@
-"""Worker for the gloo tests of movie.process_movie's per-row cell-type columns (CPU; the per-frame compute is numpy)."""
-import os
+"""Worker for the gloo tests of movie.process_movie's per-row cell-type columns (tests/test_movie_cell_types.py; CPU, the
+per-frame compute is _movie_worker's TypingBackend)."""
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-TYPE_COLUMNS = (("type", np.uint8), ("valid", np.uint8), ("mean_intensity", np.float64))
-
-
-def numpy_cell_types(labels, marker, threshold=0.1, percentage_above_threshold=90, type_index=0, min_cell_area=0.1,
-                     max_cell_area=10):
-    """calc_cell_types on a fresh table without the peak test, in plain numpy (np.percentile per label): per row 0..n-1
-    the type byte, the validity and the mean intensity."""
-    n = int(labels.max())
-    area = np.bincount(labels.ravel(), minlength=n + 1)[1:n + 1]
-    isum = np.bincount(labels.ravel(), weights=marker.ravel(), minlength=n + 1)[1:n + 1]
-    mean = np.mean(area)
-    valid = ((area > min_cell_area * mean) & (area < max_cell_area * mean)).astype(np.uint8)
-    cut = threshold * np.percentile(marker, 99)
-    typ = np.zeros(n, np.uint8)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        mean_intensity = np.where(area > 0, isum / area, np.nan)
-    for l in range(1, n + 1):
-        if area[l - 1] and np.percentile(marker[labels == l], 100 - percentage_above_threshold) > cut:
-            typ[l - 1] = 1 << type_index
-    return typ, valid, mean_intensity
-
-
-class TypingBackend(object):
-    """Stands in for GpuFrameBackend(cell_types=...) on CPU: frames are (label map, marker plane); with typed=False it
-    behaves as a backend without cell typing (no extra columns)."""
-
-    def __init__(self, typed):
-        self.labels = {}
-        self.extra_columns = TYPE_COLUMNS if typed else ()
-
-    def process_frame(self, t, frame):
-        labels, marker = frame
-        self.labels[t] = np.ascontiguousarray(labels, np.int32)
-        n = int(labels.max())
-        yy, xx = np.indices(labels.shape)
-        area = np.bincount(labels.ravel(), minlength=n + 1)[1:n + 1].astype(np.int64)
-        sy = np.bincount(labels.ravel(), weights=yy.ravel(), minlength=n + 1)[1:n + 1]
-        sx = np.bincount(labels.ravel(), weights=xx.ravel(), minlength=n + 1)[1:n + 1]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            out = dict(area=area, cy=np.where(area > 0, sy / area, 0.0), cx=np.where(area > 0, sx / area, 0.0))
-        if self.extra_columns:
-            out["type"], out["valid"], out["mean_intensity"] = numpy_cell_types(labels, marker, threshold=0.4)
-        return out
-
-    def lookup(self, t, qy, qx):
-        lab = self.labels[t]
-        Y, X = lab.shape
-        pad = np.pad(lab, 1)
-        mx = np.max([pad[dy:dy + Y, dx:dx + X] for dy in range(3) for dx in range(3)], axis=0)
-        ok = (qy >= 0) & (qy < Y) & (qx >= 0) & (qx < X)
-        out = np.full(qy.shape, -1, np.int32)
-        out[ok] = mx[qy[ok], qx[ok]]
-        return out
-
-
-def typed_movie(n_frames):
-    """The golden tracking frames cycled, with a marker plane per frame: integer values (ties), a few bright cells, one
-    label removed from every third frame (absent rows) and a single-pixel label."""
-    g = np.load(os.path.join(ROOT, "tests", "golden", "tracking.npz"))
-    labs = list(g["labels"])
-    rng = np.random.default_rng(11)
-    frames = []
-    for t in range(n_frames):
-        lab = labs[t % len(labs)].copy()
-        n = int(lab.max())
-        if t % 3 == 0:
-            lab[lab == 5] = 0
-        lab[0, 0] = n + 1
-        bright = rng.random(n + 2) < 0.3
-        marker = np.round(rng.normal(10, 3, lab.shape)) + np.where(bright[lab], 40.0, 0.0)
-        marker[lab == 0] = 0.0
-        frames.append((lab, marker))
-    return frames
+from _movie_worker import TypingBackend, typed_movie
+from gloo_launch import gloo_group
 
 
 def main():
-    import torch.distributed as dist
     from tissue_image_processing_amd import movie
     out_path, n_frames, block, typed = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     frames = typed_movie(n_frames)
     drifts = np.zeros((n_frames, 2))
     drifts[1:] = (0.5, -0.3)
-    tabs, ids = movie.process_movie(n_frames, lambda t: frames[t], TypingBackend(bool(typed)), rank, world, dist, "cpu", drifts,
-                                    block_frames=block or None)
-    if rank == 0:
-        out = dict(n=n_frames)
-        for t in range(n_frames):
-            out["ids_%d" % t] = ids[t]
-            out["keys_%d" % t] = np.array(sorted(tabs[t]))
-            for k, v in tabs[t].items():
-                out["%s_%d" % (k, t)] = v
-        np.savez(out_path, **out)
-    dist.barrier()
-    dist.destroy_process_group()
+    with gloo_group() as (rank, world, dist):
+        tabs, ids = movie.process_movie(n_frames, lambda t: frames[t], TypingBackend(bool(typed)), rank, world, dist, "cpu",
+                                        drifts, block_frames=block or None)
+        if rank == 0:
+            out = dict(n=n_frames)
+            for t in range(n_frames):
+                out["ids_%d" % t] = ids[t]
+                out["keys_%d" % t] = np.array(sorted(tabs[t]))
+                for k, v in tabs[t].items():
+                    out["%s_%d" % (k, t)] = v
+            np.savez(out_path, **out)
 
 
 if __name__ == "__main__":

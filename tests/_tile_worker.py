@@ -33,26 +33,19 @@ def test_stack():
     return synthetic.make_stack(6, 420, 500, seed=17)
 
 
-def main():
-    import torch.distributed as dist
+def run(out_path, rank, world, dist):
     from tissue_image_processing_amd import tiling
     from oracle import oracle as orc
-    out_path = sys.argv[1]
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    if world > 1:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
     st = test_stack()
     C, Z, Y, X = st.shape
     src = lambda a, b, c, d: st[:, :, a:b, c:d]
-    proj, zmap, labels = tiling.process_tiled_frame(src, C, Y, X, (2, 2), OracleTileBackend(), rank, world,
-                                                    dist if world > 1 else None, "cpu",
+    proj, zmap, labels = tiling.process_tiled_frame(src, C, Y, X, (2, 2), OracleTileBackend(), rank, world, dist, "cpu",
                                                     segment=lambda plane: orc.watershed_segmentation(plane, 0.03, 3, 3))
     if rank == 0:
         np.savez(out_path, proj=proj, zmap=zmap, labels=labels)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
-    main()
+    from gloo_launch import gloo_group
+    with gloo_group(single=False) as (rank, world, dist):
+        run(sys.argv[1], rank, world, dist)

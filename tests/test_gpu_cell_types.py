@@ -1,16 +1,12 @@
 """GPU: cell typing on the device (tip_cell_types_i32_dev, FramePipeline.cell_types, GpuFrameBackend(cell_types=...)) equals
 Tissue.calc_cell_types on a fresh table (the mixin, golden-pinned in test_gpu_segmentation.py), and the sharded movie driver
 carries the types without touching the tracks."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from gloo_launch import run_ranks
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def mixin_types(labels, marker, threshold, percentage, window, min_cell_area=0.1, max_cell_area=10):
@@ -196,24 +192,8 @@ def test_process_movie_types_equal_mixin(inflight):
     typed.close()
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _run(world, out):
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   LOCAL_RANK="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_gpu_movie_celltypes_worker.py"), out],
-                                      env=env))
-    for p in procs:
-        assert p.wait(timeout=600) == 0
+    run_ranks("_gpu_movie_celltypes_worker.py", world, (out,), timeout=600, local_rank="0")
 
 
 def test_two_processes_equal_one(tmp_path):

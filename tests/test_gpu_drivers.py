@@ -3,12 +3,11 @@ the REFERENCE's own functions over an in-memory stand-in for its absent reader /
 gold_drivers): projections, z-maps, uint16 TIFF contents, file names, stage records."""
 import os
 import pickle
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+from gloo_launch import run_ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -130,14 +129,8 @@ def test_movie_surface_projection(g, tmp_path):
 
 def test_drivers_sharded_over_two_processes(g, tmp_path):
     """Time points dealt to two processes (rank t % 2), outputs written by rank 0: identical files."""
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     odir = str(tmp_path)
-    procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), LOCAL_RANK="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_driver_worker.py"), odir], env=env))
-    for p in procs:
-        assert p.wait(timeout=600) == 0
+    run_ranks("_driver_worker.py", 2, (odir,), timeout=600, local_rank="0")
     _check_movie_outputs(g, odir, stage=False)
     from tissue_image_processing_amd import basic_image_manipulations as bim
     img, axes, _, _ = bim.read_tiff(os.path.join(odir, "bigt_projection.tif"))

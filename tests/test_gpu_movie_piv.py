@@ -1,12 +1,10 @@
 """GPU: the PIV step of the sharded movie tracker (csrc/tip_piv.hip, movie.process_movie(use_piv=True)).
 
-The sampling-and-lookup kernel against the numpy statement of upstream's steps (tests/_movie_piv_worker.piv_hits), the flow
+The sampling-and-lookup kernel against the numpy statement of upstream's steps (tests/_movie_worker.piv_hits), the flow
 inside the new entry against tip_optical_flow_tvl1 on the uint16-truncated planes (bit-identical), the driver on the
 reference's own use_piv run, on a synthetic square movie against Tissue.track_cells_iterator(use_piv=True), and two
 processes on one GPU against one."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +13,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from gloo_launch import run_ranks  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -54,7 +54,7 @@ def _rows(rng, Y, X, n):
 @pytest.mark.parametrize("quantized", [False, True])
 @pytest.mark.parametrize("shape", [(64, 64), (48, 80), (80, 48)])
 def test_sample_kernel_matches_numpy(reg, quantized, shape):
-    from _movie_piv_worker import piv_hits
+    from _movie_worker import piv_hits
     Y, X = shape
     rng = np.random.default_rng(5 + Y)
     flow = rng.uniform(-8, 8, (2, Y, X)).astype(np.float32)
@@ -79,7 +79,7 @@ def test_sample_kernel_matches_numpy(reg, quantized, shape):
     [(41, "cy", -64.5)],                           # a tie that rounds to -64: wraps, no error
 ])
 def test_sample_kernel_index_errors_as_numpy(reg, bad):
-    from _movie_piv_worker import piv_hits
+    from _movie_worker import piv_hits
     Y = X = 64
     rng = np.random.default_rng(2)
     flow = rng.uniform(-3, 3, (2, Y, X)).astype(np.float32)
@@ -104,7 +104,7 @@ def test_entry_flow_is_tvl1_on_truncated_planes(reg):
     """The flow inside tip_piv_lookup_max3_i32_dev is tip_optical_flow_tvl1 on the uint16-truncated planes, bit for bit; the
     hits are the numpy statement on that flow; n == 0 computes nothing and returns."""
     import torch
-    from _movie_piv_worker import golden_frames, piv_hits
+    from _movie_worker import golden_frames, piv_hits
     from oracle import oracle as orc
     (lab0, p0), (lab1, p1) = golden_frames()[:2]
     assert np.any(p0 != np.floor(p0))
@@ -138,7 +138,7 @@ def test_installed_golden_through_gpu_backend(reg, golden):
     """The driver with the device step on the reference's own use_piv run (label maps and float64 planes installed on the
     device, one process, rounds of one frame)."""
     from _gpu_movie_piv_worker import installed_backend_class
-    from _movie_piv_worker import golden_frames
+    from _movie_worker import golden_frames
     from tissue_image_processing_amd import movie
     g = golden("piv_tracking")
     frames = golden_frames()
@@ -179,30 +179,8 @@ def test_synthetic_square_movie_equals_tissue_tracker(reg):
         assert np.isin(ids[f], ids[f - 1]).mean() > 0.5
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _run(world, out, mode, timeout=600):
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   LOCAL_RANK="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_gpu_movie_piv_worker.py"), out, mode],
-                                      env=env))
-    try:
-        for p in procs:
-            assert p.wait(timeout=timeout) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait(timeout=30)
+    run_ranks("_gpu_movie_piv_worker.py", world, (out, mode), timeout=timeout, local_rank="0")
 
 
 def test_world2_equals_world1(tmp_path):

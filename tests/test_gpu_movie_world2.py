@@ -1,34 +1,15 @@
 """GPU: the frame-sharded movie driver with TWO processes (gloo collectives, both on GPU 0) equals the one-process run;
 and the watershed's fallback machinery (wide tile pass + global-minimum commits) gives the same labels as the endgame."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from gloo_launch import run_ranks
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _run(world, out):
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   LOCAL_RANK="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_gpu_movie_worker.py"), out], env=env))
-    for p in procs:
-        assert p.wait(timeout=600) == 0
+    run_ranks("_gpu_movie_worker.py", world, (out,), timeout=600, local_rank="0")
 
 
 def test_world2_equals_world1(tmp_path):

@@ -1,8 +1,6 @@
 """CPU (gloo): process_movie carries a backend's per-row cell-type columns (type, valid, mean_intensity) through the per-round
 all-gather, so rank 0's tables hold them at any world size; without them the tables are what they were."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -11,27 +9,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from gloo_launch import run_ranks  # noqa: E402
+
 BASE_KEYS = ["area", "cx", "cy", "drift"]
 TYPE_KEYS = ["mean_intensity", "type", "valid"]
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _run(world, out, n_frames, block=0, typed=1):
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_movie_celltypes_worker.py"), out,
-                                       str(n_frames), str(block), str(typed)], env=env))
-    for p in procs:
-        assert p.wait(timeout=300) == 0
+    run_ranks("_movie_celltypes_worker.py", world, (out, n_frames, block, typed), timeout=300)
     return np.load(out)
 
 
@@ -46,7 +31,7 @@ def _assert_same(a, b, n, keys):
 
 
 def test_world1_tables_hold_the_numpy_types():
-    from _movie_celltypes_worker import TypingBackend, numpy_cell_types, typed_movie
+    from _movie_worker import TypingBackend, numpy_cell_types, typed_movie
     from tissue_image_processing_amd import movie
     frames = typed_movie(4)
     tabs, _ = movie.process_movie(4, lambda t: frames[t], TypingBackend(True), 0, 1, None, "cpu")

@@ -1,9 +1,7 @@
 """movie.process_movie(use_piv=True) on CPU: the sharded driver's PIV mode with a numpy stand-in for the device step
-(tests/_movie_piv_worker.py), against the reference's own use_piv run (tests/golden/piv_tracking.npz), one process and
+(tests/_movie_worker.py), against the reference's own use_piv run (tests/golden/piv_tracking.npz), one process and
 gloo worlds of 2 and 4, the IndexError protocol and the rejected argument combinations."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -12,38 +10,18 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from gloo_launch import run_ranks  # noqa: E402
 
 
 def _run(world, out, mode="golden", block=0, timeout=300):
-    """Starts `world` gloo ranks of _movie_piv_worker.py; every rank must exit 0 within `timeout` (an IndexError is written
-    to out.rank<r>.err, not raised out of the process)."""
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_movie_piv_worker.py"), out, mode,
-                                       str(block)], env=env))
-    try:
-        for p in procs:
-            assert p.wait(timeout=timeout) == 0
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait(timeout=30)
+    """`world` gloo ranks of _movie_piv_worker.py (an IndexError is written to out.rank<r>.err, not raised out of the process)."""
+    run_ranks("_movie_piv_worker.py", world, (out, mode, block), timeout=timeout)
 
 
 def test_piv_hits_restatement_pins_the_transposed_sampling():
     """The numpy statement the stand-in and the GPU tests use: the ROW flow is read at (round(cx), round(cy)) and moves cx,
     the column flow moves cy; the moved point is looked up at (round(cy), round(cx)); absent rows give -1."""
-    from _movie_piv_worker import piv_hits
+    from _movie_worker import piv_hits
     flow = np.zeros((2, 8, 8), np.float32)
     flow[0, 2, 5] = -4.0            # at (row = round(cx) = 2, col = round(cy) = 5): cx 2 -> 6
     flow[1, 2, 5] = 4.0             # cy 5 -> 1
@@ -56,7 +34,7 @@ def test_piv_hits_restatement_pins_the_transposed_sampling():
 
 
 def test_single_process_matches_reference_use_piv(golden):
-    from _movie_piv_worker import PivOracleBackend, golden_frames
+    from _movie_worker import PivOracleBackend, golden_frames
     from tissue_image_processing_amd import movie
     g = golden("piv_tracking")
     frames = golden_frames()
@@ -82,7 +60,7 @@ def test_gloo_worlds_match_reference_use_piv(tmp_path, golden, world, block):
 
 
 def test_single_process_non_square_raises_index_error():
-    from _movie_piv_worker import PivOracleBackend, golden_frames
+    from _movie_worker import PivOracleBackend, golden_frames
     from tissue_image_processing_amd import movie
     frames = golden_frames(crop=True)
     with pytest.raises(IndexError, match="out of bounds for axis 0 with size 64"):
@@ -113,8 +91,7 @@ class _NoPlanes(object):
     (dict(), "no_planes"),          # keep_planes=False
 ])
 def test_rejected_combinations(kw, backend):
-    from _movie_worker import OracleBackend
-    from _movie_piv_worker import PivOracleBackend
+    from _movie_worker import OracleBackend, PivOracleBackend
     from tissue_image_processing_amd import movie
     b = {"piv": PivOracleBackend, "oracle": OracleBackend, "no_planes": _NoPlanes}[backend]()
     calls = []

@@ -1,7 +1,5 @@
 """Multi-process (gloo, world_size 2) test of the frame-sharded movie driver and its track stitching, on CPU."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -10,24 +8,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from gloo_launch import run_ranks  # noqa: E402
 
 
 def _run(world, out, n_rep=1, n_keep=0, block=0):
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_movie_worker.py"), out, str(n_rep), str(n_keep),
-                                       str(block)], env=env))
-    for p in procs:
-        assert p.wait(timeout=300) == 0
+    run_ranks("_movie_worker.py", world, (out, n_rep, n_keep, block), timeout=300)
 
 
 def test_frames_for_rank():

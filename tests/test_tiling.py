@@ -1,8 +1,6 @@
 """CPU: the spatial-tiling driver of config 5 (tiling.py) with the gloo process group and an oracle-backed stand-in:
 tiles + halo + a summed percentile histogram reproduce the untiled frame exactly, on 1 and on 2 ranks."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -10,23 +8,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from gloo_launch import run_ranks  # noqa: E402
 
 
 def _run(world, out):
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_tile_worker.py"), out], env=env))
-    for p in procs:
-        assert p.wait(timeout=600) == 0
+    run_ranks("_tile_worker.py", world, (out,), timeout=600)
 
 
 def test_tile_boxes_cover_the_plane_once():

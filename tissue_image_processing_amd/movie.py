@@ -32,6 +32,8 @@ import ctypes
 
 import numpy as np
 
+from ._collectives import gather_varlen
+
 
 class _Job(object):
     """One process_frames call: a shared frame iterator the workers pull from."""
@@ -96,7 +98,9 @@ class _FrameWorker(object):
 class GpuFrameBackend(object):
     """Per-frame compute on this rank's MI355X through FramePipeline.  What later stages need stays resident per owned
     frame: the int32 label map (tracker look-ups) and, when drift is estimated, the reference channel's projection plane
-    -- both kept with device-to-device copies.  The planes are torch tensors so that RCCL can send them as they are."""
+    -- both kept with device-to-device copies.  The planes are torch tensors so that RCCL can send them as they are.
+    close() is what releases process_frames' worker threads and their library contexts: each worker holds its backend, so a
+    backend dropped without close() keeps them for the life of the process."""
 
     CELL_TYPE_COLUMNS = (("type", np.uint8), ("valid", np.uint8), ("mean_intensity", np.float64))
     CELL_TYPE_OPTIONS = ("atoh_channel", "threshold", "percentage_above_threshold", "peak_window_size", "type_index",
@@ -161,12 +165,6 @@ class GpuFrameBackend(object):
             w.jobs.put(None)
         for w in workers:
             w.join()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _process_with(self, p, t, stack_u16):
         from . import _lib
@@ -249,38 +247,43 @@ class GpuFrameBackend(object):
         return float(sh[0]), float(sh[1])
 
 
-def _all_gather_arrays(arrs, dist, world, device):
-    """all-gather a list of float64 1-D arrays of per-rank varying length -> list (per rank) of arrays."""
-    import torch
-    flat = np.concatenate([np.asarray(a, np.float64).ravel() for a in arrs]) if arrs else np.zeros(0)
-    n = torch.tensor([flat.size], dtype=torch.int64, device=device)
-    sizes = [torch.zeros(1, dtype=torch.int64, device=device) for _ in range(world)]
-    dist.all_gather(sizes, n)
-    sizes = [int(s.item()) for s in sizes]
-    m = max(max(sizes), 1)
-    buf = torch.zeros(m, dtype=torch.float64, device=device)
-    buf[:flat.size] = torch.from_numpy(flat).to(device)
-    out = [torch.zeros(m, dtype=torch.float64, device=device) for _ in range(world)]
-    dist.all_gather(out, buf)
-    return [o[:s].cpu().numpy() for o, s in zip(out, sizes)]
+def pack_tables(tables, extra=()):
+    """Wire format of a round's cell tables ({t: dict}) -> one float64 array: per frame the header [t, n, drift row, drift
+    column], then area, cy, cx and every column named in `extra` ((name, dtype) pairs), n values each."""
+    parts = []
+    for t, tb in tables.items():
+        parts += [np.array([t, tb["area"].size, tb["drift"][0], tb["drift"][1]], np.float64), tb["area"], tb["cy"], tb["cx"]]
+        parts += [tb[name] for name, _ in extra]
+    return np.concatenate([np.asarray(a, np.float64).ravel() for a in parts]) if parts else np.zeros(0)
 
 
-def _gather_to_root(flat, dist, rank, world, device):
-    """gatherv of an int64 array to rank 0 (counts all-gathered first, then one padded gather)."""
-    import torch
-    flat = np.asarray(flat, np.int64).ravel()
-    n = torch.tensor([flat.size], dtype=torch.int64, device=device)
-    sizes = [torch.zeros(1, dtype=torch.int64, device=device) for _ in range(world)]
-    dist.all_gather(sizes, n)
-    sizes = [int(s.item()) for s in sizes]
-    m = max(max(sizes), 1)
-    buf = torch.zeros(m, dtype=torch.int64, device=device)
-    buf[:flat.size] = torch.from_numpy(flat).to(device)
-    out = [torch.zeros(m, dtype=torch.int64, device=device) for _ in range(world)] if rank == 0 else None
-    dist.gather(buf, out, dst=0)
-    if rank != 0:
-        return None
-    return [o[:s].cpu().numpy() for o, s in zip(out, sizes)]
+def unpack_tables(flat, extra=()):
+    """pack_tables undone -> {t: dict}: area int64, extra columns in their dtype, drift its own pair."""
+    tables, pos = {}, 0
+    while pos < flat.size:
+        t, n = int(flat[pos]), int(flat[pos + 1])
+        cols = flat[pos + 4:pos + 4 + (3 + len(extra)) * n].reshape(3 + len(extra), n)
+        tables[t] = dict(area=cols[0].astype(np.int64), cy=cols[1], cx=cols[2], drift=flat[pos + 2:pos + 4].copy())
+        for (name, dtype), col in zip(extra, cols[3:]):
+            tables[t][name] = col.astype(dtype)
+        pos += 4 + cols.size
+    return tables
+
+
+def pack_lookups(lookups):
+    """Wire format of a round's look-ups ({t: hits}) -> one int64 array: per frame [t, n], then the n hits."""
+    parts = [np.concatenate([[t, r.size], r]).astype(np.int64) for t, r in lookups.items()]
+    return np.concatenate(parts) if parts else np.zeros(0, np.int64)
+
+
+def unpack_lookups(flat):
+    """pack_lookups undone -> {t: int64 hits}."""
+    lookups, pos = {}, 0
+    while pos < flat.size:
+        t, n = int(flat[pos]), int(flat[pos + 1])
+        lookups[t] = flat[pos + 2:pos + 2 + n]
+        pos += 2 + n
+    return lookups
 
 
 def assign_track_ids(prev_ids, hit, n_cur, start_ids=None):
@@ -320,7 +323,7 @@ def propagate_ids(tables, lookups):
     return out
 
 
-def exchange_planes(n_frames, sends, recvs, backend, rank, world, dist):
+def exchange_planes(sends, recvs, backend, rank, world, dist):
     """Plane hand-off for drift estimation: frame t's owner needs frame t-1's reference-channel plane, which lives on rank
     (t-1) % world.  `sends`: this rank's frames whose planes go to rank (rank+1) % world; `recvs`: frames t-1 owned by rank
     (rank-1) % world whose planes arrive here -- both in increasing order on either side of a pair, all pairs at once
@@ -368,17 +371,103 @@ def link_ids(tables, drifts):
     return out
 
 
-def _first_piv_failure(failed, rank, world, dist, device):
-    """all-gather of every rank's first failing PIV frame this round ((frame, kind) or (-1, 0); kind 1: IndexError, 2: other)
-    -> the lowest failing frame over all ranks as (frame, kind, owner rank), or None."""
-    import torch
+def _validate(stitcher, estimate_drift, use_piv, backend):
+    if stitcher not in ("lookup", "linker"):
+        raise ValueError("stitcher must be 'lookup' or 'linker'")
+    if use_piv and estimate_drift:
+        raise ValueError("use_piv and estimate_drift are two drift sources: pass one of them")
+    if use_piv and stitcher != "lookup":
+        raise ValueError("use_piv needs stitcher='lookup' (the reference's trackpy linker has no PIV mode)")
+    if use_piv and (not hasattr(backend, "piv_lookup") or not getattr(backend, "keep_planes", True)):
+        raise ValueError("use_piv needs a backend with the reference-channel planes (GpuFrameBackend(keep_planes=True))")
+
+
+def plan_rounds(n_frames, rank, world, block_frames=None):
+    """`rank`'s frames per round: round k holds the global frames [k B W, (k+1) B W), B = block_frames (None: the whole shard
+    in one round).  Every rank gets the same number of rounds, at least one; a round may leave a rank without a frame."""
+    from .pipeline import frames_for_rank
+    per_round = (int(block_frames) if block_frames else max(1, -(-n_frames // world))) * world
+    rounds = [[] for _ in range(max(1, -(-n_frames // per_round)))]
+    for t in frames_for_rank(n_frames, rank, world):
+        rounds[t // per_round].append(t)
+    return rounds
+
+
+def _compute_round(frames, frame_source, backend):
+    """{t: the backend's dict} for one round's frames of this rank; runs on the driver's compute thread."""
+    if hasattr(backend, "process_frames") and frames:      # several frames in flight on this rank's GPU
+        return backend.process_frames(frames, frame_source)
+    return {t: backend.process_frame(t, frame_source(t)) for t in frames}
+
+
+def _drift_step(mine, local, drifts, backend, held_planes, estimate_drift):
+    """Writes tables' "drift": the given row, or with estimate_drift the owner's estimate against the held plane of frame t-1."""
+    for t in mine:
+        if estimate_drift and t >= 1:
+            drifts[t] = backend.drift(t, held_planes.pop(t))
+        local[t]["drift"] = drifts[t].copy()
+
+
+def _exchange_tables(mine, local, extra, dist, rank, world, device):
+    """The round's cell tables on every rank, {t: dict}.  One process: the backend's own dicts, as they are."""
     if world == 1:
-        return failed + (rank,) if failed[0] >= 0 else None
-    mine = torch.tensor(list(failed), dtype=torch.int64, device=device)
-    allv = [torch.zeros(2, dtype=torch.int64, device=device) for _ in range(world)]
-    dist.all_gather(allv, mine)
+        return {t: local[t] for t in mine}
+    parts = gather_varlen(pack_tables({t: local[t] for t in mine}, extra), np.float64, dist, rank, world, device)
+    return {t: tb for part in parts for t, tb in unpack_tables(part, extra).items()}
+
+
+def _owner_lookups(mine, tables, backend, piv_planes=None):
+    """For each of this rank's frames t >= 1 the label of frame t under every row of frame t-1, -1 for absent (zero-area) rows:
+    backend.lookup at the drift-corrected centroids, or with piv_planes (the held planes) backend.piv_lookup, whose first
+    exception ends the loop.  Returns ({t: hits}, (failed frame or -1, kind 1: IndexError / 2: other), the exception)."""
+    hits = {}
+    for t in [t for t in mine if t >= 1]:
+        prev = tables[t - 1]
+        if piv_planes is not None:
+            try:
+                res = backend.piv_lookup(t, piv_planes.pop(t), prev)
+            except Exception as e:            # the round's collectives still run: _agree_on_piv_failure tells every rank
+                return hits, (t, 1 if isinstance(e, IndexError) else 2), e
+        else:
+            dy, dx = tables[t]["drift"]
+            res = backend.lookup(t, np.round(prev["cy"] - dy).astype(np.int64), np.round(prev["cx"] - dx).astype(np.int64))
+        hits[t] = np.where(prev["area"] > 0, res, -1)
+    return hits, (-1, 0), None
+
+
+def _agree_on_piv_failure(failed, error, rank, world, dist, device):
+    """All-gather of every rank's first failing PIV frame of the round; if there is one, every rank raises for the lowest:
+    its owner its own exception, the others an error that names frame and rank."""
+    allv = [failed]
+    if world > 1:
+        import torch
+        mine = torch.tensor(list(failed), dtype=torch.int64, device=device)
+        allv = [torch.zeros(2, dtype=torch.int64, device=device) for _ in range(world)]
+        dist.all_gather(allv, mine)
     hits = [(int(v[0]), int(v[1]), r) for r, v in enumerate(allv) if int(v[0]) >= 0]
-    return min(hits) if hits else None
+    if hits:
+        t_bad, kind, owner = min(hits)
+        if owner == rank and t_bad == failed[0]:
+            raise error
+        if kind == 1:
+            raise IndexError("use_piv: frame %d's flow sampling is out of bounds on rank %d" % (t_bad, owner))
+        raise RuntimeError("use_piv: frame %d's PIV look-up failed on rank %d" % (t_bad, owner))
+
+
+def _gather_lookups(hits, dist, rank, world, device):
+    """The round's look-ups on rank 0, {t: hits}; {} on the other ranks."""
+    if world == 1:
+        return hits
+    parts = gather_varlen(pack_lookups(hits), np.int64, dist, rank, world, device, root=0) or ()
+    return {t: found for part in parts for t, found in unpack_lookups(part).items()}
+
+
+def _stitch(tables, lookups, stitcher):
+    """Rank 0's sequential part -> (tables per frame, track ids per frame)."""
+    tabs = [tables[t] for t in range(len(tables))]
+    if stitcher == "linker":
+        return tabs, link_ids(tabs, [tb["drift"] for tb in tabs])
+    return tabs, propagate_ids(tabs, [None] + [lookups[t] for t in range(1, len(tabs))])
 
 
 def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, device="cpu", drifts=None,
@@ -396,138 +485,38 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
     estimate_drift (ValueError).  Upstream's transposed sampling makes only square frames safe: where its numpy indexing
     raises, every rank raises IndexError for the lowest failing frame of that round -- each rank first takes part in the
     round's small all-gather of failures and joins its worker thread, so no collective is left waiting and no further
-    round starts.
+    round starts.  Any other exception of a round (a backend's, a collective's) leaves the same way: the one compute thread,
+    which serves every round, finishes the round it has begun before the exception reaches the caller.
 
-    The movie is worked off in ROUNDS of `block_frames` frames per rank (round k = global frames [k B W, (k+1) B W)): while
-    the workers compute round k+1, this thread runs round k's exchange -- planes to the neighbour rank, drift, all-gather of
-    the centroid tables, owner-side look-ups, gather of the index arrays to rank 0 -- so the stitching traffic and the drift
-    correlations hide behind the next frames' kernels instead of forming a tail after the last frame.  Every rank runs the same
-    number of rounds (a rank without frames in a round takes part with empty payloads: the collectives stay matched), so any
-    n_frames works, including fewer frames than ranks.  block_frames=None: the whole shard in one round (no overlap)."""
-    import threading
-    if stitcher not in ("lookup", "linker"):
-        raise ValueError("stitcher must be 'lookup' or 'linker'")
-    if use_piv:
-        if estimate_drift:
-            raise ValueError("use_piv and estimate_drift are two drift sources: pass one of them")
-        if stitcher != "lookup":
-            raise ValueError("use_piv needs stitcher='lookup' (the reference's trackpy linker has no PIV mode)")
-        if not hasattr(backend, "piv_lookup") or not getattr(backend, "keep_planes", True):
-            raise ValueError("use_piv needs a backend with the reference-channel planes (GpuFrameBackend(keep_planes=True))")
-    if drifts is None:
-        drifts = np.zeros((n_frames, 2))
-    drifts = np.array(drifts, dtype=np.float64)
+    The movie is worked off in ROUNDS of `block_frames` frames per rank (plan_rounds; None: the whole shard in one round, no
+    overlap).  While a thread computes round k+1 (_compute_round), this one runs round k's exchange: planes to the neighbour rank
+    (exchange_planes), drift (_drift_step), all-gather of the cell tables (_exchange_tables), owner-side look-ups (_owner_lookups;
+    with use_piv the failure agreement, _agree_on_piv_failure), gather of the index arrays to rank 0 (_gather_lookups) -- so the
+    stitching traffic and the drift correlations hide behind the next frames' kernels instead of forming a tail after the last
+    frame; rank 0 then stitches (_stitch).  Every rank runs the same rounds and joins their collectives, with empty payloads
+    when it has no frame in one, so any n_frames works, including fewer frames than ranks."""
+    from concurrent.futures import ThreadPoolExecutor
+    _validate(stitcher, estimate_drift, use_piv, backend)
+    drifts = np.zeros((n_frames, 2)) if drifts is None else np.array(drifts, dtype=np.float64)
     extra = tuple(getattr(backend, "extra_columns", ()))      # further per-row columns every frame's dict carries
-    per_round = (int(block_frames) if block_frames else max(1, -(-n_frames // world))) * world
-    n_rounds = max(1, -(-n_frames // per_round))
-    rounds = [[t for t in range(k * per_round, min(n_frames, (k + 1) * per_round)) if t % world == rank] for k in range(n_rounds)]
-
-    def compute(frames, out):
-        try:
-            if not frames:
-                return
-            if hasattr(backend, "process_frames"):
-                out.update(backend.process_frames(frames, frame_source))        # several frames in flight on this rank's GPU
-            else:
-                out.update({t: backend.process_frame(t, frame_source(t)) for t in frames})
-        except BaseException as e:
-            out["error"] = e
-
+    rounds = plan_rounds(n_frames, rank, world, block_frames)
+    upstream = plan_rounds(n_frames, (rank - 1) % world, world, block_frames)      # the neighbour whose planes arrive here
     tables, lookups, held_planes = {}, {}, {}
-    results = [dict() for _ in range(n_rounds)]
-    worker = threading.Thread(target=compute, args=(rounds[0], results[0]))
-    worker.start()
-    for k in range(n_rounds):
-        worker.join()
-        if "error" in results[k]:
-            raise results[k]["error"]
-        local, mine = results[k], rounds[k]
-        if k + 1 < n_rounds:                       # the next round computes while this one is exchanged
-            worker = threading.Thread(target=compute, args=(rounds[k + 1], results[k + 1]))
-            worker.start()
-        lo, hi = k * per_round, min(n_frames, (k + 1) * per_round)
-        if estimate_drift or use_piv:
-            sends = [t for t in mine if t + 1 < n_frames]
-            recvs = [t for t in range(lo, hi) if t % world == (rank - 1) % world and t + 1 < n_frames]
-            held_planes.update(exchange_planes(n_frames, sends, recvs, backend, rank, world, dist))
-        if estimate_drift:
-            for t in mine:
-                if t >= 1:
-                    drifts[t] = backend.drift(t, held_planes.pop(t))
-        for t in mine:
-            local[t]["drift"] = drifts[t].copy()
-        # 1. centroid tables of the round everywhere
-        if world > 1:
-            payload = []
-            for t in mine:
-                tb = local[t]
-                payload += [np.array([t, tb["area"].size, tb["drift"][0], tb["drift"][1]], np.float64),
-                            tb["area"].astype(np.float64), tb["cy"], tb["cx"]]
-                payload += [np.asarray(tb[name], np.float64) for name, _ in extra]
-            for flat in _all_gather_arrays(payload, dist, world, device):
-                pos = 0
-                while pos < flat.size:
-                    t, n = int(flat[pos]), int(flat[pos + 1])
-                    drift_t = flat[pos + 2:pos + 4].copy()
-                    pos += 4
-                    tables[t] = dict(area=flat[pos:pos + n].astype(np.int64), cy=flat[pos + n:pos + 2 * n],
-                                     cx=flat[pos + 2 * n:pos + 3 * n], drift=drift_t)
-                    pos += 3 * n
-                    for name, dtype in extra:
-                        tables[t][name] = flat[pos:pos + n].astype(dtype)
-                        pos += n
-        else:
-            tables.update({t: local[t] for t in mine})
-        if stitcher == "linker":
-            continue
-        # 2. owners look the previous frame's centroids up in their resident label maps
-        my_lookups, failed, error = {}, (-1, 0), None
-        for t in mine:
-            if t == 0:
+    with ThreadPoolExecutor(1) as pool:               # (left only when the compute thread is idle, also by an exception)
+        pending = pool.submit(_compute_round, rounds[0], frame_source, backend)
+        for k, mine in enumerate(rounds):
+            local = pending.result()
+            if k + 1 < len(rounds):                   # the next round computes while this one is exchanged
+                pending = pool.submit(_compute_round, rounds[k + 1], frame_source, backend)
+            if estimate_drift or use_piv:             # frame t's plane goes to the owner of frame t+1, if there is one
+                held_planes.update(exchange_planes([t for t in mine if t + 1 < n_frames],
+                                                   [t for t in upstream[k] if t + 1 < n_frames], backend, rank, world, dist))
+            _drift_step(mine, local, drifts, backend, held_planes, estimate_drift)
+            tables.update(_exchange_tables(mine, local, extra, dist, rank, world, device))
+            if stitcher == "linker":
                 continue
-            prev = tables[t - 1]
+            hits, failed, error = _owner_lookups(mine, tables, backend, held_planes if use_piv else None)
             if use_piv:
-                try:
-                    res = backend.piv_lookup(t, held_planes.pop(t), prev)
-                except Exception as e:            # the round's collectives still run: every rank learns of it below
-                    failed, error = (t, 1 if isinstance(e, IndexError) else 2), e
-                    break
-            else:
-                cy = prev["cy"] - tables[t]["drift"][0]
-                cx = prev["cx"] - tables[t]["drift"][1]
-                qy, qx = np.round(cy).astype(np.int64), np.round(cx).astype(np.int64)
-                res = backend.lookup(t, qy, qx)
-            my_lookups[t] = np.where(prev["area"] > 0, res, -1)   # absent rows never match (empty_cell / zero-area rows)
-        if use_piv:
-            first = _first_piv_failure(failed, rank, world, dist, device)
-            if first is not None:
-                worker.join()                     # (round k+1's frames: nothing is left running)
-                t_bad, kind, owner = first
-                if owner == rank and t_bad == failed[0]:
-                    raise error
-                if kind == 1:
-                    raise IndexError("use_piv: frame %d's flow sampling is out of bounds on rank %d" % (t_bad, owner))
-                raise RuntimeError("use_piv: frame %d's PIV look-up failed on rank %d" % (t_bad, owner))
-        # 3. gather to rank 0
-        if world > 1:
-            flat = []
-            for t, r in my_lookups.items():
-                flat += [np.array([t, r.size], np.int64), r.astype(np.int64)]
-            flat = np.concatenate(flat) if flat else np.zeros(0, np.int64)
-            parts = _gather_to_root(flat, dist, rank, world, device)
-            if rank == 0:
-                for p in parts:
-                    pos = 0
-                    while pos < p.size:
-                        t, n = int(p[pos]), int(p[pos + 1])
-                        lookups[t] = p[pos + 2:pos + 2 + n]
-                        pos += 2 + n
-        else:
-            lookups.update(my_lookups)
-    if rank != 0:
-        return None, None
-    tabs = [tables[t] for t in range(n_frames)]
-    if stitcher == "linker":
-        return tabs, link_ids(tabs, [tb["drift"] for tb in tabs])
-    ids = propagate_ids(tabs, [None] + [lookups[t] for t in range(1, n_frames)])
-    return tabs, ids
+                _agree_on_piv_failure(failed, error, rank, world, dist, device)
+            lookups.update(_gather_lookups(hits, dist, rank, world, device))
+    return _stitch(tables, lookups, stitcher) if rank == 0 else (None, None)

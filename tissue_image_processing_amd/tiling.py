@@ -19,6 +19,8 @@ import ctypes
 
 import numpy as np
 
+from ._collectives import gather_varlen
+
 HALO = 4 + 120 + 8   # radius of sigma 1 (4 * 1) + sigma 30 (4 * 30) + sigma 2 (4 * 2): support of one projected pixel
 
 
@@ -79,23 +81,6 @@ class GpuTileBackend(object):
         return proj, zmap
 
 
-def _gather_f64_to_root(flat, dist, rank, world, device):
-    import torch
-    flat = np.asarray(flat, np.float64).ravel()
-    n = torch.tensor([flat.size], dtype=torch.int64, device=device)
-    sizes = [torch.zeros(1, dtype=torch.int64, device=device) for _ in range(world)]
-    dist.all_gather(sizes, n)
-    sizes = [int(s.item()) for s in sizes]
-    m = max(max(sizes), 1)
-    buf = torch.zeros(m, dtype=torch.float64, device=device)
-    buf[:flat.size] = torch.from_numpy(flat).to(device)
-    out = [torch.zeros(m, dtype=torch.float64, device=device) for _ in range(world)] if rank == 0 else None
-    dist.gather(buf, out, dst=0)
-    if rank != 0:
-        return None
-    return [o[:s].cpu().numpy() for o, s in zip(out, sizes)]
-
-
 def project_tiled(tile_source, C, Y, X, grid, backend, rank=0, world=1, dist=None, device="cpu", halo=HALO):
     """Tiled surface projection of one (C, Z, Y, X) frame.  tile_source(py0, py1, px0, px1) -> the uint16 sub-stack
     (C, Z, py1-py0, px1-px0) (a rank only ever asks for its own tiles).  grid = (ny, nx); tile k -> rank k % world.
@@ -119,7 +104,7 @@ def project_tiled(tile_source, C, Y, X, grid, backend, rank=0, world=1, dist=Non
         sy, sx = slice(y0 - py0, y1 - py0), slice(x0 - px0, x1 - px0)
         payload += [np.array([k], np.float64), proj[:, sy, sx].ravel(), zmap[sy, sx].astype(np.float64).ravel()]
     flat = np.concatenate(payload) if payload else np.zeros(0)
-    parts = _gather_f64_to_root(flat, dist, rank, world, device) if world > 1 else [flat]
+    parts = gather_varlen(flat, np.float64, dist, rank, world, device, root=0) if world > 1 else [flat]
     if rank != 0:
         return None, None
     proj = np.empty((C, Y, X), np.float64)
