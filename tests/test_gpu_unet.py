@@ -291,7 +291,7 @@ def test_unet_leg_three_frames_in_flight_every_step_exact():
     assert len(results) == THREADS * STEPS
     for (k, step), (p0, lab, hc, flags) in sorted(results.items()):
         assert flags & _lib.WS_FLAG_TWO_VALUED and not (flags & (_lib.WS_FLAG_SERIAL_EXACT | _lib.WS_FLAG_SERIAL_FINISH)), (k, step, flags)
-        # the network passes of the three threads are ordered on the device (prediction_local._forward_gated): same input, same bits,
+        # the network passes of the three threads are ordered on the device (_unet_hip.forward): same input, same bits,
         # whatever ran beside the pass
         np.testing.assert_array_equal(p0, base[k])
         closed = orc.erosion(orc.dilation(255.0 * (p0 > np.float32(0.1)), 5), 5)

@@ -13,7 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 MODES = {"f16x3": (2, 1), "bf16x3": (2, 0), "bf16x6": (3, 0)}     # mode -> (planes, piece format)
-ACT = 16.0                                                        # prediction_local._F16_ACT_SCALE
+ACT = 16.0                                                        # _unet_hip._F16_ACT_SCALE
 
 
 @pytest.fixture()
@@ -270,22 +270,28 @@ def test_network_hip_path_other_extents(shape, mode, arith, monkeypatch):
     errsep = float((sep.cpu().double() - exp).abs().max())
     dhead = float((sep - fused).abs().max())
     monkeypatch.delenv("TISSUE_HIP_UNET_SEPARATE_HEAD")
-    # the transposed convolution as ONE launch over the four output parity classes (TISSUE_HIP_UNET_TCONV=fused; measured slower, kept
-    # as a selectable variant) instead of the default four: the same accumulation order per output, so the same bits
-    monkeypatch.setenv("TISSUE_HIP_UNET_TCONV", "fused")
-    assert torch.equal(gpu.forward(xg), fused), "one-launch vs four-launch transposed convolution"
-    with _lib.tuning(TIP_UNET_TILE8="1"):
-        one8 = gpu.forward(xg)
-    monkeypatch.delenv("TISSUE_HIP_UNET_TCONV")
-    with _lib.tuning(TIP_UNET_TILE8="1"):
-        assert torch.equal(gpu.forward(xg), one8), "one-launch vs four-launch transposed convolution, 8-row tiles"
     # steps per barrier of the 3x3 16-row kernel (default three) and the workgroup order change the schedule, not the arithmetic
-    for knob, val in (("TIP_UNET_SPB", "1"), ("TIP_UNET_SPB", "2"), ("TIP_UNET_XCD_MAP", "0")):
+    for knob, val in (("TIP_UNET_SPB", "1"), ("TIP_UNET_XCD_MAP", "0")):
         with _lib.tuning(**{knob: val}):
             assert torch.equal(gpu.forward(xg), fused), (knob, val)
     print("%s %dx%d: max |dp| %.2e (8-row tiles everywhere: %.2e, 16-row wherever possible: %.2e, separate head: %.2e, fused vs separate head %.2e)"
           % (mode, shape[0], shape[1], err, err8, err16, errsep, dhead))
     assert err < tol and err8 < tol and err16 < tol and errsep < tol and dhead < tol
+
+
+def test_two_steps_per_barrier_means_three():
+    """TIP_UNET_SPB=2 named a schedule that is retired: every value above 1 now selects the three-step one (include/tissue_hip.h),
+    so the pass is the default pass, bit for bit -- and not the one-step schedule's flavour or a refused launch."""
+    import torch
+    from tissue_image_processing_amd import prediction_local as pl, _lib
+    gpu = pl._UNet(2, torch.device("cuda", 0), dtype=torch.float32, seed=7)
+    gpu.randomize_statistics(9)
+    xg = torch.from_numpy(np.random.default_rng(128).random((1, 2, 128, 512))).to("cuda").float()
+    assert gpu.hip_path_ok(xg)
+    default = gpu.forward(xg)
+    with _lib.tuning(TIP_UNET_SPB="2"):
+        assert torch.equal(gpu.forward(xg), default)
+    assert gpu.last_mode == "f16x3"
 
 
 def _bench_like_image(N, M, seed):

@@ -1,0 +1,255 @@
+"""Driver of the hand-written U-Net kernels (csrc/tip_unet_conv.h, csrc/tip_unet.hip) for prediction_local._UNet: the arithmetic
+modes, the C-ABI's convolution descriptor, the splitting and packing of the weights (cached per mode on the network), the
+one-pass-at-a-time gate and the launch sequence of a forward pass.  The network's parameters, the decision whether an input takes
+this path and the torch / MIOpen restatement of the same layers stay in prediction_local."""
+import ctypes
+import os
+import threading
+
+import numpy as np
+
+from . import _lib
+
+_MODES = {  # mode -> (pieces per value, piece format of the C-ABI: 0 bf16, 1 fp16, products per term, dropped part of a term)
+    "f16x3": (2, 1, 3, "7.2e-7"),
+    "bf16x3": (2, 0, 3, "1.6e-5"),
+    "bf16x6": (3, 0, 6, "9e-8"),
+}
+_F16_ACT_SCALE = 16.0      # fp16 pieces: activations are stored times 2^4 (saturate beyond |v| = 4094, absolute floor 2^-29)
+
+
+class _ConvDesc(ctypes.Structure):
+    """tip_unet_conv_desc of include/tissue_hip.h."""
+    _fields_ = [("in0", ctypes.c_void_p), ("in1", ctypes.c_void_p), ("c0", ctypes.c_int), ("c1", ctypes.c_int), ("h", ctypes.c_int),
+                ("w", ctypes.c_int), ("planes", ctypes.c_int), ("weights", ctypes.c_void_p), ("ntaps", ctypes.c_int),
+                ("dy", ctypes.c_int * 9), ("dx", ctypes.c_int * 9), ("cout", ctypes.c_int), ("bias", ctypes.c_void_p),
+                ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_h", ctypes.c_int),
+                ("out_w", ctypes.c_int), ("sy", ctypes.c_int), ("sx", ctypes.c_int), ("oy", ctypes.c_int), ("ox", ctypes.c_int),
+                ("pool_out", ctypes.c_void_p), ("head_w", ctypes.c_void_p), ("head_b", ctypes.c_void_p), ("head_out", ctypes.c_void_p),
+                ("format", ctypes.c_int), ("acc_scale", ctypes.c_float)]
+
+
+def split_pack(taps, planes, fmt=0):
+    """taps: (T, Cin, Cout) float32 on the device -> packed split weights [T][Cin/16][Cout/128][plane][128][16] in bf16 (fmt 0) or
+    fp16 (fmt 1: the caller has scaled the taps into fp16's range) pieces.
+
+    Row order inside every group of 32 output channels: row 8 g + 4 h + j (g < 4, h < 2, j < 4) holds channel 16 h + 4 g + j --
+    the matrix core's output register i = 4 g + j of half-wave h is then channel 16 h + i, i.e. a lane of the kernel ends up with
+    sixteen ADJACENT channels of its pixel (csrc/tip_unet_conv.h, epilogue)."""
+    import torch
+    T, cin, cout = taps.shape
+    pieces, rest = [], taps.float()
+    for _ in range(planes):
+        h = rest.to(torch.float16 if fmt else torch.bfloat16)
+        pieces.append(h)
+        rest = rest - h.float()
+    row = torch.arange(32, device=taps.device)
+    chan = 16 * ((row >> 2) & 1) + 4 * (row >> 3) + (row & 3)          # channel (within its group of 32) stored in each row
+    pk = torch.stack(pieces, 0).view(planes, T, cin // 16, 16, cout // 32, 32)[..., chan]
+    pk = pk.reshape(planes, T, cin // 16, 16, cout // 128, 128)
+    return pk.permute(1, 2, 4, 0, 5, 3).contiguous()
+
+
+def weights(net, mode):
+    """Packed weights and per-channel constants of one arithmetic mode, cached in net._hipw.  fp16 pieces (mode f16x3) carry
+    power-of-two scales: activations are stored times A = 2^4, a layer's weights times W = the power of two that puts its largest
+    weight in [2^14, 2^15); the kernel multiplies the accumulator by 1 / (A W) before the bias (entry 3 of a layer's tuple), the
+    BatchNorm scale / shift (and a bias-only layer's bias and accumulator factor) are multiplied by A, the head's weights by
+    1 / A -- exact, so the stored values are A times what the unscaled network computes, bit for bit."""
+    hw = net._hipw.get(mode)
+    if hw is not None:
+        return hw
+    torch = net.torch
+    p = net.p
+    planes, fmt = _MODES[mode][:2]
+    act = _F16_ACT_SCALE if fmt else 1.0
+    hw = {}
+
+    def pack(taps, bias_only):
+        if not fmt:
+            return split_pack(taps, planes), 1.0
+        big = float(taps.abs().max())
+        wscale = 2.0 ** (14 - int(np.floor(np.log2(big)))) if big > 0 and np.isfinite(big) else 1.0
+        inv = 1.0 / (act * wscale)
+        return split_pack(taps * wscale, planes, fmt), (inv * act if bias_only else inv)
+
+    def conv3(name):
+        w = p[name + ".w"].float()                                  # (cout, cin, 3, 3): cross-correlation, tap (ky, kx) reads (y + ky - 1, x + kx - 1)
+        taps = torch.stack([w[:, :, ky, kx].t() for ky in range(3) for kx in range(3)], 0)
+        wp, inv = pack(taps, False)
+        hw[name] = (wp, [ky - 1 for ky in range(3) for kx in range(3)], [kx - 1 for ky in range(3) for kx in range(3)], inv)
+
+    def conv_t(name):
+        # conv_transpose2d(stride 2): out[2 i + k] += in[i] w[k], cropped to the first 2N rows / columns.  Even outputs take
+        # k = 0 from i = o / 2 and k = 2 from i = o / 2 - 1, odd outputs k = 1 from i = (o - 1) / 2: four parity classes
+        w = p[name + ".w"].float()                                  # (cin, cout, 3, 3)
+        per_axis = {0: [(0, 0), (2, -1)], 1: [(1, 0)]}             # parity -> [(k, input offset)]
+        for py in (0, 1):
+            for px in (0, 1):
+                tl = [(ky, dy, kx, dx) for ky, dy in per_axis[py] for kx, dx in per_axis[px]]
+                taps = torch.stack([w[:, :, ky, kx] for ky, _, kx, _ in tl], 0)
+                wp, inv = pack(taps, True)
+                hw["%s.%d%d" % (name, py, px)] = (wp, [t[1] for t in tl], [t[3] for t in tl], inv)
+
+    for blk in ("d0", "d1", "d2", "mid", "u0", "u1", "u2"):
+        if blk != "d0":
+            conv3(blk + ".c1")
+        conv3(blk + ".c2")
+    for i in range(3):
+        conv_t("u%d.t" % i)
+    w0 = p["d0.c1.w"].float()                                       # (128, 2, 3, 3) -> [tap][ci][cout]
+    hw["first"] = w0.permute(2, 3, 1, 0).reshape(18, 128).contiguous()
+    hw["head"] = (p["head.w"].float().reshape(2, 128) / act).contiguous()
+    for k in list(p):
+        if k.endswith((".b", ".s", ".t")) and not k.endswith(".t.w"):
+            v = p[k].float().reshape(-1)
+            # times A: BatchNorm scale (".s") / shift (".t"), and the bias of a bias-only (transposed convolution) layer (".t.b")
+            scaled = k.endswith((".s", ".t", ".t.b"))
+            hw["f:" + k] = (v * act if scaled else v).contiguous()
+    net._hipw[mode] = hw
+    return hw
+
+
+_FORWARD_GATES = {}
+_FORWARD_GATES_LOCK = threading.Lock()
+
+
+def _forward_gate(device_index):
+    with _FORWARD_GATES_LOCK:
+        g = _FORWARD_GATES.get(device_index)
+        if g is None:
+            g = _FORWARD_GATES[device_index] = {"lock": threading.Lock(), "event": None, "stream": None}
+        return g
+
+
+def forward(net, x, mode, logits):
+    """One network at a time on a device.  Frames in flight (worker threads, each with its own stream: movie.py, bench.py) would
+    otherwise run their forward passes CONCURRENTLY -- the queues share the chip kernel by kernel, every pass takes N times as
+    long, all of them end together and the frames' tails (small kernels, host stages) then run together with nothing to
+    hide behind: the kernel trace shows the matrix cores idle for 8.5 % of the time (profiles/r04n_*).  Here a pass waits ON THE
+    DEVICE (stream.wait_event, no host stall) for the pass queued before it, so that the passes run back to back in ticket order
+    and the other frames' tails and projections fill in beside them.  TISSUE_HIP_UNET_SERIAL=0 restores the free-for-all."""
+    torch = net.torch
+    if os.environ.get("TISSUE_HIP_UNET_SERIAL", "1") == "0":
+        return _launch(net, x, mode, logits)
+    gate = _forward_gate(x.device.index)
+    with gate["lock"]:
+        s = torch.cuda.current_stream(x.device)
+        if gate["event"] is not None and gate["stream"] != s.cuda_stream:
+            s.wait_event(gate["event"])
+        out = _launch(net, x, mode, logits)
+        ev = torch.cuda.Event()
+        ev.record(s)
+        gate["event"], gate["stream"] = ev, s.cuda_stream
+    return out
+
+
+def _conv_desc(layer, planes, fmt, src, skip, h, w, bias, scale=None, shift=None, out=None, out_h=None, out_w=None, stride=1, oy=0, ox=0,
+               pooled=None, head=None):
+    """The descriptor of one tip_unet_conv_dev launch.  layer: (packed weights, dy, dx, accumulator factor) from weights(); src,
+    skip: split activations on the h x w grid (skip's channels are appended to src's: the decoder's concatenate); bias, scale,
+    shift: float32 vectors (no scale / shift: a bias-only layer); out: split output of out_h x out_w pixels (default: the input
+    grid), input-grid pixel (y, x) goes to (y * stride + oy, x * stride + ox); pooled: MaxPool2D(2) of the output; head: (weights,
+    bias, float32 output) of the network's head computed in this layer's epilogue -- the layer's own output is then not stored."""
+    wp, dy, dx, inv = layer
+    d = _ConvDesc()
+    d.format, d.acc_scale = fmt, inv
+    d.in0, d.c0 = src.data_ptr(), src.shape[3]
+    d.in1, d.c1 = (skip.data_ptr(), skip.shape[3]) if skip is not None else (None, 0)
+    d.h, d.w, d.planes = h, w, planes
+    d.weights, d.ntaps, d.cout = wp.data_ptr(), len(dy), wp.shape[2] * 128
+    for i in range(len(dy)):
+        d.dy[i], d.dx[i] = dy[i], dx[i]
+    d.bias = bias.data_ptr()
+    d.scale, d.shift = (scale.data_ptr(), shift.data_ptr()) if scale is not None else (None, None)
+    if head is not None:
+        d.head_w, d.head_b, d.head_out = (t.data_ptr() for t in head)
+    d.out = out.data_ptr() if out is not None else None
+    d.out_h, d.out_w = (h, w) if out_h is None else (out_h, out_w)
+    d.sy, d.sx, d.oy, d.ox = stride, stride, oy, ox
+    d.pool_out = pooled.data_ptr() if pooled is not None else None
+    return d
+
+
+def _launch(net, x, mode, logits):
+    """The forward pass on torch's current stream: (1, 2, H, W) float32 -> class probabilities (or logits) (1, 2, H, W)."""
+    torch = net.torch
+    planes, fmt = _MODES[mode][:2]
+    hw = weights(net, mode)
+    net.last_mode = mode                  # (bench.py / tests: which arithmetic the last forward pass really used)
+    lib = _lib.lib()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    H, W = int(x.shape[2]), int(x.shape[3])
+    x = x.to(torch.float32).contiguous()
+    D = lambda t: ctypes.c_void_p(t.data_ptr())
+    trace = getattr(net, "trace", None)       # tools/unet_layers.py: [(layer, flop, event, event)] per launch
+
+    def timed(name, flop, fn):
+        if trace is None:
+            return fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = fn()
+        e1.record()
+        trace.append((name, flop, e0, e1))
+        return r
+
+    def buf(h, w, c):
+        return torch.empty((planes, h, w, c), dtype=torch.float16 if fmt else torch.bfloat16, device=x.device)
+
+    def launch_conv(name, d):
+        timed("%s %dx%d %d+%d->%d x%d taps" % (name, d.h, d.w, d.c0, d.c1, d.cout, d.ntaps), 2.0 * d.h * d.w * d.ntaps * d.cout * (d.c0 + d.c1),
+              lambda: _lib.check(lib.tip_unet_conv_dev(ctypes.byref(d), stream)))
+
+    def conv3(name, bn, src, skip, h, w, pooled=None, head=None):
+        """Conv2D(3x3) -> ReLU -> BatchNormalization `bn`; head: the probabilities' tensor when the head rides in the epilogue"""
+        out = buf(h, w, hw[name][0].shape[2] * 128) if head is None else None
+        launch_conv(name, _conv_desc(hw[name], planes, fmt, src, skip, h, w, hw["f:" + name + ".b"], hw["f:" + bn + ".s"], hw["f:" + bn + ".t"],
+                                     out=out, pooled=pooled, head=None if head is None else (hw["head"], hw["f:head.b"], head)))
+        return out
+
+    def first(h, w):
+        """Conv2D(2 -> 128, 3x3) -> ReLU -> BatchNormalization on the float32 network input"""
+        out = buf(h, w, 128)
+        timed("first %dx%d 2->128" % (h, w), 2.0 * h * w * 18 * 128,
+              lambda: _lib.check(lib.tip_unet_conv_first_dev(D(x), h, w, D(hw["first"]), D(hw["f:d0.c1.b"]), D(hw["f:d0.b1.s"]),
+                                                             D(hw["f:d0.b1.t"]), D(out), planes, fmt, stream)))
+        return out
+
+    def double(blk, src, skip, h, w, pooled=None, head=None):
+        """a block's two convolutions; src None: the block reads the float32 network input (first-layer kernel)"""
+        a = first(h, w) if src is None else conv3(blk + ".c1", blk + ".b1", src, skip, h, w)
+        return conv3(blk + ".c2", blk + ".b2", a, None, h, w, pooled=pooled, head=head)
+
+    def conv_t(name, src, h, w):
+        """Conv2DTranspose(3x3, stride 2): one launch per output parity class, into one 2h x 2w tensor"""
+        up = buf(2 * h, 2 * w, hw[name + ".00"][0].shape[2] * 128)
+        for py in (0, 1):
+            for px in (0, 1):
+                cls = "%s.%d%d" % (name, py, px)
+                launch_conv(cls, _conv_desc(hw[cls], planes, fmt, src, None, h, w, hw["f:" + name + ".b"], out=up, out_h=2 * h, out_w=2 * w,
+                                            stride=2, oy=py, ox=px))
+        return up
+
+    with torch.no_grad():
+        skips, cur, h, w = [], None, H, W
+        for i in range(3):                    # encoder: MaxPool2D(2) comes out of the second convolution's epilogue
+            pooled = buf(h // 2, w // 2, net.filters[i])
+            skips.append(double("d%d" % i, cur, None, h, w, pooled=pooled))
+            cur, h, w = pooled, h // 2, w // 2
+        cur = double("mid", cur, None, h, w)  # bottleneck
+        for i in range(3):                    # decoder: the convolution reads [up-sampled, skip] as one concatenated tensor
+            up = conv_t("u%d.t" % i, cur, h, w)
+            h, w = 2 * h, 2 * w
+            # the last convolution's epilogue computes the head: softmax probabilities instead of the layer's own output
+            probs = None
+            if i == 2 and not logits and not os.environ.get("TISSUE_HIP_UNET_SEPARATE_HEAD"):
+                probs = torch.empty((1, 2, H, W), dtype=torch.float32, device=x.device)
+            cur = double("u%d" % i, up, skips[2 - i], h, w, head=probs)
+        if probs is not None:
+            return probs
+        out = torch.empty((1, 2, H, W), dtype=torch.float32, device=x.device)
+        timed("head %dx%d" % (H, W), 2.0 * H * W * 256,
+              lambda: _lib.check(lib.tip_unet_head_dev(D(cur), ctypes.c_long(H * W), D(hw["head"]), D(hw["f:head.b"]), D(out), planes, fmt,
+                                                       1 if logits else 0, stream)))
+    return out

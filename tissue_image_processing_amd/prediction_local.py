@@ -3,9 +3,12 @@
     find_desired_shape, normalize_channel                      pl.py:10-29
     build_unet_model / SegmentationPredictor                   pl.py:31-198
 
-The U-Net's dense 3x3 convolutions run through PyTorch-ROCm (MIOpen -> MFMA), as BASELINE.json's north_star
-prescribes for the weight/conv path; everything after the network (threshold, 5x5 closing, 7x7 erosion, boundary,
-watershed: pl.py:167-194) runs in libtissue_hip.so on the same resident buffers.
+The network (_UNet) runs on the hand-written HIP kernels of libtissue_hip.so (csrc/tip_unet_conv.h: implicit-GEMM convolutions
+on the 16-bit matrix cores with split float32 operands; driven by _unet_hip.py) for the reference's widths in float32 on extents
+that are multiples of 64 x 256, and otherwise -- or with TISSUE_HIP_UNET_ARITH=miopen -- as the torch expressions of the same
+layers (PyTorch-ROCm / MIOpen convolutions, the bias -> ReLU -> BatchNorm epilogue in the library).  Image preparation
+(percentiles, clip, scale, transpose, pad: pl.py:90-122) and everything after the network (threshold, 5x5 closing, 7x7 erosion,
+boundary, watershed: pl.py:167-194) run in libtissue_hip.so on the same resident buffers.
 
 Deliberate deviations from the reference (documented in DESIGN.md):
   * pl.py:96-135 writes nine debug TIFFs to hard-coded C:\\Users\\... paths on every call; not reproduced.
@@ -17,11 +20,11 @@ Deliberate deviations from the reference (documented in DESIGN.md):
 """
 import ctypes
 import os
-import threading
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _unet_hip
+from ._unet_hip import _ConvDesc, _MODES      # (tests and tools reach the descriptor through this module)
 
 
 def find_desired_shape(shape_y, shape_x):
@@ -62,14 +65,6 @@ def shares_runtime_with_torch(t):
         ok = _lib.load().tip_pointer_device(_lib.dptr(t.data_ptr())) == idx
         _shared_runtime[idx] = ok
     return ok
-
-
-_MODES = {  # mode -> (pieces per value, piece format of the C-ABI: 0 bf16, 1 fp16, products per term, dropped part of a term)
-    "f16x3": (2, 1, 3, "7.2e-7"),
-    "bf16x3": (2, 0, 3, "1.6e-5"),
-    "bf16x6": (3, 0, 6, "9e-8"),
-}
-_F16_ACT_SCALE = 16.0      # fp16 pieces: activations are stored times 2^4 (saturate beyond |v| = 4094, absolute floor 2^-29)
 
 
 def _unet_mode():
@@ -127,17 +122,6 @@ def unet_algorithmic_bytes(h, w):
     return total
 
 
-class _ConvDesc(ctypes.Structure):
-    """tip_unet_conv_desc of include/tissue_hip.h."""
-    _fields_ = [("in0", ctypes.c_void_p), ("in1", ctypes.c_void_p), ("c0", ctypes.c_int), ("c1", ctypes.c_int), ("h", ctypes.c_int),
-                ("w", ctypes.c_int), ("planes", ctypes.c_int), ("weights", ctypes.c_void_p), ("ntaps", ctypes.c_int),
-                ("dy", ctypes.c_int * 9), ("dx", ctypes.c_int * 9), ("cout", ctypes.c_int), ("bias", ctypes.c_void_p),
-                ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_h", ctypes.c_int),
-                ("out_w", ctypes.c_int), ("sy", ctypes.c_int), ("sx", ctypes.c_int), ("oy", ctypes.c_int), ("ox", ctypes.c_int),
-                ("pool_out", ctypes.c_void_p), ("head_w", ctypes.c_void_p), ("head_b", ctypes.c_void_p), ("head_out", ctypes.c_void_p),
-                ("format", ctypes.c_int), ("acc_scale", ctypes.c_float), ("tf", ctypes.c_int), ("nmask", ctypes.c_int * 9)]
-
-
 _FILTERS = (128, 256, 512)
 _BN_EPS = 1e-3  # Keras BatchNormalization default
 
@@ -158,32 +142,6 @@ def _percentile_linear_t(flat_sorted, q):
     if gamma >= 0.5:
         res = hi - diff * (1 - gamma)
     return res
-
-
-_FORWARD_GATES = {}
-_FORWARD_GATES_LOCK = threading.Lock()
-
-
-def _forward_gate(device_index):
-    with _FORWARD_GATES_LOCK:
-        g = _FORWARD_GATES.get(device_index)
-        if g is None:
-            g = _FORWARD_GATES[device_index] = {"lock": threading.Lock(), "event": None, "stream": None}
-        return g
-
-
-_SIDE = threading.local()
-
-
-def _side_streams(device):
-    """three extra streams per (thread, device) for the transposed convolution's parity classes"""
-    import torch
-    d = getattr(_SIDE, "streams", None)
-    if d is None:
-        d = _SIDE.streams = {}
-    if device.index not in d:
-        d[device.index] = [torch.cuda.Stream(device=device) for _ in range(3)]
-    return d[device.index]
 
 
 class _UNet(object):
@@ -211,6 +169,7 @@ class _UNet(object):
             os.environ.get("TISSUE_HIP_UNET_DTYPE", "fp32")]
         g = torch.Generator().manual_seed(seed)
         self.p = {}
+        self._hipw = {}                           # packed weights of the hand-written path, per arithmetic mode (_unet_hip.weights)
         it = iter(weights) if weights is not None else None
 
         def expect(name, arr, shape):
@@ -335,116 +294,14 @@ class _UNet(object):
             else:
                 continue
             self.p[k] = new.to(device=v.device, dtype=v.dtype).view(v.shape)
-        for m in list(_MODES):
-            if hasattr(self, "_hipw_" + m):
-                delattr(self, "_hipw_" + m)
+        self._hipw.clear()
 
-    # -- hand-written convolution path (csrc/tip_unet_conv.h) ---------------------------------------------------------------
+    # -- hand-written convolution path (csrc/tip_unet_conv.h, driven by _unet_hip.py) -----------------------------------------------
     def _split_pack(self, taps, planes, fmt=0):
-        """taps: (T, Cin, Cout) float32 on the device -> packed split weights [T][Cin/16][Cout/128][plane][128][16] in bf16 (fmt 0) or
-        fp16 (fmt 1: the caller has scaled the taps into fp16's range) pieces.
-
-        Row order inside every group of 32 output channels: row 8 g + 4 h + j (g < 4, h < 2, j < 4) holds channel 16 h + 4 g + j --
-        the matrix core's output register i = 4 g + j of half-wave h is then channel 16 h + i, i.e. a lane of the kernel ends up with
-        sixteen ADJACENT channels of its pixel (csrc/tip_unet_conv.h, epilogue)."""
-        torch = self.torch
-        T, cin, cout = taps.shape
-        pieces, rest = [], taps.float()
-        for _ in range(planes):
-            h = rest.to(torch.float16 if fmt else torch.bfloat16)
-            pieces.append(h)
-            rest = rest - h.float()
-        row = torch.arange(32, device=taps.device)
-        chan = 16 * ((row >> 2) & 1) + 4 * (row >> 3) + (row & 3)          # channel (within its group of 32) stored in each row
-        pk = torch.stack(pieces, 0).view(planes, T, cin // 16, 16, cout // 32, 32)[..., chan]
-        pk = pk.reshape(planes, T, cin // 16, 16, cout // 128, 128)
-        return pk.permute(1, 2, 4, 0, 5, 3).contiguous()
+        return _unet_hip.split_pack(taps, planes, fmt)
 
     def _hip_weights(self, mode):
-        """Packed weights and per-channel constants of one arithmetic mode.  fp16 pieces (mode f16x3) carry power-of-two scales:
-        activations are stored times A = 2^4, a layer's weights times W = the power of two that puts its largest weight in
-        [2^14, 2^15); the kernel multiplies the accumulator by 1 / (A W) before the bias (entry 3 of a layer's tuple), the
-        BatchNorm scale / shift (and a bias-only layer's bias and accumulator factor) are multiplied by A, the head's weights by
-        1 / A -- exact, so the stored values are A times what the unscaled network computes, bit for bit."""
-        key = "_hipw_" + mode
-        if getattr(self, key, None) is not None:
-            return getattr(self, key)
-        torch = self.torch
-        p = self.p
-        planes, fmt = _MODES[mode][:2]
-        act = _F16_ACT_SCALE if fmt else 1.0
-        hw = {}
-
-        def pack(taps, bias_only):
-            if not fmt:
-                return self._split_pack(taps, planes), 1.0
-            big = float(taps.abs().max())
-            wscale = 2.0 ** (14 - int(np.floor(np.log2(big)))) if big > 0 and np.isfinite(big) else 1.0
-            inv = 1.0 / (act * wscale)
-            return self._split_pack(taps * wscale, planes, fmt), (inv * act if bias_only else inv)
-
-        def conv3(name):
-            w = p[name + ".w"].float()                                  # (cout, cin, 3, 3): cross-correlation, tap (ky, kx) reads (y + ky - 1, x + kx - 1)
-            taps = torch.stack([w[:, :, ky, kx].t() for ky in range(3) for kx in range(3)], 0)
-            wp, inv = pack(taps, False)
-            hw[name] = (wp, [ky - 1 for ky in range(3) for kx in range(3)], [kx - 1 for ky in range(3) for kx in range(3)], inv)
-
-        def conv_t(name):
-            # conv_transpose2d(stride 2): out[2 i + k] += in[i] w[k], cropped to the first 2N rows / columns.  Even outputs take
-            # k = 0 from i = o / 2 and k = 2 from i = o / 2 - 1, odd outputs k = 1 from i = (o - 1) / 2: four parity classes
-            w = p[name + ".w"].float()                                  # (cin, cout, 3, 3)
-            per_axis = {0: [(0, 0), (2, -1)], 1: [(1, 0)]}             # parity -> [(k, input offset)]
-            for py in (0, 1):
-                for px in (0, 1):
-                    tl = [(ky, dy, kx, dx) for ky, dy in per_axis[py] for kx, dx in per_axis[px]]
-                    taps = torch.stack([w[:, :, ky, kx] for ky, _, kx, _ in tl], 0)
-                    wp, inv = pack(taps, True)
-                    hw["%s.%d%d" % (name, py, px)] = (wp, [t[1] for t in tl], [t[3] for t in tl], inv)
-
-        def conv_t_fused(name):
-            # the same transposed convolution as ONE launch (csrc/tip_unet_conv.h, template TF): the taps are the four input offsets
-            # (dy, dx) = (0, 0), (0, -1), (-1, 0), (-1, -1); output channels are VIRTUAL, ordered [group of 32][class py * 2 + px][32]:
-            # class (py, px) takes kernel element (ky, kx) = (py ? 1 : (dy ? 2 : 0), px ? 1 : (dx ? 2 : 0)) where its parity has one
-            # at that offset (odd parities only at offset 0), zeros elsewhere -- nmask says which classes a tap feeds
-            w = p[name + ".w"].float()                                  # (cin, cout, 3, 3)
-            cin, cout = int(w.shape[0]), int(w.shape[1])
-            offs = [(0, 0), (0, -1), (-1, 0), (-1, -1)]
-            taps = torch.zeros((4, cin, cout // 32, 4, 32), dtype=torch.float32, device=w.device)
-            masks = []
-            for t, (dy, dx) in enumerate(offs):
-                m = 0
-                for py in (0, 1):
-                    for px in (0, 1):
-                        if (py == 1 and dy != 0) or (px == 1 and dx != 0):
-                            continue
-                        ky = 1 if py else (2 if dy else 0)
-                        kx = 1 if px else (2 if dx else 0)
-                        taps[t, :, :, py * 2 + px, :] = w[:, :, ky, kx].reshape(cin, cout // 32, 32)
-                        m |= 1 << (py * 2 + px)
-                masks.append(m)
-            wp, inv = pack(taps.reshape(4, cin, 4 * cout), True)
-            bias = p[name + ".b"].float().reshape(cout // 32, 1, 32).expand(cout // 32, 4, 32).reshape(-1)
-            hw[name + ".fused"] = (wp, [o[0] for o in offs], [o[1] for o in offs], inv, masks, (bias * act).contiguous())
-
-        for blk in ("d0", "d1", "d2", "mid", "u0", "u1", "u2"):
-            if blk != "d0":
-                conv3(blk + ".c1")
-            conv3(blk + ".c2")
-        for i in range(3):
-            conv_t("u%d.t" % i)
-            if planes == 2:
-                conv_t_fused("u%d.t" % i)
-        w0 = p["d0.c1.w"].float()                                       # (128, 2, 3, 3) -> [tap][ci][cout]
-        hw["first"] = w0.permute(2, 3, 1, 0).reshape(18, 128).contiguous()
-        hw["head"] = (p["head.w"].float().reshape(2, 128) / act).contiguous()
-        for k in list(p):
-            if k.endswith((".b", ".s", ".t")) and not k.endswith(".t.w"):
-                v = p[k].float().reshape(-1)
-                # times A: BatchNorm scale (".s") / shift (".t"), and the bias of a bias-only (transposed convolution) layer (".t.b")
-                scaled = k.endswith((".s", ".t", ".t.b"))
-                hw["f:" + k] = (v * act if scaled else v).contiguous()
-        setattr(self, key, hw)
-        return hw
+        return _unet_hip.weights(self, mode)
 
     def hip_path_ok(self, x):
         """The hand-written kernels tile every level's grid in 8 x 32 pixels: extents that are multiples of 64 x 256 (what
@@ -455,169 +312,12 @@ class _UNet(object):
                 and self.filters == _FILTERS and self.bottleneck == 1024        # (the reference's widths, pl.py:60-69)
                 and x.shape[2] % 64 == 0 and x.shape[3] % 256 == 0 and shares_runtime_with_torch(x))
 
-    def _forward_gated(self, x, logits):
-        """One network at a time on a device.  Frames in flight (worker threads, each with its own stream: movie.py, bench.py) would
-        otherwise run their forward passes CONCURRENTLY -- the queues share the chip kernel by kernel, every pass takes N times as
-        long, all of them end together and the frames' tails (small kernels, host stages) then run together with nothing to
-        hide behind: the kernel trace shows the matrix cores idle for 8.5 % of the time (profiles/r04n_*).  Here a pass waits ON THE
-        DEVICE (stream.wait_event, no host stall) for the pass queued before it, so that the passes run back to back in ticket order
-        and the other frames' tails and projections fill in beside them.  TISSUE_HIP_UNET_SERIAL=0 restores the free-for-all."""
-        torch = self.torch
-        if os.environ.get("TISSUE_HIP_UNET_SERIAL", "1") == "0":
-            return self._forward_hip(x, logits)
-        gate = _forward_gate(x.device.index)
-        with gate["lock"]:
-            s = torch.cuda.current_stream(x.device)
-            if gate["event"] is not None and gate["stream"] != s.cuda_stream:
-                s.wait_event(gate["event"])
-            out = self._forward_hip(x, logits)
-            ev = torch.cuda.Event()
-            ev.record(s)
-            gate["event"], gate["stream"] = ev, s.cuda_stream
-        return out
-
-    def _forward_hip(self, x, logits):
-        torch = self.torch
-        mode = _unet_mode()
-        planes, fmt = _MODES[mode][:2]
-        hw = self._hip_weights(mode)
-        self.last_mode = mode                 # (bench.py / tests: which arithmetic the last forward pass really used)
-        lib = _lib.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        H, W = int(x.shape[2]), int(x.shape[3])
-        x = x.to(torch.float32).contiguous()
-        D = lambda t: ctypes.c_void_p(t.data_ptr())
-
-        trace = getattr(self, "trace", None)      # tools/unet_layers.py: [(layer, flop, event, event)] per launch
-        tconv_mode = os.environ.get("TISSUE_HIP_UNET_TCONV", "split")
-        side = _side_streams(x.device) if tconv_mode == "parallel" else None
-
-        def timed(name, flop, fn):
-            if trace is None:
-                return fn()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            r = fn()
-            e1.record()
-            trace.append((name, flop, e0, e1))
-            return r
-
-        def buf(h, w, c):
-            return torch.empty((planes, h, w, c), dtype=torch.float16 if fmt else torch.bfloat16, device=x.device)
-
-        def conv(name, src, skip, h, w, bn, out=None, oh=None, ow=None, sy=1, sx=1, oy=0, ox=0, bias=None, pooled=None, head=None, fused_t=False,
-                 on=None):
-            wp, dy, dx, inv = hw[name][:4]
-            cout = wp.shape[2] * 128
-            d = _ConvDesc()
-            d.format, d.acc_scale = fmt, inv
-            if fused_t:
-                d.tf = 1
-                for i, m in enumerate(hw[name][4]):
-                    d.nmask[i] = m
-            d.in0, d.c0 = src.data_ptr(), src.shape[3]
-            d.in1, d.c1 = (skip.data_ptr(), skip.shape[3]) if skip is not None else (None, 0)
-            d.h, d.w, d.planes = h, w, planes
-            d.weights, d.ntaps = wp.data_ptr(), len(dy)
-            for i in range(len(dy)):
-                d.dy[i], d.dx[i] = dy[i], dx[i]
-            d.cout = cout
-            if bn is not None:
-                d.bias, d.scale, d.shift = hw["f:" + name + ".b"].data_ptr(), hw["f:" + bn + ".s"].data_ptr(), hw["f:" + bn + ".t"].data_ptr()
-            elif fused_t:
-                d.bias, d.scale, d.shift = hw[name][5].data_ptr(), None, None
-            else:
-                d.bias, d.scale, d.shift = hw["f:" + bias + ".b"].data_ptr(), None, None
-            if head is not None:                  # the network's head in this layer's epilogue: the layer's own output is not stored
-                d.head_w, d.head_b, d.head_out = hw["head"].data_ptr(), hw["f:head.b"].data_ptr(), head.data_ptr()
-                out, oh, ow = None, h, w
-            elif out is None:
-                out, oh, ow = buf(h, w, cout), h, w
-            d.out, d.out_h, d.out_w, d.sy, d.sx, d.oy, d.ox = (out.data_ptr() if out is not None else None), oh, ow, sy, sx, oy, ox
-            d.pool_out = pooled.data_ptr() if pooled is not None else None
-            timed("%s %dx%d %d+%d->%d x%d taps" % (name, h, w, d.c0, d.c1, cout // 4 if fused_t else cout, 9 if fused_t else len(dy)),
-                  2.0 * h * w * (9 * (cout // 4) if fused_t else len(dy) * cout) * (d.c0 + d.c1),
-                  lambda: _lib.check(lib.tip_unet_conv_dev(ctypes.byref(d), stream if on is None else ctypes.c_void_p(on.cuda_stream))))
-            return out
-
-        def double(blk, src, skip, h, w, first=False, pooled=None, head=None):
-            if first:
-                a = buf(h, w, 128)
-                timed("first %dx%d 2->128" % (h, w), 2.0 * h * w * 18 * 128,
-                      lambda: _lib.check(lib.tip_unet_conv_first_dev(D(x), h, w, D(hw["first"]), D(hw["f:d0.c1.b"]), D(hw["f:d0.b1.s"]),
-                                                                     D(hw["f:d0.b1.t"]), D(a), planes, fmt, stream)))
-            else:
-                a = conv(blk + ".c1", src, skip, h, w, blk + ".b1")
-            return conv(blk + ".c2", a, None, h, w, blk + ".b2", pooled=pooled, head=head)
-
-        def pool(t, h, w):
-            o = buf(h // 2, w // 2, t.shape[3])
-            timed("pool %dx%d x%d" % (h, w, t.shape[3]), 0.0,
-                  lambda: _lib.check(lib.tip_unet_pool2_dev(D(t), h, w, int(t.shape[3]), planes, fmt, D(o), stream)))
-            return o
-
-        with torch.no_grad():
-            skips = []
-            h, w = H, W
-            cur = None
-            for i in range(3):
-                nxt = buf(h // 2, w // 2, _FILTERS[i])           # MaxPool2D(2) comes out of the second convolution's epilogue
-                f = double("d%d" % i, cur, None, h, w, first=(i == 0), pooled=nxt)
-                skips.append(f)
-                cur = nxt
-                h, w = h // 2, w // 2
-            cur = double("mid", cur, None, h, w)
-            for i in range(3):
-                name = "u%d.t" % i
-                cout = hw[name + ".00"][0].shape[2] * 128
-                up = buf(2 * h, 2 * w, cout)
-                if planes == 2 and tconv_mode == "fused":
-                    # ONE launch for the four output parity classes (nine products per staged tile; bit-identical).  Measured SLOWER
-                    # than the four launches (6.44 against 6.02 ms over the three layers at 2048^2): a workgroup then covers 32 output
-                    # channels and its four steps per chunk carry 24 / 12 / 12 / 6 MFMAs per wave behind a barrier each, where the
-                    # four-tap class launch carries 24 behind each -- the per-step barrier cost outweighs the shared staging
-                    conv(name + ".fused", cur, None, h, w, None, out=up, oh=2 * h, ow=2 * w, sy=2, sx=2, fused_t=True)
-                elif tconv_mode == "parallel":
-                    # the four parity classes side by side on four streams (they read one tensor and write disjoint pixels): the idea was
-                    # that the one- and two-tap launches (bound by the L2 -> LDS copies of a tile they use once or twice) and the four-tap
-                    # launch (bound by the matrix pipe) fill each other's gaps.  Measured SLOWER: forward pass 49.7 / 50.0 ms against
-                    # 48.0 / 48.8 ms on one box -- a 512-thread workgroup has its CU to itself whichever launch it belongs to, so nothing
-                    # overlaps inside a CU and the fork / join events add their latency.  An experiment switch, like "fused".
-                    main = torch.cuda.current_stream(x.device)
-                    fork = torch.cuda.Event()
-                    fork.record(main)
-                    for k, (py, px) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
-                        on = main if k == 0 else side[k - 1]
-                        if k:
-                            on.wait_event(fork)
-                        conv("%s.%d%d" % (name, py, px), cur, None, h, w, None, out=up, oh=2 * h, ow=2 * w, sy=2, sx=2, oy=py, ox=px, bias=name, on=on)
-                        if k:
-                            join = torch.cuda.Event()
-                            join.record(on)
-                            main.wait_event(join)
-                else:
-                    for py in (0, 1):
-                        for px in (0, 1):
-                            conv("%s.%d%d" % (name, py, px), cur, None, h, w, None, out=up, oh=2 * h, ow=2 * w, sy=2, sx=2, oy=py, ox=px, bias=name)
-                h, w = 2 * h, 2 * w
-                fuse_head = i == 2 and not logits and not os.environ.get("TISSUE_HIP_UNET_SEPARATE_HEAD")
-                if fuse_head:                          # softmax probabilities straight out of the last convolution's epilogue
-                    out = torch.empty((1, 2, H, W), dtype=torch.float32, device=x.device)
-                    double("u%d" % i, up, skips[2 - i], h, w, head=out)
-                    return out
-                cur = double("u%d" % i, up, skips[2 - i], h, w)
-            out = torch.empty((1, 2, H, W), dtype=torch.float32, device=x.device)
-            timed("head %dx%d" % (H, W), 2.0 * H * W * 256,
-                  lambda: _lib.check(lib.tip_unet_head_dev(D(cur), ctypes.c_long(H * W), D(hw["head"]), D(hw["f:head.b"]), D(out), planes, fmt,
-                                                           1 if logits else 0, stream)))
-        return out
-
     def forward(self, x, logits=False):
         """x: (1, C, H, W) tensor on the device -> class probabilities (1, 2, H, W) float32."""
         torch = self.torch
         F = torch.nn.functional
         if self.hip_path_ok(x):
-            return self._forward_gated(x, logits)
+            return _unet_hip.forward(self, x, _unet_mode(), logits)
         self.last_mode = "miopen"
         with torch.no_grad():
             x = x.to(self.dtype).contiguous(memory_format=torch.channels_last)
