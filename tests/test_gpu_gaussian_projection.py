@@ -197,7 +197,7 @@ def test_projection_full_size_properties(mods):
 
 
 def test_projection_fast_path_equals_generic_path(mods):
-    """Register-sliding / sparse-mask kernels are the same arithmetic as the generic kernels: bit-identical output."""
+    """Register-sliding / fused-mask kernels are the same arithmetic as the generic kernels: bit-identical output."""
     _, sp, _ = mods
     from tissue_image_processing_amd import _lib, synthetic
     for shape, seed in [((9, 200, 264), 1), ((5, 77, 136), 2), ((30, 128, 512), 3)]:
@@ -212,7 +212,7 @@ def test_projection_fast_path_equals_generic_path(mods):
 
 def test_fused_mask_kernel_equals_separate_kernels(mods):
     """k_mask_wmax_fused (y pass + x pass of the blurred one-hot mask + weighted z-max in one kernel, the mask volume never
-    written) against the separate sparse kernels: bit-identical, with airyscan offset, three channels, a shifted second
+    written) against the separate dense kernels: bit-identical, with airyscan offset, three channels, a shifted second
     mask, frames that are not multiples of the tile and a rough z-map (random planes: wide z ranges per tile)."""
     _, sp, _ = mods
     from tissue_image_processing_amd import _lib, synthetic

@@ -105,6 +105,8 @@ struct TapsF {   // float32 copy for the certified fast score passes
 
 int make_taps(Taps &t, const double *w, int n);  // validates odd + symmetric (scipy's symmetric branch)
 int libm_taps(double sigma, double truncate, double *w, int cap);
+// tip_gauss.hip: one scipy-order correlate pass on device volumes.  dtype 0 = f32, 1 = f64.  force: 0 auto, 1 generic, 2 long
+int correlate1d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, int axis, const Taps &t, int force);
 
 // tip_optflow.hip: the TV-L1 flow on device planes, asynchronous unless warps_host is given; returns the pyramid's level
 // count or an error code.  dtype: the public codes of tip_optical_flow_tvl1 or OF_F64_AS_U16, a float64 plane truncated to

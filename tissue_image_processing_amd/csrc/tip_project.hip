@@ -5,27 +5,38 @@
 //   P3  Gaussian (0.5,1,1)  (sp.py:37)                              exact scipy-order correlate passes
 //   P4  Gaussian (0.5,30,30) score (sp.py:55)                       long-kernel passes (tip_corr.h)
 //   P5  argmax over z, first maximum (sp.py:61)
-//   P6/P7 one-hot mask + Gaussian (1,2,2) (sp.py:62-71)             z pass = ZxZ table, y pass from the z-map,
-//   P8  per-channel max_z(image * mask) -> float64 (sp.py:72-81)    x pass fused with the weighted z-max
+//   P6/P7 one-hot mask + Gaussian (1,2,2) (sp.py:62-71)             z pass = ZxZ table; y pass, x pass and the weighted z-max
+//   P8  per-channel max_z(image * mask) -> float64 (sp.py:72-81)    in one kernel (k_mask_wmax_fused), or the dense fallback:
+//                                                                   y pass from the z-map, x pass fused with the z-max
 #include "tip_slide.h"
 #include "tip_preblur.h"
 #include "tip_corr.h"
 #include "tip_corr_f16.h"
-#include <atomic>
 #include "tip_manifold.h"
+#include "tip_project_binned.h"
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 namespace tip {
-
-
-int correlate1d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, int axis, const Taps &t, int force);
 
 struct ClipInfo {
     double p95d;
     float p95;
     int has;
 };
+
+// ---- P1: the airyscan offset (sp.py:26-29), on the integer sample for the histograms and on the float for the readers ----
+__device__ __forceinline__ int airy_offset(int v, int airy)
+{
+    if (airy) { v -= 10000; if (v < 0) v = 0; }
+    return v;
+}
+__device__ __forceinline__ float airy_offset(float v, int airy)
+{
+    if (airy) { v -= 10000.f; if (v < 0.f) v = 0.f; }
+    return v;
+}
 
 // ---- P2: histogram of the (offset-corrected) reference channel -----------------------------------------
 // One persistent 1024-thread block per CU with a private 65536-bin LDS histogram of 16-bit counters packed two per dword.
@@ -57,8 +68,7 @@ __global__ void __launch_bounds__(1024) k_hist_u16(const uint16_t *__restrict__ 
                 for (int j = 0; j < 4; ++j) {
 #pragma unroll
                     for (int s = 0; s < 2; ++s) {
-                        int val = (int)((w[j] >> (16 * s)) & 0xffffu);
-                        if (airy) { val -= 10000; if (val < 0) val = 0; }
+                        const int val = airy_offset((int)((w[j] >> (16 * s)) & 0xffffu), airy);
                         atomicAdd(&h[val >> 1], 1u << (16 * (val & 1)));
                     }
                 }
@@ -68,8 +78,7 @@ __global__ void __launch_bounds__(1024) k_hist_u16(const uint16_t *__restrict__ 
                 const long i0 = base + ((long)k * 1024 + threadIdx.x) * 8;
                 for (int j = 0; j < 8; ++j) {
                     if (i0 + j < n) {
-                        int val = in[i0 + j];
-                        if (airy) { val -= 10000; if (val < 0) val = 0; }
+                        const int val = airy_offset((int)in[i0 + j], airy);
                         atomicAdd(&h[val >> 1], 1u << (16 * (val & 1)));
                     }
                 }
@@ -107,8 +116,7 @@ __global__ void __launch_bounds__(1024) k_hist_u16_box(const uint16_t *__restric
         const long i = base + (long)k * 1024 + threadIdx.x;
         if (i < n) {
             const int x = (int)(i % bx), y = (int)((i / bx) % by), z = (int)(i / ((long)bx * by));
-            int val = in[((long)(z0 + z) * Y + (y0 + y)) * X + (x0 + x)];
-            if (airy) { val -= 10000; if (val < 0) val = 0; }
+            const int val = airy_offset((int)in[((long)(z0 + z) * Y + (y0 + y)) * X + (x0 + x)], airy);
             atomicAdd(&h[val >> 1], 1u << (16 * (val & 1)));
         }
     }
@@ -199,8 +207,7 @@ struct LoadU16Clip {
     const ClipInfo *clip;
     __device__ __forceinline__ double operator()(int z, int y, int x) const
     {
-        float f = (float)p[z * sz + y * sy + x];
-        if (airy) { f -= 10000.f; if (f < 0.f) f = 0.f; }
+        float f = airy_offset((float)p[z * sz + y * sy + x], airy);
         if (clip->has && f > clip->p95) f = clip->p95;
         return (double)f;
     }
@@ -283,8 +290,7 @@ __global__ void __launch_bounds__(256) k_xpass_wmax(const float *__restrict__ ym
 #pragma unroll
         for (int c = 0; c < MAXC; ++c) {
             if (c < C && ((chan_mask >> c) & 1u)) {
-                float v = (float)img[((long)c * Zfull + zlo + z) * P + (long)y * X + x];
-                if (airy) { v -= 10000.f; if (v < 0.f) v = 0.f; }
+                const float v = airy_offset((float)img[((long)c * Zfull + zlo + z) * P + (long)y * X + x], airy);
                 const float pr = v * m;
                 // np.max over z of a float32 array; first z initialises
                 mx[c] = z == 0 ? pr : (pr > mx[c] ? pr : mx[c]);
@@ -296,139 +302,16 @@ __global__ void __launch_bounds__(256) k_xpass_wmax(const float *__restrict__ ym
         if (c < C && ((chan_mask >> c) & 1u)) proj[(long)c * P + (long)y * X + x] = (double)mx[c];
 }
 
-// ---- fast mask stage: the blurred one-hot mask is exactly zero more than 4 planes away from every chosen plane that
-// feeds it, and adding exact zeros changes nothing, so only the planes inside [zmin-4, zmax+4] of the 17-wide windows
-// are computed (same arithmetic, same order, bit-identical to the dense kernels above) -----------------------------------
-constexpr int MASK_R = 8, MASK_W = 2 * MASK_R + 1, MASK_ZR = 4;
-
-template <int SEG>
-__global__ void __launch_bounds__(256) k_mask_y_sparse(const float *__restrict__ table, const int32_t *__restrict__ zsel, int Zs,
-                                                       int Y, int X, Taps taps, float *__restrict__ out,
-                                                       int32_t *__restrict__ zrange)
-{
-    extern __shared__ float sT[];  // Zs*Zs: T[z*Zs + z0]
-    for (int i = threadIdx.x; i < Zs * Zs; i += blockDim.x) sT[i] = table[i];
-    __syncthreads();
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= X) return;
-    const int y0 = blockIdx.y * (SEG * MASK_W);
-    const long P = (long)Y * X;
-    int win[MASK_W];
-#pragma unroll
-    for (int i = 0; i < MASK_W; ++i) win[i] = zsel[(long)clampi(y0 - MASK_R + i, 0, Y - 1) * X + x];
-    for (int s = 0; s < SEG; ++s) {
-#pragma unroll
-        for (int o = 0; o < MASK_W; ++o) {
-            const int y = y0 + s * MASK_W + o;
-            if (y < Y) {
-                int zmin = win[0], zmax = win[0];
-#pragma unroll
-                for (int i = 1; i < MASK_W; ++i) { zmin = min(zmin, win[i]); zmax = max(zmax, win[i]); }
-                zrange[(long)y * X + x] = zmin | (zmax << 16);
-                const int za = max(zmin - MASK_ZR, 0), zb = min(zmax + MASK_ZR, Zs - 1);
-                float *dst = out + (long)y * X + x;
-                for (int z = 0; z < za; ++z) dst[(long)z * P] = 0.f;
-                for (int z = za; z <= zb; ++z) {
-                    const float *Tz = sT + z * Zs;
-                    double tmp = (double)Tz[win[(o + MASK_R) % MASK_W]] * taps.w[MASK_R];
-#pragma unroll
-                    for (int d = MASK_R; d >= 1; --d)
-                        tmp += ((double)Tz[win[(o + MASK_R - d) % MASK_W]] + (double)Tz[win[(o + MASK_R + d) % MASK_W]]) *
-                               taps.w[MASK_R - d];
-                    dst[(long)z * P] = (float)tmp;
-                }
-                for (int z = zb + 1; z < Zs; ++z) dst[(long)z * P] = 0.f;
-            }
-            win[o % MASK_W] = zsel[(long)clampi(y + MASK_R + 1, 0, Y - 1) * X + x];
-        }
-    }
-}
-
-template <int MAXC>
-__global__ void __launch_bounds__(256) k_xpass_wmax_sparse(const float *__restrict__ ymask, const int32_t *__restrict__ zrange,
-                                                           const uint16_t *__restrict__ img, int C, int Zfull, int zlo, int Zs,
-                                                           int Y, int X, int airy, unsigned chan_mask, Taps taps,
-                                                           double *__restrict__ proj)
-{
-    constexpr int N = 8 + 2 * MASK_R;  // 24 inputs for 8 outputs
-    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 8;
-    const int y = blockIdx.y;
-    if (x0 >= X) return;
-    const long P = (long)Y * X;
-    const bool interior = x0 - MASK_R >= 0 && x0 + 8 + MASK_R <= X && (X & 3) == 0;
-    int zmin = 1 << 30, zmax = -1;
-    for (int i = 0; i < N; ++i) {
-        const int r = zrange[(long)y * X + clampi(x0 - MASK_R + i, 0, X - 1)];
-        zmin = min(zmin, r & 0xffff);
-        zmax = max(zmax, r >> 16);
-    }
-    const int za = max(zmin - MASK_ZR, 0), zb = min(zmax + MASK_ZR, Zs - 1);
-    float mx[MAXC][8];
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) mx[c][k] = 0.f;
-    for (int z = za; z <= zb; ++z) {
-        const float *row = ymask + (long)z * P + (long)y * X;
-        float v[N];
-        if (interior) {
-#pragma unroll
-            for (int i = 0; i < N / 4; ++i) {
-                const float4 f = *reinterpret_cast<const float4 *>(row + x0 - MASK_R + 4 * i);
-                v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < N; ++i) v[i] = row[clampi(x0 - MASK_R + i, 0, X - 1)];
-        }
-        float m[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            double tmp = (double)v[k + MASK_R] * taps.w[MASK_R];
-#pragma unroll
-            for (int d = MASK_R; d >= 1; --d)
-                tmp += ((double)v[k + MASK_R - d] + (double)v[k + MASK_R + d]) * taps.w[MASK_R - d];
-            m[k] = (float)tmp;
-        }
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            if (c < C && ((chan_mask >> c) & 1u)) {
-                const uint16_t *ip = img + ((long)c * Zfull + zlo + z) * P + (long)y * X + x0;
-                unsigned short pix[8];
-                if (x0 + 8 <= X && (X & 7) == 0) {
-                    const uint4 u = *reinterpret_cast<const uint4 *>(ip);
-                    pix[0] = u.x & 0xffff; pix[1] = u.x >> 16; pix[2] = u.y & 0xffff; pix[3] = u.y >> 16;
-                    pix[4] = u.z & 0xffff; pix[5] = u.z >> 16; pix[6] = u.w & 0xffff; pix[7] = u.w >> 16;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) pix[k] = x0 + k < X ? ip[k] : 0;
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (x0 + k < X) {
-                        float val = (float)pix[k];
-                        if (airy) { val -= 10000.f; if (val < 0.f) val = 0.f; }
-                        const float pr = val * m[k];
-                        mx[c][k] = pr > mx[c][k] ? pr : mx[c][k];
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c)
-        if (c < C && ((chan_mask >> c) & 1u))
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (x0 + k < X) proj[(long)c * P + (long)y * X + x0 + k] = (double)mx[c][k];
-}
-
 // ---- P7 y + x pass and P8 fused: the blurred one-hot mask never reaches HBM -----------------------------------------------
+// The mask is exactly zero more than MASK_ZR = 4 planes away from every chosen plane that feeds it (9 z taps), and adding
+// exact zeros changes nothing, so only the planes inside [zmin - 4, zmax + 4] of the 17-wide windows are computed: the same
+// arithmetic in the same order as the dense kernels above, bit-identical to them.
 // One block = FT_Y x FT_X outputs.  The chosen-plane map of the tile (+ 8-pixel halo, edges replicated) sits in LDS; plane
 // by plane the block computes the y pass of the tile's columns into an LDS buffer (exact scipy order, zero outside a
 // column's [zmin - 4, zmax + 4] exactly as the dense pass gives) and every thread finishes the x pass for its 8 outputs
-// from that buffer, multiplies with the raw stack and keeps the per-channel maximum -- the arithmetic of k_mask_y_sparse
-// + k_xpass_wmax_sparse, without writing the 503 MB mask volume and reading a third of it back.
+// from that buffer, multiplies with the raw stack and keeps the per-channel maximum -- without writing the 503 MB mask
+// volume and reading it back.
+constexpr int MASK_R = 8, MASK_W = 2 * MASK_R + 1, MASK_ZR = 4;
 constexpr int FT_Y = 16, FT_X = 128, FT_W = FT_X + 2 * MASK_R, FT_H = FT_Y + 2 * MASK_R;
 template <int MAXC>
 __global__ void __launch_bounds__(256) k_mask_wmax_fused(const float *__restrict__ table, const int32_t *__restrict__ zsel,
@@ -524,9 +407,7 @@ __global__ void __launch_bounds__(256) k_mask_wmax_fused(const float *__restrict
                     }
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {
-                        float val = (float)pix[k];
-                        if (airy) { val -= 10000.f; if (val < 0.f) val = 0.f; }
-                        const float pr = val * m[k];
+                        const float pr = airy_offset((float)pix[k], airy) * m[k];
                         mx[c][k] = pr > mx[c][k] ? pr : mx[c][k];
                     }
                 }
@@ -745,155 +626,6 @@ __global__ void __launch_bounds__(256) k_emit_zmaps(const int *__restrict__ best
     zsel_atoh[p] = ca;
 }
 
-// build_manifold with bin_size > 1 (sp.py:56-65): the (Yb, Xb) plane map of the binned score goes back to the frame through
-// skimage.transform.resize(order 1, mode 'reflect') -- for 2-D arrays the bilinear warp of _warps_cy: source coordinate
-// a * i + b (a = n_in / n_out, b = a / 2 - 1 / 2) evaluated in float32, corners floor / ceil with numpy 'reflect' (mirror
-// without the edge: index -1 -> 1), top = (1 - dc) v00 + dc v01, bottom likewise, (1 - dr) top + dr bottom in double, float32
-// result -- and np.round (half to even).  The float result agrees with skimage's to ~1e-6 (upstream's affine matrix comes out
-// of a least-squares estimate, LAPACK-dependent in the last bit); the rounded maps equal the reference's on every golden,
-// exact .5 ties included.  The atoh map is clip(plane + shift, 0, Z) BEFORE the resize, as upstream.
-__device__ __forceinline__ int mirror_index(int n, int c)
-{
-    if (n == 1) return 0;
-    const int p = 2 * (n - 1);
-    c = (c < 0 ? -c : c) % p;
-    return c > n - 1 ? p - c : c;
-}
-__global__ void __launch_bounds__(256) k_resize_round_zmaps(const int *__restrict__ bz, int Yb, int Xb, int Y, int X, int Z, int atoh_shift,
-                                                            int32_t *__restrict__ zsel, int32_t *__restrict__ zsel_atoh,
-                                                            int64_t *__restrict__ zmap, int *__restrict__ err)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= X) return;
-    const double sy = (double)Yb / Y, sx = (double)Xb / X;
-    const float ar = (float)sy, br = (float)(0.5 * sy - 0.5), ac = (float)sx, bc = (float)(0.5 * sx - 0.5);
-    const float fr = ar * (float)y + br, fc = ac * (float)x + bc;
-    const int r0 = (int)floorf(fr), c0 = (int)floorf(fc), r1 = (int)ceilf(fr), c1 = (int)ceilf(fc);
-    const double dr = (double)(fr - (float)r0), dc = (double)(fc - (float)c0);
-    const int y0 = mirror_index(Yb, r0), y1 = mirror_index(Yb, r1), x0 = mirror_index(Xb, c0), x1 = mirror_index(Xb, c1);
-    int res[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        auto at = [&](int yy, int xx) -> double {
-            int v = bz[(long)yy * Xb + xx];
-            if (k == 1 && atoh_shift != 0) { v += atoh_shift; v = v < 0 ? 0 : (v > Z ? Z : v); }
-            return (double)v;
-        };
-        const double top = (1.0 - dc) * at(y0, x0) + dc * at(y0, x1);
-        const double bot = (1.0 - dc) * at(y1, x0) + dc * at(y1, x1);
-        res[k] = (int)rintf((float)((1.0 - dr) * top + dr * bot));      // np.round: half to even (default rounding mode)
-    }
-    const long p = (long)y * X + x;
-    if (zmap) zmap[p] = res[0];
-    if (res[0] >= Z || res[1] >= Z) atomicOr(err, 1);
-    zsel[p] = res[0] >= Z ? Z - 1 : res[0];
-    zsel_atoh[p] = res[1] >= Z ? Z - 1 : res[1];
-}
-
-// ---- P4': bin_size > 1 (sp.py:39-65) -------------------------------------------------------------------------------
-// skimage.measure.block_reduce(vol, (1, b, b), np.mean / np.var) in float32 with numpy's summation order: every row of
-// a block (b contiguous samples, zeros beyond the frame) goes through numpy's pairwise_sum -- a running sum below 8
-// elements, else eight running partial sums combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) plus the tail -- and the row
-// sums are added up one after the other; mean = sum / float32(b*b); var = the same reduction of (x - mean)^2.
-__device__ __forceinline__ float pw_row_sum(const float *__restrict__ row, int b, int valid, float mean, bool sq)
-{
-    auto at = [&](int i) -> float {
-        const float v = i < valid ? row[i] : 0.f;
-        if (!sq) return v;
-        const float d = v - mean;
-        return d * d;
-    };
-    if (b < 8) {
-        float res = at(0);
-        for (int i = 1; i < b; ++i) res += at(i);
-        return res;
-    }
-    float r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = at(j);
-    int i = 8;
-    for (; i < b - (b % 8); i += 8)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] += at(i + j);
-    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < b; ++i) res += at(i);
-    return res;
-}
-
-template <bool VAR>
-__global__ void __launch_bounds__(256) k_block_reduce(const float *__restrict__ vol, float *__restrict__ out, int Z, int Y, int X,
-                                                      int b, int Yb, int Xb)
-{
-    const long o = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= (long)Z * Yb * Xb) return;
-    const int xb = (int)(o % Xb), yb = (int)((o / Xb) % Yb), z = (int)(o / ((long)Xb * Yb));
-    const int x0 = xb * b, y0 = yb * b;
-    const int valid = min(b, X - x0);
-    const float *base = vol + ((long)z * Y + y0) * X + x0;
-    const float cnt = (float)(b * b);
-    float acc = 0.f;
-    for (int r = 0; r < b; ++r) {
-        const float row = pw_row_sum(base + (long)r * X, b, y0 + r < Y ? valid : 0, 0.f, false);
-        acc = r == 0 ? row : acc + row;
-    }
-    const float mean = acc / cnt;
-    if (!VAR) { out[o] = mean; return; }
-    for (int r = 0; r < b; ++r) {
-        const float row = pw_row_sum(base + (long)r * X, b, y0 + r < Y ? valid : 0, mean, true);
-        acc = r == 0 ? row : acc + row;
-    }
-    out[o] = acc / cnt;
-}
-
-__global__ void __launch_bounds__(256) k_mul_f32(float *__restrict__ a, const float *__restrict__ b, long n)
-{
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = a[i] * b[i];
-}
-
-// skimage.transform.resize(score, (Z, Y, X)) (order 1, mode 'reflect' -> scipy map_coordinates 'mirror'; the z factor is
-// 1) fused with the first-maximum argmax over z.  One axis: coordinate f * (i + 0.5) - 0.5 in float64 with f = n_in /
-// n_out, mirrored at both ends, weights (1 - t, 1 - (1 - t)); scipy adds the four corner terms (v * wy) * wx in float64 in
-// the order (y0,x0), (y0,x1), (y1,x0), (y1,x1) and rounds to float32.
-struct LinTap { int i0, i1; double w0, w1; };
-__device__ __forceinline__ LinTap lin_tap(int i, int n_in, int n_out)
-{
-    LinTap t;
-    if (n_in <= 1) { t.i0 = 0; t.i1 = 0; t.w0 = 1.0; t.w1 = 0.0; return t; }
-    const double f = (double)n_in / (double)n_out;
-    double c = f * ((double)i + 0.5) - 0.5;
-    if (c < 0.0) c = -c;
-    const double fl = floor(c);
-    t.i0 = (int)fl;
-    t.i1 = t.i0 + 1;
-    if (t.i1 >= n_in) t.i1 = 2 * n_in - 2 - t.i1;
-    t.w0 = 1.0 - (c - fl);
-    t.w1 = 1.0 - t.w0;
-    return t;
-}
-
-__global__ void __launch_bounds__(256) k_resize_argmax(const float *__restrict__ binned, int Z, int Yb, int Xb, int Y, int X,
-                                                       int *__restrict__ best_z)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= X) return;
-    const LinTap ty = lin_tap(y, Yb, Y), tx = lin_tap(x, Xb, X);
-    float best = 0.f;
-    int bi = 0;
-    for (int z = 0; z < Z; ++z) {
-        const float *pl = binned + (long)z * Yb * Xb;
-        const double v00 = pl[(long)ty.i0 * Xb + tx.i0], v01 = pl[(long)ty.i0 * Xb + tx.i1];
-        const double v10 = pl[(long)ty.i1 * Xb + tx.i0], v11 = pl[(long)ty.i1 * Xb + tx.i1];
-        double t = (v00 * ty.w0) * tx.w0;
-        t += (v01 * ty.w0) * tx.w1;
-        t += (v10 * ty.w1) * tx.w0;
-        t += (v11 * ty.w1) * tx.w1;
-        const float s = (float)t;
-        if (z == 0 || s > best) { best = s; bi = z; }
-    }
-    best_z[(long)y * X + x] = bi;
-}
-
 static int resolve_taps(const double *given, double sigma, int expect, Taps &t)
 {
     double buf[256];
@@ -927,218 +659,283 @@ static int manifold_dev(const float *score, int Zs, int Y, int X, int *bestz, in
     return TIP_OK;
 }
 
+// ---- the host side: project_dev is a sequence of stages over one ProjJob ---------------------------------------------------
+struct ProjJob {
+    const uint16_t *czyx, *ref;     // the (C, Z, Y, X) stack; plane zlo of its reference channel
+    int C, Z, Y, X, zlo, Zs;        // planes [zlo, zlo + Zs) take part
+    long P, V;                      // Y * X, Zs * P
+    int min_z, ref_ch, method, bin, airyscan, atoh_shift;   // method: without the manifold flag
+    bool manifold;                  // sp.py:56-57: the spiral z-map instead of the argmax
+    bool fast;                      // X % 4 == 0 and no TIP_PROJECT_GENERIC: the register-sliding / fused / fp16 kernels
+    Taps k05, k1, k2, k30;
+    WsGuard ws;                     // a tier takes the buffers only it uses from here
+    float *A, *B;                   // two (Zs, Y, X) volumes
+    unsigned long long *hist;
+    ClipInfo *clip;
+    int32_t *zsel, *zsel_a;         // chosen plane per pixel, as it is and atoh-shifted
+    float *ident, *table;           // Zs x Zs: identity, and its z pass (the mask's z pass as a lookup)
+    int *err;                       // bit 1 plane index beyond the stack, 2 manifold hole, 8 fp16 tile range
+    double *proj;
+    int64_t *zmap;
+    hipStream_t stream;
+};
+
+static int check_args(const ProjJob &s, int zhi, bool tile)
+{
+    if (!s.czyx || !s.proj) return fail(TIP_ERR_ARG, "project: null pointer");
+    if (s.C < 1 || s.C > 8) return fail(TIP_ERR_ARG, "project: 1..8 channels supported (got %d)", s.C);
+    if (s.ref_ch < 0 || s.ref_ch >= s.C) return fail(TIP_ERR_INDEX, "project: reference_channel %d out of range", s.ref_ch);
+    if (s.zlo < 0 || zhi > s.Z || zhi <= s.zlo) return fail(TIP_ERR_ARG, "project: bad z range [%d,%d) of %d", s.zlo, zhi, s.Z);
+    if (s.Y < 1 || s.X < 1 || s.Y > 65535) return fail(TIP_ERR_ARG, "project: bad frame size %dx%d", s.Y, s.X);
+    if (s.manifold && tile) return fail(TIP_ERR_UNSUPPORTED, "project: build_manifold takes whole frames");
+    if (s.manifold && (s.V >= 0xffffffffL || s.Zs > 144)) return fail(TIP_ERR_UNSUPPORTED, "project: build_manifold: stack too large");
+    return TIP_OK;
+}
+
+static int take_workspace(ProjJob &s)
+{
+    s.A = s.ws.get<float>(s.V), s.B = s.ws.get<float>(s.V);
+    s.hist = s.ws.get<unsigned long long>(65536);
+    s.clip = s.ws.get<ClipInfo>(1);
+    s.zsel = s.ws.get<int32_t>(s.P), s.zsel_a = s.ws.get<int32_t>(s.P);
+    s.ident = s.ws.get<float>((size_t)s.Zs * s.Zs), s.table = s.ws.get<float>((size_t)s.Zs * s.Zs);
+    s.err = s.ws.get<int>(1);
+    if (!s.A || !s.B || !s.hist || !s.clip || !s.zsel || !s.zsel_a || !s.ident || !s.table || !s.err) return TIP_ERR_NOMEM;
+    return TIP_OK;
+}
+
+// P2: the clip value of one channel's planes (with_zero: see k_percentile95)
+static int clip_of_channel(ProjJob &s, const uint16_t *src, int with_zero, ClipInfo *clip)
+{
+    TIP_HIP(hipMemsetAsync(s.hist, 0, 65536 * sizeof(unsigned long long), s.stream));
+    TIP_LAUNCH("hist_u16", k_hist_u16, dim3((unsigned)std::min<long>(cdiv(s.V, HIST_PER_BLOCK), cu_count())), dim3(1024), 0, src, s.V,
+               s.airyscan, s.hist);
+    TIP_LAUNCH("percentile95", k_percentile95, dim3(1), dim3(1024), 0, (const unsigned long long *)s.hist, clip, with_zero);
+    return TIP_OK;
+}
+
+// P3: (0.5, 1, 1) of the clipped channel -> A, then P4's z pass (0.5) of that -> B
+static int short_blur(ProjJob &s, const uint16_t *src, ClipInfo *ci)
+{
+    const int Zs = s.Zs, Y = s.Y, X = s.X;
+    if (s.fast && s.bin == 1 && !tuning().project_unfused_preblur) {
+        // bin_size == 1 only needs the z-passed blur (B): the four short passes run as one kernel (tip_preblur.h)
+        ShortTaps s05, s1;
+        for (int i = 0; i < 8; ++i) { s05.w[i] = i < 3 ? s.k05.w[i] : 0.0; s1.w[i] = i < 5 ? s.k1.w[i] : 0.0; }
+        TIP_LAUNCH("preblur_fused", k_preblur_fused, dim3(cdiv(X, PB_X), cdiv(Y, PB_Y)), dim3(PB_T), 0, src, s.airyscan,
+                   (const float *)&ci->p95, (const int *)&ci->has, s.B, Zs, Y, X, s05, s1);
+        return TIP_OK;
+    }
+    if (s.fast) {   // register-sliding kernels (each input loaded once per thread)
+        Src4U16Clip su{src, s.airyscan, &ci->p95, &ci->has};
+        TIP_LAUNCH("zpass_u16clip_x4", (k_zpass_r2_x4<Src4U16Clip>), dim3(cdiv(s.P / 4, 256)), dim3(256), 0, su, s.A, Zs, s.P, s.k05);
+        // (36-row segments; 72-row segments halve the re-read halo rows but measured slower -- 0.257 against 0.235 ms --
+        // and so did four columns per thread with 16-byte accesses: the pass wants many independent row streams)
+        TIP_LAUNCH("ypass_slide_r4", (k_ypass_slide<float, 4, 4>), dim3(cdiv(X, 256), cdiv(Y, 36), Zs), dim3(256), 0,
+                   (const float *)s.A, s.B, Y, X, s.k1);
+        TIP_LAUNCH("xpass_slide_r4", (k_xpass_slide<float, 4>), dim3(cdiv(cdiv(X, 8), 256), Y, Zs), dim3(256), 0, (const float *)s.B,
+                   s.A, Y, X, s.k1);
+        Src4F32 sf{s.A};
+        TIP_LAUNCH("zpass_f32_x4", (k_zpass_r2_x4<Src4F32>), dim3(cdiv(s.P / 4, 256)), dim3(256), 0, sf, s.B, Zs, s.P, s.k05);
+        return TIP_OK;
+    }
+    LoadU16Clip ld{src, s.P, (long)X, s.airyscan, ci};
+    dim3 grid(cdiv(X, 256), Y, Zs), block(256);
+    TIP_LAUNCH("corr_z_u16clip", (k_corr_generic<float, 0, LoadU16Clip>), grid, block, 0, ld, s.A, Zs, Y, X, s.k05);
+    int rc;
+    if ((rc = correlate1d_dev(s.A, s.B, 0, Zs, Y, X, 1, s.k1, 0))) return rc;
+    if ((rc = correlate1d_dev(s.B, s.A, 0, Zs, Y, X, 2, s.k1, 0))) return rc;
+    return correlate1d_dev(s.A, s.B, 0, Zs, Y, X, 0, s.k05, 0);
+}
+
+// P4 in exact scipy arithmetic: the sigma-30 y and x passes of B, result in B (A is scratch)
+static int score_exact(ProjJob &s)
+{
+    int rc;
+    if ((rc = correlate1d_dev(s.B, s.A, 0, s.Zs, s.Y, s.X, 1, s.k30, 0))) return rc;
+    return correlate1d_dev(s.A, s.B, 0, s.Zs, s.Y, s.X, 2, s.k30, 0);
+}
+
+static int emit_from_planes(ProjJob &s, const int *bestz, int min_z)
+{
+    TIP_LAUNCH("emit_zmaps", k_emit_zmaps, dim3(cdiv(s.P, 256)), dim3(256), 0, bestz, s.Zs, s.P, min_z, s.atoh_shift, s.zsel, s.zsel_a,
+               s.zmap, s.err);
+    return TIP_OK;
+}
+
+// P4' (sp.py:39-65): score on bin x bin blocks, resized back to the frame for the argmax
+static int zmaps_binned(ProjJob &s)
+{
+    const int Zs = s.Zs, Y = s.Y, X = s.X, bin = s.bin, Yb = cdiv(Y, bin), Xb = cdiv(X, bin);
+    const long nb = (long)Zs * Yb * Xb;
+    float *S1 = s.ws.get<float>(nb);
+    int *bestz = s.ws.get<int>(s.P);
+    if (!S1 || !bestz) return TIP_ERR_NOMEM;
+    int rc;
+    if (s.method == 0) {          // max_averages: block mean of the (exact) (0.5, 30, 30) blur
+        if ((rc = score_exact(s))) return rc;
+        TIP_LAUNCH("block_mean", (k_block_reduce<false>), dim3(cdiv(nb, 256)), dim3(256), 0, (const float *)s.B, S1, Zs, Y, X, bin, Yb, Xb);
+    } else {                      // max_std / multi_channel: block variance of the (0.5, 1, 1) blur
+        TIP_LAUNCH("block_var", (k_block_reduce<true>), dim3(cdiv(nb, 256)), dim3(256), 0, (const float *)s.A, S1, Zs, Y, X, bin, Yb, Xb);
+    }
+    if (s.method == 2) {          // times the block mean of the next channel's (0.5, 30, 30) blur (sp.py:45-51)
+        const uint16_t *other = s.czyx + ((long)((s.ref_ch + 1) % s.C) * s.Z + s.zlo) * s.P;
+        float *S2 = s.ws.get<float>(nb);
+        ClipInfo *clip2 = s.ws.get<ClipInfo>(1);
+        if (!S2 || !clip2) return TIP_ERR_NOMEM;
+        if ((rc = clip_of_channel(s, other, 1, clip2)) || (rc = short_blur(s, other, clip2)) || (rc = score_exact(s))) return rc;
+        TIP_LAUNCH("block_mean", (k_block_reduce<false>), dim3(cdiv(nb, 256)), dim3(256), 0, (const float *)s.B, S2, Zs, Y, X, bin, Yb, Xb);
+        TIP_LAUNCH("mul_f32", k_mul_f32, dim3(cdiv(nb, 256)), dim3(256), 0, S1, (const float *)S2, nb);
+    }
+    if (!s.manifold) {
+        TIP_LAUNCH("resize_argmax", k_resize_argmax, dim3(cdiv(X, 256), Y), dim3(256), 0, (const float *)S1, Zs, Yb, Xb, Y, X, bestz);
+        return emit_from_planes(s, bestz, s.min_z);
+    }
+    // sp.py:56-57, 63-65: the spiral on the BINNED score, then the plane maps resized to the frame and rounded
+    int *bz = s.ws.get<int>((size_t)Yb * Xb);
+    if (!bz) return TIP_ERR_NOMEM;
+    if ((rc = manifold_dev((const float *)S1, Zs, Yb, Xb, bz, s.err))) return rc;
+    TIP_LAUNCH("resize_round_zmaps", k_resize_round_zmaps, dim3(cdiv(X, 256), Y), dim3(256), 0, (const int *)bz, Yb, Xb, Y, X, Zs,
+               s.atoh_shift, s.zsel, s.zsel_a, s.zmap, s.err);
+    return TIP_OK;
+}
+
+// P4 + P5 with the certified argmax (see above): fp16 score, certify, exact fix-up of the uncertified pixels
+static int zmaps_certified(ProjJob &s)
+{
+    const int Zs = s.Zs, Y = s.Y, X = s.X;
+    const long P = s.P;
+    float *D = s.ws.get<float>(s.V);
+    int *bestz = s.ws.get<int>(P), *unc = s.ws.get<int>(P), *uncn = s.ws.get<int>(1);
+    if (!D || !bestz || !unc || !uncn) return TIP_ERR_NOMEM;
+    TapsF f30;
+    f30.n = s.k30.n;
+    for (int i = 0; i < 256; ++i) f30.w[i] = (float)s.k30.w[i];
+    // fast y pass B -> A, fast x pass A -> D   (B, the exact z-passed volume, is kept for the exact fix-up).  The fp16 tiles
+    // take the clip value: their samples are scaled into fp16's range by it, and the volume B -- convex combinations of
+    // clipped voxels -- is bounded by it; err bit 8 would report a sample beyond that range.
+    int rc;
+    if ((rc = launch_f16<1>((const float *)s.B, s.A, Zs, Y, X, f30, s.clip, s.err))) return rc;
+    if ((rc = launch_f16<2>((const float *)s.A, D, Zs, Y, X, f30, s.clip, s.err))) return rc;
+    TIP_HIP(hipMemsetAsync(uncn, 0, sizeof(int), s.stream));
+    TIP_LAUNCH("argmax_certify", k_argmax_certify, dim3(cdiv(cdiv(P, 4), 256)), dim3(256), 0, (const float *)D, Zs, P, bestz, unc, uncn,
+               (const ClipInfo *)s.clip);
+    TIP_LAUNCH("argmax_exact_fix", k_argmax_exact_fix, dim3(8192), dim3(256), 0, (const float *)s.B, (const float *)D, Zs, Y, X,
+               s.k30, (const int *)unc, (const int *)uncn, bestz, (const ClipInfo *)s.clip);
+    if ((rc = emit_from_planes(s, bestz, s.min_z))) return rc;
+    if (tuning().project_debug) {
+        int hn = 0, he = 0;
+        TIP_HIP(hipMemcpyAsync(&hn, uncn, sizeof(int), hipMemcpyDeviceToHost, s.stream));
+        TIP_HIP(hipMemcpyAsync(&he, s.err, sizeof(int), hipMemcpyDeviceToHost, s.stream));
+        TIP_HIP(hipStreamSynchronize(s.stream));
+        fprintf(stderr, "certified argmax: %d of %ld pixels recomputed exactly\n", hn, P);
+        if (he & 8) return fail(TIP_ERR_HIP, "score pass: a sample beyond the clip value's range reached the fp16 tiles");
+    }
+    return TIP_OK;
+}
+
+// P4 + P5 at full resolution: (0.5, 30, 30) score and its argmax
+static int zmaps_full(ProjJob &s)
+{
+    if (s.fast && s.Zs <= 64 && !s.manifold && !tuning().project_exact_score) return zmaps_certified(s);
+    int rc;
+    if ((rc = score_exact(s))) return rc;
+    if (!s.manifold) {   // P5
+        TIP_LAUNCH("argmax_z", k_argmax_z, dim3(cdiv(s.P, 256)), dim3(256), 0, s.B, s.Zs, s.P, s.min_z, s.atoh_shift, s.zsel, s.zsel_a,
+                   s.zmap, s.err);
+        return TIP_OK;
+    }
+    // the spiral reads score VALUES (window argmaxes), so it gets the exact score; min_z is not added (sp.py:57)
+    int *bestz = s.ws.get<int>(s.P);
+    if (!bestz) return TIP_ERR_NOMEM;
+    if ((rc = manifold_dev((const float *)s.B, s.Zs, s.Y, s.X, bestz, s.err))) return rc;
+    return emit_from_planes(s, bestz, 0);
+}
+
+// (instantiated per channel count: the per-channel running maxima are registers, 8 channels' worth of them cost the
+//  two-channel case a third of its occupancy)
+template <int MAXC>
+static int launch_mask_fused(const ProjJob &s, const int32_t *sel, unsigned cm)
+{
+    TIP_LAUNCH("mask_wmax_fused", (k_mask_wmax_fused<MAXC>), dim3(cdiv(s.X, FT_X), cdiv(s.Y, FT_Y)), dim3(256),
+               (size_t)s.Zs * s.Zs * sizeof(float), (const float *)s.table, sel, s.czyx, s.C, s.Z, s.zlo, s.Zs, s.Y, s.X, s.airyscan, cm,
+               s.k2, s.proj);
+    return TIP_OK;
+}
+
+// P6-P8: one pass over all channels, or (atoh_shift != 0, sp.py:75-79) the reference channel under the chosen planes and
+// the others under the shifted ones
+static int mask_and_project(ProjJob &s)
+{
+    const int Zs = s.Zs, Y = s.Y, X = s.X, C = s.C;
+    // P6/P7 z pass as a Zs x Zs table (sigma 1 -> 9 taps), built with the same correlate kernel
+    TIP_LAUNCH("identity", k_identity, dim3(cdiv((long)Zs * Zs, 256)), dim3(256), 0, s.ident, Zs);
+    int rc;
+    if ((rc = correlate1d_dev(s.ident, s.table, 0, Zs, Zs, 1, 0, s.k1, 1))) return rc;
+    const bool fused = s.fast && Zs <= 64 && !tuning().project_unfused_mask;
+    const unsigned all = (1u << C) - 1u;
+    for (int pass = 0; pass < (s.atoh_shift != 0 ? 2 : 1); ++pass) {
+        const int32_t *sel = pass == 0 ? s.zsel : s.zsel_a;
+        const unsigned cm = s.atoh_shift == 0 ? all : (pass == 0 ? (1u << s.ref_ch) : (all & ~(1u << s.ref_ch)));
+        if (!cm) continue;
+        if (fused) {
+            rc = C <= 2 ? launch_mask_fused<2>(s, sel, cm) : C <= 4 ? launch_mask_fused<4>(s, sel, cm) : launch_mask_fused<8>(s, sel, cm);
+            if (rc) return rc;
+            continue;
+        }
+        // the dense form in literal scipy order (X % 4 != 0, Zs > 64, TIP_PROJECT_GENERIC, TIP_PROJECT_UNFUSED_MASK)
+        LoadMaskTable ld{s.table, sel, Zs, (long)X};
+        dim3 grid(cdiv(X, 256), Y, Zs), block(256);
+        TIP_LAUNCH("mask_ypass", (k_corr_generic<float, 1, LoadMaskTable>), grid, block, 0, ld, s.A, Zs, Y, X, s.k2);
+        TIP_LAUNCH("xpass_wmax", (k_xpass_wmax<8>), dim3(cdiv(X, 256), Y), dim3(256), 0, s.A, s.czyx, C, s.Z, s.zlo, Zs, Y, X, s.airyscan,
+                   cm, s.k2, s.proj);
+    }
+    return TIP_OK;
+}
+
+// the read-back costs a synchronise: only for the arguments that can raise err bit 1 or 2
+static int read_err(ProjJob &s)
+{
+    if (!(s.min_z > 0 || s.atoh_shift > 0 || s.manifold)) return TIP_OK;
+    int h = 0;
+    TIP_HIP(hipMemcpyAsync(&h, s.err, sizeof(int), hipMemcpyDeviceToHost, s.stream));
+    TIP_HIP(hipStreamSynchronize(s.stream));
+    if (h & 2) return fail(TIP_ERR_HIP, "build_manifold: a pixel without a visited neighbour (upstream raises TypeError here)");
+    if (h & 8) return fail(TIP_ERR_HIP, "score pass: a sample beyond the clip value's range reached the fp16 tiles");
+    if (h)
+        return fail(TIP_ERR_INDEX, "chosen z index out of bounds for the %d-plane mask (min_z=%d, atoh_shift=%d): "
+                                   "the reference raises IndexError here (sp.py:62,68-69)", s.Zs, s.min_z, s.atoh_shift);
+    return TIP_OK;
+}
+
 int project_dev(const uint16_t *czyx, int C, int Z, int Y, int X, int zlo, int zhi, int min_z, int ref_ch, int method, int bin,
                 int airyscan, int atoh_shift, const double *t05, const double *t1, const double *t2,
                 const double *t30, double *proj, int64_t *zmap, const unsigned long long *hist_in = nullptr)
 {
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
-    if (!czyx || !proj) return fail(TIP_ERR_ARG, "project: null pointer");
-    if (C < 1 || C > 8) return fail(TIP_ERR_ARG, "project: 1..8 channels supported (got %d)", C);
-    if (ref_ch < 0 || ref_ch >= C) return fail(TIP_ERR_INDEX, "project: reference_channel %d out of range", ref_ch);
-    if (zlo < 0 || zhi > Z || zhi <= zlo) return fail(TIP_ERR_ARG, "project: bad z range [%d,%d) of %d", zlo, zhi, Z);
-    if (Y < 1 || X < 1 || Y > 65535) return fail(TIP_ERR_ARG, "project: bad frame size %dx%d", Y, X);
-    const int Zs = zhi - zlo;
-    const long P = (long)Y * X, V = (long)Zs * P;
-    const bool manifold = (method & TIP_PROJECT_MANIFOLD) != 0;      // sp.py:56-57: the spiral z-map instead of the argmax
-    method &= ~TIP_PROJECT_MANIFOLD;
-    if (manifold && hist_in) return fail(TIP_ERR_UNSUPPORTED, "project: build_manifold takes whole frames");
-    if (manifold && (V >= 0xffffffffL || Zs > 144)) return fail(TIP_ERR_UNSUPPORTED, "project: build_manifold: stack too large");
-    Taps k05, k1, k2, k30;
+    ProjJob s;
+    s.stream = ctx().stream;
+    if (!s.stream) return TIP_ERR_HIP;
+    s.czyx = czyx; s.C = C; s.Z = Z; s.Y = Y; s.X = X; s.zlo = zlo; s.Zs = zhi - zlo;
+    s.P = (long)Y * X; s.V = (long)s.Zs * s.P;
+    s.min_z = min_z; s.ref_ch = ref_ch; s.bin = bin; s.airyscan = airyscan; s.atoh_shift = atoh_shift;
+    s.manifold = (method & TIP_PROJECT_MANIFOLD) != 0;
+    s.method = method & ~TIP_PROJECT_MANIFOLD;
+    s.fast = (X % 4 == 0) && !tuning().project_generic;
+    s.proj = proj; s.zmap = zmap;
     int rc;
-    if ((rc = resolve_taps(t05, 0.5, 5, k05)) || (rc = resolve_taps(t1, 1.0, 9, k1)) ||
-        (rc = resolve_taps(t2, 2.0, 17, k2)) || (rc = resolve_taps(t30, 30.0, 241, k30)))
+    if ((rc = check_args(s, zhi, hist_in != nullptr)) || (rc = resolve_taps(t05, 0.5, 5, s.k05)) || (rc = resolve_taps(t1, 1.0, 9, s.k1)) ||
+        (rc = resolve_taps(t2, 2.0, 17, s.k2)) || (rc = resolve_taps(t30, 30.0, 241, s.k30)) || (rc = take_workspace(s)))
         return rc;
-
-    WsGuard ws;
-    float *A = ws.get<float>(V), *B = ws.get<float>(V);
-    unsigned long long *hist = ws.get<unsigned long long>(65536);
-    ClipInfo *clip = ws.get<ClipInfo>(1);
-    int32_t *zsel = ws.get<int32_t>(P), *zsel_a = ws.get<int32_t>(P);
-    float *ident = ws.get<float>((size_t)Zs * Zs), *table = ws.get<float>((size_t)Zs * Zs);
-    int *err = ws.get<int>(1);
-    int32_t *zrange = ws.get<int32_t>(P);
-    if (!zrange) return TIP_ERR_NOMEM;
-    if (!A || !B || !hist || !clip || !zsel || !zsel_a || !ident || !table || !err) return TIP_ERR_NOMEM;
-
-    const uint16_t *ref = czyx + ((long)ref_ch * Z + zlo) * P;
-    TIP_HIP(hipMemsetAsync(err, 0, sizeof(int), c.stream));
+    s.ref = czyx + ((long)ref_ch * Z + zlo) * s.P;
+    TIP_HIP(hipMemsetAsync(s.err, 0, sizeof(int), s.stream));
     if (hist_in) {   // a tile of a larger frame: the caller brings the whole frame's histogram
-        if (bin > 1 && method == 2) return fail(TIP_ERR_UNSUPPORTED, "project: tiles with method multi_channel");
-        TIP_LAUNCH("percentile95", k_percentile95, dim3(1), dim3(1024), 0, hist_in, clip, 0);
-    } else {
-        TIP_HIP(hipMemsetAsync(hist, 0, 65536 * sizeof(unsigned long long), c.stream));
-        TIP_LAUNCH("hist_u16", k_hist_u16, dim3((unsigned)std::min<long>(cdiv(V, HIST_PER_BLOCK), cu_count())), dim3(1024), 0, ref, V, airyscan, hist);
-        TIP_LAUNCH("percentile95", k_percentile95, dim3(1), dim3(1024), 0, (const unsigned long long *)hist, clip, 0);
-    }
-
-    const bool fast = (X % 4 == 0) && !tuning().project_generic;
-    // P3: (0.5, 1, 1) of the clipped channel -> A_, then P4's z pass (0.5) of that -> B_
-    auto short_blur = [&](const uint16_t *src, ClipInfo *ci, float *A_, float *B_) -> int {
-        if (fast) {   // register-sliding kernels (each input loaded once per thread)
-            Src4U16Clip su{src, airyscan, &ci->p95, &ci->has};
-            TIP_LAUNCH("zpass_u16clip_x4", (k_zpass_r2_x4<Src4U16Clip>), dim3(cdiv(P / 4, 256)), dim3(256), 0, su, A_, Zs, P, k05);
-            // (36-row segments; 72-row segments halve the re-read halo rows but measured slower -- 0.257 against 0.235 ms --
-            // and so did four columns per thread with 16-byte accesses: the pass wants many independent row streams)
-            TIP_LAUNCH("ypass_slide_r4", (k_ypass_slide<float, 4, 4>), dim3(cdiv(X, 256), cdiv(Y, 36), Zs), dim3(256), 0,
-                       (const float *)A_, B_, Y, X, k1);
-            TIP_LAUNCH("xpass_slide_r4", (k_xpass_slide<float, 4>), dim3(cdiv(cdiv(X, 8), 256), Y, Zs), dim3(256), 0, (const float *)B_,
-                       A_, Y, X, k1);
-            Src4F32 sf{A_};
-            TIP_LAUNCH("zpass_f32_x4", (k_zpass_r2_x4<Src4F32>), dim3(cdiv(P / 4, 256)), dim3(256), 0, sf, B_, Zs, P, k05);
-            return TIP_OK;
-        }
-        LoadU16Clip ld{src, P, (long)X, airyscan, ci};
-        dim3 grid(cdiv(X, 256), Y, Zs), block(256);
-        TIP_LAUNCH("corr_z_u16clip", (k_corr_generic<float, 0, LoadU16Clip>), grid, block, 0, ld, A_, Zs, Y, X, k05);
-        int r2;
-        if ((r2 = correlate1d_dev(A_, B_, 0, Zs, Y, X, 1, k1, 0))) return r2;
-        if ((r2 = correlate1d_dev(B_, A_, 0, Zs, Y, X, 2, k1, 0))) return r2;
-        return correlate1d_dev(A_, B_, 0, Zs, Y, X, 0, k05, 0);
-    };
-    // bin_size == 1 only needs the z-passed blur (B): the four short passes run as one kernel (tip_preblur.h)
-    const bool fused_pre = fast && bin == 1 && !tuning().project_unfused_preblur;
-    if (fused_pre) {
-        ShortTaps s05, s1;
-        for (int i = 0; i < 8; ++i) { s05.w[i] = i < 3 ? k05.w[i] : 0.0; s1.w[i] = i < 5 ? k1.w[i] : 0.0; }
-        TIP_LAUNCH("preblur_fused", k_preblur_fused, dim3(cdiv(X, PB_X), cdiv(Y, PB_Y)), dim3(PB_T), 0, ref, airyscan,
-                   (const float *)&clip->p95, (const int *)&clip->has, B, Zs, Y, X, s05, s1);
-    } else if ((rc = short_blur(ref, clip, A, B))) return rc;
-    if (bin > 1) {
-        // P4' (sp.py:39-65): score on bin x bin blocks, resized back to the frame for the argmax
-        const int Yb = cdiv(Y, bin), Xb = cdiv(X, bin);
-        const long nb = (long)Zs * Yb * Xb;
-        float *S1 = ws.get<float>(nb);
-        int *bestz = ws.get<int>(P);
-        if (!S1 || !bestz) return TIP_ERR_NOMEM;
-        if (method == 0) {          // max_averages: block mean of the (exact) (0.5, 30, 30) blur
-            if ((rc = correlate1d_dev(B, A, 0, Zs, Y, X, 1, k30, 0))) return rc;
-            if ((rc = correlate1d_dev(A, B, 0, Zs, Y, X, 2, k30, 0))) return rc;
-            TIP_LAUNCH("block_mean", (k_block_reduce<false>), dim3(cdiv(nb, 256)), dim3(256), 0, (const float *)B, S1, Zs, Y, X, bin, Yb, Xb);
-        } else {                    // max_std / multi_channel: block variance of the (0.5, 1, 1) blur
-            TIP_LAUNCH("block_var", (k_block_reduce<true>), dim3(cdiv(nb, 256)), dim3(256), 0, (const float *)A, S1, Zs, Y, X, bin, Yb, Xb);
-            if (method == 2) {      // times the block mean of the next channel's (0.5, 30, 30) blur (sp.py:45-51)
-                const uint16_t *other = czyx + ((long)((ref_ch + 1) % C) * Z + zlo) * P;
-                float *S2 = ws.get<float>(nb);
-                ClipInfo *clip2 = ws.get<ClipInfo>(1);
-                if (!S2 || !clip2) return TIP_ERR_NOMEM;
-                TIP_HIP(hipMemsetAsync(hist, 0, 65536 * sizeof(unsigned long long), c.stream));
-                TIP_LAUNCH("hist_u16", k_hist_u16, dim3((unsigned)std::min<long>(cdiv(V, HIST_PER_BLOCK), cu_count())), dim3(1024), 0, other, V, airyscan, hist);
-                TIP_LAUNCH("percentile95", k_percentile95, dim3(1), dim3(1024), 0, (const unsigned long long *)hist, clip2, 1);
-                if ((rc = short_blur(other, clip2, A, B))) return rc;
-                if ((rc = correlate1d_dev(B, A, 0, Zs, Y, X, 1, k30, 0))) return rc;
-                if ((rc = correlate1d_dev(A, B, 0, Zs, Y, X, 2, k30, 0))) return rc;
-                TIP_LAUNCH("block_mean", (k_block_reduce<false>), dim3(cdiv(nb, 256)), dim3(256), 0, (const float *)B, S2, Zs, Y, X, bin, Yb, Xb);
-                TIP_LAUNCH("mul_f32", k_mul_f32, dim3(cdiv(nb, 256)), dim3(256), 0, S1, (const float *)S2, nb);
-            }
-        }
-        if (manifold) {
-            // sp.py:56-57, 63-65: the spiral on the BINNED score, then the plane maps resized to the frame and rounded
-            int *bz = ws.get<int>((size_t)Yb * Xb);
-            if (!bz) return TIP_ERR_NOMEM;
-            if ((rc = manifold_dev((const float *)S1, Zs, Yb, Xb, bz, err))) return rc;
-            TIP_LAUNCH("resize_round_zmaps", k_resize_round_zmaps, dim3(cdiv(X, 256), Y), dim3(256), 0, (const int *)bz, Yb, Xb, Y, X, Zs,
-                       atoh_shift, zsel, zsel_a, zmap, err);
-        } else {
-        TIP_LAUNCH("resize_argmax", k_resize_argmax, dim3(cdiv(X, 256), Y), dim3(256), 0, (const float *)S1, Zs, Yb, Xb, Y, X, bestz);
-        TIP_LAUNCH("emit_zmaps", k_emit_zmaps, dim3(cdiv(P, 256)), dim3(256), 0, (const int *)bestz, Zs, P, min_z, atoh_shift, zsel,
-                   zsel_a, zmap, err);
-        }
-    } else {
-    // P4 + P5: (0.5, 30, 30) score and its argmax
-    const bool certified = fast && Zs <= 64 && !manifold && !tuning().project_exact_score;
-    if (manifold) {
-        // the spiral reads score VALUES (window argmaxes), so it gets the exact score; min_z is not added (sp.py:57)
-        if ((rc = correlate1d_dev(B, A, 0, Zs, Y, X, 1, k30, 0))) return rc;
-        if ((rc = correlate1d_dev(A, B, 0, Zs, Y, X, 2, k30, 0))) return rc;
-        int *bestz = ws.get<int>(P);
-        if (!bestz) return TIP_ERR_NOMEM;
-        if ((rc = manifold_dev((const float *)B, Zs, Y, X, bestz, err))) return rc;
-        TIP_LAUNCH("emit_zmaps", k_emit_zmaps, dim3(cdiv(P, 256)), dim3(256), 0, (const int *)bestz, Zs, P, 0, atoh_shift, zsel, zsel_a,
-                   zmap, err);
-    } else if (certified) {
-        float *D = ws.get<float>(V);
-        int *bestz = ws.get<int>(P), *unc = ws.get<int>(P), *uncn = ws.get<int>(1);
-        if (!D || !bestz || !unc || !uncn) return TIP_ERR_NOMEM;
-        TapsF f30;
-        f30.n = k30.n;
-        for (int i = 0; i < 256; ++i) f30.w[i] = (float)k30.w[i];
-        // fast y pass B -> A, fast x pass A -> D   (B, the exact z-passed volume, is kept for the exact fix-up).  The fp16 tiles
-        // take the clip value: their samples are scaled into fp16's range by it, and the volume B -- convex combinations of
-        // clipped voxels -- is bounded by it; err bit 8 would report a sample beyond that range.
-        if ((rc = launch_f16<1>((const float *)B, A, Zs, Y, X, f30, clip, err))) return rc;
-        if ((rc = launch_f16<2>((const float *)A, D, Zs, Y, X, f30, clip, err))) return rc;
-        TIP_HIP(hipMemsetAsync(uncn, 0, sizeof(int), c.stream));
-        TIP_LAUNCH("argmax_certify", k_argmax_certify, dim3(cdiv(cdiv(P, 4), 256)), dim3(256), 0, (const float *)D, Zs, P, bestz, unc, uncn,
-                   (const ClipInfo *)clip);
-        TIP_LAUNCH("argmax_exact_fix", k_argmax_exact_fix, dim3(8192), dim3(256), 0, (const float *)B, (const float *)D, Zs, Y, X,
-                   k30, (const int *)unc, (const int *)uncn, bestz, (const ClipInfo *)clip);
-        TIP_LAUNCH("emit_zmaps", k_emit_zmaps, dim3(cdiv(P, 256)), dim3(256), 0, (const int *)bestz, Zs, P, min_z, atoh_shift, zsel,
-                   zsel_a, zmap, err);
-        if (tuning().project_debug) {
-            int hn = 0, he = 0;
-            TIP_HIP(hipMemcpyAsync(&hn, uncn, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-            TIP_HIP(hipMemcpyAsync(&he, err, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-            TIP_HIP(hipStreamSynchronize(c.stream));
-            fprintf(stderr, "certified argmax: %d of %ld pixels recomputed exactly\n", hn, P);
-            if (he & 8) return fail(TIP_ERR_HIP, "score pass: a sample beyond the clip value's range reached the fp16 tiles");
-        }
-    } else {
-        if ((rc = correlate1d_dev(B, A, 0, Zs, Y, X, 1, k30, 0))) return rc;
-        if ((rc = correlate1d_dev(A, B, 0, Zs, Y, X, 2, k30, 0))) return rc;
-        // P5
-        TIP_LAUNCH("argmax_z", k_argmax_z, dim3(cdiv(P, 256)), dim3(256), 0, B, Zs, P, min_z, atoh_shift, zsel, zsel_a, zmap,
-                   err);
-    }
-    }   // bin == 1
-    // P6/P7 z pass as a Zs x Zs table (sigma 1 -> 9 taps), built with the same correlate kernel
-    TIP_LAUNCH("identity", k_identity, dim3(cdiv((long)Zs * Zs, 256)), dim3(256), 0, ident, Zs);
-    if ((rc = correlate1d_dev(ident, table, 0, Zs, Zs, 1, 0, k1, 1))) return rc;
-
-    const unsigned all = (1u << C) - 1u;
-    for (int pass = 0; pass < (atoh_shift != 0 ? 2 : 1); ++pass) {
-        const int32_t *sel = pass == 0 ? zsel : zsel_a;
-        unsigned cm = atoh_shift == 0 ? all : (pass == 0 ? (1u << ref_ch) : (all & ~(1u << ref_ch)));
-        if (!cm) continue;
-        if (fast && Zs <= 64 && !tuning().project_unfused_mask) {
-            // (instantiated per channel count: the per-channel running maxima are registers, 8 channels' worth of them cost
-            //  the two-channel case a third of its occupancy)
-            const dim3 fgrid(cdiv(X, FT_X), cdiv(Y, FT_Y));
-            const size_t flds = (size_t)Zs * Zs * sizeof(float);
-            if (C <= 2) {
-                TIP_LAUNCH("mask_wmax_fused", (k_mask_wmax_fused<2>), fgrid, dim3(256), flds, (const float *)table, sel, czyx, C, Z, zlo, Zs,
-                           Y, X, airyscan, cm, k2, proj);
-            } else if (C <= 4) {
-                TIP_LAUNCH("mask_wmax_fused", (k_mask_wmax_fused<4>), fgrid, dim3(256), flds, (const float *)table, sel, czyx, C, Z, zlo, Zs,
-                           Y, X, airyscan, cm, k2, proj);
-            } else {
-                TIP_LAUNCH("mask_wmax_fused", (k_mask_wmax_fused<8>), fgrid, dim3(256), flds, (const float *)table, sel, czyx, C, Z, zlo, Zs,
-                           Y, X, airyscan, cm, k2, proj);
-            }
-        } else if (fast && Zs <= 64 && (long)Zs * Y < 2147483647L) {
-            TIP_LAUNCH("mask_y_sparse", (k_mask_y_sparse<2>), dim3(cdiv(X, 256), cdiv(Y, 2 * MASK_W)), dim3(256),
-                       (size_t)Zs * Zs * sizeof(float), (const float *)table, sel, Zs, Y, X, k2, A, zrange);
-            TIP_LAUNCH("xpass_wmax_sparse", (k_xpass_wmax_sparse<8>), dim3(cdiv(cdiv(X, 8), 256), Y), dim3(256), 0, (const float *)A,
-                       (const int32_t *)zrange, czyx, C, Z, zlo, Zs, Y, X, airyscan, cm, k2, proj);
-        } else {
-            LoadMaskTable ld{table, sel, Zs, (long)X};
-            dim3 grid(cdiv(X, 256), Y, Zs), block(256);
-            TIP_LAUNCH("mask_ypass", (k_corr_generic<float, 1, LoadMaskTable>), grid, block, 0, ld, A, Zs, Y, X, k2);
-            TIP_LAUNCH("xpass_wmax", (k_xpass_wmax<8>), dim3(cdiv(X, 256), Y), dim3(256), 0, A, czyx, C, Z, zlo, Zs, Y, X,
-                       airyscan, cm, k2, proj);
-        }
-    }
-    if (min_z > 0 || atoh_shift > 0 || manifold) {
-        int h = 0;
-        TIP_HIP(hipMemcpyAsync(&h, err, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-        TIP_HIP(hipStreamSynchronize(c.stream));
-        if (h & 2) return fail(TIP_ERR_HIP, "build_manifold: a pixel without a visited neighbour (upstream raises TypeError here)");
-        if (h & 8) return fail(TIP_ERR_HIP, "score pass: a sample beyond the clip value's range reached the fp16 tiles");
-        if (h)
-            return fail(TIP_ERR_INDEX, "chosen z index out of bounds for the %d-plane mask (min_z=%d, atoh_shift=%d): "
-                                       "the reference raises IndexError here (sp.py:62,68-69)", Zs, min_z, atoh_shift);
-    }
-    return TIP_OK;
+        if (bin > 1 && s.method == 2) return fail(TIP_ERR_UNSUPPORTED, "project: tiles with method multi_channel");
+        TIP_LAUNCH("percentile95", k_percentile95, dim3(1), dim3(1024), 0, hist_in, s.clip, 0);
+    } else if ((rc = clip_of_channel(s, s.ref, 0, s.clip))) return rc;
+    if ((rc = short_blur(s, s.ref, s.clip))) return rc;
+    if ((rc = bin > 1 ? zmaps_binned(s) : zmaps_full(s))) return rc;
+    if ((rc = mask_and_project(s))) return rc;
+    return read_err(s);
 }
 
 }  // namespace tip
@@ -1172,9 +969,7 @@ static int project_host(const uint16_t *czyx, int c, int z, int y, int x, int zl
 
 static int check_binned(int method, int bin)
 {
-    if (method >= 0 && (method & TIP_PROJECT_MANIFOLD)) {
-        method &= ~TIP_PROJECT_MANIFOLD;
-    }
+    if (method >= 0) method &= ~TIP_PROJECT_MANIFOLD;   // a flag on top of the method, not a method (negative: reported as given)
     if (method < 0 || method > 2) return fail(TIP_ERR_ARG, "projection: method %d (0 max_averages, 1 max_std, 2 multi_channel)", method);
     if (bin < 1 || bin > 128) return fail(TIP_ERR_UNSUPPORTED, "projection: bin_size %d (1..128 supported)", bin);
     return TIP_OK;
@@ -1235,7 +1030,6 @@ int tip_project_u16_binned(const uint16_t *czyx, int c, int z, int y, int x, int
     return project_host(czyx, c, z, y, x, zlo, zhi, min_z, ref_ch, method, bin_size, airyscan, atoh_shift, t05, t1, t2, t30, proj, zmap);
 }
 
-// sp.py:87-165 on its own: score float32 (z, y, x) host -> int64 (y, x) plane map
 // ---- diagnostics of the fp16 score tiles (tests) ---------------------------------------------------------------------------------
 __global__ void k_set_clip(ClipInfo *c, float v) { c->has = 1; c->p95 = v; c->p95d = (double)v; }
 
@@ -1299,6 +1093,7 @@ int tip_mfma_f16_probe(const float *a, const float *b, const float *cvals, float
     return TIP_OK;
 }
 
+// sp.py:87-165 on its own: score float32 (z, y, x) host -> int64 (y, x) plane map
 int tip_build_manifold_f32(const float *score, int z, int y, int x, int64_t *chosen)
 {
     Ctx &c = ctx();

@@ -47,7 +47,6 @@ struct WsScratch {
     unsigned long long *st;
 };
 
-int correlate1d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, int axis, const Taps &t, int force);
 int marker_pop_order(const uint8_t *c, long M, uint32_t *order);   // tip_heaporder.hip
 int flood_exact(const double *img, const int32_t *markers, int32_t *labels, int Y, int X);   // tip_ws_serial.hip
 long flood_keyed_finish(const double *img, uint64_t *st, int Y, int X);
