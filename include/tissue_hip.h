@@ -219,12 +219,15 @@ TIP_API int tip_draw_lines_f64(int y, int x, int n, const int32_t *ends, const d
 /* scipy.ndimage.maximum_filter / minimum_filter (ti.py:1822,2081,2969,4079-4084) and             */
 /* skimage.morphology.erosion/dilation with a flat footprint (pl.py:170-193).                     */
 /* footprint_kind: 0 = full ky x kx rectangle, 1 = 3x3 cross without centre ([[0,1,0],[1,0,1],[0,1,0]]). */
-/* border_mode: 0 = constant 0, 1 = reflect.  is_max: 1 max / 0 min.                              */
+/* border_mode: 0 = constant 0, 1 = reflect.  is_max: 1 max / 0 min.  Window sides 1..255: up to   */
+/* 31 x 31 in one pass over the window, wider rectangles as a row pass and a column pass (a         */
+/* rectangular max / min is exactly separable: the same bits).                                     */
 TIP_API int tip_rankfilter2d(const void *in, void *out, int dtype /*1=f64, 2=i32*/, int y, int x, int ky, int kx,
                              int footprint_kind, int border_mode, int is_max);
 TIP_API int tip_rankfilter2d_dev(const void *in, void *out, int dtype, int y, int x, int ky, int kx,
                                  int footprint_kind, int border_mode, int is_max);
-/* bim.py:464-473: thr = imgthresh*max_filter(img, block, reflect) ; out = img < thr ? 0 : img (float64) */
+/* bim.py:464-473: thr = imgthresh*max_filter(img, block, reflect) ; out = img < thr ? 0 : img (float64). */
+/* block 1..255, an even block acts as block + 1 (the GUI's spin box gives 0..100, taken as 1..101).     */
 TIP_API int tip_local_threshold_f64_dev(const double *img, double *out, int y, int x, double imgthresh, int block);
 
 /* ---- connected components: skimage.measure.label(connectivity=1) (ti.py:2922,3470) ----------- */
@@ -261,7 +264,10 @@ TIP_API int tip_marker_pop_order_host(const uint8_t *c, long m, uint32_t *e);
 TIP_API int tip_watershed_serial_host(const double *img, const int32_t *markers, int32_t *labels, int y, int x);
 /* number of labels (= markers) produced by the calling thread's last watershed call                 */
 TIP_API int tip_last_watershed_labels(void);
-/* bim.py:446-476 as one device pipeline: local threshold -> Gaussian(sigma) -> watershed          */
+/* bim.py:446-476 as one device pipeline: local threshold -> Gaussian(sigma) -> watershed.         */
+/* block as tip_local_threshold_f64_dev; taps: odd, symmetric, at most 8191 (sigma up to 2047 at   */
+/* truncate 4; more than 255 taps travel through device memory like tip_gaussian3d_w's), NULL or   */
+/* ntaps 0: no blur.                                                                               */
 TIP_API int tip_watershed_segmentation_f64_dev(const double *img, int32_t *labels, int y, int x, double imgthresh,
                                                const double *taps, int ntaps, int block, int32_t *flags_host);
 

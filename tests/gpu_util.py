@@ -15,3 +15,17 @@ def taps_patch(monkeypatch, golden_taps):
         return orig(sigma, radius)
 
     monkeypatch.setattr(bim, "_gaussian_kernel1d", patched)
+
+
+def integer_segmentation_reference(orc, image, imgthresh, stdeviation, blocksize):
+    """What bim.py:446-476 does to an integer image, restated on the oracle (whose blur_image refuses integers): threshold,
+    scipy's integer-dtype blur (float64 passes, truncated after every axis), serial flood."""
+    seg = np.copy(image)
+    seg[seg < orc.threshold_local_generic_max(seg.astype(np.float64), imgthresh, blocksize)] = 0
+    cur = seg.astype(np.float64)
+    for ax in range(2):
+        if float(stdeviation) > 1e-15:
+            sg = [0, 0]
+            sg[ax] = stdeviation
+            cur = np.trunc(orc.blur_image(cur, tuple(sg)))
+    return orc.watershed(cur)

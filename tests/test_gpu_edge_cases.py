@@ -2,7 +2,7 @@
 import numpy as np
 import pytest
 
-from gpu_util import taps_patch
+from gpu_util import integer_segmentation_reference, taps_patch
 
 pytestmark = pytest.mark.gpu
 
@@ -167,16 +167,17 @@ def test_thread_reentrancy(env):
 def test_integer_images_follow_scipy_truncation(env):
     """uint16 frames (what the GUI loads from the projection TIFF): scipy keeps the dtype and truncates after every axis."""
     ndi = pytest.importorskip("scipy.ndimage")
-    bim, _, seg, _ = env
+    bim, _, seg, orc = env
     rng = np.random.default_rng(12)
     img = rng.integers(0, 4000, (90, 120)).astype(np.uint16)
-    from tissue_image_processing_amd import basic_image_manipulations as b
-    taps = {}
     np.testing.assert_array_equal(bim.blur_image(img, 3), ndi.gaussian_filter(img, 3, mode="nearest"))
     i16 = (rng.integers(-300, 300, (40, 50))).astype(np.int16)
     np.testing.assert_array_equal(bim.blur_image(i16, (1, 2)), ndi.gaussian_filter(i16, (1, 2), mode="nearest"))
     labels, flags = seg.watershed_segmentation(img, 0.03, 3, 3, return_flags=True)
-    assert labels.dtype == np.int32 and labels.max() > 10
+    assert labels.dtype == np.int32
+    ref = integer_segmentation_reference(orc, img, 0.03, 3, 3)
+    assert ref.max() > 10
+    np.testing.assert_array_equal(labels, ref)
     assert flags & 1 and flags & 4        # integer landscape: value ties are reported and flooded by the exact serial replay
 
 

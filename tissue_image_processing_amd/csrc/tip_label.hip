@@ -208,23 +208,44 @@ __global__ void __launch_bounds__(256) k_rank2d(const T *__restrict__ in, T *__r
     out[(long)y * X + x] = best;
 }
 
+// Windows up to RANK_DIRECT_MAX on both sides: one launch that visits all ky * kx pixels (every call site of the reference).
+// Wider rectangles run as a row pass and a column pass of the same kernel: a rectangular maximum / minimum is exactly separable
+// (reflection acts per axis; the zero padding of 'constant' takes part in both passes, and a window that leaves the frame along
+// either axis sees it either way), ky + kx reads per pixel instead of ky * kx and the same bits.
+constexpr int RANK_DIRECT_MAX = 31, RANK_MAX = 255;
+
+template <typename T>
+static int rank2d_launch(const T *in, T *out, int Y, int X, int ky, int kx, int fp, int border, int is_max)
+{
+    TIP_LAUNCH(sizeof(T) == 8 ? "rank2d_f64" : "rank2d_i32", k_rank2d<T>, dim3(cdiv(X, 256), Y), dim3(256), 0, in, out, Y, X, ky, kx,
+               fp, border, is_max);
+    return TIP_OK;
+}
+
+template <typename T>
+static int rank2d(const T *in, T *out, int Y, int X, int ky, int kx, int fp, int border, int is_max)
+{
+    if ((ky <= RANK_DIRECT_MAX && kx <= RANK_DIRECT_MAX) || ky == 1 || kx == 1)
+        return rank2d_launch(in, out, Y, X, ky, kx, fp, border, is_max);
+    WsGuard ws;
+    T *rows = ws.get<T>((size_t)Y * X);
+    if (!rows) return TIP_ERR_NOMEM;
+    int rc = rank2d_launch(in, rows, Y, X, 1, kx, 0, border, is_max);
+    if (rc) return rc;
+    return rank2d_launch((const T *)rows, out, Y, X, ky, 1, 0, border, is_max);
+}
+
 int rankfilter2d_dev(const void *in, void *out, int dtype, int Y, int X, int ky, int kx, int fp, int border, int is_max)
 {
     if (!in || !out || in == out) return fail(TIP_ERR_ARG, "rankfilter2d: null or aliased pointers");
     if (Y < 1 || X < 1 || Y > 65535) return fail(TIP_ERR_ARG, "rankfilter2d: bad shape");
-    if (ky < 1 || kx < 1 || ky > 31 || kx > 31) return fail(TIP_ERR_ARG, "rankfilter2d: window %dx%d", ky, kx);
+    if (ky < 1 || kx < 1 || ky > RANK_MAX || kx > RANK_MAX)
+        return fail(TIP_ERR_ARG, "rankfilter2d: window %dx%d (sides 1..%d)", ky, kx, RANK_MAX);
     if (fp == 1 && (ky != 3 || kx != 3)) return fail(TIP_ERR_ARG, "cross footprint is 3x3");
     if (fp != 0 && fp != 1) return fail(TIP_ERR_ARG, "footprint_kind %d", fp);
-    dim3 grid(cdiv(X, 256), Y), block(256);
-    if (dtype == 1)
-        TIP_LAUNCH("rank2d_f64", k_rank2d<double>, grid, block, 0, (const double *)in, (double *)out, Y, X, ky, kx, fp, border,
-                   is_max);
-    else if (dtype == 2)
-        TIP_LAUNCH("rank2d_i32", k_rank2d<int32_t>, grid, block, 0, (const int32_t *)in, (int32_t *)out, Y, X, ky, kx, fp,
-                   border, is_max);
-    else
-        return fail(TIP_ERR_ARG, "rankfilter2d: dtype %d (1=f64, 2=i32)", dtype);
-    return TIP_OK;
+    if (dtype == 1) return rank2d((const double *)in, (double *)out, Y, X, ky, kx, fp, border, is_max);
+    if (dtype == 2) return rank2d((const int32_t *)in, (int32_t *)out, Y, X, ky, kx, fp, border, is_max);
+    return fail(TIP_ERR_ARG, "rankfilter2d: dtype %d (1=f64, 2=i32)", dtype);
 }
 
 // bim.py:464-473: thr = imgthresh * max(block x block, reflect) (float64); out = img < thr ? 0 : img
@@ -243,6 +264,17 @@ __global__ void __launch_bounds__(256) k_local_threshold(const double *__restric
     const double thr = imgthresh * best;
     const double v = img[(long)y * X + x];
     out[(long)y * X + x] = v < thr ? 0.0 : v;
+}
+
+// ... the same from a maximum that the separable rank filter has already formed (blocks wider than RANK_DIRECT_MAX)
+__global__ void __launch_bounds__(256) k_threshold_by_max(const double *__restrict__ img, const double *__restrict__ mx,
+                                                          double *__restrict__ out, long n, double imgthresh)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double thr = imgthresh * mx[i];
+    const double v = img[i];
+    out[i] = v < thr ? 0.0 : v;
 }
 
 __global__ void __launch_bounds__(256) k_update_labels(const int32_t *__restrict__ in, int32_t *__restrict__ out, int Y, int X)
@@ -355,10 +387,20 @@ int tip_rankfilter2d(const void *in, void *out, int dtype, int y, int x, int ky,
 int tip_local_threshold_f64_dev(const double *img, double *out, int y, int x, double imgthresh, int block)
 {
     if (!img || !out || img == out) return fail(TIP_ERR_ARG, "tip_local_threshold_f64_dev: null or aliased pointers");
-    if (block < 1 || block > 63) return fail(TIP_ERR_ARG, "block size %d", block);
+    if (block < 1 || block > RANK_MAX) return fail(TIP_ERR_ARG, "block size %d (1..%d)", block, RANK_MAX);
     if (block % 2 == 0) block += 1;  // bim.py:466-467
     if (y < 1 || x < 1 || y > 65535) return fail(TIP_ERR_ARG, "bad shape");
-    TIP_LAUNCH("local_threshold", k_local_threshold, dim3(cdiv(x, 256), y), dim3(256), 0, img, out, y, x, imgthresh, block);
+    if (block <= RANK_DIRECT_MAX) {
+        TIP_LAUNCH("local_threshold", k_local_threshold, dim3(cdiv(x, 256), y), dim3(256), 0, img, out, y, x, imgthresh, block);
+        return TIP_OK;
+    }
+    const long n = (long)y * x;
+    WsGuard ws;
+    double *mx = ws.get<double>((size_t)n);
+    if (!mx) return TIP_ERR_NOMEM;
+    int rc = rankfilter2d_dev(img, mx, 1, y, x, block, block, 0, 1, 1);
+    if (rc) return rc;
+    TIP_LAUNCH("threshold_by_max", k_threshold_by_max, dim3(cdiv(n, 256)), dim3(256), 0, img, (const double *)mx, out, n, imgthresh);
     return TIP_OK;
 }
 

@@ -30,6 +30,9 @@
 
 namespace tip {
 
+int gaussian3d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, const double *tz, int nz, const double *ty,
+                   int ny, const double *tx, int nx);                                                    // tip_gauss.hip
+
 // Both reductions: 4 independent loads per thread and trip, one atomic per BLOCK (thousands of same-address 64-bit
 // atomics serialise in L2 and used to cost more than the 32 MB read itself).
 constexpr int WS_RED_BLOCKS = 512;
@@ -294,6 +297,11 @@ int tip_watershed_segmentation_f64_dev(const double *img, int32_t *labels, int y
     if (!a || !b) return TIP_ERR_NOMEM;
     int rc = tip_local_threshold_f64_dev(img, a, y, x, imgthresh, block);
     if (rc) return rc;
+    if (taps && ntaps > 255) {
+        // sigma > 31.8: more taps than a Taps holds; blur_image's route for them (taps in device memory, tip_gauss.hip)
+        if ((rc = gaussian3d_dev(a, b, 1, 1, y, x, nullptr, 0, taps, ntaps, taps, ntaps))) return rc;
+        return watershed_dev(b, labels, y, x, 1, flags_host);
+    }
     if (taps && ntaps > 0) {
         Taps t;
         if ((rc = make_taps(t, taps, ntaps))) return rc;
