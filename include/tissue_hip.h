@@ -181,8 +181,19 @@ typedef struct tip_unet_conv_desc {
     float *head_out;            /* Conv2D(128 -> 2, 1x1) weights [2][128], bias [2], softmax -> float32 (2, h, w); `out` unused    */
     int format;                 /* 0: bf16 pieces; 1: fp16 pieces (planes == 2) -- activations, weights and the constants carry the  */
     float acc_scale;            /* caller's power-of-two scales, and the accumulator is multiplied by acc_scale before the bias      */
+    float *raw_out;             /* NULL, or float32 [out_h][out_w][cout]: the launch writes accumulator x acc_scale there through the   */
+                                /* output mapping and nothing else (no bias, no split, no saturation; out / bias may be NULL)           */
+    const float *seed;          /* NULL, or float32 [h][w][cout] added to the layer's pre-bias sum (plain output mapping): with a       */
+                                /* raw launch in front, one layer's sum over two launches                                               */
 } tip_unet_conv_desc;
 TIP_API int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream);
+/* Conv2DTranspose folded into the next Conv2D: border pass on the float32 partial `part` (2h x 2w x cout) that four  */
+/* raw launches over the low-resolution tensor x (h x w x cin, split) left.  row_w / col_w: [5][cin][cout] float32 corrections of  */
+/* the last output row / column, taps (parity, offset) = (0,-1) (0,0) (1,-1) (1,0) (1,+1); corner_w: [cin][cout]; bias_tab:        */
+/* [3][3][cout], (top, inside, bottom) x (left, inside, right); xscale: 1 / the activations' scale (fp16 pieces), else 1.          */
+TIP_API int tip_unet_compose_border_dev(const void *x, int planes, int format, int h, int w, int cin, int cout, const float *row_w,
+                                        const float *col_w, const float *corner_w, const float *bias_tab, float *part, float xscale,
+                                        void *stream);
 /* first layer, Conv2D(2 -> 128): float32 (2, h, w) in, weights [9][2][128] float32, exact float32 FMAs               */
 TIP_API int tip_unet_conv_first_dev(const float *in, int h, int w, const float *wgt, const float *bias, const float *scale,
                                     const float *shift, void *out, int planes, int format, void *stream);

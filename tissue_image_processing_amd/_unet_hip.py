@@ -26,7 +26,7 @@ class _ConvDesc(ctypes.Structure):
                 ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_h", ctypes.c_int),
                 ("out_w", ctypes.c_int), ("sy", ctypes.c_int), ("sx", ctypes.c_int), ("oy", ctypes.c_int), ("ox", ctypes.c_int),
                 ("pool_out", ctypes.c_void_p), ("head_w", ctypes.c_void_p), ("head_b", ctypes.c_void_p), ("head_out", ctypes.c_void_p),
-                ("format", ctypes.c_int), ("acc_scale", ctypes.c_float)]
+                ("format", ctypes.c_int), ("acc_scale", ctypes.c_float), ("raw_out", ctypes.c_void_p), ("seed", ctypes.c_void_p)]
 
 
 def split_pack(taps, planes, fmt=0):
@@ -50,13 +50,141 @@ def split_pack(taps, planes, fmt=0):
     return pk.permute(1, 2, 4, 0, 5, 3).contiguous()
 
 
-def weights(net, mode):
+_COMPOSE_LEVELS = (0, 1, 2)      # decoder levels whose transposed convolution is folded into the next convolution by default
+
+
+def compose_levels():
+    """TISSUE_HIP_UNET_COMPOSE: unset or 1 = the default levels, 0 = none (a transposed convolution's four parity launches and the
+    convolution over [up-sampled, skip], as before), or a list of levels such as u0,u2 (measurements)."""
+    v = os.environ.get("TISSUE_HIP_UNET_COMPOSE", "1").strip()
+    if v == "0":
+        return ()
+    if v in ("", "1"):
+        return _COMPOSE_LEVELS
+    return tuple(sorted({int(t.strip().lstrip("u")) for t in v.split(",") if t.strip()} & {0, 1, 2}))
+
+
+# Conv2DTranspose(3x3, stride 2, cropped to 2N) followed by Conv2D(3x3) along one axis, with T[k] / Wu[k] the two layers' taps:
+#     up[2i] = x[i] T0 + x[i-1] T2,  up[2i+1] = x[i] T1,  out[Y] = sum_k Wu[k] up[Y + k - 1]
+# so out[2i + parity] = sum over the pairs below of x[i + offset] T[kt] Wu[kw]:  parity -> [(offset, kw, kt)]
+_COMPOSE_AXIS = {0: [(-1, 0, 1), (-1, 1, 2), (0, 1, 0), (0, 2, 1)],
+                 1: [(-1, 0, 2), (0, 0, 0), (0, 1, 1), (0, 2, 2), (1, 2, 0)]}
+_EDGE_TAPS = [(0, -1), (0, 0), (1, -1), (1, 0), (1, 1)]      # (parity, offset) order of the border pass's weight tables
+
+
+def compose(tw, bt, w1):
+    """The algebra of DESIGN 5.7 in float64.  tw: (2C, C, 3, 3) transposed-convolution weights (torch layout: in, out, ky, kx), bt:
+    its bias (C), w1: (Cout, C + Cskip, 3, 3) weights of the convolution that follows (its first C input channels read the
+    up-sampled tensor).  Returns
+      classes  {(py, px): (taps (T, 2C, Cout), dy list, dx list)}: the composed convolution on the LOW-resolution grid per output parity,
+      bias     (Cout) what the transposed convolution's bias adds to an interior pixel of the convolution,
+      bias_tab (3, 3, Cout) an edge pixel's bias sum minus the interior's: (top, inside, bottom) x (left, inside, right),
+      row_w, col_w (5, 2C, Cout), corner_w (2C, Cout): what the border pass ADDS on the last output row / column / corner pixel
+      (taps in _EDGE_TAPS order) to take out the terms through the cropped row / column up[2N] = x[N-1] T2."""
+    import torch
+    tw, bt, w1 = tw.double(), bt.double().reshape(-1), w1.double()
+    C = tw.shape[1]
+    wu = w1[:, :C].permute(2, 3, 1, 0)             # [ky][kx] -> (C, Cout)
+    t = tw.permute(2, 3, 0, 1)                     # [ky][kx] -> (2C, C)
+    prod = {}
+
+    def pair(kty, ktx, kwy, kwx):
+        k = (kty, ktx, kwy, kwx)
+        if k not in prod:
+            prod[k] = t[kty, ktx] @ wu[kwy, kwx]
+        return prod[k]
+
+    classes = {}
+    for py in (0, 1):
+        for px in (0, 1):
+            acc = {}
+            for dy, kwy, kty in _COMPOSE_AXIS[py]:
+                for dx, kwx, ktx in _COMPOSE_AXIS[px]:
+                    m = pair(kty, ktx, kwy, kwx)
+                    acc[(dy, dx)] = acc[(dy, dx)] + m if (dy, dx) in acc else m
+            offs = sorted(acc)
+            classes[(py, px)] = (torch.stack([acc[o] for o in offs], 0), [o[0] for o in offs], [o[1] for o in offs])
+    through = torch.einsum("yxco,c->yxo", wu, bt)   # the bias through every tap of the convolution
+    bias = through.sum((0, 1))
+    bias_tab = torch.zeros((3, 3, bias.numel()), dtype=torch.float64, device=bias.device)
+    for ry in range(3):
+        for rx in range(3):
+            for ky in range(3):
+                for kx in range(3):
+                    if (ry == 0 and ky == 0) or (ry == 2 and ky == 2) or (rx == 0 and kx == 0) or (rx == 2 and kx == 2):
+                        bias_tab[ry, rx] -= through[ky, kx]      # the tap reads outside the up-sampled image
+    zero = torch.zeros_like(pair(2, 2, 2, 2))
+    row_w, col_w = [], []
+    for par, off in _EDGE_TAPS:
+        # last output row (parity 1): the pair (Wu2, T2) at offset 0 along y, with every pair along x -- and the same along the column
+        row_w.append(-sum((pair(2, ktx, 2, kwx) for dx, kwx, ktx in _COMPOSE_AXIS[par] if dx == off), zero))
+        col_w.append(-sum((pair(kty, 2, kwy, 2) for dy, kwy, kty in _COMPOSE_AXIS[par] if dy == off), zero))
+    return classes, bias, bias_tab, torch.stack(row_w, 0), torch.stack(col_w, 0), pair(2, 2, 2, 2)
+
+
+def _pack(taps, planes, fmt, bias_only=False):
+    """split_pack with the fp16 pieces' per-layer power-of-two weight scale -> (packed weights, accumulator factor)"""
+    if not fmt:
+        return split_pack(taps, planes), 1.0
+    big = float(taps.abs().max())
+    wscale = 2.0 ** (14 - int(np.floor(np.log2(big)))) if big > 0 and np.isfinite(big) else 1.0
+    inv = 1.0 / (_F16_ACT_SCALE * wscale)
+    return split_pack(taps * wscale, planes, fmt), (inv * _F16_ACT_SCALE if bias_only else inv)
+
+
+def compose_layers(tw, bt, w1, b1, planes, fmt):
+    """A transposed convolution (tw, bt) folded into the convolution (w1, b1) behind it, ready to launch: the four composed
+    stencils on the low-resolution grid ("x00" .. "x11": raw float32 output, so their accumulator factor yields the layer's true
+    units), the convolution's skip half ("skip"), its bias with the transposed convolution's folded in ("bias") and the border
+    pass's float32 tables ("border").  Neither the transposed convolution nor the up half is packed."""
+    import torch
+    w1 = w1.float()
+    C = tw.shape[1]
+    classes, bias, bias_tab, row_w, col_w, corner_w = compose(tw, bt, w1)
+    st = {}
+    for (py, px), (taps, dy, dx) in classes.items():
+        wp, inv = _pack(taps.float(), planes, fmt)
+        st["x%d%d" % (py, px)] = (wp, dy, dx, inv)
+    skip = torch.stack([w1[:, C:, ky, kx].t() for ky in range(3) for kx in range(3)], 0)
+    wp, inv = _pack(skip, planes, fmt)
+    st["skip"] = (wp, [ky - 1 for ky in range(3) for kx in range(3)], [kx - 1 for ky in range(3) for kx in range(3)], inv)
+    st["bias"] = (b1.double().reshape(-1) + bias).float().contiguous()
+    st["border"] = tuple(v.float().contiguous() for v in (row_w, col_w, corner_w, bias_tab))
+    return st
+
+
+def composed_up(st, planes, fmt, src, h, w, stream, name="", launch=None):
+    """The launches of compose_layers' `st` over the split low-resolution tensor src (planes, h, w, cin): four composed stencils leave
+    the next convolution's sum over its up-sampled half as float32 (2h, 2w, cout), the border pass corrects its edges.  That
+    convolution then runs over the skip tensor alone with st["bias"] and seed = the returned tensor.  launch(name, flop, fn): the
+    caller's per-launch timing hook."""
+    import torch
+    lib = _lib.lib()
+    launch = launch or (lambda name, flop, fn: fn())
+    cin, cout = src.shape[3], st["x00"][0].shape[2] * 128
+    part = torch.empty((2 * h, 2 * w, cout), dtype=torch.float32, device=src.device)
+    for py in (0, 1):
+        for px in (0, 1):
+            layer = st["x%d%d" % (py, px)]
+            d = _conv_desc(layer, planes, fmt, src, None, h, w, None, raw=part, out_h=2 * h, out_w=2 * w, stride=2, oy=py, ox=px)
+            launch("%sx.%d%d %dx%d %d+0->%d x%d taps" % (name, py, px, h, w, cin, cout, d.ntaps), 2.0 * h * w * d.ntaps * cout * cin,
+                   lambda: _lib.check(lib.tip_unet_conv_dev(ctypes.byref(d), stream)))
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    row_w, col_w, corner_w, bias_tab = st["border"]
+    launch("%sborder %dx%d %d->%d" % (name, 2 * h, 2 * w, cin, cout), 2.0 * 2.5 * (h + w) * cin * cout,
+           lambda: _lib.check(lib.tip_unet_compose_border_dev(P(src), planes, fmt, h, w, cin, cout, P(row_w), P(col_w), P(corner_w), P(bias_tab),
+                                                              P(part), ctypes.c_float(1.0 / _F16_ACT_SCALE if fmt else 1.0), stream)))
+    return part
+
+
+def weights(net, mode, levels=None):
     """Packed weights and per-channel constants of one arithmetic mode, cached in net._hipw.  fp16 pieces (mode f16x3) carry
     power-of-two scales: activations are stored times A = 2^4, a layer's weights times W = the power of two that puts its largest
     weight in [2^14, 2^15); the kernel multiplies the accumulator by 1 / (A W) before the bias (entry 3 of a layer's tuple), the
     BatchNorm scale / shift (and a bias-only layer's bias and accumulator factor) are multiplied by A, the head's weights by
     1 / A -- exact, so the stored values are A times what the unscaled network computes, bit for bit."""
-    hw = net._hipw.get(mode)
+    levels = compose_levels() if levels is None else tuple(levels)
+    hw = net._hipw.get((mode, levels))
     if hw is not None:
         return hw
     torch = net.torch
@@ -66,12 +194,7 @@ def weights(net, mode):
     hw = {}
 
     def pack(taps, bias_only):
-        if not fmt:
-            return split_pack(taps, planes), 1.0
-        big = float(taps.abs().max())
-        wscale = 2.0 ** (14 - int(np.floor(np.log2(big)))) if big > 0 and np.isfinite(big) else 1.0
-        inv = 1.0 / (act * wscale)
-        return split_pack(taps * wscale, planes, fmt), (inv * act if bias_only else inv)
+        return _pack(taps, planes, fmt, bias_only)
 
     def conv3(name):
         w = p[name + ".w"].float()                                  # (cout, cin, 3, 3): cross-correlation, tap (ky, kx) reads (y + ky - 1, x + kx - 1)
@@ -92,11 +215,14 @@ def weights(net, mode):
                 hw["%s.%d%d" % (name, py, px)] = (wp, [t[1] for t in tl], [t[3] for t in tl], inv)
 
     for blk in ("d0", "d1", "d2", "mid", "u0", "u1", "u2"):
-        if blk != "d0":
+        if blk != "d0" and not (blk[0] == "u" and int(blk[1]) in levels):
             conv3(blk + ".c1")
         conv3(blk + ".c2")
     for i in range(3):
-        conv_t("u%d.t" % i)
+        if i in levels:        # folded into the level's first convolution
+            hw["u%d.x" % i] = compose_layers(p["u%d.t.w" % i], p["u%d.t.b" % i], p["u%d.c1.w" % i], p["u%d.c1.b" % i], planes, fmt)
+        else:
+            conv_t("u%d.t" % i)
     w0 = p["d0.c1.w"].float()                                       # (128, 2, 3, 3) -> [tap][ci][cout]
     hw["first"] = w0.permute(2, 3, 1, 0).reshape(18, 128).contiguous()
     hw["head"] = (p["head.w"].float().reshape(2, 128) / act).contiguous()
@@ -106,7 +232,7 @@ def weights(net, mode):
             # times A: BatchNorm scale (".s") / shift (".t"), and the bias of a bias-only (transposed convolution) layer (".t.b")
             scaled = k.endswith((".s", ".t", ".t.b"))
             hw["f:" + k] = (v * act if scaled else v).contiguous()
-    net._hipw[mode] = hw
+    net._hipw[(mode, levels)] = hw
     return hw
 
 
@@ -145,12 +271,14 @@ def forward(net, x, mode, logits):
 
 
 def _conv_desc(layer, planes, fmt, src, skip, h, w, bias, scale=None, shift=None, out=None, out_h=None, out_w=None, stride=1, oy=0, ox=0,
-               pooled=None, head=None):
+               pooled=None, head=None, raw=None, seed=None):
     """The descriptor of one tip_unet_conv_dev launch.  layer: (packed weights, dy, dx, accumulator factor) from weights(); src,
     skip: split activations on the h x w grid (skip's channels are appended to src's: the decoder's concatenate); bias, scale,
     shift: float32 vectors (no scale / shift: a bias-only layer); out: split output of out_h x out_w pixels (default: the input
     grid), input-grid pixel (y, x) goes to (y * stride + oy, x * stride + ox); pooled: MaxPool2D(2) of the output; head: (weights,
-    bias, float32 output) of the network's head computed in this layer's epilogue -- the layer's own output is then not stored."""
+    bias, float32 output) of the network's head computed in this layer's epilogue -- the layer's own output is then not stored;
+    raw: float32 (out_h, out_w, cout) that receives the bare sum through the output mapping instead of everything else (no bias
+    needed); seed: float32 (h, w, cout) added to the layer's pre-bias sum."""
     wp, dy, dx, inv = layer
     d = _ConvDesc()
     d.format, d.acc_scale = fmt, inv
@@ -160,7 +288,9 @@ def _conv_desc(layer, planes, fmt, src, skip, h, w, bias, scale=None, shift=None
     d.weights, d.ntaps, d.cout = wp.data_ptr(), len(dy), wp.shape[2] * 128
     for i in range(len(dy)):
         d.dy[i], d.dx[i] = dy[i], dx[i]
-    d.bias = bias.data_ptr()
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.raw_out = raw.data_ptr() if raw is not None else None
+    d.seed = seed.data_ptr() if seed is not None else None
     d.scale, d.shift = (scale.data_ptr(), shift.data_ptr()) if scale is not None else (None, None)
     if head is not None:
         d.head_w, d.head_b, d.head_out = (t.data_ptr() for t in head)
@@ -175,8 +305,10 @@ def _launch(net, x, mode, logits):
     """The forward pass on torch's current stream: (1, 2, H, W) float32 -> class probabilities (or logits) (1, 2, H, W)."""
     torch = net.torch
     planes, fmt = _MODES[mode][:2]
-    hw = weights(net, mode)
+    levels = compose_levels()
+    hw = weights(net, mode, levels)
     net.last_mode = mode                  # (bench.py / tests: which arithmetic the last forward pass really used)
+    net.last_compose = tuple("u%d" % i for i in levels)      # ... and which decoder levels ran composed (empty: none)
     lib = _lib.lib()
     stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
     H, W = int(x.shape[2]), int(x.shape[3])
@@ -201,11 +333,14 @@ def _launch(net, x, mode, logits):
         timed("%s %dx%d %d+%d->%d x%d taps" % (name, d.h, d.w, d.c0, d.c1, d.cout, d.ntaps), 2.0 * d.h * d.w * d.ntaps * d.cout * (d.c0 + d.c1),
               lambda: _lib.check(lib.tip_unet_conv_dev(ctypes.byref(d), stream)))
 
-    def conv3(name, bn, src, skip, h, w, pooled=None, head=None):
-        """Conv2D(3x3) -> ReLU -> BatchNormalization `bn`; head: the probabilities' tensor when the head rides in the epilogue"""
-        out = buf(h, w, hw[name][0].shape[2] * 128) if head is None else None
-        launch_conv(name, _conv_desc(hw[name], planes, fmt, src, skip, h, w, hw["f:" + name + ".b"], hw["f:" + bn + ".s"], hw["f:" + bn + ".t"],
-                                     out=out, pooled=pooled, head=None if head is None else (hw["head"], hw["f:head.b"], head)))
+    def conv3(name, bn, src, skip, h, w, pooled=None, head=None, seed=None):
+        """Conv2D(3x3) -> ReLU -> BatchNormalization `bn`; head: the probabilities' tensor when the head rides in the epilogue;
+        seed: the layer's partial sum over the up-sampled half (composed level) -- src is then the skip tensor alone"""
+        layer, bias = (hw[name], hw["f:" + name + ".b"]) if seed is None else (hw[name[:2] + ".x"]["skip"], hw[name[:2] + ".x"]["bias"])
+        out = buf(h, w, layer[0].shape[2] * 128) if head is None else None
+        launch_conv(name if seed is None else name + ".seeded",
+                    _conv_desc(layer, planes, fmt, src, skip, h, w, bias, hw["f:" + bn + ".s"], hw["f:" + bn + ".t"],
+                               out=out, pooled=pooled, head=None if head is None else (hw["head"], hw["f:head.b"], head), seed=seed))
         return out
 
     def first(h, w):
@@ -216,9 +351,9 @@ def _launch(net, x, mode, logits):
                                                              D(hw["f:d0.b1.t"]), D(out), planes, fmt, stream)))
         return out
 
-    def double(blk, src, skip, h, w, pooled=None, head=None):
+    def double(blk, src, skip, h, w, pooled=None, head=None, seed=None):
         """a block's two convolutions; src None: the block reads the float32 network input (first-layer kernel)"""
-        a = first(h, w) if src is None else conv3(blk + ".c1", blk + ".b1", src, skip, h, w)
+        a = first(h, w) if src is None else conv3(blk + ".c1", blk + ".b1", src, skip, h, w, seed=seed)
         return conv3(blk + ".c2", blk + ".b2", a, None, h, w, pooled=pooled, head=head)
 
     def conv_t(name, src, h, w):
@@ -239,13 +374,17 @@ def _launch(net, x, mode, logits):
             cur, h, w = pooled, h // 2, w // 2
         cur = double("mid", cur, None, h, w)  # bottleneck
         for i in range(3):                    # decoder: the convolution reads [up-sampled, skip] as one concatenated tensor
-            up = conv_t("u%d.t" % i, cur, h, w)
+            part = composed_up(hw["u%d.x" % i], planes, fmt, cur, h, w, stream, "u%d." % i, timed) if i in levels else None
+            up = conv_t("u%d.t" % i, cur, h, w) if part is None else None
             h, w = 2 * h, 2 * w
             # the last convolution's epilogue computes the head: softmax probabilities instead of the layer's own output
             probs = None
             if i == 2 and not logits and not os.environ.get("TISSUE_HIP_UNET_SEPARATE_HEAD"):
                 probs = torch.empty((1, 2, H, W), dtype=torch.float32, device=x.device)
-            cur = double("u%d" % i, up, skips[2 - i], h, w, head=probs)
+            if part is None:
+                cur = double("u%d" % i, up, skips[2 - i], h, w, head=probs)
+            else:
+                cur = double("u%d" % i, skips[2 - i], None, h, w, head=probs, seed=part)
         if probs is not None:
             return probs
         out = torch.empty((1, 2, H, W), dtype=torch.float32, device=x.device)

@@ -445,7 +445,7 @@ int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    if (!d || !d->in0 || !d->weights || !d->bias || (!d->out && !d->head_out)) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: null pointer");
+    if (!d || !d->in0 || !d->weights || (!d->bias && !d->raw_out) || (!d->out && !d->head_out && !d->raw_out)) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: null pointer");
     if (d->planes != 2 && d->planes != 3) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: planes must be 2 or 3");
     if (d->format != 0 && d->format != 1) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: format is 0 (bf16 pieces) or 1 (fp16 pieces)");
     if (d->format == 1 && (d->planes != 2 || !(d->acc_scale > 0.f))) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: fp16 pieces come in two planes with a positive acc_scale");
@@ -485,6 +485,10 @@ int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
         return fail(TIP_ERR_ARG, "tip_unet_conv_dev: the fused head needs a 128-channel Conv2D + BatchNorm layer with the plain output mapping");
     if (d->pool_out && (d->sy != 1 || d->sx != 1 || d->oy != 0 || d->ox != 0 || d->out_h != d->h || d->out_w != d->w))
         return fail(TIP_ERR_ARG, "tip_unet_conv_dev: pool_out needs the plain output mapping");
+    p.raw_out = d->raw_out; p.seed = d->seed;
+    if (d->raw_out && (d->head_out || d->pool_out)) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: raw output goes without the head and the pooled map");
+    if (d->seed && (d->sy != 1 || d->sx != 1 || d->oy != 0 || d->ox != 0 || d->out_h != d->h || d->out_w != d->w))
+        return fail(TIP_ERR_ARG, "tip_unet_conv_dev: the accumulator seed needs the plain output mapping");
     // 16-row tiles (one 512-thread workgroup per CU) where the grid allows: half the weight copies per MFMA, and LDS for five
     // weight buffers (copies four steps ahead) when the stencil has >= 4 taps; two pieces only (LDS)
     const int t8 = tuning().unet_tile8;
@@ -558,6 +562,42 @@ int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
     }
 #endif
     return unet_launch_check("unet_conv");
+}
+
+// Border pass of a composed decoder level (tip_unet_conv.h) on the float32 partial of 2h x 2w x cout values: the edge
+// bias table on all four edges, then the bottom row's, the right column's and the corner's linear corrections, in stream order.
+int tip_unet_compose_border_dev(const void *x, int planes, int format, int h, int w, int cin, int cout, const float *row_w, const float *col_w,
+                                const float *corner_w, const float *bias_tab, float *part, float xscale, void *stream)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (!x || !row_w || !col_w || !corner_w || !bias_tab || !part || (planes != 2 && planes != 3) || (format != 0 && !(format == 1 && planes == 2)) ||
+        h < 1 || w < 1 || cin < 1 || cout < 128 || cout % 128 || !(xscale > 0.f))
+        return fail(TIP_ERR_ARG, "tip_unet_compose_border_dev: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    const int H2 = 2 * h, W2 = 2 * w;
+    const long nb = (2L * W2 + 2L * (H2 - 2)) * (cout / 4);
+    hipLaunchKernelGGL(k_unet_compose_edge_bias, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, s, part, H2, W2, cout, bias_tab);
+    EdgeParams p;
+    p.x = (const uint16_t *)x; p.xplane = (long)h * w * cin; p.planes = planes; p.f16 = format; p.xscale = xscale;
+    p.cin = cin; p.cout = cout; p.part = part;
+    const long wstride = (long)cin * cout;
+    // bottom row: positions run along x on input row h - 1, output row 2h - 1
+    p.L = w; p.x0 = (long)(h - 1) * w * cin; p.xstep = cin; p.tapmask = 0x1f;
+    for (int t = 0; t < 5; ++t) p.wgt[t] = row_w + t * wstride;
+    p.o0 = (long)(H2 - 1) * W2 * cout; p.ostep = cout;
+    hipLaunchKernelGGL(k_unet_compose_edge, dim3((unsigned)cdiv(p.L, EB_J), (unsigned)(cout / EB_CO)), dim3(EB_CO * EB_G), 0, s, p);
+    // right column: positions run along y on input column w - 1, output column 2w - 1
+    p.L = h; p.x0 = (long)(w - 1) * cin; p.xstep = (long)w * cin;
+    for (int t = 0; t < 5; ++t) p.wgt[t] = col_w + t * wstride;
+    p.o0 = (long)(W2 - 1) * cout; p.ostep = (long)W2 * cout;
+    hipLaunchKernelGGL(k_unet_compose_edge, dim3((unsigned)cdiv(p.L, EB_J), (unsigned)(cout / EB_CO)), dim3(EB_CO * EB_G), 0, s, p);
+    // corner: the doubly removed term back -- one position, its parity-1 pixel, the tap at offset 0
+    p.L = 1; p.x0 = ((long)(h - 1) * w + (w - 1)) * cin; p.xstep = cin; p.tapmask = 0x8;
+    for (int t = 0; t < 5; ++t) p.wgt[t] = corner_w;
+    p.o0 = ((long)(H2 - 1) * W2 + (W2 - 2)) * cout; p.ostep = cout;
+    hipLaunchKernelGGL(k_unet_compose_edge, dim3(1, (unsigned)(cout / EB_CO)), dim3(EB_CO * EB_G), 0, s, p);
+    return unet_launch_check("unet_compose_border");
 }
 
 int tip_unet_conv_first_dev(const float *in, int h, int w, const float *wgt, const float *bias, const float *scale, const float *shift,

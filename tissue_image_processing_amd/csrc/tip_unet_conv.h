@@ -29,6 +29,16 @@
 // Two inputs (in0 with c0 channels, then in1 with c1) are read as one concatenated tensor: the decoder's
 // concatenate([upsampled, skip]) (pl.py:52) never exists in memory.  A stride-2 transposed convolution is four such
 // convolutions, one per output parity class, with 4 / 2 / 2 / 1 taps and a strided output (tap lists built by the caller).
+// Two more modes let ONE layer's sum be spread over several launches, both runtime branches on a pointer in every flavour:
+//   * raw output (raw_out): the epilogue writes accumulator x acc_scale as float32 [outH][outW][cout] through the strided output
+//     mapping and nothing else -- no bias, no split, no saturation;
+//   * accumulator seed (seed): a float32 [H][W][cout] tensor is added to the layer's pre-bias sum -- loaded into the accumulator
+//     registers in the prologue (times 1 / acc_scale, a power of two), behind the first tiles' copies.
+// The decoder uses them to fold every Conv2DTranspose into the Conv2D behind it (there is no activation between the two, so their
+// composition is a 4 / 6 / 6 / 9-tap convolution per output parity on the LOW-resolution grid; weights built by the caller): four raw
+// launches leave the convolution's sum over its up-sampled half, k_unet_compose_edge / k_unet_compose_edge_bias (end of this file)
+// correct the edges the cropped transposed convolution makes special, and the convolution itself runs over the skip tensor alone,
+// seeded.  The up-sampled tensor never exists and the 2 / 2 / 1-tap parity launches, the slowest of the pass, are not run.
 // The kernel body has the details next to the code; DESIGN.md 5.7 has the measurements (clock trace, power-limited MFMA ceiling).
 #pragma once
 #include "tip_internal.h"
@@ -67,6 +77,8 @@ struct ConvParams {
     int xcd_map;                   // workgroup -> (tile, channel block) mapping, see the kernel
     float acc_scale;               // fp16 pieces: the accumulator is multiplied by this (1 / (activation scale x weight scale), a power of two) before the bias
     uint16_t *pool_out;            // nullptr, or [plane][outH / 2][outW / 2][cout]: MaxPool2D(2) of the output (needs sy = sx = 1)
+    float *raw_out;                // nullptr, or float32 [outH][outW][cout]: accumulator x acc_scale through the output mapping, nothing else ("raw output")
+    const float *seed;             // nullptr, or float32 [H][W][cout] added to the layer's pre-bias sum ("accumulator seed"; plain output mapping)
 };
 
 __device__ __forceinline__ unsigned bf16_rne_bits(float v)
@@ -322,6 +334,24 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
     copy_a(0, 0);
     if (DA == 2 && nchunks > 1) copy_a(1, 1);
     for (int s0 = 0; s0 < (PAIR ? 2 * SPB : D) && s0 < nsteps; ++s0) copy_b(s0 / p.ntaps, s0 % p.ntaps, s0);
+    if (p.seed) {
+        // accumulator seed: the lane's 2 x 4 x 16 values of a float32 [H][W][cout] tensor (its pixel's sixteen adjacent channels per
+        // 32-channel block: 64 contiguous bytes), in the accumulator's units (1 / acc_scale is a power of two: exact).  The loads go
+        // out behind the first tiles' copies and are waited for together with them.
+        const float up = 1.f / p.acc_scale;
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const float *sp = p.seed + ((long)(ty0 + wave * 2 + m) * p.W + tx0 + (lane & 31)) * p.cout + nblk * UC_BN + 16 * (lane >> 5);
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 v = *reinterpret_cast<const float4 *>(sp + n * 32 + q * 4);
+                    acc[m][n][q * 4 + 0] = F16 ? v.x * up : v.x; acc[m][n][q * 4 + 1] = F16 ? v.y * up : v.y;
+                    acc[m][n][q * 4 + 2] = F16 ? v.z * up : v.z; acc[m][n][q * 4 + 3] = F16 ? v.w * up : v.w;
+                }
+        }
+    }
     uc_wait_barrier<0>();
 
     const int r = lane & 31, h = lane >> 5;
@@ -514,6 +544,24 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
     int pxl = lane & 31, hf = lane >> 5;
     asm volatile("" : "+v"(pxl), "+v"(hf));           // (opaque: nothing of the epilogue's addressing is hoisted into the main loop's registers)
     unsigned char *ep = smem + wave * EP_BYTES;
+    if (p.raw_out) {
+        // raw output: accumulator x acc_scale as float32 [outH][outW][cout] -- a partial sum for a later launch's seed.  A lane's
+        // sixteen adjacent channels of a block are 64 contiguous bytes: stored straight from the registers.
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const int y = ty0 + wave * 2 + m;
+            float *op = p.raw_out + ((long)(y * p.sy + p.oy) * p.outW + ((long)(tx0 + pxl) * p.sx + p.ox)) * p.cout + nblk * UC_BN + 16 * hf;
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float4 v = {acc[m][n][q * 4 + 0], acc[m][n][q * 4 + 1], acc[m][n][q * 4 + 2], acc[m][n][q * 4 + 3]};
+                    if constexpr (F16) { v.x *= p.acc_scale; v.y *= p.acc_scale; v.z *= p.acc_scale; v.w *= p.acc_scale; }
+                    *reinterpret_cast<float4 *>(op + n * 32 + q * 4) = v;
+                }
+        }
+        return;
+    }
     {
         const float *bip = p.bias + nblk * UC_BN + 16 * hf;
         const float *scp = p.scale + nblk * UC_BN + 16 * hf, *shp = p.shift + nblk * UC_BN + 16 * hf;
@@ -839,6 +887,113 @@ __global__ void __launch_bounds__(256) k_unet_head(const uint16_t *__restrict__ 
         out[pix] = e0 / s;
         out[npix + pix] = e1 / s;
     }
+}
+
+// ---- border pass of a composed decoder level (Conv2DTranspose folded into the next Conv2D) -----------------------------
+// The composed launches compute the convolution of the UNCROPPED transposed convolution; the real network crops it to 2N rows and
+// columns, so on the last output row / column the term through the virtual row up[2N] = x[N-1] T2 has to go (and comes back once
+// at the corner), and the transposed convolution's bias reaches an edge pixel through fewer taps than an interior one.
+// k_unet_compose_edge walks ONE edge line of the float32 partial: low-resolution position j of the line owns the output pixels
+// 2j (parity 0: taps at j - 1, j) and 2j + 1 (parity 1: taps at j - 1, j, j + 1); part += sum over taps and input channels of
+// x[j + d] * wgt[tap] in plain float32 FMAs on the rejoined pieces of x.  A block: EB_J positions x EB_CO output channels, the input
+// channels dealt in sixteens to EB_G groups of threads whose sums are added in a fixed order (deterministic).
+constexpr int EB_J = 8, EB_CO = 64, EB_G = 8, EB_CH = 16 * EB_G;
+struct EdgeParams {
+    const uint16_t *x;             // split activations of the low-resolution grid
+    long xplane;                   // elements per plane
+    int planes, f16;
+    float xscale;                  // 1 / activation scale (fp16 pieces)
+    int cin, cout, L;              // line length in low-resolution positions
+    long x0, xstep;                // element offset of position 0 / from one position to the next
+    const float *wgt[5];           // [cin][cout] each: taps (parity, offset) = (0, -1) (0, 0) (1, -1) (1, 0) (1, +1), signs included
+    int tapmask;                   // taps that exist (the corner: tap 3 alone)
+    float *part;
+    long o0, ostep;                // element offset of the line's output pixel 0 / from one output pixel to the next
+};
+static __global__ void __launch_bounds__(EB_CO * EB_G) k_unet_compose_edge(const EdgeParams p)
+{
+    __shared__ float xs[EB_J + 2][EB_CH];
+    __shared__ float red[EB_G - 1][2 * EB_J][EB_CO];
+    const int tid = threadIdx.x, col = tid % EB_CO, g = tid / EB_CO;
+    const int j0 = blockIdx.x * EB_J, co = blockIdx.y * EB_CO + col;
+    float a[2][EB_J];
+#pragma unroll
+    for (int jj = 0; jj < EB_J; ++jj) a[0][jj] = a[1][jj] = 0.f;
+    for (int c0 = 0; c0 < p.cin; c0 += EB_CH) {
+        const int nch = min(EB_CH, p.cin - c0);          // (a multiple of 16: group g's sixteen channels exist or do not)
+        __syncthreads();
+        for (int i = tid; i < (EB_J + 2) * EB_CH; i += EB_CO * EB_G) {
+            const int jj = i / EB_CH, c = i - jj * EB_CH, j = j0 + jj - 1;
+            float v = 0.f;
+            if (c < nch && j >= 0 && j < p.L) {
+                const uint16_t *src = p.x + p.x0 + (long)j * p.xstep + c0 + c;
+                for (int pl = p.planes - 1; pl >= 0; --pl)       // smallest piece first; the sum is exact (<= 24 significant bits)
+                    v += p.f16 ? uc_piece_value<true>(src[pl * p.xplane]) : uc_piece_value<false>(src[pl * p.xplane]);
+                v *= p.xscale;
+            }
+            xs[jj][c] = v;
+        }
+        __syncthreads();
+        if (g * 16 < nch) {
+#pragma unroll
+            for (int k8 = 0; k8 < 16; k8 += 8) {
+                float w[8][5];          // eight channels' weights on their way before the first is used (the loop is latency-bound otherwise)
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+#pragma unroll
+                    for (int t = 0; t < 5; ++t)
+                        w[u][t] = ((p.tapmask >> t) & 1) ? p.wgt[t][(long)(c0 + g * 16 + k8 + u) * p.cout + co] : 0.f;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int k = g * 16 + k8 + u;
+#pragma unroll
+                    for (int jj = 0; jj < EB_J; ++jj) {
+                        const float xm = xs[jj][k], xc = xs[jj + 1][k], xp = xs[jj + 2][k];
+                        a[0][jj] = __builtin_fmaf(xc, w[u][1], __builtin_fmaf(xm, w[u][0], a[0][jj]));
+                        a[1][jj] = __builtin_fmaf(xp, w[u][4], __builtin_fmaf(xc, w[u][3], __builtin_fmaf(xm, w[u][2], a[1][jj])));
+                    }
+                }
+            }
+        }
+    }
+    if (g > 0) {
+#pragma unroll
+        for (int jj = 0; jj < EB_J; ++jj) { red[g - 1][2 * jj][col] = a[0][jj]; red[g - 1][2 * jj + 1][col] = a[1][jj]; }
+    }
+    __syncthreads();
+    if (g > 0) return;
+#pragma unroll
+    for (int jj = 0; jj < EB_J; ++jj)
+#pragma unroll
+        for (int par = 0; par < 2; ++par) {
+            if (j0 + jj >= p.L || !(p.tapmask & (par ? 0x1c : 0x3))) continue;
+            float v = a[par][jj];
+#pragma unroll
+            for (int q = 0; q < EB_G - 1; ++q) v += red[q][2 * jj + par][col];
+            p.part[p.o0 + (long)(2 * (j0 + jj) + par) * p.ostep + co] += v;
+        }
+}
+
+// the transposed convolution's bias through the next convolution's taps: the interior sum sits in that layer's bias vector, an edge
+// pixel gets (its own sum - the interior's) from a table [3 rows: top, inside, bottom][3 columns: left, inside, right][cout]
+static __global__ void __launch_bounds__(256) k_unet_compose_edge_bias(float *__restrict__ part, int H2, int W2, int cout, const float *__restrict__ tab)
+{
+    const int c4 = cout / 4;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long npix = 2L * W2 + 2L * (H2 - 2);
+    if (i >= npix * c4) return;
+    const long e = i / c4;
+    const int c = (int)(i - e * c4) * 4;
+    int y, x;
+    if (e < W2) { y = 0; x = (int)e; }
+    else if (e < 2L * W2) { y = H2 - 1; x = (int)(e - W2); }
+    else { const long k = e - 2L * W2; y = 1 + (int)(k >> 1); x = (k & 1) ? W2 - 1 : 0; }
+    const int type = (y == 0 ? 0 : (y == H2 - 1 ? 2 : 1)) * 3 + (x == 0 ? 0 : (x == W2 - 1 ? 2 : 1));
+    float4 *dst = reinterpret_cast<float4 *>(part + ((long)y * W2 + x) * cout + c);
+    const float4 t = *reinterpret_cast<const float4 *>(tab + (long)type * cout + c);
+    float4 v = *dst;
+    v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
+    *dst = v;
 }
 
 }  // namespace tip

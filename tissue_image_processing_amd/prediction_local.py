@@ -319,6 +319,7 @@ class _UNet(object):
         if self.hip_path_ok(x):
             return _unet_hip.forward(self, x, _unet_mode(), logits)
         self.last_mode = "miopen"
+        self.last_compose = ()
         with torch.no_grad():
             x = x.to(self.dtype).contiguous(memory_format=torch.channels_last)
             skips = []
