@@ -54,6 +54,12 @@ TIP_API int tip_memcpy_d2h(void *dst, const void *src, size_t bytes);
 TIP_API int tip_memcpy_d2d(void *dst, const void *src, size_t bytes);   /* asynchronous, calling thread's stream */
 /* a (height x width_bytes) block between pitched device buffers: the windows of the local-drift map (ti.py:2152-2166) */
 TIP_API int tip_memcpy2d_d2d(void *dst, size_t dst_pitch, const void *src, size_t src_pitch, size_t width_bytes, size_t height);
+/* out[c][r] = in[r][c] for a (rows x cols) plane of 4- or 8-byte elements (elem_bytes), DEVICE buffers, asynchronous on   */
+/* the calling thread's stream.  Replaces the `.T` a caller applies to SegmentationPredictor.predict's outputs (gui.py:2063: */
+/* predict(image (C, Y, X)) returns its int32 labels and float64 HC map as (X, Y), pl.py:102, 194) when it wants them in   */
+/* the image's own orientation and they are device tensors.  A bit copy (NaN payloads and -0.0 survive); any extents; not */
+/* in place: in == out, a null pointer, an extent < 1 or another element size give TIP_ERR_ARG.                           */
+TIP_API int tip_transpose2d_dev(const void *in, void *out, int rows, int cols, int elem_bytes);
 TIP_API int tip_memset(void *dst, int value, size_t bytes);
 TIP_API int tip_sync(void);                       /* wait for this thread's stream */
 /* Tuning and test hooks, process-wide.  The library reads the TIP_* environment variables ONCE (at first use) and   */

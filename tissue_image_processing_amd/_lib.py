@@ -146,6 +146,12 @@ class DeviceBuffer:
             pass
 
 
+def transpose2d_dev(in_ptr, out_ptr, rows, cols, elem_bytes):
+    """tip_transpose2d_dev: out[c][r] = in[r][c] between DEVICE buffers of 4- or 8-byte elements (a bit copy), asynchronous on
+    the calling thread's library stream.  ValueError for another element size, an extent < 1, a null pointer or in == out."""
+    check(lib().tip_transpose2d_dev(dptr(in_ptr or 0), dptr(out_ptr or 0), int(rows), int(cols), int(elem_bytes)))
+
+
 WS_FLAG_TIES, WS_FLAG_TWO_VALUED, WS_FLAG_SERIAL_EXACT, WS_FLAG_SERIAL_FINISH, WS_FLAG_COUNT_SHIFT = 1, 2, 4, 8, 8
 
 

@@ -335,7 +335,10 @@ int tip_memcpy_d2d(void *dst, const void *src, size_t bytes)   // asynchronous o
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    TIP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c.stream));
+    prof_begin("memcpy_d2d");      // (timed like a kernel when profiling is on: the yardstick of tip_transpose2d_dev)
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c.stream);
+    prof_end();
+    TIP_HIP(e);
     return TIP_OK;
 }
 

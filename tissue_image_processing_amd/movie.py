@@ -25,6 +25,11 @@ on the resident labels and Atoh-channel projection (one device call, tip_cell_ty
 and mean_intensity, named in the backend's `extra_columns`, travel with the centroid tables, and the type map stays on the
 owner GPU next to the label map.
 
+With `GpuFrameBackend(segmentation="unet")` every frame is segmented as the GUI's "use Unet?" path does (gui.py:2059-2063):
+network and closing / watershed tail through FramePipeline.segment_unet, whose labels (and, with keep_hc, HC map) come back in
+frame orientation (Y, X) and are copied on the device into the buffers the classical segmentation fills, so that every stage
+above runs on them unchanged.  Each pipeline has its own predictor and each worker thread its own torch stream.
+
 `backend` supplies the per-frame compute so the same driver runs on GPUs (GpuFrameBackend) and, for the
 multi-process CPU tests, on a stand-in backend with the gloo process group.
 """
@@ -63,6 +68,14 @@ class _FrameWorker(object):
         from . import _lib
         from .pipeline import FramePipeline
         b = self.backend
+        if b.segmentation == "unet":      # the threads do not share torch's default stream: no frame waits for another's network
+            import torch
+            with torch.cuda.stream(torch.cuda.Stream(b.device)):
+                self.serve(b, _lib, FramePipeline)
+        else:
+            self.serve(b, _lib, FramePipeline)
+
+    def serve(self, b, _lib, FramePipeline):
         pipe, setup_error = None, None
         try:
             _lib.init(b.device)
@@ -88,6 +101,7 @@ class _FrameWorker(object):
                 finally:
                     job.done.release()
         finally:
+            b._predictors.pop(id(pipe), None)    # (U-Net mode: this pipeline's predictor goes with it)
             pipe = None                          # (its DeviceBuffers go back before the context that launched on them)
             try:
                 _lib.load().tip_shutdown()
@@ -106,9 +120,33 @@ class GpuFrameBackend(object):
     CELL_TYPE_OPTIONS = ("atoh_channel", "threshold", "percentage_above_threshold", "peak_window_size", "type_index",
                          "min_cell_area", "max_cell_area")
 
-    def __init__(self, C, Z, Y, X, device=None, keep_planes=False, inflight=1, cell_types=None, **kw):
+    SEGMENTATIONS = ("classical", "unet")
+
+    def __init__(self, C, Z, Y, X, device=None, keep_planes=False, inflight=1, cell_types=None, segmentation="classical",
+                 unet_weights=None, unet_channels=(1, 0), predictor_factory=None, keep_hc=False, **kw):
         from .pipeline import FramePipeline
         from . import _lib
+        # segmentation: "classical" (FramePipeline.segment: threshold, blur, watershed on channel 0) or "unet", the GUI's "use
+        # Unet?" path (FramePipeline.segment_unet_frame: network + closing / watershed tail on the (atoh, zo) planes
+        # unet_channels, labels (Y, X) copied on the device into the pipeline's label buffer).  Every pipeline -- this one and each worker's -- then owns
+        # a predictor, built the first time that pipeline segments: predictor_factory(device), by default
+        # SegmentationPredictor(unet_weights, (2, X, Y), device=device).  keep_hc: every frame's HC map stays resident (fetch_hc).
+        if segmentation not in self.SEGMENTATIONS:
+            raise ValueError("segmentation must be one of %s, not %r" % (", ".join(repr(s) for s in self.SEGMENTATIONS), segmentation))
+        if segmentation == "classical":
+            given = [name for name, v in (("unet_weights", unet_weights), ("predictor_factory", predictor_factory), ("keep_hc", keep_hc))
+                     if v is not None and v is not False]
+            if given:
+                raise ValueError("%s: only with segmentation='unet' (segmentation is one of %s)"
+                                 % (", ".join(given), ", ".join(repr(s) for s in self.SEGMENTATIONS)))
+        else:
+            kw = dict(kw, use_torch=True)      # the projection is a torch tensor the predictor reads in place
+        self.segmentation, self.unet_weights, self.unet_channels = segmentation, unet_weights, tuple(unet_channels)
+        self.predictor_factory, self.keep_hc = predictor_factory, bool(keep_hc)
+        self._predictors = {}   # id(pipeline) -> its SegmentationPredictor (U-Net mode), built on first use
+        self.hc_maps = {}       # frame -> DeviceBuffer (float64 HC map (Y, X)), with keep_hc
+        self.unet_modes = {}    # frame -> the arithmetic its network pass really ran in (model.last_mode; "miopen": torch's layers)
+        self.ws_flags = {}      # frame -> flags of its tail's watershed (U-Net mode)
         self._shape, self._kw = (C, Z, Y, X), kw
         # cell_types: None, or FramePipeline.cell_types' keyword arguments (atoh_channel, threshold, percentage_above_threshold,
         # peak_window_size, type_index, min_cell_area, max_cell_area) -- every frame is then typed on the device after its
@@ -159,12 +197,44 @@ class GpuFrameBackend(object):
         return job.out
 
     def close(self):
-        """Ends the worker threads; each releases its pipeline buffers and its library context (tip_shutdown) on the way out."""
+        """Ends the worker threads; each releases its pipeline buffers and its library context (tip_shutdown) on the way out --
+        in U-Net mode its predictor and its torch stream too; this pipeline's predictor goes as well (a later frame builds
+        a new one)."""
         workers, self._workers = self._workers, []
         for w in workers:
             w.jobs.put(None)
         for w in workers:
             w.join()
+        self._predictors.clear()
+
+    def _predictor_for(self, p):
+        """Pipeline p's own predictor, built on the thread that first segments with p."""
+        pred = self._predictors.get(id(p))
+        if pred is None:
+            if self.predictor_factory is not None:
+                pred = self.predictor_factory(self.device)
+            else:
+                from .prediction_local import SegmentationPredictor
+                pred = SegmentationPredictor(self.unet_weights, (2, self.X, self.Y), device=self.device)
+            self._predictors[id(p)] = pred
+        return pred
+
+    def _segment_unet(self, p, t):
+        """Frame t's U-Net segmentation on pipeline p: labels in p.d_labels as (Y, X), as segment() leaves them; the frame's
+        network mode and watershed flags are noted, and with keep_hc its HC map is kept like the label map."""
+        from . import _lib
+        pred = self._predictor_for(p)
+        p.segment_unet_frame(pred, self.unet_channels[0], self.unet_channels[1], keep_hc=self.keep_hc)
+        self.unet_modes[t], self.ws_flags[t] = getattr(pred.model, "last_mode", None), int(pred.last_flags)
+        if self.keep_hc:
+            nbytes = self.Y * self.X * 8
+            keep = _lib.DeviceBuffer(nbytes)
+            _lib.check(p.lib.tip_memcpy_d2d(_lib.dptr(keep.ptr), _lib.dptr(p.d_hc.ptr), nbytes))
+            self.hc_maps[t] = keep
+
+    def fetch_hc(self, t):
+        """Frame t's HC map (float64 (Y, X): 255 inside the eroded closed class map, 0 elsewhere), downloaded."""
+        return self.hc_maps[t].download((self.Y, self.X), np.float64)
 
     def _process_with(self, p, t, stack_u16):
         from . import _lib
@@ -175,7 +245,10 @@ class GpuFrameBackend(object):
         else:
             d_stack = p.upload_stack(stack_u16)
         p.project(d_stack)
-        p.segment(0)
+        if self.segmentation == "unet":
+            self._segment_unet(p, t)
+        else:
+            p.segment(0)
         nbytes = self.Y * self.X * 4
         keep = _lib.DeviceBuffer(nbytes)
         _lib.check(p.lib.tip_memcpy_d2d(_lib.dptr(keep.ptr), _lib.dptr(p.d_labels.ptr), nbytes))

@@ -80,6 +80,34 @@ class FramePipeline:
         self._unet_labels = lab
         return lab, hc
 
+    def segment_unet_frame(self, predictor, atoh_channel=1, zo_channel=0, keep_hc=False):
+        """segment_unet with the result left where segment() leaves its own: the int32 labels in self.d_labels as (Y, X) --
+        cell_tables(), cell_types(...) and fetch_labels() then work as after segment(), the label count being the tail's --
+        and, with keep_hc, the float64 HC map in self.d_hc (fetch_hc()).
+
+        No transpose is needed: segment_unet hands predict the TRANSPOSED planes (2, X, Y) and predict returns its results
+        transposed against its input (pl.py:102, 194: labels of shape (input.shape[2], input.shape[1])), so the two cancel
+        and the tensors come back in frame orientation (Y, X), aligned with the projection.  They are copied on the library's
+        stream behind the tail (device to device, nothing waits here).  The copies read torch tensors, so both stay referenced
+        by the pipeline until the next U-Net call has passed the tail's tip_sync: a block must not go back to torch's caching
+        allocator while the library's stream still reads it."""
+        lab, hc = self.segment_unet(predictor, atoh_channel, zo_channel)
+        if tuple(lab.shape) != (self.Y, self.X) or tuple(hc.shape) != (self.Y, self.X):
+            raise RuntimeError("segment_unet returned %s labels for a %d x %d frame" % (tuple(lab.shape), self.Y, self.X))
+        P = self.Y * self.X
+        _lib.check(self.lib.tip_memcpy_d2d(_lib.dptr(self.d_labels.ptr), _lib.dptr(lab.data_ptr()), ctypes.c_size_t(P * 4)))
+        if keep_hc:
+            if getattr(self, "d_hc", None) is None:
+                self.d_hc = _lib.DeviceBuffer(P * 8)
+            _lib.check(self.lib.tip_memcpy_d2d(_lib.dptr(self.d_hc.ptr), _lib.dptr(hc.data_ptr()), ctypes.c_size_t(P * 8)))
+        self._unet_hc = hc          # (the labels are held as self._unet_labels)
+
+    def fetch_hc(self):
+        """The HC map of the last segment_unet_frame(keep_hc=True): float64 (Y, X), downloaded."""
+        if getattr(self, "d_hc", None) is None:
+            raise RuntimeError("no HC map is resident: segment_unet_frame(..., keep_hc=True) keeps it")
+        return self.d_hc.download((self.Y, self.X), np.float64)
+
     def cell_tables(self, max_cells=None, labels_ptr=None, shape=None):
         """C1-C2 (ti.py:880-909, 1815-1842): per-cell reductions + neighbour pairs on the resident label map; the small
         per-cell arrays come back to the host (they are what a rank gathers for track stitching)."""
