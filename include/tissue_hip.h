@@ -334,6 +334,34 @@ TIP_API int tip_lookup_max3_i32_dev(const int32_t *labels, int y, int x, const i
 /* Tissue.get_trackking_labels (ti.py:4021-4028): out[p] = lut[labels[p]] (lut[0] = 0)              */
 TIP_API int tip_lut_gather_i32(const int32_t *labels, const int64_t *lut, int64_t n_lut, int64_t *out, int64_t n);
 
+/* ---- window statistics and spatial feature maps (ti.py:1200-1266: calculate_spatial_data, the windows of get_frame_data) ---- */
+/* For each of m centres (qy, qx) and a table of n rows (cy, cx float64, area int64, type uint8, feat float64 or NULL = zeros):   */
+/* n_in = rows with (cx - qx)^2 + (cy - qy)^2 < r2 -- two subtractions, two squarings, one addition, each rounded to float64, a  */
+/* strict <, as numpy evaluates upstream's query (ti.py:1266); area_in = the exact sum of their areas; n_sel = those that also   */
+/* pass the type selector; sum_sel = the sum of feat over the selected ones, in table order.  Selector: sel_bit -1 = every row, */
+/* else is_positive_for_type(type, sel_bit) (bit set and type != 255, ti.py:146-176) when sel_positive != 0 and its negation    */
+/* otherwise.  r2 = +inf takes every row with finite coordinates.  m = 0 and n = 0 are valid.  The caller applies upstream's   */
+/* "%f" rounding of the centres and of r2 (ti.py:1266) before the call.                                                         */
+TIP_API int tip_window_stats_f64(const double *qy, const double *qx, int64_t m, double r2, const double *cy, const double *cx,
+                                 const int64_t *area, const uint8_t *type, const double *feat, int64_t n, int sel_bit,
+                                 int sel_positive, int64_t *n_in, int64_t *area_in, int64_t *n_sel, double *sum_sel);
+TIP_API int tip_window_stats_f64_dev(const double *qy, const double *qx, int64_t m, double r2, const double *cy, const double *cx,
+                                     const int64_t *area, const uint8_t *type, const double *feat, int64_t n, int sel_bit,
+                                     int sel_positive, int64_t *n_in, int64_t *area_in, int64_t *n_sel, double *sum_sel);
+/* Tissue.calculate_spatial_data (ti.py:1239-1258): the statistics above at the grid points (s/2 + i s, s/2 + j s) below (y, x),  */
+/* s = step; per point the value of `mode` -- 0 density: n_sel / area_in (0 when n_sel == 0 or area_in <= 0), 1 type fraction:  */
+/* n_sel / n_in (0 when n_sel == 0), 2 mean: sum_sel / n_sel (NaN when n_sel == 0) -- and the (y, x) float64 map: zero, with the */
+/* block [py - s/2, py + s/2) x [px - s/2, px + s/2) of each point set to its value (an odd s leaves one-pixel seams, s = 1 an  */
+/* empty map, the frame clips the last block: upstream's slices).  n_sel_grid: NULL, or ceil((y - s/2) / s) x ceil((x - s/2) /  */
+/* s) counts, row-major -- a mean-mode caller finds there the windows that selected no cell.  The _dev form takes device       */
+/* pointers and leaves map (and n_sel_grid) in the caller's device buffers.                                                    */
+TIP_API int tip_spatial_map_f64(int y, int x, int step, double r2, const double *cy, const double *cx, const int64_t *area,
+                                const uint8_t *type, const double *feat, int64_t n, int sel_bit, int sel_positive, int mode,
+                                double *map, int64_t *n_sel_grid);
+TIP_API int tip_spatial_map_f64_dev(int y, int x, int step, double r2, const double *cy, const double *cx, const int64_t *area,
+                                    const uint8_t *type, const double *feat, int64_t n, int sel_bit, int sel_positive, int mode,
+                                    double *map, int64_t *n_sel_grid);
+
 /* ---- drift: skimage.registration.phase_cross_correlation(ref, mov, upsample_factor) ---------------------------- */
 /* (ti.py:1976-1977, 2029-2030 update_drift / calculate_refine_drift; bim.py:522-536 calculate_drift).               */
 /* dtype: 0 float32, 1 float64, 3 uint16; extents in [2, 4096] (powers of two: radix-2 FFT rows; anything else: Bluestein).  out4 = whole-pixel peak (row, col) of       */

@@ -248,3 +248,74 @@ def cell_types_dev(labels_ptr, marker_ptr, y, x, n, percentage_above_threshold, 
         ctypes.c_double(threshold), int(peak_window_size), _lib.ptr(taps), 0 if taps is None else int(taps.size), int(type_index),
         ctypes.c_double(min_cell_area), ctypes.c_double(max_cell_area), _lib.dptr(out_type_ptr or 0), _lib.dptr(out_valid_ptr or 0),
         _lib.dptr(out_mean_ptr or 0), _lib.dptr(out_type_map_ptr)))
+
+
+def _cell_columns(cy, cx, area, type, feat):
+    """the table's columns as the C-ABI takes them (float64 / int64 / uint8, contiguous); feat None: no feature column"""
+    cy = np.ascontiguousarray(cy, dtype=np.float64)
+    cx = np.ascontiguousarray(cx, dtype=np.float64)
+    area = np.ascontiguousarray(area, dtype=np.int64)
+    type = np.ascontiguousarray(type, dtype=np.uint8)
+    feat = None if feat is None else np.ascontiguousarray(feat, dtype=np.float64)
+    n = cy.size
+    if any(a is not None and a.size != n for a in (cx, area, type, feat)):
+        raise ValueError("the cell table's columns differ in length")
+    return cy, cx, area, type, feat, n
+
+
+def window_stats(qy, qx, r2, cy, cx, area, type, feat=None, sel_bit=-1, sel_positive=True):
+    """tip_window_stats_f64: per centre (qy[i], qx[i]) the rows with (cx - qx)**2 + (cy - qy)**2 < r2 -> (n_in, area_in, n_sel,
+    sum_sel); n_sel / sum_sel count the rows that also pass the type selector (sel_bit -1: all of them)."""
+    qy = np.ascontiguousarray(qy, dtype=np.float64).reshape(-1)
+    qx = np.ascontiguousarray(qx, dtype=np.float64).reshape(-1)
+    if qy.size != qx.size:
+        raise ValueError("qy and qx differ in length")
+    cy, cx, area, type, feat, n = _cell_columns(cy, cx, area, type, feat)
+    m = qy.size
+    n_in, area_in, n_sel = np.zeros(m, np.int64), np.zeros(m, np.int64), np.zeros(m, np.int64)
+    sum_sel = np.zeros(m, np.float64)
+    _lib.check(_lib.lib().tip_window_stats_f64(
+        _lib.ptr(qy), _lib.ptr(qx), ctypes.c_int64(m), ctypes.c_double(r2), _lib.ptr(cy), _lib.ptr(cx), _lib.ptr(area), _lib.ptr(type),
+        _lib.ptr(feat), ctypes.c_int64(n), int(sel_bit), 1 if sel_positive else 0, _lib.ptr(n_in), _lib.ptr(area_in), _lib.ptr(n_sel),
+        _lib.ptr(sum_sel)))
+    return n_in, area_in, n_sel, sum_sel
+
+
+SPATIAL_MODES = {"density": 0, "type_fraction": 1, "mean": 2}
+
+
+def spatial_grid_shape(shape, step):
+    """number of grid points range(step // 2, extent, step) per axis"""
+    return tuple(len(range(step // 2, int(e), step)) for e in shape)
+
+
+def spatial_map(shape, step, r2, cy, cx, area, type, feat=None, sel_bit=-1, sel_positive=True, mode="density"):
+    """tip_spatial_map_f64: the (Y, X) float64 map of Tissue.calculate_spatial_data and the grid's n_sel counts."""
+    Y, X = int(shape[0]), int(shape[1])
+    cy, cx, area, type, feat, n = _cell_columns(cy, cx, area, type, feat)
+    out = np.empty((Y, X), np.float64)
+    n_sel = np.zeros(spatial_grid_shape((Y, X), int(step)), np.int64)
+    _lib.check(_lib.lib().tip_spatial_map_f64(
+        Y, X, int(step), ctypes.c_double(r2), _lib.ptr(cy), _lib.ptr(cx), _lib.ptr(area), _lib.ptr(type), _lib.ptr(feat),
+        ctypes.c_int64(n), int(sel_bit), 1 if sel_positive else 0, SPATIAL_MODES[mode], _lib.ptr(out), _lib.ptr(n_sel)))
+    return out, n_sel
+
+
+def spatial_map_dev(shape, step, r2, cy_ptr, cx_ptr, area_ptr, type_ptr, feat_ptr, n, sel_bit, sel_positive, mode, map_ptr,
+                    n_sel_ptr=None):
+    """tip_spatial_map_f64_dev: the same on DEVICE buffers (addresses), asynchronous on the calling thread's stream; the map
+    stays in the caller's device buffer map_ptr ((Y, X) float64), the grid's n_sel counts in n_sel_ptr when given."""
+    _lib.check(_lib.lib().tip_spatial_map_f64_dev(
+        int(shape[0]), int(shape[1]), int(step), ctypes.c_double(r2), _lib.dptr(cy_ptr or 0), _lib.dptr(cx_ptr or 0),
+        _lib.dptr(area_ptr or 0), _lib.dptr(type_ptr or 0), _lib.dptr(feat_ptr or 0), ctypes.c_int64(n), int(sel_bit),
+        1 if sel_positive else 0, SPATIAL_MODES[mode], _lib.dptr(map_ptr or 0), _lib.dptr(n_sel_ptr or 0)))
+
+
+def window_stats_dev(qy_ptr, qx_ptr, m, r2, cy_ptr, cx_ptr, area_ptr, type_ptr, feat_ptr, n, sel_bit, sel_positive, n_in_ptr,
+                     area_in_ptr, n_sel_ptr, sum_sel_ptr):
+    """tip_window_stats_f64_dev: device addresses in and out, asynchronous on the calling thread's stream."""
+    _lib.check(_lib.lib().tip_window_stats_f64_dev(
+        _lib.dptr(qy_ptr or 0), _lib.dptr(qx_ptr or 0), ctypes.c_int64(m), ctypes.c_double(r2), _lib.dptr(cy_ptr or 0),
+        _lib.dptr(cx_ptr or 0), _lib.dptr(area_ptr or 0), _lib.dptr(type_ptr or 0), _lib.dptr(feat_ptr or 0), ctypes.c_int64(n),
+        int(sel_bit), 1 if sel_positive else 0, _lib.dptr(n_in_ptr or 0), _lib.dptr(area_in_ptr or 0), _lib.dptr(n_sel_ptr or 0),
+        _lib.dptr(sum_sel_ptr or 0)))

@@ -12,6 +12,8 @@ reference's state / cache / persistence code (ti.py:193-353, 3462-3823) stays th
     calc_neighbors_contact_matrix(frame)                   ti.py:4073-4094 -> tip_rankfilter2d (cross footprint)
     track_cells_iterator(...)                              ti.py:2037-2113 -> tip_rankfilter2d + host table logic
     get_trackking_labels(frame)                            ti.py:4021-4028 -> tip_lut_gather_i32
+    calculate_spatial_data(...), get_frame_data(...),      ti.py:1035-1134, 1194-1266 -> tip_spatial_map_f64, tip_window_stats_f64
+    calculate_data_around_a_given_point / _cell
 """
 import ctypes
 
@@ -1034,6 +1036,245 @@ class TissueHipMixin(object):
             yield frame
         return 0
 
+    # ---- spatial feature maps and window statistics (ti.py:1035-1134, 1194-1266, 1610-1644) -----------------------------------
+    # feature names the GUI offers (ti.py:198-208); get_frame_data's callers pass these lists back in
+    SPECIAL_FEATURES = ["shape index", "roundness", "neighbors from the same type", "HC neighbors", "SC neighbors", "HC second neighbors",
+                        "SC second neighbors", "second neighbors", "second neighbors from the same type", "contact length",
+                        "HC contact length", "SC contact length", "Mean atoh intensity", "Distance from ablation", "neighbors by type"]
+    SPATIAL_FEATURES = ["HC density", "SC density", "HC type_fraction", "SC type_fraction"]
+    SPECIAL_X_ONLY_FEATURES = ["psi6"]
+    GLOBAL_FEATURES = ["density", "type_fraction", "total_area", "number_of_cells", "neighbors correlation",
+                       "neighbors correlation average"]
+
+    def get_valid_non_edge_cells(self, frame, cells):
+        """ti.py:1194-1198: the valid, non-empty rows whose cell does not touch the frame's border."""
+        on_border = self.detect_edge_cells(self.get_labels(frame))
+        keep = (cells["valid"].to_numpy() == 1) & (cells["empty_cell"].to_numpy() == 0) & ~cells.index.isin(on_border)
+        return cells[keep]
+
+    @staticmethod
+    def _window_r2(radius):
+        """upstream writes radius**2 into its query text with "%f" (ti.py:1266): six decimals reach the comparison"""
+        return float("%f" % (radius ** 2))
+
+    @staticmethod
+    def get_cells_inside_a_circle(cells, center, radius):
+        """ti.py:1262-1266: rows with (cx - x)**2 + (cy - y)**2 < radius**2, center = (y, x); centre and squared radius pass
+        through "%f" (six decimals) first, as upstream's query text does."""
+        y, x = float("%f" % center[0]), float("%f" % center[1])
+        r2 = TissueHipMixin._window_r2(radius)
+        cx, cy = cells["cx"].to_numpy(dtype=np.float64), cells["cy"].to_numpy(dtype=np.float64)
+        return cells[(cx - x) ** 2 + (cy - y) ** 2 < r2]
+
+    @staticmethod
+    def calculate_cells_roundness(cells):
+        """ti.py:1610-1612: 4 pi area / perimeter^2 with upstream's six-decimal pi ("%f" % np.pi)."""
+        six_decimal_pi = float("%f" % np.pi)
+        return 4 * six_decimal_pi * cells["area"].to_numpy() / (cells["perimeter"].to_numpy() ** 2)
+
+    @staticmethod
+    def calculate_cells_shape_index(cells):
+        """ti.py:1614-1616: perimeter / area**(1/2) (a power, as upstream evaluates it, not np.sqrt: numpy's pow may differ from
+        the square root in the last bit)."""
+        return cells["perimeter"].to_numpy() / (cells["area"].to_numpy() ** (1 / 2))
+
+    @staticmethod
+    def calculate_total_area(cells):
+        return np.sum(cells["area"].to_numpy())
+
+    def calculate_density(self, frame, relevant_cells, reference_area=None):
+        """ti.py:1622-1632: cells per pixel of reference area (default: the area of every non-empty row); -1 without a table."""
+        table = self.get_cells_info(frame)
+        if table is None:
+            return -1
+        if reference_area is None:
+            reference_area = self.calculate_total_area(table[table["empty_cell"].to_numpy() == 0])
+        return relevant_cells.shape[0] / reference_area if reference_area > 0 else 0
+
+    def calculate_type_fraction(self, frame, relevant_cells, reference_cell_num=None):
+        """ti.py:1634-1644: share of the reference cell number (default: the valid non-empty rows); -1 without a table."""
+        table = self.get_cells_info(frame)
+        if table is None:
+            return -1
+        if reference_cell_num is None:
+            reference_cell_num = int(np.count_nonzero((table["valid"].to_numpy() == 1) & (table["empty_cell"].to_numpy() == 0)))
+        return relevant_cells.shape[0] / reference_cell_num if reference_cell_num > 0 else 0
+
+    def _split_spatial_feature(self, feature, cells_type):
+        """"HC density" -> ("density", "HC") for the names in SPATIAL_FEATURES (ti.py:1209-1212)"""
+        if feature in self.SPATIAL_FEATURES:
+            cells_type, feature = feature.split(" ")[:2]
+        return feature, cells_type
+
+    def _window_selector(self, cells_type, positive_for_type):
+        """(type bit or -1, polarity) for tip_window_stats_f64.  A name that is no type raises KeyError: upstream indexes the
+        table with the scalar False that is_positive_for_type gives for index -1 (ti.py:164-165, 1223)."""
+        if cells_type == "all":
+            return -1, True
+        index = self.type_name_to_index(cells_type)
+        if isinstance(index, tuple):
+            raise NotImplementedError("window statistics over a pos / neg type list (%r)" % (cells_type,))
+        if index < 0:
+            raise KeyError(cells_type)
+        return int(index), bool(positive_for_type)
+
+    def _behind_mixin(self, name):
+        """the method `name` of the class this mixin sits in front of (`class Tissue(TissueHipMixin, reference.Tissue)`), or None
+        when nothing is behind it (the stand-alone Tissue below)"""
+        return getattr(super(TissueHipMixin, self), name, None)
+
+    def _window_feature(self, frame, feature, cells):
+        """(mode, feature column over `cells`): the two ratio features need no column, everything else is averaged.  A feature
+        that is no per-row column (the other globals; a special feature that gives another number of values) raises
+        NotImplementedError: the device map has the three modes of tip_spatial_map_f64 only."""
+        if feature in ("density", "type_fraction"):
+            return feature, None
+        if feature in self.GLOBAL_FEATURES or feature in self.SPATIAL_FEATURES:
+            raise NotImplementedError("window statistics of the feature %r" % (feature,))
+        column, _ = self.get_frame_data(frame, feature, cells, special_features=self.SPECIAL_FEATURES + self.SPECIAL_X_ONLY_FEATURES,
+                                        spatial_features=self.SPATIAL_FEATURES, global_features=self.GLOBAL_FEATURES,
+                                        for_histogram=True, reference=1)
+        column = np.asarray(column, dtype=np.float64)
+        if column.shape != (cells.shape[0],):
+            raise NotImplementedError("window statistics of the feature %r (not one value per cell)" % (feature,))
+        return "mean", column
+
+    @staticmethod
+    def _window_stats(cells, qy, qx, r2, selector, feat=None, everywhere=False):
+        """tip_window_stats_f64 over the rows of `cells`; everywhere: every row counts as inside (the rows were chosen before).
+        area and type go to the device as int64 / uint8, as the table holds them; a float area column would be truncated"""
+        n = cells.shape[0]
+        cy = np.zeros(n) if everywhere else cells["cy"].to_numpy(dtype=np.float64)
+        cx = np.zeros(n) if everywhere else cells["cx"].to_numpy(dtype=np.float64)
+        return seg.window_stats(qy, qx, r2, cy, cx, cells["area"].to_numpy().astype(np.int64),
+                                cells["type"].to_numpy().astype(np.uint8), feat, selector[0], selector[1])
+
+    @staticmethod
+    def _ratio_value(mode, n_in, area_in, n_sel):
+        """density / type_fraction of one window from its counts (ti.py:1214-1234, 1629-1632, 1641-1644)"""
+        if n_sel == 0:
+            return 0
+        if mode == "density":
+            return n_sel / area_in if area_in > 0 else 0
+        return n_sel / n_in
+
+    def calculate_spatial_data_for_given_cells(self, frame, relevant_cells, feature, cells_type, positive_for_type=True):
+        """ti.py:1208-1236 for rows already chosen: (density or type fraction, "") -- the selected rows over the area / the number
+        of all given rows --, or (the feature's values over the selected rows, ""), or (None, "No matching cells").  The counts
+        come from tip_window_stats_f64 with one window that takes every row."""
+        feature, cells_type = self._split_spatial_feature(feature, cells_type)
+        selector = self._window_selector(cells_type, positive_for_type)
+        n_in, area_in, n_sel, _ = self._window_stats(relevant_cells, [0.0], [0.0], np.inf, selector, everywhere=True)
+        if feature in ("density", "type_fraction"):
+            return self._ratio_value(feature, int(n_in[0]), int(area_in[0]), int(n_sel[0])), ""
+        if int(n_sel[0]) == 0:
+            return None, "No matching cells"
+        chosen = relevant_cells
+        if selector[0] >= 0:
+            positive = is_positive_for_type(relevant_cells["type"].to_numpy(), selector[0])
+            chosen = relevant_cells[positive if selector[1] else ~positive]
+        return self.get_frame_data(frame, feature, chosen, special_features=self.SPECIAL_FEATURES + self.SPECIAL_X_ONLY_FEATURES,
+                                   spatial_features=self.SPATIAL_FEATURES, global_features=self.GLOBAL_FEATURES, for_histogram=True,
+                                   reference=1)
+
+    def calculate_data_around_a_given_point(self, frame, point_x, point_y, valid_cells, radius, feature, cells_type,
+                                            positive_for_type=True):
+        """ti.py:1204-1206: the same over the rows of valid_cells inside the circle of `radius` around (point_x, point_y).  The
+        two ratio features come straight from the window statistics; a feature that returns per-cell values needs the rows."""
+        name, kind = self._split_spatial_feature(feature, cells_type)
+        if name in ("density", "type_fraction"):
+            selector = self._window_selector(kind, positive_for_type)
+            n_in, area_in, n_sel, _ = self._window_stats(valid_cells, [float("%f" % point_y)], [float("%f" % point_x)],
+                                                         self._window_r2(radius), selector)
+            return self._ratio_value(name, int(n_in[0]), int(area_in[0]), int(n_sel[0])), ""
+        inside = self.get_cells_inside_a_circle(valid_cells, (point_y, point_x), radius)
+        return self.calculate_spatial_data_for_given_cells(frame, inside, feature, cells_type, positive_for_type=positive_for_type)
+
+    def calculate_data_around_a_given_cell(self, frame, cell, valid_cells, radius, feature, cells_type, positive_for_type=True):
+        """ti.py:1200-1202: the window around a table row's centroid."""
+        return self.calculate_data_around_a_given_point(frame, cell.cx, cell.cy, valid_cells, radius, feature, cells_type,
+                                                        positive_for_type=positive_for_type)
+
+    def calculate_spatial_data(self, frame, window_radius, step_size, feature, cells_type='all', positive_for_type=True):
+        """ti.py:1239-1258: the (Y, X) map of a feature averaged over the valid non-edge cells inside a circle of window_radius
+        around every step_size-th pixel; (map, "") or (None, message).  One device call (tip_spatial_map_f64): grid, window
+        statistics, per-point value and the block fill, upstream's slices included (step_size // 2 on both sides of a grid point:
+        an odd step leaves seams, step 1 an empty map).  A feature that is averaged gives (None, "No matching cells") as soon as
+        one window selects no cell, as upstream."""
+        labels = self.get_labels(frame)
+        cells = self.get_valid_non_edge_cells(frame, self.get_cells_info(frame))
+        shape = np.shape(labels)
+        if 0 in seg.spatial_grid_shape(shape, step_size):
+            return np.zeros(shape), ""
+        asked = (feature, cells_type)
+        feature, cells_type = self._split_spatial_feature(feature, cells_type)
+        selector = self._window_selector(cells_type, positive_for_type)
+        try:
+            mode, column = ("mean", None) if cells.shape[0] == 0 and feature not in ("density", "type_fraction") else \
+                self._window_feature(frame, feature, cells)
+        except NotImplementedError:
+            behind = self._behind_mixin("calculate_spatial_data")      # e.g. "total_area": the host class's own loop, when there is one
+            if behind is None:
+                raise
+            return behind(frame, window_radius, step_size, asked[0], cells_type=asked[1], positive_for_type=positive_for_type)
+        out, n_sel = seg.spatial_map(shape, step_size, self._window_r2(window_radius), cells["cy"].to_numpy(dtype=np.float64),
+                                     cells["cx"].to_numpy(dtype=np.float64), cells["area"].to_numpy().astype(np.int64),
+                                     cells["type"].to_numpy().astype(np.uint8), column, selector[0], selector[1], mode)
+        if mode == "mean" and (n_sel == 0).any():
+            return None, "No matching cells"
+        return out, ""
+
+    def get_frame_data(self, frame, feature, valid_cells, special_features=[], global_features=[], spatial_features=[],
+                       for_histogram=False, reference=None, intensity_img=None, window_radius=0, types=None):
+        """ti.py:1035-1134: (data, "") for plain table columns, "shape index" / "roundness" / "Mean atoh intensity", the globals
+        "density", "type_fraction", "total_area", "number_of_cells", and the SPATIAL_FEATURES as one window per row of valid_cells
+        (all windows in one tip_window_stats_f64 call).  A feature is special / global / spatial only when the caller lists it so,
+        as upstream.  The other special and global features are not built here: in front of a class that has its own
+        get_frame_data (`class Tissue(TissueHipMixin, reference.Tissue)`) they go to that method, unchanged; with nothing behind
+        the mixin (the stand-alone Tissue) they raise NotImplementedError naming the feature."""
+        if feature in special_features:
+            if feature == "shape index":
+                return self.calculate_cells_shape_index(valid_cells), ""
+            if feature == "roundness":
+                return self.calculate_cells_roundness(valid_cells), ""
+            if feature == "Mean atoh intensity":
+                return self.calculate_mean_intensity(frame, valid_cells, intensity_img=intensity_img, type_name="HC"), ""
+        if feature in global_features:
+            if feature == "total_area":
+                return self.calculate_total_area(valid_cells), ""
+            if feature == "density":
+                return self.calculate_density(frame, valid_cells, reference), ""
+            if feature == "type_fraction":
+                return self.calculate_type_fraction(frame, valid_cells, reference), ""
+            if feature == "number_of_cells":
+                return valid_cells.shape[0], ""
+        if feature in special_features or feature in global_features:
+            behind = self._behind_mixin("get_frame_data")
+            if behind is None:
+                raise NotImplementedError("get_frame_data: the %s feature %r" % ("special" if feature in special_features else "global",
+                                                                                 feature))
+            return behind(frame, feature, valid_cells, special_features=special_features, global_features=global_features,
+                          spatial_features=spatial_features, for_histogram=for_histogram, reference=reference,
+                          intensity_img=intensity_img, window_radius=window_radius, types=types)
+        if feature in spatial_features:
+            data = np.zeros((valid_cells.shape[0],))
+            if data.size:
+                window_cells = self.get_valid_non_edge_cells(frame, self.get_cells_info(frame))
+                name, kind = self._split_spatial_feature(feature, "all")
+                selector = self._window_selector(kind, True)
+                qy = [float("%f" % v) for v in valid_cells["cy"].to_numpy()]
+                qx = [float("%f" % v) for v in valid_cells["cx"].to_numpy()]
+                n_in, area_in, n_sel, _ = self._window_stats(window_cells, qy, qx, self._window_r2(window_radius), selector)
+                for i in range(data.size):
+                    data[i] = self._ratio_value(name, int(n_in[i]), int(area_in[i]), int(n_sel[i]))
+            return data, ""
+        if ":" in feature:
+            shape_name, shape_feature = feature.split(":")[:2]
+            fitted = self.shape_fitting_results[frame - 1]
+            if shape_name in fitted:
+                return tuple(fitted[shape_name][shape_feature]), ""
+        return valid_cells[feature].to_numpy(), ""
+
 
 EVENTS_INFO_SPEC = {"type": "TBA", "start_frame": 0, "end_frame": 0, "start_pos_x": 0, "start_pos_y": 0, "end_pos_x": 0,
                     "end_pos_y": 0, "daughter_pos_x": 0, "daughter_pos_y": 0, "cell_id": 0, "daughter_id": 0,
@@ -1043,7 +1284,7 @@ EVENTS_INFO_SPEC = {"type": "TBA", "start_frame": 0, "end_frame": 0, "start_pos_
 class Tissue(TissueHipMixin):
     """In-memory host of the hot methods (per-frame labels / cell tables / type maps kept in lists) that reads and writes
     the reference's `.seg` archives (ti.py:3474-3524, 3616-3757), so that the unmodified GUI opens what the GPU pipeline
-    produced and vice versa.  The reference's interactive state (undo, line drawing, events editing, statistics) is out
+    produced and vice versa.  The reference's interactive state (undo, line drawing, events editing, plots) is out
     of scope."""
 
     def __init__(self, number_of_frames, data_path=None, channel_names=(), max_cell_area=10, min_cell_area=0.1,
