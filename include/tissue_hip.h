@@ -370,6 +370,9 @@ TIP_API int tip_spatial_map_f64_dev(int y, int x, int step, double r2, const dou
 TIP_API int tip_phase_correlation(const void *ref, const void *mov, int dtype, int y, int x, int upsample, int64_t *out4);
 TIP_API int tip_phase_correlation_dev(const void *ref, const void *mov, int dtype, int y, int x, int upsample,
                                       int64_t *out4_host);
+/* diagnostics (tests): the 2-D transform tip_phase_correlation runs, by itself.  in / out: host complex128 (y, x),    */
+/* interleaved re, im; inverse != 0: conjugate twiddles, no scaling (= y * x * ifft2).  Extents as tip_phase_correlation. */
+TIP_API int tip_fft2_c128(const double *in, double *out, int y, int x, int inverse);
 
 /* ---- PIV drift: skimage.registration.optical_flow_tvl1(ref, mov, attachment, tightness, num_warp, num_iter, tol) --- */
 /* (ti.py:2061-2070 track_cells_iterator(use_piv=True)); scikit-image 0.18.3, 2-D, float32, prefilter=False.           */

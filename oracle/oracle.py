@@ -695,13 +695,21 @@ def phase_cross_correlation(reference_image, moving_image, upsample_factor=1):
     """skimage.registration.phase_cross_correlation (0.18.3, space='real', no normalisation) restated with numpy.fft:
     whole-pixel peak of ifft2(F1 * conj(F2)), then the matrix-multiply upsampled DFT in a 1.5-pixel neighbourhood
     (skimage/registration/_phase_cross_correlation.py:11-76, 196-262).  Returns the shift vector only."""
+    return phase_cross_correlation_surfaces(reference_image, moving_image, upsample_factor)[0]
+
+
+def phase_cross_correlation_surfaces(reference_image, moving_image, upsample_factor=1):
+    """phase_cross_correlation with the two |cross-correlation| surfaces its argmaxes are taken over: (shifts, coarse (y, x),
+    upsampled (region, region) or None for upsample_factor 1).  Tests use the surfaces to see how far the winner is ahead."""
     a = np.asarray(reference_image, dtype=np.float64)
     b = np.asarray(moving_image, dtype=np.float64)
     src, tgt = np.fft.fft2(a), np.fft.fft2(b)
     shape = src.shape
     prod = src * tgt.conj()
     cc = np.fft.ifft2(prod)
-    maxima = np.unravel_index(np.argmax(np.abs(cc)), cc.shape)
+    coarse = np.abs(cc)
+    fine = None
+    maxima = np.unravel_index(np.argmax(coarse), cc.shape)
     mid = np.array([np.fix(s / 2) for s in shape])
     shifts = np.stack(maxima).astype(np.float64)
     shifts[shifts > mid] -= np.array(shape)[shifts > mid]
@@ -717,12 +725,13 @@ def phase_cross_correlation(reference_image, moving_image, upsample_factor=1):
             kernel = np.exp(-1j * 2 * np.pi * kernel)
             data = np.tensordot(kernel, data, axes=(1, -1))
         cc2 = data.conj()
-        mx = np.unravel_index(np.argmax(np.abs(cc2)), cc2.shape)
+        fine = np.abs(cc2)
+        mx = np.unravel_index(np.argmax(fine), cc2.shape)
         shifts = shifts + (np.stack(mx).astype(np.float64) - dftshift) / uf
     for d in range(2):
         if shape[d] == 1:
             shifts[d] = 0
-    return shifts
+    return shifts, coarse, fine
 
 
 def update_drift(previous_img, current_img):

@@ -152,7 +152,22 @@ def transpose2d_dev(in_ptr, out_ptr, rows, cols, elem_bytes):
     check(lib().tip_transpose2d_dev(dptr(in_ptr or 0), dptr(out_ptr or 0), int(rows), int(cols), int(elem_bytes)))
 
 
-WS_FLAG_TIES, WS_FLAG_TWO_VALUED, WS_FLAG_SERIAL_EXACT, WS_FLAG_SERIAL_FINISH, WS_FLAG_COUNT_SHIFT = 1, 2, 4, 8, 8
+def fft2_c128(z, inverse=False):
+    """tip_fft2_c128 (diagnostic): the 2-D transform behind the drift estimate on one host (y, x) complex128 array; inverse:
+    conjugate twiddles without scaling (y * x * ifft2).  NotImplementedError outside extents [2, 4096], like the drift entry."""
+    z = np.ascontiguousarray(z, dtype=np.complex128)
+    if z.ndim != 2:
+        raise ValueError("fft2_c128 takes a 2-D array")
+    ny, nx = z.shape
+    for n in (ny, nx):
+        if n < 2 or n > 4096:
+            raise NotImplementedError("MI355X FFT takes extents in [2, 4096] (got %dx%d)" % (ny, nx))
+    out = np.empty_like(z)
+    check(lib().tip_fft2_c128(ptr(z), ptr(out), ny, nx, 1 if inverse else 0))
+    return out
+
+
+WS_FLAG_TIES,WS_FLAG_TWO_VALUED, WS_FLAG_SERIAL_EXACT, WS_FLAG_SERIAL_FINISH, WS_FLAG_COUNT_SHIFT = 1, 2, 4, 8, 8
 
 
 def set_tuning(name, value=None):

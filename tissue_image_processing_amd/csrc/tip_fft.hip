@@ -409,4 +409,26 @@ int tip_phase_correlation(const void *ref, const void *mov, int dtype, int y, in
     return phase_correlation_dev(da, db, dtype, y, x, upsample, out4);
 }
 
+// diagnostics (tests): the plan, row and transpose kernels phase_correlation_dev runs, on one host complex128 array
+int tip_fft2_c128(const double *in, double *out, int y, int x, int inverse)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (!in || !out) return fail(TIP_ERR_ARG, "tip_fft2_c128: null pointer");
+    if (y < 2 || x < 2 || y > 4096 || x > 4096)
+        return fail(TIP_ERR_UNSUPPORTED, "tip_fft2_c128: extents must lie in [2, 4096] (got %dx%d)", y, x);
+    const long n = (long)y * x;
+    WsGuard ws;
+    cplx *A = ws.get<cplx>(n), *T = ws.get<cplx>(n);
+    if (!A || !T) return TIP_ERR_NOMEM;
+    int rc;
+    RowPlan plx, ply;
+    if ((rc = make_plan(plx, x, ws)) || (rc = make_plan(ply, y, ws))) return rc;
+    TIP_HIP(hipMemcpyAsync(A, in, n * sizeof(cplx), hipMemcpyHostToDevice, c.stream));
+    if ((rc = fft2_inplace(A, T, y, x, plx, ply, inverse ? 1 : 0, false))) return rc;
+    TIP_HIP(hipMemcpyAsync(out, A, n * sizeof(cplx), hipMemcpyDeviceToHost, c.stream));
+    TIP_HIP(hipStreamSynchronize(c.stream));
+    return TIP_OK;
+}
+
 }  // extern "C"
