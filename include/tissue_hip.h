@@ -325,6 +325,67 @@ TIP_API int tip_cell_types_i32_dev(const int32_t *labels, const double *marker, 
 /* lo) rows, counts: the pixel numbers, in no particular order.                                                        */
 TIP_API int tip_contact_pairs_i32(const int32_t *labels, int y, int x, int big, int32_t *pairs, int64_t *counts, int64_t cap,
                                   int64_t *n_pairs);
+/* The same on a DEVICE label map, the triples left in the caller's device buffers (cap rows); the number of triples comes */
+/* back to the host, so the call waits for the stream.                                                                  */
+TIP_API int tip_contact_pairs_i32_dev(const int32_t *labels, int y, int x, int big, int32_t *pairs_dev, int64_t *counts_dev,
+                                      int64_t cap, int64_t *n_pairs_host);
+
+/* ---- neighbour-graph features (ti.py:1752-1791 calculate_n_neighbors_from_type, 2513-2543 find_second_order_neighbors,   */
+/* 1065-1096 / 1844-1872 contact lengths) ------------------------------------------------------------------------------- */
+/* The graph is a CSR adjacency over the n table rows: offsets int32[n + 1], adj int32[n_adj] of 1-based labels, ASCENDING   */
+/* within a row.  Per-row bytes: valid, empty (empty_cell; NULL = no empty row), type.  query: m row indices (0-based), or   */
+/* NULL: query q is row q (m <= n).  Every entry has a host form (host arrays, checked before the upload: monotone offsets,  */
+/* labels in 1..n ascending in a row, queries below n -- TIP_ERR_ARG otherwise -- returns when the results are in place) and  */
+/* a _dev form (device arrays, asynchronous; reads are clamped to n_adj and labels outside 1..n skipped, a query outside     */
+/* 0..n-1 gives -1).  n = 0 and m = 0 are valid.                                                                            */
+#define TIP_GRAPH_ALL 0
+#define TIP_GRAPH_VALID 1
+#define TIP_GRAPH_INVALID 2
+#define TIP_GRAPH_TYPE 3
+/* The CSR that find_neighbors(only_for_labels=...) leaves in the table (ti.py:1815-1842), from the (hi, lo) rows of         */
+/* tip_neighbor_pairs_i32[_dev]: a pair gives both directions when working[hi - 1] != 0 or working is NULL (upstream visits   */
+/* the working cells and finds a pair from its larger label); a pair with a label outside 1..n takes no part.  adj has room  */
+/* for cap entries; *n_adj = the entries needed, and TIP_ERR_OVERFLOW when that exceeds cap (nothing is written to adj then). */
+/* _dev: n_adj_host NULL makes the call asynchronous -- rows that would not fit are left out, and cap = 2 n_pairs always fits. */
+TIP_API int tip_neighbor_csr_i32(const int32_t *pairs, int64_t n_pairs, int64_t n, const uint8_t *working, int32_t *offsets,
+                                 int32_t *adj, int64_t cap, int64_t *n_adj);
+TIP_API int tip_neighbor_csr_i32_dev(const int32_t *pairs, int64_t n_pairs, int64_t n, const uint8_t *working, int32_t *offsets,
+                                     int32_t *adj, int64_t cap, int64_t *n_adj_host);
+/* out[q]: mode ALL the row's degree (ti.py:1782-1783); VALID / INVALID its neighbours with valid == 1 / == 0 and empty == 0  */
+/* (ti.py:1784-1789); TYPE those with valid == 1, empty == 0 that are positive for type bit sel_bit (is_positive_for_type:    */
+/* bit set and byte != 255) when sel_positive != 0, or not positive (255 included) otherwise (ti.py:1771-1781).              */
+TIP_API int tip_graph_counts_i32(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid,
+                                 const uint8_t *empty, const uint8_t *type, const int32_t *query, int64_t m, int mode, int sel_bit,
+                                 int sel_positive, int64_t *out);
+TIP_API int tip_graph_counts_i32_dev(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid,
+                                     const uint8_t *empty, const uint8_t *type, const int32_t *query, int64_t m, int mode,
+                                     int sel_bit, int sel_positive, int64_t *out);
+/* find_second_order_neighbors: for query row i the set of k in N(j), j in N(i) with valid[j] == 1, that have valid[k] == 1,  */
+/* pass the selector (sel_bit -1: all; else type bit and polarity as above, without the empty test) and are not i itself;    */
+/* first neighbours stay in (upstream drops the result of its .difference, ti.py:2539).  sizes[q] = the set's size.  With      */
+/* members != NULL the labels of set q are written from members[member_offsets[q]] on (the caller's exclusive scan of the     */
+/* sizes; members_cap entries in all), in order of first discovery (j ascending, then k ascending).                           */
+TIP_API int tip_graph_second_i32(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid,
+                                 const uint8_t *type, const int32_t *query, int64_t m, int sel_bit, int sel_positive, int64_t *sizes,
+                                 const int64_t *member_offsets, int32_t *members, int64_t members_cap);
+TIP_API int tip_graph_second_i32_dev(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid,
+                                     const uint8_t *type, const int32_t *query, int64_t m, int sel_bit, int sel_positive,
+                                     int64_t *sizes, const int64_t *member_offsets, int32_t *members, int64_t members_cap);
+/* Contact lengths per row from the (hi, lo, pixels) triples of tip_contact_pairs_i32[_dev]: an edge of the CSR weighs its     */
+/* triple's pixels (0 without one; a triple that is no edge is ignored), sums[q] = the weights of row q's selected neighbours */
+/* and n_sel[q] their number -- mode ALL every neighbour, VALID valid == 1, TYPE the type selector alone (ti.py:1857-1866: no  */
+/* validity test there, unlike the counts).  With values != NULL the selected neighbours' weights (and labels, value_labels)  */
+/* are written from value_offsets[q] on, ascending by label (the caller's exclusive scan of n_sel; values_cap entries).        */
+TIP_API int tip_contact_sums_i32(const int32_t *pairs, const int64_t *counts, int64_t n_triples, const int32_t *offsets,
+                                 const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid, const uint8_t *type,
+                                 const int32_t *query, int64_t m, int mode, int sel_bit, int sel_positive, int64_t *sums,
+                                 int64_t *n_sel, const int64_t *value_offsets, int64_t *values, int32_t *value_labels,
+                                 int64_t values_cap);
+TIP_API int tip_contact_sums_i32_dev(const int32_t *pairs, const int64_t *counts, int64_t n_triples, const int32_t *offsets,
+                                     const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid, const uint8_t *type,
+                                     const int32_t *query, int64_t m, int mode, int sel_bit, int sel_positive, int64_t *sums,
+                                     int64_t *n_sel, const int64_t *value_offsets, int64_t *values, int32_t *value_labels,
+                                     int64_t values_cap);
 /* Tissue.update_labels (ti.py:2967-2970): negatives take the zero-padded 3x3 maximum              */
 TIP_API int tip_update_labels_i32(int32_t *labels, int y, int x);
 /* track_cells_iterator's label lookup (ti.py:2081-2090): maximum_filter(labels,(3,3),'constant') sampled at query   */

@@ -173,24 +173,8 @@ def neighbor_pairs(labels, cap=None):
 def contact_pairs(labels, cap=None):
     """{(hi, lo): pixels} for the contact-length rule of ti.py:1844-1872: pixels whose cross-footprint maximum of the labels
     is hi and whose cross-footprint minimum (zeros replaced by max + 1) is lo, hi > lo >= 1.  One device pass."""
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    big = int(labels.max()) + 1
-    grow = cap is None
-    if cap is None:
-        cap = max(4096, 16 * big)
-    while True:
-        pairs = np.empty((cap, 2), np.int32)
-        counts = np.empty(cap, np.int64)
-        n = ctypes.c_int64(0)
-        rc = _lib.lib().tip_contact_pairs_i32(_lib.ptr(labels), labels.shape[0], labels.shape[1], big, _lib.ptr(pairs),
-                                              _lib.ptr(counts), ctypes.c_int64(cap), ctypes.byref(n))
-        if rc == _lib.TIP_ERR_OVERFLOW and grow and cap < 8 * labels.size:
-            cap *= 8
-            continue
-        _lib.check(rc)
-        break
-    k = int(n.value)
-    return {(int(h), int(l)): int(c) for (h, l), c in zip(pairs[:k].tolist(), counts[:k].tolist())}
+    pairs, counts = contact_triples(labels, cap)
+    return {(int(h), int(l)): int(c) for (h, l), c in zip(pairs.tolist(), counts.tolist())}
 
 
 def label_order_stats(labels, img, nlab, ranks):
@@ -319,3 +303,165 @@ def window_stats_dev(qy_ptr, qx_ptr, m, r2, cy_ptr, cx_ptr, area_ptr, type_ptr, 
         _lib.dptr(cx_ptr or 0), _lib.dptr(area_ptr or 0), _lib.dptr(type_ptr or 0), _lib.dptr(feat_ptr or 0), ctypes.c_int64(n),
         int(sel_bit), 1 if sel_positive else 0, _lib.dptr(n_in_ptr or 0), _lib.dptr(area_in_ptr or 0), _lib.dptr(n_sel_ptr or 0),
         _lib.dptr(sum_sel_ptr or 0)))
+
+
+# ---- neighbour-graph features (csrc/tip_graph.hip) ------------------------------------------------------------------------------
+GRAPH_MODES = {"all": 0, "valid": 1, "invalid": 2, "type": 3}
+
+
+def contact_triples(labels, cap=None):
+    """tip_contact_pairs_i32 as arrays: ((k, 2) int32 (hi, lo) rows, (k,) int64 pixel counts), in no particular order."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    big = int(labels.max()) + 1
+    grow = cap is None
+    if cap is None:
+        cap = max(4096, 16 * big)
+    while True:
+        pairs = np.empty((cap, 2), np.int32)
+        counts = np.empty(cap, np.int64)
+        n = ctypes.c_int64(0)
+        rc = _lib.lib().tip_contact_pairs_i32(_lib.ptr(labels), labels.shape[0], labels.shape[1], big, _lib.ptr(pairs),
+                                              _lib.ptr(counts), ctypes.c_int64(cap), ctypes.byref(n))
+        if rc == _lib.TIP_ERR_OVERFLOW and grow and cap < 8 * labels.size:
+            cap *= 8
+            continue
+        _lib.check(rc)
+        break
+    return pairs[:n.value].copy(), counts[:n.value].copy()
+
+
+def contact_pairs_dev(labels_ptr, y, x, big, pairs_ptr, counts_ptr, cap):
+    """tip_contact_pairs_i32_dev: the triples of a DEVICE label map left in device buffers of `cap` rows; returns their number
+    (the call waits for the stream)."""
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.lib().tip_contact_pairs_i32_dev(_lib.dptr(labels_ptr), int(y), int(x), int(big), _lib.dptr(pairs_ptr),
+                                                    _lib.dptr(counts_ptr), ctypes.c_int64(cap), ctypes.byref(n)))
+    return int(n.value)
+
+
+def _bytes_column(a, n, name):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+    if a.size != n:
+        raise ValueError("%s has %d entries for %d rows" % (name, a.size, n))
+    return a
+
+
+def _graph_args(offsets, adj, valid, empty, type, query):
+    """the CSR, the per-row bytes and the query rows as the C-ABI takes them; query None: every row"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+    adj = np.ascontiguousarray(adj, dtype=np.int32).reshape(-1)
+    if offsets.size < 1:
+        raise ValueError("offsets needs n + 1 entries")
+    n = offsets.size - 1
+    valid, empty, type = (_bytes_column(a, n, name) for a, name in ((valid, "valid"), (empty, "empty"), (type, "type")))
+    query = None if query is None else np.ascontiguousarray(query, dtype=np.int32).reshape(-1)
+    m = n if query is None else query.size
+    return offsets, adj, n, valid, empty, type, query, m
+
+
+def _selector(mode, sel_bit):
+    return GRAPH_MODES[mode] if isinstance(mode, str) else int(mode), -1 if sel_bit is None else int(sel_bit)
+
+
+def neighbor_csr(pairs, n, working=None, cap=None):
+    """tip_neighbor_csr_i32: (offsets int32[n + 1], adj int32[...]) from (hi, lo) pair rows; working: one byte per row or None."""
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    working = _bytes_column(working, int(n), "working")
+    cap = 2 * pairs.shape[0] if cap is None else int(cap)
+    offsets = np.zeros(int(n) + 1, np.int32)
+    adj = np.zeros(cap, np.int32)
+    n_adj = ctypes.c_int64(0)
+    _lib.check(_lib.lib().tip_neighbor_csr_i32(_lib.ptr(pairs), ctypes.c_int64(pairs.shape[0]), ctypes.c_int64(n), _lib.ptr(working),
+                                               _lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(cap), ctypes.byref(n_adj)))
+    return offsets, adj[:n_adj.value].copy()
+
+
+def neighbor_csr_dev(pairs_ptr, n_pairs, n, working_ptr, offsets_ptr, adj_ptr, cap, want_count=False):
+    """tip_neighbor_csr_i32_dev on device addresses; asynchronous unless want_count (then the entry count comes back)."""
+    n_adj = ctypes.c_int64(0)
+    _lib.check(_lib.lib().tip_neighbor_csr_i32_dev(_lib.dptr(pairs_ptr or 0), ctypes.c_int64(n_pairs), ctypes.c_int64(n),
+                                                   _lib.dptr(working_ptr or 0), _lib.dptr(offsets_ptr or 0), _lib.dptr(adj_ptr or 0),
+                                                   ctypes.c_int64(cap), ctypes.byref(n_adj) if want_count else None))
+    return int(n_adj.value) if want_count else None
+
+
+def graph_counts(offsets, adj, valid, empty, type, query=None, mode="all", sel_bit=None, sel_positive=True):
+    """tip_graph_counts_i32: one int64 count per query row (mode "all" / "valid" / "invalid" / "type")."""
+    offsets, adj, n, valid, empty, type, query, m = _graph_args(offsets, adj, valid, empty, type, query)
+    mode, bit = _selector(mode, sel_bit)
+    out = np.zeros(m, np.int64)
+    _lib.check(_lib.lib().tip_graph_counts_i32(
+        _lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(n), ctypes.c_int64(adj.size), _lib.ptr(valid), _lib.ptr(empty), _lib.ptr(type),
+        _lib.ptr(query), ctypes.c_int64(m), mode, bit, 1 if sel_positive else 0, _lib.ptr(out)))
+    return out
+
+
+def graph_counts_dev(offsets_ptr, adj_ptr, n, n_adj, valid_ptr, empty_ptr, type_ptr, query_ptr, m, mode, sel_bit, sel_positive, out_ptr):
+    mode, bit = _selector(mode, sel_bit)
+    _lib.check(_lib.lib().tip_graph_counts_i32_dev(
+        _lib.dptr(offsets_ptr or 0), _lib.dptr(adj_ptr or 0), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr or 0),
+        _lib.dptr(empty_ptr or 0), _lib.dptr(type_ptr or 0), _lib.dptr(query_ptr or 0), ctypes.c_int64(m), mode, bit,
+        1 if sel_positive else 0, _lib.dptr(out_ptr or 0)))
+
+
+def graph_second(offsets, adj, valid, type, query=None, sel_bit=None, sel_positive=True, members=True):
+    """tip_graph_second_i32: (sizes int64[m], member_offsets int64[m + 1], members int32[...]) of find_second_order_neighbors;
+    members=False: the sizes alone."""
+    offsets, adj, n, valid, _, type, query, m = _graph_args(offsets, adj, valid, None, type, query)
+    bit = -1 if sel_bit is None else int(sel_bit)
+    sizes = np.zeros(m, np.int64)
+    head = (_lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(n), ctypes.c_int64(adj.size), _lib.ptr(valid), _lib.ptr(type), _lib.ptr(query),
+            ctypes.c_int64(m), bit, 1 if sel_positive else 0)
+    _lib.check(_lib.lib().tip_graph_second_i32(*head, _lib.ptr(sizes), None, None, ctypes.c_int64(0)))
+    if not members:
+        return sizes
+    moff = np.zeros(m + 1, np.int64)
+    moff[1:] = np.cumsum(sizes)
+    mem = np.zeros(int(moff[-1]), np.int32)
+    if mem.size:
+        _lib.check(_lib.lib().tip_graph_second_i32(*head, None, _lib.ptr(moff), _lib.ptr(mem), ctypes.c_int64(mem.size)))
+    return sizes, moff, mem
+
+
+def graph_second_dev(offsets_ptr, adj_ptr, n, n_adj, valid_ptr, type_ptr, query_ptr, m, sel_bit, sel_positive, sizes_ptr,
+                     member_offsets_ptr=None, members_ptr=None, members_cap=0):
+    _lib.check(_lib.lib().tip_graph_second_i32_dev(
+        _lib.dptr(offsets_ptr or 0), _lib.dptr(adj_ptr or 0), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr or 0),
+        _lib.dptr(type_ptr or 0), _lib.dptr(query_ptr or 0), ctypes.c_int64(m), -1 if sel_bit is None else int(sel_bit),
+        1 if sel_positive else 0, _lib.dptr(sizes_ptr or 0), _lib.dptr(member_offsets_ptr or 0), _lib.dptr(members_ptr or 0),
+        ctypes.c_int64(members_cap)))
+
+
+def contact_sums(pairs, counts, offsets, adj, valid, type, query=None, mode="all", sel_bit=None, sel_positive=True, values=False):
+    """tip_contact_sums_i32: sums int64[m] of the contact pixels towards the selected neighbours; values=True: (sums,
+    value_offsets int64[m + 1], value_labels int32[...], values int64[...]), the selected neighbours ascending by label."""
+    offsets, adj, n, valid, _, type, query, m = _graph_args(offsets, adj, valid, None, type, query)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if counts.size != pairs.shape[0]:
+        raise ValueError("%d pairs with %d counts" % (pairs.shape[0], counts.size))
+    mode, bit = _selector(mode, sel_bit)
+    sums, n_sel = np.zeros(m, np.int64), np.zeros(m, np.int64)
+    head = (_lib.ptr(pairs), _lib.ptr(counts), ctypes.c_int64(counts.size), _lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(n),
+            ctypes.c_int64(adj.size), _lib.ptr(valid), _lib.ptr(type), _lib.ptr(query), ctypes.c_int64(m), mode, bit, 1 if sel_positive else 0)
+    _lib.check(_lib.lib().tip_contact_sums_i32(*head, _lib.ptr(sums), _lib.ptr(n_sel), None, None, None, ctypes.c_int64(0)))
+    if not values:
+        return sums
+    voff = np.zeros(m + 1, np.int64)
+    voff[1:] = np.cumsum(n_sel)
+    val, lab = np.zeros(int(voff[-1]), np.int64), np.zeros(int(voff[-1]), np.int32)
+    if val.size:
+        _lib.check(_lib.lib().tip_contact_sums_i32(*head, None, None, _lib.ptr(voff), _lib.ptr(val), _lib.ptr(lab), ctypes.c_int64(val.size)))
+    return sums, voff, lab, val
+
+
+def contact_sums_dev(pairs_ptr, counts_ptr, n_triples, offsets_ptr, adj_ptr, n, n_adj, valid_ptr, type_ptr, query_ptr, m, mode, sel_bit,
+                     sel_positive, sums_ptr, n_sel_ptr=None, value_offsets_ptr=None, values_ptr=None, value_labels_ptr=None, values_cap=0):
+    mode, bit = _selector(mode, sel_bit)
+    _lib.check(_lib.lib().tip_contact_sums_i32_dev(
+        _lib.dptr(pairs_ptr or 0), _lib.dptr(counts_ptr or 0), ctypes.c_int64(n_triples), _lib.dptr(offsets_ptr or 0), _lib.dptr(adj_ptr or 0),
+        ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr or 0), _lib.dptr(type_ptr or 0), _lib.dptr(query_ptr or 0),
+        ctypes.c_int64(m), mode, bit, 1 if sel_positive else 0, _lib.dptr(sums_ptr or 0), _lib.dptr(n_sel_ptr or 0),
+        _lib.dptr(value_offsets_ptr or 0), _lib.dptr(values_ptr or 0), _lib.dptr(value_labels_ptr or 0), ctypes.c_int64(values_cap)))

@@ -478,6 +478,12 @@ int tip_neighbor_pairs_i32(const int32_t *labels, int y, int x, int32_t *pairs, 
     return TIP_OK;
 }
 
+int tip_contact_pairs_i32_dev(const int32_t *labels, int y, int x, int big, int32_t *pairs_dev, int64_t *counts_dev, int64_t cap,
+                              int64_t *n_pairs_host)
+{
+    return contact_pairs_dev(labels, y, x, big, pairs_dev, counts_dev, cap, n_pairs_host);
+}
+
 int tip_contact_pairs_i32(const int32_t *labels, int y, int x, int big, int32_t *pairs, int64_t *counts, int64_t cap, int64_t *n_pairs)
 {
     Ctx &c = ctx();

@@ -20,20 +20,12 @@
 //                    point exists (s/2 + k s < extent); every other pixel is 0.  An odd s leaves one-pixel seams, s = 1 an empty
 //                    map, and the frame clips the last block, as upstream.
 #include "tip_internal.h"
+#include "tip_typesel.h"   // sp_selected: the type selector, shared with tip_graph.hip
 
 namespace tip {
 
 constexpr int SP_TILE = 128, SP_CHUNK = 512;
 constexpr int SP_DENSITY = 0, SP_TYPE_FRACTION = 1, SP_MEAN = 2;
-
-// is_positive_for_type (ti.py:146-176) on one type byte: the bit is set and the byte is not the invalid marker 255; sel_kind
-// 0 = no selector, 1 = positive, 2 = not positive (the negation takes invalid bytes, as upstream's ~ does)
-__device__ __forceinline__ bool sp_selected(uint8_t t, int sel_kind, int bit)
-{
-    if (sel_kind == 0) return true;
-    const bool pos = ((t >> bit) & 1) && t != 255;
-    return sel_kind == 1 ? pos : !pos;
-}
 
 __global__ __launch_bounds__(SP_TILE) void k_window_stats(const double *__restrict__ qy, const double *__restrict__ qx, long M,
                                                           int grid_x, int step, double r2, const double *__restrict__ cy,

@@ -123,7 +123,7 @@ class GpuFrameBackend(object):
     SEGMENTATIONS = ("classical", "unet")
 
     def __init__(self, C, Z, Y, X, device=None, keep_planes=False, inflight=1, cell_types=None, segmentation="classical",
-                 unet_weights=None, unet_channels=(1, 0), predictor_factory=None, keep_hc=False, **kw):
+                 unet_weights=None, unet_channels=(1, 0), predictor_factory=None, keep_hc=False, neighbor_features=False, **kw):
         from .pipeline import FramePipeline
         from . import _lib
         # segmentation: "classical" (FramePipeline.segment: threshold, blur, watershed on channel 0) or "unet", the GUI's "use
@@ -156,6 +156,14 @@ class GpuFrameBackend(object):
         if unknown:
             raise ValueError("cell_types: unknown option(s) %s (known: %s)" % (sorted(unknown), ", ".join(self.CELL_TYPE_OPTIONS)))
         self.extra_columns = self.CELL_TYPE_COLUMNS if cell_types is not None else ()
+        # neighbor_features: every frame's dict also gains the neighbour-graph columns of FramePipeline.neighbor_features (int64
+        # per row), computed after the frame's type call; the hc_* / sc_* columns only together with cell_types.  Without
+        # cell_types a row is valid as calculate_frame_cellinfo has it: its area strictly between 0.1 and 10 mean areas.
+        self.neighbor_features = bool(neighbor_features)
+        if self.neighbor_features:
+            from .pipeline import FramePipeline as _FP
+            names = _FP.NEIGHBOR_COLUMNS + (_FP.TYPED_NEIGHBOR_COLUMNS if cell_types is not None else ())
+            self.extra_columns = tuple(self.extra_columns) + tuple((name, np.int64) for name in names)
         self.device = device
         self.pipe = FramePipeline(C, Z, Y, X, device=device, **kw)
         if device is None:
@@ -273,6 +281,13 @@ class GpuFrameBackend(object):
             tmap = _lib.DeviceBuffer(self.Y * self.X)      # the frame's type map is painted straight into its own buffer
             out.update(p.cell_types(n=tab["area"].size, type_map_ptr=tmap.ptr, **self.cell_types))   # (synchronises)
             self.type_maps[t] = tmap
+        if self.neighbor_features:
+            n = tab["area"].size
+            if self.cell_types is not None:
+                out.update(p.neighbor_features(n, out["valid"], out["type"], type_index=self.cell_types.get("type_index", 0)))
+            else:
+                mean = tab["area"].mean() if n else 0.0
+                out.update(p.neighbor_features(n, (tab["area"] > 0.1 * mean) & (tab["area"] < 10 * mean)))
         return out
 
     def fetch_cell_types(self, t):

@@ -176,6 +176,63 @@ class FramePipeline:
         blob = self._ct[1].download((10 * n,), np.uint8)
         return dict(type=blob[8 * n:9 * n].copy(), valid=blob[9 * n:].copy(), mean_intensity=blob[:8 * n].view(np.float64))
 
+    NEIGHBOR_COLUMNS = ("n_neighbors", "valid_neighbors", "second_neighbors", "contact_length")
+    TYPED_NEIGHBOR_COLUMNS = ("hc_neighbors", "sc_neighbors", "hc_second_neighbors", "sc_second_neighbors", "hc_contact_length",
+                              "sc_contact_length")
+
+    def neighbor_features(self, n, valid, type=None, type_index=0):
+        """The neighbour-graph columns of the n table rows (csrc/tip_graph.hip) on the resident label map and the pair list that
+        cell_tables() left on the device: CSR with working = the valid rows (the table calculate_frame_cellinfo builds), contact
+        triples, then per row the degree, the valid neighbours, the size of find_second_order_neighbors' set and the summed
+        contact length -- and, with the rows' type bytes, the same four restricted to neighbours positive (hc_*) / not positive
+        (sc_*) for bit `type_index` (the two typed second-neighbour columns are the set sizes, not upstream's all-zero column).
+        valid / type: host uint8 arrays of n rows.  Every column is int64; they come back in ONE device-to-host copy."""
+        from . import _segmentation as seg
+        n = int(n)
+        names = self.NEIGHBOR_COLUMNS + (self.TYPED_NEIGHBOR_COLUMNS if type is not None else ())
+        if n <= 0:
+            return {name: np.zeros(0, np.int64) for name in names}
+        if getattr(self, "tables", None) is None or getattr(self, "_tables", None) is None or self.tables["area"].size != n:
+            raise RuntimeError("neighbor_features(n=%d) follows cell_tables() of the same frame" % n)
+        valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
+        type = None if type is None else np.ascontiguousarray(type, dtype=np.uint8).reshape(-1)
+        if valid.size != n or (type is not None and type.size != n):
+            raise ValueError("valid / type need %d rows" % n)
+        npair = int(self.tables["pairs"].shape[0])
+        d_pairs = self._tables[1].ptr + 80 * n
+        cap_adj, cap_tri = max(2 * npair, 1), max(4096, 16 * (n + 1))
+        # ONE device block: [columns 10 n int64 | triple counts | offsets n + 1 | adj | triple pairs | valid n | type n]
+        o_cnt = 80 * n
+        o_off = o_cnt + 8 * cap_tri
+        o_adj = o_off + 4 * (n + 1)
+        o_tri = o_adj + 4 * cap_adj
+        o_valid = o_tri + 8 * cap_tri
+        o_type = o_valid + n
+        need = o_type + n
+        if getattr(self, "_nf", None) is None or self._nf.nbytes < need:
+            self._nf = _lib.DeviceBuffer(int(need * 1.5))
+        base = self._nf.ptr
+        rows = np.concatenate([valid, type if type is not None else np.zeros(n, np.uint8)])
+        _lib.check(self.lib.tip_memcpy_h2d(_lib.dptr(base + o_valid), _lib.ptr(rows), ctypes.c_size_t(2 * n)))
+        seg.neighbor_csr_dev(d_pairs, npair, n, base + o_valid, base + o_off, base + o_adj, cap_adj)
+        ntri = seg.contact_pairs_dev(self.d_labels.ptr, self.Y, self.X, n + 1, base + o_tri, base + o_cnt, cap_tri)
+        graph = (base + o_off, base + o_adj, n, cap_adj)
+        col = lambda name: base + 8 * n * names.index(name)      # noqa: E731
+        seg.graph_counts_dev(*graph, base + o_valid, None, None, None, n, "all", None, True, col("n_neighbors"))
+        seg.graph_counts_dev(*graph, base + o_valid, None, None, None, n, "valid", None, True, col("valid_neighbors"))
+        seg.graph_second_dev(*graph, base + o_valid, None, None, n, None, True, col("second_neighbors"))
+        seg.contact_sums_dev(base + o_tri, base + o_cnt, ntri, *graph, None, None, None, n, "all", None, True, col("contact_length"))
+        if type is not None:
+            for prefix, positive in (("hc", True), ("sc", False)):
+                seg.graph_counts_dev(*graph, base + o_valid, None, base + o_type, None, n, "type", type_index, positive,
+                                     col(prefix + "_neighbors"))
+                seg.graph_second_dev(*graph, base + o_valid, base + o_type, None, n, type_index, positive,
+                                     col(prefix + "_second_neighbors"))
+                seg.contact_sums_dev(base + o_tri, base + o_cnt, ntri, *graph, None, base + o_type, None, n, "type", type_index,
+                                     positive, col(prefix + "_contact_length"))
+        block = self._nf.download((len(names) * n,), np.int64)
+        return {name: block[i * n:(i + 1) * n] for i, name in enumerate(names)}
+
     def fetch_cell_types(self):
         return self.d_types.download((self.Y, self.X), np.uint8)
 

@@ -14,6 +14,9 @@ reference's state / cache / persistence code (ti.py:193-353, 3462-3823) stays th
     get_trackking_labels(frame)                            ti.py:4021-4028 -> tip_lut_gather_i32
     calculate_spatial_data(...), get_frame_data(...),      ti.py:1035-1134, 1194-1266 -> tip_spatial_map_f64, tip_window_stats_f64
     calculate_data_around_a_given_point / _cell
+    calculate_n_neighbors_from_type / _by_type,            ti.py:1752-1799, 2513-2543, 1844-1872, 1065-1096 -> tip_graph_counts_i32,
+    find_second_order_neighbors, calculate_contact_length,     tip_graph_second_i32, tip_contact_pairs_i32 + tip_contact_sums_i32
+    calculate_contact_lengths
 """
 import ctypes
 
@@ -1223,6 +1226,114 @@ class TissueHipMixin(object):
         if mode == "mean" and (n_sel == 0).any():
             return None, "No matching cells"
         return out, ""
+
+    # ---- neighbour-graph columns (csrc/tip_graph.hip) -----------------------------------------------------------------------
+    # The methods below carry upstream's names and signatures, so in front of the reference's class upstream's own
+    # get_frame_data reaches them (`self.calculate_n_neighbors_from_type(...)`); this mixin's get_frame_data does not route
+    # to them.  Rows of `cells` are looked up in the frame's table by index (row = label - 1), and it is the table's
+    # `neighbors` sets that are walked.
+    @staticmethod
+    def _graph_of(table):
+        """the table's neighbour sets as CSR (offsets, adj ascending in a row) and its valid / empty_cell / type bytes"""
+        rows = [sorted(int(v) for v in s) for s in table["neighbors"]]
+        offsets = np.zeros(len(rows) + 1, np.int32)
+        if rows:
+            offsets[1:] = np.cumsum([len(r) for r in rows])
+        adj = np.fromiter((v for r in rows for v in r), dtype=np.int32, count=int(offsets[-1]))
+        as_bytes = lambda name: table[name].to_numpy().astype(np.uint8)      # noqa: E731
+        return offsets, adj, as_bytes("valid"), as_bytes("empty_cell"), as_bytes("type")
+
+    @staticmethod
+    def _query_rows(cells):
+        return np.asarray(cells.index.to_numpy(), dtype=np.int32)
+
+    def calculate_n_neighbors_from_type(self, frame, cells, cell_type='same', positive_for_type=True, second_neighbors=False):
+        """ti.py:1752-1791: per row of `cells` the number of its neighbours -- 'all': the degree; 'valid' / 'invalid': those with
+        valid == 1 / 0 that are no empty cell; a type name: the valid, non-empty ones (not) positive for it.  With
+        second_neighbors, 'all' counts find_second_order_neighbors' sets and a type name gives zeros (no branch of upstream's
+        loop fires).  One device call.  Upstream's failures are kept as exceptions: 'same' hands type_name_to_index an integer
+        (TypeError), second neighbours of 'valid' / 'invalid' index the table with a scalar False (KeyError)."""
+        table = self.get_cells_info(frame)
+        if table is None:
+            return None
+        if cells.shape[0] == 0:
+            return np.zeros((0,)).astype(int)
+        if cell_type == 'same':
+            raise TypeError("calculate_n_neighbors_from_type(cell_type='same'): upstream looks up the row's type BYTE as a type name")
+        offsets, adj, valid, empty, type = self._graph_of(table)
+        query = self._query_rows(cells)
+        if second_neighbors:
+            if cell_type == 'all':
+                return seg.graph_second(offsets, adj, valid, type, query, members=False).astype(int)
+            self._window_selector(cell_type, positive_for_type)           # 'valid' / 'invalid' / an unknown name: KeyError
+            return np.zeros((cells.shape[0],)).astype(int)
+        if cell_type in ('all', 'valid', 'invalid'):
+            return seg.graph_counts(offsets, adj, valid, empty, type, query, mode=cell_type).astype(int)
+        bit, positive = self._window_selector(cell_type, positive_for_type)
+        return seg.graph_counts(offsets, adj, valid, empty, type, query, mode="type", sel_bit=bit, sel_positive=positive).astype(int)
+
+    def calculate_n_neighbors_by_type(self, frame, cells, type_list):
+        """ti.py:1793-1799: one column of calculate_n_neighbors_from_type per type name.  type_list None is upstream's
+        get_cell_type_names(): pos / neg type lists ("('HC-pos', 'X-neg')", ...), which the device selector does not take --
+        NotImplementedError, from here when the host class has no such list, else from the first of its names."""
+        if type_list is None:
+            if not hasattr(self, "get_cell_type_names"):
+                raise NotImplementedError("calculate_n_neighbors_by_type(type_list=None): upstream's default is a list of pos / neg "
+                                          "type lists")
+            type_list = self.get_cell_type_names()
+        return pd.DataFrame({name: self.calculate_n_neighbors_from_type(frame, cells, name) for name in type_list})
+
+    def find_second_order_neighbors(self, frame, cells=None, cell_type='all', positive_for_type=True):
+        """ti.py:2513-2543: per row of `cells` (None: the valid rows) the set of valid (and, with a type name, selected)
+        neighbours of its valid neighbours, without the row itself; first neighbours stay in, as upstream.  Two device calls
+        (sizes, then members)."""
+        table = self.get_cells_info(frame)
+        if table is None:
+            return None
+        if cells is None:
+            cells = table[table["valid"].to_numpy() == 1]
+        if cells.shape[0] == 0:
+            return []
+        bit, positive = (None, True) if cell_type == 'all' else self._window_selector(cell_type, positive_for_type)
+        offsets, adj, valid, _, type = self._graph_of(table)
+        _, moff, members = seg.graph_second(offsets, adj, valid, type, self._query_rows(cells), sel_bit=bit, sel_positive=positive)
+        return [set(members[moff[q]:moff[q + 1]].tolist()) for q in range(cells.shape[0])]
+
+    def _contact_values(self, frame, query, cell_type, positive_for_type, values):
+        table = self.get_cells_info(frame)
+        offsets, adj, valid, _, type = self._graph_of(table)
+        mode, bit, positive = "all", None, True
+        if cell_type == 'valid':
+            mode = "valid"
+        elif cell_type != 'all':
+            mode = "type"
+            bit, positive = self._window_selector(cell_type, positive_for_type)
+        pairs, counts = seg.contact_triples(self.get_labels(frame))
+        return seg.contact_sums(pairs, counts, offsets, adj, valid, type, query, mode=mode, sel_bit=bit, sel_positive=positive,
+                                values=values)
+
+    def calculate_contact_length(self, frame, cell_info, max_filtered_labels, min_filtered_labels, cell_type='all',
+                                 positive_for_type=True):
+        """ti.py:1844-1872 for one table row: (labels of the selected neighbours, pixels of the contact with each) -- 'all', 'valid'
+        (valid == 1) or a type name (no validity test, as upstream).  The two filtered images are accepted and ignored: the
+        per-pair pixel counts come from the label map in one device pass.  Neighbours come ascending by label (upstream: set
+        iteration order)."""
+        table = self.get_cells_info(frame)
+        rows = np.flatnonzero((table["label"].to_numpy() == int(cell_info.label)) & (table["empty_cell"].to_numpy() == 0))
+        if rows.size == 0:
+            raise ValueError("calculate_contact_length: no non-empty row with label %d in frame %d" % (int(cell_info.label), frame))
+        query = np.asarray(table.index.to_numpy()[rows[:1]], dtype=np.int32)
+        _, _, labels, values = self._contact_values(frame, query, cell_type, positive_for_type, True)
+        return labels.astype(np.int64), list(values)
+
+    def calculate_contact_lengths(self, frame, cells, cell_type='all', positive_for_type=True, for_histogram=False):
+        """The contact-length loop of upstream's get_frame_data (ti.py:1065-1096) for all rows of `cells` at once: per row the sum of
+        its contacts with the selected neighbours, or with for_histogram every single contact, row after row (inside a row
+        ascending by neighbour label)."""
+        if cells.shape[0] == 0:
+            return np.empty((0,))
+        res = self._contact_values(frame, self._query_rows(cells), cell_type, positive_for_type, bool(for_histogram))
+        return res[3].astype(np.float64) if for_histogram else res.astype(np.float64)
 
     def get_frame_data(self, frame, feature, valid_cells, special_features=[], global_features=[], spatial_features=[],
                        for_histogram=False, reference=None, intensity_img=None, window_radius=0, types=None):
