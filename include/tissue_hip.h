@@ -386,6 +386,41 @@ TIP_API int tip_contact_sums_i32_dev(const int32_t *pairs, const int64_t *counts
                                      const int32_t *query, int64_t m, int mode, int sel_bit, int sel_positive, int64_t *sums,
                                      int64_t *n_sel, const int64_t *value_offsets, int64_t *values, int32_t *value_labels,
                                      int64_t values_cap);
+/* ---- hexatic order and neighbour correlations (ti.py:2545-2583, 803-843; csrc/tip_order.hip) -------------------------------- */
+/* The Delaunay neighbours of n planar points (py, px float64), what scipy.spatial.Voronoi(...).ridge_points pairs up in             */
+/* find_nearest_neighbors_using_voroni_tesselation.  Rule: (i, j) is an edge iff the interval of circle centres m + t d (m the      */
+/* midpoint, d the perpendicular of p_j - p_i) that no third point enters is non-empty, lo < hi STRICTLY (cocircular quadruples     */
+/* keep neither diagonal), and no collinear point lies strictly between the two; float64, explicitly rounded operations on           */
+/* coordinates relative to p_i.  Two calls, as tip_graph_second_i32: sizes[i] (int64[n], the degree) with members    */
+/* NULL; then, after the caller's exclusive scan of the sizes into member_offsets (int64[n]), members (int32, capacity members_cap)  */
+/* = the neighbours' 0-based point positions, ascending within a row.  No degree cap.  n < 2: empty rows.  All points collinear:     */
+/* the chain of consecutive points (Qhull raises there).  The host form rejects a non-finite coordinate (TIP_ERR_ARG); in the _dev  */
+/* form such a point takes no part and has an empty row.  Coincident points are the caller's to exclude: their rows are             */
+/* unspecified (Qhull drops the later twin), though every access stays inside the arrays.                                          */
+TIP_API int tip_delaunay_neighbors_f64(const double *py, const double *px, int64_t n, int64_t *sizes, const int64_t *member_offsets,
+                                       int32_t *members, int64_t members_cap);
+TIP_API int tip_delaunay_neighbors_f64_dev(const double *py, const double *px, int64_t n, int64_t *sizes,
+                                           const int64_t *member_offsets, int32_t *members, int64_t members_cap);
+/* Tissue.calc_psin (ti.py:2563-2583): per query row q (table row query[q]; query NULL: row q) psi_n over its members               */
+/* members[member_offsets[q] .. member_offsets[q + 1]) -- 1-BASED labels looked up in the whole table's cy, cx (n rows) --:          */
+/* hypot(sum cos(n theta), sum sin(n theta)) / count, theta = atan2(cy[k] - cy[r], cx[k] - cx[r]), summed in the order given         */
+/* (ascending labels from the wrappers); 0 for an empty row.  order in 1..64.  member_offsets has m + 1 entries.                     */
+TIP_API int tip_psin_f64(const double *cy, const double *cx, int64_t n, const int32_t *query, int64_t m, const int64_t *member_offsets,
+                         const int32_t *members, int64_t n_members, int order, double *out);
+TIP_API int tip_psin_f64_dev(const double *cy, const double *cx, int64_t n, const int32_t *query, int64_t m,
+                             const int64_t *member_offsets, const int32_t *members, int64_t n_members, int order, double *out);
+/* The row loops of calculate_neighbors_correlation_function (ti.py:816-838) on the CSR above: per query row q, over its neighbours  */
+/* j with member[j - 1] != 0 (upstream's `neighbor_index - 1 in valid_cells.index`), nb_sum[q] = the sum of state[j - 1] in row      */
+/* order (float64 additions) and nb_cnt[q] = their number.  member: uint8[n], state: float64[n].                                   */
+TIP_API int tip_graph_neighbor_state_f64(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *member,
+                                         const double *state, const int32_t *query, int64_t m, double *nb_sum, int64_t *nb_cnt);
+TIP_API int tip_graph_neighbor_state_f64_dev(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj,
+                                             const uint8_t *member, const double *state, const int32_t *query, int64_t m,
+                                             double *nb_sum, int64_t *nb_cnt);
+/* The two above chained on DEVICE arrays for the movie driver (FramePipeline.order_features): degree[i] = the number of Delaunay    */
+/* neighbours of point i and psi[i] = psi_order over them; sizes, scan, members and psi stay on the device.  Waits for the stream   */
+/* once, to size the member list (4 bytes come back); psi and degree are then written asynchronously, like every _dev entry.        */
+TIP_API int tip_order_features_f64_dev(const double *py, const double *px, int64_t n, int order, double *psi, int64_t *degree);
 /* Tissue.update_labels (ti.py:2967-2970): negatives take the zero-padded 3x3 maximum              */
 TIP_API int tip_update_labels_i32(int32_t *labels, int y, int x);
 /* track_cells_iterator's label lookup (ti.py:2081-2090): maximum_filter(labels,(3,3),'constant') sampled at query   */

@@ -465,3 +465,90 @@ def contact_sums_dev(pairs_ptr, counts_ptr, n_triples, offsets_ptr, adj_ptr, n, 
         ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr or 0), _lib.dptr(type_ptr or 0), _lib.dptr(query_ptr or 0),
         ctypes.c_int64(m), mode, bit, 1 if sel_positive else 0, _lib.dptr(sums_ptr or 0), _lib.dptr(n_sel_ptr or 0),
         _lib.dptr(value_offsets_ptr or 0), _lib.dptr(values_ptr or 0), _lib.dptr(value_labels_ptr or 0), ctypes.c_int64(values_cap)))
+
+
+# ---- hexatic order and neighbour correlations (csrc/tip_order.hip) ----------------------------------------------------------------
+def _points(py, px):
+    py = np.ascontiguousarray(py, dtype=np.float64).reshape(-1)
+    px = np.ascontiguousarray(px, dtype=np.float64).reshape(-1)
+    if py.size != px.size:
+        raise ValueError("py and px differ in length")
+    return py, px
+
+
+def delaunay_neighbors(py, px, members=True):
+    """tip_delaunay_neighbors_f64: (sizes int64[n], member_offsets int64[n + 1], members int32[...]) -- per point the 0-based
+    positions of its Delaunay neighbours, ascending; members=False: the sizes alone.  ValueError for a non-finite coordinate and
+    for two points with the same coordinates (scipy's Qhull silently drops the later twin)."""
+    py, px = _points(py, px)
+    n = py.size
+    if n > 1 and np.isfinite(py).all() and np.isfinite(px).all() and np.unique(np.stack([py, px], axis=1), axis=0).shape[0] != n:
+        raise ValueError("delaunay_neighbors: two points have the same coordinates")
+    sizes = np.zeros(n, np.int64)
+    head = (_lib.ptr(py), _lib.ptr(px), ctypes.c_int64(n))
+    _lib.check(_lib.lib().tip_delaunay_neighbors_f64(*head, _lib.ptr(sizes), None, None, ctypes.c_int64(0)))
+    if not members:
+        return sizes
+    moff = np.zeros(n + 1, np.int64)
+    moff[1:] = np.cumsum(sizes)
+    mem = np.zeros(int(moff[-1]), np.int32)
+    if mem.size:
+        _lib.check(_lib.lib().tip_delaunay_neighbors_f64(*head, None, _lib.ptr(moff), _lib.ptr(mem), ctypes.c_int64(mem.size)))
+    return sizes, moff, mem
+
+
+def delaunay_neighbors_dev(py_ptr, px_ptr, n, sizes_ptr, member_offsets_ptr=None, members_ptr=None, members_cap=0):
+    """tip_delaunay_neighbors_f64_dev: device addresses, asynchronous on the calling thread's stream; no duplicate check."""
+    _lib.check(_lib.lib().tip_delaunay_neighbors_f64_dev(
+        _lib.dptr(py_ptr or 0), _lib.dptr(px_ptr or 0), ctypes.c_int64(n), _lib.dptr(sizes_ptr or 0), _lib.dptr(member_offsets_ptr or 0),
+        _lib.dptr(members_ptr or 0), ctypes.c_int64(members_cap)))
+
+
+def psin(cy, cx, member_offsets, members, query=None, order=6):
+    """tip_psin_f64: float64[m], psi_order of every query row (None: row q) over its 1-based member labels, looked up in cy, cx."""
+    cy, cx = _points(cy, cx)
+    moff = np.ascontiguousarray(member_offsets, dtype=np.int64).reshape(-1)
+    mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+    if moff.size < 1:
+        raise ValueError("member_offsets needs m + 1 entries")
+    m = moff.size - 1
+    query = None if query is None else np.ascontiguousarray(query, dtype=np.int32).reshape(-1)
+    if query is not None and query.size != m:
+        raise ValueError("%d query rows with %d member rows" % (query.size, m))
+    out = np.zeros(m, np.float64)
+    _lib.check(_lib.lib().tip_psin_f64(_lib.ptr(cy), _lib.ptr(cx), ctypes.c_int64(cy.size), _lib.ptr(query), ctypes.c_int64(m), _lib.ptr(moff),
+                                       _lib.ptr(mem), ctypes.c_int64(mem.size), int(order), _lib.ptr(out)))
+    return out
+
+
+def psin_dev(cy_ptr, cx_ptr, n, query_ptr, m, member_offsets_ptr, members_ptr, n_members, order, out_ptr):
+    _lib.check(_lib.lib().tip_psin_f64_dev(
+        _lib.dptr(cy_ptr or 0), _lib.dptr(cx_ptr or 0), ctypes.c_int64(n), _lib.dptr(query_ptr or 0), ctypes.c_int64(m),
+        _lib.dptr(member_offsets_ptr or 0), _lib.dptr(members_ptr or 0), ctypes.c_int64(n_members), int(order), _lib.dptr(out_ptr or 0)))
+
+
+def graph_neighbor_state(offsets, adj, member, state, query=None):
+    """tip_graph_neighbor_state_f64: (nb_sum float64[m], nb_cnt int64[m]) over the neighbours flagged in `member`."""
+    offsets, adj, n, member, _, _, query, m = _graph_args(offsets, adj, member, None, None, query)
+    if member is None:
+        raise ValueError("member is needed")
+    state = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
+    if state.size != n:
+        raise ValueError("state has %d entries for %d rows" % (state.size, n))
+    nb_sum, nb_cnt = np.zeros(m, np.float64), np.zeros(m, np.int64)
+    _lib.check(_lib.lib().tip_graph_neighbor_state_f64(
+        _lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(n), ctypes.c_int64(adj.size), _lib.ptr(member), _lib.ptr(state), _lib.ptr(query),
+        ctypes.c_int64(m), _lib.ptr(nb_sum), _lib.ptr(nb_cnt)))
+    return nb_sum, nb_cnt
+
+
+def graph_neighbor_state_dev(offsets_ptr, adj_ptr, n, n_adj, member_ptr, state_ptr, query_ptr, m, nb_sum_ptr, nb_cnt_ptr):
+    _lib.check(_lib.lib().tip_graph_neighbor_state_f64_dev(
+        _lib.dptr(offsets_ptr or 0), _lib.dptr(adj_ptr or 0), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(member_ptr or 0),
+        _lib.dptr(state_ptr or 0), _lib.dptr(query_ptr or 0), ctypes.c_int64(m), _lib.dptr(nb_sum_ptr or 0), _lib.dptr(nb_cnt_ptr or 0)))
+
+
+def order_features_dev(py_ptr, px_ptr, n, order, psi_ptr, degree_ptr):
+    """tip_order_features_f64_dev: Delaunay degree (int64) and psi_order (float64) of n device points, left in device buffers."""
+    _lib.check(_lib.lib().tip_order_features_f64_dev(_lib.dptr(py_ptr or 0), _lib.dptr(px_ptr or 0), ctypes.c_int64(n), int(order),
+                                                     _lib.dptr(psi_ptr or 0), _lib.dptr(degree_ptr or 0)))

@@ -99,6 +99,12 @@ __global__ __launch_bounds__(1024) void k_scan_i32(const int32_t *__restrict__ i
     if (threadIdx.x == 0) out[n] = carry;
 }
 
+int scan_i32_dev(const int32_t *in, int32_t *out, int n)
+{
+    TIP_LAUNCH("csr_scan", k_scan_i32, dim3(1), dim3(1024), 0, in, out, n);
+    return TIP_OK;
+}
+
 __global__ void k_csr_fill(const int32_t *__restrict__ pairs, long np, int n, const uint8_t *__restrict__ working,
                            const int32_t *__restrict__ offsets, int32_t *__restrict__ cursor, int32_t *__restrict__ raw, long raw_cap)
 {

@@ -115,4 +115,7 @@ constexpr int OF_F64_AS_U16 = 5;
 int optical_flow_tvl1_dev(const void *ref, const void *mov, int dtype, int y, int x, float attachment, float tightness,
                           int num_warp, int num_iter, double tol, float *flow_out, int32_t *warps_host, int cap);
 
+// tip_graph.hip: out[i] = in[0] + ... + in[i - 1] for i = 0 .. n on device arrays (out has n + 1 entries), one workgroup, asynchronous
+int scan_i32_dev(const int32_t *in, int32_t *out, int n);
+
 }  // namespace tip

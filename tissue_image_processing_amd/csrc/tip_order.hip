@@ -1,0 +1,588 @@
+// tip_order.hip -- hexatic order: the Delaunay neighbours of the cell centroids (ti.py:2545-2560,
+// find_nearest_neighbors_using_voroni_tesselation), psi_n over a list of neighbour sets (ti.py:2563-2583 calc_psin) and the two
+// per-row columns behind calculate_neighbors_correlation_function (ti.py:803-843).  DESIGN.md 5.8 has the argument.
+//
+//   k_order_grid / k_order_count / (scan_i32_dev) / k_order_fill
+//                    a uniform grid over the bounding box of the finite points, about two points per square cell of side h:
+//                    bounding box and grid shape in one workgroup, points counted into cells with atomicAdd, the exclusive scan
+//                    of tip_graph.hip, then the points (x, y, position) copied cell by cell -- the points of the cells x0 .. x1
+//                    of one grid row are one contiguous range.  A point with a non-finite coordinate takes no part.
+//   k_delaunay       one wavefront (one 64-thread workgroup) per point i.  Candidates are the points of the cells within r cells
+//                    of i's cell (r = 2, 4, 8, ...); the lanes stride over the candidates j, and for each j the interval test
+//                    runs over the candidates k:   a = p_j - p_i, b = p_k - p_i,   s = a.x b.y - a.y b.x,
+//                    t = (|b|^2 - a.b) / (2 s);   hi = min t over s > 0, lo = max t over s < 0;   s == 0 kills the pair when
+//                    |b|^2 - a.b < 0 (k strictly between the two);   (i, j) is an edge iff lo < hi.  Every operation is an
+//                    explicitly rounded one (__dsub_rn / __dmul_rn / __dadd_rn / __ddiv_rn), min and max do not depend on the
+//                    order of the k, and a lane stops early once lo >= hi -- so the decision is the one the numpy restatement
+//                    (tests/order_restate.py) takes over ALL k whenever the ring is certified:  with R the largest distance from
+//                    p_i to an end of an accepted edge's interval (the farthest vertex of the cell the candidates leave),
+//                    2 R <= r h means no point outside the ring can cut the cell.  Otherwise r doubles; an unbounded cell (a hull
+//                    point) ends with the whole grid.  A candidate list of at most O_CAP points is held in LDS; a longer one
+//                    streams from global memory, each j first against the last list that did fit (nearly every far j dies there).
+//                    The certified sweep is repeated to write the members (two-call convention: sizes, the caller's scan,
+//                    members), unsorted into a scratch row that k_row_sort ranks into ascending order.  No degree cap.
+//   k_psin           one thread per query row: hypot(sum cos(n theta), sum sin(n theta)) / count over the row's members.
+//   k_neighbor_state one thread per query row of the neighbour CSR: sum of state[j] and number of the neighbours j with member[j].
+// Every index read from memory is checked before it is used, every write is checked against its capacity.
+#include <cmath>
+#include "tip_internal.h"
+
+namespace tip {
+
+constexpr int O_CAP = 512;          // candidates held in LDS per wavefront (20 bytes each)
+constexpr double O_INF = __builtin_huge_val();
+
+struct OGrid {
+    double minx, miny, h;
+    int gx, gy;
+};
+
+__device__ __forceinline__ bool finite2(double a, double b) { return isfinite(a) && isfinite(b); }
+
+__device__ __forceinline__ int cell_coord(double v, double lo, double h, int g)
+{
+    const double c = floor(__ddiv_rn(__dsub_rn(v, lo), h));
+    if (!(c >= 0.0)) return 0;
+    return c > (double)(g - 1) ? g - 1 : (int)c;
+}
+
+__global__ __launch_bounds__(256) void k_order_grid(const double *__restrict__ py, const double *__restrict__ px, int n, int cell_cap,
+                                                    OGrid *__restrict__ g)
+{
+    __shared__ double s[4][256];
+    double x0 = O_INF, x1 = -O_INF, y0 = O_INF, y1 = -O_INF;
+    for (int p = threadIdx.x; p < n; p += 256) {
+        const double x = px[p], y = py[p];
+        if (!finite2(x, y)) continue;
+        x0 = fmin(x0, x), x1 = fmax(x1, x), y0 = fmin(y0, y), y1 = fmax(y1, y);
+    }
+    s[0][threadIdx.x] = x0, s[1][threadIdx.x] = x1, s[2][threadIdx.x] = y0, s[3][threadIdx.x] = y1;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+            s[0][threadIdx.x] = fmin(s[0][threadIdx.x], s[0][threadIdx.x + off]);
+            s[1][threadIdx.x] = fmax(s[1][threadIdx.x], s[1][threadIdx.x + off]);
+            s[2][threadIdx.x] = fmin(s[2][threadIdx.x], s[2][threadIdx.x + off]);
+            s[3][threadIdx.x] = fmax(s[3][threadIdx.x], s[3][threadIdx.x + off]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    x0 = s[0][0], x1 = s[1][0], y0 = s[2][0], y1 = s[3][0];
+    if (!(x0 <= x1)) x0 = x1 = y0 = y1 = 0.0;      // no finite point
+    const double W = x1 - x0, H = y1 - y0, target = n / 2 > 1 ? (double)(n / 2) : 1.0;
+    double h = W > 0.0 && H > 0.0 ? sqrt(W / target * H) : (W > 0.0 || H > 0.0 ? fmax(W, H) / target : 1.0);
+    if (!(h > 0.0) || !isfinite(h)) h = 1.0;
+    double fx = 1.0, fy = 1.0;
+    bool ok = false;
+    for (int it = 0; it < 2200 && !ok; ++it) {     // (a thin box: cells of side h would outnumber the points; h doubles)
+        fx = floor(W / h) + 1.0, fy = floor(H / h) + 1.0;
+        ok = fx * fy <= (double)cell_cap;
+        if (!ok) h *= 2.0;
+    }
+    if (!ok) fx = fy = 1.0, h = O_INF;
+    g->minx = x0, g->miny = y0, g->h = h, g->gx = (int)fx, g->gy = (int)fy;
+}
+
+__global__ void k_order_count(const double *__restrict__ py, const double *__restrict__ px, int n, const OGrid *__restrict__ gp,
+                              int cell_cap, int32_t *__restrict__ cell_of, int32_t *__restrict__ cnt)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const OGrid g = *gp;
+    const double x = px[p], y = py[p];
+    int c = -1;
+    if (finite2(x, y)) c = cell_coord(y, g.miny, g.h, g.gy) * g.gx + cell_coord(x, g.minx, g.h, g.gx);
+    if (c >= cell_cap) c = -1;
+    cell_of[p] = c;
+    if (c >= 0) atomicAdd(&cnt[c], 1);
+}
+
+__global__ void k_order_fill(const double *__restrict__ py, const double *__restrict__ px, int n, const int32_t *__restrict__ cell_of,
+                             const int32_t *__restrict__ start, int32_t *__restrict__ cursor, double *__restrict__ sx,
+                             double *__restrict__ sy, int32_t *__restrict__ sidx)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int c = cell_of[p];
+    if (c < 0) return;
+    const long pos = (long)start[c] + atomicAdd(&cursor[c], 1);
+    if (pos < 0 || pos >= n) return;
+    sx[pos] = px[p], sy[pos] = py[p], sidx[pos] = p;
+}
+
+// the interval of pair (i, j), a = p_j - p_i, cut by one point b = p_k - p_i.  k = i (b = 0) and k = j (b = a) give s = 0 and
+// |b|^2 - a.b = 0 exactly and cut nothing, so the callers do not single them out.
+__device__ __forceinline__ void cut(double ax, double ay, double bx, double by, bool &alive, double &lo, double &hi)
+{
+    const double s = __dsub_rn(__dmul_rn(ax, by), __dmul_rn(ay, bx));
+    const double num = __dsub_rn(__dadd_rn(__dmul_rn(bx, bx), __dmul_rn(by, by)), __dadd_rn(__dmul_rn(ax, bx), __dmul_rn(ay, by)));
+    if (s == 0.0) {
+        if (num < 0.0) alive = false;
+    } else {
+        const double t = __ddiv_rn(num, __dmul_rn(2.0, s));
+        if (s > 0.0) hi = fmin(hi, t);
+        else lo = fmax(lo, t);
+    }
+    if (!(lo < hi)) alive = false;
+}
+
+struct ORect { int x0, x1, y0, y1; };
+
+__device__ __forceinline__ void rect_row(const int32_t *__restrict__ start, const OGrid &g, const ORect &rc, int row, int n_fin, int &b, int &e)
+{
+    b = start[row * g.gx + rc.x0];
+    e = start[row * g.gx + rc.x1 + 1];
+    if (b < 0) b = 0;
+    if (e > n_fin) e = n_fin;
+    if (e < b) e = b;
+}
+
+// squared distance from p_i to the farther end of a live pair's interval (the circle's centre is a / 2 + t perp(a))
+__device__ __forceinline__ double reach2(double ax, double ay, double lo, double hi)
+{
+    if (!(lo > -O_INF) || !(hi < O_INF)) return O_INF;
+    const double t2 = fmax(lo * lo, hi * hi);
+    return (ax * ax + ay * ay) * (0.25 + t2);
+}
+
+struct OSweep {
+    long total;      // edges found
+    double reach;    // this lane's largest reach2
+};
+
+// One sweep over the candidates of rectangle rc.  in_lds: the rectangle's points are the n_near points staged in LDS; otherwise
+// they stream from the sorted arrays and the staged points are only the first filter.  raw != NULL: the edges' point positions
+// go to raw[raw_base ...] (bounded by raw_cap).
+__device__ OSweep sweep(const double *__restrict__ kx, const double *__restrict__ ky, const int *__restrict__ ki, int n_near, bool in_lds,
+                        const int32_t *__restrict__ start, const OGrid &g, const ORect &rc, int n_fin, const double *__restrict__ sx,
+                        const double *__restrict__ sy, const int32_t *__restrict__ sidx, double xi, double yi, int i, int lane,
+                        int32_t *__restrict__ raw, long raw_base, long raw_cap)
+{
+    OSweep out = {0, 0.0};
+    const unsigned long long below = (1ULL << lane) - 1ULL;
+    const int rows = in_lds ? 1 : rc.y1 - rc.y0 + 1;
+    for (int rr = 0; rr < rows; ++rr) {
+        int jb = 0, je = n_near;
+        if (!in_lds) rect_row(start, g, rc, rc.y0 + rr, n_fin, jb, je);
+        for (int j0 = jb; j0 < je; j0 += 64) {
+            const int j = j0 + lane;
+            bool alive = j < je;
+            double ax = 0.0, ay = 0.0, lo = -O_INF, hi = O_INF;
+            int idx = -1;
+            if (alive) {
+                if (in_lds) ax = kx[j], ay = ky[j], idx = ki[j];
+                else ax = __dsub_rn(sx[j], xi), ay = __dsub_rn(sy[j], yi), idx = sidx[j];
+                alive = idx != i;
+            }
+            for (int k = 0; k < n_near && __any(alive); ++k)
+                if (alive) cut(ax, ay, kx[k], ky[k], alive, lo, hi);
+            if (!in_lds)
+                for (int r2 = rc.y0; r2 <= rc.y1 && __any(alive); ++r2) {
+                    int kb, ke;
+                    rect_row(start, g, rc, r2, n_fin, kb, ke);
+                    for (int k = kb; k < ke && __any(alive); ++k)
+                        if (alive) cut(ax, ay, __dsub_rn(sx[k], xi), __dsub_rn(sy[k], yi), alive, lo, hi);
+                }
+            const unsigned long long mask = __ballot(alive);
+            if (alive) {
+                out.reach = fmax(out.reach, reach2(ax, ay, lo, hi));
+                if (raw) {
+                    const long pos = raw_base + out.total + __popcll(mask & below);
+                    if (pos >= 0 && pos < raw_cap) raw[pos] = idx;
+                }
+            }
+            out.total += __popcll(mask);
+        }
+    }
+    return out;
+}
+
+template <typename OffT>
+__global__ __launch_bounds__(64) void k_delaunay(const OGrid *__restrict__ gp, const int32_t *__restrict__ start, int cell_cap,
+                                                 const double *__restrict__ sx, const double *__restrict__ sy,
+                                                 const int32_t *__restrict__ sidx, int n, int64_t *__restrict__ sizes,
+                                                 int32_t *__restrict__ deg32, const OffT *__restrict__ moff, int32_t *__restrict__ raw,
+                                                 int32_t *__restrict__ row_len, long raw_cap)
+{
+    __shared__ double kx[O_CAP], ky[O_CAP];
+    __shared__ int ki[O_CAP];
+    const int lane = threadIdx.x;
+    const OGrid g = *gp;
+    int n_fin = start[cell_cap];
+    if (n_fin > n) n_fin = n;
+    const int p = blockIdx.x;                       // the same for every lane: all control flow below is uniform
+    if (p >= n_fin || g.gx < 1 || g.gy < 1 || (long)g.gx * g.gy > cell_cap) return;
+    const int i = sidx[p];
+    if ((unsigned)i >= (unsigned)n) return;
+    const double xi = sx[p], yi = sy[p];
+    const int cxi = cell_coord(xi, g.minx, g.h, g.gx), cyi = cell_coord(yi, g.miny, g.h, g.gy);
+    const long base = raw ? (long)moff[i] : 0;
+    int n_near = 0;
+    long total = 0;
+    for (long r = 2;; r *= 2) {
+        ORect rc;
+        rc.x0 = (int)((long)cxi - r > 0 ? (long)cxi - r : 0), rc.x1 = (int)((long)cxi + r < g.gx - 1 ? (long)cxi + r : g.gx - 1);
+        rc.y0 = (int)((long)cyi - r > 0 ? (long)cyi - r : 0), rc.y1 = (int)((long)cyi + r < g.gy - 1 ? (long)cyi + r : g.gy - 1);
+        const bool whole = rc.x0 == 0 && rc.y0 == 0 && rc.x1 == g.gx - 1 && rc.y1 == g.gy - 1;
+        long count = 0;
+        for (int row = rc.y0; row <= rc.y1; ++row) {
+            int b, e;
+            rect_row(start, g, rc, row, n_fin, b, e);
+            count += e - b;
+        }
+        const bool fits = count <= O_CAP;
+        if (fits) {
+            __syncthreads();                        // (one wavefront: orders the LDS traffic of the previous sweep and this fill)
+            int at = 0;
+            for (int row = rc.y0; row <= rc.y1; ++row) {
+                int b, e;
+                rect_row(start, g, rc, row, n_fin, b, e);
+                for (int q = b + lane; q < e; q += 64) {
+                    const int slot = at + (q - b);
+                    if (slot < O_CAP) kx[slot] = __dsub_rn(sx[q], xi), ky[slot] = __dsub_rn(sy[q], yi), ki[slot] = sidx[q];
+                }
+                at += e - b;
+            }
+            n_near = (int)count;
+            __syncthreads();
+        }
+        OSweep sw = sweep(kx, ky, ki, n_near, fits, start, g, rc, n_fin, sx, sy, sidx, xi, yi, i, lane, nullptr, 0, 0);
+        double reach = sw.reach;
+        for (int off = 32; off > 0; off >>= 1) reach = fmax(reach, __shfl_xor(reach, off));
+        if (sw.total == 0) reach = O_INF;
+        const double span = (double)r * g.h;
+        if (whole || 4.0 * reach * (1.0 + 1e-9) <= span * span) {
+            if (raw) sw = sweep(kx, ky, ki, n_near, fits, start, g, rc, n_fin, sx, sy, sidx, xi, yi, i, lane, raw, base, raw_cap);
+            total = sw.total;
+            break;
+        }
+    }
+    if (lane == 0) {
+        if (sizes) sizes[i] = total;
+        if (deg32) deg32[i] = (int32_t)total;
+        if (row_len) row_len[i] = (int32_t)total;
+    }
+}
+
+// one wavefront per row: entry a of raw goes to the slot numbered by the entries below it
+template <typename OffT>
+__global__ __launch_bounds__(256) void k_row_sort(const OffT *__restrict__ moff, const int32_t *__restrict__ row_len,
+                                                  const int32_t *__restrict__ raw, int32_t *__restrict__ members, int n, long cap, int add)
+{
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n) return;
+    const long b = (long)moff[row], e = b + row_len[row];
+    if (b < 0 || e < b || e > cap) return;
+    for (long a = b + lane; a < e; a += 64) {
+        const int v = raw[a];
+        long rank = 0;
+        for (long c = b; c < e; ++c) {
+            const int w = raw[c];
+            rank += (w < v || (w == v && c < a)) ? 1 : 0;
+        }
+        members[b + rank] = v + add;
+    }
+}
+
+template <typename OffT>
+__global__ void k_psin(const double *__restrict__ cy, const double *__restrict__ cx, int n, const int32_t *__restrict__ query, long m,
+                       const OffT *__restrict__ moff, const int32_t *__restrict__ members, long n_members, int order,
+                       double *__restrict__ out)
+{
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= m) return;
+    const long r = query ? (long)query[q] : q;
+    if (r < 0 || r >= n) { out[q] = 0.0; return; }
+    long b = (long)moff[q], e = (long)moff[q + 1];
+    if (b < 0) b = 0;
+    if (e > n_members) e = n_members;
+    const double y0 = cy[r], x0 = cx[r], nn = (double)order;
+    double sc = 0.0, ss = 0.0;
+    long cnt = 0;
+    for (long a = b; a < e; ++a) {
+        const int k = members[a] - 1;
+        if ((unsigned)k >= (unsigned)n) continue;
+        const double th = __dmul_rn(nn, atan2(__dsub_rn(cy[k], y0), __dsub_rn(cx[k], x0)));
+        double sn, cs;
+        sincos(th, &sn, &cs);
+        sc = __dadd_rn(sc, cs), ss = __dadd_rn(ss, sn);
+        ++cnt;
+    }
+    out[q] = cnt ? __ddiv_rn(hypot(sc, ss), (double)cnt) : 0.0;
+}
+
+__global__ void k_neighbor_state(const int32_t *__restrict__ offsets, const int32_t *__restrict__ adj, int n, long n_adj,
+                                 const uint8_t *__restrict__ member, const double *__restrict__ state, const int32_t *__restrict__ query,
+                                 long m, double *__restrict__ nb_sum, int64_t *__restrict__ nb_cnt)
+{
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= m) return;
+    const long r = query ? (long)query[q] : q;
+    double sum = 0.0;
+    int64_t cnt = 0;
+    if (r >= 0 && r < n) {
+        long b = offsets[r], e = offsets[r + 1];
+        if (b < 0) b = 0;
+        if (e > n_adj) e = n_adj;
+        for (long a = b; a < e; ++a) {
+            const int j = adj[a] - 1;
+            if ((unsigned)j >= (unsigned)n || member[j] == 0) continue;
+            sum = __dadd_rn(sum, state[j]);
+            ++cnt;
+        }
+    } else cnt = -1;
+    nb_sum[q] = sum;
+    nb_cnt[q] = cnt;
+}
+
+// ---- launches on device arrays --------------------------------------------------------------------------------------------------
+// sizes / deg32 (either may be NULL): the degrees; members (with moff, of OffT): the rows, ascending, each entry + add
+template <typename OffT>
+static int delaunay_launch(const double *py, const double *px, int64_t n, int64_t *sizes, int32_t *deg32, const OffT *moff, int32_t *members,
+                           int64_t members_cap, int add)
+{
+    Ctx &c = ctx();
+    if (sizes && n) TIP_HIP(hipMemsetAsync(sizes, 0, (size_t)n * 8, c.stream));
+    if (deg32 && n) TIP_HIP(hipMemsetAsync(deg32, 0, (size_t)n * 4, c.stream));
+    if (n < 2) return TIP_OK;
+    WsGuard ws;
+    const int cell_cap = (int)(n < 0x7ffffff0 - 4 ? n + 4 : 0x7ffffff0);
+    OGrid *g = ws.get<OGrid>(1);
+    int32_t *cell_of = ws.get<int32_t>((size_t)n), *cnt = ws.get<int32_t>((size_t)cell_cap), *start = ws.get<int32_t>((size_t)cell_cap + 1);
+    int32_t *sidx = ws.get<int32_t>((size_t)n), *raw = members ? ws.get<int32_t>((size_t)members_cap) : nullptr;
+    int32_t *row_len = members ? ws.get<int32_t>((size_t)n) : nullptr;
+    double *sx = ws.get<double>((size_t)n), *sy = ws.get<double>((size_t)n);
+    if (!g || !cell_of || !cnt || !start || !sidx || !sx || !sy || (members && (!raw || !row_len))) return TIP_ERR_NOMEM;
+    TIP_HIP(hipMemsetAsync(cnt, 0, (size_t)cell_cap * 4, c.stream));
+    TIP_LAUNCH("order_grid", k_order_grid, dim3(1), dim3(256), 0, py, px, (int)n, cell_cap, g);
+    TIP_LAUNCH("order_count", k_order_count, dim3(cdiv(n, 256)), dim3(256), 0, py, px, (int)n, (const OGrid *)g, cell_cap, cell_of, cnt);
+    if (int rc = scan_i32_dev(cnt, start, cell_cap)) return rc;
+    TIP_HIP(hipMemsetAsync(cnt, 0, (size_t)cell_cap * 4, c.stream));
+    TIP_LAUNCH("order_fill", k_order_fill, dim3(cdiv(n, 256)), dim3(256), 0, py, px, (int)n, (const int32_t *)cell_of, (const int32_t *)start, cnt,
+               sx, sy, sidx);
+    if (row_len) TIP_HIP(hipMemsetAsync(row_len, 0, (size_t)n * 4, c.stream));
+    TIP_LAUNCH("delaunay", k_delaunay<OffT>, dim3((unsigned)n), dim3(64), 0, (const OGrid *)g, (const int32_t *)start, cell_cap, (const double *)sx,
+               (const double *)sy, (const int32_t *)sidx, (int)n, sizes, deg32, moff, raw, row_len, (long)members_cap);
+    if (members)
+        TIP_LAUNCH("order_row_sort", k_row_sort<OffT>, dim3(cdiv(n, 4)), dim3(256), 0, moff, (const int32_t *)row_len, (const int32_t *)raw, members,
+                   (int)n, (long)members_cap, add);
+    return TIP_OK;
+}
+
+template <typename OffT>
+static int psin_launch(const double *cy, const double *cx, int64_t n, const int32_t *query, int64_t m, const OffT *moff, const int32_t *members,
+                       int64_t n_members, int order, double *out)
+{
+    if (m == 0) return TIP_OK;
+    TIP_LAUNCH("psin", k_psin<OffT>, dim3(cdiv(m, 256)), dim3(256), 0, cy, cx, (int)n, query, (long)m, moff, members, (long)n_members, order, out);
+    return TIP_OK;
+}
+
+static int check_delaunay_args(const char *who, const double *py, const double *px, int64_t n, const int64_t *sizes, const int64_t *moff,
+                               const int32_t *members, int64_t members_cap)
+{
+    if (n < 0 || n > 0x7ffffff0 - 8) return fail(TIP_ERR_ARG, "%s: n = %ld points", who, (long)n);
+    if (n > 0 && (!py || !px)) return fail(TIP_ERR_ARG, "%s: the coordinates (py, px)", who);
+    if (n > 0 && !sizes && !members) return fail(TIP_ERR_ARG, "%s: no output", who);
+    if (members && (!moff || members_cap < 0 || members_cap > 0x7fffffff)) return fail(TIP_ERR_ARG, "%s: members need member_offsets and a capacity", who);
+    return TIP_OK;
+}
+
+static int check_psin_args(const char *who, const double *cy, const double *cx, int64_t n, int64_t m, const int64_t *moff, const int32_t *members,
+                           int64_t n_members, int order, const double *out)
+{
+    if (n < 0 || n > 0x7ffffffe || m < 0 || n_members < 0 || n_members > 0x7fffffff)
+        return fail(TIP_ERR_ARG, "%s: n = %ld rows, m = %ld queries, %ld members", who, (long)n, (long)m, (long)n_members);
+    if (order < 1 || order > 64) return fail(TIP_ERR_ARG, "%s: order %d (1..64)", who, order);
+    if ((n > 0 && (!cy || !cx)) || !moff || (n_members > 0 && !members) || (m > 0 && !out)) return fail(TIP_ERR_ARG, "%s: null pointer", who);
+    return TIP_OK;
+}
+
+static int check_state_args(const char *who, const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *member,
+                            const double *state, int64_t m, const double *nb_sum, const int64_t *nb_cnt)
+{
+    if (n < 0 || n > 0x7ffffffe || m < 0 || n_adj < 0 || n_adj > 0x7fffffff)
+        return fail(TIP_ERR_ARG, "%s: n = %ld rows, m = %ld queries, n_adj = %ld", who, (long)n, (long)m, (long)n_adj);
+    if (!offsets || (n_adj > 0 && !adj) || (n > 0 && (!member || !state)) || (m > 0 && (!nb_sum || !nb_cnt)))
+        return fail(TIP_ERR_ARG, "%s: null pointer", who);
+    return TIP_OK;
+}
+
+template <typename T> static int up(WsGuard &ws, const T *host, size_t count, T *&dev)
+{
+    dev = ws.get<T>(count);
+    if (!dev) return TIP_ERR_NOMEM;
+    if (host && count) TIP_HIP(hipMemcpyAsync(dev, host, count * sizeof(T), hipMemcpyHostToDevice, ctx().stream));
+    return TIP_OK;
+}
+
+template <typename T> static int down(T *host, const T *dev, size_t count)
+{
+    if (host && count) TIP_HIP(hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx().stream));
+    return TIP_OK;
+}
+
+}  // namespace tip
+
+using namespace tip;
+
+extern "C" {
+
+int tip_delaunay_neighbors_f64_dev(const double *py, const double *px, int64_t n, int64_t *sizes, const int64_t *member_offsets,
+                                   int32_t *members, int64_t members_cap)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_delaunay_args("tip_delaunay_neighbors_f64_dev", py, px, n, sizes, member_offsets, members, members_cap)) return rc;
+    return delaunay_launch<int64_t>(py, px, n, sizes, nullptr, member_offsets, members, members_cap, 0);
+}
+
+int tip_delaunay_neighbors_f64(const double *py, const double *px, int64_t n, int64_t *sizes, const int64_t *member_offsets, int32_t *members,
+                               int64_t members_cap)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_delaunay_args("tip_delaunay_neighbors_f64", py, px, n, sizes, member_offsets, members, members_cap)) return rc;
+    for (int64_t p = 0; p < n; ++p) {
+        if (!std::isfinite(py[p]) || !std::isfinite(px[p]))
+            return fail(TIP_ERR_ARG, "tip_delaunay_neighbors_f64: point %ld has a non-finite coordinate", (long)p);
+        if (members && (member_offsets[p] < 0 || member_offsets[p] > members_cap))
+            return fail(TIP_ERR_ARG, "tip_delaunay_neighbors_f64: member_offsets[%ld] = %ld, capacity %ld", (long)p, (long)member_offsets[p],
+                        (long)members_cap);
+    }
+    if (n == 0) return TIP_OK;
+    WsGuard ws;
+    double *dy = nullptr, *dx = nullptr;
+    int64_t *dsizes = nullptr, *dmoff = nullptr;
+    int32_t *dmem = nullptr;
+    if (int rc = up(ws, py, (size_t)n, dy)) return rc;
+    if (int rc = up(ws, px, (size_t)n, dx)) return rc;
+    if (int rc = up(ws, (const int64_t *)nullptr, (size_t)n, dsizes)) return rc;
+    if (members) {
+        if (int rc = up(ws, member_offsets, (size_t)n, dmoff)) return rc;
+        if (int rc = up(ws, (const int32_t *)nullptr, (size_t)members_cap, dmem)) return rc;
+        if (members_cap) TIP_HIP(hipMemsetAsync(dmem, 0, (size_t)members_cap * 4, c.stream));
+    }
+    if (int rc = delaunay_launch<int64_t>(dy, dx, n, dsizes, nullptr, dmoff, dmem, members_cap, 0)) return rc;
+    if (int rc = down(sizes, (const int64_t *)dsizes, (size_t)n)) return rc;
+    if (int rc = down(members, (const int32_t *)dmem, (size_t)members_cap)) return rc;
+    TIP_HIP(hipStreamSynchronize(c.stream));
+    return TIP_OK;
+}
+
+int tip_psin_f64_dev(const double *cy, const double *cx, int64_t n, const int32_t *query, int64_t m, const int64_t *member_offsets,
+                     const int32_t *members, int64_t n_members, int order, double *out)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_psin_args("tip_psin_f64_dev", cy, cx, n, m, member_offsets, members, n_members, order, out)) return rc;
+    return psin_launch<int64_t>(cy, cx, n, query, m, member_offsets, members, n_members, order, out);
+}
+
+int tip_psin_f64(const double *cy, const double *cx, int64_t n, const int32_t *query, int64_t m, const int64_t *member_offsets,
+                 const int32_t *members, int64_t n_members, int order, double *out)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_psin_args("tip_psin_f64", cy, cx, n, m, member_offsets, members, n_members, order, out)) return rc;
+    if (!query && m > n) return fail(TIP_ERR_ARG, "tip_psin_f64: %ld queries of %ld rows", (long)m, (long)n);
+    for (int64_t q = 0; q < m; ++q) {
+        if (query && (query[q] < 0 || query[q] >= n)) return fail(TIP_ERR_ARG, "tip_psin_f64: query %ld is row %d of %ld", (long)q, query[q], (long)n);
+        if (member_offsets[q] < 0 || member_offsets[q + 1] < member_offsets[q] || member_offsets[q + 1] > n_members)
+            return fail(TIP_ERR_ARG, "tip_psin_f64: member_offsets[%ld .. %ld] = %ld, %ld with %ld members", (long)q, (long)q + 1,
+                        (long)member_offsets[q], (long)member_offsets[q + 1], (long)n_members);
+    }
+    for (int64_t a = 0; a < n_members; ++a)
+        if (members[a] < 1 || members[a] > n) return fail(TIP_ERR_ARG, "tip_psin_f64: member %ld is label %d (1..%ld)", (long)a, members[a], (long)n);
+    if (m == 0) return TIP_OK;
+    WsGuard ws;
+    double *dy = nullptr, *dx = nullptr, *dout = nullptr;
+    int32_t *dq = nullptr, *dmem = nullptr;
+    int64_t *dmoff = nullptr;
+    if (int rc = up(ws, cy, (size_t)n, dy)) return rc;
+    if (int rc = up(ws, cx, (size_t)n, dx)) return rc;
+    if (query) if (int rc = up(ws, query, (size_t)m, dq)) return rc;
+    if (int rc = up(ws, member_offsets, (size_t)m + 1, dmoff)) return rc;
+    if (int rc = up(ws, members, (size_t)n_members, dmem)) return rc;
+    if (int rc = up(ws, (const double *)nullptr, (size_t)m, dout)) return rc;
+    if (int rc = psin_launch<int64_t>(dy, dx, n, dq, m, dmoff, dmem, n_members, order, dout)) return rc;
+    if (int rc = down(out, (const double *)dout, (size_t)m)) return rc;
+    TIP_HIP(hipStreamSynchronize(c.stream));
+    return TIP_OK;
+}
+
+int tip_graph_neighbor_state_f64_dev(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *member,
+                                     const double *state, const int32_t *query, int64_t m, double *nb_sum, int64_t *nb_cnt)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_state_args("tip_graph_neighbor_state_f64_dev", offsets, adj, n, n_adj, member, state, m, nb_sum, nb_cnt)) return rc;
+    if (m == 0) return TIP_OK;
+    TIP_LAUNCH("neighbor_state", k_neighbor_state, dim3(cdiv(m, 256)), dim3(256), 0, offsets, adj, (int)n, (long)n_adj, member, state, query, (long)m,
+               nb_sum, nb_cnt);
+    return TIP_OK;
+}
+
+int tip_graph_neighbor_state_f64(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *member, const double *state,
+                                 const int32_t *query, int64_t m, double *nb_sum, int64_t *nb_cnt)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_state_args("tip_graph_neighbor_state_f64", offsets, adj, n, n_adj, member, state, m, nb_sum, nb_cnt)) return rc;
+    if (offsets[0] != 0 || offsets[n] != n_adj)
+        return fail(TIP_ERR_ARG, "tip_graph_neighbor_state_f64: offsets run from %d to %d, adj has %ld entries", offsets[0], offsets[n], (long)n_adj);
+    for (int64_t r = 0; r < n; ++r) {
+        if (offsets[r + 1] < offsets[r]) return fail(TIP_ERR_ARG, "tip_graph_neighbor_state_f64: offsets decrease at row %ld", (long)r);
+        for (int a = offsets[r]; a < offsets[r + 1]; ++a)
+            if (adj[a] < 1 || adj[a] > n) return fail(TIP_ERR_ARG, "tip_graph_neighbor_state_f64: row %ld holds label %d (1..%ld)", (long)r, adj[a], (long)n);
+    }
+    if (!query && m > n) return fail(TIP_ERR_ARG, "tip_graph_neighbor_state_f64: %ld queries of %ld rows", (long)m, (long)n);
+    for (int64_t q = 0; query && q < m; ++q)
+        if (query[q] < 0 || query[q] >= n) return fail(TIP_ERR_ARG, "tip_graph_neighbor_state_f64: query %ld is row %d of %ld", (long)q, query[q], (long)n);
+    if (m == 0) return TIP_OK;
+    WsGuard ws;
+    int32_t *doff = nullptr, *dadj = nullptr, *dq = nullptr;
+    uint8_t *dmember = nullptr;
+    double *dstate = nullptr, *dsum = nullptr;
+    int64_t *dcnt = nullptr;
+    if (int rc = up(ws, offsets, (size_t)n + 1, doff)) return rc;
+    if (int rc = up(ws, adj, (size_t)n_adj, dadj)) return rc;
+    if (int rc = up(ws, member, (size_t)n, dmember)) return rc;
+    if (int rc = up(ws, state, (size_t)n, dstate)) return rc;
+    if (query) if (int rc = up(ws, query, (size_t)m, dq)) return rc;
+    if (int rc = up(ws, (const double *)nullptr, (size_t)m, dsum)) return rc;
+    if (int rc = up(ws, (const int64_t *)nullptr, (size_t)m, dcnt)) return rc;
+    TIP_LAUNCH("neighbor_state", k_neighbor_state, dim3(cdiv(m, 256)), dim3(256), 0, (const int32_t *)doff, (const int32_t *)dadj, (int)n, (long)n_adj,
+               (const uint8_t *)dmember, (const double *)dstate, (const int32_t *)dq, (long)m, dsum, dcnt);
+    if (int rc = down(nb_sum, (const double *)dsum, (size_t)m)) return rc;
+    if (int rc = down(nb_cnt, (const int64_t *)dcnt, (size_t)m)) return rc;
+    TIP_HIP(hipStreamSynchronize(c.stream));
+    return TIP_OK;
+}
+
+int tip_order_features_f64_dev(const double *py, const double *px, int64_t n, int order, double *psi, int64_t *degree)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (n < 0 || n > 0x7ffffff0 - 8 || order < 1 || order > 64) return fail(TIP_ERR_ARG, "tip_order_features_f64_dev: n = %ld points, order %d", (long)n, order);
+    if (n > 0 && (!py || !px || !psi || !degree)) return fail(TIP_ERR_ARG, "tip_order_features_f64_dev: null pointer");
+    if (n == 0) return TIP_OK;
+    WsGuard ws;
+    int32_t *deg32 = ws.get<int32_t>((size_t)n), *off32 = ws.get<int32_t>((size_t)n + 1);
+    if (!deg32 || !off32) return TIP_ERR_NOMEM;
+    if (int rc = delaunay_launch<int32_t>(py, px, n, degree, deg32, nullptr, nullptr, 0, 0)) return rc;
+    if (int rc = scan_i32_dev(deg32, off32, (int)n)) return rc;
+    int32_t total = 0;
+    TIP_HIP(hipMemcpyAsync(&total, off32 + n, 4, hipMemcpyDeviceToHost, c.stream));
+    TIP_HIP(hipStreamSynchronize(c.stream));
+    if (total < 0) return fail(TIP_ERR_OVERFLOW, "tip_order_features_f64_dev: the neighbour lists overflow int32");
+    int32_t *mem = ws.get<int32_t>((size_t)total);
+    if (!mem) return TIP_ERR_NOMEM;
+    if (total) TIP_HIP(hipMemsetAsync(mem, 0, (size_t)total * 4, c.stream));
+    if (total)
+        if (int rc = delaunay_launch<int32_t>(py, px, n, nullptr, nullptr, (const int32_t *)off32, mem, total, 1)) return rc;
+    return psin_launch<int32_t>(py, px, n, nullptr, n, (const int32_t *)off32, (const int32_t *)mem, total, order, psi);
+}
+
+}  // extern "C"

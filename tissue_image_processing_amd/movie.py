@@ -123,7 +123,8 @@ class GpuFrameBackend(object):
     SEGMENTATIONS = ("classical", "unet")
 
     def __init__(self, C, Z, Y, X, device=None, keep_planes=False, inflight=1, cell_types=None, segmentation="classical",
-                 unet_weights=None, unet_channels=(1, 0), predictor_factory=None, keep_hc=False, neighbor_features=False, **kw):
+                 unet_weights=None, unet_channels=(1, 0), predictor_factory=None, keep_hc=False, neighbor_features=False,
+                 order_features=False, **kw):
         from .pipeline import FramePipeline
         from . import _lib
         # segmentation: "classical" (FramePipeline.segment: threshold, blur, watershed on channel 0) or "unet", the GUI's "use
@@ -164,6 +165,11 @@ class GpuFrameBackend(object):
             from .pipeline import FramePipeline as _FP
             names = _FP.NEIGHBOR_COLUMNS + (_FP.TYPED_NEIGHBOR_COLUMNS if cell_types is not None else ())
             self.extra_columns = tuple(self.extra_columns) + tuple((name, np.int64) for name in names)
+        # order_features: every frame's dict also gains FramePipeline.order_features' columns psi6 (float64) and voronoi_neighbors
+        # (int64) over its valid rows -- valid as cell_types has them, else by the area rule above; independent of neighbor_features
+        self.order_features = bool(order_features)
+        if self.order_features:
+            self.extra_columns = tuple(self.extra_columns) + tuple(FramePipeline.ORDER_COLUMNS)
         self.device = device
         self.pipe = FramePipeline(C, Z, Y, X, device=device, **kw)
         if device is None:
@@ -288,6 +294,14 @@ class GpuFrameBackend(object):
             else:
                 mean = tab["area"].mean() if n else 0.0
                 out.update(p.neighbor_features(n, (tab["area"] > 0.1 * mean) & (tab["area"] < 10 * mean)))
+        if self.order_features:
+            n = tab["area"].size
+            if self.cell_types is not None:
+                valid = out["valid"]
+            else:
+                mean = tab["area"].mean() if n else 0.0
+                valid = (tab["area"] > 0.1 * mean) & (tab["area"] < 10 * mean)
+            out.update(p.order_features(n, valid, out["cy"], out["cx"]))
         return out
 
     def fetch_cell_types(self, t):

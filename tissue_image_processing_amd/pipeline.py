@@ -233,6 +233,40 @@ class FramePipeline:
         block = self._nf.download((len(names) * n,), np.int64)
         return {name: block[i * n:(i + 1) * n] for i, name in enumerate(names)}
 
+    ORDER_COLUMNS = (("psi6", np.float64), ("voronoi_neighbors", np.int64))
+
+    def order_features(self, n, valid, cy, cx, order=6):
+        """The hexatic order of the n table rows (csrc/tip_order.hip): the rows with valid == 1 are the points, their Delaunay
+        neighbours are found on the device and psi_order is taken over them (find_nearest_neighbors_using_voroni_tesselation +
+        calc_psin, ti.py:2545-2583).  Returns psi6 (float64) and voronoi_neighbors (int64, the number of Delaunay neighbours), 0 for
+        the other rows and everywhere when fewer than 4 rows are valid (upstream's rule).  valid, cy, cx: host arrays of n rows.
+        One device block: the points go up in one copy, the two columns come back in one."""
+        from . import _segmentation as seg
+        n = int(n)
+        valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
+        cy = np.ascontiguousarray(cy, dtype=np.float64).reshape(-1)
+        cx = np.ascontiguousarray(cx, dtype=np.float64).reshape(-1)
+        if valid.size != n or cy.size != n or cx.size != n:
+            raise ValueError("valid / cy / cx need %d rows" % n)
+        out = dict(psi6=np.zeros(n, np.float64), voronoi_neighbors=np.zeros(n, np.int64))
+        rows = np.flatnonzero(valid == 1)
+        m = rows.size
+        if m < 4:
+            return out
+        if getattr(self, "_of", None) is None or self._of.nbytes < 32 * m:
+            self._of = _lib.DeviceBuffer(48 * m)
+        base = self._of.ptr                     # [py m | px m | psi m | degree m], 8 bytes each
+        pts = np.concatenate([cy[rows], cx[rows]])
+        if not np.isfinite(pts).all():
+            raise ValueError("order_features: a valid row has a non-finite centroid")
+        _lib.check(self.lib.tip_memcpy_h2d(_lib.dptr(base), _lib.ptr(pts), ctypes.c_size_t(16 * m)))
+        seg.order_features_dev(base, base + 8 * m, m, order, base + 16 * m, base + 24 * m)
+        blob = np.empty(16 * m, np.uint8)
+        _lib.check(self.lib.tip_memcpy_d2h(_lib.ptr(blob), _lib.dptr(base + 16 * m), ctypes.c_size_t(16 * m)))
+        out["psi6"][rows] = blob[:8 * m].view(np.float64)
+        out["voronoi_neighbors"][rows] = blob[8 * m:].view(np.int64)
+        return out
+
     def fetch_cell_types(self):
         return self.d_types.download((self.Y, self.X), np.uint8)
 

@@ -1335,6 +1335,83 @@ class TissueHipMixin(object):
         res = self._contact_values(frame, self._query_rows(cells), cell_type, positive_for_type, bool(for_histogram))
         return res[3].astype(np.float64) if for_histogram else res.astype(np.float64)
 
+    # ---- hexatic order and neighbour correlations (csrc/tip_order.hip) ------------------------------------------------------
+    # Upstream's names and signatures again, reached through `self` by upstream's get_frame_data when this mixin sits in front
+    # of the reference's class; this mixin's own get_frame_data still hands "psi6" and the correlations on.
+    @staticmethod
+    def find_nearest_neighbors_using_voroni_tesselation(cells):
+        """ti.py:2545-2560: per row of `cells` the set of labels (index + 1) of its Delaunay neighbours among the rows' centroids
+        (cx, cy) -- what scipy.spatial.Voronoi(...).ridge_points pairs up.  Empty sets for fewer than 4 rows, as upstream.  Two
+        device calls (tip_delaunay_neighbors_f64: sizes, then members).  Deviations, see DESIGN.md 5.8: rows that all lie on one
+        line give the chain of consecutive rows (upstream: QhullError); two rows with the same centroid raise ValueError
+        (Qhull silently drops the later one); cocircular quadruples keep neither diagonal (Qhull: merged facets, the same)."""
+        neighbors = [set() for _ in range(cells.shape[0])]
+        if cells.shape[0] < 4:
+            return neighbors
+        index = cells.index.to_numpy()
+        _, moff, members = seg.delaunay_neighbors(cells["cy"].to_numpy(dtype=np.float64), cells["cx"].to_numpy(dtype=np.float64))
+        labels = index[members] + 1
+        return [set(labels[moff[q]:moff[q + 1]].tolist()) for q in range(cells.shape[0])]
+
+    def calc_psin(self, frame, cells, second_order_neighbors, n=6, for_histogram=False):
+        """ti.py:2563-2583: per row of `cells` |sum exp(-n i theta)| / count over the labels of its entry in
+        second_order_neighbors (any list of label sets: find_nearest_neighbors_using_voroni_tesselation's or
+        find_second_order_neighbors'), theta the direction from the row's centroid to the neighbour's, both looked up in the frame's
+        table; 0 for an empty set.  None without a table.  for_histogram: upstream only skips the rows with an empty set, which
+        would stay 0 anyway, so the array is the same with and without it.  One device call (tip_psin_f64), members summed in
+        ascending label order (upstream: set iteration order)."""
+        table = self.get_cells_info(frame)
+        if table is None:
+            return None
+        if cells.shape[0] == 0:
+            return np.zeros(0)
+        if len(second_order_neighbors) != cells.shape[0]:
+            raise ValueError("calc_psin: %d neighbour sets for %d rows" % (len(second_order_neighbors), cells.shape[0]))
+        rows = [sorted(int(v) for v in s) for s in second_order_neighbors]
+        moff = np.zeros(len(rows) + 1, np.int64)
+        moff[1:] = np.cumsum([len(r) for r in rows])
+        members = np.fromiter((v for r in rows for v in r), dtype=np.int32, count=int(moff[-1]))
+        return seg.psin(table["cy"].to_numpy(dtype=np.float64), table["cx"].to_numpy(dtype=np.float64), moff, members,
+                        self._query_rows(cells), order=n)
+
+    def calculate_neighbors_correlation_function(self, frame, valid_cells, set_state_by="type", method="neighbors", type_name=""):
+        """ti.py:803-843: the correlation of a cell's state (set_state_by "type": 1 when positive for type_name, else 0;
+        "intensity": its mean_intensity_<type_name> column) with its neighbours' -- method "neighbors": the mean over the contacts
+        between rows of valid_cells of the product of the two deviations, over the variance; "neighbors average": the Pearson
+        coefficient between a row's state and the mean state of its neighbours in valid_cells.  The row loops are one device call
+        (tip_graph_neighbor_state_f64: per row the sum of its listed neighbours' states and their number, over the CSR of the
+        table's `neighbors` sets); the rest is O(rows) numpy.  As upstream: a type_name that is no type raises KeyError (type
+        states), any other method raises NotImplementedError (the GUI's "neighbors_average" included), zero variance or no contact
+        gives NaN."""
+        if set_state_by == "intensity":
+            state = valid_cells["mean_intensity_" + type_name].to_numpy(dtype=np.float64)
+        elif set_state_by == "type":
+            bit, _ = self._window_selector(type_name, True)
+            if bit < 0:
+                raise KeyError(type_name)
+            state = is_positive_for_type(valid_cells["type"].to_numpy(), bit).astype(np.float64)
+        else:
+            raise ValueError("set_state_by must be 'type' or 'intensity', not %r" % (set_state_by,))
+        if method not in ("neighbors", "neighbors average"):
+            raise NotImplementedError
+        table = self.get_cells_info(frame)
+        offsets, adj, _, _, _ = self._graph_of(table)
+        query = self._query_rows(valid_cells)
+        member, full = np.zeros(table.shape[0], np.uint8), np.zeros(table.shape[0], np.float64)
+        member[query] = 1
+        full[query] = state
+        nb_sum, nb_cnt = seg.graph_neighbor_state(offsets, adj, member, full, query)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            state_avg, states_var = np.average(state), np.var(state)
+            if method == "neighbors":
+                frame_corr = np.sum((state - state_avg) * (nb_sum - nb_cnt * state_avg))
+                return frame_corr / (int(nb_cnt.sum()) * states_var)
+            neighbors_states = np.zeros(valid_cells.shape[0])
+            has = nb_cnt > 0
+            neighbors_states[has] = nb_sum[has] / nb_cnt[has]
+            return np.sum((state - state_avg) * (neighbors_states - np.average(neighbors_states))) / \
+                (valid_cells.shape[0] * np.sqrt(states_var) * np.std(neighbors_states))
+
     def get_frame_data(self, frame, feature, valid_cells, special_features=[], global_features=[], spatial_features=[],
                        for_histogram=False, reference=None, intensity_img=None, window_radius=0, types=None):
         """ti.py:1035-1134: (data, "") for plain table columns, "shape index" / "roundness" / "Mean atoh intensity", the globals
