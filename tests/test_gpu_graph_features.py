@@ -137,6 +137,23 @@ def test_adj_capacity_one_short_is_an_overflow():
     np.testing.assert_array_equal(adj, f["all_adj"])
 
 
+def test_a_null_optional_output_of_contact_sums_is_skipped():
+    from tissue_image_processing_amd import _lib
+    f = gc.frame("B")
+    pairs, counts = np.ascontiguousarray(f["triples"][0], np.int32).reshape(-1, 2), np.ascontiguousarray(f["triples"][1], np.int64)
+    n, i64 = f["n"], ctypes.c_int64
+    head = (_lib.ptr(pairs), _lib.ptr(counts), i64(counts.size), _lib.ptr(f["offsets"]), _lib.ptr(f["adj"]), i64(n), i64(f["adj"].size),
+            _lib.ptr(f["valid"]), _lib.ptr(f["type"]), None, i64(n), 1, -1, 1)
+    got = {}
+    for name, skip in (("both", ()), ("no_n_sel", ("n_sel",)), ("no_sums", ("sums",))):
+        out = {k: None if k in skip else np.full(n, -7, np.int64) for k in ("sums", "n_sel")}
+        _lib.check(_lib.lib().tip_contact_sums_i32(*head, _lib.ptr(out["sums"]), _lib.ptr(out["n_sel"]), None, None, None, i64(0)))
+        got[name] = out
+    assert got["both"]["sums"].max() > 0 and got["both"]["n_sel"].max() > 0
+    np.testing.assert_array_equal(got["no_n_sel"]["sums"], got["both"]["sums"])
+    np.testing.assert_array_equal(got["no_sums"]["n_sel"], got["both"]["n_sel"])
+
+
 def test_argument_errors():
     seg = _seg()
     from tissue_image_processing_amd import _lib

@@ -107,10 +107,15 @@ def test_neighbour_state_equals_the_restatement_bit_for_bit(tag):
             assert nb_sum.tobytes() == want_sum.tobytes()
 
 
-def test_dev_forms_equal_the_host_forms():
+@pytest.mark.parametrize("tag", ["C", "H"])
+def test_dev_forms_equal_the_host_forms(tag):
+    """H: 73 points around a hub of 71 Delaunay neighbours, so the chained entry's row sort (int32 offsets, labels = positions
+    + 1) meets a row of two 64-lane chunks"""
     from tissue_image_processing_amd import _lib
     seg = _seg()
-    f = oc.frame("C")
+    f = oc.frame(tag)
+    if tag == "H":
+        assert f["cells"].size == 73 and int(np.diff(f["vor"][0]).max()) == 71      # (from the golden, on the CPU)
     py, px = np.ascontiguousarray(f["cy"][f["cells"]]), np.ascontiguousarray(f["cx"][f["cells"]])
     n = py.size
     sizes, moff, mem = seg.delaunay_neighbors(py, px)
@@ -139,6 +144,22 @@ def test_dev_forms_equal_the_host_forms():
     seg.graph_neighbor_state_dev(d_off.ptr, d_adj.ptr, N, f["adj"].size, d_member.ptr, d_state.ptr, None, N, d_sum.ptr, d_cnt.ptr)
     assert d_sum.download((N,), np.float64).tobytes() == want_sum.tobytes()
     np.testing.assert_array_equal(d_cnt.download((N,), np.int64), want_cnt)
+
+
+def test_neighbour_state_sums_in_row_order_and_takes_a_row_that_does_not_ascend():
+    """(-1e16 + 1e16) + 1.0 = 1.0 in the row's order 4, 2, 3; the ascending order 2, 3, 4 would give (1e16 + 1.0) - 1e16 = 0.0"""
+    from tissue_image_processing_amd import _lib
+    seg = _seg()
+    offsets, adj = np.asarray([0, 3, 3, 3, 3], np.int32), np.asarray([4, 2, 3], np.int32)
+    member, state, query = np.ones(4, np.uint8), np.asarray([0.0, 1e16, 1.0, -1e16]), np.asarray([0], np.int32)
+    nb_sum, nb_cnt = seg.graph_neighbor_state(offsets, adj, member, state, query)
+    assert nb_sum.tolist() == [1.0] and nb_cnt.tolist() == [3]
+    bufs = [_lib.DeviceBuffer(a.nbytes).upload(a) for a in (offsets, adj, member, state, query)]
+    d_sum, d_cnt = _lib.DeviceBuffer(8), _lib.DeviceBuffer(8)
+    seg.graph_neighbor_state_dev(bufs[0].ptr, bufs[1].ptr, 4, 3, bufs[2].ptr, bufs[3].ptr, bufs[4].ptr, 1, d_sum.ptr, d_cnt.ptr)
+    assert d_sum.download((1,), np.float64).tolist() == [1.0] and d_cnt.download((1,), np.int64).tolist() == [3]
+    with pytest.raises(ValueError):                                            # the entries that search a row ask for ascending rows
+        seg.graph_counts(offsets, adj, member, 0 * member, 0 * member, query, "valid")
 
 
 def golden_tissue(tag):

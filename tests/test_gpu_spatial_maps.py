@@ -6,6 +6,7 @@ Bounds: counts, the integer area sum, density and type_fraction (one division of
 doubles taken in another order differs by at most n_sel 2^-52 relative (worst-case reordering error); that is the bound of sum_sel and of
 every mean, per centre / grid point with its own n_sel.  The kernel tile is 128 centres and the LDS chunk 512 table rows."""
 import builtins
+import ctypes
 import threading
 
 import numpy as np
@@ -207,6 +208,13 @@ def test_dev_and_host_entries_give_the_same_map(g):
         _lib.check(_lib.lib().tip_sync())
         np.testing.assert_array_equal(d_map.download(host_map.shape, np.float64), host_map)
         np.testing.assert_array_equal(d_n.download(host_n.shape, np.int64), host_n)
+    # ... a NULL n_sel_grid is skipped: the host entry gives the same map without it
+    host_map, _ = seg.spatial_map(labels.shape, 7, 650.25, cy, cx, area, typ, feat, 0, True, "density")
+    alone = np.full(host_map.shape, -7.0)
+    _lib.check(_lib.lib().tip_spatial_map_f64(
+        labels.shape[0], labels.shape[1], 7, ctypes.c_double(650.25), _lib.ptr(cy), _lib.ptr(cx), _lib.ptr(area), _lib.ptr(typ), _lib.ptr(feat),
+        ctypes.c_int64(n), 0, 1, seg.SPATIAL_MODES["density"], _lib.ptr(alone), None))
+    np.testing.assert_array_equal(alone, host_map)
     # ... and the statistics' device entry
     qy, qx = np.ascontiguousarray(cy[:50]), np.ascontiguousarray(cx[:50])
     host = seg.window_stats(qy, qx, 650.25, cy, cx, area, typ, feat, 0, False)

@@ -110,7 +110,8 @@ def ptr(a):
 
 
 def dptr(addr):
-    return c_void_p(int(addr))
+    """a device address as a pointer argument; None is the NULL pointer"""
+    return c_void_p(None if addr is None else int(addr))
 
 
 class DeviceBuffer:

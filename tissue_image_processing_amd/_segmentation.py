@@ -230,8 +230,8 @@ def cell_types_dev(labels_ptr, marker_ptr, y, x, n, percentage_above_threshold, 
     _lib.check(_lib.lib().tip_cell_types_i32_dev(
         _lib.dptr(labels_ptr), _lib.dptr(marker_ptr), int(y), int(x), int(n), ctypes.c_double(q_over_100),
         ctypes.c_double(threshold), int(peak_window_size), _lib.ptr(taps), 0 if taps is None else int(taps.size), int(type_index),
-        ctypes.c_double(min_cell_area), ctypes.c_double(max_cell_area), _lib.dptr(out_type_ptr or 0), _lib.dptr(out_valid_ptr or 0),
-        _lib.dptr(out_mean_ptr or 0), _lib.dptr(out_type_map_ptr)))
+        ctypes.c_double(min_cell_area), ctypes.c_double(max_cell_area), _lib.dptr(out_type_ptr), _lib.dptr(out_valid_ptr),
+        _lib.dptr(out_mean_ptr), _lib.dptr(out_type_map_ptr)))
 
 
 def _cell_columns(cy, cx, area, type, feat):
@@ -290,19 +290,19 @@ def spatial_map_dev(shape, step, r2, cy_ptr, cx_ptr, area_ptr, type_ptr, feat_pt
     """tip_spatial_map_f64_dev: the same on DEVICE buffers (addresses), asynchronous on the calling thread's stream; the map
     stays in the caller's device buffer map_ptr ((Y, X) float64), the grid's n_sel counts in n_sel_ptr when given."""
     _lib.check(_lib.lib().tip_spatial_map_f64_dev(
-        int(shape[0]), int(shape[1]), int(step), ctypes.c_double(r2), _lib.dptr(cy_ptr or 0), _lib.dptr(cx_ptr or 0),
-        _lib.dptr(area_ptr or 0), _lib.dptr(type_ptr or 0), _lib.dptr(feat_ptr or 0), ctypes.c_int64(n), int(sel_bit),
-        1 if sel_positive else 0, SPATIAL_MODES[mode], _lib.dptr(map_ptr or 0), _lib.dptr(n_sel_ptr or 0)))
+        int(shape[0]), int(shape[1]), int(step), ctypes.c_double(r2), _lib.dptr(cy_ptr), _lib.dptr(cx_ptr),
+        _lib.dptr(area_ptr), _lib.dptr(type_ptr), _lib.dptr(feat_ptr), ctypes.c_int64(n), int(sel_bit),
+        1 if sel_positive else 0, SPATIAL_MODES[mode], _lib.dptr(map_ptr), _lib.dptr(n_sel_ptr)))
 
 
 def window_stats_dev(qy_ptr, qx_ptr, m, r2, cy_ptr, cx_ptr, area_ptr, type_ptr, feat_ptr, n, sel_bit, sel_positive, n_in_ptr,
                      area_in_ptr, n_sel_ptr, sum_sel_ptr):
     """tip_window_stats_f64_dev: device addresses in and out, asynchronous on the calling thread's stream."""
     _lib.check(_lib.lib().tip_window_stats_f64_dev(
-        _lib.dptr(qy_ptr or 0), _lib.dptr(qx_ptr or 0), ctypes.c_int64(m), ctypes.c_double(r2), _lib.dptr(cy_ptr or 0),
-        _lib.dptr(cx_ptr or 0), _lib.dptr(area_ptr or 0), _lib.dptr(type_ptr or 0), _lib.dptr(feat_ptr or 0), ctypes.c_int64(n),
-        int(sel_bit), 1 if sel_positive else 0, _lib.dptr(n_in_ptr or 0), _lib.dptr(area_in_ptr or 0), _lib.dptr(n_sel_ptr or 0),
-        _lib.dptr(sum_sel_ptr or 0)))
+        _lib.dptr(qy_ptr), _lib.dptr(qx_ptr), ctypes.c_int64(m), ctypes.c_double(r2), _lib.dptr(cy_ptr),
+        _lib.dptr(cx_ptr), _lib.dptr(area_ptr), _lib.dptr(type_ptr), _lib.dptr(feat_ptr), ctypes.c_int64(n),
+        int(sel_bit), 1 if sel_positive else 0, _lib.dptr(n_in_ptr), _lib.dptr(area_in_ptr), _lib.dptr(n_sel_ptr),
+        _lib.dptr(sum_sel_ptr)))
 
 
 # ---- neighbour-graph features (csrc/tip_graph.hip) ------------------------------------------------------------------------------
@@ -361,6 +361,22 @@ def _graph_args(offsets, adj, valid, empty, type, query):
     return offsets, adj, n, valid, empty, type, query, m
 
 
+def _two_calls(entry, head, first, counts, dtypes, want_rows=True):
+    """The two-call convention of the entries whose rows have no known length: one call with the per-row outputs `first` (among
+    them `counts`, the rows' lengths) and no rows; the exclusive scan of the lengths on the host; a second call that fills one
+    zeroed array per dtype at those offsets.  Returns (offsets int64[m + 1], one array per dtype), or () without want_rows."""
+    no_rows = (None,) * (1 + len(dtypes))
+    _lib.check(entry(*head, *[_lib.ptr(a) for a in first], *no_rows, ctypes.c_int64(0)))
+    if not want_rows:
+        return ()
+    off = np.zeros(counts.size + 1, np.int64)
+    off[1:] = np.cumsum(counts)
+    rows = [np.zeros(int(off[-1]), dt) for dt in dtypes]
+    if off[-1]:
+        _lib.check(entry(*head, *(None,) * len(first), _lib.ptr(off), *[_lib.ptr(r) for r in rows], ctypes.c_int64(int(off[-1]))))
+    return (off, *rows)
+
+
 def _selector(mode, sel_bit):
     return GRAPH_MODES[mode] if isinstance(mode, str) else int(mode), -1 if sel_bit is None else int(sel_bit)
 
@@ -381,8 +397,8 @@ def neighbor_csr(pairs, n, working=None, cap=None):
 def neighbor_csr_dev(pairs_ptr, n_pairs, n, working_ptr, offsets_ptr, adj_ptr, cap, want_count=False):
     """tip_neighbor_csr_i32_dev on device addresses; asynchronous unless want_count (then the entry count comes back)."""
     n_adj = ctypes.c_int64(0)
-    _lib.check(_lib.lib().tip_neighbor_csr_i32_dev(_lib.dptr(pairs_ptr or 0), ctypes.c_int64(n_pairs), ctypes.c_int64(n),
-                                                   _lib.dptr(working_ptr or 0), _lib.dptr(offsets_ptr or 0), _lib.dptr(adj_ptr or 0),
+    _lib.check(_lib.lib().tip_neighbor_csr_i32_dev(_lib.dptr(pairs_ptr), ctypes.c_int64(n_pairs), ctypes.c_int64(n),
+                                                   _lib.dptr(working_ptr), _lib.dptr(offsets_ptr), _lib.dptr(adj_ptr),
                                                    ctypes.c_int64(cap), ctypes.byref(n_adj) if want_count else None))
     return int(n_adj.value) if want_count else None
 
@@ -401,9 +417,9 @@ def graph_counts(offsets, adj, valid, empty, type, query=None, mode="all", sel_b
 def graph_counts_dev(offsets_ptr, adj_ptr, n, n_adj, valid_ptr, empty_ptr, type_ptr, query_ptr, m, mode, sel_bit, sel_positive, out_ptr):
     mode, bit = _selector(mode, sel_bit)
     _lib.check(_lib.lib().tip_graph_counts_i32_dev(
-        _lib.dptr(offsets_ptr or 0), _lib.dptr(adj_ptr or 0), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr or 0),
-        _lib.dptr(empty_ptr or 0), _lib.dptr(type_ptr or 0), _lib.dptr(query_ptr or 0), ctypes.c_int64(m), mode, bit,
-        1 if sel_positive else 0, _lib.dptr(out_ptr or 0)))
+        _lib.dptr(offsets_ptr), _lib.dptr(adj_ptr), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr),
+        _lib.dptr(empty_ptr), _lib.dptr(type_ptr), _lib.dptr(query_ptr), ctypes.c_int64(m), mode, bit,
+        1 if sel_positive else 0, _lib.dptr(out_ptr)))
 
 
 def graph_second(offsets, adj, valid, type, query=None, sel_bit=None, sel_positive=True, members=True):
@@ -414,23 +430,16 @@ def graph_second(offsets, adj, valid, type, query=None, sel_bit=None, sel_positi
     sizes = np.zeros(m, np.int64)
     head = (_lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(n), ctypes.c_int64(adj.size), _lib.ptr(valid), _lib.ptr(type), _lib.ptr(query),
             ctypes.c_int64(m), bit, 1 if sel_positive else 0)
-    _lib.check(_lib.lib().tip_graph_second_i32(*head, _lib.ptr(sizes), None, None, ctypes.c_int64(0)))
-    if not members:
-        return sizes
-    moff = np.zeros(m + 1, np.int64)
-    moff[1:] = np.cumsum(sizes)
-    mem = np.zeros(int(moff[-1]), np.int32)
-    if mem.size:
-        _lib.check(_lib.lib().tip_graph_second_i32(*head, None, _lib.ptr(moff), _lib.ptr(mem), ctypes.c_int64(mem.size)))
-    return sizes, moff, mem
+    rows = _two_calls(_lib.lib().tip_graph_second_i32, head, (sizes,), sizes, (np.int32,), members)
+    return (sizes, *rows) if members else sizes
 
 
 def graph_second_dev(offsets_ptr, adj_ptr, n, n_adj, valid_ptr, type_ptr, query_ptr, m, sel_bit, sel_positive, sizes_ptr,
                      member_offsets_ptr=None, members_ptr=None, members_cap=0):
     _lib.check(_lib.lib().tip_graph_second_i32_dev(
-        _lib.dptr(offsets_ptr or 0), _lib.dptr(adj_ptr or 0), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr or 0),
-        _lib.dptr(type_ptr or 0), _lib.dptr(query_ptr or 0), ctypes.c_int64(m), -1 if sel_bit is None else int(sel_bit),
-        1 if sel_positive else 0, _lib.dptr(sizes_ptr or 0), _lib.dptr(member_offsets_ptr or 0), _lib.dptr(members_ptr or 0),
+        _lib.dptr(offsets_ptr), _lib.dptr(adj_ptr), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr),
+        _lib.dptr(type_ptr), _lib.dptr(query_ptr), ctypes.c_int64(m), -1 if sel_bit is None else int(sel_bit),
+        1 if sel_positive else 0, _lib.dptr(sizes_ptr), _lib.dptr(member_offsets_ptr), _lib.dptr(members_ptr),
         ctypes.c_int64(members_cap)))
 
 
@@ -446,14 +455,10 @@ def contact_sums(pairs, counts, offsets, adj, valid, type, query=None, mode="all
     sums, n_sel = np.zeros(m, np.int64), np.zeros(m, np.int64)
     head = (_lib.ptr(pairs), _lib.ptr(counts), ctypes.c_int64(counts.size), _lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(n),
             ctypes.c_int64(adj.size), _lib.ptr(valid), _lib.ptr(type), _lib.ptr(query), ctypes.c_int64(m), mode, bit, 1 if sel_positive else 0)
-    _lib.check(_lib.lib().tip_contact_sums_i32(*head, _lib.ptr(sums), _lib.ptr(n_sel), None, None, None, ctypes.c_int64(0)))
+    rows = _two_calls(_lib.lib().tip_contact_sums_i32, head, (sums, n_sel), n_sel, (np.int64, np.int32), values)
     if not values:
         return sums
-    voff = np.zeros(m + 1, np.int64)
-    voff[1:] = np.cumsum(n_sel)
-    val, lab = np.zeros(int(voff[-1]), np.int64), np.zeros(int(voff[-1]), np.int32)
-    if val.size:
-        _lib.check(_lib.lib().tip_contact_sums_i32(*head, None, None, _lib.ptr(voff), _lib.ptr(val), _lib.ptr(lab), ctypes.c_int64(val.size)))
+    voff, val, lab = rows
     return sums, voff, lab, val
 
 
@@ -461,10 +466,10 @@ def contact_sums_dev(pairs_ptr, counts_ptr, n_triples, offsets_ptr, adj_ptr, n, 
                      sel_positive, sums_ptr, n_sel_ptr=None, value_offsets_ptr=None, values_ptr=None, value_labels_ptr=None, values_cap=0):
     mode, bit = _selector(mode, sel_bit)
     _lib.check(_lib.lib().tip_contact_sums_i32_dev(
-        _lib.dptr(pairs_ptr or 0), _lib.dptr(counts_ptr or 0), ctypes.c_int64(n_triples), _lib.dptr(offsets_ptr or 0), _lib.dptr(adj_ptr or 0),
-        ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr or 0), _lib.dptr(type_ptr or 0), _lib.dptr(query_ptr or 0),
-        ctypes.c_int64(m), mode, bit, 1 if sel_positive else 0, _lib.dptr(sums_ptr or 0), _lib.dptr(n_sel_ptr or 0),
-        _lib.dptr(value_offsets_ptr or 0), _lib.dptr(values_ptr or 0), _lib.dptr(value_labels_ptr or 0), ctypes.c_int64(values_cap)))
+        _lib.dptr(pairs_ptr), _lib.dptr(counts_ptr), ctypes.c_int64(n_triples), _lib.dptr(offsets_ptr), _lib.dptr(adj_ptr),
+        ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr), _lib.dptr(type_ptr), _lib.dptr(query_ptr),
+        ctypes.c_int64(m), mode, bit, 1 if sel_positive else 0, _lib.dptr(sums_ptr), _lib.dptr(n_sel_ptr),
+        _lib.dptr(value_offsets_ptr), _lib.dptr(values_ptr), _lib.dptr(value_labels_ptr), ctypes.c_int64(values_cap)))
 
 
 # ---- hexatic order and neighbour correlations (csrc/tip_order.hip) ----------------------------------------------------------------
@@ -486,22 +491,15 @@ def delaunay_neighbors(py, px, members=True):
         raise ValueError("delaunay_neighbors: two points have the same coordinates")
     sizes = np.zeros(n, np.int64)
     head = (_lib.ptr(py), _lib.ptr(px), ctypes.c_int64(n))
-    _lib.check(_lib.lib().tip_delaunay_neighbors_f64(*head, _lib.ptr(sizes), None, None, ctypes.c_int64(0)))
-    if not members:
-        return sizes
-    moff = np.zeros(n + 1, np.int64)
-    moff[1:] = np.cumsum(sizes)
-    mem = np.zeros(int(moff[-1]), np.int32)
-    if mem.size:
-        _lib.check(_lib.lib().tip_delaunay_neighbors_f64(*head, None, _lib.ptr(moff), _lib.ptr(mem), ctypes.c_int64(mem.size)))
-    return sizes, moff, mem
+    rows = _two_calls(_lib.lib().tip_delaunay_neighbors_f64, head, (sizes,), sizes, (np.int32,), members)
+    return (sizes, *rows) if members else sizes
 
 
 def delaunay_neighbors_dev(py_ptr, px_ptr, n, sizes_ptr, member_offsets_ptr=None, members_ptr=None, members_cap=0):
     """tip_delaunay_neighbors_f64_dev: device addresses, asynchronous on the calling thread's stream; no duplicate check."""
     _lib.check(_lib.lib().tip_delaunay_neighbors_f64_dev(
-        _lib.dptr(py_ptr or 0), _lib.dptr(px_ptr or 0), ctypes.c_int64(n), _lib.dptr(sizes_ptr or 0), _lib.dptr(member_offsets_ptr or 0),
-        _lib.dptr(members_ptr or 0), ctypes.c_int64(members_cap)))
+        _lib.dptr(py_ptr), _lib.dptr(px_ptr), ctypes.c_int64(n), _lib.dptr(sizes_ptr), _lib.dptr(member_offsets_ptr),
+        _lib.dptr(members_ptr), ctypes.c_int64(members_cap)))
 
 
 def psin(cy, cx, member_offsets, members, query=None, order=6):
@@ -523,8 +521,8 @@ def psin(cy, cx, member_offsets, members, query=None, order=6):
 
 def psin_dev(cy_ptr, cx_ptr, n, query_ptr, m, member_offsets_ptr, members_ptr, n_members, order, out_ptr):
     _lib.check(_lib.lib().tip_psin_f64_dev(
-        _lib.dptr(cy_ptr or 0), _lib.dptr(cx_ptr or 0), ctypes.c_int64(n), _lib.dptr(query_ptr or 0), ctypes.c_int64(m),
-        _lib.dptr(member_offsets_ptr or 0), _lib.dptr(members_ptr or 0), ctypes.c_int64(n_members), int(order), _lib.dptr(out_ptr or 0)))
+        _lib.dptr(cy_ptr), _lib.dptr(cx_ptr), ctypes.c_int64(n), _lib.dptr(query_ptr), ctypes.c_int64(m),
+        _lib.dptr(member_offsets_ptr), _lib.dptr(members_ptr), ctypes.c_int64(n_members), int(order), _lib.dptr(out_ptr)))
 
 
 def graph_neighbor_state(offsets, adj, member, state, query=None):
@@ -544,11 +542,11 @@ def graph_neighbor_state(offsets, adj, member, state, query=None):
 
 def graph_neighbor_state_dev(offsets_ptr, adj_ptr, n, n_adj, member_ptr, state_ptr, query_ptr, m, nb_sum_ptr, nb_cnt_ptr):
     _lib.check(_lib.lib().tip_graph_neighbor_state_f64_dev(
-        _lib.dptr(offsets_ptr or 0), _lib.dptr(adj_ptr or 0), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(member_ptr or 0),
-        _lib.dptr(state_ptr or 0), _lib.dptr(query_ptr or 0), ctypes.c_int64(m), _lib.dptr(nb_sum_ptr or 0), _lib.dptr(nb_cnt_ptr or 0)))
+        _lib.dptr(offsets_ptr), _lib.dptr(adj_ptr), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(member_ptr),
+        _lib.dptr(state_ptr), _lib.dptr(query_ptr), ctypes.c_int64(m), _lib.dptr(nb_sum_ptr), _lib.dptr(nb_cnt_ptr)))
 
 
 def order_features_dev(py_ptr, px_ptr, n, order, psi_ptr, degree_ptr):
     """tip_order_features_f64_dev: Delaunay degree (int64) and psi_order (float64) of n device points, left in device buffers."""
-    _lib.check(_lib.lib().tip_order_features_f64_dev(_lib.dptr(py_ptr or 0), _lib.dptr(px_ptr or 0), ctypes.c_int64(n), int(order),
-                                                     _lib.dptr(psi_ptr or 0), _lib.dptr(degree_ptr or 0)))
+    _lib.check(_lib.lib().tip_order_features_f64_dev(_lib.dptr(py_ptr), _lib.dptr(px_ptr), ctypes.c_int64(n), int(order),
+                                                     _lib.dptr(psi_ptr), _lib.dptr(degree_ptr)))

@@ -115,16 +115,13 @@ int tip_draw_cell_types_u8(const uint8_t *types, long n, int must_mask, int lack
     if (!c.stream) return TIP_ERR_HIP;
     if (!types || !pos_rgb || !neg_rgb || !out3 || n < 1 || must_mask < 0 || must_mask > 255 || lack_mask < 0 || lack_mask > 255)
         return fail(TIP_ERR_ARG, "tip_draw_cell_types_u8: bad arguments");
-    WsGuard ws;
-    uint8_t *dt = ws.get<uint8_t>((size_t)n);
-    double *dout = ws.get<double>((size_t)3 * n);
-    if (!dt || !dout) return TIP_ERR_NOMEM;
-    TIP_HIP(hipMemcpyAsync(dt, types, (size_t)n, hipMemcpyHostToDevice, c.stream));
-    TIP_LAUNCH("draw_cell_types", k_draw_cell_types, dim3(cdiv(n, 256)), dim3(256), 0, (const uint8_t *)dt, n, must_mask, lack_mask,
-               must_mask != 0 ? 1 : 0, pos_rgb[0], pos_rgb[1], pos_rgb[2], neg_rgb[0], neg_rgb[1], neg_rgb[2], dout);
-    TIP_HIP(hipMemcpyAsync(out3, dout, (size_t)3 * n * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    Staging st;
+    const uint8_t *dt = st.in(types, (size_t)n);
+    double *dout = st.out(out3, (size_t)3 * n);
+    if (st.rc) return st.rc;
+    TIP_LAUNCH("draw_cell_types", k_draw_cell_types, dim3(cdiv(n, 256)), dim3(256), 0, dt, n, must_mask, lack_mask, must_mask != 0 ? 1 : 0,
+               pos_rgb[0], pos_rgb[1], pos_rgb[2], neg_rgb[0], neg_rgb[1], neg_rgb[2], dout);
+    return st.finish();
 }
 
 int tip_draw_tracking_i32(const int32_t *track, long n, const double *cycle18, double *out3)
@@ -132,18 +129,15 @@ int tip_draw_tracking_i32(const int32_t *track, long n, const double *cycle18, d
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
     if (!track || !cycle18 || !out3 || n < 1) return fail(TIP_ERR_ARG, "tip_draw_tracking_i32: bad arguments");
-    WsGuard ws;
-    int32_t *dt = ws.get<int32_t>((size_t)n);
-    double *dout = ws.get<double>((size_t)3 * n);
-    if (!dt || !dout) return TIP_ERR_NOMEM;
     Cycle cyc;
     for (int k = 0; k < 6; ++k)
         for (int j = 0; j < 3; ++j) cyc.c[k][j] = cycle18[3 * k + j];
-    TIP_HIP(hipMemcpyAsync(dt, track, (size_t)n * 4, hipMemcpyHostToDevice, c.stream));
-    TIP_LAUNCH("draw_tracking", k_draw_tracking, dim3(cdiv(n, 256)), dim3(256), 0, (const int32_t *)dt, n, cyc, dout);
-    TIP_HIP(hipMemcpyAsync(out3, dout, (size_t)3 * n * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    Staging st;
+    const int32_t *dt = st.in(track, (size_t)n);
+    double *dout = st.out(out3, (size_t)3 * n);
+    if (st.rc) return st.rc;
+    TIP_LAUNCH("draw_tracking", k_draw_tracking, dim3(cdiv(n, 256)), dim3(256), 0, dt, n, cyc, dout);
+    return st.finish();
 }
 
 int tip_draw_disks_f64(int y, int x, int n, const double *cy, const double *cx, double radius, const double *rgb, double *out3)
@@ -153,20 +147,12 @@ int tip_draw_disks_f64(int y, int x, int n, const double *cy, const double *cx, 
     if (!out3 || y < 1 || x < 1 || n < 0 || (n > 0 && (!cy || !cx || !rgb)) || !(radius > 0.0))
         return fail(TIP_ERR_ARG, "tip_draw_disks_f64: bad arguments");
     const long P = (long)y * x;
-    WsGuard ws;
-    double *dcy = ws.get<double>((size_t)n + 1), *dcx = ws.get<double>((size_t)n + 1), *drgb = ws.get<double>((size_t)3 * n + 1);
-    double *dout = ws.get<double>((size_t)3 * P);
-    if (!dcy || !dcx || !drgb || !dout) return TIP_ERR_NOMEM;
-    if (n > 0) {
-        TIP_HIP(hipMemcpyAsync(dcy, cy, (size_t)n * 8, hipMemcpyHostToDevice, c.stream));
-        TIP_HIP(hipMemcpyAsync(dcx, cx, (size_t)n * 8, hipMemcpyHostToDevice, c.stream));
-        TIP_HIP(hipMemcpyAsync(drgb, rgb, (size_t)3 * n * 8, hipMemcpyHostToDevice, c.stream));
-    }
-    TIP_LAUNCH("draw_disks", k_draw_disks, dim3(cdiv(x, 256), y), dim3(256), 0, y, x, n, (const double *)dcy, (const double *)dcx, radius,
-               (const double *)drgb, dout);
-    TIP_HIP(hipMemcpyAsync(out3, dout, (size_t)3 * P * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    Staging st;
+    const double *dcy = st.in(cy, (size_t)n), *dcx = st.in(cx, (size_t)n), *drgb = st.in(rgb, (size_t)3 * n);
+    double *dout = st.out(out3, (size_t)3 * P);
+    if (st.rc) return st.rc;
+    TIP_LAUNCH("draw_disks", k_draw_disks, dim3(cdiv(x, 256), y), dim3(256), 0, y, x, n, dcy, dcx, radius, drgb, dout);
+    return st.finish();
 }
 
 int tip_draw_lines_f64(int y, int x, int n, const int32_t *ends, const double *rgb, double *out3)
@@ -175,20 +161,15 @@ int tip_draw_lines_f64(int y, int x, int n, const int32_t *ends, const double *r
     if (!c.stream) return TIP_ERR_HIP;
     if (!out3 || !rgb || y < 1 || x < 1 || n < 0 || (n > 0 && !ends)) return fail(TIP_ERR_ARG, "tip_draw_lines_f64: bad arguments");
     const long P = (long)y * x;
-    WsGuard ws;
-    int32_t *de = ws.get<int32_t>((size_t)4 * n + 4);
-    unsigned char *img = ws.get<unsigned char>((size_t)P);
-    double *dout = ws.get<double>((size_t)3 * P);
-    if (!de || !img || !dout) return TIP_ERR_NOMEM;
+    Staging st;
+    const int32_t *de = st.in(ends, (size_t)4 * n);
+    unsigned char *img = st.scratch<unsigned char>((size_t)P);
+    double *dout = st.out(out3, (size_t)3 * P);
+    if (st.rc) return st.rc;
     TIP_HIP(hipMemsetAsync(img, 0, (size_t)P, c.stream));
-    if (n > 0) {
-        TIP_HIP(hipMemcpyAsync(de, ends, (size_t)4 * n * 4, hipMemcpyHostToDevice, c.stream));
-        TIP_LAUNCH("draw_lines", k_draw_lines, dim3(cdiv(n, 256)), dim3(256), 0, y, x, n, (const int32_t *)de, img);
-    }
+    if (n > 0) TIP_LAUNCH("draw_lines", k_draw_lines, dim3(cdiv(n, 256)), dim3(256), 0, y, x, n, de, img);
     TIP_LAUNCH("draw_expand", k_draw_expand, dim3(cdiv(P, 256)), dim3(256), 0, (const unsigned char *)img, P, rgb[0], rgb[1], rgb[2], dout);
-    TIP_HIP(hipMemcpyAsync(out3, dout, (size_t)3 * P * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    return st.finish();
 }
 
 }  // extern "C"

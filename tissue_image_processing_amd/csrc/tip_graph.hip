@@ -1,15 +1,16 @@
 // tip_graph.hip -- the per-cell features that walk the cell neighbour graph (ti.py:1752-1791 calculate_n_neighbors_from_type,
-// 2513-2543 find_second_order_neighbors, 1065-1096 / 1844-1872 the contact-length loop).  The reference answers every table row
-// with pandas look-ups over Python sets; here the graph is a CSR adjacency (offsets int32[n + 1], adj int32[...] of 1-based
-// labels, ASCENDING within a row) and every feature is one launch over the query rows.
+// 2513-2543 find_second_order_neighbors, 1065-1096 / 1844-1872 the contact-length loop, 803-843 the neighbour sums behind
+// calculate_neighbors_correlation_function).  The reference answers every table row with pandas look-ups over Python sets; here
+// the graph is a CSR adjacency (offsets int32[n + 1], adj int32[...] of 1-based labels, ASCENDING within a row) and every feature
+// is one launch over the query rows.  tip_csr.h has the pieces shared with tip_order.hip: label_ok / row_of / row_find, the
+// rank-sort kernel and the host checks of a CSR.
 //
-//   k_csr_count / k_scan_i32 / k_csr_fill / k_csr_sort
+//   k_csr_count / k_scan_i32 / k_csr_fill / k_rank_sort ("csr_sort")
 //                    the CSR from the unique (hi, lo) pairs of tip_neighbor_pairs_i32: a pair gives both directions when
 //                    working[hi - 1] is set (or working is NULL) -- upstream's find_neighbors visits working cells only and finds
 //                    a pair from its larger label (ti.py:1827-1838).  Degrees with atomicAdd, one workgroup's exclusive scan,
 //                    slots handed out with atomicAdd into a scratch copy, then one wavefront per row ranks the row's entries
-//                    (lanes stride over the row in chunks of 64, so a hub row longer than a wavefront takes several chunks) and
-//                    writes them in ascending order.  A pair with a label outside 1..n takes no part.
+//                    and writes them in ascending order.  A pair with a label outside 1..n takes no part.
 //   k_graph_counts   one thread per query row: degree, or the neighbours that pass valid / empty / type tests.
 //   k_graph_second   one wavefront per query row i: for every intermediate j in N(i) with valid[j] == 1 the lanes stride over
 //                    N(j); a candidate k counts when k != i, valid[k] == 1, it passes the selector and NO earlier qualifying
@@ -21,39 +22,16 @@
 //                    pair is no edge is dropped (upstream asks about members of `neighbors` only).
 //   k_contact_sums   one thread per query row: the sum of the weights of the selected neighbours, their number and, for the
 //                    histogram, the per-edge values in CSR form.
+//   k_neighbor_state one thread per query row: sum of state[j] (__dadd_rn, in row order) and number of the neighbours j with
+//                    member[j].  It searches no row, so its host form does not ask for ascending rows.
 // Every read of adj is clamped to n_adj and every label is checked against 1..n, so a malformed device CSR gives wrong numbers,
-// never an access outside the caller's arrays; the host forms check their CSR before it is uploaded.
-#include "tip_internal.h"
+// never an access outside the caller's arrays; the host forms check their CSR before it is uploaded (Staging, tip_internal.h).
+#include "tip_csr.h"
 #include "tip_typesel.h"
 
 namespace tip {
 
 constexpr int G_ALL = TIP_GRAPH_ALL, G_VALID = TIP_GRAPH_VALID, G_INVALID = TIP_GRAPH_INVALID, G_TYPE = TIP_GRAPH_TYPE;
-constexpr int G_WAVE = 64, G_BLOCK = 256, G_WPB = G_BLOCK / G_WAVE;
-
-__device__ __forceinline__ bool label_ok(int l, int n) { return (unsigned)(l - 1) < (unsigned)n; }
-
-// row r of the CSR, clamped to [0, n_adj]
-__device__ __forceinline__ void row_of(const int32_t *__restrict__ offsets, int r, long n_adj, int &b, int &e)
-{
-    b = offsets[r];
-    e = offsets[r + 1];
-    if (b < 0) b = 0;
-    if (e > n_adj) e = (int)n_adj;
-    if (e < b) e = b;
-}
-
-// position of label k in the ascending row [b, e) of adj, or -1
-__device__ __forceinline__ int row_find(const int32_t *__restrict__ adj, int b, int e, int k)
-{
-    while (b < e) {
-        const int mid = b + ((e - b) >> 1), v = adj[mid];
-        if (v == k) return mid;
-        if (v < k) b = mid + 1;
-        else e = mid;
-    }
-    return -1;
-}
 
 __device__ __forceinline__ bool pair_takes_part(const int32_t *__restrict__ pairs, long p, int n, const uint8_t *__restrict__ working,
                                                 int &hi, int &lo)
@@ -117,26 +95,6 @@ __global__ void k_csr_fill(const int32_t *__restrict__ pairs, long np, int n, co
     if (b >= 0 && b < raw_cap) raw[b] = hi;
 }
 
-// one wavefront per row: entry i goes to the row's slot number (entries below it); a row that does not fit adj is left out
-// (the entry point reports the overflow)
-__global__ __launch_bounds__(G_BLOCK) void k_csr_sort(const int32_t *__restrict__ offsets, const int32_t *__restrict__ raw, long raw_cap,
-                                                      int32_t *__restrict__ adj, int n, long cap)
-{
-    const int row = blockIdx.x * G_WPB + (threadIdx.x >> 6), lane = threadIdx.x & (G_WAVE - 1);
-    if (row >= n) return;
-    const int b = offsets[row], e = offsets[row + 1];
-    if (b < 0 || e < b || e > cap || e > raw_cap) return;
-    for (int i = b + lane; i < e; i += G_WAVE) {
-        const int v = raw[i];
-        int rank = 0;
-        for (int j = b; j < e; ++j) {
-            const int w = raw[j];
-            rank += (w < v || (w == v && j < i)) ? 1 : 0;
-        }
-        adj[b + rank] = v;
-    }
-}
-
 __global__ void k_graph_counts(const int32_t *__restrict__ offsets, const int32_t *__restrict__ adj, int n, long n_adj,
                                const uint8_t *__restrict__ valid, const uint8_t *__restrict__ empty, const uint8_t *__restrict__ type,
                                const int32_t *__restrict__ query, long m, int mode, int sel_kind, int bit, int64_t *__restrict__ out)
@@ -159,14 +117,14 @@ __global__ void k_graph_counts(const int32_t *__restrict__ offsets, const int32_
     out[q] = cnt;
 }
 
-__global__ __launch_bounds__(G_BLOCK) void k_graph_second(const int32_t *__restrict__ offsets, const int32_t *__restrict__ adj, int n, long n_adj,
+__global__ __launch_bounds__(CSR_BLOCK) void k_graph_second(const int32_t *__restrict__ offsets, const int32_t *__restrict__ adj, int n, long n_adj,
                                                           const uint8_t *__restrict__ valid, const uint8_t *__restrict__ type,
                                                           const int32_t *__restrict__ query, long m, int sel_kind, int bit,
                                                           int64_t *__restrict__ sizes, const int64_t *__restrict__ member_offsets,
                                                           int32_t *__restrict__ members, long members_cap)
 {
-    const long q = (long)blockIdx.x * G_WPB + (threadIdx.x >> 6);      // the same for every lane of a wavefront
-    const int lane = threadIdx.x & (G_WAVE - 1);
+    const long q = (long)blockIdx.x * CSR_WPB + (threadIdx.x >> 6);      // the same for every lane of a wavefront
+    const int lane = threadIdx.x & (CSR_WAVE - 1);
     if (q >= m) return;
     const long r = query ? (long)query[q] : q;
     if (r < 0 || r >= n) {
@@ -183,7 +141,7 @@ __global__ __launch_bounds__(G_BLOCK) void k_graph_second(const int32_t *__restr
         if ((unsigned)j >= (unsigned)n || valid[j] != 1) continue;
         int jb, je;
         row_of(offsets, j, n_adj, jb, je);
-        for (int kb = jb; kb < je; kb += G_WAVE) {
+        for (int kb = jb; kb < je; kb += CSR_WAVE) {
             const int a = kb + lane;
             bool take = false;
             int k = 0;
@@ -265,74 +223,27 @@ __global__ void k_contact_sums(const int32_t *__restrict__ offsets, const int32_
     if (n_sel) n_sel[q] = cnt;
 }
 
-// ---- argument checks shared by the host and the device forms -----------------------------------------------------------------
-static int check_graph(const char *who, const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, int64_t m)
+__global__ void k_neighbor_state(const int32_t *__restrict__ offsets, const int32_t *__restrict__ adj, int n, long n_adj,
+                                 const uint8_t *__restrict__ member, const double *__restrict__ state, const int32_t *__restrict__ query,
+                                 long m, double *__restrict__ nb_sum, int64_t *__restrict__ nb_cnt)
 {
-    if (n < 0 || n > 0x7ffffffe || m < 0) return fail(TIP_ERR_ARG, "%s: n = %ld rows, m = %ld queries", who, (long)n, (long)m);
-    if (n_adj < 0 || n_adj > 0x7fffffff) return fail(TIP_ERR_ARG, "%s: n_adj = %ld", who, (long)n_adj);
-    if (!offsets || (n_adj > 0 && !adj)) return fail(TIP_ERR_ARG, "%s: the CSR arrays (offsets, adj)", who);
-    return TIP_OK;
-}
-
-static int check_selector(const char *who, int mode, int sel_bit, int sel_positive, int &sel_kind)
-{
-    sel_kind = 0;
-    if (mode != G_TYPE) return TIP_OK;
-    if (sel_bit < 0 || sel_bit > 7) return fail(TIP_ERR_ARG, "%s: type bit %d (0..7)", who, sel_bit);
-    sel_kind = sel_positive ? 1 : 2;
-    return TIP_OK;
-}
-
-// a HOST CSR and query list, before they are uploaded: monotone offsets that end at n_adj, labels in 1..n ascending in a row,
-// queries below n (NULL: query q is row q, so m <= n)
-static int check_host_graph(const char *who, const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const int32_t *query,
-                            int64_t m)
-{
-    if (offsets[0] != 0 || offsets[n] != n_adj) return fail(TIP_ERR_ARG, "%s: offsets run from %d to %d, adj has %ld entries", who, offsets[0], offsets[n], (long)n_adj);
-    for (int64_t r = 0; r < n; ++r) {
-        if (offsets[r + 1] < offsets[r]) return fail(TIP_ERR_ARG, "%s: offsets decrease at row %ld", who, (long)r);
-        for (int a = offsets[r]; a < offsets[r + 1]; ++a) {
-            if (adj[a] < 1 || adj[a] > n) return fail(TIP_ERR_ARG, "%s: row %ld holds label %d (1..%ld)", who, (long)r, adj[a], (long)n);
-            if (a > offsets[r] && adj[a] <= adj[a - 1]) return fail(TIP_ERR_ARG, "%s: row %ld is not ascending", who, (long)r);
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= m) return;
+    const long r = query ? (long)query[q] : q;
+    double sum = 0.0;
+    int64_t cnt = 0;
+    if (r >= 0 && r < n) {
+        int b, e;
+        row_of(offsets, (int)r, n_adj, b, e);
+        for (int a = b; a < e; ++a) {
+            const int j = adj[a] - 1;
+            if ((unsigned)j >= (unsigned)n || member[j] == 0) continue;
+            sum = __dadd_rn(sum, state[j]);
+            ++cnt;
         }
-    }
-    if (!query && m > n) return fail(TIP_ERR_ARG, "%s: %ld queries of %ld rows", who, (long)m, (long)n);
-    for (int64_t q = 0; query && q < m; ++q)
-        if (query[q] < 0 || query[q] >= n) return fail(TIP_ERR_ARG, "%s: query %ld is row %d of %ld", who, (long)q, query[q], (long)n);
-    return TIP_OK;
-}
-
-// the device copies of a host graph (CSR, per-row bytes, queries); a NULL host array stays NULL
-struct DevGraph {
-    int32_t *offsets = nullptr, *adj = nullptr, *query = nullptr;
-    uint8_t *valid = nullptr, *empty = nullptr, *type = nullptr;
-};
-
-template <typename T> static int upload(WsGuard &ws, const T *host, size_t count, T *&dev)
-{
-    dev = nullptr;
-    if (!host) return TIP_OK;
-    dev = ws.get<T>(count);
-    if (!dev) return TIP_ERR_NOMEM;
-    if (count) TIP_HIP(hipMemcpyAsync(dev, host, count * sizeof(T), hipMemcpyHostToDevice, ctx().stream));
-    return TIP_OK;
-}
-
-static int upload_graph(WsGuard &ws, const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid,
-                        const uint8_t *empty, const uint8_t *type, const int32_t *query, int64_t m, DevGraph &g)
-{
-    if (int rc = upload(ws, offsets, (size_t)n + 1, g.offsets)) return rc;
-    if (int rc = upload(ws, adj, (size_t)n_adj, g.adj)) return rc;
-    if (int rc = upload(ws, valid, (size_t)n, g.valid)) return rc;
-    if (int rc = upload(ws, empty, (size_t)n, g.empty)) return rc;
-    if (int rc = upload(ws, type, (size_t)n, g.type)) return rc;
-    return upload(ws, query, (size_t)m, g.query);
-}
-
-template <typename T> static int download(T *host, const T *dev, size_t count)
-{
-    if (host && count) TIP_HIP(hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx().stream));
-    return TIP_OK;
+    } else cnt = -1;
+    nb_sum[q] = sum;
+    nb_cnt[q] = cnt;
 }
 
 // ---- CSR ------------------------------------------------------------------------------------------------------------------------
@@ -354,7 +265,7 @@ static int neighbor_csr_dev(const char *who, const int32_t *pairs, int64_t np, i
     if (!deg || !raw) return TIP_ERR_NOMEM;
     if (n) TIP_HIP(hipMemsetAsync(deg, 0, (size_t)n * 4, c.stream));
     if (np && n) TIP_LAUNCH("csr_count", k_csr_count, dim3(cdiv(np, 256)), dim3(256), 0, pairs, (long)np, (int)n, working, deg);
-    TIP_LAUNCH("csr_scan", k_scan_i32, dim3(1), dim3(1024), 0, (const int32_t *)deg, offsets, (int)n);
+    if (int rc = scan_i32_dev(deg, offsets, (int)n)) return rc;
     if (n_adj_host) {
         int32_t total = 0;
         TIP_HIP(hipMemcpyAsync(&total, offsets + n, 4, hipMemcpyDeviceToHost, c.stream));
@@ -366,35 +277,35 @@ static int neighbor_csr_dev(const char *who, const int32_t *pairs, int64_t np, i
         TIP_HIP(hipMemsetAsync(deg, 0, (size_t)n * 4, c.stream));
         TIP_LAUNCH("csr_fill", k_csr_fill, dim3(cdiv(np, 256)), dim3(256), 0, pairs, (long)np, (int)n, working, (const int32_t *)offsets, deg,
                    raw, (long)raw_cap);
-        TIP_LAUNCH("csr_sort", k_csr_sort, dim3(cdiv(n, G_WPB)), dim3(G_BLOCK), 0, (const int32_t *)offsets, (const int32_t *)raw,
-                   (long)raw_cap, adj, (int)n, (long)cap);
+        TIP_LAUNCH("csr_sort", k_rank_sort<int32_t>, dim3(cdiv(n, CSR_WPB)), dim3(CSR_BLOCK), 0, (const int32_t *)offsets, (const int32_t *)nullptr,
+                   (const int32_t *)raw, (long)raw_cap, adj, (int)n, (long)cap, 0);
     }
     return TIP_OK;
 }
 
 // ---- launches on device arrays (arguments checked by the entry points) ------------------------------------------------------------
 static int graph_counts_launch(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid, const uint8_t *empty,
-                               const uint8_t *type, const int32_t *query, int64_t m, int mode, int sel_kind, int bit, int64_t *out)
+                               const uint8_t *type, const int32_t *query, int64_t m, int mode, Selector sel, int64_t *out)
 {
     if (m == 0) return TIP_OK;
     TIP_LAUNCH("graph_counts", k_graph_counts, dim3(cdiv(m, 256)), dim3(256), 0, offsets, adj, (int)n, (long)n_adj, valid, empty, type, query,
-               (long)m, mode, sel_kind, bit, out);
+               (long)m, mode, sel.kind, sel.bit, out);
     return TIP_OK;
 }
 
 static int graph_second_launch(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid, const uint8_t *type,
-                               const int32_t *query, int64_t m, int sel_kind, int bit, int64_t *sizes, const int64_t *member_offsets,
+                               const int32_t *query, int64_t m, Selector sel, int64_t *sizes, const int64_t *member_offsets,
                                int32_t *members, int64_t members_cap)
 {
     if (m == 0) return TIP_OK;
-    TIP_LAUNCH("graph_second", k_graph_second, dim3(cdiv(m, G_WPB)), dim3(G_BLOCK), 0, offsets, adj, (int)n, (long)n_adj, valid, type, query,
-               (long)m, sel_kind, bit, sizes, member_offsets, members, (long)members_cap);
+    TIP_LAUNCH("graph_second", k_graph_second, dim3(cdiv(m, CSR_WPB)), dim3(CSR_BLOCK), 0, offsets, adj, (int)n, (long)n_adj, valid, type, query,
+               (long)m, sel.kind, sel.bit, sizes, member_offsets, members, (long)members_cap);
     return TIP_OK;
 }
 
 static int contact_sums_launch(const int32_t *pairs, const int64_t *counts, int64_t nt, const int32_t *offsets, const int32_t *adj, int64_t n,
                                int64_t n_adj, const uint8_t *valid, const uint8_t *type, const int32_t *query, int64_t m, int mode,
-                               int sel_kind, int bit, int64_t *sums, int64_t *n_sel, const int64_t *value_offsets, int64_t *values,
+                               Selector sel, int64_t *sums, int64_t *n_sel, const int64_t *value_offsets, int64_t *values,
                                int32_t *value_labels, int64_t values_cap)
 {
     if (m == 0) return TIP_OK;
@@ -406,16 +317,27 @@ static int contact_sums_launch(const int32_t *pairs, const int64_t *counts, int6
         TIP_LAUNCH("edge_weights", k_edge_weights, dim3(cdiv(nt, 256)), dim3(256), 0, pairs, counts, (long)nt, offsets, adj, (int)n, (long)n_adj,
                    weight);
     TIP_LAUNCH("contact_sums", k_contact_sums, dim3(cdiv(m, 256)), dim3(256), 0, offsets, adj, (const int64_t *)weight, (int)n, (long)n_adj, valid,
-               type, query, (long)m, mode, sel_kind, bit, sums, n_sel, value_offsets, values, value_labels, (long)values_cap);
+               type, query, (long)m, mode, sel.kind, sel.bit, sums, n_sel, value_offsets, values, value_labels, (long)values_cap);
     return TIP_OK;
 }
 
+static int neighbor_state_launch(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *member, const double *state,
+                                 const int32_t *query, int64_t m, double *nb_sum, int64_t *nb_cnt)
+{
+    if (m == 0) return TIP_OK;
+    TIP_LAUNCH("neighbor_state", k_neighbor_state, dim3(cdiv(m, 256)), dim3(256), 0, offsets, adj, (int)n, (long)n_adj, member, state, query, (long)m,
+               nb_sum, nb_cnt);
+    return TIP_OK;
+}
+
+// ---- argument checks shared by the host and the device forms -----------------------------------------------------------------
 static int check_counts_args(const char *who, const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid,
-                             const uint8_t *type, int64_t m, int mode, int sel_bit, int sel_positive, const int64_t *out, int &sel_kind)
+                             const uint8_t *type, int64_t m, int mode, int sel_bit, int sel_positive, const int64_t *out, Selector &sel)
 {
     if (int rc = check_graph(who, offsets, adj, n, n_adj, m)) return rc;
     if (mode < G_ALL || mode > G_TYPE) return fail(TIP_ERR_ARG, "%s: mode %d (0 all, 1 valid, 2 invalid, 3 type)", who, mode);
-    if (int rc = check_selector(who, mode, sel_bit, sel_positive, sel_kind)) return rc;
+    if (mode == G_TYPE)
+        if (int rc = parse_selector(who, sel_bit, sel_positive, false, sel)) return rc;
     if (n > 0 && ((mode != G_ALL && !valid) || (mode == G_TYPE && !type))) return fail(TIP_ERR_ARG, "%s: mode %d needs the valid / type bytes", who, mode);
     if (m > 0 && !out) return fail(TIP_ERR_ARG, "%s: no output", who);
     return TIP_OK;
@@ -423,12 +345,11 @@ static int check_counts_args(const char *who, const int32_t *offsets, const int3
 
 static int check_second_args(const char *who, const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid,
                              const uint8_t *type, int64_t m, int sel_bit, int sel_positive, const int64_t *sizes, const int64_t *member_offsets,
-                             const int32_t *members, int64_t members_cap, int &sel_kind)
+                             const int32_t *members, int64_t members_cap, Selector &sel)
 {
     if (int rc = check_graph(who, offsets, adj, n, n_adj, m)) return rc;
-    if (sel_bit < -1 || sel_bit > 7) return fail(TIP_ERR_ARG, "%s: type bit %d (0..7, or -1 for no selector)", who, sel_bit);
-    sel_kind = sel_bit < 0 ? 0 : (sel_positive ? 1 : 2);
-    if (n > 0 && (!valid || (sel_kind && !type))) return fail(TIP_ERR_ARG, "%s: the valid / type bytes", who);
+    if (int rc = parse_selector(who, sel_bit, sel_positive, true, sel)) return rc;
+    if (n > 0 && (!valid || (sel.kind && !type))) return fail(TIP_ERR_ARG, "%s: the valid / type bytes", who);
     if (m > 0 && !sizes && !members) return fail(TIP_ERR_ARG, "%s: no output", who);
     if (members && (!member_offsets || members_cap < 0)) return fail(TIP_ERR_ARG, "%s: members need member_offsets and a capacity", who);
     return TIP_OK;
@@ -437,16 +358,41 @@ static int check_second_args(const char *who, const int32_t *offsets, const int3
 static int check_contact_args(const char *who, const int32_t *pairs, const int64_t *counts, int64_t nt, const int32_t *offsets, const int32_t *adj,
                               int64_t n, int64_t n_adj, const uint8_t *valid, const uint8_t *type, int64_t m, int mode, int sel_bit,
                               int sel_positive, const int64_t *sums, const int64_t *n_sel, const int64_t *value_offsets, const int64_t *values,
-                              const int32_t *value_labels, int64_t values_cap, int &sel_kind)
+                              const int32_t *value_labels, int64_t values_cap, Selector &sel)
 {
     if (int rc = check_graph(who, offsets, adj, n, n_adj, m)) return rc;
     if (nt < 0 || nt > 0x7fffffff || (nt > 0 && (!pairs || !counts))) return fail(TIP_ERR_ARG, "%s: the contact triples (%ld)", who, (long)nt);
     if (mode != G_ALL && mode != G_VALID && mode != G_TYPE) return fail(TIP_ERR_ARG, "%s: mode %d (0 all, 1 valid, 3 type)", who, mode);
-    if (int rc = check_selector(who, mode, sel_bit, sel_positive, sel_kind)) return rc;
+    if (mode == G_TYPE)
+        if (int rc = parse_selector(who, sel_bit, sel_positive, false, sel)) return rc;
     if (n > 0 && ((mode == G_VALID && !valid) || (mode == G_TYPE && !type))) return fail(TIP_ERR_ARG, "%s: mode %d needs the valid / type bytes", who, mode);
     if (m > 0 && !sums && !n_sel && !values) return fail(TIP_ERR_ARG, "%s: no output", who);
     if ((values || value_labels) && (!values || !value_offsets || values_cap < 0))
         return fail(TIP_ERR_ARG, "%s: per-edge values need value_offsets and a capacity", who);
+    return TIP_OK;
+}
+
+static int check_state_args(const char *who, const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *member,
+                            const double *state, int64_t m, const double *nb_sum, const int64_t *nb_cnt)
+{
+    if (int rc = check_graph(who, offsets, adj, n, n_adj, m)) return rc;
+    if ((n > 0 && (!member || !state)) || (m > 0 && (!nb_sum || !nb_cnt))) return fail(TIP_ERR_ARG, "%s: null pointer", who);
+    return TIP_OK;
+}
+
+// a host CSR whose rows are searched: sound and ascending
+static int check_sorted_host_graph(const char *who, const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const int32_t *query,
+                                   int64_t m)
+{
+    if (int rc = check_host_graph(who, offsets, adj, n, n_adj, query, m)) return rc;
+    return check_rows_ascend(who, offsets, adj, n);
+}
+
+// the capacity offsets of a two-call entry's second call (member_offsets, value_offsets), checked on the host
+static int check_host_offsets(const char *who, const char *name, const int64_t *off, int64_t m, int64_t cap)
+{
+    for (int64_t q = 0; q < m; ++q)
+        if (off[q] < 0 || off[q] > cap) return fail(TIP_ERR_ARG, "%s: %s[%ld] = %ld, capacity %ld", who, name, (long)q, (long)off[q], (long)cap);
     return TIP_OK;
 }
 
@@ -472,17 +418,14 @@ int tip_neighbor_csr_i32(const int32_t *pairs, int64_t n_pairs, int64_t n, const
     if (!c.stream) return TIP_ERR_HIP;
     if (int rc = check_csr_args("tip_neighbor_csr_i32", pairs, n_pairs, n, offsets, adj, cap)) return rc;
     if (!n_adj) return fail(TIP_ERR_ARG, "tip_neighbor_csr_i32: n_adj is NULL");
-    WsGuard ws;
-    int32_t *dp = nullptr, *doff = ws.get<int32_t>((size_t)n + 1), *dadj = ws.get<int32_t>((size_t)cap);
-    uint8_t *dw = nullptr;
-    if (!doff || !dadj) return TIP_ERR_NOMEM;
-    if (int rc = upload(ws, pairs, (size_t)2 * n_pairs, dp)) return rc;
-    if (int rc = upload(ws, working, (size_t)n, dw)) return rc;
+    Staging st;
+    int32_t *doff = st.out(offsets, (size_t)n + 1), *dadj = st.out(adj, (size_t)cap);
+    const int32_t *dp = st.in(pairs, (size_t)2 * n_pairs);
+    const uint8_t *dw = st.in(working, (size_t)n);
+    if (st.rc) return st.rc;
     if (int rc = neighbor_csr_dev("tip_neighbor_csr_i32", dp, n_pairs, n, dw, doff, dadj, cap, n_adj)) return rc;
-    if (int rc = download(offsets, (const int32_t *)doff, (size_t)n + 1)) return rc;
-    if (int rc = download(adj, (const int32_t *)dadj, (size_t)*n_adj)) return rc;
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    st.set_count(dadj, (size_t)*n_adj);
+    return st.finish();
 }
 
 int tip_graph_counts_i32_dev(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid, const uint8_t *empty,
@@ -490,10 +433,10 @@ int tip_graph_counts_i32_dev(const int32_t *offsets, const int32_t *adj, int64_t
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    int sel_kind = 0;
-    if (int rc = check_counts_args("tip_graph_counts_i32_dev", offsets, adj, n, n_adj, valid, type, m, mode, sel_bit, sel_positive, out, sel_kind))
+    Selector sel;
+    if (int rc = check_counts_args("tip_graph_counts_i32_dev", offsets, adj, n, n_adj, valid, type, m, mode, sel_bit, sel_positive, out, sel))
         return rc;
-    return graph_counts_launch(offsets, adj, n, n_adj, valid, empty, type, query, m, mode, sel_kind, sel_bit, out);
+    return graph_counts_launch(offsets, adj, n, n_adj, valid, empty, type, query, m, mode, sel, out);
 }
 
 int tip_graph_counts_i32(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid, const uint8_t *empty,
@@ -501,19 +444,17 @@ int tip_graph_counts_i32(const int32_t *offsets, const int32_t *adj, int64_t n, 
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    int sel_kind = 0;
-    if (int rc = check_counts_args("tip_graph_counts_i32", offsets, adj, n, n_adj, valid, type, m, mode, sel_bit, sel_positive, out, sel_kind)) return rc;
-    if (int rc = check_host_graph("tip_graph_counts_i32", offsets, adj, n, n_adj, query, m)) return rc;
+    Selector sel;
+    if (int rc = check_counts_args("tip_graph_counts_i32", offsets, adj, n, n_adj, valid, type, m, mode, sel_bit, sel_positive, out, sel)) return rc;
+    if (int rc = check_sorted_host_graph("tip_graph_counts_i32", offsets, adj, n, n_adj, query, m)) return rc;
     if (m == 0) return TIP_OK;
-    WsGuard ws;
-    DevGraph g;
-    if (int rc = upload_graph(ws, offsets, adj, n, n_adj, valid, empty, type, query, m, g)) return rc;
-    int64_t *dout = ws.get<int64_t>((size_t)m);
-    if (!dout) return TIP_ERR_NOMEM;
-    if (int rc = graph_counts_launch(g.offsets, g.adj, n, n_adj, g.valid, g.empty, g.type, g.query, m, mode, sel_kind, sel_bit, dout)) return rc;
-    if (int rc = download(out, (const int64_t *)dout, (size_t)m)) return rc;
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    Staging st;
+    const int32_t *doff = st.in(offsets, (size_t)n + 1), *dadj = st.in(adj, (size_t)n_adj), *dq = st.in(query, (size_t)m);
+    const uint8_t *dvalid = st.in(valid, (size_t)n), *dempty = st.in(empty, (size_t)n), *dtype = st.in(type, (size_t)n);
+    int64_t *dout = st.out(out, (size_t)m);
+    if (st.rc) return st.rc;
+    if (int rc = graph_counts_launch(doff, dadj, n, n_adj, dvalid, dempty, dtype, dq, m, mode, sel, dout)) return rc;
+    return st.finish();
 }
 
 int tip_graph_second_i32_dev(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid, const uint8_t *type,
@@ -522,12 +463,11 @@ int tip_graph_second_i32_dev(const int32_t *offsets, const int32_t *adj, int64_t
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    int sel_kind = 0;
+    Selector sel;
     if (int rc = check_second_args("tip_graph_second_i32_dev", offsets, adj, n, n_adj, valid, type, m, sel_bit, sel_positive, sizes, member_offsets,
-                                   members, members_cap, sel_kind))
+                                   members, members_cap, sel))
         return rc;
-    return graph_second_launch(offsets, adj, n, n_adj, valid, type, query, m, sel_kind, sel_bit < 0 ? 0 : sel_bit, sizes, member_offsets, members,
-                               members_cap);
+    return graph_second_launch(offsets, adj, n, n_adj, valid, type, query, m, sel, sizes, member_offsets, members, members_cap);
 }
 
 int tip_graph_second_i32(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *valid, const uint8_t *type,
@@ -536,30 +476,23 @@ int tip_graph_second_i32(const int32_t *offsets, const int32_t *adj, int64_t n, 
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    int sel_kind = 0;
+    Selector sel;
     if (int rc = check_second_args("tip_graph_second_i32", offsets, adj, n, n_adj, valid, type, m, sel_bit, sel_positive, sizes, member_offsets,
-                                   members, members_cap, sel_kind))
+                                   members, members_cap, sel))
         return rc;
-    if (int rc = check_host_graph("tip_graph_second_i32", offsets, adj, n, n_adj, query, m)) return rc;
+    if (int rc = check_sorted_host_graph("tip_graph_second_i32", offsets, adj, n, n_adj, query, m)) return rc;
     if (m == 0) return TIP_OK;
-    for (int64_t q = 0; members && q < m; ++q)
-        if (member_offsets[q] < 0 || member_offsets[q] > members_cap)
-            return fail(TIP_ERR_ARG, "tip_graph_second_i32: member_offsets[%ld] = %ld, capacity %ld", (long)q, (long)member_offsets[q], (long)members_cap);
-    WsGuard ws;
-    DevGraph g;
-    if (int rc = upload_graph(ws, offsets, adj, n, n_adj, valid, nullptr, type, query, m, g)) return rc;
-    int64_t *dsizes = ws.get<int64_t>((size_t)m), *dmoff = nullptr;
-    int32_t *dmem = members ? ws.get<int32_t>((size_t)members_cap) : nullptr;
-    if (!dsizes || (members && !dmem)) return TIP_ERR_NOMEM;
-    if (int rc = upload(ws, member_offsets, (size_t)m, dmoff)) return rc;
-    if (dmem && members_cap) TIP_HIP(hipMemsetAsync(dmem, 0, (size_t)members_cap * 4, c.stream));
-    if (int rc = graph_second_launch(g.offsets, g.adj, n, n_adj, g.valid, g.type, g.query, m, sel_kind, sel_bit < 0 ? 0 : sel_bit, dsizes, dmoff, dmem,
-                                     members_cap))
-        return rc;
-    if (int rc = download(sizes, (const int64_t *)dsizes, (size_t)m)) return rc;
-    if (int rc = download(members, (const int32_t *)dmem, (size_t)members_cap)) return rc;
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    if (members)
+        if (int rc = check_host_offsets("tip_graph_second_i32", "member_offsets", member_offsets, m, members_cap)) return rc;
+    Staging st;
+    const int32_t *doff = st.in(offsets, (size_t)n + 1), *dadj = st.in(adj, (size_t)n_adj), *dq = st.in(query, (size_t)m);
+    const uint8_t *dvalid = st.in(valid, (size_t)n), *dtype = st.in(type, (size_t)n);
+    const int64_t *dmoff = st.in(member_offsets, (size_t)m);
+    int64_t *dsizes = st.out(sizes, (size_t)m);
+    int32_t *dmem = st.out(members, (size_t)members_cap, true);
+    if (st.rc) return st.rc;
+    if (int rc = graph_second_launch(doff, dadj, n, n_adj, dvalid, dtype, dq, m, sel, dsizes, dmoff, dmem, members_cap)) return rc;
+    return st.finish();
 }
 
 int tip_contact_sums_i32_dev(const int32_t *pairs, const int64_t *counts, int64_t n_triples, const int32_t *offsets, const int32_t *adj, int64_t n,
@@ -569,12 +502,12 @@ int tip_contact_sums_i32_dev(const int32_t *pairs, const int64_t *counts, int64_
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    int sel_kind = 0;
+    Selector sel;
     if (int rc = check_contact_args("tip_contact_sums_i32_dev", pairs, counts, n_triples, offsets, adj, n, n_adj, valid, type, m, mode, sel_bit,
-                                    sel_positive, sums, n_sel, value_offsets, values, value_labels, values_cap, sel_kind))
+                                    sel_positive, sums, n_sel, value_offsets, values, value_labels, values_cap, sel))
         return rc;
-    return contact_sums_launch(pairs, counts, n_triples, offsets, adj, n, n_adj, valid, type, query, m, mode, sel_kind, sel_bit, sums, n_sel,
-                               value_offsets, values, value_labels, values_cap);
+    return contact_sums_launch(pairs, counts, n_triples, offsets, adj, n, n_adj, valid, type, query, m, mode, sel, sums, n_sel, value_offsets, values,
+                               value_labels, values_cap);
 }
 
 int tip_contact_sums_i32(const int32_t *pairs, const int64_t *counts, int64_t n_triples, const int32_t *offsets, const int32_t *adj, int64_t n,
@@ -584,35 +517,54 @@ int tip_contact_sums_i32(const int32_t *pairs, const int64_t *counts, int64_t n_
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    int sel_kind = 0;
+    Selector sel;
     if (int rc = check_contact_args("tip_contact_sums_i32", pairs, counts, n_triples, offsets, adj, n, n_adj, valid, type, m, mode, sel_bit, sel_positive,
-                                    sums, n_sel, value_offsets, values, value_labels, values_cap, sel_kind))
+                                    sums, n_sel, value_offsets, values, value_labels, values_cap, sel))
         return rc;
-    if (int rc = check_host_graph("tip_contact_sums_i32", offsets, adj, n, n_adj, query, m)) return rc;
+    if (int rc = check_sorted_host_graph("tip_contact_sums_i32", offsets, adj, n, n_adj, query, m)) return rc;
     if (m == 0) return TIP_OK;
-    for (int64_t q = 0; values && q < m; ++q)
-        if (value_offsets[q] < 0 || value_offsets[q] > values_cap)
-            return fail(TIP_ERR_ARG, "tip_contact_sums_i32: value_offsets[%ld] = %ld, capacity %ld", (long)q, (long)value_offsets[q], (long)values_cap);
-    WsGuard ws;
-    DevGraph g;
-    if (int rc = upload_graph(ws, offsets, adj, n, n_adj, valid, nullptr, type, query, m, g)) return rc;
-    int32_t *dp = nullptr, *dlab = value_labels ? ws.get<int32_t>((size_t)values_cap) : nullptr;
-    int64_t *dc = nullptr, *dvoff = nullptr, *dsum = ws.get<int64_t>((size_t)2 * m), *dval = values ? ws.get<int64_t>((size_t)values_cap) : nullptr;
-    if (!dsum || (values && !dval) || (value_labels && !dlab)) return TIP_ERR_NOMEM;
-    if (int rc = upload(ws, pairs, (size_t)2 * n_triples, dp)) return rc;
-    if (int rc = upload(ws, counts, (size_t)n_triples, dc)) return rc;
-    if (int rc = upload(ws, value_offsets, (size_t)m, dvoff)) return rc;
-    if (dval && values_cap) TIP_HIP(hipMemsetAsync(dval, 0, (size_t)values_cap * 8, c.stream));
-    if (dlab && values_cap) TIP_HIP(hipMemsetAsync(dlab, 0, (size_t)values_cap * 4, c.stream));
-    if (int rc = contact_sums_launch(dp, dc, n_triples, g.offsets, g.adj, n, n_adj, g.valid, g.type, g.query, m, mode, sel_kind, sel_bit, dsum,
-                                     dsum + m, values ? dvoff : nullptr, dval, dlab, values_cap))
+    if (values)
+        if (int rc = check_host_offsets("tip_contact_sums_i32", "value_offsets", value_offsets, m, values_cap)) return rc;
+    Staging st;
+    const int32_t *doff = st.in(offsets, (size_t)n + 1), *dadj = st.in(adj, (size_t)n_adj), *dq = st.in(query, (size_t)m);
+    const uint8_t *dvalid = st.in(valid, (size_t)n), *dtype = st.in(type, (size_t)n);
+    const int32_t *dp = st.in(pairs, (size_t)2 * n_triples);
+    const int64_t *dc = st.in(counts, (size_t)n_triples), *dvoff = st.in(value_offsets, (size_t)m);
+    int64_t *dsum = st.out(sums, (size_t)m), *dnsel = st.out(n_sel, (size_t)m), *dval = st.out(values, (size_t)values_cap, true);
+    int32_t *dlab = st.out(value_labels, (size_t)values_cap, true);
+    if (st.rc) return st.rc;
+    if (int rc = contact_sums_launch(dp, dc, n_triples, doff, dadj, n, n_adj, dvalid, dtype, dq, m, mode, sel, dsum, dnsel, dvoff, dval, dlab,
+                                     values_cap))
         return rc;
-    if (int rc = download(sums, (const int64_t *)dsum, (size_t)m)) return rc;
-    if (int rc = download(n_sel, (const int64_t *)(dsum + m), (size_t)m)) return rc;
-    if (int rc = download(values, (const int64_t *)dval, (size_t)values_cap)) return rc;
-    if (int rc = download(value_labels, (const int32_t *)dlab, (size_t)values_cap)) return rc;
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    return st.finish();
+}
+
+int tip_graph_neighbor_state_f64_dev(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *member,
+                                     const double *state, const int32_t *query, int64_t m, double *nb_sum, int64_t *nb_cnt)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_state_args("tip_graph_neighbor_state_f64_dev", offsets, adj, n, n_adj, member, state, m, nb_sum, nb_cnt)) return rc;
+    return neighbor_state_launch(offsets, adj, n, n_adj, member, state, query, m, nb_sum, nb_cnt);
+}
+
+int tip_graph_neighbor_state_f64(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *member, const double *state,
+                                 const int32_t *query, int64_t m, double *nb_sum, int64_t *nb_cnt)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_state_args("tip_graph_neighbor_state_f64", offsets, adj, n, n_adj, member, state, m, nb_sum, nb_cnt)) return rc;
+    if (int rc = check_host_graph("tip_graph_neighbor_state_f64", offsets, adj, n, n_adj, query, m)) return rc;   // (rows in any order)
+    if (m == 0) return TIP_OK;
+    Staging st;
+    const int32_t *doff = st.in(offsets, (size_t)n + 1), *dadj = st.in(adj, (size_t)n_adj), *dq = st.in(query, (size_t)m);
+    const uint8_t *dmember = st.in(member, (size_t)n);
+    const double *dstate = st.in(state, (size_t)n);
+    double *dsum = st.out(nb_sum, (size_t)m);
+    int64_t *dcnt = st.out(nb_cnt, (size_t)m);
+    if (st.rc) return st.rc;
+    if (int rc = neighbor_state_launch(doff, dadj, n, n_adj, dmember, dstate, dq, m, dsum, dcnt)) return rc;
+    return st.finish();
 }
 
 }  // extern "C"

@@ -49,6 +49,58 @@ struct WsGuard {                  // frees workspaces at scope exit
     ~WsGuard() { for (void *p : ptrs) ws_free(p); }
 };
 
+// The device side of one host-form call (host arrays in and out): uploads, output buffers and scratch on the context stream.
+// The first failure -- an allocation or a HIP call -- stays in rc and turns every later call into a no-op, so a host form tests
+// rc once before it launches.  finish() queues the downloads of the registered outputs and waits for the stream; a form that
+// returns early never reaches it, and nothing is written to the caller's arrays.
+struct Staging {
+    WsGuard ws;
+    int rc = TIP_OK;
+    struct Out { void *host; const void *dev; size_t bytes; };
+    std::vector<Out> outs;
+
+    bool hip(hipError_t e, const char *what)
+    {
+        if (e != hipSuccess && !rc) rc = fail(TIP_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        return !rc;
+    }
+    template <typename T> T *scratch(size_t count)
+    {
+        if (rc) return nullptr;
+        T *d = ws.get<T>(count);
+        if (!d) rc = TIP_ERR_NOMEM;
+        return d;
+    }
+    // the device copy of a host array; a NULL host array stays NULL
+    template <typename T> T *in(const T *host, size_t count)
+    {
+        T *d = host ? scratch<T>(count) : nullptr;
+        if (d && count) hip(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, ctx().stream), "hipMemcpyAsync (upload)");
+        return d;
+    }
+    // a device buffer that finish() copies to the host array; a NULL host array gives NULL and no copy
+    template <typename T> T *out(T *host, size_t count, bool zero = false)
+    {
+        T *d = host ? scratch<T>(count) : nullptr;
+        if (d && zero && count) hip(hipMemsetAsync(d, 0, count * sizeof(T), ctx().stream), "hipMemsetAsync");
+        if (d) outs.push_back({host, d, count * sizeof(T)});
+        return d;
+    }
+    // an output whose element count is known only after the launch: finish() copies the first `count` (at most what out() took)
+    template <typename T> void set_count(const T *dev, size_t count)
+    {
+        for (Out &o : outs)
+            if (o.dev == dev && count * sizeof(T) < o.bytes) o.bytes = count * sizeof(T);
+    }
+    int finish()
+    {
+        for (const Out &o : outs)
+            if (o.bytes && !hip(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, ctx().stream), "hipMemcpyAsync (download)")) break;
+        if (!rc) hip(hipStreamSynchronize(ctx().stream), "hipStreamSynchronize");
+        return rc;
+    }
+};
+
 void prof_begin(const char *name);
 void prof_end();
 

@@ -1,6 +1,7 @@
 // tip_order.hip -- hexatic order: the Delaunay neighbours of the cell centroids (ti.py:2545-2560,
 // find_nearest_neighbors_using_voroni_tesselation), psi_n over a list of neighbour sets (ti.py:2563-2583 calc_psin) and the two
-// per-row columns behind calculate_neighbors_correlation_function (ti.py:803-843).  DESIGN.md 5.8 has the argument.
+// per-row columns behind calculate_neighbors_correlation_function (ti.py:803-843; their kernel, k_neighbor_state, walks the
+// neighbour CSR and lives in tip_graph.hip).  DESIGN.md 5.8 has the argument.
 //
 //   k_order_grid / k_order_count / (scan_i32_dev) / k_order_fill
 //                    a uniform grid over the bounding box of the finite points, about two points per square cell of side h:
@@ -20,12 +21,12 @@
 //                    point) ends with the whole grid.  A candidate list of at most O_CAP points is held in LDS; a longer one
 //                    streams from global memory, each j first against the last list that did fit (nearly every far j dies there).
 //                    The certified sweep is repeated to write the members (two-call convention: sizes, the caller's scan,
-//                    members), unsorted into a scratch row that k_row_sort ranks into ascending order.  No degree cap.
+//                    members), unsorted into a scratch row that k_rank_sort (tip_csr.h, launched as "order_row_sort") ranks into
+//                    ascending order.  No degree cap.
 //   k_psin           one thread per query row: hypot(sum cos(n theta), sum sin(n theta)) / count over the row's members.
-//   k_neighbor_state one thread per query row of the neighbour CSR: sum of state[j] and number of the neighbours j with member[j].
 // Every index read from memory is checked before it is used, every write is checked against its capacity.
 #include <cmath>
-#include "tip_internal.h"
+#include "tip_csr.h"
 
 namespace tip {
 
@@ -265,26 +266,6 @@ __global__ __launch_bounds__(64) void k_delaunay(const OGrid *__restrict__ gp, c
     }
 }
 
-// one wavefront per row: entry a of raw goes to the slot numbered by the entries below it
-template <typename OffT>
-__global__ __launch_bounds__(256) void k_row_sort(const OffT *__restrict__ moff, const int32_t *__restrict__ row_len,
-                                                  const int32_t *__restrict__ raw, int32_t *__restrict__ members, int n, long cap, int add)
-{
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= n) return;
-    const long b = (long)moff[row], e = b + row_len[row];
-    if (b < 0 || e < b || e > cap) return;
-    for (long a = b + lane; a < e; a += 64) {
-        const int v = raw[a];
-        long rank = 0;
-        for (long c = b; c < e; ++c) {
-            const int w = raw[c];
-            rank += (w < v || (w == v && c < a)) ? 1 : 0;
-        }
-        members[b + rank] = v + add;
-    }
-}
-
 template <typename OffT>
 __global__ void k_psin(const double *__restrict__ cy, const double *__restrict__ cx, int n, const int32_t *__restrict__ query, long m,
                        const OffT *__restrict__ moff, const int32_t *__restrict__ members, long n_members, int order,
@@ -310,30 +291,6 @@ __global__ void k_psin(const double *__restrict__ cy, const double *__restrict__
         ++cnt;
     }
     out[q] = cnt ? __ddiv_rn(hypot(sc, ss), (double)cnt) : 0.0;
-}
-
-__global__ void k_neighbor_state(const int32_t *__restrict__ offsets, const int32_t *__restrict__ adj, int n, long n_adj,
-                                 const uint8_t *__restrict__ member, const double *__restrict__ state, const int32_t *__restrict__ query,
-                                 long m, double *__restrict__ nb_sum, int64_t *__restrict__ nb_cnt)
-{
-    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= m) return;
-    const long r = query ? (long)query[q] : q;
-    double sum = 0.0;
-    int64_t cnt = 0;
-    if (r >= 0 && r < n) {
-        long b = offsets[r], e = offsets[r + 1];
-        if (b < 0) b = 0;
-        if (e > n_adj) e = n_adj;
-        for (long a = b; a < e; ++a) {
-            const int j = adj[a] - 1;
-            if ((unsigned)j >= (unsigned)n || member[j] == 0) continue;
-            sum = __dadd_rn(sum, state[j]);
-            ++cnt;
-        }
-    } else cnt = -1;
-    nb_sum[q] = sum;
-    nb_cnt[q] = cnt;
 }
 
 // ---- launches on device arrays --------------------------------------------------------------------------------------------------
@@ -365,8 +322,8 @@ static int delaunay_launch(const double *py, const double *px, int64_t n, int64_
     TIP_LAUNCH("delaunay", k_delaunay<OffT>, dim3((unsigned)n), dim3(64), 0, (const OGrid *)g, (const int32_t *)start, cell_cap, (const double *)sx,
                (const double *)sy, (const int32_t *)sidx, (int)n, sizes, deg32, moff, raw, row_len, (long)members_cap);
     if (members)
-        TIP_LAUNCH("order_row_sort", k_row_sort<OffT>, dim3(cdiv(n, 4)), dim3(256), 0, moff, (const int32_t *)row_len, (const int32_t *)raw, members,
-                   (int)n, (long)members_cap, add);
+        TIP_LAUNCH("order_row_sort", k_rank_sort<OffT>, dim3(cdiv(n, CSR_WPB)), dim3(CSR_BLOCK), 0, moff, (const int32_t *)row_len,
+                   (const int32_t *)raw, (long)members_cap, members, (int)n, (long)members_cap, add);
     return TIP_OK;
 }
 
@@ -399,30 +356,6 @@ static int check_psin_args(const char *who, const double *cy, const double *cx, 
     return TIP_OK;
 }
 
-static int check_state_args(const char *who, const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *member,
-                            const double *state, int64_t m, const double *nb_sum, const int64_t *nb_cnt)
-{
-    if (n < 0 || n > 0x7ffffffe || m < 0 || n_adj < 0 || n_adj > 0x7fffffff)
-        return fail(TIP_ERR_ARG, "%s: n = %ld rows, m = %ld queries, n_adj = %ld", who, (long)n, (long)m, (long)n_adj);
-    if (!offsets || (n_adj > 0 && !adj) || (n > 0 && (!member || !state)) || (m > 0 && (!nb_sum || !nb_cnt)))
-        return fail(TIP_ERR_ARG, "%s: null pointer", who);
-    return TIP_OK;
-}
-
-template <typename T> static int up(WsGuard &ws, const T *host, size_t count, T *&dev)
-{
-    dev = ws.get<T>(count);
-    if (!dev) return TIP_ERR_NOMEM;
-    if (host && count) TIP_HIP(hipMemcpyAsync(dev, host, count * sizeof(T), hipMemcpyHostToDevice, ctx().stream));
-    return TIP_OK;
-}
-
-template <typename T> static int down(T *host, const T *dev, size_t count)
-{
-    if (host && count) TIP_HIP(hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx().stream));
-    return TIP_OK;
-}
-
 }  // namespace tip
 
 using namespace tip;
@@ -452,23 +385,14 @@ int tip_delaunay_neighbors_f64(const double *py, const double *px, int64_t n, in
                         (long)members_cap);
     }
     if (n == 0) return TIP_OK;
-    WsGuard ws;
-    double *dy = nullptr, *dx = nullptr;
-    int64_t *dsizes = nullptr, *dmoff = nullptr;
-    int32_t *dmem = nullptr;
-    if (int rc = up(ws, py, (size_t)n, dy)) return rc;
-    if (int rc = up(ws, px, (size_t)n, dx)) return rc;
-    if (int rc = up(ws, (const int64_t *)nullptr, (size_t)n, dsizes)) return rc;
-    if (members) {
-        if (int rc = up(ws, member_offsets, (size_t)n, dmoff)) return rc;
-        if (int rc = up(ws, (const int32_t *)nullptr, (size_t)members_cap, dmem)) return rc;
-        if (members_cap) TIP_HIP(hipMemsetAsync(dmem, 0, (size_t)members_cap * 4, c.stream));
-    }
+    Staging st;
+    const double *dy = st.in(py, (size_t)n), *dx = st.in(px, (size_t)n);
+    const int64_t *dmoff = members ? st.in(member_offsets, (size_t)n) : nullptr;
+    int64_t *dsizes = st.out(sizes, (size_t)n);
+    int32_t *dmem = st.out(members, (size_t)members_cap, true);
+    if (st.rc) return st.rc;
     if (int rc = delaunay_launch<int64_t>(dy, dx, n, dsizes, nullptr, dmoff, dmem, members_cap, 0)) return rc;
-    if (int rc = down(sizes, (const int64_t *)dsizes, (size_t)n)) return rc;
-    if (int rc = down(members, (const int32_t *)dmem, (size_t)members_cap)) return rc;
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    return st.finish();
 }
 
 int tip_psin_f64_dev(const double *cy, const double *cx, int64_t n, const int32_t *query, int64_t m, const int64_t *member_offsets,
@@ -496,69 +420,14 @@ int tip_psin_f64(const double *cy, const double *cx, int64_t n, const int32_t *q
     for (int64_t a = 0; a < n_members; ++a)
         if (members[a] < 1 || members[a] > n) return fail(TIP_ERR_ARG, "tip_psin_f64: member %ld is label %d (1..%ld)", (long)a, members[a], (long)n);
     if (m == 0) return TIP_OK;
-    WsGuard ws;
-    double *dy = nullptr, *dx = nullptr, *dout = nullptr;
-    int32_t *dq = nullptr, *dmem = nullptr;
-    int64_t *dmoff = nullptr;
-    if (int rc = up(ws, cy, (size_t)n, dy)) return rc;
-    if (int rc = up(ws, cx, (size_t)n, dx)) return rc;
-    if (query) if (int rc = up(ws, query, (size_t)m, dq)) return rc;
-    if (int rc = up(ws, member_offsets, (size_t)m + 1, dmoff)) return rc;
-    if (int rc = up(ws, members, (size_t)n_members, dmem)) return rc;
-    if (int rc = up(ws, (const double *)nullptr, (size_t)m, dout)) return rc;
+    Staging st;
+    const double *dy = st.in(cy, (size_t)n), *dx = st.in(cx, (size_t)n);
+    const int32_t *dq = st.in(query, (size_t)m), *dmem = st.in(members, (size_t)n_members);
+    const int64_t *dmoff = st.in(member_offsets, (size_t)m + 1);
+    double *dout = st.out(out, (size_t)m);
+    if (st.rc) return st.rc;
     if (int rc = psin_launch<int64_t>(dy, dx, n, dq, m, dmoff, dmem, n_members, order, dout)) return rc;
-    if (int rc = down(out, (const double *)dout, (size_t)m)) return rc;
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
-}
-
-int tip_graph_neighbor_state_f64_dev(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *member,
-                                     const double *state, const int32_t *query, int64_t m, double *nb_sum, int64_t *nb_cnt)
-{
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
-    if (int rc = check_state_args("tip_graph_neighbor_state_f64_dev", offsets, adj, n, n_adj, member, state, m, nb_sum, nb_cnt)) return rc;
-    if (m == 0) return TIP_OK;
-    TIP_LAUNCH("neighbor_state", k_neighbor_state, dim3(cdiv(m, 256)), dim3(256), 0, offsets, adj, (int)n, (long)n_adj, member, state, query, (long)m,
-               nb_sum, nb_cnt);
-    return TIP_OK;
-}
-
-int tip_graph_neighbor_state_f64(const int32_t *offsets, const int32_t *adj, int64_t n, int64_t n_adj, const uint8_t *member, const double *state,
-                                 const int32_t *query, int64_t m, double *nb_sum, int64_t *nb_cnt)
-{
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
-    if (int rc = check_state_args("tip_graph_neighbor_state_f64", offsets, adj, n, n_adj, member, state, m, nb_sum, nb_cnt)) return rc;
-    if (offsets[0] != 0 || offsets[n] != n_adj)
-        return fail(TIP_ERR_ARG, "tip_graph_neighbor_state_f64: offsets run from %d to %d, adj has %ld entries", offsets[0], offsets[n], (long)n_adj);
-    for (int64_t r = 0; r < n; ++r) {
-        if (offsets[r + 1] < offsets[r]) return fail(TIP_ERR_ARG, "tip_graph_neighbor_state_f64: offsets decrease at row %ld", (long)r);
-        for (int a = offsets[r]; a < offsets[r + 1]; ++a)
-            if (adj[a] < 1 || adj[a] > n) return fail(TIP_ERR_ARG, "tip_graph_neighbor_state_f64: row %ld holds label %d (1..%ld)", (long)r, adj[a], (long)n);
-    }
-    if (!query && m > n) return fail(TIP_ERR_ARG, "tip_graph_neighbor_state_f64: %ld queries of %ld rows", (long)m, (long)n);
-    for (int64_t q = 0; query && q < m; ++q)
-        if (query[q] < 0 || query[q] >= n) return fail(TIP_ERR_ARG, "tip_graph_neighbor_state_f64: query %ld is row %d of %ld", (long)q, query[q], (long)n);
-    if (m == 0) return TIP_OK;
-    WsGuard ws;
-    int32_t *doff = nullptr, *dadj = nullptr, *dq = nullptr;
-    uint8_t *dmember = nullptr;
-    double *dstate = nullptr, *dsum = nullptr;
-    int64_t *dcnt = nullptr;
-    if (int rc = up(ws, offsets, (size_t)n + 1, doff)) return rc;
-    if (int rc = up(ws, adj, (size_t)n_adj, dadj)) return rc;
-    if (int rc = up(ws, member, (size_t)n, dmember)) return rc;
-    if (int rc = up(ws, state, (size_t)n, dstate)) return rc;
-    if (query) if (int rc = up(ws, query, (size_t)m, dq)) return rc;
-    if (int rc = up(ws, (const double *)nullptr, (size_t)m, dsum)) return rc;
-    if (int rc = up(ws, (const int64_t *)nullptr, (size_t)m, dcnt)) return rc;
-    TIP_LAUNCH("neighbor_state", k_neighbor_state, dim3(cdiv(m, 256)), dim3(256), 0, (const int32_t *)doff, (const int32_t *)dadj, (int)n, (long)n_adj,
-               (const uint8_t *)dmember, (const double *)dstate, (const int32_t *)dq, (long)m, dsum, dcnt);
-    if (int rc = down(nb_sum, (const double *)dsum, (size_t)m)) return rc;
-    if (int rc = down(nb_cnt, (const int64_t *)dcnt, (size_t)m)) return rc;
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    return st.finish();
 }
 
 int tip_order_features_f64_dev(const double *py, const double *px, int64_t n, int order, double *psi, int64_t *degree)

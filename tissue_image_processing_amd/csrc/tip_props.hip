@@ -434,26 +434,15 @@ int tip_regionprops_i32(const int32_t *labels, const double *intensity, int y, i
     if (!c.stream) return TIP_ERR_HIP;
     if (!labels || y < 1 || x < 1 || n < 0) return fail(TIP_ERR_ARG, "tip_regionprops_i32: bad arguments");
     if (n == 0) return TIP_OK;
-    const size_t P = (size_t)y * x;
-    WsGuard ws;
-    int32_t *dl = ws.get<int32_t>(P);
-    double *di = intensity ? ws.get<double>(P) : nullptr;
-    int64_t *da = ws.get<int64_t>(n), *db = ws.get<int64_t>((size_t)4 * n), *dsy = ws.get<int64_t>(n),
-            *dsx = ws.get<int64_t>(n), *dp = ws.get<int64_t>((size_t)3 * n);
-    double *dis = intensity ? ws.get<double>(n) : nullptr;
-    if (!dl || !da || !db || !dsy || !dsx || !dp || (intensity && (!di || !dis))) return TIP_ERR_NOMEM;
-    TIP_HIP(hipMemcpyAsync(dl, labels, P * 4, hipMemcpyHostToDevice, c.stream));
-    if (intensity) TIP_HIP(hipMemcpyAsync(di, intensity, P * 8, hipMemcpyHostToDevice, c.stream));
-    int rc = regionprops_dev(dl, di, y, x, n, da, db, dsy, dsx, dp, dis);
-    if (rc) return rc;
-    TIP_HIP(hipMemcpyAsync(area, da, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipMemcpyAsync(bbox4, db, (size_t)n * 32, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipMemcpyAsync(sumy, dsy, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipMemcpyAsync(sumx, dsx, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipMemcpyAsync(pc3, dp, (size_t)n * 24, hipMemcpyDeviceToHost, c.stream));
-    if (isum) TIP_HIP(hipMemcpyAsync(isum, dis, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    const size_t P = (size_t)y * x, N = (size_t)n;
+    Staging st;
+    const int32_t *dl = st.in(labels, P);
+    const double *di = st.in(intensity, P);
+    int64_t *da = st.out(area, N), *db = st.out(bbox4, 4 * N), *dsy = st.out(sumy, N), *dsx = st.out(sumx, N), *dp = st.out(pc3, 3 * N);
+    double *dis = isum ? st.out(isum, N) : (intensity ? st.scratch<double>(N) : nullptr);   // (an intensity without isum: summed and dropped)
+    if (st.rc) return st.rc;
+    if (int rc = regionprops_dev(dl, di, y, x, n, da, db, dsy, dsx, dp, dis)) return rc;
+    return st.finish();
 }
 
 int tip_neighbor_pairs_i32_dev(const int32_t *labels, int y, int x, int32_t *pairs_dev, int64_t cap, int64_t *n_pairs_host)
@@ -466,16 +455,13 @@ int tip_neighbor_pairs_i32(const int32_t *labels, int y, int x, int32_t *pairs, 
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
     if (!labels || !pairs || !n_pairs || y < 1 || x < 1 || cap < 1) return fail(TIP_ERR_ARG, "tip_neighbor_pairs_i32: bad arguments");
-    const size_t P = (size_t)y * x;
-    WsGuard ws;
-    int32_t *dl = ws.get<int32_t>(P), *dp = ws.get<int32_t>((size_t)2 * cap);
-    if (!dl || !dp) return TIP_ERR_NOMEM;
-    TIP_HIP(hipMemcpyAsync(dl, labels, P * 4, hipMemcpyHostToDevice, c.stream));
-    int rc = neighbor_pairs_dev(dl, y, x, dp, cap, n_pairs);
-    if (rc) return rc;
-    TIP_HIP(hipMemcpyAsync(pairs, dp, (size_t)(*n_pairs) * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    Staging st;
+    const int32_t *dl = st.in(labels, (size_t)y * x);
+    int32_t *dp = st.out(pairs, (size_t)2 * cap);
+    if (st.rc) return st.rc;
+    if (int rc = neighbor_pairs_dev(dl, y, x, dp, cap, n_pairs)) return rc;
+    st.set_count(dp, (size_t)2 * *n_pairs);
+    return st.finish();
 }
 
 int tip_contact_pairs_i32_dev(const int32_t *labels, int y, int x, int big, int32_t *pairs_dev, int64_t *counts_dev, int64_t cap,
@@ -489,18 +475,15 @@ int tip_contact_pairs_i32(const int32_t *labels, int y, int x, int big, int32_t 
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
     if (!labels || !pairs || !counts || !n_pairs || y < 1 || x < 1 || cap < 1) return fail(TIP_ERR_ARG, "tip_contact_pairs_i32: bad arguments");
-    const size_t P = (size_t)y * x;
-    WsGuard ws;
-    int32_t *dl = ws.get<int32_t>(P), *dp = ws.get<int32_t>((size_t)2 * cap);
-    int64_t *dc = ws.get<int64_t>((size_t)cap);
-    if (!dl || !dp || !dc) return TIP_ERR_NOMEM;
-    TIP_HIP(hipMemcpyAsync(dl, labels, P * 4, hipMemcpyHostToDevice, c.stream));
-    int rc = contact_pairs_dev(dl, y, x, big, dp, dc, cap, n_pairs);
-    if (rc) return rc;
-    TIP_HIP(hipMemcpyAsync(pairs, dp, (size_t)(*n_pairs) * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipMemcpyAsync(counts, dc, (size_t)(*n_pairs) * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    Staging st;
+    const int32_t *dl = st.in(labels, (size_t)y * x);
+    int32_t *dp = st.out(pairs, (size_t)2 * cap);
+    int64_t *dc = st.out(counts, (size_t)cap);
+    if (st.rc) return st.rc;
+    if (int rc = contact_pairs_dev(dl, y, x, big, dp, dc, cap, n_pairs)) return rc;
+    st.set_count(dp, (size_t)2 * *n_pairs);
+    st.set_count(dc, (size_t)*n_pairs);
+    return st.finish();
 }
 
 }  // extern "C"

@@ -19,8 +19,7 @@
 //                    the grid is below 2 (s / 2) -- upstream's block [y - s/2, y + s/2) around y = s/2 + k s -- and the grid
 //                    point exists (s/2 + k s < extent); every other pixel is 0.  An odd s leaves one-pixel seams, s = 1 an empty
 //                    map, and the frame clips the last block, as upstream.
-#include "tip_internal.h"
-#include "tip_typesel.h"   // sp_selected: the type selector, shared with tip_graph.hip
+#include "tip_typesel.h"   // sp_selected / parse_selector: the type selector, shared with tip_graph.hip
 
 namespace tip {
 
@@ -114,21 +113,20 @@ __global__ void k_spatial_fill(const double *__restrict__ val, int Y, int X, int
 static inline int grid_points(int extent, int step) { return extent > step / 2 ? (extent - step / 2 + step - 1) / step : 0; }
 
 static int check_table(const char *who, const double *cy, const double *cx, const int64_t *area, const uint8_t *type, int64_t n,
-                       int sel_bit, int sel_positive, double r2, int &sel_kind)
+                       int sel_bit, int sel_positive, double r2, Selector &sel)
 {
     if (n < 0 || (n > 0 && (!cy || !cx || !area || !type))) return fail(TIP_ERR_ARG, "%s: the table's columns (n = %ld)", who, (long)n);
-    if (sel_bit < -1 || sel_bit > 7) return fail(TIP_ERR_ARG, "%s: type bit %d (0..7, or -1 for no selector)", who, sel_bit);
+    if (int rc = parse_selector(who, sel_bit, sel_positive, true, sel)) return rc;
     if (r2 != r2) return fail(TIP_ERR_ARG, "%s: r2 is NaN", who);
-    sel_kind = sel_bit < 0 ? 0 : (sel_positive ? 1 : 2);
     return TIP_OK;
 }
 
 // the arguments of tip_window_stats_f64[_dev] / tip_spatial_map_f64[_dev], checked once for both forms under the entry's own name
 static int check_stats_args(const char *who, const double *qy, const double *qx, int64_t m, double r2, const double *cy, const double *cx,
                             const int64_t *area, const uint8_t *type, int64_t n, int sel_bit, int sel_positive, const int64_t *n_in,
-                            const int64_t *area_in, const int64_t *n_sel, const double *sum_sel, int &sel_kind)
+                            const int64_t *area_in, const int64_t *n_sel, const double *sum_sel, Selector &sel)
 {
-    if (int rc = check_table(who, cy, cx, area, type, n, sel_bit, sel_positive, r2, sel_kind)) return rc;
+    if (int rc = check_table(who, cy, cx, area, type, n, sel_bit, sel_positive, r2, sel)) return rc;
     if (m < 0 || (m > 0 && (!qy || !qx || !n_in || !area_in || !n_sel || !sum_sel)))
         return fail(TIP_ERR_ARG, "%s: the centres or the outputs (m = %ld)", who, (long)m);
     return TIP_OK;
@@ -136,9 +134,9 @@ static int check_stats_args(const char *who, const double *qy, const double *qx,
 
 static int check_map_args(const char *who, int y, int x, int step, double r2, const double *cy, const double *cx, const int64_t *area,
                           const uint8_t *type, const double *feat, int64_t n, int sel_bit, int sel_positive, int mode, const double *map,
-                          int &sel_kind)
+                          Selector &sel)
 {
-    if (int rc = check_table(who, cy, cx, area, type, n, sel_bit, sel_positive, r2, sel_kind)) return rc;
+    if (int rc = check_table(who, cy, cx, area, type, n, sel_bit, sel_positive, r2, sel)) return rc;
     if (!map || y < 1 || x < 1 || step < 1) return fail(TIP_ERR_ARG, "%s: map %d x %d, step %d", who, y, x, step);
     if (mode < SP_DENSITY || mode > SP_MEAN) return fail(TIP_ERR_ARG, "%s: mode %d (0 density, 1 type fraction, 2 mean)", who, mode);
     if (mode == SP_MEAN && n > 0 && !feat) return fail(TIP_ERR_ARG, "%s: the mean needs a feature column", who);
@@ -147,18 +145,18 @@ static int check_map_args(const char *who, int y, int x, int step, double r2, co
 
 // the statistics of M centres (qy / qx device arrays, or NULL: the (grid_y x grid_x) grid of `step`) over device columns
 static int window_stats_launch(const double *qy, const double *qx, long M, int grid_x, int step, double r2, const double *cy,
-                               const double *cx, const int64_t *area, const uint8_t *type, const double *feat, long N, int sel_kind,
-                               int sel_bit, int64_t *n_in, int64_t *area_in, int64_t *n_sel, double *sum_sel)
+                               const double *cx, const int64_t *area, const uint8_t *type, const double *feat, long N, Selector sel,
+                               int64_t *n_in, int64_t *area_in, int64_t *n_sel, double *sum_sel)
 {
     if (M <= 0) return TIP_OK;
     TIP_LAUNCH("window_stats", k_window_stats, dim3(cdiv(M, SP_TILE)), dim3(SP_TILE), 0, qy, qx, M, grid_x, step, r2, cy, cx, area,
-               type, feat, N, sel_kind, sel_bit < 0 ? 0 : sel_bit, n_in, area_in, n_sel, sum_sel);
+               type, feat, N, sel.kind, sel.bit, n_in, area_in, n_sel, sum_sel);
     return TIP_OK;
 }
 
 // grid, statistics, values and fill on device columns (arguments checked by the entry point)
 static int spatial_map_launch(int y, int x, int step, double r2, const double *cy, const double *cx, const int64_t *area, const uint8_t *type,
-                              const double *feat, long n, int sel_kind, int sel_bit, int mode, double *map, int64_t *n_sel_grid)
+                              const double *feat, long n, Selector sel, int mode, double *map, int64_t *n_sel_grid)
 {
     const int gy = grid_points(y, step), gx = grid_points(x, step);
     const long M = (long)gy * gx;
@@ -167,7 +165,7 @@ static int spatial_map_launch(int y, int x, int step, double r2, const double *c
     double *sum = ws.get<double>((size_t)M), *val = ws.get<double>((size_t)M);
     if (!stats || !sum || !val) return TIP_ERR_NOMEM;
     int64_t *nsel = n_sel_grid ? n_sel_grid : stats + 2 * M;
-    if (int rc = window_stats_launch(nullptr, nullptr, M, gx, step, r2, cy, cx, area, type, feat, n, sel_kind, sel_bit, stats,
+    if (int rc = window_stats_launch(nullptr, nullptr, M, gx, step, r2, cy, cx, area, type, feat, n, sel, stats,
                                      stats + M, nsel, sum))
         return rc;
     if (M > 0)
@@ -175,6 +173,18 @@ static int spatial_map_launch(int y, int x, int step, double r2, const double *c
                    (const int64_t *)nsel, (const double *)sum, M, mode, val);
     TIP_LAUNCH("spatial_fill", k_spatial_fill, dim3(cdiv(x, 256), y), dim3(256), 0, (const double *)val, y, x, step, gy, gx, map);
     return TIP_OK;
+}
+
+// the device copies of a host table's five columns (feat may be NULL)
+struct DevTable {
+    const double *cy, *cx, *feat;
+    const int64_t *area;
+    const uint8_t *type;
+};
+
+static DevTable upload_table(Staging &st, const double *cy, const double *cx, const int64_t *area, const uint8_t *type, const double *feat, size_t n)
+{
+    return {st.in(cy, n), st.in(cx, n), st.in(feat, n), st.in(area, n), st.in(type, n)};
 }
 
 }  // namespace tip
@@ -189,12 +199,11 @@ int tip_window_stats_f64_dev(const double *qy, const double *qx, int64_t m, doub
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    int sel_kind = 0;
+    Selector sel;
     if (int rc = check_stats_args("tip_window_stats_f64_dev", qy, qx, m, r2, cy, cx, area, type, n, sel_bit, sel_positive, n_in, area_in, n_sel, sum_sel,
-                                  sel_kind))
+                                  sel))
         return rc;
-    return window_stats_launch(qy, qx, (long)m, 1, 1, r2, cy, cx, area, type, feat, (long)n, sel_kind, sel_bit, n_in, area_in, n_sel,
-                               sum_sel);
+    return window_stats_launch(qy, qx, (long)m, 1, 1, r2, cy, cx, area, type, feat, (long)n, sel, n_in, area_in, n_sel, sum_sel);
 }
 
 int tip_window_stats_f64(const double *qy, const double *qx, int64_t m, double r2, const double *cy, const double *cx,
@@ -203,36 +212,21 @@ int tip_window_stats_f64(const double *qy, const double *qx, int64_t m, double r
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    int sel_kind = 0;
+    Selector sel;
     if (int rc = check_stats_args("tip_window_stats_f64", qy, qx, m, r2, cy, cx, area, type, n, sel_bit, sel_positive, n_in, area_in, n_sel, sum_sel,
-                                  sel_kind))
+                                  sel))
         return rc;
     if (m == 0) return TIP_OK;
-    const size_t M = (size_t)m, N = (size_t)n;
-    WsGuard ws;
-    double *dq = ws.get<double>(2 * M), *dpos = ws.get<double>(2 * N), *dfeat = feat ? ws.get<double>(N) : nullptr;
-    int64_t *darea = ws.get<int64_t>(N), *dout = ws.get<int64_t>(3 * M);
-    uint8_t *dtype = ws.get<uint8_t>(N);
-    double *dsum = ws.get<double>(M);
-    if (!dq || !dpos || (feat && !dfeat) || !darea || !dout || !dtype || !dsum) return TIP_ERR_NOMEM;
-    TIP_HIP(hipMemcpyAsync(dq, qy, M * 8, hipMemcpyHostToDevice, c.stream));
-    TIP_HIP(hipMemcpyAsync(dq + M, qx, M * 8, hipMemcpyHostToDevice, c.stream));
-    if (N) {
-        TIP_HIP(hipMemcpyAsync(dpos, cy, N * 8, hipMemcpyHostToDevice, c.stream));
-        TIP_HIP(hipMemcpyAsync(dpos + N, cx, N * 8, hipMemcpyHostToDevice, c.stream));
-        TIP_HIP(hipMemcpyAsync(darea, area, N * 8, hipMemcpyHostToDevice, c.stream));
-        TIP_HIP(hipMemcpyAsync(dtype, type, N, hipMemcpyHostToDevice, c.stream));
-        if (feat) TIP_HIP(hipMemcpyAsync(dfeat, feat, N * 8, hipMemcpyHostToDevice, c.stream));
-    }
-    if (int rc = window_stats_launch(dq, dq + M, (long)m, 1, 1, r2, dpos, dpos + N, darea, dtype, dfeat, (long)n, sel_kind, sel_bit, dout,
-                                     dout + M, dout + 2 * M, dsum))
+    const size_t M = (size_t)m;
+    Staging st;
+    const double *dqy = st.in(qy, M), *dqx = st.in(qx, M);
+    const DevTable t = upload_table(st, cy, cx, area, type, feat, (size_t)n);
+    int64_t *dn_in = st.out(n_in, M), *darea_in = st.out(area_in, M), *dn_sel = st.out(n_sel, M);
+    double *dsum = st.out(sum_sel, M);
+    if (st.rc) return st.rc;
+    if (int rc = window_stats_launch(dqy, dqx, (long)m, 1, 1, r2, t.cy, t.cx, t.area, t.type, t.feat, (long)n, sel, dn_in, darea_in, dn_sel, dsum))
         return rc;
-    TIP_HIP(hipMemcpyAsync(n_in, dout, M * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipMemcpyAsync(area_in, dout + M, M * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipMemcpyAsync(n_sel, dout + 2 * M, M * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipMemcpyAsync(sum_sel, dsum, M * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    return st.finish();
 }
 
 int tip_spatial_map_f64_dev(int y, int x, int step, double r2, const double *cy, const double *cx, const int64_t *area,
@@ -241,11 +235,10 @@ int tip_spatial_map_f64_dev(int y, int x, int step, double r2, const double *cy,
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    int sel_kind = 0;
-    if (int rc = check_map_args("tip_spatial_map_f64_dev", y, x, step, r2, cy, cx, area, type, feat, n, sel_bit, sel_positive, mode, map,
-                                sel_kind))
+    Selector sel;
+    if (int rc = check_map_args("tip_spatial_map_f64_dev", y, x, step, r2, cy, cx, area, type, feat, n, sel_bit, sel_positive, mode, map, sel))
         return rc;
-    return spatial_map_launch(y, x, step, r2, cy, cx, area, type, feat, (long)n, sel_kind, sel_bit, mode, map, n_sel_grid);
+    return spatial_map_launch(y, x, step, r2, cy, cx, area, type, feat, (long)n, sel, mode, map, n_sel_grid);
 }
 
 int tip_spatial_map_f64(int y, int x, int step, double r2, const double *cy, const double *cx, const int64_t *area,
@@ -254,28 +247,16 @@ int tip_spatial_map_f64(int y, int x, int step, double r2, const double *cy, con
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    int sel_kind = 0;
-    if (int rc = check_map_args("tip_spatial_map_f64", y, x, step, r2, cy, cx, area, type, feat, n, sel_bit, sel_positive, mode, map, sel_kind))
+    Selector sel;
+    if (int rc = check_map_args("tip_spatial_map_f64", y, x, step, r2, cy, cx, area, type, feat, n, sel_bit, sel_positive, mode, map, sel))
         return rc;
-    const size_t N = (size_t)n, P = (size_t)y * x, M = (size_t)grid_points(y, step) * grid_points(x, step);
-    WsGuard ws;
-    double *dpos = ws.get<double>(2 * N), *dfeat = feat ? ws.get<double>(N) : nullptr, *dmap = ws.get<double>(P);
-    int64_t *darea = ws.get<int64_t>(N), *dnsel = n_sel_grid ? ws.get<int64_t>(M) : nullptr;
-    uint8_t *dtype = ws.get<uint8_t>(N);
-    if (!dpos || (feat && !dfeat) || !dmap || !darea || (n_sel_grid && !dnsel) || !dtype) return TIP_ERR_NOMEM;
-    if (N) {
-        TIP_HIP(hipMemcpyAsync(dpos, cy, N * 8, hipMemcpyHostToDevice, c.stream));
-        TIP_HIP(hipMemcpyAsync(dpos + N, cx, N * 8, hipMemcpyHostToDevice, c.stream));
-        TIP_HIP(hipMemcpyAsync(darea, area, N * 8, hipMemcpyHostToDevice, c.stream));
-        TIP_HIP(hipMemcpyAsync(dtype, type, N, hipMemcpyHostToDevice, c.stream));
-        if (feat) TIP_HIP(hipMemcpyAsync(dfeat, feat, N * 8, hipMemcpyHostToDevice, c.stream));
-    }
-    if (int rc = spatial_map_launch(y, x, step, r2, dpos, dpos + N, darea, dtype, dfeat, (long)n, sel_kind, sel_bit, mode, dmap, dnsel))
-        return rc;
-    TIP_HIP(hipMemcpyAsync(map, dmap, P * 8, hipMemcpyDeviceToHost, c.stream));
-    if (n_sel_grid && M) TIP_HIP(hipMemcpyAsync(n_sel_grid, dnsel, M * 8, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    Staging st;
+    const DevTable t = upload_table(st, cy, cx, area, type, feat, (size_t)n);
+    double *dmap = st.out(map, (size_t)y * x);
+    int64_t *dnsel = st.out(n_sel_grid, (size_t)grid_points(y, step) * grid_points(x, step));
+    if (st.rc) return st.rc;
+    if (int rc = spatial_map_launch(y, x, step, r2, t.cy, t.cx, t.area, t.type, t.feat, (long)n, sel, mode, dmap, dnsel)) return rc;
+    return st.finish();
 }
 
 }  // extern "C"
