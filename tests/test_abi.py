@@ -1,4 +1,5 @@
-"""CPU: the C-ABI library loads and exports every symbol include/tissue_hip.h declares (no compute calls)."""
+"""CPU: the C-ABI library loads and exports every symbol include/tissue_hip.h declares, with the argument types
+_abi.SIGNATURES gives them (no device calls)."""
 import ctypes
 import os
 import re
@@ -11,6 +12,65 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def declared_symbols():
     text = open(os.path.join(ROOT, "include", "tissue_hip.h")).read()
     return sorted(set(re.findall(r"TIP_API\s+int\s+(tip_\w+)\s*\(", text)))
+
+
+def declared_signatures():
+    """{name: (return type, argtypes)} of every TIP_API prototype, in the header's order; a prototype that does not parse
+    raises."""
+    from tissue_image_processing_amd import _abi
+    scalars = {"int": _abi.I, "int32_t": _abi.I, "int64_t": _abi.L, "long": _abi.L, "size_t": _abi.Z, "double": _abi.D,
+               "float": _abi.F}
+    text = open(os.path.join(ROOT, "include", "tissue_hip.h")).read()
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    text = re.sub(r"#define\s+TIP_API\b[^\n]*", "", text)
+    protos = re.findall(r"TIP_API\s+(\w+)\s+(tip_\w+)\s*\(([^()]*)\)\s*;", text)
+    assert len(protos) == len(re.findall(r"\bTIP_API\b", text)), "a TIP_API prototype did not parse"
+    out = {}
+    for ret, name, params in protos:
+        sig = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            if "*" in p:
+                sig.append(_abi.P)
+            else:
+                ctype, _pname = [t for t in p.split() if t != "const"]
+                sig.append(scalars[ctype])
+        assert name not in out, name
+        out[name] = (ret, tuple(sig))
+    return out
+
+
+def test_signature_table_is_the_header():
+    """_abi.SIGNATURES against include/tissue_hip.h: the same names in the same order, every argument type equal under the six
+    mapping rules, every return type int (what _lib.load() declares)."""
+    from tissue_image_processing_amd import _abi
+    header = declared_signatures()
+    assert sorted(header) == declared_symbols()
+    assert list(_abi.SIGNATURES) == list(header)
+    for name, (ret, sig) in header.items():
+        assert ret == "int", name
+        assert _abi.SIGNATURES[name] == sig, name
+
+
+def test_declared_entry_takes_plain_numbers():
+    """tip_gaussian_taps touches no device: plain Python and numpy numbers arrive as the header's double and int."""
+    import numpy as np
+    from tissue_image_processing_amd import _lib
+    lib = _lib.load()
+    w = np.zeros(64)
+    assert lib.tip_gaussian_taps(1.0, 4.0, _lib.ptr(w), 64) == 9
+    assert w[:9].sum() == 1.0
+    assert lib.tip_gaussian_taps(np.float32(1.0), 4, _lib.ptr(w), np.int64(64)) == 9
+
+
+def test_declared_entry_rejects_mistakes():
+    import numpy as np
+    from tissue_image_processing_amd import _lib
+    lib = _lib.load()
+    w = np.zeros(64)
+    with pytest.raises(TypeError):
+        lib.tip_gaussian_taps(1.0, 4.0, _lib.ptr(w))
+    with pytest.raises(ctypes.ArgumentError):
+        lib.tip_gaussian_taps(1.0, 4.0, _lib.ptr(w), 2.5)
 
 
 def test_header_declares_the_hot_path():

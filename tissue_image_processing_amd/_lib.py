@@ -9,15 +9,14 @@ import threading
 
 import numpy as np
 
+from ._abi import SIGNATURES
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TISSUE_HIP_LIB: another build of the same library (diagnostic builds, tools/unet_trace.sh); never a different implementation
 LIB_PATH = os.environ.get("TISSUE_HIP_LIB") or os.path.join(_HERE, "libtissue_hip.so")
 _lib = None
 _lock = threading.Lock()
 _tls = threading.local()
-
-c_int, c_long, c_double, c_void_p, c_size_t = ctypes.c_int, ctypes.c_long, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
-c_i64 = ctypes.c_int64
 
 TIP_ERR_ARG, TIP_ERR_INDEX, TIP_ERR_OVERFLOW = -2, -4, -6
 
@@ -36,9 +35,21 @@ def load():
                     "libtissue_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
                     "or `python -m tissue_image_processing_amd.build`. There is no CPU fallback." % LIB_PATH)
             _preload_torch_hip_runtime()
-            _lib = ctypes.CDLL(LIB_PATH)
-            _lib.tip_prof_report.restype = c_int
+            _lib = _declare(ctypes.CDLL(LIB_PATH))
     return _lib
+
+
+def _declare(cdll):
+    """Gives every entry point its argument types (_abi.SIGNATURES): plain Python and numpy numbers then convert at the
+    header's width, and a wrong kind or a missing argument is a TypeError instead of a misread register."""
+    for name, sig in SIGNATURES.items():
+        try:
+            fn = getattr(cdll, name)
+        except AttributeError:
+            raise TissueHipError("%s does not export %s (declared in include/tissue_hip.h)" % (LIB_PATH, name)) from None
+        fn.argtypes = sig
+        fn.restype = ctypes.c_int
+    return cdll
 
 
 def _preload_torch_hip_runtime():
@@ -72,12 +83,13 @@ def init(device=None):
     """Binds the calling thread to a GPU (default: env TISSUE_HIP_DEVICE, LOCAL_RANK, else 0)."""
     lib = load()
     if device is None:
-        device = int(os.environ.get("TISSUE_HIP_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+        device = os.environ.get("TISSUE_HIP_DEVICE", os.environ.get("LOCAL_RANK", "0"))
+    device = int(device)
     if lib.tip_device_count() <= 0:
         raise TissueHipError("no HIP device visible: the tissue_image_processing_amd operators need an MI355X "
                              "(there is no CPU fallback)")
-    check(lib.tip_init(int(device)))
-    _tls.device = int(device)
+    check(lib.tip_init(device))
+    _tls.device = device
     return lib
 
 
@@ -90,7 +102,7 @@ def lib():
 
 def last_error():
     buf = ctypes.create_string_buffer(1024)
-    load().tip_last_error(buf, c_size_t(1024))
+    load().tip_last_error(buf, 1024)
     return buf.value.decode("utf-8", "replace")
 
 
@@ -106,38 +118,38 @@ def check(rc):
 
 
 def ptr(a):
-    return None if a is None else a.ctypes.data_as(c_void_p)
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def dptr(addr):
     """a device address as a pointer argument; None is the NULL pointer"""
-    return c_void_p(None if addr is None else int(addr))
+    return ctypes.c_void_p(None if addr is None else int(addr))
 
 
 class DeviceBuffer:
     """Owned device allocation (tip_malloc/tip_free)."""
 
     def __init__(self, nbytes):
-        p = c_void_p()
-        check(lib().tip_malloc(ctypes.byref(p), c_size_t(int(nbytes))))
+        p = ctypes.c_void_p()
+        check(lib().tip_malloc(ctypes.byref(p), nbytes))
         self.ptr = p.value
         self.nbytes = int(nbytes)
 
     def upload(self, arr):
         arr = np.ascontiguousarray(arr)
         assert arr.nbytes <= self.nbytes
-        check(lib().tip_memcpy_h2d(dptr(self.ptr), ptr(arr), c_size_t(arr.nbytes)))
+        check(lib().tip_memcpy_h2d(self.ptr, ptr(arr), arr.nbytes))
         return self
 
     def download(self, shape, dtype):
         out = np.empty(shape, dtype)
         assert out.nbytes <= self.nbytes
-        check(lib().tip_memcpy_d2h(ptr(out), dptr(self.ptr), c_size_t(out.nbytes)))
+        check(lib().tip_memcpy_d2h(ptr(out), self.ptr, out.nbytes))
         return out
 
     def free(self):
         if self.ptr:
-            load().tip_free(dptr(self.ptr))
+            load().tip_free(self.ptr)
             self.ptr = None
 
     def __del__(self):
@@ -150,7 +162,7 @@ class DeviceBuffer:
 def transpose2d_dev(in_ptr, out_ptr, rows, cols, elem_bytes):
     """tip_transpose2d_dev: out[c][r] = in[r][c] between DEVICE buffers of 4- or 8-byte elements (a bit copy), asynchronous on
     the calling thread's library stream.  ValueError for another element size, an extent < 1, a null pointer or in == out."""
-    check(lib().tip_transpose2d_dev(dptr(in_ptr or 0), dptr(out_ptr or 0), int(rows), int(cols), int(elem_bytes)))
+    check(lib().tip_transpose2d_dev(in_ptr, out_ptr, rows, cols, elem_bytes))
 
 
 def fft2_c128(z, inverse=False):
@@ -164,7 +176,7 @@ def fft2_c128(z, inverse=False):
         if n < 2 or n > 4096:
             raise NotImplementedError("MI355X FFT takes extents in [2, 4096] (got %dx%d)" % (ny, nx))
     out = np.empty_like(z)
-    check(lib().tip_fft2_c128(ptr(z), ptr(out), ny, nx, 1 if inverse else 0))
+    check(lib().tip_fft2_c128(ptr(z), ptr(out), ny, nx, bool(inverse)))
     return out
 
 
@@ -207,9 +219,9 @@ def prof_reset():
 
 def prof_report():
     """{kernel_name: (count, total_ms)} measured with HIP events on the library's stream."""
-    n = lib().tip_prof_report(None, c_size_t(0))
+    n = lib().tip_prof_report(None, 0)
     buf = ctypes.create_string_buffer(n + 16)
-    lib().tip_prof_report(buf, c_size_t(n + 16))
+    lib().tip_prof_report(buf, n + 16)
     out = {}
     for line in buf.value.decode().splitlines():
         name, cnt, ms = line.rsplit(" ", 2)

@@ -59,8 +59,7 @@ def phase_cross_correlation_dev(ref_ptr, mov_ptr, ny, nx, upsample_factor=100, d
     """The same on two device-resident (ny, nx) planes (device addresses); returns the shift array."""
     dt = {"float32": 0, "float64": 1, "uint16": 3}[dtype]
     out = (ctypes.c_int64 * 4)()
-    _lib.check(_lib.lib().tip_phase_correlation_dev(_lib.dptr(ref_ptr), _lib.dptr(mov_ptr), dt, int(ny), int(nx),
-                                                    int(upsample_factor), out))
+    _lib.check(_lib.lib().tip_phase_correlation_dev(ref_ptr, mov_ptr, dt, ny, nx, int(upsample_factor), out))
     return _finish_shifts(out, ny, nx, upsample_factor)
 
 
@@ -120,8 +119,7 @@ def local_drifts(first_image, second_image, initial_shift_x=0, initial_shift_y=0
             if ny < 2 or nx < 2:
                 raise NotImplementedError("MI355X phase correlation takes extents in [2, 4096] (got %dx%d)" % (ny, nx))
             for dst, src, ro, co in ((wa, da, r0 + pr, c0 + pc), (wb, db, r0 + cr, c0 + cc)):
-                _lib.check(lib.tip_memcpy2d_d2d(_lib.dptr(dst.ptr), ctypes.c_size_t(nx * es), _lib.dptr(src.ptr + (ro * W + co) * es),
-                                                ctypes.c_size_t(W * es), ctypes.c_size_t(nx * es), ctypes.c_size_t(ny)))
+                _lib.check(lib.tip_memcpy2d_d2d(dst.ptr, nx * es, src.ptr + (ro * W + co) * es, W * es, nx * es, ny))
             sh = phase_cross_correlation_dev(wa.ptr, wb.ptr, ny, nx, 100, dtype=name)
             out.append(((r0, r1, c0, c1), rx + sh[-2], ry + sh[-1]))
     finally:
@@ -196,8 +194,8 @@ def optical_flow_tvl1_levels(reference_image, moving_image, *, attachment=15, ti
     flow = np.empty((2,) + a.shape, np.float32)
     warps = np.zeros(10, np.int32)
     _lib.check(_lib.lib().tip_optical_flow_tvl1(_lib.ptr(a), _lib.ptr(b), _OF_DTYPES[a.dtype], a.shape[0], a.shape[1],
-                                                ctypes.c_float(attachment), ctypes.c_float(tightness), int(num_warp),
-                                                int(num_iter), ctypes.c_double(tol), _lib.ptr(flow), _lib.ptr(warps), 10))
+                                                attachment, tightness, int(num_warp), int(num_iter), tol, _lib.ptr(flow),
+                                                _lib.ptr(warps), 10))
     return flow, [int(w) for w in warps[:pyramid_levels(a.shape)]]
 
 
@@ -216,9 +214,8 @@ def optical_flow_tvl1_dev(ref_ptr, mov_ptr, ny, nx, flow_ptr, dtype="float32", a
     """The same on device-resident (ny, nx) frames; the (2, ny, nx) float32 flow goes to the device address flow_ptr.
     Asynchronous on the calling thread's stream."""
     dt = {"float32": 0, "float64": 1, "uint16": 3, "uint8": 4}[dtype]
-    _lib.check(_lib.lib().tip_optical_flow_tvl1_dev(_lib.dptr(ref_ptr), _lib.dptr(mov_ptr), dt, int(ny), int(nx),
-                                                    ctypes.c_float(attachment), ctypes.c_float(tightness), int(num_warp),
-                                                    int(num_iter), ctypes.c_double(tol), _lib.dptr(flow_ptr), None, 0))
+    _lib.check(_lib.lib().tip_optical_flow_tvl1_dev(ref_ptr, mov_ptr, dt, ny, nx, attachment, tightness, int(num_warp),
+                                                    int(num_iter), tol, flow_ptr, None, 0))
 
 
 # ---- PIV step of the sharded movie tracker (movie.process_movie(use_piv=True); ti.py:2061-2106) ---------------------------
@@ -241,9 +238,8 @@ def piv_lookup_dev(prev_ptr, cur_ptr, labels_ptr, ny, nx, prev_table, flow_ptr=N
     cy, cx, present = _piv_rows(prev_table)
     hit = np.empty(cy.shape, np.int32)
     _lib.check(_lib.lib().tip_piv_lookup_max3_i32_dev(
-        _lib.dptr(prev_ptr), _lib.dptr(cur_ptr), _lib.dptr(labels_ptr), int(ny), int(nx), _lib.ptr(cy), _lib.ptr(cx),
-        _lib.ptr(present), ctypes.c_int64(cy.size), ctypes.c_float(attachment), ctypes.c_float(tightness), int(num_warp),
-        int(num_iter), ctypes.c_double(tol), None if flow_ptr is None else _lib.dptr(flow_ptr), _lib.ptr(hit)))
+        prev_ptr, cur_ptr, labels_ptr, ny, nx, _lib.ptr(cy), _lib.ptr(cx), _lib.ptr(present), cy.size, attachment, tightness,
+        int(num_warp), int(num_iter), tol, flow_ptr, _lib.ptr(hit)))
     return hit
 
 
@@ -251,6 +247,6 @@ def piv_sample_dev(flow_ptr, labels_ptr, ny, nx, prev_table):
     """tip_piv_sample_max3_i32_dev: piv_lookup_dev's sampling and look-up on a given device (2, ny, nx) float32 flow."""
     cy, cx, present = _piv_rows(prev_table)
     hit = np.empty(cy.shape, np.int32)
-    _lib.check(_lib.lib().tip_piv_sample_max3_i32_dev(_lib.dptr(flow_ptr), _lib.dptr(labels_ptr), int(ny), int(nx), _lib.ptr(cy),
-                                                      _lib.ptr(cx), _lib.ptr(present), ctypes.c_int64(cy.size), _lib.ptr(hit)))
+    _lib.check(_lib.lib().tip_piv_sample_max3_i32_dev(flow_ptr, labels_ptr, ny, nx, _lib.ptr(cy), _lib.ptr(cx),
+                                                      _lib.ptr(present), cy.size, _lib.ptr(hit)))
     return hit

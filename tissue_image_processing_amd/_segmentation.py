@@ -45,8 +45,8 @@ def watershed_segmentation(image, imgthresh, stdeviation, blocksize, return_flag
         d_lab = _lib.DeviceBuffer(labels.nbytes)
         taps = _taps(stdeviation)
         _lib.check(lib.tip_watershed_segmentation_f64_dev(
-            _lib.dptr(d_img.ptr), _lib.dptr(d_lab.ptr), Y, X, ctypes.c_double(imgthresh), _lib.ptr(taps),
-            0 if taps is None else taps.size, int(blocksize), ctypes.byref(flags)))
+            d_img.ptr, d_lab.ptr, Y, X, imgthresh, _lib.ptr(taps), 0 if taps is None else taps.size, int(blocksize),
+            ctypes.byref(flags)))
         _lib.check(lib.tip_sync())
         labels = d_lab.download((Y, X), np.int32)
         d_img.free()
@@ -83,8 +83,7 @@ def label(input, background=None, return_num=False, connectivity=None):
     bg = 0 if background is None else int(background)
     out = np.empty(a32.shape, np.int32)
     n = ctypes.c_int32(0)
-    _lib.check(_lib.lib().tip_label4_i32(_lib.ptr(a32), ctypes.c_int32(bg), _lib.ptr(out), a32.shape[0], a32.shape[1],
-                                         ctypes.byref(n)))
+    _lib.check(_lib.lib().tip_label4_i32(_lib.ptr(a32), bg, _lib.ptr(out), a32.shape[0], a32.shape[1], ctypes.byref(n)))
     out = out.astype(np.int64)  # skimage returns the platform integer
     return (out, n.value) if return_num else out
 
@@ -157,8 +156,8 @@ def neighbor_pairs(labels, cap=None):
     while True:
         pairs = np.empty((cap, 2), np.int32)
         n = ctypes.c_int64(0)
-        rc = _lib.lib().tip_neighbor_pairs_i32(_lib.ptr(labels), labels.shape[0], labels.shape[1], _lib.ptr(pairs),
-                                               ctypes.c_int64(cap), ctypes.byref(n))
+        rc = _lib.lib().tip_neighbor_pairs_i32(_lib.ptr(labels), labels.shape[0], labels.shape[1], _lib.ptr(pairs), cap,
+                                               ctypes.byref(n))
         if rc == _lib.TIP_ERR_OVERFLOW and grow and cap < 8 * labels.size:
             cap *= 8
             continue
@@ -185,7 +184,7 @@ def label_order_stats(labels, img, nlab, ranks):
     lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32)
     lo = np.empty(nlab, np.float64)
     hi = np.empty(nlab, np.float64)
-    _lib.check(_lib.lib().tip_label_order_stats_f64(_lib.ptr(lab), _lib.ptr(img), img.shape[0], img.shape[1], int(nlab),
+    _lib.check(_lib.lib().tip_label_order_stats_f64(_lib.ptr(lab), _lib.ptr(img), img.shape[0], img.shape[1], nlab,
                                                     _lib.ptr(ranks), _lib.ptr(lo), _lib.ptr(hi)))
     return lo, hi
 
@@ -228,10 +227,9 @@ def cell_types_dev(labels_ptr, marker_ptr, y, x, n, percentage_above_threshold, 
     taps = None if not peak_window_size else np.ascontiguousarray(peak_taps, dtype=np.float64)
     q_over_100 = (100 - percentage_above_threshold) / 100.0      # percentile_per_label's q / 100.0, q = 100 - p
     _lib.check(_lib.lib().tip_cell_types_i32_dev(
-        _lib.dptr(labels_ptr), _lib.dptr(marker_ptr), int(y), int(x), int(n), ctypes.c_double(q_over_100),
-        ctypes.c_double(threshold), int(peak_window_size), _lib.ptr(taps), 0 if taps is None else int(taps.size), int(type_index),
-        ctypes.c_double(min_cell_area), ctypes.c_double(max_cell_area), _lib.dptr(out_type_ptr), _lib.dptr(out_valid_ptr),
-        _lib.dptr(out_mean_ptr), _lib.dptr(out_type_map_ptr)))
+        labels_ptr, marker_ptr, y, x, n, q_over_100, threshold, int(peak_window_size), _lib.ptr(taps),
+        0 if taps is None else taps.size, int(type_index), min_cell_area, max_cell_area, out_type_ptr, out_valid_ptr,
+        out_mean_ptr, out_type_map_ptr))
 
 
 def _cell_columns(cy, cx, area, type, feat):
@@ -259,9 +257,8 @@ def window_stats(qy, qx, r2, cy, cx, area, type, feat=None, sel_bit=-1, sel_posi
     n_in, area_in, n_sel = np.zeros(m, np.int64), np.zeros(m, np.int64), np.zeros(m, np.int64)
     sum_sel = np.zeros(m, np.float64)
     _lib.check(_lib.lib().tip_window_stats_f64(
-        _lib.ptr(qy), _lib.ptr(qx), ctypes.c_int64(m), ctypes.c_double(r2), _lib.ptr(cy), _lib.ptr(cx), _lib.ptr(area), _lib.ptr(type),
-        _lib.ptr(feat), ctypes.c_int64(n), int(sel_bit), 1 if sel_positive else 0, _lib.ptr(n_in), _lib.ptr(area_in), _lib.ptr(n_sel),
-        _lib.ptr(sum_sel)))
+        _lib.ptr(qy), _lib.ptr(qx), m, r2, _lib.ptr(cy), _lib.ptr(cx), _lib.ptr(area), _lib.ptr(type), _lib.ptr(feat), n,
+        int(sel_bit), 1 if sel_positive else 0, _lib.ptr(n_in), _lib.ptr(area_in), _lib.ptr(n_sel), _lib.ptr(sum_sel)))
     return n_in, area_in, n_sel, sum_sel
 
 
@@ -280,8 +277,8 @@ def spatial_map(shape, step, r2, cy, cx, area, type, feat=None, sel_bit=-1, sel_
     out = np.empty((Y, X), np.float64)
     n_sel = np.zeros(spatial_grid_shape((Y, X), int(step)), np.int64)
     _lib.check(_lib.lib().tip_spatial_map_f64(
-        Y, X, int(step), ctypes.c_double(r2), _lib.ptr(cy), _lib.ptr(cx), _lib.ptr(area), _lib.ptr(type), _lib.ptr(feat),
-        ctypes.c_int64(n), int(sel_bit), 1 if sel_positive else 0, SPATIAL_MODES[mode], _lib.ptr(out), _lib.ptr(n_sel)))
+        Y, X, int(step), r2, _lib.ptr(cy), _lib.ptr(cx), _lib.ptr(area), _lib.ptr(type), _lib.ptr(feat), n, int(sel_bit),
+        1 if sel_positive else 0, SPATIAL_MODES[mode], _lib.ptr(out), _lib.ptr(n_sel)))
     return out, n_sel
 
 
@@ -290,19 +287,16 @@ def spatial_map_dev(shape, step, r2, cy_ptr, cx_ptr, area_ptr, type_ptr, feat_pt
     """tip_spatial_map_f64_dev: the same on DEVICE buffers (addresses), asynchronous on the calling thread's stream; the map
     stays in the caller's device buffer map_ptr ((Y, X) float64), the grid's n_sel counts in n_sel_ptr when given."""
     _lib.check(_lib.lib().tip_spatial_map_f64_dev(
-        int(shape[0]), int(shape[1]), int(step), ctypes.c_double(r2), _lib.dptr(cy_ptr), _lib.dptr(cx_ptr),
-        _lib.dptr(area_ptr), _lib.dptr(type_ptr), _lib.dptr(feat_ptr), ctypes.c_int64(n), int(sel_bit),
-        1 if sel_positive else 0, SPATIAL_MODES[mode], _lib.dptr(map_ptr), _lib.dptr(n_sel_ptr)))
+        shape[0], shape[1], int(step), r2, cy_ptr, cx_ptr, area_ptr, type_ptr, feat_ptr, n, int(sel_bit),
+        1 if sel_positive else 0, SPATIAL_MODES[mode], map_ptr, n_sel_ptr))
 
 
 def window_stats_dev(qy_ptr, qx_ptr, m, r2, cy_ptr, cx_ptr, area_ptr, type_ptr, feat_ptr, n, sel_bit, sel_positive, n_in_ptr,
                      area_in_ptr, n_sel_ptr, sum_sel_ptr):
     """tip_window_stats_f64_dev: device addresses in and out, asynchronous on the calling thread's stream."""
     _lib.check(_lib.lib().tip_window_stats_f64_dev(
-        _lib.dptr(qy_ptr), _lib.dptr(qx_ptr), ctypes.c_int64(m), ctypes.c_double(r2), _lib.dptr(cy_ptr),
-        _lib.dptr(cx_ptr), _lib.dptr(area_ptr), _lib.dptr(type_ptr), _lib.dptr(feat_ptr), ctypes.c_int64(n),
-        int(sel_bit), 1 if sel_positive else 0, _lib.dptr(n_in_ptr), _lib.dptr(area_in_ptr), _lib.dptr(n_sel_ptr),
-        _lib.dptr(sum_sel_ptr)))
+        qy_ptr, qx_ptr, m, r2, cy_ptr, cx_ptr, area_ptr, type_ptr, feat_ptr, n, int(sel_bit), 1 if sel_positive else 0,
+        n_in_ptr, area_in_ptr, n_sel_ptr, sum_sel_ptr))
 
 
 # ---- neighbour-graph features (csrc/tip_graph.hip) ------------------------------------------------------------------------------
@@ -321,7 +315,7 @@ def contact_triples(labels, cap=None):
         counts = np.empty(cap, np.int64)
         n = ctypes.c_int64(0)
         rc = _lib.lib().tip_contact_pairs_i32(_lib.ptr(labels), labels.shape[0], labels.shape[1], big, _lib.ptr(pairs),
-                                              _lib.ptr(counts), ctypes.c_int64(cap), ctypes.byref(n))
+                                              _lib.ptr(counts), cap, ctypes.byref(n))
         if rc == _lib.TIP_ERR_OVERFLOW and grow and cap < 8 * labels.size:
             cap *= 8
             continue
@@ -334,8 +328,8 @@ def contact_pairs_dev(labels_ptr, y, x, big, pairs_ptr, counts_ptr, cap):
     """tip_contact_pairs_i32_dev: the triples of a DEVICE label map left in device buffers of `cap` rows; returns their number
     (the call waits for the stream)."""
     n = ctypes.c_int64(0)
-    _lib.check(_lib.lib().tip_contact_pairs_i32_dev(_lib.dptr(labels_ptr), int(y), int(x), int(big), _lib.dptr(pairs_ptr),
-                                                    _lib.dptr(counts_ptr), ctypes.c_int64(cap), ctypes.byref(n)))
+    _lib.check(_lib.lib().tip_contact_pairs_i32_dev(labels_ptr, y, x, big, pairs_ptr, counts_ptr, cap,
+                                                    ctypes.byref(n)))
     return int(n.value)
 
 
@@ -366,14 +360,14 @@ def _two_calls(entry, head, first, counts, dtypes, want_rows=True):
     them `counts`, the rows' lengths) and no rows; the exclusive scan of the lengths on the host; a second call that fills one
     zeroed array per dtype at those offsets.  Returns (offsets int64[m + 1], one array per dtype), or () without want_rows."""
     no_rows = (None,) * (1 + len(dtypes))
-    _lib.check(entry(*head, *[_lib.ptr(a) for a in first], *no_rows, ctypes.c_int64(0)))
+    _lib.check(entry(*head, *[_lib.ptr(a) for a in first], *no_rows, 0))
     if not want_rows:
         return ()
     off = np.zeros(counts.size + 1, np.int64)
     off[1:] = np.cumsum(counts)
     rows = [np.zeros(int(off[-1]), dt) for dt in dtypes]
     if off[-1]:
-        _lib.check(entry(*head, *(None,) * len(first), _lib.ptr(off), *[_lib.ptr(r) for r in rows], ctypes.c_int64(int(off[-1]))))
+        _lib.check(entry(*head, *(None,) * len(first), _lib.ptr(off), *[_lib.ptr(r) for r in rows], off[-1]))
     return (off, *rows)
 
 
@@ -389,17 +383,16 @@ def neighbor_csr(pairs, n, working=None, cap=None):
     offsets = np.zeros(int(n) + 1, np.int32)
     adj = np.zeros(cap, np.int32)
     n_adj = ctypes.c_int64(0)
-    _lib.check(_lib.lib().tip_neighbor_csr_i32(_lib.ptr(pairs), ctypes.c_int64(pairs.shape[0]), ctypes.c_int64(n), _lib.ptr(working),
-                                               _lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(cap), ctypes.byref(n_adj)))
+    _lib.check(_lib.lib().tip_neighbor_csr_i32(_lib.ptr(pairs), pairs.shape[0], n, _lib.ptr(working), _lib.ptr(offsets),
+                                               _lib.ptr(adj), cap, ctypes.byref(n_adj)))
     return offsets, adj[:n_adj.value].copy()
 
 
 def neighbor_csr_dev(pairs_ptr, n_pairs, n, working_ptr, offsets_ptr, adj_ptr, cap, want_count=False):
     """tip_neighbor_csr_i32_dev on device addresses; asynchronous unless want_count (then the entry count comes back)."""
     n_adj = ctypes.c_int64(0)
-    _lib.check(_lib.lib().tip_neighbor_csr_i32_dev(_lib.dptr(pairs_ptr), ctypes.c_int64(n_pairs), ctypes.c_int64(n),
-                                                   _lib.dptr(working_ptr), _lib.dptr(offsets_ptr), _lib.dptr(adj_ptr),
-                                                   ctypes.c_int64(cap), ctypes.byref(n_adj) if want_count else None))
+    _lib.check(_lib.lib().tip_neighbor_csr_i32_dev(pairs_ptr, n_pairs, n, working_ptr, offsets_ptr, adj_ptr, cap,
+                                                   ctypes.byref(n_adj) if want_count else None))
     return int(n_adj.value) if want_count else None
 
 
@@ -409,17 +402,16 @@ def graph_counts(offsets, adj, valid, empty, type, query=None, mode="all", sel_b
     mode, bit = _selector(mode, sel_bit)
     out = np.zeros(m, np.int64)
     _lib.check(_lib.lib().tip_graph_counts_i32(
-        _lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(n), ctypes.c_int64(adj.size), _lib.ptr(valid), _lib.ptr(empty), _lib.ptr(type),
-        _lib.ptr(query), ctypes.c_int64(m), mode, bit, 1 if sel_positive else 0, _lib.ptr(out)))
+        _lib.ptr(offsets), _lib.ptr(adj), n, adj.size, _lib.ptr(valid), _lib.ptr(empty), _lib.ptr(type), _lib.ptr(query), m,
+        mode, bit, 1 if sel_positive else 0, _lib.ptr(out)))
     return out
 
 
 def graph_counts_dev(offsets_ptr, adj_ptr, n, n_adj, valid_ptr, empty_ptr, type_ptr, query_ptr, m, mode, sel_bit, sel_positive, out_ptr):
     mode, bit = _selector(mode, sel_bit)
     _lib.check(_lib.lib().tip_graph_counts_i32_dev(
-        _lib.dptr(offsets_ptr), _lib.dptr(adj_ptr), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr),
-        _lib.dptr(empty_ptr), _lib.dptr(type_ptr), _lib.dptr(query_ptr), ctypes.c_int64(m), mode, bit,
-        1 if sel_positive else 0, _lib.dptr(out_ptr)))
+        offsets_ptr, adj_ptr, n, n_adj, valid_ptr, empty_ptr, type_ptr, query_ptr, m, mode, bit, 1 if sel_positive else 0,
+        out_ptr))
 
 
 def graph_second(offsets, adj, valid, type, query=None, sel_bit=None, sel_positive=True, members=True):
@@ -428,8 +420,8 @@ def graph_second(offsets, adj, valid, type, query=None, sel_bit=None, sel_positi
     offsets, adj, n, valid, _, type, query, m = _graph_args(offsets, adj, valid, None, type, query)
     bit = -1 if sel_bit is None else int(sel_bit)
     sizes = np.zeros(m, np.int64)
-    head = (_lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(n), ctypes.c_int64(adj.size), _lib.ptr(valid), _lib.ptr(type), _lib.ptr(query),
-            ctypes.c_int64(m), bit, 1 if sel_positive else 0)
+    head = (_lib.ptr(offsets), _lib.ptr(adj), n, adj.size, _lib.ptr(valid), _lib.ptr(type), _lib.ptr(query), m, bit,
+            1 if sel_positive else 0)
     rows = _two_calls(_lib.lib().tip_graph_second_i32, head, (sizes,), sizes, (np.int32,), members)
     return (sizes, *rows) if members else sizes
 
@@ -437,10 +429,8 @@ def graph_second(offsets, adj, valid, type, query=None, sel_bit=None, sel_positi
 def graph_second_dev(offsets_ptr, adj_ptr, n, n_adj, valid_ptr, type_ptr, query_ptr, m, sel_bit, sel_positive, sizes_ptr,
                      member_offsets_ptr=None, members_ptr=None, members_cap=0):
     _lib.check(_lib.lib().tip_graph_second_i32_dev(
-        _lib.dptr(offsets_ptr), _lib.dptr(adj_ptr), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr),
-        _lib.dptr(type_ptr), _lib.dptr(query_ptr), ctypes.c_int64(m), -1 if sel_bit is None else int(sel_bit),
-        1 if sel_positive else 0, _lib.dptr(sizes_ptr), _lib.dptr(member_offsets_ptr), _lib.dptr(members_ptr),
-        ctypes.c_int64(members_cap)))
+        offsets_ptr, adj_ptr, n, n_adj, valid_ptr, type_ptr, query_ptr, m, -1 if sel_bit is None else int(sel_bit),
+        1 if sel_positive else 0, sizes_ptr, member_offsets_ptr, members_ptr, members_cap))
 
 
 def contact_sums(pairs, counts, offsets, adj, valid, type, query=None, mode="all", sel_bit=None, sel_positive=True, values=False):
@@ -453,8 +443,8 @@ def contact_sums(pairs, counts, offsets, adj, valid, type, query=None, mode="all
         raise ValueError("%d pairs with %d counts" % (pairs.shape[0], counts.size))
     mode, bit = _selector(mode, sel_bit)
     sums, n_sel = np.zeros(m, np.int64), np.zeros(m, np.int64)
-    head = (_lib.ptr(pairs), _lib.ptr(counts), ctypes.c_int64(counts.size), _lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(n),
-            ctypes.c_int64(adj.size), _lib.ptr(valid), _lib.ptr(type), _lib.ptr(query), ctypes.c_int64(m), mode, bit, 1 if sel_positive else 0)
+    head = (_lib.ptr(pairs), _lib.ptr(counts), counts.size, _lib.ptr(offsets), _lib.ptr(adj), n, adj.size, _lib.ptr(valid),
+            _lib.ptr(type), _lib.ptr(query), m, mode, bit, 1 if sel_positive else 0)
     rows = _two_calls(_lib.lib().tip_contact_sums_i32, head, (sums, n_sel), n_sel, (np.int64, np.int32), values)
     if not values:
         return sums
@@ -466,10 +456,8 @@ def contact_sums_dev(pairs_ptr, counts_ptr, n_triples, offsets_ptr, adj_ptr, n, 
                      sel_positive, sums_ptr, n_sel_ptr=None, value_offsets_ptr=None, values_ptr=None, value_labels_ptr=None, values_cap=0):
     mode, bit = _selector(mode, sel_bit)
     _lib.check(_lib.lib().tip_contact_sums_i32_dev(
-        _lib.dptr(pairs_ptr), _lib.dptr(counts_ptr), ctypes.c_int64(n_triples), _lib.dptr(offsets_ptr), _lib.dptr(adj_ptr),
-        ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(valid_ptr), _lib.dptr(type_ptr), _lib.dptr(query_ptr),
-        ctypes.c_int64(m), mode, bit, 1 if sel_positive else 0, _lib.dptr(sums_ptr), _lib.dptr(n_sel_ptr),
-        _lib.dptr(value_offsets_ptr), _lib.dptr(values_ptr), _lib.dptr(value_labels_ptr), ctypes.c_int64(values_cap)))
+        pairs_ptr, counts_ptr, n_triples, offsets_ptr, adj_ptr, n, n_adj, valid_ptr, type_ptr, query_ptr, m, mode, bit,
+        1 if sel_positive else 0, sums_ptr, n_sel_ptr, value_offsets_ptr, values_ptr, value_labels_ptr, values_cap))
 
 
 # ---- hexatic order and neighbour correlations (csrc/tip_order.hip) ----------------------------------------------------------------
@@ -490,16 +478,15 @@ def delaunay_neighbors(py, px, members=True):
     if n > 1 and np.isfinite(py).all() and np.isfinite(px).all() and np.unique(np.stack([py, px], axis=1), axis=0).shape[0] != n:
         raise ValueError("delaunay_neighbors: two points have the same coordinates")
     sizes = np.zeros(n, np.int64)
-    head = (_lib.ptr(py), _lib.ptr(px), ctypes.c_int64(n))
+    head = (_lib.ptr(py), _lib.ptr(px), n)
     rows = _two_calls(_lib.lib().tip_delaunay_neighbors_f64, head, (sizes,), sizes, (np.int32,), members)
     return (sizes, *rows) if members else sizes
 
 
 def delaunay_neighbors_dev(py_ptr, px_ptr, n, sizes_ptr, member_offsets_ptr=None, members_ptr=None, members_cap=0):
     """tip_delaunay_neighbors_f64_dev: device addresses, asynchronous on the calling thread's stream; no duplicate check."""
-    _lib.check(_lib.lib().tip_delaunay_neighbors_f64_dev(
-        _lib.dptr(py_ptr), _lib.dptr(px_ptr), ctypes.c_int64(n), _lib.dptr(sizes_ptr), _lib.dptr(member_offsets_ptr),
-        _lib.dptr(members_ptr), ctypes.c_int64(members_cap)))
+    _lib.check(_lib.lib().tip_delaunay_neighbors_f64_dev(py_ptr, px_ptr, n, sizes_ptr, member_offsets_ptr, members_ptr,
+                                                         members_cap))
 
 
 def psin(cy, cx, member_offsets, members, query=None, order=6):
@@ -514,15 +501,14 @@ def psin(cy, cx, member_offsets, members, query=None, order=6):
     if query is not None and query.size != m:
         raise ValueError("%d query rows with %d member rows" % (query.size, m))
     out = np.zeros(m, np.float64)
-    _lib.check(_lib.lib().tip_psin_f64(_lib.ptr(cy), _lib.ptr(cx), ctypes.c_int64(cy.size), _lib.ptr(query), ctypes.c_int64(m), _lib.ptr(moff),
-                                       _lib.ptr(mem), ctypes.c_int64(mem.size), int(order), _lib.ptr(out)))
+    _lib.check(_lib.lib().tip_psin_f64(_lib.ptr(cy), _lib.ptr(cx), cy.size, _lib.ptr(query), m, _lib.ptr(moff),
+                                       _lib.ptr(mem), mem.size, int(order), _lib.ptr(out)))
     return out
 
 
 def psin_dev(cy_ptr, cx_ptr, n, query_ptr, m, member_offsets_ptr, members_ptr, n_members, order, out_ptr):
-    _lib.check(_lib.lib().tip_psin_f64_dev(
-        _lib.dptr(cy_ptr), _lib.dptr(cx_ptr), ctypes.c_int64(n), _lib.dptr(query_ptr), ctypes.c_int64(m),
-        _lib.dptr(member_offsets_ptr), _lib.dptr(members_ptr), ctypes.c_int64(n_members), int(order), _lib.dptr(out_ptr)))
+    _lib.check(_lib.lib().tip_psin_f64_dev(cy_ptr, cx_ptr, n, query_ptr, m, member_offsets_ptr, members_ptr, n_members,
+                                           int(order), out_ptr))
 
 
 def graph_neighbor_state(offsets, adj, member, state, query=None):
@@ -535,18 +521,16 @@ def graph_neighbor_state(offsets, adj, member, state, query=None):
         raise ValueError("state has %d entries for %d rows" % (state.size, n))
     nb_sum, nb_cnt = np.zeros(m, np.float64), np.zeros(m, np.int64)
     _lib.check(_lib.lib().tip_graph_neighbor_state_f64(
-        _lib.ptr(offsets), _lib.ptr(adj), ctypes.c_int64(n), ctypes.c_int64(adj.size), _lib.ptr(member), _lib.ptr(state), _lib.ptr(query),
-        ctypes.c_int64(m), _lib.ptr(nb_sum), _lib.ptr(nb_cnt)))
+        _lib.ptr(offsets), _lib.ptr(adj), n, adj.size, _lib.ptr(member), _lib.ptr(state), _lib.ptr(query), m, _lib.ptr(nb_sum),
+        _lib.ptr(nb_cnt)))
     return nb_sum, nb_cnt
 
 
 def graph_neighbor_state_dev(offsets_ptr, adj_ptr, n, n_adj, member_ptr, state_ptr, query_ptr, m, nb_sum_ptr, nb_cnt_ptr):
-    _lib.check(_lib.lib().tip_graph_neighbor_state_f64_dev(
-        _lib.dptr(offsets_ptr), _lib.dptr(adj_ptr), ctypes.c_int64(n), ctypes.c_int64(n_adj), _lib.dptr(member_ptr),
-        _lib.dptr(state_ptr), _lib.dptr(query_ptr), ctypes.c_int64(m), _lib.dptr(nb_sum_ptr), _lib.dptr(nb_cnt_ptr)))
+    _lib.check(_lib.lib().tip_graph_neighbor_state_f64_dev(offsets_ptr, adj_ptr, n, n_adj, member_ptr, state_ptr, query_ptr, m,
+                                                           nb_sum_ptr, nb_cnt_ptr))
 
 
 def order_features_dev(py_ptr, px_ptr, n, order, psi_ptr, degree_ptr):
     """tip_order_features_f64_dev: Delaunay degree (int64) and psi_order (float64) of n device points, left in device buffers."""
-    _lib.check(_lib.lib().tip_order_features_f64_dev(_lib.dptr(py_ptr), _lib.dptr(px_ptr), ctypes.c_int64(n), int(order),
-                                                     _lib.dptr(psi_ptr), _lib.dptr(degree_ptr)))
+    _lib.check(_lib.lib().tip_order_features_f64_dev(py_ptr, px_ptr, n, int(order), psi_ptr, degree_ptr))

@@ -169,11 +169,11 @@ def composed_up(st, planes, fmt, src, h, w, stream, name="", launch=None):
             d = _conv_desc(layer, planes, fmt, src, None, h, w, None, raw=part, out_h=2 * h, out_w=2 * w, stride=2, oy=py, ox=px)
             launch("%sx.%d%d %dx%d %d+0->%d x%d taps" % (name, py, px, h, w, cin, cout, d.ntaps), 2.0 * h * w * d.ntaps * cout * cin,
                    lambda: _lib.check(lib.tip_unet_conv_dev(ctypes.byref(d), stream)))
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     row_w, col_w, corner_w, bias_tab = st["border"]
     launch("%sborder %dx%d %d->%d" % (name, 2 * h, 2 * w, cin, cout), 2.0 * 2.5 * (h + w) * cin * cout,
-           lambda: _lib.check(lib.tip_unet_compose_border_dev(P(src), planes, fmt, h, w, cin, cout, P(row_w), P(col_w), P(corner_w), P(bias_tab),
-                                                              P(part), ctypes.c_float(1.0 / _F16_ACT_SCALE if fmt else 1.0), stream)))
+           lambda: _lib.check(lib.tip_unet_compose_border_dev(src.data_ptr(), planes, fmt, h, w, cin, cout, row_w.data_ptr(),
+                                                              col_w.data_ptr(), corner_w.data_ptr(), bias_tab.data_ptr(),
+                                                              part.data_ptr(), 1.0 / _F16_ACT_SCALE if fmt else 1.0, stream)))
     return part
 
 
@@ -310,10 +310,9 @@ def _launch(net, x, mode, logits):
     net.last_mode = mode                  # (bench.py / tests: which arithmetic the last forward pass really used)
     net.last_compose = tuple("u%d" % i for i in levels)      # ... and which decoder levels ran composed (empty: none)
     lib = _lib.lib()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
     H, W = int(x.shape[2]), int(x.shape[3])
     x = x.to(torch.float32).contiguous()
-    D = lambda t: ctypes.c_void_p(t.data_ptr())
     trace = getattr(net, "trace", None)       # tools/unet_layers.py: [(layer, flop, event, event)] per launch
 
     def timed(name, flop, fn):
@@ -347,8 +346,9 @@ def _launch(net, x, mode, logits):
         """Conv2D(2 -> 128, 3x3) -> ReLU -> BatchNormalization on the float32 network input"""
         out = buf(h, w, 128)
         timed("first %dx%d 2->128" % (h, w), 2.0 * h * w * 18 * 128,
-              lambda: _lib.check(lib.tip_unet_conv_first_dev(D(x), h, w, D(hw["first"]), D(hw["f:d0.c1.b"]), D(hw["f:d0.b1.s"]),
-                                                             D(hw["f:d0.b1.t"]), D(out), planes, fmt, stream)))
+              lambda: _lib.check(lib.tip_unet_conv_first_dev(x.data_ptr(), h, w, hw["first"].data_ptr(), hw["f:d0.c1.b"].data_ptr(),
+                                                             hw["f:d0.b1.s"].data_ptr(), hw["f:d0.b1.t"].data_ptr(), out.data_ptr(),
+                                                             planes, fmt, stream)))
         return out
 
     def double(blk, src, skip, h, w, pooled=None, head=None, seed=None):
@@ -389,6 +389,6 @@ def _launch(net, x, mode, logits):
             return probs
         out = torch.empty((1, 2, H, W), dtype=torch.float32, device=x.device)
         timed("head %dx%d" % (H, W), 2.0 * H * W * 256,
-              lambda: _lib.check(lib.tip_unet_head_dev(D(cur), ctypes.c_long(H * W), D(hw["head"]), D(hw["f:head.b"]), D(out), planes, fmt,
-                                                       1 if logits else 0, stream)))
+              lambda: _lib.check(lib.tip_unet_head_dev(cur.data_ptr(), H * W, hw["head"].data_ptr(), hw["f:head.b"].data_ptr(),
+                                                       out.data_ptr(), planes, fmt, 1 if logits else 0, stream)))
     return out

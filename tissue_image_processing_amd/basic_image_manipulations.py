@@ -8,7 +8,6 @@ Same function names, argument meaning, return dtypes and error behaviour as the 
                                                                      bim.py:28-188, 478-495 (host I/O around the GPU path;
                                                                      image sources: arrays, .npy, TIFF stacks, aicsimageio objects)
 """
-import ctypes
 
 import numpy as np
 
@@ -105,7 +104,7 @@ def blur_image(image, std):
     lib = _lib.lib()
     args = []
     for t in taps:
-        args += [_lib.ptr(t), ctypes.c_int(0 if t is None else t.size)]
+        args += [_lib.ptr(t), 0 if t is None else t.size]
     _lib.check(lib.tip_gaussian3d_w(_lib.ptr(src), _lib.ptr(out), dtype, shape3[0], shape3[1], shape3[2], *args))
     return out
 

@@ -33,7 +33,6 @@ above runs on them unchanged.  Each pipeline has its own predictor and each work
 `backend` supplies the per-frame compute so the same driver runs on GPUs (GpuFrameBackend) and, for the
 multi-process CPU tests, on a stand-in backend with the gloo process group.
 """
-import ctypes
 
 import numpy as np
 
@@ -243,7 +242,7 @@ class GpuFrameBackend(object):
         if self.keep_hc:
             nbytes = self.Y * self.X * 8
             keep = _lib.DeviceBuffer(nbytes)
-            _lib.check(p.lib.tip_memcpy_d2d(_lib.dptr(keep.ptr), _lib.dptr(p.d_hc.ptr), nbytes))
+            _lib.check(p.lib.tip_memcpy_d2d(keep.ptr, p.d_hc.ptr, nbytes))
             self.hc_maps[t] = keep
 
     def fetch_hc(self, t):
@@ -255,7 +254,7 @@ class GpuFrameBackend(object):
         if hasattr(stack_u16, "data_ptr"):        # a (pinned) torch tensor: copied straight from its storage
             nbytes = stack_u16.numel() * stack_u16.element_size()
             d_stack = _lib.DeviceBuffer(nbytes)
-            _lib.check(p.lib.tip_memcpy_h2d(_lib.dptr(d_stack.ptr), _lib.dptr(stack_u16.data_ptr()), nbytes))
+            _lib.check(p.lib.tip_memcpy_h2d(d_stack.ptr, stack_u16.data_ptr(), nbytes))
         else:
             d_stack = p.upload_stack(stack_u16)
         p.project(d_stack)
@@ -265,15 +264,15 @@ class GpuFrameBackend(object):
             p.segment(0)
         nbytes = self.Y * self.X * 4
         keep = _lib.DeviceBuffer(nbytes)
-        _lib.check(p.lib.tip_memcpy_d2d(_lib.dptr(keep.ptr), _lib.dptr(p.d_labels.ptr), nbytes))
+        _lib.check(p.lib.tip_memcpy_d2d(keep.ptr, p.d_labels.ptr, nbytes))
         self.labels[t] = keep
         if self.keep_planes:
             import torch
             dev = torch.device("cuda", _lib.device_for_thread() or 0)
             plane = torch.empty((self.Y, self.X), dtype=torch.float64, device=dev)
             # (the block may still be in use by kernels queued on torch's stream: order the library's copy after them)
-            _lib.check(p.lib.tip_wait_stream(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-            _lib.check(p.lib.tip_memcpy_d2d(_lib.dptr(plane.data_ptr()), _lib.dptr(p.d_proj.ptr + p.ref * self.Y * self.X * 8),
+            _lib.check(p.lib.tip_wait_stream(torch.cuda.current_stream(dev).cuda_stream))
+            _lib.check(p.lib.tip_memcpy_d2d(plane.data_ptr(), p.d_proj.ptr + p.ref * self.Y * self.X * 8,
                                             self.Y * self.X * 8))
             self.planes[t] = plane
         tab = p.cell_tables()          # (synchronises: the small per-cell arrays come to the host)
@@ -313,8 +312,8 @@ class GpuFrameBackend(object):
         qy = np.ascontiguousarray(qy, dtype=np.int64)
         qx = np.ascontiguousarray(qx, dtype=np.int64)
         out = np.empty(qy.shape, np.int32)
-        _lib.check(self.pipe.lib.tip_lookup_max3_i32_dev(_lib.dptr(self.labels[t].ptr), self.Y, self.X, _lib.ptr(qy),
-                                                          _lib.ptr(qx), qy.size, _lib.ptr(out)))
+        _lib.check(self.pipe.lib.tip_lookup_max3_i32_dev(self.labels[t].ptr, self.Y, self.X, _lib.ptr(qy), _lib.ptr(qx),
+                                                          qy.size, _lib.ptr(out)))
         return out
 
     # -- drift (T2) ------------------------------------------------------------------------------------------

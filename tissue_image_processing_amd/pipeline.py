@@ -54,17 +54,16 @@ class FramePipeline:
     def project(self, d_stack):
         """P0-P9 (sp.py:17-85) on a resident uint16 stack; asynchronous."""
         _lib.check(self.lib.tip_project_u16_dev(
-            _lib.dptr(d_stack.ptr), self.C, self.Z, self.Y, self.X, 0, self.Z, 0, self.ref,
-            1 if self.airy else 0, self.atoh, _lib.ptr(self.t05), _lib.ptr(self.t1), _lib.ptr(self.t2),
-            _lib.ptr(self.t30), _lib.dptr(self.d_proj.ptr), _lib.dptr(self.d_zmap.ptr)))
+            d_stack.ptr, self.C, self.Z, self.Y, self.X, 0, self.Z, 0, self.ref, 1 if self.airy else 0, self.atoh,
+            _lib.ptr(self.t05), _lib.ptr(self.t1), _lib.ptr(self.t2), _lib.ptr(self.t30), self.d_proj.ptr, self.d_zmap.ptr))
 
     def segment(self, channel=0):
         """W1-W3 (bim.py:446-476) on the resident projection of `channel`."""
         P = self.Y * self.X
         img = self.d_proj.ptr + channel * P * 8
         _lib.check(self.lib.tip_watershed_segmentation_f64_dev(
-            _lib.dptr(img), _lib.dptr(self.d_labels.ptr), self.Y, self.X, ctypes.c_double(self.imgthresh),
-            _lib.ptr(self.tseg), self.tseg.size, self.block, ctypes.byref(self.flags)))
+            img, self.d_labels.ptr, self.Y, self.X, self.imgthresh, _lib.ptr(self.tseg), self.tseg.size, self.block,
+            ctypes.byref(self.flags)))
 
     def segment_unet(self, predictor, atoh_channel=1, zo_channel=0):
         """U1-U5 (pl.py:90-198) on the resident projection: (atoh, zo) planes transposed to (X, Y) as gui.py:2059-2061
@@ -73,7 +72,7 @@ class FramePipeline:
         if getattr(self, "_proj_t", None) is None:
             raise RuntimeError("FramePipeline(use_torch=True) is needed for the U-Net path")
         # the projection was written on the library's stream: torch's current stream waits for it (no host round trip)
-        _lib.check(self.lib.tip_stream_wait_tip(ctypes.c_void_p(torch.cuda.current_stream(self._proj_t.device).cuda_stream)))
+        _lib.check(self.lib.tip_stream_wait_tip(torch.cuda.current_stream(self._proj_t.device).cuda_stream))
         # (atoh, zo) planes, each transposed: one straight gather + a strided view (prepare_image transposes back while it reads)
         img = self._proj_t[[atoh_channel, zo_channel]].transpose(1, 2)
         lab, hc = predictor.predict(img, return_device=True)
@@ -95,11 +94,11 @@ class FramePipeline:
         if tuple(lab.shape) != (self.Y, self.X) or tuple(hc.shape) != (self.Y, self.X):
             raise RuntimeError("segment_unet returned %s labels for a %d x %d frame" % (tuple(lab.shape), self.Y, self.X))
         P = self.Y * self.X
-        _lib.check(self.lib.tip_memcpy_d2d(_lib.dptr(self.d_labels.ptr), _lib.dptr(lab.data_ptr()), ctypes.c_size_t(P * 4)))
+        _lib.check(self.lib.tip_memcpy_d2d(self.d_labels.ptr, lab.data_ptr(), P * 4))
         if keep_hc:
             if getattr(self, "d_hc", None) is None:
                 self.d_hc = _lib.DeviceBuffer(P * 8)
-            _lib.check(self.lib.tip_memcpy_d2d(_lib.dptr(self.d_hc.ptr), _lib.dptr(hc.data_ptr()), ctypes.c_size_t(P * 8)))
+            _lib.check(self.lib.tip_memcpy_d2d(self.d_hc.ptr, hc.data_ptr(), P * 8))
         self._unet_hc = hc          # (the labels are held as self._unet_labels)
 
     def fetch_hc(self):
@@ -129,13 +128,10 @@ class FramePipeline:
         n = ncells
         base = d_tab.ptr
         o_area, o_bbox, o_sy, o_sx, o_pc, o_pairs = 0, 8 * n, 40 * n, 48 * n, 56 * n, 80 * n
-        _lib.check(self.lib.tip_regionprops_i32_dev(_lib.dptr(lab_ptr), None, LY, LX, n,
-                                                    _lib.dptr(base + o_area), _lib.dptr(base + o_bbox), _lib.dptr(base + o_sy),
-                                                    _lib.dptr(base + o_sx), _lib.dptr(base + o_pc), None))
+        _lib.check(self.lib.tip_regionprops_i32_dev(lab_ptr, None, LY, LX, n, base + o_area, base + o_bbox, base + o_sy,
+                                                    base + o_sx, base + o_pc, None))
         npairs = ctypes.c_int64(0)
-        _lib.check(self.lib.tip_neighbor_pairs_i32_dev(_lib.dptr(lab_ptr), LY, LX,
-                                                       _lib.dptr(base + o_pairs), ctypes.c_int64(16 * cap),
-                                                       ctypes.byref(npairs)))
+        _lib.check(self.lib.tip_neighbor_pairs_i32_dev(lab_ptr, LY, LX, base + o_pairs, 16 * cap, ctypes.byref(npairs)))
         npair = int(npairs.value)
         blob = d_tab.download((80 * n + 8 * npair,), np.uint8)
         i64 = blob[:80 * n].view(np.int64)
@@ -213,7 +209,7 @@ class FramePipeline:
             self._nf = _lib.DeviceBuffer(int(need * 1.5))
         base = self._nf.ptr
         rows = np.concatenate([valid, type if type is not None else np.zeros(n, np.uint8)])
-        _lib.check(self.lib.tip_memcpy_h2d(_lib.dptr(base + o_valid), _lib.ptr(rows), ctypes.c_size_t(2 * n)))
+        _lib.check(self.lib.tip_memcpy_h2d(base + o_valid, _lib.ptr(rows), 2 * n))
         seg.neighbor_csr_dev(d_pairs, npair, n, base + o_valid, base + o_off, base + o_adj, cap_adj)
         ntri = seg.contact_pairs_dev(self.d_labels.ptr, self.Y, self.X, n + 1, base + o_tri, base + o_cnt, cap_tri)
         graph = (base + o_off, base + o_adj, n, cap_adj)
@@ -259,10 +255,10 @@ class FramePipeline:
         pts = np.concatenate([cy[rows], cx[rows]])
         if not np.isfinite(pts).all():
             raise ValueError("order_features: a valid row has a non-finite centroid")
-        _lib.check(self.lib.tip_memcpy_h2d(_lib.dptr(base), _lib.ptr(pts), ctypes.c_size_t(16 * m)))
+        _lib.check(self.lib.tip_memcpy_h2d(base, _lib.ptr(pts), 16 * m))
         seg.order_features_dev(base, base + 8 * m, m, order, base + 16 * m, base + 24 * m)
         blob = np.empty(16 * m, np.uint8)
-        _lib.check(self.lib.tip_memcpy_d2h(_lib.ptr(blob), _lib.dptr(base + 16 * m), ctypes.c_size_t(16 * m)))
+        _lib.check(self.lib.tip_memcpy_d2h(_lib.ptr(blob), base + 16 * m, 16 * m))
         out["psi6"][rows] = blob[:8 * m].view(np.float64)
         out["voronoi_neighbors"][rows] = blob[8 * m:].view(np.int64)
         return out

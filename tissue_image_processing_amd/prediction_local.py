@@ -62,7 +62,7 @@ def shares_runtime_with_torch(t):
     idx = t.device.index if t.device.index is not None else 0
     ok = _shared_runtime.get(idx)
     if ok is None:
-        ok = _lib.load().tip_pointer_device(_lib.dptr(t.data_ptr())) == idx
+        ok = _lib.load().tip_pointer_device(t.data_ptr()) == idx
         _shared_runtime[idx] = ok
     return ok
 
@@ -242,9 +242,8 @@ class _UNet(object):
                 and shares_runtime_with_torch(x)):
             lib = _lib.lib()
             stream = torch.cuda.current_stream(x.device).cuda_stream
-            _lib.check(lib.tip_bias_relu_affine_f32_dev(_lib.dptr(x.data_ptr()), _lib.dptr(bias.data_ptr()),
-                                                        _lib.dptr(scale.data_ptr()), _lib.dptr(shift.data_ptr()),
-                                                        ctypes.c_long(x.numel()), int(x.shape[1]), ctypes.c_void_p(stream)))
+            _lib.check(lib.tip_bias_relu_affine_f32_dev(x.data_ptr(), bias.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                                        x.numel(), x.shape[1], stream))
             return x
         x = torch.nn.functional.relu(x + bias.view(1, -1, 1, 1))
         return x * scale + shift
@@ -461,9 +460,8 @@ class SegmentationPredictor:
             padded = torch.empty((1, C, first_axis_pixels, second_axis_pixels), dtype=torch.float32, device=t.device)
             kind = 2 if integer_in else (1 if single_in else 0)
             _lib.check(_lib.lib().tip_unet_prepare_f64_dev(
-                _lib.dptr(t.data_ptr()), C, Y, X, ctypes.c_long(t.stride(0)), ctypes.c_long(t.stride(1)), ctypes.c_long(t.stride(2)), kind,
-                _lib.dptr(padded.data_ptr()), second_axis_pixels, first_axis_pixels,
-                ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)))
+                t.data_ptr(), C, Y, X, t.stride(0), t.stride(1), t.stride(2), kind, padded.data_ptr(), second_axis_pixels,
+                first_axis_pixels, torch.cuda.current_stream(t.device).cuda_stream))
             return padded, npad
         chans = []
         for c in range(C):
@@ -533,11 +531,10 @@ class SegmentationPredictor:
         lab = torch.empty((Xn, Yn), dtype=torch.int32, device=p0.device)
         hc = torch.empty((Xn, Yn), dtype=torch.float64, device=p0.device)
         stream = torch.cuda.current_stream(p0.device).cuda_stream
-        _lib.check(lib.tip_wait_stream(ctypes.c_void_p(stream)))
+        _lib.check(lib.tip_wait_stream(stream))
         flags = ctypes.c_int32(0)
-        rc = lib.tip_unet_tail_dev(_lib.dptr(p0.data_ptr()), 0 if p0.dtype == torch.float32 else 1, ctypes.c_long(int(p0.stride(0))),
-                                   Xn, Yn, ctypes.c_double(thr), _lib.dptr(lab.data_ptr()), _lib.dptr(hc.data_ptr()),
-                                   ctypes.byref(flags))
+        rc = lib.tip_unet_tail_dev(p0.data_ptr(), 0 if p0.dtype == torch.float32 else 1, p0.stride(0), Xn, Yn, thr,
+                                   lab.data_ptr(), hc.data_ptr(), ctypes.byref(flags))
         self.last_flags = flags.value
         self.last_markers = int(lib.tip_last_watershed_labels())
         _lib.check(rc)

@@ -9,7 +9,6 @@ movie_surface_projection's default use) and bin_size > 1 with methods 'max_avera
 
 _METHODS = {"max_averages": 0, "max_std": 1, "multi_channel": 2}
 _MANIFOLD = 16                 # TIP_PROJECT_MANIFOLD (include/tissue_hip.h)
-import ctypes
 
 import numpy as np
 

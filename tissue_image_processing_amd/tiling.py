@@ -15,7 +15,6 @@ stages on the full plane.  Exchange steps: one all-reduce (histograms), one gath
 `backend` supplies the per-tile compute so that the same driver runs on GPUs (GpuTileBackend) and, for the multi-process
 CPU tests, on a stand-in with the gloo process group.
 """
-import ctypes
 
 import numpy as np
 
@@ -56,10 +55,9 @@ class GpuTileBackend(object):
         d = _lib.DeviceBuffer(tile_u16.nbytes).upload(tile_u16)
         self.resident[key] = (d, tile_u16.shape)
         h = _lib.DeviceBuffer(65536 * 8)
-        _lib.check(self.lib.tip_memset(_lib.dptr(h.ptr), 0, ctypes.c_size_t(65536 * 8)))
+        _lib.check(self.lib.tip_memset(h.ptr, 0, 65536 * 8))
         y0, y1, x0, x1 = box
-        _lib.check(self.lib.tip_hist_u16_box_dev(_lib.dptr(d.ptr), C, Z, Yt, Xt, self.ref, 0, Z, int(y0), int(y1), int(x0), int(x1),
-                                                 1 if self.airy else 0, _lib.dptr(h.ptr)))
+        _lib.check(self.lib.tip_hist_u16_box_dev(d.ptr, C, Z, Yt, Xt, self.ref, 0, Z, y0, y1, x0, x1, 1 if self.airy else 0, h.ptr))
         out = h.download((65536,), np.uint64)
         h.free()
         return out
@@ -72,9 +70,9 @@ class GpuTileBackend(object):
         h = _lib.DeviceBuffer(65536 * 8).upload(np.ascontiguousarray(hist, dtype=np.uint64))
         dp, dz = _lib.DeviceBuffer(C * Yt * Xt * 8), _lib.DeviceBuffer(Yt * Xt * 8)
         t05, t1, t2, t30 = (gaussian_taps(s) for s in (0.5, 1.0, 2.0, 30.0))
-        _lib.check(self.lib.tip_project_u16_hist_dev(_lib.dptr(d.ptr), C, Z, Yt, Xt, 0, Z, 0, self.ref, 1 if self.airy else 0,
+        _lib.check(self.lib.tip_project_u16_hist_dev(d.ptr, C, Z, Yt, Xt, 0, Z, 0, self.ref, 1 if self.airy else 0,
                                                      self.atoh, _lib.ptr(t05), _lib.ptr(t1), _lib.ptr(t2), _lib.ptr(t30),
-                                                     _lib.dptr(h.ptr), _lib.dptr(dp.ptr), _lib.dptr(dz.ptr)))
+                                                     h.ptr, dp.ptr, dz.ptr))
         proj, zmap = dp.download((C, Yt, Xt), np.float64), dz.download((Yt, Xt), np.int64)
         for b in (d, h, dp, dz):
             b.free()

@@ -18,7 +18,6 @@ reference's state / cache / persistence code (ti.py:193-353, 3462-3823) stays th
     find_second_order_neighbors, calculate_contact_length,     tip_graph_second_i32, tip_contact_pairs_i32 + tip_contact_sums_i32
     calculate_contact_lengths
 """
-import ctypes
 
 import numpy as np
 import pandas as pd
@@ -430,8 +429,8 @@ class TissueHipMixin(object):
             qx = np.round(prev["cx"]).astype(np.int64)
             hit = np.empty(qy.shape, np.int32)
             d_lab = _lib.DeviceBuffer(lab.nbytes).upload(lab)
-            _lib.check(_lib.lib().tip_lookup_max3_i32_dev(_lib.dptr(d_lab.ptr), lab.shape[0], lab.shape[1], _lib.ptr(qy),
-                                                         _lib.ptr(qx), ctypes.c_int64(qy.size), _lib.ptr(hit)))
+            _lib.check(_lib.lib().tip_lookup_max3_i32_dev(d_lab.ptr, lab.shape[0], lab.shape[1], _lib.ptr(qy), _lib.ptr(qx),
+                                                         qy.size, _lib.ptr(hit)))
             d_lab.free()
             hit = np.where(prev["empty"] == 0, hit, -1)
             ids = assign_track_ids(prev["ids"], hit, table.shape[0])
@@ -693,8 +692,8 @@ class TissueHipMixin(object):
         cell_ids = np.ascontiguousarray(np.insert(cells_info.label.to_numpy(), 0, 0), dtype=np.int64)
         lab32 = np.ascontiguousarray(labels, dtype=np.int32)
         out = np.empty(lab32.shape, np.int64)
-        _lib.check(_lib.lib().tip_lut_gather_i32(_lib.ptr(lab32), _lib.ptr(cell_ids), ctypes.c_int64(cell_ids.size),
-                                                 _lib.ptr(out), ctypes.c_int64(lab32.size)))
+        _lib.check(_lib.lib().tip_lut_gather_i32(_lib.ptr(lab32), _lib.ptr(cell_ids), cell_ids.size, _lib.ptr(out),
+                                                 lab32.size))
         return out
 
 
@@ -724,8 +723,8 @@ class TissueHipMixin(object):
         cx = np.ascontiguousarray([c[1] for c in centers], dtype=np.float64)
         rgb = np.ascontiguousarray(colors, dtype=np.float64).reshape(-1)
         out = np.empty((3, Y, X), np.float64)
-        _lib.check(_lib.lib().tip_draw_disks_f64(Y, X, int(cy.size), _lib.ptr(cy), _lib.ptr(cx), ctypes.c_double(float(radius)),
-                                                 _lib.ptr(rgb), _lib.ptr(out)))
+        _lib.check(_lib.lib().tip_draw_disks_f64(Y, X, cy.size, _lib.ptr(cy), _lib.ptr(cx), radius, _lib.ptr(rgb),
+                                                 _lib.ptr(out)))
         return out
 
     def draw_cell_types(self, frame_number, type_name=""):
@@ -742,7 +741,7 @@ class TissueHipMixin(object):
         types = np.ascontiguousarray(np.asarray(cell_types).astype(np.uint8))
         out = np.empty((3,) + types.shape, np.float64)
         pos, neg = np.asarray(POS_COLOR, np.float64), np.asarray(NEG_COLOR, np.float64)
-        _lib.check(_lib.lib().tip_draw_cell_types_u8(_lib.ptr(types), ctypes.c_long(types.size), must, lack, _lib.ptr(pos), _lib.ptr(neg),
+        _lib.check(_lib.lib().tip_draw_cell_types_u8(_lib.ptr(types), types.size, must, lack, _lib.ptr(pos), _lib.ptr(neg),
                                                      _lib.ptr(out)))
         return out
 
@@ -782,7 +781,7 @@ class TissueHipMixin(object):
         track = np.ascontiguousarray(self.get_trackking_labels(frame), dtype=np.int32)
         out = np.empty((3,) + track.shape, np.float64)
         cyc = np.ascontiguousarray(TRACKING_COLOR_CYCLE, dtype=np.float64).reshape(-1)
-        _lib.check(_lib.lib().tip_draw_tracking_i32(_lib.ptr(track), ctypes.c_long(track.size), _lib.ptr(cyc), _lib.ptr(out)))
+        _lib.check(_lib.lib().tip_draw_tracking_i32(_lib.ptr(track), track.size, _lib.ptr(cyc), _lib.ptr(out)))
         return out
 
     def draw_marking_points(self, frame_number, radius=5):

@@ -26,12 +26,12 @@ def time_transposes(Y, X, reps):
     for elem, label in ((4, "labels_i32"), (8, "hc_f64")):
         nbytes = Y * X * elem
         src, dst = _lib.DeviceBuffer(nbytes), _lib.DeviceBuffer(nbytes)
-        _lib.check(lib.tip_memset(_lib.dptr(src.ptr), 1, nbytes))
+        _lib.check(lib.tip_memset(src.ptr, 1, nbytes))
         ms = {"transpose": [], "memcpy_d2d": []}
         for _ in range(reps + 2):                 # (the first two calls warm up: code object, clocks)
             _lib.prof_reset()
             _lib.transpose2d_dev(src.ptr, dst.ptr, X, Y, elem)
-            _lib.check(lib.tip_memcpy_d2d(_lib.dptr(dst.ptr), _lib.dptr(src.ptr), nbytes))
+            _lib.check(lib.tip_memcpy_d2d(dst.ptr, src.ptr, nbytes))
             _lib.check(lib.tip_sync())
             rep = _lib.prof_report()
             ms["transpose"].append(rep["transpose2d_b%d" % elem][1])
@@ -76,7 +76,7 @@ def main():
     ups = []
     for _ in range(5):
         t0 = time.perf_counter()
-        _lib.check(_lib.lib().tip_memcpy_h2d(_lib.dptr(d_stack.ptr), _lib.dptr(pair[0].data_ptr()), pair[0].numel() * 2))
+        _lib.check(_lib.lib().tip_memcpy_h2d(d_stack.ptr, pair[0].data_ptr(), pair[0].numel() * 2))
         ups.append(1e3 * (time.perf_counter() - t0))
     d_stack.free()
     out["upload_ms_per_frame"] = round(float(np.median(ups)), 3)
