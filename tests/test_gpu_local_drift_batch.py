@@ -1,0 +1,216 @@
+"""GPU: the batched windowed phase correlation (tip_phase_correlation_windows_dev) against the per-window path it restates --
+tip_memcpy2d_d2d crops and phase_cross_correlation_dev, window by window.  The contract is an equality: the batch changes how
+the work is indexed and nothing in its arithmetic, so every comparison below is exact."""
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+H, W = 53, 61
+STEP, WINDOW = 8, 16
+NAMES = {np.dtype(np.uint16): "uint16", np.dtype(np.float32): "float32", np.dtype(np.float64): "float64"}
+
+
+def _blur(a, passes=3):
+    """a few (1, 2, 1) / 4 passes along both axes, edges replicated"""
+    for _ in range(passes):
+        p = np.pad(a, 1, mode="edge")
+        a = (p[:-2, 1:-1] + 2.0 * p[1:-1, 1:-1] + p[2:, 1:-1]) / 4.0
+        p = np.pad(a, 1, mode="edge")
+        a = (p[1:-1, :-2] + 2.0 * p[1:-1, 1:-1] + p[1:-1, 2:]) / 4.0
+    return a
+
+
+def _pair():
+    """A seeded uint16 pair: blurred noise, and the same texture sampled (bilinear) at smoothly displaced positions."""
+    rng = np.random.default_rng(53)
+    big = _blur(rng.random((H + 16, W + 16)))
+    big = (big - big.min()) / (big.max() - big.min())
+    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+
+    def sample(yy, xx):
+        y0, x0 = np.floor(yy).astype(int), np.floor(xx).astype(int)
+        fy, fx = yy - y0, xx - x0
+        return ((1 - fy) * (1 - fx) * big[y0, x0] + (1 - fy) * fx * big[y0, x0 + 1] + fy * (1 - fx) * big[y0 + 1, x0]
+                + fy * fx * big[y0 + 1, x0 + 1])
+
+    a = sample(y + 8.0, x + 8.0)
+    b = sample(y + 8.0 + 1.3 + 1.1 * np.sin(x / 20.0), x + 8.0 - 0.8 + 0.9 * np.cos(y / 17.0))
+    return (a * 60000.0).astype(np.uint16), (b * 60000.0).astype(np.uint16)
+
+
+def _as(dtype):
+    a, b = _pair()
+    if dtype == "uint16":
+        return a, b
+    return (a * 0.37).astype(dtype), (b * 0.37).astype(dtype)      # not whole numbers: the float paths see real fractions
+
+
+class _Frames(object):
+    """Both frames on the device for the length of a with block."""
+
+    def __init__(self, a, b):
+        self.a, self.b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+
+    def __enter__(self):
+        from tissue_image_processing_amd import _lib
+        self.da = _lib.DeviceBuffer(self.a.nbytes).upload(self.a)
+        self.db = _lib.DeviceBuffer(self.b.nbytes).upload(self.b)
+        return self
+
+    def __exit__(self, *exc):
+        self.da.free()
+        self.db.free()
+        return False
+
+
+def loop_shifts(fr, origins, ny, nx, upsample=100):
+    """The comparator: per window two tip_memcpy2d_d2d crops and one phase_cross_correlation_dev."""
+    from tissue_image_processing_amd import _lib
+    from tissue_image_processing_amd._registration import phase_cross_correlation_dev
+    lib = _lib.lib()
+    es, fw = fr.a.dtype.itemsize, fr.a.shape[1]
+    wa, wb = _lib.DeviceBuffer(ny * nx * es), _lib.DeviceBuffer(ny * nx * es)
+    out = np.empty((len(origins), 2), np.float64)
+    try:
+        for i, (ra, ca, rb, cb) in enumerate(origins):
+            for dst, src, ro, co in ((wa, fr.da, ra, ca), (wb, fr.db, rb, cb)):
+                _lib.check(lib.tip_memcpy2d_d2d(dst.ptr, nx * es, src.ptr + (int(ro) * fw + int(co)) * es, fw * es, nx * es, ny))
+            out[i] = phase_cross_correlation_dev(wa.ptr, wb.ptr, ny, nx, upsample, dtype=NAMES[fr.a.dtype])
+    finally:
+        wa.free()
+        wb.free()
+    return out
+
+
+def loop_local_drifts(a, b, shift_x, shift_y, step_size, window_size):
+    """local_drifts as a loop over the windows, on the comparator: [(window, shift_x, shift_y)]."""
+    from tissue_image_processing_amd._registration import local_drift_windows, _overlap
+    rx, ry = int(np.floor(shift_x)), int(np.floor(shift_y))
+    if a.dtype != b.dtype or a.dtype not in NAMES:
+        a, b = a.astype(np.float64), b.astype(np.float64)
+    out = []
+    with _Frames(a, b) as fr:
+        for (r0, r1, c0, c1) in local_drift_windows(a.shape, step_size, window_size):
+            pr, cr, ny = _overlap(r1 - r0, rx)
+            pc, cc, nx = _overlap(c1 - c0, ry)
+            sh = loop_shifts(fr, [(r0 + pr, c0 + pc, r0 + cr, c0 + cc)], ny, nx)[0]
+            out.append(((r0, r1, c0, c1), rx + sh[0], ry + sh[1]))
+    return out
+
+
+def _groups():
+    """{(ny, nx): origins (n, 4)} of the 30 windows of the 53 x 61 pair."""
+    from tissue_image_processing_amd._registration import local_drift_windows
+    groups = {}
+    for r0, r1, c0, c1 in local_drift_windows((H, W), STEP, WINDOW):
+        groups.setdefault((r1 - r0, c1 - c0), []).append((r0, c0, r0, c0))
+    return {k: np.array(v, np.int32) for k, v in groups.items()}
+
+
+_expected = {}
+
+
+def expected(dtype):
+    """The comparator's shifts per extent group, computed once per dtype."""
+    if dtype not in _expected:
+        a, b = _as(dtype)
+        with _Frames(a, b) as fr:
+            _expected[dtype] = {ext: loop_shifts(fr, org, *ext) for ext, org in _groups().items()}
+    return _expected[dtype]
+
+
+def test_window_groups():
+    g = _groups()
+    assert {k: len(v) for k, v in g.items()} == {(16, 16): 20, (16, 21): 4, (21, 16): 5, (21, 21): 1}
+
+
+@pytest.mark.parametrize("max_batch", [0, 3])
+@pytest.mark.parametrize("dtype", ["uint16", "float32", "float64"])
+def test_batch_equals_the_window_loop(dtype, max_batch):
+    from tissue_image_processing_amd._registration import phase_cross_correlation_windows_dev
+    want = expected(dtype)
+    a, b = _as(dtype)
+    with _Frames(a, b) as fr:
+        for (ny, nx), org in _groups().items():
+            got = phase_cross_correlation_windows_dev(fr.da.ptr, fr.db.ptr, (H, W), org, ny, nx, 100, dtype=dtype, max_batch=max_batch)
+            assert got.shape == (len(org), 2)
+            np.testing.assert_array_equal(got, want[(ny, nx)], err_msg="%dx%d windows" % (ny, nx))
+    moved = np.concatenate([v for v in want.values()])
+    assert np.abs(moved).max() > 0.5 and len(np.unique(moved[:, 0])) > 3      # the pair really moves, and not rigidly
+
+
+def test_whole_pixel_peaks_without_upsampling_and_the_whole_frame_as_one_window():
+    from tissue_image_processing_amd._registration import phase_cross_correlation_dev, phase_cross_correlation_windows_dev
+    a, b = _as("float64")
+    org = _groups()[(21, 16)]
+    with _Frames(a, b) as fr:
+        got = phase_cross_correlation_windows_dev(fr.da.ptr, fr.db.ptr, (H, W), org, 21, 16, 1, max_batch=2)
+        want = loop_shifts(fr, org, 21, 16, upsample=1)
+        whole = phase_cross_correlation_windows_dev(fr.da.ptr, fr.db.ptr, (H, W), [(0, 0, 0, 0)], H, W, 100)
+        np.testing.assert_array_equal(whole[0], phase_cross_correlation_dev(fr.da.ptr, fr.db.ptr, H, W, 100))
+    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(got, np.round(got))
+
+
+def test_differing_origins_through_local_drifts():
+    """A coarse shift crops the overlap: floors 3 and -3, extents 13 x 13 to 18 x 18, different origins in the two frames."""
+    from tissue_image_processing_amd._registration import local_drifts
+    a, b = _pair()
+    got = local_drifts(a, b, 3.4, -2.2, STEP, WINDOW)
+    want = loop_local_drifts(a, b, 3.4, -2.2, STEP, WINDOW)
+    assert len(got) == len(want) == 30
+    assert got == want
+
+
+def test_no_windows():
+    from tissue_image_processing_amd import _lib
+    from tissue_image_processing_amd._registration import phase_cross_correlation_windows_dev
+    out = phase_cross_correlation_windows_dev(0, 0, (H, W), np.zeros((0, 4), np.int32), 16, 16)
+    assert out.shape == (0, 2)
+    assert _lib.lib().tip_phase_correlation_windows_dev(None, None, 1, H, W, 0, None, 1, 4097, 100, 0, None) == 0
+
+
+def test_argument_errors_and_the_next_call():
+    """A window that leaves its frame: TIP_ERR_ARG (-2); an extent of 1 or 4097: TIP_ERR_UNSUPPORTED (-5); the thread's next
+    valid call succeeds."""
+    from tissue_image_processing_amd import _lib
+    from tissue_image_processing_amd._registration import phase_cross_correlation_windows_dev
+    lib = _lib.lib()
+    a, b = _as("float64")
+    out = np.zeros((2, 4), np.int64)
+    with _Frames(a, b) as fr:
+        def call(org, ny, nx, n=None, max_batch=0, dtype=1):
+            org = np.array(org, np.int32)
+            return lib.tip_phase_correlation_windows_dev(fr.da.ptr, fr.db.ptr, dtype, H, W, len(org) if n is None else n, _lib.ptr(org),
+                                                         ny, nx, 100, max_batch, _lib.ptr(out))
+        for org in ([(0, 0, 0, 0), (H - 15, 0, 0, 0)], [(0, 0, 0, W - 15)], [(-1, 0, 0, 0)], [(0, 0, 0, -1)]):
+            assert call(org, 16, 16) == -2
+            assert "leaves" in _lib.last_error()
+        assert call([(0, 0, 0, 0)], 1, 16) == -5
+        assert call([(0, 0, 0, 0)], 16, 1) == -5
+        assert call([(0, 0, 0, 0)], 4097, 16) == -5
+        assert call([(0, 0, 0, 0)], 16, 4097) == -5
+        assert call([(0, 0, 0, 0)], 16, 16, n=-1) == -2
+        assert call([(0, 0, 0, 0)], 16, 16, max_batch=-1) == -2
+        assert call([(0, 0, 0, 0)], 16, 16, dtype=2) == -2
+        with pytest.raises(ValueError):
+            phase_cross_correlation_windows_dev(fr.da.ptr, fr.db.ptr, (H, W), [(H - 15, 0, 0, 0)], 16, 16)
+        org = _groups()[(16, 21)]
+        got = phase_cross_correlation_windows_dev(fr.da.ptr, fr.db.ptr, (H, W), org, 16, 21, 100)
+    np.testing.assert_array_equal(got, expected("float64")[(16, 21)])
+
+
+def test_golden_pair_window_for_window():
+    """tests/golden/local_drifts.npz (216 x 216, 49 windows of 64 with step 24): local_drifts equals the loop."""
+    from tissue_image_processing_amd._registration import local_drifts
+    g = np.load(os.path.join(ROOT, "tests", "golden", "local_drifts.npz"))
+    a, b = g["images"][0], g["images"][2]
+    assert a.shape == (216, 216)
+    got = local_drifts(a, b, 0, 0, step_size=24, window_size=64)
+    want = loop_local_drifts(a, b, 0, 0, 24, 64)
+    assert len(got) == len(want) == 49
+    assert got == want

@@ -55,9 +55,12 @@ def _finish_shifts(out, ny, nx, upsample_factor):
     return shifts
 
 
+_DTYPE_CODES = {"float32": 0, "float64": 1, "uint16": 3}
+
+
 def phase_cross_correlation_dev(ref_ptr, mov_ptr, ny, nx, upsample_factor=100, dtype="float64"):
     """The same on two device-resident (ny, nx) planes (device addresses); returns the shift array."""
-    dt = {"float32": 0, "float64": 1, "uint16": 3}[dtype]
+    dt = _DTYPE_CODES[dtype]
     out = (ctypes.c_int64 * 4)()
     _lib.check(_lib.lib().tip_phase_correlation_dev(ref_ptr, mov_ptr, dt, ny, nx, int(upsample_factor), out))
     return _finish_shifts(out, ny, nx, upsample_factor)
@@ -87,10 +90,38 @@ def _overlap(n, shift):
     return 0, 0, n
 
 
+def phase_cross_correlation_windows_dev(ref_ptr, mov_ptr, frame_shape, origins, ny, nx, upsample_factor=100, dtype="float64",
+                                        max_batch=0):
+    """phase_cross_correlation_dev on n windows of one device-resident frame pair in one call
+    (tip_phase_correlation_windows_dev): ref_ptr / mov_ptr are (frame_y, frame_x) planes, window w the ny x nx block at
+    origins[w] = (ref row, ref col, mov row, mov col).  Returns the (n, 2) shifts, row w exactly what
+    phase_cross_correlation_dev gives on the two cropped windows.  max_batch: windows per pass (0: what fits the library's
+    workspace budget); the result does not depend on it."""
+    org = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1, 4)
+    n = org.shape[0]
+    out = np.zeros((n, 4), np.int64)
+    _lib.check(_lib.lib().tip_phase_correlation_windows_dev(ref_ptr, mov_ptr, _DTYPE_CODES[dtype], int(frame_shape[0]),
+                                                            int(frame_shape[1]), n, _lib.ptr(org), int(ny), int(nx),
+                                                            int(upsample_factor), int(max_batch), _lib.ptr(out)))
+    shifts = np.empty((n, 2), np.float64)
+    for w in range(n):
+        shifts[w] = _finish_shifts(out[w], ny, nx, upsample_factor)
+    return shifts
+
+
+def _windows_by_extent(items):
+    """{(ny, nx): [index, ...]} over items = [(ny, nx), ...], extents in the order of their first window."""
+    groups = {}
+    for i, ext in enumerate(items):
+        groups.setdefault(ext, []).append(i)
+    return groups
+
+
 def local_drifts(first_image, second_image, initial_shift_x=0, initial_shift_y=0, step_size=100, window_size=700):
     """[(window, shift_x, shift_y)] in upstream's loop order: Tissue.calculate_refine_drift on every window of the pair
-    (ti.py:2152-2166).  Both frames are uploaded once; every window is cut on the device (tip_memcpy2d_d2d) and goes
-    through the device phase correlation (upsample factor 100)."""
+    (ti.py:2152-2166).  Both frames are uploaded once; the windows of one extent (the edge windows run to the frame's edge:
+    at most four extents) go through the device phase correlation (upsample factor 100) in one batched call, which crops
+    them out of the frames itself and returns what the per-window call returns."""
     a = np.asarray(first_image)
     b = np.asarray(second_image)
     if a.shape != b.shape or a.ndim != 2:
@@ -101,31 +132,29 @@ def local_drifts(first_image, second_image, initial_shift_x=0, initial_shift_y=0
     a = np.ascontiguousarray(a)
     b = np.ascontiguousarray(b)
     name = {np.dtype(np.uint16): "uint16", np.dtype(np.float32): "float32", np.dtype(np.float64): "float64"}[a.dtype]
-    es = a.dtype.itemsize
     H, W = a.shape
     windows = local_drift_windows((H, W), step_size, window_size)
     if not windows:
         return []
     rx, ry = int(np.floor(initial_shift_x)), int(np.floor(initial_shift_y))
-    lib = _lib.lib()
+    origins, extents = [], []
+    for (r0, r1, c0, c1) in windows:
+        pr, cr, ny = _overlap(r1 - r0, rx)
+        pc, cc, nx = _overlap(c1 - c0, ry)
+        if ny < 2 or nx < 2:
+            raise NotImplementedError("MI355X phase correlation takes extents in [2, 4096] (got %dx%d)" % (ny, nx))
+        origins.append((r0 + pr, c0 + pc, r0 + cr, c0 + cc))
+        extents.append((ny, nx))
+    origins = np.array(origins, np.int32)
+    shifts = np.empty((len(windows), 2), np.float64)
     da, db = _lib.DeviceBuffer(a.nbytes).upload(a), _lib.DeviceBuffer(b.nbytes).upload(b)
-    big = max((r1 - r0) * (c1 - c0) for r0, r1, c0, c1 in windows) * es
-    wa, wb = _lib.DeviceBuffer(big), _lib.DeviceBuffer(big)
-    out = []
     try:
-        for (r0, r1, c0, c1) in windows:
-            pr, cr, ny = _overlap(r1 - r0, rx)
-            pc, cc, nx = _overlap(c1 - c0, ry)
-            if ny < 2 or nx < 2:
-                raise NotImplementedError("MI355X phase correlation takes extents in [2, 4096] (got %dx%d)" % (ny, nx))
-            for dst, src, ro, co in ((wa, da, r0 + pr, c0 + pc), (wb, db, r0 + cr, c0 + cc)):
-                _lib.check(lib.tip_memcpy2d_d2d(dst.ptr, nx * es, src.ptr + (ro * W + co) * es, W * es, nx * es, ny))
-            sh = phase_cross_correlation_dev(wa.ptr, wb.ptr, ny, nx, 100, dtype=name)
-            out.append(((r0, r1, c0, c1), rx + sh[-2], ry + sh[-1]))
+        for (ny, nx), idx in _windows_by_extent(extents).items():
+            shifts[idx] = phase_cross_correlation_windows_dev(da.ptr, db.ptr, (H, W), origins[idx], ny, nx, 100, dtype=name)
     finally:
-        for buf in (da, db, wa, wb):
+        for buf in (da, db):
             buf.free()
-    return out
+    return [(win, rx + sh[-2], ry + sh[-1]) for win, sh in zip(windows, shifts)]
 
 
 def sample_local_drift(drifts, rows, cols):

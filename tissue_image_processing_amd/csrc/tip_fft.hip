@@ -22,6 +22,20 @@ __global__ void __launch_bounds__(256) k_to_complex(const T *__restrict__ in, cp
     if (i < n) out[i] = make_double2((double)in[i], 0.0);
 }
 
+// batch: window w = blockIdx.y is the Ny x Nx block at (org[4w + side], org[4w + side + 1]) of a frame with rows of frame_x
+// elements (side 0: reference, 2: moving frame), cropped, converted and laid out contiguously (window w at out + w * Ny * Nx)
+template <typename T>
+__global__ void __launch_bounds__(256) k_load_windows(const T *__restrict__ frame, int frame_x, const int *__restrict__ org, int side,
+                                                      cplx *__restrict__ out, int Ny, int Nx)
+{
+    const long n = (long)Ny * Nx;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int w = blockIdx.y, y = (int)(i / Nx), x = (int)(i - (long)y * Nx);
+    const long r0 = org[4 * w + side], c0 = org[4 * w + side + 1];
+    out[(long)w * n + i] = make_double2((double)frame[(r0 + y) * frame_x + c0 + x], 0.0);
+}
+
 __global__ void __launch_bounds__(256) k_twiddles(cplx *__restrict__ w, int N)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -151,9 +165,12 @@ __global__ void __launch_bounds__(256) k_fft_rows_bluestein(cplx *__restrict__ d
     }
 }
 
+// (blockIdx.z: the window of a batch, rows * cols elements each)
 __global__ void __launch_bounds__(256) k_transpose_c(const cplx *__restrict__ in, cplx *__restrict__ out, int rows, int cols)
 {
     __shared__ double2 t[16][17];
+    in += (long)blockIdx.z * rows * cols;
+    out += (long)blockIdx.z * rows * cols;
     const int bx = blockIdx.x * 16, by = blockIdx.y * 16;
     const int lx = threadIdx.x & 15, ly = threadIdx.x >> 4;
     if (by + ly < rows && bx + lx < cols) t[ly][lx] = in[(long)(by + ly) * cols + bx + lx];
@@ -167,10 +184,13 @@ __global__ void __launch_bounds__(256) k_cmul_conj(const cplx *__restrict__ a, c
     if (i < n) { const cplx x = a[i], y = b[i]; out[i] = make_double2(x.x * y.x + x.y * y.y, x.y * y.x - x.x * y.y); }
 }
 
-// first maximum of |z| in raster order (np.argmax): pack (|z|^2 bits, ~index) and take the max
+// first maximum of |z| in raster order (np.argmax): pack (|z|^2 bits, ~index) and take the max.  Segmented over a batch: window
+// blockIdx.y has its n elements at z + blockIdx.y * n and its own best_v / best_i entry (indices within the window)
 __global__ void __launch_bounds__(256) k_absargmax(const cplx *__restrict__ z, long n, unsigned long long *__restrict__ best_v,
                                                    unsigned long long *__restrict__ best_i)
 {
+    z += (long)blockIdx.y * n;
+    best_v += blockIdx.y;
     // two passes would be cleaner; a single one with a (value, index) lexicographic atomic is enough here:
     // |z|^2 >= 0, so its IEEE bits order like the value
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -189,15 +209,14 @@ __global__ void __launch_bounds__(256) k_absargmax2(const cplx *__restrict__ z, 
 {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    z += (long)blockIdx.y * n;
     const double m = hypot(z[i].x, z[i].y);
-    if ((unsigned long long)__double_as_longlong(m) == *best_v) atomicMin(best_i, (unsigned long long)i);
+    if ((unsigned long long)__double_as_longlong(m) == best_v[blockIdx.y]) atomicMin(best_i + blockIdx.y, (unsigned long long)i);
 }
 
 // K[u][k] = exp(-2 pi i (u - off) * fftfreq(N, ups)[k])   (skimage _upsampled_dft kernel)
-__global__ void __launch_bounds__(256) k_dft_kernel(cplx *__restrict__ K, int region, int N, double off, double ups)
+__device__ __forceinline__ cplx dft_kernel_entry(long i, int N, double off, double ups)
 {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)region * N) return;
     const int u = (int)(i / N), k = (int)(i - (long)u * N);
     const int kk = k < (N + 1) / 2 ? k : k - N;                 // numpy fftfreq ordering
     const double val = 1.0 / ((double)N * ups);                 // numpy.fft.fftfreq: integer results * (1 / (n * d))
@@ -205,7 +224,29 @@ __global__ void __launch_bounds__(256) k_dft_kernel(cplx *__restrict__ K, int re
     const double arg = ((double)u - off) * f;                    // kernel = (arange - off)[:, None] * fftfreq
     double s, c;
     sincos(-2.0 * 3.141592653589793 * arg, &s, &c);              // np.exp(-1j * 2 * pi * kernel)
-    K[i] = make_double2(c, s);
+    return make_double2(c, s);
+}
+
+__global__ void __launch_bounds__(256) k_dft_kernel(cplx *__restrict__ K, int region, int N, double off, double ups)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (long)region * N) K[i] = dft_kernel_entry(i, N, off, ups);
+}
+
+// The batch's form: window blockIdx.y takes its offset from its own coarse peak (peak[w], raster index in the Ny x Nx window)
+// on the device; axis 0: the row kernel (N = Ny), 1: the column kernel (N = Nx).  The signed whole-pixel shift s is an integer
+// and so is ups, so s * ups, its rounding onto the upsampled grid (nearbyint(s * ups) / ups = s) and dftshift - s * ups are all
+// exact in double, whatever the order or contraction of the operations: this offset and the one phase_correlation_dev forms on
+// the host are the same number, and every K entry the same bits.
+__global__ void __launch_bounds__(256) k_dft_kernel_windows(cplx *__restrict__ K, int region, int N, const unsigned long long *__restrict__ peak,
+                                                            int Nx, int axis, double dftshift, double ups)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)region * N) return;
+    const long p = (long)peak[blockIdx.y];
+    double s = axis == 0 ? (double)(p / Nx) : (double)(p % Nx);
+    if (s > floor(N / 2.0)) s -= N;
+    K[(long)blockIdx.y * region * N + i] = dft_kernel_entry(i, N, dftshift - s * ups, ups);
 }
 
 // C1[u][j] = sum_k Kx[u][k] * conj(conj(PT[k][j])) ... data = conj(P): C1[u][j] = sum_k Kx[u][k] * conj(P[j][k]);
@@ -215,6 +256,9 @@ __global__ void __launch_bounds__(256) k_updft1(const cplx *__restrict__ Kx, con
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x, u = blockIdx.y;
     if (j >= Ny) return;
+    Kx += (long)blockIdx.z * region * Nx;                       // (blockIdx.z: the window of a batch)
+    PT += (long)blockIdx.z * Nx * Ny;
+    C1 += (long)blockIdx.z * region * Ny;
     double ax = 0.0, ay = 0.0;
     const cplx *kr = Kx + (long)u * Nx;
     for (int k = 0; k < Nx; ++k) {
@@ -232,6 +276,9 @@ __global__ void __launch_bounds__(64) k_updft2(const cplx *__restrict__ Ky, cons
                                                int Ny)
 {
     const int u = blockIdx.x, v = blockIdx.y;
+    Ky += (long)blockIdx.z * region * Ny;                       // (blockIdx.z: the window of a batch)
+    C1 += (long)blockIdx.z * region * Ny;
+    out += (long)blockIdx.z * region * region;
     double ax = 0.0, ay = 0.0;
     for (int j = threadIdx.x; j < Ny; j += 64) {
         const cplx w = Ky[(long)v * Ny + j], d = C1[(long)u * Ny + j];
@@ -383,6 +430,127 @@ int phase_correlation_dev(const void *ref, const void *mov, int dtype, int Ny, i
     return TIP_OK;
 }
 
+// ---- batch: the same correlation on n windows of one frame pair, a chunk of windows per pass ------------------------------
+// Nothing in the arithmetic differs from phase_correlation_dev on the cropped windows -- the rows of all windows of a chunk
+// are more rows for the row kernels, every other kernel takes the window as a grid dimension -- so the four integers per
+// window are the same ones.  Per chunk: one load kernel per frame, the launches of one correlation, ONE stream wait.
+
+// Workspace a chunk may take when the caller leaves the chunk size open: the four complex planes plus the upsampled-DFT
+// matrices of its windows (58 windows of 700 x 700 with upsample 100, about 40 000 rows per row launch).  From this arithmetic,
+// not from a measurement.
+constexpr size_t WINDOW_BATCH_BYTES = (size_t)2 << 30;
+constexpr int WINDOW_BATCH_MAX = 65535;    // a window is a grid's y or z index
+
+template <typename T>
+static int load_windows(const void *frame, int frame_x, const int *org, int side, cplx *out, int nb, int Ny, int Nx)
+{
+    TIP_LAUNCH("load_windows", k_load_windows<T>, dim3(cdiv((long)Ny * Nx, 256), nb), dim3(256), 0, (const T *)frame, frame_x, org, side,
+               out, Ny, Nx);
+    return TIP_OK;
+}
+
+static int fft2_windows(cplx *a, cplx *tmp, int nb, int Ny, int Nx, const RowPlan &px, const RowPlan &py)   // tmp = F^T per window
+{
+    int rc;
+    if ((rc = fft_rows(a, nb * Ny, px, 0))) return rc;
+    TIP_LAUNCH("transpose_c", k_transpose_c, dim3(cdiv(Nx, 16), cdiv(Ny, 16), nb), dim3(256), 0, (const cplx *)a, tmp, Ny, Nx);
+    return fft_rows(tmp, nb * Nx, py, 0);
+}
+
+int phase_correlation_windows_dev(const void *ref, const void *mov, int dtype, int frame_y, int frame_x, int n, const int32_t *origins,
+                                  int Ny, int Nx, int upsample, int max_batch, int64_t *out4n_host)
+{
+    if (n == 0) return TIP_OK;
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (!ref || !mov || !origins || !out4n_host) return fail(TIP_ERR_ARG, "phase_correlation_windows: null pointer");
+    if (n < 0 || max_batch < 0) return fail(TIP_ERR_ARG, "phase_correlation_windows: n %d, max_batch %d", n, max_batch);
+    if (Ny < 2 || Nx < 2 || Ny > 4096 || Nx > 4096)
+        return fail(TIP_ERR_UNSUPPORTED, "phase_correlation_windows: extents must lie in [2, 4096] (got %dx%d)", Ny, Nx);
+    if (upsample < 1 || upsample > 1000) return fail(TIP_ERR_ARG, "phase_correlation_windows: upsample_factor %d", upsample);
+    if (dtype != 0 && dtype != 1 && dtype != 3) return fail(TIP_ERR_ARG, "phase_correlation_windows: dtype %d (0 f32, 1 f64, 3 u16)", dtype);
+    if (frame_y < Ny || frame_x < Nx) return fail(TIP_ERR_ARG, "phase_correlation_windows: %dx%d windows in a %dx%d frame", Ny, Nx, frame_y, frame_x);
+    for (int w = 0; w < n; ++w)
+        for (int side = 0; side < 4; side += 2) {
+            const int r0 = origins[4 * w + side], c0 = origins[4 * w + side + 1];
+            if (r0 < 0 || c0 < 0 || r0 > frame_y - Ny || c0 > frame_x - Nx)
+                return fail(TIP_ERR_ARG, "phase_correlation_windows: window %d (%dx%d at %d, %d) leaves its %dx%d frame", w, Ny, Nx, r0, c0,
+                            frame_y, frame_x);
+        }
+    const size_t nw = (size_t)Ny * Nx;
+    const int region = upsample > 1 ? (int)ceil(upsample * 1.5) : 0;
+    const size_t per_window = sizeof(cplx) * (4 * nw + (size_t)region * Nx + 2 * (size_t)region * Ny + (size_t)region * region);
+    long cap = max_batch > 0 ? max_batch : (long)(WINDOW_BATCH_BYTES / per_window);
+    if (cap < 1) cap = 1;
+    if (cap > WINDOW_BATCH_MAX) cap = WINDOW_BATCH_MAX;
+    const int nbmax = n < cap ? n : (int)cap;
+    WsGuard ws;
+    cplx *A = ws.get<cplx>(nbmax * nw), *B = ws.get<cplx>(nbmax * nw), *T1 = ws.get<cplx>(nbmax * nw), *T2 = ws.get<cplx>(nbmax * nw);
+    unsigned long long *best = ws.get<unsigned long long>(4 * (size_t)nbmax);   // coarse value, fine value | coarse index, fine index
+    int *org = ws.get<int>(4 * (size_t)n);
+    if (!A || !B || !T1 || !T2 || !best || !org) return TIP_ERR_NOMEM;
+    cplx *Kx = nullptr, *Ky = nullptr, *C1 = nullptr, *O = nullptr;
+    if (region) {
+        Kx = ws.get<cplx>((size_t)nbmax * region * Nx); Ky = ws.get<cplx>((size_t)nbmax * region * Ny);
+        C1 = ws.get<cplx>((size_t)nbmax * region * Ny); O = ws.get<cplx>((size_t)nbmax * region * region);
+        if (!Kx || !Ky || !C1 || !O) return TIP_ERR_NOMEM;
+    }
+    int rc;
+    RowPlan plx, ply;                                                        // one plan per extent for the whole call
+    if ((rc = make_plan(plx, Nx, ws)) || (rc = make_plan(ply, Ny, ws))) return rc;
+    TIP_HIP(hipMemcpyAsync(org, origins, 4 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, c.stream));
+    std::vector<unsigned long long> h(2 * (size_t)nbmax);
+    const double uf = (double)upsample, dftshift = floor(region / 2.0);
+    const long nr = (long)region * region;
+    for (int w0 = 0; w0 < n; w0 += nbmax) {
+        const int nb = n - w0 < nbmax ? n - w0 : nbmax;
+        const long tot = (long)nb * (long)nw;
+        unsigned long long *bv = best, *bi = best + 2 * (size_t)nbmax;       // [0, nb): coarse, [nbmax, nbmax + nb): fine
+        for (int side = 0; side < 4; side += 2) {
+            const void *src = side == 0 ? ref : mov;
+            cplx *dst = side == 0 ? A : B;
+            if (dtype == 0) rc = load_windows<float>(src, frame_x, org + 4 * w0, side, dst, nb, Ny, Nx);
+            else if (dtype == 1) rc = load_windows<double>(src, frame_x, org + 4 * w0, side, dst, nb, Ny, Nx);
+            else rc = load_windows<uint16_t>(src, frame_x, org + 4 * w0, side, dst, nb, Ny, Nx);
+            if (rc) return rc;
+        }
+        if ((rc = fft2_windows(A, T1, nb, Ny, Nx, plx, ply))) return rc;     // T1 = F1^T
+        if ((rc = fft2_windows(B, T2, nb, Ny, Nx, plx, ply))) return rc;     // T2 = F2^T
+        cplx *PT = A;                                                        // P^T = F1^T * conj(F2^T), window after window
+        TIP_LAUNCH("cmul_conj", k_cmul_conj, dim3(cdiv(tot, 256)), dim3(256), 0, (const cplx *)T1, (const cplx *)T2, PT, tot);
+        TIP_HIP(hipMemcpyAsync(B, PT, tot * sizeof(cplx), hipMemcpyDeviceToDevice, c.stream));
+        if ((rc = fft_rows(B, nb * Nx, ply, 1))) return rc;
+        TIP_LAUNCH("transpose_c", k_transpose_c, dim3(cdiv(Ny, 16), cdiv(Nx, 16), nb), dim3(256), 0, (const cplx *)B, T1, Nx, Ny);
+        if ((rc = fft_rows(T1, nb * Ny, plx, 1))) return rc;
+        TIP_HIP(hipMemsetAsync(bv, 0, 2 * (size_t)nbmax * 8, c.stream));
+        TIP_HIP(hipMemsetAsync(bi, 0xff, 2 * (size_t)nbmax * 8, c.stream));
+        TIP_LAUNCH("absargmax", k_absargmax, dim3(cdiv((long)nw, 256), nb), dim3(256), 0, (const cplx *)T1, (long)nw, bv, bi);
+        TIP_LAUNCH("absargmax2", k_absargmax2, dim3(cdiv((long)nw, 256), nb), dim3(256), 0, (const cplx *)T1, (long)nw,
+                   (const unsigned long long *)bv, bi);
+        if (region) {
+            TIP_LAUNCH("dft_kernel", k_dft_kernel_windows, dim3(cdiv((long)region * Nx, 256), nb), dim3(256), 0, Kx, region, Nx,
+                       (const unsigned long long *)bi, Nx, 1, dftshift, uf);
+            TIP_LAUNCH("dft_kernel", k_dft_kernel_windows, dim3(cdiv((long)region * Ny, 256), nb), dim3(256), 0, Ky, region, Ny,
+                       (const unsigned long long *)bi, Nx, 0, dftshift, uf);
+            TIP_LAUNCH("updft1", k_updft1, dim3(cdiv(Ny, 256), region, nb), dim3(256), 0, (const cplx *)Kx, (const cplx *)PT, C1, region, Nx,
+                       Ny);
+            TIP_LAUNCH("updft2", k_updft2, dim3(region, region, nb), dim3(64), 0, (const cplx *)Ky, (const cplx *)C1, O, region, Ny);
+            TIP_LAUNCH("absargmax", k_absargmax, dim3(cdiv(nr, 256), nb), dim3(256), 0, (const cplx *)O, nr, bv + nbmax, bi + nbmax);
+            TIP_LAUNCH("absargmax2", k_absargmax2, dim3(cdiv(nr, 256), nb), dim3(256), 0, (const cplx *)O, nr,
+                       (const unsigned long long *)(bv + nbmax), bi + nbmax);
+        }
+        TIP_HIP(hipMemcpyAsync(h.data(), bi, 2 * (size_t)nbmax * 8, hipMemcpyDeviceToHost, c.stream));
+        TIP_HIP(hipStreamSynchronize(c.stream));                             // the chunk's one wait
+        for (int w = 0; w < nb; ++w) {
+            int64_t *o = out4n_host + 4 * (size_t)(w0 + w);
+            const long peak = (long)h[w];
+            o[0] = peak / Nx; o[1] = peak % Nx; o[2] = 0; o[3] = 0;
+            if (region) { o[2] = (int64_t)(h[nbmax + w] / region); o[3] = (int64_t)(h[nbmax + w] % region); }
+        }
+    }
+    return TIP_OK;
+}
+
 }  // namespace tip
 
 using namespace tip;
@@ -392,6 +560,12 @@ extern "C" {
 int tip_phase_correlation_dev(const void *ref, const void *mov, int dtype, int y, int x, int upsample, int64_t *out4_host)
 {
     return phase_correlation_dev(ref, mov, dtype, y, x, upsample, out4_host);
+}
+
+int tip_phase_correlation_windows_dev(const void *ref, const void *mov, int dtype, int frame_y, int frame_x, int n, const int32_t *origins,
+                                      int ny, int nx, int upsample, int max_batch, int64_t *out4n_host)
+{
+    return phase_correlation_windows_dev(ref, mov, dtype, frame_y, frame_x, n, origins, ny, nx, upsample, max_batch, out4n_host);
 }
 
 int tip_phase_correlation(const void *ref, const void *mov, int dtype, int y, int x, int upsample, int64_t *out4)

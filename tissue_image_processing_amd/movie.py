@@ -20,6 +20,12 @@ runs the TV-L1 flow from frame t-1's plane to its own (both truncated to uint16 
 it at frame t-1's centroids with upstream's transposed indexing and looks the moved centroids up in its label map -- one
 device call per frame (tip_piv_lookup_max3_i32_dev), the flow never leaves the GPU.  Drifts are not written.
 
+With `local_drifts=...` the drift is a MAP (Tissue.fix_one_frame_tracking_using_local_drifts, ti.py:2149-2173): the owner of
+frame t correlates every window of the pair (frame t-1's plane, its own) in one batched device call per window extent
+(tip_phase_correlation_windows_dev), and every centroid of frame t-1 moves by the mean shift of the windows that contain it
+before it is looked up -- the mode between one rigid shift and the dense flow.  The window shifts stay on the owner
+(backend.local_drifts[t]).
+
 With `GpuFrameBackend(cell_types=...)` the owner of frame t also classifies its cells as calc_cell_types does (ti.py:2338-2408)
 on the resident labels and Atoh-channel projection (one device call, tip_cell_types_i32_dev): the per-row columns type, valid
 and mean_intensity, named in the backend's `extra_columns`, travel with the centroid tables, and the type map stays on the
@@ -179,6 +185,7 @@ class GpuFrameBackend(object):
         self.labels = {}   # frame -> DeviceBuffer (int32 label map)
         self.planes = {}   # frame -> torch tensor (Y, X) float64 on this GPU
         self.type_maps = {}   # frame -> DeviceBuffer (uint8 type map), with cell_types
+        self.local_drifts = {}   # frame -> [(window, row shift, column shift)] of local_drift_lookup
         self._workers = []  # persistent worker threads (process_frames)
 
     def process_frame(self, t, stack_u16):
@@ -338,6 +345,29 @@ class GpuFrameBackend(object):
         torch.cuda.current_stream(prev_plane.device).synchronize()      # the received plane is complete
         return piv_lookup_dev(prev_plane.data_ptr(), self.planes[t].data_ptr(), self.labels[t].ptr, self.Y, self.X, prev_table)
 
+    def local_drift_lookup(self, t, prev_plane, prev_table, step_size=100, window_size=700):
+        """The local-drift step of the tracker for frame t >= 1: every window of _registration.local_drift_windows((Y, X),
+        step_size, window_size) is correlated between frame t-1's plane (prev_plane) and frame t's -- float64, zero coarse
+        shift, upsample factor 100, what drift() does for the whole plane -- in one batched device call per window extent;
+        row i of prev_table (area, cy, cx) moves by the mean (row, column) shift of the windows that contain
+        (round(cy_i), round(cx_i)) and is looked up in frame t's label map: local_drift_hits.  The window shifts stay in
+        self.local_drifts[t] as [(window, row shift, column shift)]."""
+        import torch
+        from ._registration import local_drift_windows, phase_cross_correlation_windows_dev, _windows_by_extent
+        if not self.keep_planes:
+            raise ValueError("local_drift_lookup needs the reference-channel planes: GpuFrameBackend(..., keep_planes=True)")
+        windows = local_drift_windows((self.Y, self.X), step_size, window_size)
+        if not windows:
+            raise ValueError("local drifts: the %dx%d frame must exceed window_size %d in both extents" % (self.Y, self.X, window_size))
+        torch.cuda.current_stream(prev_plane.device).synchronize()      # the received plane is complete
+        origins = np.array([(r0, c0, r0, c0) for r0, _, c0, _ in windows], np.int32)
+        shifts = np.empty((len(windows), 2), np.float64)
+        for (ny, nx), idx in _windows_by_extent([(r1 - r0, c1 - c0) for r0, r1, c0, c1 in windows]).items():
+            shifts[idx] = phase_cross_correlation_windows_dev(prev_plane.data_ptr(), self.planes[t].data_ptr(), (self.Y, self.X),
+                                                              origins[idx], ny, nx, 100)
+        self.local_drifts[t] = [(win, float(sh[0]), float(sh[1])) for win, sh in zip(windows, shifts)]
+        return local_drift_hits(self.local_drifts[t], prev_table, lambda qy, qx: self.lookup(t, qy, qx))
+
     def drift(self, t, prev_plane):
         """(row shift, column shift) that registers frame t onto frame t-1: Tissue.update_drift without a stage table
         (ti.py:1982-2035 -> calculate_refine_drift with a zero coarse shift -> phase_cross_correlation(upsample 100))."""
@@ -346,6 +376,42 @@ class GpuFrameBackend(object):
         torch.cuda.current_stream(prev_plane.device).synchronize()      # the received plane is complete
         sh = phase_cross_correlation_dev(prev_plane.data_ptr(), self.planes[t].data_ptr(), self.Y, self.X, 100)
         return float(sh[0]), float(sh[1])
+
+
+def local_drift_hits(drifts, prev_table, lookup):
+    """The look-up half of the local-drift step.  drifts: [((r0, r1, c0, c1), row shift, column shift)] in window loop order;
+    row i of prev_table gets the mean shift of the windows that contain (round(cy_i), round(cx_i)) -- the shifts summed in
+    loop order, then one division by the count (ti.py:2165-2169, _registration.sample_local_drift) -- and the result is
+    lookup(round(cy - d_row), round(cx - d_col)) as int32.  A point that no window contains (upstream: 0 / 0) finds nothing: -1."""
+    from ._registration import sample_local_drift
+    cy = np.asarray(prev_table["cy"], dtype=np.float64)
+    cx = np.asarray(prev_table["cx"], dtype=np.float64)
+    d_row, d_col = sample_local_drift(drifts, np.round(cy).astype(np.int64), np.round(cx).astype(np.int64))
+    covered = ~np.isnan(d_row)
+    qy = np.where(covered, np.round(cy - np.where(covered, d_row, 0.0)), -1).astype(np.int64)
+    qx = np.where(covered, np.round(cx - np.where(covered, d_col, 0.0)), -1).astype(np.int64)
+    return np.where(covered, lookup(qy, qx), -1).astype(np.int32)
+
+
+LOCAL_DRIFT_DEFAULTS = dict(step_size=100, window_size=700)      # upstream's (ti.py:2115)
+
+
+def local_drift_options(local_drifts):
+    """None, or the step_size / window_size of process_movie's `local_drifts` (None; True: upstream's; a dict of either)."""
+    if local_drifts is None or local_drifts is False:
+        return None
+    opts = dict(LOCAL_DRIFT_DEFAULTS)
+    if local_drifts is not True:
+        if not isinstance(local_drifts, dict):
+            raise ValueError("local_drifts must be None, True or dict(step_size=..., window_size=...)")
+        unknown = set(local_drifts) - set(opts)
+        if unknown:
+            raise ValueError("local_drifts: unknown key(s) %s (known: step_size, window_size)" % sorted(unknown))
+        opts.update(local_drifts)
+    opts = {k: int(v) for k, v in opts.items()}
+    if opts["step_size"] < 1 or opts["window_size"] < 2:
+        raise ValueError("local_drifts: step_size >= 1 and window_size >= 2 (got %(step_size)d, %(window_size)d)" % opts)
+    return opts
 
 
 def pack_tables(tables, extra=()):
@@ -472,7 +538,22 @@ def link_ids(tables, drifts):
     return out
 
 
-def _validate(stitcher, estimate_drift, use_piv, backend):
+def _validate(stitcher, estimate_drift, use_piv, backend, local_drifts=None):
+    local = local_drift_options(local_drifts)
+    if local is not None:
+        if estimate_drift or use_piv:
+            raise ValueError("local_drifts, estimate_drift and use_piv are three drift sources: pass one of them")
+        if stitcher != "lookup":
+            raise ValueError("local_drifts needs stitcher='lookup' (the trackpy-model linker with local drifts is not built)")
+        if not hasattr(backend, "local_drift_lookup") or not getattr(backend, "keep_planes", True):
+            raise ValueError("local_drifts needs a backend with local_drift_lookup and the reference-channel planes "
+                             "(GpuFrameBackend(keep_planes=True))")
+        Y, X = getattr(backend, "Y", None), getattr(backend, "X", None)
+        if Y is None or X is None:
+            raise ValueError("local_drifts needs a backend that knows its frame extents (Y, X)")
+        if Y <= local["window_size"] or X <= local["window_size"]:      # upstream's loop is then empty and divides 0 by 0
+            raise ValueError("local_drifts: the %dx%d frame must exceed window_size %d in both extents"
+                             % (Y, X, local["window_size"]))
     if stitcher not in ("lookup", "linker"):
         raise ValueError("stitcher must be 'lookup' or 'linker'")
     if use_piv and estimate_drift:
@@ -517,10 +598,10 @@ def _exchange_tables(mine, local, extra, dist, rank, world, device):
     return {t: tb for part in parts for t, tb in unpack_tables(part, extra).items()}
 
 
-def _owner_lookups(mine, tables, backend, piv_planes=None):
+def _owner_lookups(mine, tables, backend, piv_planes=None, local_planes=None, local=None):
     """For each of this rank's frames t >= 1 the label of frame t under every row of frame t-1, -1 for absent (zero-area) rows:
     backend.lookup at the drift-corrected centroids, or with piv_planes (the held planes) backend.piv_lookup, whose first
-    exception ends the loop.  Returns ({t: hits}, (failed frame or -1, kind 1: IndexError / 2: other), the exception)."""
+    exception ends the loop, or with local_planes (the held planes) backend.local_drift_lookup with the options `local`.  Returns ({t: hits}, (failed frame or -1, kind 1: IndexError / 2: other), the exception)."""
     hits = {}
     for t in [t for t in mine if t >= 1]:
         prev = tables[t - 1]
@@ -529,6 +610,8 @@ def _owner_lookups(mine, tables, backend, piv_planes=None):
                 res = backend.piv_lookup(t, piv_planes.pop(t), prev)
             except Exception as e:            # the round's collectives still run: _agree_on_piv_failure tells every rank
                 return hits, (t, 1 if isinstance(e, IndexError) else 2), e
+        elif local_planes is not None:
+            res = backend.local_drift_lookup(t, local_planes.pop(t), prev, **local)
         else:
             dy, dx = tables[t]["drift"]
             res = backend.lookup(t, np.round(prev["cy"] - dy).astype(np.int64), np.round(prev["cx"] - dx).astype(np.int64))
@@ -572,7 +655,7 @@ def _stitch(tables, lookups, stitcher):
 
 
 def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, device="cpu", drifts=None,
-                  estimate_drift=False, stitcher="lookup", block_frames=None, use_piv=False):
+                  estimate_drift=False, stitcher="lookup", block_frames=None, use_piv=False, local_drifts=None):
     """Runs the sharded pipeline.  frame_source(t) -> uint16 stack (or whatever backend.process_frame takes).
     Returns on rank 0: (tables per frame, track ids per frame); on other ranks (None, None).  tables[t]["drift"] holds
     the (row, column) drift used between frames t-1 and t (estimated by frame t's owner when estimate_drift).  A backend
@@ -589,6 +672,14 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
     round starts.  Any other exception of a round (a backend's, a collective's) leaves the same way: the one compute thread,
     which serves every round, finishes the round it has begun before the exception reaches the caller.
 
+    local_drifts: None, True (upstream's step_size 100, window_size 700) or dict(step_size=..., window_size=...): the local-drift
+    map as the drift source (Tissue.fix_one_frame_tracking_using_local_drifts' map, ti.py:2149-2173).  Planes are exchanged as for
+    estimate_drift, and the owner of frame t >= 1 calls backend.local_drift_lookup(t, plane of frame t-1, table of frame t-1,
+    step_size, window_size): every centroid moves by the mean shift of the windows that contain it.  tables[t]["drift"] keeps
+    the `drifts` row given; the window shifts stay on the owner (backend.local_drifts[t]).  It needs a backend with planes, frame
+    extents (Y, X) above window_size and the "lookup" stitcher, and excludes estimate_drift and use_piv (ValueError, before any
+    frame is computed).
+
     The movie is worked off in ROUNDS of `block_frames` frames per rank (plan_rounds; None: the whole shard in one round, no
     overlap).  While a thread computes round k+1 (_compute_round), this one runs round k's exchange: planes to the neighbour rank
     (exchange_planes), drift (_drift_step), all-gather of the cell tables (_exchange_tables), owner-side look-ups (_owner_lookups;
@@ -597,7 +688,8 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
     frame; rank 0 then stitches (_stitch).  Every rank runs the same rounds and joins their collectives, with empty payloads
     when it has no frame in one, so any n_frames works, including fewer frames than ranks."""
     from concurrent.futures import ThreadPoolExecutor
-    _validate(stitcher, estimate_drift, use_piv, backend)
+    _validate(stitcher, estimate_drift, use_piv, backend, local_drifts)
+    local_opts = local_drift_options(local_drifts)
     drifts = np.zeros((n_frames, 2)) if drifts is None else np.array(drifts, dtype=np.float64)
     extra = tuple(getattr(backend, "extra_columns", ()))      # further per-row columns every frame's dict carries
     rounds = plan_rounds(n_frames, rank, world, block_frames)
@@ -609,14 +701,15 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
             local = pending.result()
             if k + 1 < len(rounds):                   # the next round computes while this one is exchanged
                 pending = pool.submit(_compute_round, rounds[k + 1], frame_source, backend)
-            if estimate_drift or use_piv:             # frame t's plane goes to the owner of frame t+1, if there is one
+            if estimate_drift or use_piv or local_opts:   # frame t's plane goes to the owner of frame t+1, if there is one
                 held_planes.update(exchange_planes([t for t in mine if t + 1 < n_frames],
                                                    [t for t in upstream[k] if t + 1 < n_frames], backend, rank, world, dist))
             _drift_step(mine, local, drifts, backend, held_planes, estimate_drift)
             tables.update(_exchange_tables(mine, local, extra, dist, rank, world, device))
             if stitcher == "linker":
                 continue
-            hits, failed, error = _owner_lookups(mine, tables, backend, held_planes if use_piv else None)
+            hits, failed, error = _owner_lookups(mine, tables, backend, held_planes if use_piv else None,
+                                                 held_planes if local_opts else None, local_opts)
             if use_piv:
                 _agree_on_piv_failure(failed, error, rank, world, dist, device)
             lookups.update(_gather_lookups(hits, dist, rank, world, device))
