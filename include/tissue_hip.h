@@ -463,16 +463,17 @@ TIP_API int tip_spatial_map_f64_dev(int y, int x, int step, double r2, const dou
 /* dtype: 0 float32, 1 float64, 3 uint16; extents in [2, 4096] (powers of two: radix-2 FFT rows; anything else: Bluestein).  out4 = whole-pixel peak (row, col) of       */
 /* |ifft2(F1 conj F2)| and the peak (row, col) on the ceil(1.5*upsample)^2 upsampled grid; the caller forms the shift  */
 /* exactly as skimage does (wrap past the midpoint, round to the grid, add (fine - floor(region/2)) / upsample).       */
+/* Both are the windowed correlation below with ONE window of the frame's extent at the origin: one body, one stream wait. */
 TIP_API int tip_phase_correlation(const void *ref, const void *mov, int dtype, int y, int x, int upsample, int64_t *out4);
 TIP_API int tip_phase_correlation_dev(const void *ref, const void *mov, int dtype, int y, int x, int upsample,
                                       int64_t *out4_host);
-/* The same correlation on n windows of one DEVICE frame pair at once (the local-drift map, ti.py:2149-2173): ref and mov are  */
+/* The correlation on n windows of one DEVICE frame pair at once (the local-drift map, ti.py:2149-2173): ref and mov are  */
 /* (frame_y, frame_x) planes of `dtype`; window w is the ny x nx block at (origins[4w], origins[4w+1]) of ref and at             */
 /* (origins[4w+2], origins[4w+3]) of mov (origins: HOST int32, n x 4).  out4n_host (n x 4) receives per window exactly the four */
-/* integers tip_phase_correlation_dev returns on the two cropped windows: the batch changes how the work is indexed -- one crop- */
-/* and-convert kernel that reads the frames through their pitch, one plan per extent, the rows of all windows of a chunk in one  */
-/* row launch, the window as a grid dimension everywhere else, each window's upsampled-DFT offsets taken from its coarse peak on */
-/* the device -- and nothing in its arithmetic.  Windows go through in chunks of max_batch (0: as many as fit a fixed 2 GiB      */
+/* integers tip_phase_correlation_dev returns on the two cropped windows: a window's result does not depend on the windows      */
+/* beside it -- one crop-and-convert kernel that reads the frames through their pitch, one plan per extent, the rows of all      */
+/* windows of a chunk in one row launch, the window as a grid dimension everywhere else, each window's upsampled-DFT offsets     */
+/* taken from its coarse peak on the device.  Windows go through in chunks of max_batch (0: as many as fit a fixed 2 GiB      */
 /* workspace budget), one stream wait per chunk; results do not depend on the chunking.  ny, nx outside [2, 4096]:               */
 /* TIP_ERR_UNSUPPORTED; a window that leaves its frame, a null pointer, n < 0, max_batch < 0, another dtype: TIP_ERR_ARG;        */
 /* n == 0: TIP_OK, nothing is touched.                                                                                          */

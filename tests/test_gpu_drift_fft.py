@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import dft_restate as dr
+from oracle_guard import guarded_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -171,18 +172,6 @@ def wrapped(roll, shape):
     mid = np.array([np.fix(n / 2) for n in shape])
     s[s > mid] -= np.array(shape)[s > mid]
     return s
-
-
-def guarded_oracle(a, b, ups):
-    """the oracle's shift, after asserting on its own |cc| surfaces (numpy alone) that each winner is ahead of the runner-up by a
-    relative 1e-9: far above float64 rounding, so equality with the oracle does not hang on the last bits of either transform"""
-    from oracle import oracle as orc
-    shifts, coarse, fine = orc.phase_cross_correlation_surfaces(a, b, ups)
-    for name, s in (("coarse", coarse), ("upsampled", fine)):
-        if s is not None:
-            top = np.partition(s.ravel(), s.size - 2)[-2:]
-            assert top[1] - top[0] > 1e-9 * top[1], "%s surface: winner %r, runner-up %r" % (name, top[1], top[0])
-    return shifts
 
 
 def check_roll(ref, roll, ups, mov=None):

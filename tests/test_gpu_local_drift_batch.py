@@ -1,10 +1,14 @@
 """GPU: the batched windowed phase correlation (tip_phase_correlation_windows_dev) against the per-window path it restates --
 tip_memcpy2d_d2d crops and phase_cross_correlation_dev, window by window.  The contract is an equality: the batch changes how
-the work is indexed and nothing in its arithmetic, so every comparison below is exact."""
+the work is indexed and nothing in its arithmetic, so every comparison below is exact.  The per-window path is the same
+correlation body with one window, so that comparison pins the indexing and the chunking; the arithmetic of a batch of several
+windows is pinned against the oracle on the numpy crops (test_batch_equals_the_oracle_on_the_crops)."""
 import os
 
 import numpy as np
 import pytest
+
+from oracle_guard import guarded_oracle
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -141,6 +145,34 @@ def test_batch_equals_the_window_loop(dtype, max_batch):
             np.testing.assert_array_equal(got, want[(ny, nx)], err_msg="%dx%d windows" % (ny, nx))
     moved = np.concatenate([v for v in want.values()])
     assert np.abs(moved).max() > 0.5 and len(np.unique(moved[:, 0])) > 3      # the pair really moves, and not rigidly
+
+
+_oracle = {}
+
+
+def oracle_shifts(dtype):
+    """The oracle's shift on the numpy crops of every window, per extent group; computed once per dtype.  Every window passes
+    guarded_oracle's winner-ahead check (relative margin 1e-9 on both surfaces; the smallest margin over the 60 surfaces of a
+    dtype is about 4.06e-8), so none is left out."""
+    if dtype not in _oracle:
+        a, b = _as(dtype)
+        _oracle[dtype] = {(ny, nx): np.array([guarded_oracle(a[ra:ra + ny, ca:ca + nx], b[rb:rb + ny, cb:cb + nx], 100)
+                                              for ra, ca, rb, cb in org]) for (ny, nx), org in _groups().items()}
+    return _oracle[dtype]
+
+
+@pytest.mark.parametrize("max_batch", [0, 3])
+@pytest.mark.parametrize("dtype", ["uint16", "float32", "float64"])
+def test_batch_equals_the_oracle_on_the_crops(dtype, max_batch):
+    """All 30 windows, several per launch: the independent reference for the arithmetic of n > 1 windows."""
+    from tissue_image_processing_amd._registration import phase_cross_correlation_windows_dev
+    want = oracle_shifts(dtype)
+    assert sum(len(v) for v in want.values()) == 30
+    a, b = _as(dtype)
+    with _Frames(a, b) as fr:
+        for (ny, nx), org in _groups().items():
+            got = phase_cross_correlation_windows_dev(fr.da.ptr, fr.db.ptr, (H, W), org, ny, nx, 100, dtype=dtype, max_batch=max_batch)
+            np.testing.assert_array_equal(got, want[(ny, nx)], err_msg="%dx%d windows" % (ny, nx))
 
 
 def test_whole_pixel_peaks_without_upsampling_and_the_whole_frame_as_one_window():

@@ -1,7 +1,5 @@
 """phase_cross_correlation on MI355X (tip_phase_correlation): the drop-in for the skimage call behind
 Tissue.update_drift / calculate_refine_drift (ti.py:1941-2035) and bim.calculate_drift (bim.py:522-536)."""
-import ctypes
-
 import numpy as np
 
 from . import _lib
@@ -35,22 +33,23 @@ def phase_cross_correlation(reference_image, moving_image, upsample_factor=1, sp
     for n in (ny, nx):
         if n < 2 or n > 4096:
             raise NotImplementedError("MI355X phase correlation takes extents in [2, 4096] (got %dx%d)" % (ny, nx))
-    out = (ctypes.c_int64 * 4)()
-    _lib.check(_lib.lib().tip_phase_correlation(_lib.ptr(a), _lib.ptr(b), dt, ny, nx, int(upsample_factor), out))
-    return _finish_shifts(out, ny, nx, upsample_factor), None, None
+    out = np.zeros((1, 4), np.int64)
+    _lib.check(_lib.lib().tip_phase_correlation(_lib.ptr(a), _lib.ptr(b), dt, ny, nx, int(upsample_factor), _lib.ptr(out)))
+    return _finish_shifts(out, ny, nx, upsample_factor)[0], None, None
 
 
 def _finish_shifts(out, ny, nx, upsample_factor):
-    """skimage's closing arithmetic on the two integer peaks the library returns (whole-pixel peak, upsampled-DFT peak)."""
+    """skimage's closing arithmetic on the integer peaks the library returns, for n correlations of one extent at once:
+    out (n, 4) = whole-pixel peak (row, col), upsampled-DFT peak (row, col); returns the (n, 2) shifts."""
     shape = np.array([ny, nx])
-    shifts = np.array([out[0], out[1]], dtype=np.float64)
+    shifts = out[:, :2].astype(np.float64)
     midpoints = np.array([np.fix(s / 2) for s in shape])
-    shifts[shifts > midpoints] -= shape[shifts > midpoints]
+    shifts = np.where(shifts > midpoints, shifts - shape, shifts)
     if upsample_factor > 1:
         uf = float(upsample_factor)
         shifts = np.round(shifts * uf) / uf
         dftshift = np.fix(np.ceil(uf * 1.5) / 2.0)
-        maxima = np.array([out[2], out[3]], dtype=np.float64) - dftshift
+        maxima = out[:, 2:].astype(np.float64) - dftshift
         shifts = shifts + maxima / uf
     return shifts
 
@@ -61,9 +60,9 @@ _DTYPE_CODES = {"float32": 0, "float64": 1, "uint16": 3}
 def phase_cross_correlation_dev(ref_ptr, mov_ptr, ny, nx, upsample_factor=100, dtype="float64"):
     """The same on two device-resident (ny, nx) planes (device addresses); returns the shift array."""
     dt = _DTYPE_CODES[dtype]
-    out = (ctypes.c_int64 * 4)()
-    _lib.check(_lib.lib().tip_phase_correlation_dev(ref_ptr, mov_ptr, dt, ny, nx, int(upsample_factor), out))
-    return _finish_shifts(out, ny, nx, upsample_factor)
+    out = np.zeros((1, 4), np.int64)
+    _lib.check(_lib.lib().tip_phase_correlation_dev(ref_ptr, mov_ptr, dt, ny, nx, int(upsample_factor), _lib.ptr(out)))
+    return _finish_shifts(out, ny, nx, upsample_factor)[0]
 
 
 # ---- local drifts (ti.py:2149-2175): one refined drift per window of a frame pair ----------------------------------------
@@ -103,25 +102,28 @@ def phase_cross_correlation_windows_dev(ref_ptr, mov_ptr, frame_shape, origins, 
     _lib.check(_lib.lib().tip_phase_correlation_windows_dev(ref_ptr, mov_ptr, _DTYPE_CODES[dtype], int(frame_shape[0]),
                                                             int(frame_shape[1]), n, _lib.ptr(org), int(ny), int(nx),
                                                             int(upsample_factor), int(max_batch), _lib.ptr(out)))
-    shifts = np.empty((n, 2), np.float64)
-    for w in range(n):
-        shifts[w] = _finish_shifts(out[w], ny, nx, upsample_factor)
-    return shifts
+    return _finish_shifts(out, ny, nx, upsample_factor)
 
 
-def _windows_by_extent(items):
-    """{(ny, nx): [index, ...]} over items = [(ny, nx), ...], extents in the order of their first window."""
+def correlate_windows_by_extent(ref_ptr, mov_ptr, frame_shape, origins, extents, dtype="float64", upsample_factor=100):
+    """The (n, 2) shifts of n windows of any extents on one device-resident frame pair: origins (n, 4) as above, extents
+    [(ny, nx), ...] per window; one phase_cross_correlation_windows_dev call per distinct extent, in the order of its first
+    window (local_drift_windows gives at most four: the edge windows run to the frame's edge)."""
+    origins = np.asarray(origins, np.int32).reshape(-1, 4)
     groups = {}
-    for i, ext in enumerate(items):
-        groups.setdefault(ext, []).append(i)
-    return groups
+    for i, ext in enumerate(extents):
+        groups.setdefault(tuple(ext), []).append(i)
+    shifts = np.empty((len(origins), 2), np.float64)
+    for (ny, nx), idx in groups.items():
+        shifts[idx] = phase_cross_correlation_windows_dev(ref_ptr, mov_ptr, frame_shape, origins[idx], ny, nx, upsample_factor,
+                                                          dtype=dtype)
+    return shifts
 
 
 def local_drifts(first_image, second_image, initial_shift_x=0, initial_shift_y=0, step_size=100, window_size=700):
     """[(window, shift_x, shift_y)] in upstream's loop order: Tissue.calculate_refine_drift on every window of the pair
-    (ti.py:2152-2166).  Both frames are uploaded once; the windows of one extent (the edge windows run to the frame's edge:
-    at most four extents) go through the device phase correlation (upsample factor 100) in one batched call, which crops
-    them out of the frames itself and returns what the per-window call returns."""
+    (ti.py:2152-2166).  Both frames are uploaded once; correlate_windows_by_extent (upsample factor 100) crops the windows out
+    of them on the device and returns what the per-window call returns."""
     a = np.asarray(first_image)
     b = np.asarray(second_image)
     if a.shape != b.shape or a.ndim != 2:
@@ -145,12 +147,9 @@ def local_drifts(first_image, second_image, initial_shift_x=0, initial_shift_y=0
             raise NotImplementedError("MI355X phase correlation takes extents in [2, 4096] (got %dx%d)" % (ny, nx))
         origins.append((r0 + pr, c0 + pc, r0 + cr, c0 + cc))
         extents.append((ny, nx))
-    origins = np.array(origins, np.int32)
-    shifts = np.empty((len(windows), 2), np.float64)
     da, db = _lib.DeviceBuffer(a.nbytes).upload(a), _lib.DeviceBuffer(b.nbytes).upload(b)
     try:
-        for (ny, nx), idx in _windows_by_extent(extents).items():
-            shifts[idx] = phase_cross_correlation_windows_dev(da.ptr, db.ptr, (H, W), origins[idx], ny, nx, 100, dtype=name)
+        shifts = correlate_windows_by_extent(da.ptr, db.ptr, (H, W), origins, extents, dtype=name)
     finally:
         for buf in (da, db):
             buf.free()

@@ -7,6 +7,8 @@
 // Everything in float64 (the reference hands uint16 / float64 frames to scipy.fft -> complex128).  The library returns
 // the two integer peaks; the host turns them into the shift with numpy's own arithmetic.  Hand-written radix-2 FFT:
 // power-of-two extents up to 4096 (one block per row, the row in LDS), columns through a tiled transpose.
+// There is ONE correlation body (correlate_windows): n windows of a frame pair, a chunk of windows per pass.  The whole
+// plane (phase_correlation_dev) is the batch of one window that covers the frame.
 #include "tip_internal.h"
 
 namespace tip {
@@ -15,14 +17,7 @@ typedef double2 cplx;
 
 __device__ __forceinline__ cplx cmul(cplx a, cplx b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
-template <typename T>
-__global__ void __launch_bounds__(256) k_to_complex(const T *__restrict__ in, cplx *__restrict__ out, long n)
-{
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = make_double2((double)in[i], 0.0);
-}
-
-// batch: window w = blockIdx.y is the Ny x Nx block at (org[4w + side], org[4w + side + 1]) of a frame with rows of frame_x
+// window w = blockIdx.y is the Ny x Nx block at (org[4w + side], org[4w + side + 1]) of a frame with rows of frame_x
 // elements (side 0: reference, 2: moving frame), cropped, converted and laid out contiguously (window w at out + w * Ny * Nx)
 template <typename T>
 __global__ void __launch_bounds__(256) k_load_windows(const T *__restrict__ frame, int frame_x, const int *__restrict__ org, int side,
@@ -227,17 +222,11 @@ __device__ __forceinline__ cplx dft_kernel_entry(long i, int N, double off, doub
     return make_double2(c, s);
 }
 
-__global__ void __launch_bounds__(256) k_dft_kernel(cplx *__restrict__ K, int region, int N, double off, double ups)
-{
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (long)region * N) K[i] = dft_kernel_entry(i, N, off, ups);
-}
-
-// The batch's form: window blockIdx.y takes its offset from its own coarse peak (peak[w], raster index in the Ny x Nx window)
-// on the device; axis 0: the row kernel (N = Ny), 1: the column kernel (N = Nx).  The signed whole-pixel shift s is an integer
-// and so is ups, so s * ups, its rounding onto the upsampled grid (nearbyint(s * ups) / ups = s) and dftshift - s * ups are all
-// exact in double, whatever the order or contraction of the operations: this offset and the one phase_correlation_dev forms on
-// the host are the same number, and every K entry the same bits.
+// Window blockIdx.y takes its offset from its own coarse peak (peak[w], raster index in the Ny x Nx window) on the device, so
+// the host never waits for the coarse peak; axis 0: the row kernel (N = Ny), 1: the column kernel (N = Nx).  The signed
+// whole-pixel shift s is an integer and so is ups, so s * ups, its rounding onto the upsampled grid (np.round(s * ups) / ups
+// = s) and dftshift - s * ups are all exact in double, whatever the order or contraction of the operations: the offset is the
+// number skimage forms on the host.
 __global__ void __launch_bounds__(256) k_dft_kernel_windows(cplx *__restrict__ K, int region, int N, const unsigned long long *__restrict__ peak,
                                                             int Nx, int axis, double dftshift, double ups)
 {
@@ -334,106 +323,21 @@ static int fft_rows(cplx *data, int nrows, const RowPlan &pl, int inverse)
     return TIP_OK;
 }
 
-// rows (length Nx), transpose, rows (length Ny) -> result transposed (Nx rows of Ny) in tmp; optionally transposed back into a
-static int fft2_inplace(cplx *a, cplx *tmp, int Ny, int Nx, const RowPlan &px, const RowPlan &py, int inverse, bool leave_transposed)
+// 2-D transform of nb windows (Ny rows of Nx each, window after window in a): rows over all nb * Ny rows, transpose per
+// window, rows over all nb * Nx rows -> every window's transform TRANSPOSED (Nx rows of Ny) in tmp.  The inverse of such a
+// transposed transform is the same call with the two extents and plans swapped.
+static int fft2_windows(cplx *a, cplx *tmp, int nb, int Ny, int Nx, const RowPlan &px, const RowPlan &py, int inverse)
 {
     int rc;
-    if ((rc = fft_rows(a, Ny, px, inverse))) return rc;
-    TIP_LAUNCH("transpose_c", k_transpose_c, dim3(cdiv(Nx, 16), cdiv(Ny, 16)), dim3(256), 0, (const cplx *)a, tmp, Ny, Nx);
-    if ((rc = fft_rows(tmp, Nx, py, inverse))) return rc;
-    if (!leave_transposed)
-        TIP_LAUNCH("transpose_c", k_transpose_c, dim3(cdiv(Ny, 16), cdiv(Nx, 16)), dim3(256), 0, (const cplx *)tmp, a, Nx, Ny);
-    return TIP_OK;
+    if ((rc = fft_rows(a, nb * Ny, px, inverse))) return rc;
+    TIP_LAUNCH("transpose_c", k_transpose_c, dim3(cdiv(Nx, 16), cdiv(Ny, 16), nb), dim3(256), 0, (const cplx *)a, tmp, Ny, Nx);
+    return fft_rows(tmp, nb * Nx, py, inverse);
 }
 
-template <typename T>
-static int to_complex(const void *in, cplx *out, long n)
-{
-    TIP_LAUNCH("to_complex", k_to_complex<T>, dim3(cdiv(n, 256)), dim3(256), 0, (const T *)in, out, n);
-    return TIP_OK;
-}
-
-// dtype: 0 f32, 1 f64, 3 u16.  out4 (host): coarse peak (row, col) and fine peak (row, col) on the upsampled grid
-int phase_correlation_dev(const void *ref, const void *mov, int dtype, int Ny, int Nx, int upsample, int64_t *out4_host)
-{
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
-    if (!ref || !mov || !out4_host) return fail(TIP_ERR_ARG, "phase_correlation: null pointer");
-    if (Ny < 2 || Nx < 2 || Ny > 4096 || Nx > 4096)
-        return fail(TIP_ERR_UNSUPPORTED, "phase_correlation: extents must lie in [2, 4096] (got %dx%d)", Ny, Nx);
-    if (upsample < 1 || upsample > 1000) return fail(TIP_ERR_ARG, "phase_correlation: upsample_factor %d", upsample);
-    const long n = (long)Ny * Nx;
-    const int region = upsample > 1 ? (int)ceil(upsample * 1.5) : 0;
-    WsGuard ws;
-    cplx *A = ws.get<cplx>(n), *B = ws.get<cplx>(n), *T1 = ws.get<cplx>(n), *T2 = ws.get<cplx>(n);
-    unsigned long long *best = ws.get<unsigned long long>(4);
-    if (!A || !B || !T1 || !T2 || !best) return TIP_ERR_NOMEM;
-    int rc;
-    RowPlan plx, ply;
-    if ((rc = make_plan(plx, Nx, ws)) || (rc = make_plan(ply, Ny, ws))) return rc;
-    for (int w = 0; w < 2; ++w) {
-        const void *src = w == 0 ? ref : mov;
-        cplx *dst = w == 0 ? A : B;
-        if (dtype == 0) rc = to_complex<float>(src, dst, n);
-        else if (dtype == 1) rc = to_complex<double>(src, dst, n);
-        else if (dtype == 3) rc = to_complex<uint16_t>(src, dst, n);
-        else return fail(TIP_ERR_ARG, "phase_correlation: dtype %d (0 f32, 1 f64, 3 u16)", dtype);
-        if (rc) return rc;
-    }
-    if ((rc = fft2_inplace(A, T1, Ny, Nx, plx, ply, 0, true))) return rc;   // T1 = F1^T
-    if ((rc = fft2_inplace(B, T2, Ny, Nx, plx, ply, 0, true))) return rc;   // T2 = F2^T
-    cplx *PT = A;                                                            // P^T = F1^T * conj(F2^T)
-    TIP_LAUNCH("cmul_conj", k_cmul_conj, dim3(cdiv(n, 256)), dim3(256), 0, (const cplx *)T1, (const cplx *)T2, PT, n);
-    // cross-correlation = ifft2(P): inverse transform of P^T (Nx rows of Ny) -> rows Ny-point, transpose, rows Nx-point
-    TIP_HIP(hipMemcpyAsync(B, PT, n * sizeof(cplx), hipMemcpyDeviceToDevice, c.stream));
-    if ((rc = fft_rows(B, Nx, ply, 1))) return rc;
-    TIP_LAUNCH("transpose_c", k_transpose_c, dim3(cdiv(Ny, 16), cdiv(Nx, 16)), dim3(256), 0, (const cplx *)B, T1, Nx, Ny);
-    if ((rc = fft_rows(T1, Ny, plx, 1))) return rc;
-    TIP_HIP(hipMemsetAsync(best, 0, 8, c.stream));
-    TIP_HIP(hipMemsetAsync(best + 1, 0xff, 8, c.stream));
-    TIP_LAUNCH("absargmax", k_absargmax, dim3(cdiv(n, 256)), dim3(256), 0, (const cplx *)T1, n, best, best + 1);
-    TIP_LAUNCH("absargmax2", k_absargmax2, dim3(cdiv(n, 256)), dim3(256), 0, (const cplx *)T1, n, (const unsigned long long *)best,
-               best + 1);
-    unsigned long long h[4] = {0, 0, 0, 0};
-    TIP_HIP(hipMemcpyAsync(h, best, 16, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    const long peak = (long)h[1];
-    const int py = (int)(peak / Nx), px = (int)(peak % Nx);
-    out4_host[0] = py; out4_host[1] = px; out4_host[2] = 0; out4_host[3] = 0;
-    if (upsample <= 1) return TIP_OK;
-    // signed whole-pixel shifts as numpy computes them, rounded onto the upsampled grid
-    double sy = py, sx = px;
-    if (sy > floor(Ny / 2.0)) sy -= Ny;
-    if (sx > floor(Nx / 2.0)) sx -= Nx;
-    const double uf = (double)upsample;
-    sy = nearbyint(sy * uf) / uf;   // np.round: half to even, like nearbyint in the default rounding mode
-    sx = nearbyint(sx * uf) / uf;
-    const double dftshift = floor(region / 2.0);
-    const double offy = dftshift - sy * uf, offx = dftshift - sx * uf;
-    cplx *Kx = ws.get<cplx>((size_t)region * Nx), *Ky = ws.get<cplx>((size_t)region * Ny);
-    cplx *C1 = ws.get<cplx>((size_t)region * Ny), *O = ws.get<cplx>((size_t)region * region);
-    if (!Kx || !Ky || !C1 || !O) return TIP_ERR_NOMEM;
-    TIP_LAUNCH("dft_kernel", k_dft_kernel, dim3(cdiv((long)region * Nx, 256)), dim3(256), 0, Kx, region, Nx, offx, uf);
-    TIP_LAUNCH("dft_kernel", k_dft_kernel, dim3(cdiv((long)region * Ny, 256)), dim3(256), 0, Ky, region, Ny, offy, uf);
-    TIP_LAUNCH("updft1", k_updft1, dim3(cdiv(Ny, 256), region), dim3(256), 0, (const cplx *)Kx, (const cplx *)PT, C1, region, Nx, Ny);
-    TIP_LAUNCH("updft2", k_updft2, dim3(region, region), dim3(64), 0, (const cplx *)Ky, (const cplx *)C1, O, region, Ny);
-    TIP_HIP(hipMemsetAsync(best, 0, 8, c.stream));
-    TIP_HIP(hipMemsetAsync(best + 1, 0xff, 8, c.stream));
-    const long nr = (long)region * region;
-    TIP_LAUNCH("absargmax", k_absargmax, dim3(cdiv(nr, 256)), dim3(256), 0, (const cplx *)O, nr, best, best + 1);
-    TIP_LAUNCH("absargmax2", k_absargmax2, dim3(cdiv(nr, 256)), dim3(256), 0, (const cplx *)O, nr, (const unsigned long long *)best,
-               best + 1);
-    TIP_HIP(hipMemcpyAsync(h, best, 16, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    out4_host[2] = (int64_t)(h[1] / region);
-    out4_host[3] = (int64_t)(h[1] % region);
-    return TIP_OK;
-}
-
-// ---- batch: the same correlation on n windows of one frame pair, a chunk of windows per pass ------------------------------
-// Nothing in the arithmetic differs from phase_correlation_dev on the cropped windows -- the rows of all windows of a chunk
-// are more rows for the row kernels, every other kernel takes the window as a grid dimension -- so the four integers per
-// window are the same ones.  Per chunk: one load kernel per frame, the launches of one correlation, ONE stream wait.
+// ---- the correlation: n windows of one frame pair, a chunk of windows per pass --------------------------------------------
+// The rows of all windows of a chunk are more rows for the row kernels, every other kernel takes the window as a grid
+// dimension, so a window's four integers do not depend on the windows beside it.  Per chunk: one load kernel per frame, the
+// launches of one correlation, ONE stream wait.
 
 // Workspace a chunk may take when the caller leaves the chunk size open: the four complex planes plus the upsampled-DFT
 // matrices of its windows (58 windows of 700 x 700 with upsample 100, about 40 000 rows per row launch).  From this arithmetic,
@@ -449,33 +353,26 @@ static int load_windows(const void *frame, int frame_x, const int *org, int side
     return TIP_OK;
 }
 
-static int fft2_windows(cplx *a, cplx *tmp, int nb, int Ny, int Nx, const RowPlan &px, const RowPlan &py)   // tmp = F^T per window
+// dtype: 0 f32, 1 f64, 3 u16.  origins (host): n x (ref row, ref col, mov row, mov col); null: every window at (0, 0, 0, 0),
+// which costs no upload.  out4n (host): per window the coarse peak (row, col) and the fine peak (row, col) on the upsampled
+// grid.  who: the entry's name for the messages.
+static int correlate_windows(const char *who, const void *ref, const void *mov, int dtype, int frame_y, int frame_x, int n,
+                             const int32_t *origins, int Ny, int Nx, int upsample, int max_batch, int64_t *out4n_host)
 {
-    int rc;
-    if ((rc = fft_rows(a, nb * Ny, px, 0))) return rc;
-    TIP_LAUNCH("transpose_c", k_transpose_c, dim3(cdiv(Nx, 16), cdiv(Ny, 16), nb), dim3(256), 0, (const cplx *)a, tmp, Ny, Nx);
-    return fft_rows(tmp, nb * Nx, py, 0);
-}
-
-int phase_correlation_windows_dev(const void *ref, const void *mov, int dtype, int frame_y, int frame_x, int n, const int32_t *origins,
-                                  int Ny, int Nx, int upsample, int max_batch, int64_t *out4n_host)
-{
-    if (n == 0) return TIP_OK;
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
-    if (!ref || !mov || !origins || !out4n_host) return fail(TIP_ERR_ARG, "phase_correlation_windows: null pointer");
-    if (n < 0 || max_batch < 0) return fail(TIP_ERR_ARG, "phase_correlation_windows: n %d, max_batch %d", n, max_batch);
+    if (!ref || !mov || !out4n_host) return fail(TIP_ERR_ARG, "%s: null pointer", who);
+    if (n < 0 || max_batch < 0) return fail(TIP_ERR_ARG, "%s: n %d, max_batch %d", who, n, max_batch);
     if (Ny < 2 || Nx < 2 || Ny > 4096 || Nx > 4096)
-        return fail(TIP_ERR_UNSUPPORTED, "phase_correlation_windows: extents must lie in [2, 4096] (got %dx%d)", Ny, Nx);
-    if (upsample < 1 || upsample > 1000) return fail(TIP_ERR_ARG, "phase_correlation_windows: upsample_factor %d", upsample);
-    if (dtype != 0 && dtype != 1 && dtype != 3) return fail(TIP_ERR_ARG, "phase_correlation_windows: dtype %d (0 f32, 1 f64, 3 u16)", dtype);
-    if (frame_y < Ny || frame_x < Nx) return fail(TIP_ERR_ARG, "phase_correlation_windows: %dx%d windows in a %dx%d frame", Ny, Nx, frame_y, frame_x);
-    for (int w = 0; w < n; ++w)
+        return fail(TIP_ERR_UNSUPPORTED, "%s: extents must lie in [2, 4096] (got %dx%d)", who, Ny, Nx);
+    if (upsample < 1 || upsample > 1000) return fail(TIP_ERR_ARG, "%s: upsample_factor %d", who, upsample);
+    if (dtype != 0 && dtype != 1 && dtype != 3) return fail(TIP_ERR_ARG, "%s: dtype %d (0 f32, 1 f64, 3 u16)", who, dtype);
+    if (frame_y < Ny || frame_x < Nx) return fail(TIP_ERR_ARG, "%s: %dx%d windows in a %dx%d frame", who, Ny, Nx, frame_y, frame_x);
+    for (int w = 0; origins && w < n; ++w)
         for (int side = 0; side < 4; side += 2) {
             const int r0 = origins[4 * w + side], c0 = origins[4 * w + side + 1];
             if (r0 < 0 || c0 < 0 || r0 > frame_y - Ny || c0 > frame_x - Nx)
-                return fail(TIP_ERR_ARG, "phase_correlation_windows: window %d (%dx%d at %d, %d) leaves its %dx%d frame", w, Ny, Nx, r0, c0,
-                            frame_y, frame_x);
+                return fail(TIP_ERR_ARG, "%s: window %d (%dx%d at %d, %d) leaves its %dx%d frame", who, w, Ny, Nx, r0, c0, frame_y, frame_x);
         }
     const size_t nw = (size_t)Ny * Nx;
     const int region = upsample > 1 ? (int)ceil(upsample * 1.5) : 0;
@@ -498,7 +395,8 @@ int phase_correlation_windows_dev(const void *ref, const void *mov, int dtype, i
     int rc;
     RowPlan plx, ply;                                                        // one plan per extent for the whole call
     if ((rc = make_plan(plx, Nx, ws)) || (rc = make_plan(ply, Ny, ws))) return rc;
-    TIP_HIP(hipMemcpyAsync(org, origins, 4 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, c.stream));
+    if (origins) TIP_HIP(hipMemcpyAsync(org, origins, 4 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, c.stream));
+    else TIP_HIP(hipMemsetAsync(org, 0, 4 * (size_t)n * sizeof(int), c.stream));
     std::vector<unsigned long long> h(2 * (size_t)nbmax);
     const double uf = (double)upsample, dftshift = floor(region / 2.0);
     const long nr = (long)region * region;
@@ -514,14 +412,13 @@ int phase_correlation_windows_dev(const void *ref, const void *mov, int dtype, i
             else rc = load_windows<uint16_t>(src, frame_x, org + 4 * w0, side, dst, nb, Ny, Nx);
             if (rc) return rc;
         }
-        if ((rc = fft2_windows(A, T1, nb, Ny, Nx, plx, ply))) return rc;     // T1 = F1^T
-        if ((rc = fft2_windows(B, T2, nb, Ny, Nx, plx, ply))) return rc;     // T2 = F2^T
+        if ((rc = fft2_windows(A, T1, nb, Ny, Nx, plx, ply, 0))) return rc;  // T1 = F1^T
+        if ((rc = fft2_windows(B, T2, nb, Ny, Nx, plx, ply, 0))) return rc;  // T2 = F2^T
         cplx *PT = A;                                                        // P^T = F1^T * conj(F2^T), window after window
         TIP_LAUNCH("cmul_conj", k_cmul_conj, dim3(cdiv(tot, 256)), dim3(256), 0, (const cplx *)T1, (const cplx *)T2, PT, tot);
+        // cross-correlation = ifft2(P): the inverse transform of P^T (Nx rows of Ny) lands untransposed (Ny rows of Nx) in T1
         TIP_HIP(hipMemcpyAsync(B, PT, tot * sizeof(cplx), hipMemcpyDeviceToDevice, c.stream));
-        if ((rc = fft_rows(B, nb * Nx, ply, 1))) return rc;
-        TIP_LAUNCH("transpose_c", k_transpose_c, dim3(cdiv(Ny, 16), cdiv(Nx, 16), nb), dim3(256), 0, (const cplx *)B, T1, Nx, Ny);
-        if ((rc = fft_rows(T1, nb * Ny, plx, 1))) return rc;
+        if ((rc = fft2_windows(B, T1, nb, Nx, Ny, ply, plx, 1))) return rc;
         TIP_HIP(hipMemsetAsync(bv, 0, 2 * (size_t)nbmax * 8, c.stream));
         TIP_HIP(hipMemsetAsync(bi, 0xff, 2 * (size_t)nbmax * 8, c.stream));
         TIP_LAUNCH("absargmax", k_absargmax, dim3(cdiv((long)nw, 256), nb), dim3(256), 0, (const cplx *)T1, (long)nw, bv, bi);
@@ -549,6 +446,21 @@ int phase_correlation_windows_dev(const void *ref, const void *mov, int dtype, i
         }
     }
     return TIP_OK;
+}
+
+// the whole plane: one window of the frame's extent at the origin
+int phase_correlation_dev(const void *ref, const void *mov, int dtype, int Ny, int Nx, int upsample, int64_t *out4_host)
+{
+    return correlate_windows("phase_correlation", ref, mov, dtype, Ny, Nx, 1, nullptr, Ny, Nx, upsample, 0, out4_host);
+}
+
+int phase_correlation_windows_dev(const void *ref, const void *mov, int dtype, int frame_y, int frame_x, int n, const int32_t *origins,
+                                  int Ny, int Nx, int upsample, int max_batch, int64_t *out4n_host)
+{
+    if (n == 0) return TIP_OK;
+    if (!origins) return fail(TIP_ERR_ARG, "phase_correlation_windows: null pointer");      // (null is the whole plane's form)
+    return correlate_windows("phase_correlation_windows", ref, mov, dtype, frame_y, frame_x, n, origins, Ny, Nx, upsample, max_batch,
+                             out4n_host);
 }
 
 }  // namespace tip
@@ -583,7 +495,7 @@ int tip_phase_correlation(const void *ref, const void *mov, int dtype, int y, in
     return phase_correlation_dev(da, db, dtype, y, x, upsample, out4);
 }
 
-// diagnostics (tests): the plan, row and transpose kernels phase_correlation_dev runs, on one host complex128 array
+// diagnostics (tests): the plan, row and transpose kernels the correlation runs, on one host complex128 array
 int tip_fft2_c128(const double *in, double *out, int y, int x, int inverse)
 {
     Ctx &c = ctx();
@@ -599,7 +511,8 @@ int tip_fft2_c128(const double *in, double *out, int y, int x, int inverse)
     RowPlan plx, ply;
     if ((rc = make_plan(plx, x, ws)) || (rc = make_plan(ply, y, ws))) return rc;
     TIP_HIP(hipMemcpyAsync(A, in, n * sizeof(cplx), hipMemcpyHostToDevice, c.stream));
-    if ((rc = fft2_inplace(A, T, y, x, plx, ply, inverse ? 1 : 0, false))) return rc;
+    if ((rc = fft2_windows(A, T, 1, y, x, plx, ply, inverse ? 1 : 0))) return rc;            // T = the transform transposed
+    TIP_LAUNCH("transpose_c", k_transpose_c, dim3(cdiv(y, 16), cdiv(x, 16)), dim3(256), 0, (const cplx *)T, A, x, y);
     TIP_HIP(hipMemcpyAsync(out, A, n * sizeof(cplx), hipMemcpyDeviceToHost, c.stream));
     TIP_HIP(hipStreamSynchronize(c.stream));
     return TIP_OK;

@@ -40,6 +40,8 @@ above runs on them unchanged.  Each pipeline has its own predictor and each work
 multi-process CPU tests, on a stand-in backend with the gloo process group.
 """
 
+import collections
+
 import numpy as np
 
 from ._collectives import gather_varlen
@@ -242,15 +244,24 @@ class GpuFrameBackend(object):
     def _segment_unet(self, p, t):
         """Frame t's U-Net segmentation on pipeline p: labels in p.d_labels as (Y, X), as segment() leaves them; the frame's
         network mode and watershed flags are noted, and with keep_hc its HC map is kept like the label map."""
-        from . import _lib
         pred = self._predictor_for(p)
         p.segment_unet_frame(pred, self.unet_channels[0], self.unet_channels[1], keep_hc=self.keep_hc)
         self.unet_modes[t], self.ws_flags[t] = getattr(pred.model, "last_mode", None), int(pred.last_flags)
         if self.keep_hc:
-            nbytes = self.Y * self.X * 8
-            keep = _lib.DeviceBuffer(nbytes)
-            _lib.check(p.lib.tip_memcpy_d2d(keep.ptr, p.d_hc.ptr, nbytes))
-            self.hc_maps[t] = keep
+            self.hc_maps[t] = self._keep(p, p.d_hc.ptr, 8)
+
+    def _keep(self, p, src_ptr, itemsize, dst=None):
+        """A device copy of a (Y, X) map of pipeline p, on p's stream: into the tensor dst, or a new DeviceBuffer."""
+        from . import _lib
+        keep = _lib.DeviceBuffer(self.Y * self.X * itemsize) if dst is None else dst
+        _lib.check(p.lib.tip_memcpy_d2d(keep.ptr if dst is None else dst.data_ptr(), src_ptr, self.Y * self.X * itemsize))
+        return keep
+
+    @staticmethod
+    def _valid_by_area(area):
+        """calculate_frame_cellinfo's rule: a row is valid when its area lies strictly between 0.1 and 10 mean areas."""
+        mean = area.mean() if area.size else 0.0
+        return (area > 0.1 * mean) & (area < 10 * mean)
 
     def fetch_hc(self, t):
         """Frame t's HC map (float64 (Y, X): 255 inside the eroded closed class map, 0 elsewhere), downloaded."""
@@ -269,19 +280,13 @@ class GpuFrameBackend(object):
             self._segment_unet(p, t)
         else:
             p.segment(0)
-        nbytes = self.Y * self.X * 4
-        keep = _lib.DeviceBuffer(nbytes)
-        _lib.check(p.lib.tip_memcpy_d2d(keep.ptr, p.d_labels.ptr, nbytes))
-        self.labels[t] = keep
+        self.labels[t] = self._keep(p, p.d_labels.ptr, 4)
         if self.keep_planes:
             import torch
-            dev = torch.device("cuda", _lib.device_for_thread() or 0)
-            plane = torch.empty((self.Y, self.X), dtype=torch.float64, device=dev)
+            plane = self.empty_plane()
             # (the block may still be in use by kernels queued on torch's stream: order the library's copy after them)
-            _lib.check(p.lib.tip_wait_stream(torch.cuda.current_stream(dev).cuda_stream))
-            _lib.check(p.lib.tip_memcpy_d2d(plane.data_ptr(), p.d_proj.ptr + p.ref * self.Y * self.X * 8,
-                                            self.Y * self.X * 8))
-            self.planes[t] = plane
+            _lib.check(p.lib.tip_wait_stream(torch.cuda.current_stream(plane.device).cuda_stream))
+            self.planes[t] = self._keep(p, p.d_proj.ptr + p.ref * self.Y * self.X * 8, 8, dst=plane)
         tab = p.cell_tables()          # (synchronises: the small per-cell arrays come to the host)
         d_stack.free()
         area = tab["area"].astype(np.float64)
@@ -293,20 +298,11 @@ class GpuFrameBackend(object):
             tmap = _lib.DeviceBuffer(self.Y * self.X)      # the frame's type map is painted straight into its own buffer
             out.update(p.cell_types(n=tab["area"].size, type_map_ptr=tmap.ptr, **self.cell_types))   # (synchronises)
             self.type_maps[t] = tmap
-        if self.neighbor_features:
-            n = tab["area"].size
-            if self.cell_types is not None:
-                out.update(p.neighbor_features(n, out["valid"], out["type"], type_index=self.cell_types.get("type_index", 0)))
-            else:
-                mean = tab["area"].mean() if n else 0.0
-                out.update(p.neighbor_features(n, (tab["area"] > 0.1 * mean) & (tab["area"] < 10 * mean)))
+        n = tab["area"].size
+        valid = out["valid"] if self.cell_types is not None else self._valid_by_area(tab["area"])
+        if self.neighbor_features:      # (untyped without cell_types: no "type" column)
+            out.update(p.neighbor_features(n, valid, out.get("type"), type_index=(self.cell_types or {}).get("type_index", 0)))
         if self.order_features:
-            n = tab["area"].size
-            if self.cell_types is not None:
-                valid = out["valid"]
-            else:
-                mean = tab["area"].mean() if n else 0.0
-                valid = (tab["area"] > 0.1 * mean) & (tab["area"] < 10 * mean)
             out.update(p.order_features(n, valid, out["cy"], out["cx"]))
         return out
 
@@ -332,17 +328,21 @@ class GpuFrameBackend(object):
         from . import _lib
         return torch.empty((self.Y, self.X), dtype=torch.float64, device=torch.device("cuda", _lib.device_for_thread() or 0))
 
+    def _received(self, what, prev_plane):
+        """What every drift step starts with: the backend keeps planes, and the plane received from the neighbour is complete."""
+        import torch
+        if not self.keep_planes:
+            raise ValueError("%s needs the reference-channel planes: GpuFrameBackend(..., keep_planes=True)" % what)
+        torch.cuda.current_stream(prev_plane.device).synchronize()
+
     def piv_lookup(self, t, prev_plane, prev_table):
         """The PIV step of the tracker for frame t (ti.py:2061-2106): TV-L1 flow from frame t-1's reference-channel plane
         (prev_plane, received from the neighbour rank) to frame t's, both truncated to uint16 on the device; frame t-1's
         centroids (prev_table: area, cy, cx) moved by the flow sampled as upstream samples it (row flow at (round(cx),
         round(cy)), numpy's wrap and IndexError rules) and looked up in frame t's 3x3-max-filtered label map.  Returns int32
         hits (-1: outside the frame or an absent row); raises IndexError where upstream's numpy indexing would."""
-        import torch
         from ._registration import piv_lookup_dev
-        if not self.keep_planes:
-            raise ValueError("piv_lookup needs the reference-channel planes: GpuFrameBackend(..., keep_planes=True)")
-        torch.cuda.current_stream(prev_plane.device).synchronize()      # the received plane is complete
+        self._received("piv_lookup", prev_plane)
         return piv_lookup_dev(prev_plane.data_ptr(), self.planes[t].data_ptr(), self.labels[t].ptr, self.Y, self.X, prev_table)
 
     def local_drift_lookup(self, t, prev_plane, prev_table, step_size=100, window_size=700):
@@ -352,28 +352,21 @@ class GpuFrameBackend(object):
         row i of prev_table (area, cy, cx) moves by the mean (row, column) shift of the windows that contain
         (round(cy_i), round(cx_i)) and is looked up in frame t's label map: local_drift_hits.  The window shifts stay in
         self.local_drifts[t] as [(window, row shift, column shift)]."""
-        import torch
-        from ._registration import local_drift_windows, phase_cross_correlation_windows_dev, _windows_by_extent
-        if not self.keep_planes:
-            raise ValueError("local_drift_lookup needs the reference-channel planes: GpuFrameBackend(..., keep_planes=True)")
+        from ._registration import local_drift_windows, correlate_windows_by_extent
+        self._received("local_drift_lookup", prev_plane)
+        _check_window_fits(self.Y, self.X, window_size)
         windows = local_drift_windows((self.Y, self.X), step_size, window_size)
-        if not windows:
-            raise ValueError("local drifts: the %dx%d frame must exceed window_size %d in both extents" % (self.Y, self.X, window_size))
-        torch.cuda.current_stream(prev_plane.device).synchronize()      # the received plane is complete
-        origins = np.array([(r0, c0, r0, c0) for r0, _, c0, _ in windows], np.int32)
-        shifts = np.empty((len(windows), 2), np.float64)
-        for (ny, nx), idx in _windows_by_extent([(r1 - r0, c1 - c0) for r0, r1, c0, c1 in windows]).items():
-            shifts[idx] = phase_cross_correlation_windows_dev(prev_plane.data_ptr(), self.planes[t].data_ptr(), (self.Y, self.X),
-                                                              origins[idx], ny, nx, 100)
+        shifts = correlate_windows_by_extent(prev_plane.data_ptr(), self.planes[t].data_ptr(), (self.Y, self.X),
+                                             [(r0, c0, r0, c0) for r0, _, c0, _ in windows],
+                                             [(r1 - r0, c1 - c0) for r0, r1, c0, c1 in windows])
         self.local_drifts[t] = [(win, float(sh[0]), float(sh[1])) for win, sh in zip(windows, shifts)]
         return local_drift_hits(self.local_drifts[t], prev_table, lambda qy, qx: self.lookup(t, qy, qx))
 
     def drift(self, t, prev_plane):
         """(row shift, column shift) that registers frame t onto frame t-1: Tissue.update_drift without a stage table
         (ti.py:1982-2035 -> calculate_refine_drift with a zero coarse shift -> phase_cross_correlation(upsample 100))."""
-        import torch
         from ._registration import phase_cross_correlation_dev
-        torch.cuda.current_stream(prev_plane.device).synchronize()      # the received plane is complete
+        self._received("drift", prev_plane)
         sh = phase_cross_correlation_dev(prev_plane.data_ptr(), self.planes[t].data_ptr(), self.Y, self.X, 100)
         return float(sh[0]), float(sh[1])
 
@@ -391,6 +384,11 @@ def local_drift_hits(drifts, prev_table, lookup):
     qy = np.where(covered, np.round(cy - np.where(covered, d_row, 0.0)), -1).astype(np.int64)
     qx = np.where(covered, np.round(cx - np.where(covered, d_col, 0.0)), -1).astype(np.int64)
     return np.where(covered, lookup(qy, qx), -1).astype(np.int32)
+
+
+def _check_window_fits(Y, X, window_size):
+    if Y <= window_size or X <= window_size:      # upstream's window loop is then empty and divides 0 by 0
+        raise ValueError("local_drifts: the %dx%d frame must exceed window_size %d in both extents" % (Y, X, window_size))
 
 
 LOCAL_DRIFT_DEFAULTS = dict(step_size=100, window_size=700)      # upstream's (ti.py:2115)
@@ -538,30 +536,32 @@ def link_ids(tables, drifts):
     return out
 
 
-def _validate(stitcher, estimate_drift, use_piv, backend, local_drifts=None):
+DriftSource = collections.namedtuple("DriftSource", "kind planes local")
+
+
+def _drift_source(stitcher, estimate_drift, use_piv, local_drifts, backend):
+    """The one drift source of a process_movie call; every combination the driver does not run is a ValueError here.  kind:
+    "given" (the `drifts` rows), "estimate" (backend.drift), "piv" (backend.piv_lookup) or "local" (backend.local_drift_lookup
+    with the options `local`); planes: frame t-1's plane travels to frame t's owner."""
     local = local_drift_options(local_drifts)
-    if local is not None:
-        if estimate_drift or use_piv:
-            raise ValueError("local_drifts, estimate_drift and use_piv are three drift sources: pass one of them")
+    chosen = [kind for kind, on in (("estimate", estimate_drift), ("piv", use_piv), ("local", local is not None)) if on]
+    if len(chosen) > 1:
+        raise ValueError("estimate_drift, use_piv and local_drifts are three drift sources: pass one of them")
+    if stitcher not in ("lookup", "linker"):
+        raise ValueError("stitcher must be 'lookup' or 'linker'")
+    kind = chosen[0] if chosen else "given"
+    if kind in ("piv", "local"):      # the owner's look-up is the backend's own step
+        flag, method = {"piv": ("use_piv", "piv_lookup"), "local": ("local_drifts", "local_drift_lookup")}[kind]
         if stitcher != "lookup":
-            raise ValueError("local_drifts needs stitcher='lookup' (the trackpy-model linker with local drifts is not built)")
-        if not hasattr(backend, "local_drift_lookup") or not getattr(backend, "keep_planes", True):
-            raise ValueError("local_drifts needs a backend with local_drift_lookup and the reference-channel planes "
-                             "(GpuFrameBackend(keep_planes=True))")
+            raise ValueError("%s needs stitcher='lookup' (the trackpy-model linker has no such mode)" % flag)
+        if not hasattr(backend, method) or not getattr(backend, "keep_planes", True):
+            raise ValueError("%s needs a backend with %s and planes (GpuFrameBackend(keep_planes=True))" % (flag, method))
+    if kind == "local":
         Y, X = getattr(backend, "Y", None), getattr(backend, "X", None)
         if Y is None or X is None:
             raise ValueError("local_drifts needs a backend that knows its frame extents (Y, X)")
-        if Y <= local["window_size"] or X <= local["window_size"]:      # upstream's loop is then empty and divides 0 by 0
-            raise ValueError("local_drifts: the %dx%d frame must exceed window_size %d in both extents"
-                             % (Y, X, local["window_size"]))
-    if stitcher not in ("lookup", "linker"):
-        raise ValueError("stitcher must be 'lookup' or 'linker'")
-    if use_piv and estimate_drift:
-        raise ValueError("use_piv and estimate_drift are two drift sources: pass one of them")
-    if use_piv and stitcher != "lookup":
-        raise ValueError("use_piv needs stitcher='lookup' (the reference's trackpy linker has no PIV mode)")
-    if use_piv and (not hasattr(backend, "piv_lookup") or not getattr(backend, "keep_planes", True)):
-        raise ValueError("use_piv needs a backend with the reference-channel planes (GpuFrameBackend(keep_planes=True))")
+        _check_window_fits(Y, X, local["window_size"])
+    return DriftSource(kind, kind != "given", local)
 
 
 def plan_rounds(n_frames, rank, world, block_frames=None):
@@ -582,10 +582,10 @@ def _compute_round(frames, frame_source, backend):
     return {t: backend.process_frame(t, frame_source(t)) for t in frames}
 
 
-def _drift_step(mine, local, drifts, backend, held_planes, estimate_drift):
-    """Writes tables' "drift": the given row, or with estimate_drift the owner's estimate against the held plane of frame t-1."""
+def _drift_step(mine, local, drifts, backend, held_planes, source):
+    """Writes tables' "drift": the given row, or for the "estimate" source the owner's estimate against the held plane of frame t-1."""
     for t in mine:
-        if estimate_drift and t >= 1:
+        if source.kind == "estimate" and t >= 1:
             drifts[t] = backend.drift(t, held_planes.pop(t))
         local[t]["drift"] = drifts[t].copy()
 
@@ -598,20 +598,21 @@ def _exchange_tables(mine, local, extra, dist, rank, world, device):
     return {t: tb for part in parts for t, tb in unpack_tables(part, extra).items()}
 
 
-def _owner_lookups(mine, tables, backend, piv_planes=None, local_planes=None, local=None):
+def _owner_lookups(mine, tables, backend, held_planes, source):
     """For each of this rank's frames t >= 1 the label of frame t under every row of frame t-1, -1 for absent (zero-area) rows:
-    backend.lookup at the drift-corrected centroids, or with piv_planes (the held planes) backend.piv_lookup, whose first
-    exception ends the loop, or with local_planes (the held planes) backend.local_drift_lookup with the options `local`.  Returns ({t: hits}, (failed frame or -1, kind 1: IndexError / 2: other), the exception)."""
+    backend.lookup at the drift-corrected centroids, or by the source's kind backend.piv_lookup on the held plane, whose first
+    exception ends the loop, or backend.local_drift_lookup on it with the source's options.  Returns ({t: hits}, (failed frame or
+    -1, kind 1: IndexError / 2: other), the exception)."""
     hits = {}
     for t in [t for t in mine if t >= 1]:
         prev = tables[t - 1]
-        if piv_planes is not None:
+        if source.kind == "piv":
             try:
-                res = backend.piv_lookup(t, piv_planes.pop(t), prev)
+                res = backend.piv_lookup(t, held_planes.pop(t), prev)
             except Exception as e:            # the round's collectives still run: _agree_on_piv_failure tells every rank
                 return hits, (t, 1 if isinstance(e, IndexError) else 2), e
-        elif local_planes is not None:
-            res = backend.local_drift_lookup(t, local_planes.pop(t), prev, **local)
+        elif source.kind == "local":
+            res = backend.local_drift_lookup(t, held_planes.pop(t), prev, **source.local)
         else:
             dy, dx = tables[t]["drift"]
             res = backend.lookup(t, np.round(prev["cy"] - dy).astype(np.int64), np.round(prev["cx"] - dx).astype(np.int64))
@@ -688,8 +689,7 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
     frame; rank 0 then stitches (_stitch).  Every rank runs the same rounds and joins their collectives, with empty payloads
     when it has no frame in one, so any n_frames works, including fewer frames than ranks."""
     from concurrent.futures import ThreadPoolExecutor
-    _validate(stitcher, estimate_drift, use_piv, backend, local_drifts)
-    local_opts = local_drift_options(local_drifts)
+    source = _drift_source(stitcher, estimate_drift, use_piv, local_drifts, backend)
     drifts = np.zeros((n_frames, 2)) if drifts is None else np.array(drifts, dtype=np.float64)
     extra = tuple(getattr(backend, "extra_columns", ()))      # further per-row columns every frame's dict carries
     rounds = plan_rounds(n_frames, rank, world, block_frames)
@@ -701,16 +701,15 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
             local = pending.result()
             if k + 1 < len(rounds):                   # the next round computes while this one is exchanged
                 pending = pool.submit(_compute_round, rounds[k + 1], frame_source, backend)
-            if estimate_drift or use_piv or local_opts:   # frame t's plane goes to the owner of frame t+1, if there is one
+            if source.planes:                         # frame t's plane goes to the owner of frame t+1, if there is one
                 held_planes.update(exchange_planes([t for t in mine if t + 1 < n_frames],
                                                    [t for t in upstream[k] if t + 1 < n_frames], backend, rank, world, dist))
-            _drift_step(mine, local, drifts, backend, held_planes, estimate_drift)
+            _drift_step(mine, local, drifts, backend, held_planes, source)
             tables.update(_exchange_tables(mine, local, extra, dist, rank, world, device))
             if stitcher == "linker":
                 continue
-            hits, failed, error = _owner_lookups(mine, tables, backend, held_planes if use_piv else None,
-                                                 held_planes if local_opts else None, local_opts)
-            if use_piv:
+            hits, failed, error = _owner_lookups(mine, tables, backend, held_planes, source)
+            if source.kind == "piv":
                 _agree_on_piv_failure(failed, error, rank, world, dist, device)
             lookups.update(_gather_lookups(hits, dist, rank, world, device))
     return _stitch(tables, lookups, stitcher) if rank == 0 else (None, None)

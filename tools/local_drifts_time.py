@@ -10,8 +10,8 @@ A size^2 float64 pair (low-passed noise, the second frame shifted and perturbed)
   batched  one tip_phase_correlation_windows_dev call per window extent.
 After a warm-up the two alternate `repeats` times; all values and the medians are recorded, with a check that the shifts are
 equal.  A separate pass with the library's launch profiler on counts the kernel launches of either path (and gives the batched
-path's kernel times from HIP events); the stream waits follow from them: either path waits once after each absargmax pair, the
-loop twice per window, the batch once per chunk (upsample 100: two pairs per wait in the batch, one in the loop).
+path's kernel times from HIP events); the stream waits follow from them: both paths run the one correlation body, which waits
+once per chunk after its two absargmax pairs (upsample 100) -- the loop once per window, the batch once per chunk.
 --only batched runs the batched path alone `repeats` times, for a kernel trace with nothing else in it.
 With --movie-frames N > 0: the wall time of movie.process_movie over N synthetic size^2 frames on one GPU with
 local_drifts=True against estimate_drift=True, alternating."""
@@ -46,8 +46,8 @@ class Pair(object):
         self.da, self.db = _lib.DeviceBuffer(a.nbytes).upload(a), _lib.DeviceBuffer(b.nbytes).upload(b)
         self.windows = reg.local_drift_windows(a.shape)
         self.origins = np.array([(r0, c0, r0, c0) for r0, _, c0, _ in self.windows], np.int32)
-        self.groups = reg._windows_by_extent([(r1 - r0, c1 - c0) for r0, r1, c0, c1 in self.windows])
-        big = max(ny * nx for ny, nx in self.groups) * 8
+        self.extents = [(r1 - r0, c1 - c0) for r0, r1, c0, c1 in self.windows]
+        big = max(ny * nx for ny, nx in self.extents) * 8
         self.wa, self.wb = _lib.DeviceBuffer(big), _lib.DeviceBuffer(big)
 
     def loop(self):
@@ -61,10 +61,7 @@ class Pair(object):
         return out
 
     def batched(self):
-        out = np.empty((len(self.windows), 2))
-        for (ny, nx), idx in self.groups.items():
-            out[idx] = reg.phase_cross_correlation_windows_dev(self.da.ptr, self.db.ptr, self.shape, self.origins[idx], ny, nx, 100)
-        return out
+        return reg.correlate_windows_by_extent(self.da.ptr, self.db.ptr, self.shape, self.origins, self.extents)
 
 
 def timed(fn):
@@ -130,14 +127,14 @@ def main():
         batched_ms.append(ms)
     rep_loop, rep_batched = counted(pair.loop), counted(pair.batched)
     res = {"size": a.size, "dtype": "float64", "windows": len(pair.windows),
-           "windows_per_extent": {"%dx%d" % k: len(v) for k, v in pair.groups.items()},
+           "windows_per_extent": {"%dx%d" % ext: pair.extents.count(ext) for ext in dict.fromkeys(pair.extents)},
            "shifts_equal": bool(np.array_equal(want, got)),
            "loop_ms": [round(v, 3) for v in loop_ms], "loop_ms_median": round(float(np.median(loop_ms)), 3),
            "batched_ms": [round(v, 3) for v in batched_ms], "batched_ms_median": round(float(np.median(batched_ms)), 3),
            "loop_ms_spread": round(max(loop_ms) - min(loop_ms), 3), "batched_ms_spread": round(max(batched_ms) - min(batched_ms), 3),
            "loop_kernel_launches": int(sum(c for c, _ in rep_loop.values())),
            "batched_kernel_launches": int(sum(c for c, _ in rep_batched.values())),
-           "loop_stream_waits": int(rep_loop["absargmax"][0]), "batched_stream_waits": int(rep_batched["absargmax"][0] // 2),
+           "loop_stream_waits": int(rep_loop["absargmax"][0] // 2), "batched_stream_waits": int(rep_batched["absargmax"][0] // 2),
            "batched_kernels_hip_events": {k: {"count": c, "ms": round(ms, 3)}
                                           for k, (c, ms) in sorted(rep_batched.items(), key=lambda kv: -kv[1][1])},
            "loop_kernels_hip_events": {k: {"count": c, "ms": round(ms, 3)}
