@@ -203,6 +203,14 @@ TIP_API int tip_unet_compose_border_dev(const void *x, int planes, int format, i
 /* first layer, Conv2D(2 -> 128): float32 (2, h, w) in, weights [9][2][128] float32, exact float32 FMAs               */
 TIP_API int tip_unet_conv_first_dev(const float *in, int h, int w, const float *wgt, const float *bias, const float *scale,
                                     const float *shift, void *out, int planes, int format, void *stream);
+/* The range of the fp16 pieces (format 1): activations are stored as fp16 pieces of scaled values and SATURATE at +-65504 (with  */
+/* the network's 2^4 activation scale: |v| = 4094).  Every format-1 launch of tip_unet_conv_dev (not its raw output, which is not */
+/* clamped) and of tip_unet_conv_first_dev ORs bit 0 (TIP_UNET_RANGE_F16) into a status word of the CALLING THREAD when a value  */
+/* on its way into the pieces had !(|x| <= 65504) in front of the clamp: beyond the range, infinite or NaN; exactly +-65504 is in */
+/* range.  reset zeroes the thread's word in `stream`'s order; read waits for `stream` (that stream only) and returns the word.  */
+#define TIP_UNET_RANGE_F16 1
+TIP_API int tip_unet_range_reset(void *stream);
+TIP_API int tip_unet_range_read(void *stream, int *flags);
 TIP_API int tip_unet_pool2_dev(const void *in, int h, int w, int ch, int planes, int format, void *out, void *stream);   /* MaxPool2D(2) */
 /* Conv2D(128 -> 2, 1x1) + softmax: float32 (2, npix) out; logits != 0: the pre-softmax values                         */
 TIP_API int tip_unet_head_dev(const void *in, long npix, const float *wgt, const float *bias, float *out, int planes, int format,

@@ -1,10 +1,11 @@
 """Driver of the hand-written U-Net kernels (csrc/tip_unet_conv.h, csrc/tip_unet.hip) for prediction_local._UNet: the arithmetic
 modes, the C-ABI's convolution descriptor, the splitting and packing of the weights (cached per mode on the network), the
-one-pass-at-a-time gate and the launch sequence of a forward pass.  The network's parameters, the decision whether an input takes
+one-pass-at-a-time gate, the fp16 range guard and the launch sequence of a forward pass.  The network's parameters, the decision whether an input takes
 this path and the torch / MIOpen restatement of the same layers stay in prediction_local."""
 import ctypes
 import os
 import threading
+import warnings
 
 import numpy as np
 
@@ -16,6 +17,25 @@ _MODES = {  # mode -> (pieces per value, piece format of the C-ABI: 0 bf16, 1 fp
     "bf16x6": (3, 0, 6, "9e-8"),
 }
 _F16_ACT_SCALE = 16.0      # fp16 pieces: activations are stored times 2^4 (saturate beyond |v| = 4094, absolute floor 2^-29)
+_RANGE_F16 = 1             # TIP_UNET_RANGE_F16: bit 0 of the thread's status word
+_RANGE_POLICIES = ("fallback", "raise", "off")
+_RANGE_FALLBACK_MODE = "bf16x6"      # float32's exponent range at float32-equivalent precision
+
+
+class UNetRangeError(_lib.TissueHipError):
+    """A forward pass in f16x3 met an activation beyond what its scaled fp16 pieces hold (TISSUE_HIP_UNET_RANGE=raise)."""
+
+
+def range_policy():
+    """TISSUE_HIP_UNET_RANGE: what a forward pass in f16x3 does about activations beyond fp16's range (the kernels clamp them; the
+    bf16 modes have float32's exponent range and are never guarded):
+    'fallback' (default): the pass is rerun in bf16x6, and the network object stays there (_UNet.range_exceeded, reset_range());
+    'raise': UNetRangeError;
+    'off': no check -- no reset, no read, no wait on the stream: the clamped result is returned."""
+    v = os.environ.get("TISSUE_HIP_UNET_RANGE", "fallback")
+    if v not in _RANGE_POLICIES:
+        raise ValueError("TISSUE_HIP_UNET_RANGE must be fallback, raise or off")
+    return v
 
 
 class _ConvDesc(ctypes.Structure):
@@ -249,21 +269,57 @@ def _forward_gate(device_index):
 
 
 def forward(net, x, mode, logits):
+    """A forward pass in `mode` under the range policy.  Only f16x3 is guarded: the thread's status word is zeroed on the pass's
+    stream in front of its first launch (inside the gate: the order of the launches is the gate's), and read behind its last --
+    the host waits for this stream alone and OUTSIDE the gate, so that a thread waiting for its own pass holds up nobody's ticket.
+    A set bit means some layer's output was clamped and the result is not the network's: `raise` says so, `fallback` runs the
+    same pass again in bf16x6 and keeps the network object there (no f16x3 attempt and no warning from then on)."""
+    policy = range_policy() if mode == "f16x3" else "off"
+    if policy == "fallback" and getattr(net, "range_exceeded", False):
+        return _gated(net, x, _RANGE_FALLBACK_MODE, logits)
+    out = _gated(net, x, mode, logits, guard=policy != "off")
+    if policy == "off":
+        return out
+    flags = ctypes.c_int(0)
+    _lib.check(_lib.lib().tip_unet_range_read(net.torch.cuda.current_stream(x.device).cuda_stream, ctypes.byref(flags)))
+    if not flags.value & _RANGE_F16:
+        return out
+    limit = int(65504 / _F16_ACT_SCALE)
+    if policy == "raise":
+        raise UNetRangeError("the U-Net's activations leave the range of mode f16x3 (|v| <= %d: fp16 pieces of 16 v), the result would be "
+                             "clamped; set TISSUE_HIP_UNET_ARITH=bf16x6 or TISSUE_HIP_UNET_RANGE=fallback" % limit)
+    del out
+    net.range_exceeded = True
+    if not getattr(net, "_range_warned", False):
+        net._range_warned = True
+        warnings.warn("this U-Net checkpoint's activations leave fp16's range (|v| <= %d in mode f16x3): its forward passes now run in "
+                      "%s, at about twice the matrix work" % (limit, _RANGE_FALLBACK_MODE), RuntimeWarning, stacklevel=3)
+    return _gated(net, x, _RANGE_FALLBACK_MODE, logits)
+
+
+def _gated(net, x, mode, logits, guard=False):
     """One network at a time on a device.  Frames in flight (worker threads, each with its own stream: movie.py, bench.py) would
     otherwise run their forward passes CONCURRENTLY -- the queues share the chip kernel by kernel, every pass takes N times as
     long, all of them end together and the frames' tails (small kernels, host stages) then run together with nothing to
     hide behind: the kernel trace shows the matrix cores idle for 8.5 % of the time (profiles/r04n_*).  Here a pass waits ON THE
     DEVICE (stream.wait_event, no host stall) for the pass queued before it, so that the passes run back to back in ticket order
-    and the other frames' tails and projections fill in beside them.  TISSUE_HIP_UNET_SERIAL=0 restores the free-for-all."""
+    and the other frames' tails and projections fill in beside them.  TISSUE_HIP_UNET_SERIAL=0 restores the free-for-all.
+    guard: the range word of this thread is zeroed on the stream in front of the pass (forward() reads it afterwards)."""
     torch = net.torch
-    if os.environ.get("TISSUE_HIP_UNET_SERIAL", "1") == "0":
+
+    def run():
+        if guard:
+            _lib.check(_lib.lib().tip_unet_range_reset(torch.cuda.current_stream(x.device).cuda_stream))
         return _launch(net, x, mode, logits)
+
+    if os.environ.get("TISSUE_HIP_UNET_SERIAL", "1") == "0":
+        return run()
     gate = _forward_gate(x.device.index)
     with gate["lock"]:
         s = torch.cuda.current_stream(x.device)
         if gate["event"] is not None and gate["stream"] != s.cuda_stream:
             s.wait_event(gate["event"])
-        out = _launch(net, x, mode, logits)
+        out = run()
         ev = torch.cuda.Event()
         ev.record(s)
         gate["event"], gate["stream"] = ev, s.cuda_stream

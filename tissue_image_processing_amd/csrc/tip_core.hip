@@ -280,6 +280,8 @@ int tip_shutdown(void)
     for (auto &e : c->free_events) (void)hipEventDestroy(e);
     if (c->edge_event) (void)hipEventDestroy(c->edge_event);
     if (c->prep_ws) (void)hipFree(c->prep_ws);
+    if (c->unet_status) (void)hipFree(c->unet_status);
+    if (c->unet_status_host) (void)hipHostFree(c->unet_status_host);
     if (c->pin_buf) (void)hipHostFree(c->pin_buf);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;

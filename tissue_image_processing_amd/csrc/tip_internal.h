@@ -26,6 +26,8 @@ struct Ctx {
     long last_ws_other = 0;   // ... and its number of pixels that are neither the image's minimum nor its maximum
     hipEvent_t edge_event = nullptr;   // tip_wait_stream / tip_stream_wait_tip
     void *prep_ws = nullptr;           // order-statistic state of tip_unet_prepare_f64_dev (used on the caller's stream only)
+    unsigned *unet_status = nullptr;   // 4-byte device word, bit 0: an fp16-piece U-Net launch of this thread met a value beyond fp16's range
+    int *unet_status_host = nullptr;   // ... and the pinned word tip_unet_range_read copies it to (tip_unet.hip: unet_status_word)
     void *pin_buf = nullptr;           // pinned host staging (the watershed's marker-order stage: counts down, pop order up)
     size_t pin_bytes = 0;
     bool prof = false;

@@ -395,6 +395,31 @@ static int unet_launch_check(const char *what)
     return TIP_OK;
 }
 
+// the range word's way to the host: one thread stores it into pinned host memory, in stream order (no copy engine, no second queue)
+static __global__ void k_unet_range_fetch(const unsigned *__restrict__ word, int *__restrict__ host) { *host = (int)*word; }
+
+// The calling thread's range word of the fp16-piece kernels (tip_unet_conv.h: uc_range_flag): made on the thread's first U-Net
+// launch or range call, zeroed in stream order in front of whatever that call queues on `s`, released with the context.  nullptr
+// on failure (error text set).
+static unsigned *unet_status_word(Ctx &c, hipStream_t s)
+{
+    if (c.unet_status) return c.unet_status;
+    unsigned *w = nullptr;
+    int *h = nullptr;
+    hipError_t e = hipMalloc(&w, sizeof(unsigned));
+    if (e == hipSuccess) e = hipHostMalloc(&h, sizeof(int), hipHostMallocMapped);
+    if (e == hipSuccess) e = hipMemsetAsync(w, 0, sizeof(unsigned), s);
+    if (e != hipSuccess) {
+        if (w) (void)hipFree(w);
+        if (h) (void)hipHostFree(h);
+        fail(TIP_ERR_HIP, "the U-Net's range word: %s", hipGetErrorString(e));
+        return nullptr;
+    }
+    c.unet_status = w;
+    c.unet_status_host = h;
+    return w;
+}
+
 // pl.py:90-122 + 21-29 for a device-resident image: img = (c, a, b) float64 with element strides (cstride, sa, sb), every channel
 // plane dense (sa == 1 && sb == a, or sb == 1 && sa == b); kind = dtype of the ORIGINAL image (0 float64, 1 float32, 2 integer:
 // normalize_channel's clip values take it).  out = (c, bp, ap) float32, zero-filled in front: out[c][bp - b + j][ap - a + i] =
@@ -473,6 +498,8 @@ int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
     p.out = (uint16_t *)d->out; p.outH = d->out_h; p.outW = d->out_w; p.sy = d->sy; p.sx = d->sx; p.oy = d->oy; p.ox = d->ox;
     p.pool_out = (uint16_t *)d->pool_out;
     p.acc_scale = d->format == 1 ? d->acc_scale : 1.f;
+    p.status = nullptr;
+    if (d->format == 1 && !d->raw_out && !(p.status = unet_status_word(c, (hipStream_t)stream))) return TIP_ERR_HIP;
 #ifdef UC_TRACE
     static unsigned long long *trace_dev = nullptr;
     if (!trace_dev) { TIP_HIP(hipMalloc(&trace_dev, 1024)); }
@@ -610,10 +637,42 @@ int tip_unet_conv_first_dev(const float *in, int h, int w, const float *wgt, con
         return fail(TIP_ERR_ARG, "tip_unet_conv_first_dev: bad arguments (w must be a multiple of 32, h * w of 256)");
     const dim3 grid((unsigned)((long)h * w / FIRST_PIX));
     hipStream_t s = (hipStream_t)stream;
-    if (format == 1) hipLaunchKernelGGL((k_unet_conv_first<2, true>), grid, dim3(256), 0, s, in, h, w, wgt, bias, scale, shift, (uint16_t *)out);
-    else if (planes == 2) hipLaunchKernelGGL(k_unet_conv_first<2>, grid, dim3(256), 0, s, in, h, w, wgt, bias, scale, shift, (uint16_t *)out);
-    else hipLaunchKernelGGL(k_unet_conv_first<3>, grid, dim3(256), 0, s, in, h, w, wgt, bias, scale, shift, (uint16_t *)out);
+    unsigned *status = nullptr;
+    if (format == 1 && !(status = unet_status_word(c, s))) return TIP_ERR_HIP;
+    if (format == 1) hipLaunchKernelGGL((k_unet_conv_first<2, true>), grid, dim3(256), 0, s, in, h, w, wgt, bias, scale, shift, (uint16_t *)out, status);
+    else if (planes == 2) hipLaunchKernelGGL(k_unet_conv_first<2>, grid, dim3(256), 0, s, in, h, w, wgt, bias, scale, shift, (uint16_t *)out, status);
+    else hipLaunchKernelGGL(k_unet_conv_first<3>, grid, dim3(256), 0, s, in, h, w, wgt, bias, scale, shift, (uint16_t *)out, status);
     return unet_launch_check("unet_conv_first");
+}
+
+// The fp16 pieces' range flag (tip_unet_conv.h: uc_range_flag).  reset: the calling thread's word is zeroed in stream order; read:
+// the word as it stands behind everything queued on `stream` so far -- the host waits for that stream alone.
+int tip_unet_range_reset(void *stream)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    const bool fresh = !c.unet_status;
+    unsigned *w = unet_status_word(c, (hipStream_t)stream);
+    if (!w) return TIP_ERR_HIP;
+    if (!fresh) TIP_HIP(hipMemsetAsync(w, 0, sizeof(unsigned), (hipStream_t)stream));
+    return TIP_OK;
+}
+
+int tip_unet_range_read(void *stream, int *flags)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (!flags) return fail(TIP_ERR_ARG, "tip_unet_range_read: null pointer");
+    unsigned *w = unet_status_word(c, (hipStream_t)stream);
+    if (!w) return TIP_ERR_HIP;
+    int *host_dev = nullptr;        // (the pinned word as the device addresses it)
+    TIP_HIP(hipHostGetDevicePointer((void **)&host_dev, c.unet_status_host, 0));
+    hipLaunchKernelGGL(k_unet_range_fetch, dim3(1), dim3(1), 0, (hipStream_t)stream, (const unsigned *)w, host_dev);
+    int rc = unet_launch_check("unet_range_fetch");
+    if (rc) return rc;
+    TIP_HIP(hipStreamSynchronize((hipStream_t)stream));
+    *flags = *(volatile int *)c.unet_status_host;
+    return TIP_OK;
 }
 
 int tip_unet_pool2_dev(const void *in, int h, int w, int ch, int planes, int format, void *out, void *stream)

@@ -79,6 +79,7 @@ struct ConvParams {
     uint16_t *pool_out;            // nullptr, or [plane][outH / 2][outW / 2][cout]: MaxPool2D(2) of the output (needs sy = sx = 1)
     float *raw_out;                // nullptr, or float32 [outH][outW][cout]: accumulator x acc_scale through the output mapping, nothing else ("raw output")
     const float *seed;             // nullptr, or float32 [H][W][cout] added to the layer's pre-bias sum ("accumulator seed"; plain output mapping)
+    unsigned *status;              // fp16 pieces: the launching thread's range word (tip::Ctx), see uc_range_flag; last, so that no other member moves
 };
 
 __device__ __forceinline__ unsigned bf16_rne_bits(float v)
@@ -153,6 +154,24 @@ __device__ __forceinline__ float uc_piece_value(unsigned halfword)
     else return __uint_as_float(halfword << 16);
 }
 __device__ __forceinline__ float uc_sat_f16(float v) { return __builtin_amdgcn_fmed3f(v, -UC_F16_MAX, UC_F16_MAX); }
+// The range check of the fp16 pieces.  The clamp above is silent, so every value on its way into it first goes through a running
+// max |x| of its lane -- one v_maximum3_f32 per pair of values, source modifiers for the absolute values; the instruction hands a
+// NaN on where v_max3_f32 would drop it -- and a wave compares once, when its values are through: !(max <= 65504) is true for a
+// value beyond the range, an infinity and a NaN, false for exactly +-65504.  Only a wave that fails sets bit 0 of the status word
+// (TIP_UNET_RANGE_F16 of include/tissue_hip.h), from one lane.  The pooled map, the fused head and the stored pieces all read
+// the registers this check has seen.
+__device__ __forceinline__ float uc_amax3(float m, float a, float b)
+{
+    // (as an instruction: from the builtins the compiler builds a tree of three-operand maxima with a repeated operand, 1.1 per value)
+    asm("v_maximum3_f32 %0, %0, |%1|, |%2|" : "+v"(m) : "v"(a), "v"(b));
+    return m;
+}
+__device__ __forceinline__ void uc_range_flag(float amax, unsigned *status, int lane)
+{
+    if (__any(!(amax <= UC_F16_MAX))) {
+        if (lane == 0) atomicOr(status, 1u);
+    }
+}
 
 // A counted wait on the vector-memory queue followed by the workgroup barrier.  The asynchronous global -> LDS copies of
 // LATER steps stay in flight across the barrier (a __syncthreads() would drain them: its fence waits for vmcnt(0) while an
@@ -566,6 +585,7 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
         const float *bip = p.bias + nblk * UC_BN + 16 * hf;
         const float *scp = p.scale + nblk * UC_BN + 16 * hf, *shp = p.shift + nblk * UC_BN + 16 * hf;
         const f32x2 inv2 = {p.acc_scale, p.acc_scale};      // fp16 pieces: accumulator -> the layer's units (a power of two)
+        float amax = 0.f;                                   // fp16 pieces: the lane's largest |value| in front of the clamp (uc_range_flag)
         // accumulator + bias (fp16 pieces: accumulator x acc_scale + bias, one fused multiply-add -- the product is exact)
         auto biased = [&](float a0, float a1, const f32x2 &b) -> f32x2 {
             if constexpr (F16) return __builtin_elementwise_fma(f32x2{a0, a1}, inv2, b);
@@ -587,6 +607,7 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
                         v01 = __builtin_elementwise_fma(f32x2{relu_bits(v01[0]), relu_bits(v01[1])}, s01, t01);
                         v23 = __builtin_elementwise_fma(f32x2{relu_bits(v23[0]), relu_bits(v23[1])}, s23, t23);
                         if constexpr (F16) {         // (stored values are scaled: s and t carry the activation scale)
+                            amax = uc_amax3(uc_amax3(amax, v01[0], v01[1]), v23[0], v23[1]);
                             v01 = f32x2{uc_sat_f16(v01[0]), uc_sat_f16(v01[1])};
                             v23 = f32x2{uc_sat_f16(v23[0]), uc_sat_f16(v23[1])};
                         }
@@ -599,6 +620,7 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
                         f32x2 v01 = biased(acc[m][n][q * 4 + 0], acc[m][n][q * 4 + 1], b01);     // (fp16 pieces, bias only: acc_scale and the bias carry the activation scale)
                         f32x2 v23 = biased(acc[m][n][q * 4 + 2], acc[m][n][q * 4 + 3], b23);
                         if constexpr (F16) {
+                            amax = uc_amax3(uc_amax3(amax, v01[0], v01[1]), v23[0], v23[1]);
                             v01 = f32x2{uc_sat_f16(v01[0]), uc_sat_f16(v01[1])};
                             v23 = f32x2{uc_sat_f16(v23[0]), uc_sat_f16(v23[1])};
                         }
@@ -609,6 +631,7 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
             }
             asm volatile("" ::: "memory");       // (one block's constants at a time: the loads are not all hoisted in front)
         }
+        if constexpr (F16) uc_range_flag(amax, p.status, lane);
     }
     if (p.head_out) {
         // The network's head (pl.py:69: Conv2D(2, 1) + softmax over the two classes) on the float32 values in the registers: a lane
@@ -728,7 +751,8 @@ constexpr int FIRST_PIX = 8 * FIRST_RUN;
 template <int NPL, bool F16 = false>
 __global__ void __launch_bounds__(256) k_unet_conv_first(const float *__restrict__ in, int H, int W, const float *__restrict__ wgt /* [9][2][128] */,
                                                          const float *__restrict__ bias, const float *__restrict__ scale,
-                                                         const float *__restrict__ shift, uint16_t *__restrict__ out)
+                                                         const float *__restrict__ shift, uint16_t *__restrict__ out,
+                                                         unsigned *__restrict__ status /* fp16 pieces: the range word (uc_range_flag) */)
 {
     const int cg = threadIdx.x & 31, slot = threadIdx.x >> 5;
     float4 w4[18];
@@ -763,6 +787,7 @@ __global__ void __launch_bounds__(256) k_unet_conv_first(const float *__restrict
     column(x0 - 1, win[0]);
     column(x0, win[1]);
     uint16_t *dst = out + pix0 * 128 + cg * 4;
+    float amax = 0.f;            // fp16 pieces: the thread's largest |value| in front of the clamp
     for (int it0 = 0; it0 < FIRST_RUN; it0 += 3) {
 #pragma unroll
         for (int u = 0; u < 3; ++u) {        // (unrolled by the window's period: every slot index is a compile-time constant)
@@ -784,7 +809,11 @@ __global__ void __launch_bounds__(256) k_unet_conv_first(const float *__restrict
             for (int j = 0; j < 4; ++j) {
                 const float r = a[j] > 0.f ? a[j] : 0.f;
                 a[j] = r * sv[j] + tv[j];
-                if constexpr (F16) a[j] = uc_sat_f16(a[j]);      // (s and t carry the activation scale)
+            }
+            if constexpr (F16) {      // (s and t carry the activation scale)
+                amax = uc_amax3(uc_amax3(amax, a[0], a[1]), a[2], a[3]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[j] = uc_sat_f16(a[j]);
             }
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl) {
@@ -795,6 +824,7 @@ __global__ void __launch_bounds__(256) k_unet_conv_first(const float *__restrict
             }
         }
     }
+    if constexpr (F16) uc_range_flag(amax, status, threadIdx.x & 63);
 }
 
 // value of split element e (0..7) of the 16-byte pieces pc[0..NPL)

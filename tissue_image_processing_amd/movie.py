@@ -153,7 +153,7 @@ class GpuFrameBackend(object):
         self.predictor_factory, self.keep_hc = predictor_factory, bool(keep_hc)
         self._predictors = {}   # id(pipeline) -> its SegmentationPredictor (U-Net mode), built on first use
         self.hc_maps = {}       # frame -> DeviceBuffer (float64 HC map (Y, X)), with keep_hc
-        self.unet_modes = {}    # frame -> the arithmetic its network pass really ran in (model.last_mode; "miopen": torch's layers)
+        self.unet_modes = {}    # frame -> the arithmetic its network pass really ran in (model.last_mode; "miopen": torch's layers, "bf16x6" under f16x3: the range fallback)
         self.ws_flags = {}      # frame -> flags of its tail's watershed (U-Net mode)
         self._shape, self._kw = (C, Z, Y, X), kw
         # cell_types: None, or FramePipeline.cell_types' keyword arguments (atoh_channel, threshold, percentage_above_threshold,

@@ -24,7 +24,7 @@ import os
 import numpy as np
 
 from . import _lib, _unet_hip
-from ._unet_hip import _ConvDesc, _MODES      # (tests and tools reach the descriptor through this module)
+from ._unet_hip import _ConvDesc, _MODES, UNetRangeError      # (tests and tools reach the descriptor through this module)
 
 
 def find_desired_shape(shape_y, shape_x):
@@ -170,12 +170,16 @@ class _UNet(object):
         g = torch.Generator().manual_seed(seed)
         self.p = {}
         self._hipw = {}                           # packed weights of the hand-written path, per arithmetic mode (_unet_hip.weights)
+        self.last_mode = None                     # what the last forward pass really ran in
+        self.reset_range()
         it = iter(weights) if weights is not None else None
 
         def expect(name, arr, shape):
             if tuple(arr.shape) != tuple(shape):
                 raise ValueError("checkpoint does not fit the U-Net of pl.py:31-72: %s has shape %s, expected %s"
                                  % (name, tuple(arr.shape), tuple(shape)))
+            if not np.isfinite(arr).all():        # (would otherwise be packed with scale 1 and poison every pass without a word)
+                raise ValueError("checkpoint array %s holds a NaN or an infinity" % name)
             return np.ascontiguousarray(arr, dtype=np.float32)
 
         def conv(name, cin, cout, k):
@@ -294,6 +298,13 @@ class _UNet(object):
                 continue
             self.p[k] = new.to(device=v.device, dtype=v.dtype).view(v.shape)
         self._hipw.clear()
+        self.reset_range()
+
+    def reset_range(self):
+        """Forgets that a forward pass in f16x3 left fp16's range (TISSUE_HIP_UNET_RANGE=fallback keeps such a network in bf16x6):
+        the next pass tries the requested mode again.  For callers that change the parameters in self.p themselves."""
+        self.range_exceeded = False
+        self._range_warned = False
 
     # -- hand-written convolution path (csrc/tip_unet_conv.h, driven by _unet_hip.py) -----------------------------------------------
     def _split_pack(self, taps, planes, fmt=0):
@@ -420,6 +431,7 @@ class SegmentationPredictor:
         self.model_shape = (first_axis_shape, second_axis_shape, 2)
         self.model = self.initialize_model()
         self.forward_ms = None   # bench.py sets this to a list: per-call duration of the network's forward pass
+        self.last_route = None   # predict(): dict(requested=, ran=, range_exceeded=)
 
     def initialize_model(self):
         weights = load_keras_weight_list(self.weights_path)
@@ -492,6 +504,8 @@ class SegmentationPredictor:
 
     # -- U2-U5 --------------------------------------------------------------------------------------------
     def predict(self, image, debug=False, return_device=False):
+        """debug: prints last_route, the arithmetic the network was asked for (TISSUE_HIP_UNET_ARITH) and the one that ran --
+        'miopen' when the torch layers did (small frames, another HIP runtime in the process), 'bf16x6' behind range_exceeded."""
         torch = self.torch
         padded, npad = self.prepare_image(image)
         if self.forward_ms is not None:
@@ -502,6 +516,10 @@ class SegmentationPredictor:
             ev1.record()
             ev1.synchronize()
             self.forward_ms.append(ev0.elapsed_time(ev1))
+        self.last_route = dict(requested=_unet_mode(), ran=getattr(self.model, "last_mode", None),
+                               range_exceeded=bool(getattr(self.model, "range_exceeded", False)))
+        if debug:
+            print("U-Net route: requested %(requested)s, ran %(ran)s, range_exceeded %(range_exceeded)s" % self.last_route)
         unp = prob[:, :, npad[1][0]:, npad[2][0]:]
         p0 = unp[0, 0]
         labels, hc = self.segment_probability(p0, return_device=return_device)
