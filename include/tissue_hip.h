@@ -72,6 +72,8 @@ TIP_API int tip_sync(void);                       /* wait for this thread's stre
 /*   TIP_UNET_TILE8 = -1|0|1, TIP_UNET_SPB = 1|3, TIP_UNET_XCD_MAP = 0|1               U-Net convolution schedule    */
 /*                                                  (TIP_UNET_SPB: every value above 1 means 3)                       */
 /*   TIP_UNET_TAIL_UNFUSED                                                            tail morphology as separate launches */
+/*   TIP_UNET_FIRST = mfma | valu | n    mode f16x3's first layer: matrix cores (default) or the float32 vector kernel; */
+/*                                       n > 1: matrix cores with n workgroups per CU (measurements)                    */
 /*   TIP_MB_SMALL = pixels, TIP_MB_BATCH = generations                                 two-valued flood: one-workgroup  */
 /*                                                                                    generations / host looks         */
 /* None of them changes results: they select between schedules / kernels that are tested to agree bit for bit       */
@@ -203,9 +205,17 @@ TIP_API int tip_unet_compose_border_dev(const void *x, int planes, int format, i
 /* first layer, Conv2D(2 -> 128): float32 (2, h, w) in, weights [9][2][128] float32, exact float32 FMAs               */
 TIP_API int tip_unet_conv_first_dev(const float *in, int h, int w, const float *wgt, const float *bias, const float *scale,
                                     const float *shift, void *out, int planes, int format, void *stream);
+/* the same layer for the fp16 pieces (format 1, two planes) on the matrix cores: packed_weights as tip_unet_conv_dev takes them  */
+/* for ONE tap and 32 input channels, rows k = 2 (3 ky + kx) + channel < 18 the layer's terms and the rest zeros; acc_scale as in */
+/* the descriptor; scale / shift carry the activation scale.  The input is scaled by 2^4 and split in the kernel: |x| <= 4094,    */
+/* beyond that the range flag below is raised.                                                                                    */
+TIP_API int tip_unet_conv_first_packed_dev(const float *in, int h, int w, const void *packed_weights, float acc_scale,
+                                           const float *bias, const float *scale, const float *shift, void *out, void *stream);
+/* 1: a forward pass in mode f16x3 runs its first layer through tip_unet_conv_first_packed_dev (default); 0: TIP_UNET_FIRST=valu  */
+TIP_API int tip_unet_first_mfma(void);
 /* The range of the fp16 pieces (format 1): activations are stored as fp16 pieces of scaled values and SATURATE at +-65504 (with  */
 /* the network's 2^4 activation scale: |v| = 4094).  Every format-1 launch of tip_unet_conv_dev (not its raw output, which is not */
-/* clamped) and of tip_unet_conv_first_dev ORs bit 0 (TIP_UNET_RANGE_F16) into a status word of the CALLING THREAD when a value  */
+/* clamped) and of tip_unet_conv_first[_packed]_dev ORs bit 0 (TIP_UNET_RANGE_F16) into a status word of the CALLING THREAD when a value  */
 /* on its way into the pieces had !(|x| <= 65504) in front of the clamp: beyond the range, infinite or NaN; exactly +-65504 is in */
 /* range.  reset zeroes the thread's word in `stream`'s order; read waits for `stream` (that stream only) and returns the word.  */
 #define TIP_UNET_RANGE_F16 1

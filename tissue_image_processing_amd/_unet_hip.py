@@ -245,6 +245,12 @@ def weights(net, mode, levels=None):
             conv_t("u%d.t" % i)
     w0 = p["d0.c1.w"].float()                                       # (128, 2, 3, 3) -> [tap][ci][cout]
     hw["first"] = w0.permute(2, 3, 1, 0).reshape(18, 128).contiguous()
+    if fmt:
+        # the same layer for the matrix cores (k_unet_conv_first_mfma): one tap x 32 input channels, rows k = 2 tap + channel < 18
+        # are the layer's terms in hw["first"]'s order, the rest zeros -> (packed weights, accumulator factor)
+        rows = torch.zeros((1, 32, 128), dtype=torch.float32, device=w0.device)
+        rows[0, :18] = hw["first"]
+        hw["first.packed"] = pack(rows, False)
     hw["head"] = (p["head.w"].float().reshape(2, 128) / act).contiguous()
     for k in list(p):
         if k.endswith((".b", ".s", ".t")) and not k.endswith(".t.w"):
@@ -401,6 +407,13 @@ def _launch(net, x, mode, logits):
     def first(h, w):
         """Conv2D(2 -> 128, 3x3) -> ReLU -> BatchNormalization on the float32 network input"""
         out = buf(h, w, 128)
+        if fmt == 1 and lib.tip_unet_first_mfma():       # fp16 pieces: on the matrix cores unless TIP_UNET_FIRST=valu
+            wp, inv = hw["first.packed"]
+            timed("first %dx%d 2->128" % (h, w), 2.0 * h * w * 18 * 128,
+                  lambda: _lib.check(lib.tip_unet_conv_first_packed_dev(x.data_ptr(), h, w, wp.data_ptr(), inv, hw["f:d0.c1.b"].data_ptr(),
+                                                                        hw["f:d0.b1.s"].data_ptr(), hw["f:d0.b1.t"].data_ptr(),
+                                                                        out.data_ptr(), stream)))
+            return out
         timed("first %dx%d 2->128" % (h, w), 2.0 * h * w * 18 * 128,
               lambda: _lib.check(lib.tip_unet_conv_first_dev(x.data_ptr(), h, w, hw["first"].data_ptr(), hw["f:d0.c1.b"].data_ptr(),
                                                              hw["f:d0.b1.s"].data_ptr(), hw["f:d0.b1.t"].data_ptr(), out.data_ptr(),

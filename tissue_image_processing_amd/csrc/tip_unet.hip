@@ -645,6 +645,31 @@ int tip_unet_conv_first_dev(const float *in, int h, int w, const float *wgt, con
     return unet_launch_check("unet_conv_first");
 }
 
+// The same layer for the fp16 pieces on the matrix cores (k_unet_conv_first_mfma): packed_weights as every layer's, one tap x 32
+// input channels whose rows 0 .. 17 are the 18 (tap, channel) terms.  Which of the two entries a forward pass calls is decided
+// in one place, by the caller, from tip_unet_first_mfma().
+int tip_unet_conv_first_packed_dev(const float *in, int h, int w, const void *packed_weights, float acc_scale, const float *bias,
+                                   const float *scale, const float *shift, void *out, void *stream)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (!in || !packed_weights || !bias || !scale || !shift || !out || h < 1 || w < 1 || w % FIRST_RUN || ((long)h * w) % FIRST_PIX)
+        return fail(TIP_ERR_ARG, "tip_unet_conv_first_packed_dev: bad arguments (w must be a multiple of 32, h * w of 256)");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned *status = unet_status_word(c, s);
+    if (!status) return TIP_ERR_HIP;
+    // four waves per workgroup, a wave walks the 32-pixel segments wave, wave + waves, ...: TIP_UNET_FIRST > 1 is the number of
+    // workgroups per CU (256 CUs) the launch is cut to; the default was chosen by measurement
+    const long wgs = (long)h * w / 128;                    // one segment per wave
+    const int per_cu = tuning().unet_first_mfma > 1 ? tuning().unet_first_mfma : FIRST_MFMA_WGS_PER_CU;
+    const dim3 grid((unsigned)std::min(wgs, 256L * per_cu));
+    hipLaunchKernelGGL(k_unet_conv_first_mfma, grid, dim3(256), 0, s, in, h, w, (const uint16_t *)packed_weights, acc_scale, bias, scale, shift,
+                       (uint16_t *)out, status);
+    return unet_launch_check("unet_conv_first_mfma");
+}
+
+int tip_unet_first_mfma(void) { return tuning().unet_first_mfma != 0; }
+
 // The fp16 pieces' range flag (tip_unet_conv.h: uc_range_flag).  reset: the calling thread's word is zeroed in stream order; read:
 // the word as it stands behind everything queued on `stream` so far -- the host waits for that stream alone.
 int tip_unet_range_reset(void *stream)
