@@ -8,36 +8,9 @@ import ctypes
 import numpy as np
 import pytest
 
+from unet_layers import ACT, MODES, TOL, _assert_regions, _join, _split
+
 pytestmark = pytest.mark.gpu
-
-MODES = {"f16x3": (2, 1), "bf16x3": (2, 0), "bf16x6": (3, 0)}     # mode -> (planes, piece format)
-TOL = {"f16x3": 2e-6, "bf16x3": 4e-5, "bf16x6": 2e-6}
-ACT = 16.0                                                        # _unet_hip._F16_ACT_SCALE
-
-
-def _split(t, planes, fmt):
-    import torch
-    pieces, rest = [], (t.float() * ACT if fmt else t.float())
-    for _ in range(planes):
-        h = rest.to(torch.float16 if fmt else torch.bfloat16)
-        pieces.append(h)
-        rest = rest - h.float()
-    return torch.stack(pieces, 0).contiguous()
-
-
-def _join(planes_t, fmt):
-    v = planes_t.float().sum(0)
-    return v / ACT if fmt else v
-
-
-def _regions(H, W):
-    """name -> index of the output (H, W, C): the whole tensor, the four edges, the four corners, the interior"""
-    r = {"all": (slice(None), slice(None)), "first row": (0, slice(None)), "last row": (H - 1, slice(None)),
-         "first column": (slice(None), 0), "last column": (slice(None), W - 1), "interior": (slice(1, H - 1), slice(1, W - 1))}
-    for ny, y in (("top", 0), ("bottom", H - 1)):
-        for nx, x in (("left", 0), ("right", W - 1)):
-            r["%s-%s corner" % (ny, nx)] = (y, x)
-    return r
 
 
 def _stage(mode, h, w, x, tw, bt, skip, w1, b1, scale, shift):
@@ -69,17 +42,6 @@ def _stage_reference(x, tw, bt, skip, w1, b1, scale, shift):
     cat = torch.cat([up, skip.double().permute(2, 0, 1)[None]], 1)
     ref = F.conv2d(cat, w1.double(), None, padding=1)[0].permute(1, 2, 0)
     return torch.relu(ref + b1.double()) * scale.double() + shift.double()
-
-
-def _assert_regions(mode, what, got, ref, names):
-    H, W = ref.shape[:2]
-    top = float(ref.abs().max())
-    regions = _regions(H, W)
-    for name in names:
-        idx = regions[name]
-        err = float((got[idx] - ref[idx]).abs().max()) / top
-        print("%s %s, %s: max error / max |value| = %.2e" % (mode, what, name, err))
-        assert err < TOL[mode], (what, name)
 
 
 @pytest.mark.parametrize("mode", ["f16x3", "bf16x3", "bf16x6"])

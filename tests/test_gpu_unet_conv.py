@@ -10,10 +10,9 @@ import ctypes
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from unet_layers import ACT, MODES, _join, _split
 
-MODES = {"f16x3": (2, 1), "bf16x3": (2, 0), "bf16x6": (3, 0)}     # mode -> (planes, piece format)
-ACT = 16.0                                                        # _unet_hip._F16_ACT_SCALE
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture()
@@ -21,22 +20,6 @@ def arith(monkeypatch):
     def set_mode(m):
         monkeypatch.setenv("TISSUE_HIP_UNET_ARITH", m)
     return set_mode
-
-
-def _split(t, planes, fmt=0):
-    """float32 tensor -> pieces; fp16 pieces (fmt 1) of the values times ACT, as the kernels store activations"""
-    import torch
-    pieces, rest = [], (t.float() * ACT if fmt else t.float())
-    for _ in range(planes):
-        h = rest.to(torch.float16 if fmt else torch.bfloat16)
-        pieces.append(h)
-        rest = rest - h.float()
-    return torch.stack(pieces, 0).contiguous()
-
-
-def _join(planes_t, fmt=0):
-    v = planes_t.float().sum(0)
-    return v / ACT if fmt else v
 
 
 def _pack(net, taps, planes, fmt):

@@ -97,6 +97,88 @@ def test_accuracy_against_float64(shape):
     assert err < 2e-6
 
 
+# Frames beyond one segment per wave.  The launch is min(h w / 128, 512) workgroups of four waves and a wave walks the 32-pixel
+# segments wave, wave + 2048, ...: up to 65536 pixels (every size above) the loop body runs once and the prefetch of the next
+# segment never.  264 x 256 is 2112 segments -- waves 0 .. 63 take two, the rest one (an uneven tail; a first iteration that does
+# and one that does not prefetch); 136 x 1024 is 4352 -- two or three (the prefetch guard goes false on a LATER iteration, for some
+# waves an iteration earlier than for others); 256 x 512 is 4096 -- exactly two.  TIP_UNET_FIRST=3 cuts the launch to 768 workgroups:
+# 264 x 256 is then one segment per wave from 528 workgroups, the largest single-segment launch.
+WALKS = [((264, 256), None), ((136, 1024), None), ((256, 512), None), ((264, 256), "3")]
+
+
+@pytest.mark.parametrize("shape,first", WALKS)
+def test_segment_walk(shape, first):
+    """The construction of test_exact_case_equals_the_vector_kernel_bit_for_bit (bit for bit against the vector kernel, which equals
+    float64) and the data and bound of test_accuracy_against_float64 (2e-6), on frames whose waves walk several segments; the
+    status word stays 0."""
+    import contextlib
+    import torch
+    from tissue_image_processing_amd import _lib
+    H, W = shape
+    hook = _lib.tuning(TIP_UNET_FIRST=first) if first else contextlib.nullcontext()
+    g = torch.Generator().manual_seed(29 + H)
+    x = torch.randint(0, 64, (2, H, W), generator=g).float() / 16
+    w = 2.0 ** -torch.randint(0, 4, (128, 2, 3, 3), generator=g).float() * (torch.randint(0, 2, (128, 2, 3, 3), generator=g).float() * 2 - 1)
+    bias = torch.randint(-64, 64, (128,), generator=g).float() / 16
+    scale = 2.0 ** torch.randint(-1, 2, (128,), generator=g).float()
+    shift = torch.randint(-64, 64, (128,), generator=g).float() / 16
+    with hook:
+        new, st_new = _run("mfma", x, w, bias, scale, shift)
+    old, st_old = _run("valu", x, w, bias, scale, shift)
+    assert st_new == 0 and st_old == 0
+    ref = torch.nn.functional.conv2d(x.double()[None], w.double(), None, padding=1)[0].permute(1, 2, 0)
+    ref = torch.relu(ref + bias.double()) * scale.double() + shift.double()
+    assert torch.equal(old.float().sum(0).double() / ACT, ref)
+    diff = (new.view(torch.int16) != old.view(torch.int16)).any(0).any(-1)          # (H, W): pixels with a differing piece word
+    print("%dx%d: %d of %d pixels differ from the vector kernel; first: %s" % (H, W, int(diff.sum()), diff.numel(), diff.nonzero()[:4].tolist()))
+    assert not bool(diff.any())
+    assert torch.equal(new.float().sum(0).double() / ACT, ref)
+    del new, old, diff
+
+    x = torch.randn((2, H, W), generator=g)
+    w = torch.randn((128, 2, 3, 3), generator=g) * 0.1
+    bias, scale, shift = torch.randn(128, generator=g), torch.rand(128, generator=g) + 0.5, torch.randn(128, generator=g)
+    with hook:
+        out, st = _run("mfma", x, w, bias, scale, shift)
+    got = out.float().sum(0).double() / ACT
+    ref = torch.nn.functional.conv2d(x.double()[None], w.double(), None, padding=1)[0].permute(1, 2, 0)
+    ref = torch.relu(ref + bias.double()) * scale.double() + shift.double()
+    err = float((got - ref).abs().max() / ref.abs().max())
+    print("first layer on the matrix cores, %dx%d%s: max error / max |value| = %.2e" % (H, W, ", TIP_UNET_FIRST=3" if first else "", err))
+    assert st == 0
+    assert err < 2e-6
+
+
+@pytest.mark.parametrize("mode", ["bf16x3", "bf16x6"])
+def test_vector_kernel_bf16_pieces_against_float64(mode):
+    """tip_unet_conv_first_dev with bf16 pieces (the first layer of modes bf16x3 and bf16x6, otherwise reached by whole-network runs
+    only) at 24 x 96 against float64, at the per-layer bounds of the layer tests (unet_layers.TOL)."""
+    import torch
+    from tissue_image_processing_amd import _lib
+    from unet_layers import MODES, TOL, Fenced
+    planes, fmt = MODES[mode]
+    dev, lib, stream = _ctx()
+    H, W = 24, 96
+    g = torch.Generator().manual_seed(53)
+    x = torch.randn((2, H, W), generator=g)
+    w = torch.randn((128, 2, 3, 3), generator=g) * 0.1
+    bias, scale, shift = torch.randn(128, generator=g), torch.rand(128, generator=g) + 0.5, torch.randn(128, generator=g)
+    xd = x.contiguous().to(dev)
+    rows18 = w.permute(2, 3, 1, 0).reshape(18, 128).contiguous().to(dev)
+    fb, fs, ft = bias.to(dev), scale.to(dev), shift.to(dev)
+    out = Fenced((planes, H, W, 128), torch.bfloat16, dev)
+    _lib.check(lib.tip_unet_conv_first_dev(xd.data_ptr(), H, W, rows18.data_ptr(), fb.data_ptr(), fs.data_ptr(), ft.data_ptr(),
+                                           out.t.data_ptr(), planes, fmt, stream))
+    torch.cuda.synchronize()
+    out.check("%s first layer" % mode)
+    got = out.t.cpu().float().sum(0).double()
+    ref = torch.nn.functional.conv2d(x.double()[None], w.double(), None, padding=1)[0].permute(1, 2, 0)
+    ref = torch.relu(ref + bias.double()) * scale.double() + shift.double()
+    err = float((got - ref).abs().max() / ref.abs().max())
+    print("%s first layer (vector kernel), %dx%d: max error / max |value| = %.2e" % (mode, H, W, err))
+    assert err < TOL[mode]
+
+
 def _one_channel(x_value, scale_value, pixel=None, channel=5):
     """8 x 32 pixels, input channel 0 = 1 everywhere (x_value at `pixel`), centre weight 2^-12 (input test) or 1 into `channel`, bias
     and shift 0, BatchNorm scale x activation scale = scale_value -> (status, hi and lo planes of the channel)"""

@@ -466,10 +466,18 @@ int tip_unet_prepare_f64_dev(const double *img, int c, int a, int b, long cstrid
     return unet_launch_check("unet_prepare");
 }
 
-int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
+// The flavour of k_unet_conv a descriptor's launch runs, and everything else that follows from the descriptor and the tuning alone.
+// `which` is the code include/tissue_hip.h tabulates next to tip_unet_conv_flavour.
+struct ConvPlan {
+    int which;                     // 0 <2,8,2>  1 <2,16,2>  2 <2,16,4>  3 <3,8,2>  4 <2,16,2,2>  6 <2,16,4,1,3>
+    int th, spb;                   // tile rows, steps per barrier
+    int ntiles, nblks, xcd_map;
+    size_t lds;
+};
+
+// Validates the descriptor and chooses the flavour: TIP_OK and `pl`, or the error tip_unet_conv_dev returns.  Touches no device.
+static int unet_conv_plan(const tip_unet_conv_desc *d, ConvPlan &pl)
 {
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
     if (!d || !d->in0 || !d->weights || (!d->bias && !d->raw_out) || (!d->out && !d->head_out && !d->raw_out)) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: null pointer");
     if (d->planes != 2 && d->planes != 3) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: planes must be 2 or 3");
     if (d->format != 0 && d->format != 1) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: format is 0 (bf16 pieces) or 1 (fp16 pieces)");
@@ -486,13 +494,63 @@ int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
     if (18L * d->w * (d->c0 > d->c1 ? d->c0 : d->c1) * 2 >= (1L << 32) - 65536)
         return fail(TIP_ERR_UNSUPPORTED, "tip_unet_conv_dev: 18 rows of %d pixels x %d channels exceed the 4 GB a buffer resource addresses",
                     d->w, d->c0 > d->c1 ? d->c0 : d->c1);
+    for (int t = 0; t < d->ntaps; ++t)
+        if (d->dy[t] < -1 || d->dy[t] > 1 || d->dx[t] < -1 || d->dx[t] > 1) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: tap offsets are -1, 0 or 1");
+    if (d->head_out && (!d->head_w || !d->head_b || d->cout != UC_BN || !d->scale || d->pool_out || d->sy != 1 || d->sx != 1 || d->oy != 0 || d->ox != 0 ||
+                        d->out_h != d->h || d->out_w != d->w))
+        return fail(TIP_ERR_ARG, "tip_unet_conv_dev: the fused head needs a 128-channel Conv2D + BatchNorm layer with the plain output mapping");
+    if (d->pool_out && (d->sy != 1 || d->sx != 1 || d->oy != 0 || d->ox != 0 || d->out_h != d->h || d->out_w != d->w))
+        return fail(TIP_ERR_ARG, "tip_unet_conv_dev: pool_out needs the plain output mapping");
+    if (d->raw_out && (d->head_out || d->pool_out)) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: raw output goes without the head and the pooled map");
+    if (d->seed && (d->sy != 1 || d->sx != 1 || d->oy != 0 || d->ox != 0 || d->out_h != d->h || d->out_w != d->w))
+        return fail(TIP_ERR_ARG, "tip_unet_conv_dev: the accumulator seed needs the plain output mapping");
+    // 16-row tiles (one 512-thread workgroup per CU) where the grid allows: half the weight copies per MFMA, and LDS for five
+    // weight buffers (copies four steps ahead) when the stencil has >= 4 taps; two pieces only (LDS)
+    const int t8 = tuning().unet_tile8;
+    // (measured per layer at 2048^2: the short K loops of the 128-channel 3x3 layers gain 1-3 % from two workgroups per CU -- one's
+    // epilogue behind the other's products -- every other layer is faster with the shared weight tile of the 16-row workgroup)
+    const bool want8 = t8 == 1 || (t8 < 0 && d->ntaps == 9 && d->c0 + d->c1 <= 128);
+    const int th = (d->planes == 2 && d->h % 16 == 0 && !want8) ? 16 : 8;
+    const int dist = (th == 16 && d->ntaps >= 4) ? 4 : 2;
+    const int da = (th == 16 && d->ntaps <= 2) ? 2 : 1;       // one- and two-tap stencils: activation tiles two chunks ahead
+    const int threads = th * 32, hp = UC_HW * (th + 2);
+    pl.th = th;
+    pl.ntiles = (d->h / th) * (d->w / UC_TW); pl.nblks = d->cout / UC_BN;
+    pl.xcd_map = (tuning().unet_xcd_map && pl.nblks > 1 && pl.ntiles % 8 == 0) ? 1 : 0;
+    const int a_per = (d->planes * ((hp * 2 + 63) / 64) * 64 + threads - 1) / threads;     // (a plane's halo tile padded to whole waves, as in the kernel)
+    // three steps per barrier: 3x3 stencils on 16-row tiles (a chunk's nine taps in three iterations, nine weight buffers);
+    // TIP_UNET_SPB = 1 keeps one step per barrier, every larger value means three
+    pl.spb = (th == 16 && dist == 4 && d->ntaps == 9 && tuning().unet_spb > 1) ? 3 : 1;
+    pl.lds = (size_t)(da + 1) * a_per * threads * 16 + (size_t)(pl.spb > 1 ? 3 * pl.spb : dist + 1) * d->planes * 256 * 16;
+    // the kernel flavour <pieces, tile rows, weight steps ahead, activation chunks ahead, steps per barrier>
+    if (d->planes == 3) pl.which = 3;        // <3, 8, 2>
+    else if (th == 8) pl.which = 0;          // <2, 8, 2>
+    else if (pl.spb == 3) pl.which = 6;      // <2, 16, 4, 1, 3>: 3x3 stencils
+    else if (dist == 4) pl.which = 2;        // <2, 16, 4>: four and more taps, one step per barrier
+    else if (da == 2) pl.which = 4;          // <2, 16, 2, 2>: one and two taps
+    else pl.which = 1;                       // <2, 16, 2>: three taps
+    return TIP_OK;
+}
+
+int tip_unet_conv_flavour(const tip_unet_conv_desc *d)
+{
+    ConvPlan pl;
+    const int rc = unet_conv_plan(d, pl);
+    return rc ? rc : pl.which;
+}
+
+int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    ConvPlan pl;
+    if (const int rc = unet_conv_plan(d, pl)) return rc;
     ConvParams p;
     p.in0 = (const uint16_t *)d->in0; p.in1 = (const uint16_t *)(d->c1 > 0 ? d->in1 : d->in0);
     p.c0 = d->c0; p.c1 = d->c1; p.H = d->h; p.W = d->w;
     p.w = (const uint16_t *)d->weights; p.ntaps = d->ntaps;
     for (int t = 0; t < 9; ++t) {
         p.dy[t] = t < d->ntaps ? d->dy[t] : 0; p.dx[t] = t < d->ntaps ? d->dx[t] : 0;
-        if (p.dy[t] < -1 || p.dy[t] > 1 || p.dx[t] < -1 || p.dx[t] > 1) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: tap offsets are -1, 0 or 1");
     }
     p.cout = d->cout; p.bias = d->bias; p.scale = d->scale; p.shift = d->shift;
     p.out = (uint16_t *)d->out; p.outH = d->out_h; p.outW = d->out_w; p.sy = d->sy; p.sx = d->sx; p.oy = d->oy; p.ox = d->ox;
@@ -507,42 +565,12 @@ int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
     p.trace = trace_dev;
 #endif
     p.head_w = d->head_w; p.head_b = d->head_b; p.head_out = d->head_out;
-    if (d->head_out && (!d->head_w || !d->head_b || d->cout != UC_BN || !d->scale || d->pool_out || d->sy != 1 || d->sx != 1 || d->oy != 0 || d->ox != 0 ||
-                        d->out_h != d->h || d->out_w != d->w))
-        return fail(TIP_ERR_ARG, "tip_unet_conv_dev: the fused head needs a 128-channel Conv2D + BatchNorm layer with the plain output mapping");
-    if (d->pool_out && (d->sy != 1 || d->sx != 1 || d->oy != 0 || d->ox != 0 || d->out_h != d->h || d->out_w != d->w))
-        return fail(TIP_ERR_ARG, "tip_unet_conv_dev: pool_out needs the plain output mapping");
     p.raw_out = d->raw_out; p.seed = d->seed;
-    if (d->raw_out && (d->head_out || d->pool_out)) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: raw output goes without the head and the pooled map");
-    if (d->seed && (d->sy != 1 || d->sx != 1 || d->oy != 0 || d->ox != 0 || d->out_h != d->h || d->out_w != d->w))
-        return fail(TIP_ERR_ARG, "tip_unet_conv_dev: the accumulator seed needs the plain output mapping");
-    // 16-row tiles (one 512-thread workgroup per CU) where the grid allows: half the weight copies per MFMA, and LDS for five
-    // weight buffers (copies four steps ahead) when the stencil has >= 4 taps; two pieces only (LDS)
-    const int t8 = tuning().unet_tile8;
-    // (measured per layer at 2048^2: the short K loops of the 128-channel 3x3 layers gain 1-3 % from two workgroups per CU -- one's
-    // epilogue behind the other's products -- every other layer is faster with the shared weight tile of the 16-row workgroup)
-    const bool want8 = t8 == 1 || (t8 < 0 && d->ntaps == 9 && d->c0 + d->c1 <= 128);
-    const int th = (d->planes == 2 && d->h % 16 == 0 && !want8) ? 16 : 8;
-    const int dist = (th == 16 && d->ntaps >= 4) ? 4 : 2;
-    const int da = (th == 16 && d->ntaps <= 2) ? 2 : 1;       // one- and two-tap stencils: activation tiles two chunks ahead
-    const int threads = th * 32, hp = UC_HW * (th + 2);
-    const int ntiles = (d->h / th) * (d->w / UC_TW), nblks = d->cout / UC_BN;
-    p.xcd_map = (tuning().unet_xcd_map && nblks > 1 && ntiles % 8 == 0) ? 1 : 0;
-    const dim3 grid = p.xcd_map ? dim3((unsigned)(ntiles * nblks)) : dim3(ntiles, nblks);
-    const int a_per = (d->planes * ((hp * 2 + 63) / 64) * 64 + threads - 1) / threads;     // (a plane's halo tile padded to whole waves, as in the kernel)
-    // three steps per barrier: 3x3 stencils on 16-row tiles (a chunk's nine taps in three iterations, nine weight buffers);
-    // TIP_UNET_SPB = 1 keeps one step per barrier, every larger value means three
-    const int spb = (th == 16 && dist == 4 && d->ntaps == 9 && tuning().unet_spb > 1) ? 3 : 1;
-    const size_t lds = (size_t)(da + 1) * a_per * threads * 16 + (size_t)(spb > 1 ? 3 * spb : dist + 1) * d->planes * 256 * 16;
+    p.xcd_map = pl.xcd_map;
+    const int which = pl.which, threads = pl.th * 32;
+    const size_t lds = pl.lds;
+    const dim3 grid = p.xcd_map ? dim3((unsigned)(pl.ntiles * pl.nblks)) : dim3(pl.ntiles, pl.nblks);
     hipStream_t s = (hipStream_t)stream;
-    // the kernel flavour <pieces, tile rows, weight steps ahead, activation chunks ahead, steps per barrier>
-    int which;
-    if (d->planes == 3) which = 3;        // <3, 8, 2>
-    else if (th == 8) which = 0;          // <2, 8, 2>
-    else if (spb == 3) which = 6;         // <2, 16, 4, 1, 3>: 3x3 stencils
-    else if (dist == 4) which = 2;        // <2, 16, 4>: four and more taps, one step per barrier
-    else if (da == 2) which = 4;          // <2, 16, 2, 2>: one and two taps
-    else which = 1;                       // <2, 16, 2>: three taps
     // the >64 KB dynamic LDS attribute is set once per (device, kernel): one atomic bit each
     static std::atomic<unsigned> attr_done[64];
     const unsigned bit = 1u << (which + (d->format ? 9 : 0));
@@ -579,12 +607,12 @@ int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
         unsigned long long tr[128];
         TIP_HIP(hipStreamSynchronize(s));
         TIP_HIP(hipMemcpy(tr, trace_dev, sizeof tr, hipMemcpyDeviceToHost));
-        for (int k = 0; k < th / 2; ++k) {
+        for (int k = 0; k < pl.th / 2; ++k) {
             const unsigned long long *t = tr + 16 * k;
             const double n = (double)t[4];
             fprintf(stderr, "UC_TRACE th %d spb %d taps %d cin %d cout %d grid %dx%d wave %d simd %d: per STEP (shader clocks; sums over the loop / steps): copies %.0f, products %.0f (first MFMA out after %.0f), "
                             "vmcnt wait %.0f, barrier %.0f, total %.0f; steps %.0f; whole loop %.0f, prologue %.0f, epilogue %.0f clocks\n",
-                    th, spb, d->ntaps, d->c0 + d->c1, d->cout, d->h, d->w, k, (int)((t[7] >> 4) & 3), t[0] / n, t[2] / n, t[1] / n, t[6] / n, (t[3] - t[6]) / n, t[5] / n, n, (double)t[5], (double)t[8], (double)t[9]);
+                    pl.th, pl.spb, d->ntaps, d->c0 + d->c1, d->cout, d->h, d->w, k, (int)((t[7] >> 4) & 3), t[0] / n, t[2] / n, t[1] / n, t[6] / n, (t[3] - t[6]) / n, t[5] / n, n, (double)t[5], (double)t[8], (double)t[9]);
         }
     }
 #endif
