@@ -464,7 +464,7 @@ class SegmentationPredictor:
         npad = ((0, 0), (first_axis_pixels - shape1, 0), (second_axis_pixels - shape2, 0), (0, 0))
         # One library submission on torch's stream (tip_unet_prepare_f64_dev): the four order statistics of every channel by
         # radix select, numpy's lerp, clip / scale / transpose / pad in one pass -- nothing comes back to the host.  (The torch
-        # expressions below sort every channel and make a dozen elementwise passes: 2.2 ms of a 2048^2 frame against 0.4.)
+        # expressions below sort every channel and make a dozen elementwise passes: 2.2 ms of a 2048^2 frame against 0.25.)
         dense = t.is_cuda and C <= 8 and ((t.stride(1) == 1 and t.stride(2) == Y) or (t.stride(2) == 1 and t.stride(1) == X))
         if dense and (C == 1 or t.stride(0) >= X * Y) and shares_runtime_with_torch(t) and not os.environ.get("TISSUE_HIP_PREPARE_TORCH"):
             if self.model_shape != (first_axis_pixels, second_axis_pixels, 2):
