@@ -1,5 +1,5 @@
 """GPU: a decoder level's transposed convolution folded into the convolution behind it (_unet_hip.compose, the raw-output
-and accumulator-seed modes of csrc/tip_unet_conv.h and its border pass) against float64 evaluations of the ORIGINAL, uncomposed layers
+and accumulator-seed modes of csrc/tip_unet_conv.h and the border pass of csrc/tip_unet_planes.h) against float64 evaluations of the ORIGINAL, uncomposed layers
 on the unsplit values.  Error measure and bounds are those of test_gpu_unet_conv.test_single_layers_against_float64: max error / max
 |reference| (of the whole tensor) below 2e-6 / 4e-5 / 2e-6 for f16x3 / bf16x3 / bf16x6 -- asserted on the whole output and again on
 every edge region alone, where a missing border term is an error of the values' own size."""

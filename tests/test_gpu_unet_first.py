@@ -1,4 +1,4 @@
-"""GPU: the U-Net's first layer on the matrix cores (csrc/tip_unet_conv.h: k_unet_conv_first_mfma, mode f16x3) -- an implicit im2col
+"""GPU: the U-Net's first layer on the matrix cores (csrc/tip_unet_first.h: k_unet_conv_first_mfma, mode f16x3) -- an implicit im2col
 with K = 18 padded to 32 -- against the float32 vector kernel it replaces there (bit for bit on data both compute exactly), against
 float64, its range flag, and the hook TIP_UNET_FIRST that selects between the two."""
 import ctypes

@@ -1,5 +1,5 @@
-"""Driver of the hand-written U-Net kernels (csrc/tip_unet_conv.h, csrc/tip_unet.hip) for prediction_local._UNet: the arithmetic
-modes, the C-ABI's convolution descriptor, the splitting and packing of the weights (cached per mode on the network), the
+"""Driver of the hand-written U-Net kernels (csrc/tip_unet_conv.h, tip_unet_first.h, tip_unet_planes.h; launchers in
+csrc/tip_unet.hip) for prediction_local._UNet: the arithmetic modes, the C-ABI's convolution descriptor, the splitting and packing of the weights (cached per mode on the network), the
 one-pass-at-a-time gate, the fp16 range guard and the launch sequence of a forward pass.  The network's parameters, the decision whether an input takes
 this path and the torch / MIOpen restatement of the same layers stay in prediction_local."""
 import ctypes

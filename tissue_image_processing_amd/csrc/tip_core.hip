@@ -58,6 +58,13 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
+int launch_check(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(TIP_ERR_HIP, "launch %s: %s", what, hipGetErrorString(e));
+    return TIP_OK;
+}
+
 void *ws_alloc(size_t bytes)
 {
     Ctx &c = ctx();
@@ -372,6 +379,43 @@ int tip_sync(void)
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
     TIP_HIP(hipStreamSynchronize(c.stream));
+    return TIP_OK;
+}
+
+// Which device does this runtime think `p` lives on?  >= 0: the ordinal; negative: `p` is not a device pointer THIS copy of
+// the HIP runtime knows.  A caller that hands over torch pointers and torch's stream (tip_bias_relu_affine_f32_dev,
+// tip_unet_tail_dev) checks once that torch and this library share one runtime: PyTorch wheels bundle their own
+// libamdhip64, and two loaded runtimes do not know each other's allocations or stream handles.
+int tip_pointer_device(const void *p)
+{
+    hipPointerAttribute_t a;
+    if (!p || hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return TIP_ERR_ARG; }
+    if (a.type != hipMemoryTypeDevice) return TIP_ERR_ARG;
+    return a.device;
+}
+
+// Ordering edges between the calling thread's library stream and a foreign HIP stream (torch's current stream).  Neither
+// blocks the host.  tip_wait_stream: work submitted to the library AFTER the call starts after everything queued on
+// `stream` BEFORE the call -- call it after allocating (from torch's caching allocator) every buffer the library is going
+// to write: the allocator hands out blocks whose previous owner's kernels may still be queued on that stream.
+int tip_wait_stream(void *stream)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (!c.edge_event) TIP_HIP(hipEventCreateWithFlags(&c.edge_event, hipEventDisableTiming));
+    TIP_HIP(hipEventRecord(c.edge_event, (hipStream_t)stream));
+    TIP_HIP(hipStreamWaitEvent(c.stream, c.edge_event, 0));
+    return TIP_OK;
+}
+
+// ... and the other direction: `stream` waits for everything submitted to the library so far.
+int tip_stream_wait_tip(void *stream)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (!c.edge_event) TIP_HIP(hipEventCreateWithFlags(&c.edge_event, hipEventDisableTiming));
+    TIP_HIP(hipEventRecord(c.edge_event, c.stream));
+    TIP_HIP(hipStreamWaitEvent((hipStream_t)stream, c.edge_event, 0));
     return TIP_OK;
 }
 

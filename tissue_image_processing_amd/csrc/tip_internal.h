@@ -37,6 +37,7 @@ struct Ctx {
 
 Ctx &ctx();                       // lazily initialised for device 0 unless tip_init() chose another
 int fail(int code, const char *fmt, ...);
+int launch_check(const char *what);   // hipGetLastError() behind launches on a caller's stream: TIP_OK, or TIP_ERR_HIP with "launch <what>: ..."
 void *ws_alloc(size_t bytes);     // nullptr on failure (error text set)
 void *pinned_scratch(size_t bytes);   // this thread's pinned host staging buffer, grown as needed (nullptr on failure)
 void ws_free(void *p);

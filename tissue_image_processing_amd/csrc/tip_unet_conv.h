@@ -36,7 +36,7 @@
 //     registers in the prologue (times 1 / acc_scale, a power of two), behind the first tiles' copies.
 // The decoder uses them to fold every Conv2DTranspose into the Conv2D behind it (there is no activation between the two, so their
 // composition is a 4 / 6 / 6 / 9-tap convolution per output parity on the LOW-resolution grid; weights built by the caller): four raw
-// launches leave the convolution's sum over its up-sampled half, k_unet_compose_edge / k_unet_compose_edge_bias (end of this file)
+// launches leave the convolution's sum over its up-sampled half, k_unet_compose_edge / k_unet_compose_edge_bias (tip_unet_planes.h)
 // correct the edges the cropped transposed convolution makes special, and the convolution itself runs over the skip tensor alone,
 // seeded.  The up-sampled tensor never exists and the 2 / 2 / 1-tap parity launches, the slowest of the pass, are not run.
 // The kernel body has the details next to the code; DESIGN.md 5.7 has the measurements (clock trace, power-limited MFMA ceiling).
@@ -171,6 +171,74 @@ __device__ __forceinline__ void uc_range_flag(float amax, unsigned *status, int 
     if (__any(!(amax <= UC_F16_MAX))) {
         if (lane == 0) atomicOr(status, 1u);
     }
+}
+
+// ---- the epilogue's pieces, shared by k_unet_conv and k_unet_conv_first_mfma (tip_unet_first.h) -----------------------------------
+// A lane holds sixteen adjacent channels of its pixel per 32-channel block, so the per-channel constants come as float4s and the
+// arithmetic runs on groups of FOUR adjacent channels, packed two per instruction.
+// accumulator + bias (fp16 pieces: accumulator x acc_scale (inv2, a power of two) + bias, one fused multiply-add -- the product is exact)
+template <bool F16>
+__device__ __forceinline__ f32x2 uc_biased(const f32x2 &a, const f32x2 &inv2, const f32x2 &b)
+{
+    if constexpr (F16) return __builtin_elementwise_fma(a, inv2, b);
+    else return a + b;
+}
+// fp16 pieces: the running max |x| (uc_amax3) and then the clamp; bf16 pieces: nothing
+template <bool F16>
+__device__ __forceinline__ void uc_clamp4(f32x2 &v01, f32x2 &v23, float &amax)
+{
+    if constexpr (F16) {
+        amax = uc_amax3(uc_amax3(amax, v01[0], v01[1]), v23[0], v23[1]);
+        v01 = f32x2{uc_sat_f16(v01[0]), uc_sat_f16(v01[1])};
+        v23 = f32x2{uc_sat_f16(v23[0]), uc_sat_f16(v23[1])};
+    }
+}
+// One group of four adjacent channels, accumulators in v01, v23 -> the values to split.  Conv2D + BatchNorm: bias -> ReLU -> scale,
+// shift (one fused multiply-add; fp16 pieces: s and t carry the activation scale) ...
+template <bool F16>
+__device__ __forceinline__ void uc_activate4(f32x2 &v01, f32x2 &v23, const float4 &b, const float4 &s, const float4 &t, const f32x2 &inv2, float &amax)
+{
+    v01 = uc_biased<F16>(v01, inv2, f32x2{b.x, b.y});
+    v23 = uc_biased<F16>(v23, inv2, f32x2{b.z, b.w});
+    v01 = __builtin_elementwise_fma(f32x2{relu_bits(v01[0]), relu_bits(v01[1])}, f32x2{s.x, s.y}, f32x2{t.x, t.y});
+    v23 = __builtin_elementwise_fma(f32x2{relu_bits(v23[0]), relu_bits(v23[1])}, f32x2{s.z, s.w}, f32x2{t.z, t.w});
+    uc_clamp4<F16>(v01, v23, amax);
+}
+// ... Conv2DTranspose: bias only (fp16 pieces: acc_scale and the bias carry the activation scale)
+template <bool F16>
+__device__ __forceinline__ void uc_activate4(f32x2 &v01, f32x2 &v23, const float4 &b, const f32x2 &inv2, float &amax)
+{
+    v01 = uc_biased<F16>(v01, inv2, f32x2{b.x, b.y});
+    v23 = uc_biased<F16>(v23, inv2, f32x2{b.z, b.w});
+    uc_clamp4<F16>(v01, v23, amax);
+}
+
+// eight adjacent channels -> one 16-byte word of pieces (uc_piece_word four times); the arguments keep the remainders when more pieces
+// follow.  (Eight references, not an array: handed an array, the compiler schedules the callers' conversions in another order.)
+template <bool F16>
+__device__ __forceinline__ uint4 uc_pack8(float &v0, float &v1, float &v2, float &v3, float &v4, float &v5, float &v6, float &v7, bool more)
+{
+    uint4 w;
+    w.x = uc_piece_word<F16>(v0, v1, more);
+    w.y = uc_piece_word<F16>(v2, v3, more);
+    w.z = uc_piece_word<F16>(v4, v5, more);
+    w.w = uc_piece_word<F16>(v6, v7, more);
+    return w;
+}
+
+// A wave's staging image in LDS: [32 pixels][128 channels] of one piece, padded rows (k_unet_conv's epilogue has the why).  The three
+// walks over it -- k_unet_conv's output rows and pooled map, k_unet_conv_first_mfma -- stay written out around uc_pack8: in a helper
+// that is handed the accumulators, by reference or by value, the same instructions come out in another order and register allocation.
+constexpr int EP_ROW = 272, EP_BYTES = 32 * EP_ROW;
+
+// softmax over the two classes of the network's head (pl.py:69): out[i0], out[i1] = the probabilities of logits z0, z1
+__device__ __forceinline__ void uc_softmax2(float z0, float z1, float *out, long i0, long i1)
+{
+    const float zm = z0 > z1 ? z0 : z1;
+    const float e0 = __expf(z0 - zm), e1 = __expf(z1 - zm);
+    const float es = e0 + e1;
+    out[i0] = e0 / es;
+    out[i1] = e1 / es;
 }
 
 // A counted wait on the vector-memory queue followed by the workgroup barrier.  The asynchronous global -> LDS copies of
@@ -558,14 +626,14 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
     // map goes out the same way first (max-then-split equals the pooled split map: the pieces are a monotone function of the value).
     // No barrier in front: every wave reads its last fragments and sees its last copies land BEFORE the final step's barrier, so a
     // wave that is past that barrier may overwrite the tile buffers.
-    constexpr int EP_ROW = 272, EP_BYTES = 32 * EP_ROW;
     static_assert(UC_THREADS / 64 * EP_BYTES <= (DA + 1) * A_BYTES + UC_NBBUF * B_BYTES, "the staging images fit the tile buffers");
     int pxl = lane & 31, hf = lane >> 5;
     asm volatile("" : "+v"(pxl), "+v"(hf));           // (opaque: nothing of the epilogue's addressing is hoisted into the main loop's registers)
     unsigned char *ep = smem + wave * EP_BYTES;
     if (p.raw_out) {
         // raw output: accumulator x acc_scale as float32 [outH][outW][cout] -- a partial sum for a later launch's seed.  A lane's
-        // sixteen adjacent channels of a block are 64 contiguous bytes: stored straight from the registers.
+        // sixteen adjacent channels of a block are 64 contiguous bytes: stored straight from the registers (the seed load's walk, the
+        // other way round; both stay written out: through a shared walker over `acc` the compiler allocates the kernel's registers differently).
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             const int y = ty0 + wave * 2 + m;
@@ -586,44 +654,25 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
         const float *scp = p.scale + nblk * UC_BN + 16 * hf, *shp = p.shift + nblk * UC_BN + 16 * hf;
         const f32x2 inv2 = {p.acc_scale, p.acc_scale};      // fp16 pieces: accumulator -> the layer's units (a power of two)
         float amax = 0.f;                                   // fp16 pieces: the lane's largest |value| in front of the clamp (uc_range_flag)
-        // accumulator + bias (fp16 pieces: accumulator x acc_scale + bias, one fused multiply-add -- the product is exact)
-        auto biased = [&](float a0, float a1, const f32x2 &b) -> f32x2 {
-            if constexpr (F16) return __builtin_elementwise_fma(f32x2{a0, a1}, inv2, b);
-            else return f32x2{a0, a1} + b;
-        };
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float4 b4 = *reinterpret_cast<const float4 *>(bip + n * 32 + q * 4);
-                const f32x2 b01 = {b4.x, b4.y}, b23 = {b4.z, b4.w};
+                const float4 b = *reinterpret_cast<const float4 *>(bip + n * 32 + q * 4);
                 if (p.scale) {
-                    const float4 s4 = *reinterpret_cast<const float4 *>(scp + n * 32 + q * 4), t4 = *reinterpret_cast<const float4 *>(shp + n * 32 + q * 4);
-                    const f32x2 s01 = {s4.x, s4.y}, s23 = {s4.z, s4.w}, t01 = {t4.x, t4.y}, t23 = {t4.z, t4.w};
+                    const float4 s = *reinterpret_cast<const float4 *>(scp + n * 32 + q * 4), t = *reinterpret_cast<const float4 *>(shp + n * 32 + q * 4);
 #pragma unroll
                     for (int m = 0; m < 2; ++m) {
-                        f32x2 v01 = biased(acc[m][n][q * 4 + 0], acc[m][n][q * 4 + 1], b01);
-                        f32x2 v23 = biased(acc[m][n][q * 4 + 2], acc[m][n][q * 4 + 3], b23);
-                        v01 = __builtin_elementwise_fma(f32x2{relu_bits(v01[0]), relu_bits(v01[1])}, s01, t01);
-                        v23 = __builtin_elementwise_fma(f32x2{relu_bits(v23[0]), relu_bits(v23[1])}, s23, t23);
-                        if constexpr (F16) {         // (stored values are scaled: s and t carry the activation scale)
-                            amax = uc_amax3(uc_amax3(amax, v01[0], v01[1]), v23[0], v23[1]);
-                            v01 = f32x2{uc_sat_f16(v01[0]), uc_sat_f16(v01[1])};
-                            v23 = f32x2{uc_sat_f16(v23[0]), uc_sat_f16(v23[1])};
-                        }
+                        f32x2 v01 = {acc[m][n][q * 4 + 0], acc[m][n][q * 4 + 1]}, v23 = {acc[m][n][q * 4 + 2], acc[m][n][q * 4 + 3]};
+                        uc_activate4<F16>(v01, v23, b, s, t, inv2, amax);
                         acc[m][n][q * 4 + 0] = v01[0]; acc[m][n][q * 4 + 1] = v01[1];
                         acc[m][n][q * 4 + 2] = v23[0]; acc[m][n][q * 4 + 3] = v23[1];
                     }
                 } else {
 #pragma unroll
                     for (int m = 0; m < 2; ++m) {
-                        f32x2 v01 = biased(acc[m][n][q * 4 + 0], acc[m][n][q * 4 + 1], b01);     // (fp16 pieces, bias only: acc_scale and the bias carry the activation scale)
-                        f32x2 v23 = biased(acc[m][n][q * 4 + 2], acc[m][n][q * 4 + 3], b23);
-                        if constexpr (F16) {
-                            amax = uc_amax3(uc_amax3(amax, v01[0], v01[1]), v23[0], v23[1]);
-                            v01 = f32x2{uc_sat_f16(v01[0]), uc_sat_f16(v01[1])};
-                            v23 = f32x2{uc_sat_f16(v23[0]), uc_sat_f16(v23[1])};
-                        }
+                        f32x2 v01 = {acc[m][n][q * 4 + 0], acc[m][n][q * 4 + 1]}, v23 = {acc[m][n][q * 4 + 2], acc[m][n][q * 4 + 3]};
+                        uc_activate4<F16>(v01, v23, b, inv2, amax);
                         acc[m][n][q * 4 + 0] = v01[0]; acc[m][n][q * 4 + 1] = v01[1];
                         acc[m][n][q * 4 + 2] = v23[0]; acc[m][n][q * 4 + 3] = v23[1];
                     }
@@ -658,6 +707,7 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
 #pragma unroll
             for (int c = 0; c < 2; ++c) z[m][c] += __shfl_xor(z[m][c], 32, 64);
         const float z0 = (hf ? z[1][0] : z[0][0]) + p.head_b[0], z1 = (hf ? z[1][1] : z[0][1]) + p.head_b[1];     // half-wave hf: tile row hf
+        // (uc_softmax2, written out: with the two indices computed in front of it, as the helper's arguments would be, the compiler schedules this block differently)
         const float zm = z0 > z1 ? z0 : z1;
         const float e0 = __expf(z0 - zm), e1 = __expf(z1 - zm);
         const float es = e0 + e1;
@@ -666,7 +716,6 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
         p.head_out[(long)p.H * p.W + o] = e1 / es;
         return;
     }
-    auto piece_word = [](float &a, float &b, bool more) -> unsigned { return uc_piece_word<F16>(a, b, more); };
     const int rd_row = lane >> 4, rd_col = (lane & 15) * 16;       // read-back: 16 lanes = one pixel's 256 bytes
     const long out_plane = (long)p.outH * p.outW * p.cout;
     if (p.pool_out) {
@@ -684,14 +733,9 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) {
 #pragma unroll
-            for (int n = 0; n < 4; ++n) {
-                uint4 w;
-                w.x = piece_word(q8[n][0], q8[n][1], pl + 1 < NPL);
-                w.y = piece_word(q8[n][2], q8[n][3], pl + 1 < NPL);
-                w.z = piece_word(q8[n][4], q8[n][5], pl + 1 < NPL);
-                w.w = piece_word(q8[n][6], q8[n][7], pl + 1 < NPL);
-                *reinterpret_cast<uint4 *>(ep + (pxl >> 1) * EP_ROW + (n * 32 + 16 * hf + (oddp ? 8 : 0)) * 2) = w;
-            }
+            for (int n = 0; n < 4; ++n)
+                *reinterpret_cast<uint4 *>(ep + (pxl >> 1) * EP_ROW + (n * 32 + 16 * hf + (oddp ? 8 : 0)) * 2) =
+                    uc_pack8<F16>(q8[n][0], q8[n][1], q8[n][2], q8[n][3], q8[n][4], q8[n][5], q8[n][6], q8[n][7], pl + 1 < NPL);
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
                 const int row = it * 4 + rd_row;
@@ -712,11 +756,7 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
                     float v[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[j] = acc[m][n][q * 8 + j];      // (vector elements do not bind to references)
-                    uint4 w;
-                    w.x = piece_word(v[0], v[1], pl + 1 < NPL);
-                    w.y = piece_word(v[2], v[3], pl + 1 < NPL);
-                    w.z = piece_word(v[4], v[5], pl + 1 < NPL);
-                    w.w = piece_word(v[6], v[7], pl + 1 < NPL);
+                    const uint4 w = uc_pack8<F16>(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], pl + 1 < NPL);
                     if (pl + 1 < NPL) {
 #pragma unroll
                         for (int j = 0; j < 8; ++j) acc[m][n][q * 8 + j] = v[j];
@@ -737,491 +777,6 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
     }
 #endif
 #endif
-}
-
-// ---- first layer: Conv2D(2 -> 128, 3x3) on the float32 (2, H, W) network input --------------------------------------------------
-// The vector kernel: the bf16 modes' first layer (two bf16 pieces of the input would be less accurate than these exact FMAs), and
-// mode f16x3's behind TIP_UNET_FIRST=valu; f16x3 runs k_unet_conv_first_mfma below by default.  K = 18 and float32 operands: nothing
-// for the matrix cores here -- the layer is its 2.1 GB of output.  Exact float32 FMAs; a thread owns 4 adjacent output
-// channels, keeps their 18 x 4 weights in registers and walks a run of FIRST_RUN consecutive pixels of one row with the 3 x 3 x 2
-// input window sliding through registers (six loads and no address arithmetic per pixel: with per-pixel tap addressing the kernel
-// was bound by its own index arithmetic, 210 vector instructions per pixel and thread, 0.8 ms against 0.45 ms for the stores
-// alone).  Thirty-two threads share a pixel, so the split of two adjacent channels is one v_cvt_pk_bf16_f32 (no lane exchange) and
-// a pixel's 256 bytes per piece leave in one piece.
-constexpr int FIRST_RUN = 32;       // consecutive pixels per 32-thread slot; a 256-thread block covers 8 runs = 256 pixels of a row
-constexpr int FIRST_PIX = 8 * FIRST_RUN;
-template <int NPL, bool F16 = false>
-__global__ void __launch_bounds__(256) k_unet_conv_first(const float *__restrict__ in, int H, int W, const float *__restrict__ wgt /* [9][2][128] */,
-                                                         const float *__restrict__ bias, const float *__restrict__ scale,
-                                                         const float *__restrict__ shift, uint16_t *__restrict__ out,
-                                                         unsigned *__restrict__ status /* fp16 pieces: the range word (uc_range_flag) */)
-{
-    const int cg = threadIdx.x & 31, slot = threadIdx.x >> 5;
-    float4 w4[18];
-#pragma unroll
-    for (int k = 0; k < 18; ++k) w4[k] = *reinterpret_cast<const float4 *>(wgt + k * 128 + cg * 4);
-    const float4 bb = *reinterpret_cast<const float4 *>(bias + cg * 4);
-    const float4 ss = *reinterpret_cast<const float4 *>(scale + cg * 4);
-    const float4 tt = *reinterpret_cast<const float4 *>(shift + cg * 4);
-    const long plane = (long)H * W * 128, chan = (long)H * W;
-    const long pix0 = (long)blockIdx.x * FIRST_PIX + slot * FIRST_RUN;        // (W % FIRST_RUN == 0: a run stays inside one row)
-    const int y = (int)(pix0 / W), x0 = (int)(pix0 - (long)y * W);
-    // the three input rows (clamped addresses, zero where the row lies outside the image: 'same' padding)
-    const float *rowp[3];
-    bool rowin[3];
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-        const int yy = y + dy - 1;
-        rowin[dy] = yy >= 0 && yy < H;
-        rowp[dy] = in + (long)min(max(yy, 0), H - 1) * W;
-    }
-    auto column = [&](int xx, float (&c)[3][2]) {          // input column xx of the window: [row][channel]
-        const bool xin = xx >= 0 && xx < W;
-        const int xc = min(max(xx, 0), W - 1);
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-            const float a = rowp[dy][xc], b = rowp[dy][chan + xc];
-            c[dy][0] = xin && rowin[dy] ? a : 0.f;
-            c[dy][1] = xin && rowin[dy] ? b : 0.f;
-        }
-    };
-    float win[3][3][2];          // [column slot][row][channel]; slot (it + k) % 3 holds column x - 1 + k
-    column(x0 - 1, win[0]);
-    column(x0, win[1]);
-    uint16_t *dst = out + pix0 * 128 + cg * 4;
-    float amax = 0.f;            // fp16 pieces: the thread's largest |value| in front of the clamp
-    for (int it0 = 0; it0 < FIRST_RUN; it0 += 3) {
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {        // (unrolled by the window's period: every slot index is a compile-time constant)
-            const int it = it0 + u;
-            if (it >= FIRST_RUN) break;
-            column(x0 + it + 1, win[(u + 2) % 3]);
-            f32x2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};       // packed FMAs: two channels per instruction
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const float v0 = win[(u + t % 3) % 3][t / 3][0], v1 = win[(u + t % 3) % 3][t / 3][1];
-                a01 = __builtin_elementwise_fma(f32x2{v0, v0}, f32x2{w4[2 * t].x, w4[2 * t].y}, a01);
-                a23 = __builtin_elementwise_fma(f32x2{v0, v0}, f32x2{w4[2 * t].z, w4[2 * t].w}, a23);
-                a01 = __builtin_elementwise_fma(f32x2{v1, v1}, f32x2{w4[2 * t + 1].x, w4[2 * t + 1].y}, a01);
-                a23 = __builtin_elementwise_fma(f32x2{v1, v1}, f32x2{w4[2 * t + 1].z, w4[2 * t + 1].w}, a23);
-            }
-            float a[4] = {a01[0] + bb.x, a01[1] + bb.y, a23[0] + bb.z, a23[1] + bb.w};
-            const float sv[4] = {ss.x, ss.y, ss.z, ss.w}, tv[4] = {tt.x, tt.y, tt.z, tt.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float r = a[j] > 0.f ? a[j] : 0.f;
-                a[j] = r * sv[j] + tv[j];
-            }
-            if constexpr (F16) {      // (s and t carry the activation scale)
-                amax = uc_amax3(uc_amax3(amax, a[0], a[1]), a[2], a[3]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) a[j] = uc_sat_f16(a[j]);
-            }
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) {
-                unsigned wd[2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) wd[q] = uc_piece_word<F16>(a[2 * q], a[2 * q + 1], pl + 1 < NPL);
-                *reinterpret_cast<uint2 *>(dst + (long)it * 128 + pl * plane) = make_uint2(wd[0], wd[1]);
-            }
-        }
-    }
-    if constexpr (F16) uc_range_flag(amax, status, threadIdx.x & 63);
-}
-
-// ---- the same layer on the matrix cores, fp16 pieces only (mode f16x3) ------------------------------------------------------------
-// With a value held as two fp16 pieces the layer is "just another layer": an implicit im2col with K = 18 padded to 32 -- index
-// k = 2 tap + channel (tap = 3 ky + kx, the order of the vector kernel's [9][2][128] weights), k = 18 .. 31 zero -- is two K steps of
-// v_mfma_f32_32x32x16_f16, three products per term as in k_unet_conv: 24 MFMAs per 32 pixels x 128 channels, ~0.05 ms of the
-// chip for 2048^2.  What is left is the epilogue k_unet_conv runs on the same bytes: about 13 wave instructions per pixel where the
-// vector kernel above issues 60, so the layer is its 2.1 GB of stores.
-//   * Weights (A operand) arrive packed like every layer's (host: _split_pack, one tap x 32 input channels, their own power-of-two
-//     scale); a wave keeps its sixteen 16-byte fragments (4 blocks x 2 steps x 2 planes) in registers for its whole life.
-//   * Pixels are the B operand: lane (pixel = lane & 31, g = lane >> 5) supplies k = 8 g .. 8 g + 7 of each step, i.e. taps
-//     4 g .. 4 g + 3 in step 0 and (g = 0 only) tap 8 in step 1: at most ten float32 loads per lane and segment, clamped addresses and
-//     a select to zero outside the image.  The values are scaled by the activation scale and split here; they pass through the
-//     range check's running maximum in front of the clamp, so an input beyond the range raises the flag.
-//   * A wave walks 32-pixel segments of a row (W % 32 == 0), segment s of wave g: g + s x (waves of the launch) -- neighbouring
-//     waves store neighbouring 8 KB.  The next segment's input is loaded in front of the current one's epilogue.
-//   * Epilogue: the math and the order of k_unet_conv's fp16 branch, one segment (its m = 0) at a time, through the wave's own
-//     8.5 KB LDS image.
-// UC_FIRST_STORES_ONLY (timing builds only, never the product): no input loads, no MFMAs -- the epilogue and the stores on their own.
-constexpr int FM_ROW = 272, FM_BYTES = 32 * FM_ROW;       // a wave's LDS image: 32 pixels x 128 channels of one piece, padded rows
-constexpr int FIRST_MFMA_WGS_PER_CU = 2;                  // workgroups per CU a launch is cut to: as many as are resident (two waves per SIMD: 64 weight + 64 accumulator registers)
-static __global__ void __launch_bounds__(256) k_unet_conv_first_mfma(const float *__restrict__ in, int H, int W,
-                                                              const uint16_t *__restrict__ wgt /* packed [2 steps][1][2 planes][128][16] */,
-                                                              float acc_scale, const float *__restrict__ bias, const float *__restrict__ scale,
-                                                              const float *__restrict__ shift, uint16_t *__restrict__ out,
-                                                              unsigned *__restrict__ status /* the range word (uc_range_flag) */)
-{
-#if defined(__HIP_DEVICE_COMPILE__)       // (the matrix-core builtins exist in the device pass only)
-    __shared__ __attribute__((aligned(16))) unsigned char smem[4 * FM_BYTES];
-    // The per-channel constants live in LDS: read from memory inside the loop, they would sit BEHIND the previous segment's stores in
-    // the wave's vector-memory queue (one counter for loads and stores), and every segment would wait for its predecessor's 16 KB to
-    // be acknowledged.  The only loads left in the loop are the next segment's input, issued in front of the stores.
-    __shared__ __attribute__((aligned(16))) float cst[3][UC_BN];
-    if (threadIdx.x < UC_BN) {
-        cst[0][threadIdx.x] = bias[threadIdx.x];
-        cst[1][threadIdx.x] = scale[threadIdx.x];
-        cst[2][threadIdx.x] = shift[threadIdx.x];
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // (scalar: so are the segment, its row and the store's base)
-    const int pxl = lane & 31, hf = lane >> 5;
-    unsigned char *ep = smem + wave * FM_BYTES;
-    const long chan = (long)H * W, plane = chan * 128;
-    const int segs_row = W / 32;
-    const long nseg = chan / 32, seg_step = (long)gridDim.x * 4;
-
-    uint4 wf[2][2][4];          // weight fragments [step][plane][block of 32 channels]: row (block, lane & 31), k = 8 hf .. 8 hf + 7
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-                wf[s][pl][n] = *reinterpret_cast<const uint4 *>(wgt + ((s * 2 + pl) * UC_BN + n * 32 + pxl) * UC_KC + hf * 8);
-
-    // the lane's five taps: 4 hf + j (j < 4) and tap 8, which only half-wave 0 supplies (k = 16, 17 of step 1)
-    int tdy[5], tdx[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const int tap = j < 4 ? 4 * hf + j : 8;
-        tdy[j] = tap / 3 - 1;
-        tdx[j] = tap % 3 - 1;
-    }
-    const float *in1 = in + chan;
-    // (raw values and a mask of the taps inside the image: the select is applied where the values are used, so nothing waits for a load at its issue)
-    auto load_segment = [&](long seg, float (&v)[5][2], unsigned &inmask) {
-#ifndef UC_FIRST_STORES_ONLY
-        const int y = (int)(seg / segs_row), x = (int)(seg - (long)y * segs_row) * 32 + pxl;
-        unsigned m = 0u;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const int yy = y + tdy[j], xx = x + tdx[j];
-            const bool inside = yy >= 0 && yy < H && xx >= 0 && xx < W && (j < 4 || hf == 0);
-            const unsigned o = (unsigned)(min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1));     // (H W < 2^30: the output is 512 bytes per pixel)
-            v[j][0] = in[o];
-            v[j][1] = in1[o];
-            m |= inside ? 1u << j : 0u;
-        }
-        inmask = m;
-#else
-#pragma unroll
-        for (int j = 0; j < 5; ++j) v[j][0] = v[j][1] = 0.f;
-        inmask = 0u;
-#endif
-    };
-
-    const f32x2 inv2 = {acc_scale, acc_scale};
-    const unsigned coff = 16 * hf;                                 // the lane's sixteen channels of a 32-channel block
-    const int rd_row = lane >> 4, rd_col = (lane & 15) * 16;       // read-back: 16 lanes = one pixel's 256 bytes
-    float amax = 0.f;           // the lane's largest |value| in front of a clamp, inputs and outputs alike
-    long seg = (long)blockIdx.x * 4 + wave;
-    float cur[5][2];
-    unsigned curmask = 0u;
-    if (seg < nseg) {
-        load_segment(seg, cur, curmask);
-#pragma unroll
-        for (int j = 0; j < 5; ++j) asm volatile("" : "+v"(cur[j][0]), "+v"(cur[j][1]));     // (landed in front of the loop: inside it the wait counts only the stores behind the loads)
-    }
-    for (; seg < nseg; seg += seg_step) {
-        // B fragments: the ten values times the activation scale, split into fp16 pieces (words j: taps of step 0; word 4: tap 8)
-        unsigned bhi[5], blo[5];
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            asm volatile("" : "+v"(cur[j][0]), "+v"(cur[j][1]));      // (waited for HERE, behind the previous segment's stores, not where they were issued)
-            const bool inside = (curmask >> j) & 1u;
-            float a = inside ? cur[j][0] * 16.f : 0.f, b = inside ? cur[j][1] * 16.f : 0.f;      // (16: the activation scale of the fp16 pieces, _F16_ACT_SCALE)
-            amax = uc_amax3(amax, a, b);
-            a = uc_sat_f16(a);
-            b = uc_sat_f16(b);
-            bhi[j] = uc_piece_word<true>(a, b, true);
-            blo[j] = uc_piece_word<true>(a, b, false);
-        }
-        if (seg + seg_step < nseg) load_segment(seg + seg_step, cur, curmask);     // (in flight behind the products and the epilogue)
-        asm volatile("" ::: "memory");       // (the loads stay here, in front of this segment's stores: see cst)
-        const uint4 xh[2] = {make_uint4(bhi[0], bhi[1], bhi[2], bhi[3]), make_uint4(bhi[4], 0u, 0u, 0u)};
-        const uint4 xl[2] = {make_uint4(blo[0], blo[1], blo[2], blo[3]), make_uint4(blo[4], 0u, 0u, 0u)};
-        f32x16 acc[4];
-#ifndef UC_FIRST_STORES_ONLY
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[n][i] = 0.f;
-        // products from the smallest magnitude class to the largest: lo x hi, hi x lo, hi x hi (weights = the A operand)
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[n] = uc_mfma<true>(wf[s][0][n], xl[s], acc[n]);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[n] = uc_mfma<true>(wf[s][1][n], xh[s], acc[n]);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[n] = uc_mfma<true>(wf[s][0][n], xh[s], acc[n]);
-#else
-        {
-            float z = __uint_as_float(xh[0].x | xl[1].x);      // (zero, but not to the compiler: the epilogue stays inside the loop)
-            asm volatile("" : "+v"(z));
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[n][i] = z;
-        }
-#endif
-        // epilogue: accumulator x acc_scale + bias -> ReLU -> BatchNorm scale / shift (both carry the activation scale) -> range
-        // check -> clamp, as in k_unet_conv; a lane holds channels n * 32 + 16 hf + i of its pixel
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 b4 = *reinterpret_cast<const float4 *>(&cst[0][coff + n * 32 + q * 4]);
-                const float4 s4 = *reinterpret_cast<const float4 *>(&cst[1][coff + n * 32 + q * 4]), t4 = *reinterpret_cast<const float4 *>(&cst[2][coff + n * 32 + q * 4]);
-                const f32x2 b01 = {b4.x, b4.y}, b23 = {b4.z, b4.w};
-                const f32x2 s01 = {s4.x, s4.y}, s23 = {s4.z, s4.w}, t01 = {t4.x, t4.y}, t23 = {t4.z, t4.w};
-                f32x2 v01 = __builtin_elementwise_fma(f32x2{acc[n][q * 4 + 0], acc[n][q * 4 + 1]}, inv2, b01);
-                f32x2 v23 = __builtin_elementwise_fma(f32x2{acc[n][q * 4 + 2], acc[n][q * 4 + 3]}, inv2, b23);
-                v01 = __builtin_elementwise_fma(f32x2{relu_bits(v01[0]), relu_bits(v01[1])}, s01, t01);
-                v23 = __builtin_elementwise_fma(f32x2{relu_bits(v23[0]), relu_bits(v23[1])}, s23, t23);
-                amax = uc_amax3(uc_amax3(amax, v01[0], v01[1]), v23[0], v23[1]);
-                acc[n][q * 4 + 0] = uc_sat_f16(v01[0]); acc[n][q * 4 + 1] = uc_sat_f16(v01[1]);
-                acc[n][q * 4 + 2] = uc_sat_f16(v23[0]); acc[n][q * 4 + 3] = uc_sat_f16(v23[1]);
-            }
-        }
-        // split and store: one piece at a time through the wave's LDS image, read back four whole pixels per store instruction
-        uint16_t *orow = out + seg * 32 * 128;
-        const unsigned ooff = (unsigned)((lane & 15) * 8 + rd_row * 128);
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    float v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = acc[n][q * 8 + j];
-                    uint4 w;
-                    w.x = uc_piece_word<true>(v[0], v[1], pl == 0);
-                    w.y = uc_piece_word<true>(v[2], v[3], pl == 0);
-                    w.z = uc_piece_word<true>(v[4], v[5], pl == 0);
-                    w.w = uc_piece_word<true>(v[6], v[7], pl == 0);
-                    if (pl == 0) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) acc[n][q * 8 + j] = v[j];
-                    }
-                    *reinterpret_cast<uint4 *>(ep + pxl * FM_ROW + (n * 32 + 16 * hf + 8 * q) * 2) = w;
-                }
-#pragma unroll
-            for (int it = 0; it < 8; ++it) {
-                const int row = it * 4 + rd_row;
-                *reinterpret_cast<uint4 *>(orow + pl * plane + it * 4 * 128 + ooff) = *reinterpret_cast<const uint4 *>(ep + row * FM_ROW + rd_col);
-            }
-        }
-    }
-    uc_range_flag(amax, status, lane);
-#endif
-}
-
-// value of split element e (0..7) of the 16-byte pieces pc[0..NPL)
-template <int NPL, bool F16 = false>
-__device__ __forceinline__ float split_value(const uint4 *pc, int e)
-{
-    float v = 0.f;
-#pragma unroll
-    for (int pl = NPL - 1; pl >= 0; --pl) {     // smallest piece first: the sum is exact either way (<= 24 significant bits)
-        const unsigned w = e < 2 ? pc[pl].x : (e < 4 ? pc[pl].y : (e < 6 ? pc[pl].z : pc[pl].w));
-        v += uc_piece_value<F16>((e & 1) ? (w >> 16) : (w & 0xffffu));
-    }
-    return v;
-}
-
-// ---- MaxPool2D(2) on split planes: the winner's pieces are copied (the pieces of a value are a function of the value) ---------
-template <int NPL, bool F16 = false>
-__global__ void __launch_bounds__(256) k_unet_pool2(const uint16_t *__restrict__ in, int H, int W, int C, uint16_t *__restrict__ out)
-{
-    const int Ho = H / 2, Wo = W / 2, C8 = C / 8;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)Ho * Wo * C8) return;
-    const int c8 = (int)(i % C8);
-    const long op = i / C8;
-    const int xo = (int)(op % Wo), yo = (int)(op / Wo);
-    const long in_plane = (long)H * W * C, out_plane = (long)Ho * Wo * C;
-    uint4 pc[4][NPL];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int pl = 0; pl < NPL; ++pl)
-            pc[k][pl] = *reinterpret_cast<const uint4 *>(in + pl * in_plane + ((long)(2 * yo + (k >> 1)) * W + 2 * xo + (k & 1)) * C + c8 * 8);
-    unsigned res[NPL][4];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        int best = 0;
-        float bv = split_value<NPL, F16>(pc[0], e);
-#pragma unroll
-        for (int k = 1; k < 4; ++k) {
-            const float v = split_value<NPL, F16>(pc[k], e);
-            if (v > bv) { bv = v; best = k; }
-        }
-#pragma unroll
-        for (int pl = 0; pl < NPL; ++pl) {
-            const uint4 q = best == 0 ? pc[0][pl] : (best == 1 ? pc[1][pl] : (best == 2 ? pc[2][pl] : pc[3][pl]));
-            const unsigned w = e < 2 ? q.x : (e < 4 ? q.y : (e < 6 ? q.z : q.w));
-            const unsigned hb = (e & 1) ? (w >> 16) : (w & 0xffffu);
-            if (e & 1) res[pl][e >> 1] |= hb << 16; else res[pl][e >> 1] = hb;
-        }
-    }
-#pragma unroll
-    for (int pl = 0; pl < NPL; ++pl)
-        *reinterpret_cast<uint4 *>(out + pl * out_plane + op * C + c8 * 8) = make_uint4(res[pl][0], res[pl][1], res[pl][2], res[pl][3]);
-}
-
-// ---- head: Conv2D(128 -> 2, 1x1) + softmax over the two classes (pl.py:69), float32 out (2, H, W) -------------------------------
-// eight lanes per pixel, 16 channels each; logits != 0: the pre-softmax values (the bench's head calibration)
-template <int NPL, bool F16 = false>
-__global__ void __launch_bounds__(256) k_unet_head(const uint16_t *__restrict__ in, long npix, const float *__restrict__ wgt /* [2][128] */,
-                                                   const float *__restrict__ bias, float *__restrict__ out, int logits)
-{
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long pix = t >> 3;
-    const int part = (int)(t & 7);
-    const long plane = npix * 128;
-    float z0 = 0.f, z1 = 0.f;
-    if (pix < npix) {
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            uint4 pc[NPL];
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) pc[pl] = *reinterpret_cast<const uint4 *>(in + pl * plane + pix * 128 + part * 16 + g * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float v = split_value<NPL, F16>(pc, e);
-                const int c = part * 16 + g * 8 + e;
-                z0 = __builtin_fmaf(v, wgt[c], z0);
-                z1 = __builtin_fmaf(v, wgt[128 + c], z1);
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) { z0 += __shfl_xor(z0, d, 64); z1 += __shfl_xor(z1, d, 64); }
-    if (pix < npix && part == 0) {
-        z0 += bias[0]; z1 += bias[1];
-        if (logits) { out[pix] = z0; out[npix + pix] = z1; return; }
-        const float m = z0 > z1 ? z0 : z1;
-        const float e0 = __expf(z0 - m), e1 = __expf(z1 - m);
-        const float s = e0 + e1;
-        out[pix] = e0 / s;
-        out[npix + pix] = e1 / s;
-    }
-}
-
-// ---- border pass of a composed decoder level (Conv2DTranspose folded into the next Conv2D) -----------------------------
-// The composed launches compute the convolution of the UNCROPPED transposed convolution; the real network crops it to 2N rows and
-// columns, so on the last output row / column the term through the virtual row up[2N] = x[N-1] T2 has to go (and comes back once
-// at the corner), and the transposed convolution's bias reaches an edge pixel through fewer taps than an interior one.
-// k_unet_compose_edge walks ONE edge line of the float32 partial: low-resolution position j of the line owns the output pixels
-// 2j (parity 0: taps at j - 1, j) and 2j + 1 (parity 1: taps at j - 1, j, j + 1); part += sum over taps and input channels of
-// x[j + d] * wgt[tap] in plain float32 FMAs on the rejoined pieces of x.  A block: EB_J positions x EB_CO output channels, the input
-// channels dealt in sixteens to EB_G groups of threads whose sums are added in a fixed order (deterministic).
-constexpr int EB_J = 8, EB_CO = 64, EB_G = 8, EB_CH = 16 * EB_G;
-struct EdgeParams {
-    const uint16_t *x;             // split activations of the low-resolution grid
-    long xplane;                   // elements per plane
-    int planes, f16;
-    float xscale;                  // 1 / activation scale (fp16 pieces)
-    int cin, cout, L;              // line length in low-resolution positions
-    long x0, xstep;                // element offset of position 0 / from one position to the next
-    const float *wgt[5];           // [cin][cout] each: taps (parity, offset) = (0, -1) (0, 0) (1, -1) (1, 0) (1, +1), signs included
-    int tapmask;                   // taps that exist (the corner: tap 3 alone)
-    float *part;
-    long o0, ostep;                // element offset of the line's output pixel 0 / from one output pixel to the next
-};
-static __global__ void __launch_bounds__(EB_CO * EB_G) k_unet_compose_edge(const EdgeParams p)
-{
-    __shared__ float xs[EB_J + 2][EB_CH];
-    __shared__ float red[EB_G - 1][2 * EB_J][EB_CO];
-    const int tid = threadIdx.x, col = tid % EB_CO, g = tid / EB_CO;
-    const int j0 = blockIdx.x * EB_J, co = blockIdx.y * EB_CO + col;
-    float a[2][EB_J];
-#pragma unroll
-    for (int jj = 0; jj < EB_J; ++jj) a[0][jj] = a[1][jj] = 0.f;
-    for (int c0 = 0; c0 < p.cin; c0 += EB_CH) {
-        const int nch = min(EB_CH, p.cin - c0);          // (a multiple of 16: group g's sixteen channels exist or do not)
-        __syncthreads();
-        for (int i = tid; i < (EB_J + 2) * EB_CH; i += EB_CO * EB_G) {
-            const int jj = i / EB_CH, c = i - jj * EB_CH, j = j0 + jj - 1;
-            float v = 0.f;
-            if (c < nch && j >= 0 && j < p.L) {
-                const uint16_t *src = p.x + p.x0 + (long)j * p.xstep + c0 + c;
-                for (int pl = p.planes - 1; pl >= 0; --pl)       // smallest piece first; the sum is exact (<= 24 significant bits)
-                    v += p.f16 ? uc_piece_value<true>(src[pl * p.xplane]) : uc_piece_value<false>(src[pl * p.xplane]);
-                v *= p.xscale;
-            }
-            xs[jj][c] = v;
-        }
-        __syncthreads();
-        if (g * 16 < nch) {
-#pragma unroll
-            for (int k8 = 0; k8 < 16; k8 += 8) {
-                float w[8][5];          // eight channels' weights on their way before the first is used (the loop is latency-bound otherwise)
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-#pragma unroll
-                    for (int t = 0; t < 5; ++t)
-                        w[u][t] = ((p.tapmask >> t) & 1) ? p.wgt[t][(long)(c0 + g * 16 + k8 + u) * p.cout + co] : 0.f;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int k = g * 16 + k8 + u;
-#pragma unroll
-                    for (int jj = 0; jj < EB_J; ++jj) {
-                        const float xm = xs[jj][k], xc = xs[jj + 1][k], xp = xs[jj + 2][k];
-                        a[0][jj] = __builtin_fmaf(xc, w[u][1], __builtin_fmaf(xm, w[u][0], a[0][jj]));
-                        a[1][jj] = __builtin_fmaf(xp, w[u][4], __builtin_fmaf(xc, w[u][3], __builtin_fmaf(xm, w[u][2], a[1][jj])));
-                    }
-                }
-            }
-        }
-    }
-    if (g > 0) {
-#pragma unroll
-        for (int jj = 0; jj < EB_J; ++jj) { red[g - 1][2 * jj][col] = a[0][jj]; red[g - 1][2 * jj + 1][col] = a[1][jj]; }
-    }
-    __syncthreads();
-    if (g > 0) return;
-#pragma unroll
-    for (int jj = 0; jj < EB_J; ++jj)
-#pragma unroll
-        for (int par = 0; par < 2; ++par) {
-            if (j0 + jj >= p.L || !(p.tapmask & (par ? 0x1c : 0x3))) continue;
-            float v = a[par][jj];
-#pragma unroll
-            for (int q = 0; q < EB_G - 1; ++q) v += red[q][2 * jj + par][col];
-            p.part[p.o0 + (long)(2 * (j0 + jj) + par) * p.ostep + co] += v;
-        }
-}
-
-// the transposed convolution's bias through the next convolution's taps: the interior sum sits in that layer's bias vector, an edge
-// pixel gets (its own sum - the interior's) from a table [3 rows: top, inside, bottom][3 columns: left, inside, right][cout]
-static __global__ void __launch_bounds__(256) k_unet_compose_edge_bias(float *__restrict__ part, int H2, int W2, int cout, const float *__restrict__ tab)
-{
-    const int c4 = cout / 4;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long npix = 2L * W2 + 2L * (H2 - 2);
-    if (i >= npix * c4) return;
-    const long e = i / c4;
-    const int c = (int)(i - e * c4) * 4;
-    int y, x;
-    if (e < W2) { y = 0; x = (int)e; }
-    else if (e < 2L * W2) { y = H2 - 1; x = (int)(e - W2); }
-    else { const long k = e - 2L * W2; y = 1 + (int)(k >> 1); x = (k & 1) ? W2 - 1 : 0; }
-    const int type = (y == 0 ? 0 : (y == H2 - 1 ? 2 : 1)) * 3 + (x == 0 ? 0 : (x == W2 - 1 ? 2 : 1));
-    float4 *dst = reinterpret_cast<float4 *>(part + ((long)y * W2 + x) * cout + c);
-    const float4 t = *reinterpret_cast<const float4 *>(tab + (long)type * cout + c);
-    float4 v = *dst;
-    v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
-    *dst = v;
 }
 
 }  // namespace tip

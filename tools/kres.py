@@ -1,4 +1,4 @@
-"""Kernel resource table of one csrc/*.hip (registers, spills, occupancy): python3 tools/kres.py tip_unet.hip [filter]"""
+"""Kernel resource table of one csrc/*.hip (registers, spills, occupancy): python3 tools/kres.py tip_unet.hip [filter] (the U-Net's other kernels: tip_unet_prepare.hip, tip_unet_tail.hip)"""
 import os
 import re
 import subprocess
