@@ -200,10 +200,10 @@ TIP_API int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream);
 /*   code   <pieces, tile rows, weight steps ahead D, activation chunks ahead DA, steps per barrier SPB>   chosen for               */
 /*    0     <2,  8, 2, 1, 1>   two pieces; h % 16 != 0, TIP_UNET_TILE8=1, or (default) nine taps with c0 + c1 <= 128                */
 /*    1     <2, 16, 2, 1, 1>   two pieces, 16-row tiles, three taps                                                                 */
-/*    2     <2, 16, 4, 1, 1>   two pieces, 16-row tiles, four to eight taps (nine with TIP_UNET_SPB=1)                              */
+/*    2     <2, 16, 4, 1, 1>   two pieces, 16-row tiles, four to eight taps (nine with TIP_UNET_SPB=1) except flavour 6's six taps     */
 /*    3     <3,  8, 2, 1, 1>   three pieces (bf16 only), always 8-row tiles                                                         */
 /*    4     <2, 16, 2, 2, 1>   two pieces, 16-row tiles, one or two taps                                                            */
-/*    6     <2, 16, 4, 1, 3>   two pieces, 16-row tiles, nine taps                                                                  */
+/*    6     <2, 16, 4, 1, 3>   two pieces, 16-row tiles, nine taps, and six taps with c0 + c1 >= 256                               */
 /* Every two-piece flavour exists with bf16 (format 0) and with fp16 pieces (format 1): the code does not depend on the format.   */
 TIP_API int tip_unet_conv_flavour(const tip_unet_conv_desc *d);
 /* Conv2DTranspose folded into the next Conv2D: border pass on the float32 partial `part` (2h x 2w x cout) that four  */

@@ -51,6 +51,7 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));     // a 16-byte fragment as the inline assembly's operand
 constexpr float UC_F16_MAX = 65504.f;          // largest finite fp16: scaled activations saturate there (see "piece formats")
 
 constexpr int UC_TW = 32;                     // pixel tile: TH rows (8 or 16: template parameter) x 32 columns
@@ -115,9 +116,11 @@ typedef __attribute__((address_space(3))) unsigned char lds_byte;
 // stored with s = 2^4 (they saturate beyond |v| = 4094; the absolute floor is 2^-29), every layer's weights with their own power of
 // two that puts the largest one in [2^14, 2^15); the accumulator is multiplied by acc_scale = 1 / (both) -- all powers of two, so
 // the scaling itself is exact.
-template <bool F16>
-__device__ __forceinline__ f32x16 uc_mfma(const uint4 &a, const uint4 &b, const f32x16 &c)
+// (V: a 16-byte fragment, uint4 in the first-layer kernel, u32x4 where inline assembly fills it)
+template <bool F16, typename V>
+__device__ __forceinline__ f32x16 uc_mfma(const V &a, const V &b, const f32x16 &c)
 {
+    static_assert(sizeof(V) == 16, "eight 16-bit pieces");
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
@@ -261,6 +264,37 @@ __device__ __forceinline__ void uc_wait_barrier()
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
+// The main loop's fragment reads as instructions.  Written as C++ loads, every LDS read that follows an asynchronous global -> LDS
+// copy gets an s_waitcnt vmcnt(0) from the compiler in front of it (it cannot tell which LDS bytes a pending copy writes, so it
+// waits for all of them): each step then opened by draining the copies issued for LATER steps, and the prefetch distance bought
+// nothing.  Which copies a step's reads need is what the counted wait in front of the barrier establishes; the reads themselves
+// carry no wait.  The compiler does not know these loads either, so the LDS counter is counted by hand: uc_lds_wait<N> waits until
+// at most N of the wave's LDS reads are outstanding (they return in order) and ties the fragments it names to the wait, so that no
+// product that uses them is scheduled in front of it.  (Scalar memory loads share the counter: one issued between a read and its wait
+// only makes the wait stricter; the per-step loads of p.dy / p.dx are waited for in front of the reads.)  The three-piece path
+// (NPL = 3) keeps its C++ reads and with them the compiler's wait.
+__device__ __forceinline__ unsigned uc_lds_addr(const unsigned char *q) { return (unsigned)(unsigned long long)(const lds_byte *)q; }
+template <int OFF>
+__device__ __forceinline__ void uc_lds_read(u32x4 &v, unsigned addr)
+{
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+}
+template <int N>
+__device__ __forceinline__ void uc_lds_wait(u32x4 &a)
+{
+    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N));
+}
+template <int N>
+__device__ __forceinline__ void uc_lds_wait(u32x4 &a, u32x4 &b)
+{
+    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
+}
+template <int N>
+__device__ __forceinline__ void uc_lds_wait(u32x4 &a, u32x4 &b, u32x4 &c)
+{
+    asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(N));
+}
+
 // NPL = bf16 pieces per value (2 or 3).
 //
 // LDS image (one dynamic array; 16-byte slots):  two activation buffers of A_SLOTS slots -- slot (plane * 340 + pixel) * 2 + sh --
@@ -290,7 +324,9 @@ __device__ __forceinline__ void uc_wait_barrier()
 // the earlier steps' MFMAs and that price is paid once per SPB x 24 MFMAs of a wave.  3 SPB weight buffers: the steps of this
 // iteration are read, those of the next must have landed by its end, those of the one after are issued at its start.  The next
 // chunk's activations are issued in the first iteration that BEGINS inside the current chunk: every read of the previous chunk --
-// whose buffer they overwrite -- lies behind a barrier by then, and at least six steps of flight remain.
+// whose buffer they overwrite -- lies behind a barrier by then, and at least six steps of flight remain.  The schedule needs a
+// step count that is a multiple of three and no more: the six-tap classes of a composed decoder level run it in two iterations per
+// chunk (five steps of flight for the activations), and gain more from it than the 3x3 stencils.
 template <int NPL, int TH, int D, int DA = 1, int SPB = 1, bool F16 = false>
 __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const ConvParams p)
 {
@@ -446,7 +482,7 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
     int step = 0;
     int nc = D / p.ntaps, nt = D % p.ntaps;                  // (chunk, tap) of step + D
     int buf0 = 0, buf2 = D;                                  // weight buffers of steps s and s + D (no division in the loop)
-    uint4 fa[2][NPL], fb[4][NPL];       // 16-byte fragments (eight pieces of either format)
+    u32x4 fa[2][NPL], fb[4][NPL];       // 16-byte fragments (eight pieces of either format)
 #ifdef UC_TRACE
     // clock sums over the main loop for ONE wave (block 0, wave 0): [0] copies issued, [1] fragment reads issued .. first operands
     // there (inside step_products), [2] products issued, [3] wait + barrier, [4] steps, [5] loop total
@@ -478,27 +514,48 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
             const int px = (wave * 2 + m + 1 + dy) * UC_HW + (r + 1 + dx);
             aslot[m] = px * 2 + (h ^ ((px >> 3) & 1));
         }
-        auto read_a = [&](int m, int pl) { fa[m][pl] = *reinterpret_cast<const uint4 *>(abuf + (pl * A_PLANE + aslot[m]) * 16); };
-        auto read_b = [&](int n, int pl) { fb[n][pl] = *reinterpret_cast<const uint4 *>(bbuf + (pl * 256 + n * 64 + b_row) * 16); };
+        auto read_a = [&](int m, int pl) { fa[m][pl] = *reinterpret_cast<const u32x4 *>(abuf + (pl * A_PLANE + aslot[m]) * 16); };
+        auto read_b = [&](int n, int pl) { fb[n][pl] = *reinterpret_cast<const u32x4 *>(bbuf + (pl * 256 + n * 64 + b_row) * 16); };
         if constexpr (NPL == 2) {
-            read_a(0, 1); read_a(1, 1);
-#pragma unroll
-            for (int n = 0; n < 4; ++n) read_b(n, 0);
+            // (uc_lds_read: no compiler-made wait for the copies in flight; the twelve reads return in issue order, and every
+            // uc_lds_wait<N> below names how many of them may still be out when the fragments it ties are used)
+            const unsigned ra0 = uc_lds_addr(abuf) + aslot[0] * 16, ra1 = uc_lds_addr(abuf) + aslot[1] * 16, rb = uc_lds_addr(bbuf) + b_row * 16;
+            constexpr int AP = A_PLANE * 16, BP = 256 * 16, BN = 64 * 16;
+            uc_lds_read<AP>(fa[0][1], ra0); uc_lds_read<AP>(fa[1][1], ra1);
+            uc_lds_read<0>(fb[0][0], rb); uc_lds_read<BN>(fb[1][0], rb); uc_lds_read<2 * BN>(fb[2][0], rb); uc_lds_read<3 * BN>(fb[3][0], rb);
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_setprio(1);      // the wave whose operands are in registers goes first on the shared matrix pipe
+            uc_lds_wait<3>(fa[0][1], fb[0][0]);
             acc[0][0] = uc_mfma<F16>(fb[0][0], fa[0][1], acc[0][0]);
             __builtin_amdgcn_sched_barrier(0);
-            read_a(0, 0); read_a(1, 0);
-#pragma unroll
-            for (int n = 0; n < 4; ++n) read_b(n, 1);
+            uc_lds_read<0>(fa[0][0], ra0); uc_lds_read<0>(fa[1][0], ra1);
+            uc_lds_read<BP>(fb[0][1], rb); uc_lds_read<BP + BN>(fb[1][1], rb); uc_lds_read<BP + 2 * BN>(fb[2][1], rb); uc_lds_read<BP + 3 * BN>(fb[3][1], rb);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int n = 1; n < 4; ++n) acc[0][n] = uc_mfma<F16>(fb[n][0], fa[0][1], acc[0][n]);
+            uc_lds_wait<8>(fb[1][0]);
+            acc[0][1] = uc_mfma<F16>(fb[1][0], fa[0][1], acc[0][1]);
+            uc_lds_wait<7>(fb[2][0]);
+            acc[0][2] = uc_mfma<F16>(fb[2][0], fa[0][1], acc[0][2]);
+            uc_lds_wait<6>(fb[3][0], fa[1][1]);
+            acc[0][3] = uc_mfma<F16>(fb[3][0], fa[0][1], acc[0][3]);
 #pragma unroll
             for (int n = 0; n < 4; ++n) acc[1][n] = uc_mfma<F16>(fb[n][0], fa[1][1], acc[1][n]);
             __builtin_amdgcn_sched_barrier(0);
 #ifndef UC_TWO_PRODUCTS        // (timing experiment of DESIGN 8: how the kernel's time follows the MFMA count; never part of the product)
-            UC_PRODUCT(0, 1)
+            uc_lds_wait<3>(fa[0][0], fa[1][0], fb[0][1]);
+            acc[0][0] = uc_mfma<F16>(fb[0][1], fa[0][0], acc[0][0]);
+            __builtin_amdgcn_sched_barrier(0);
+            uc_lds_wait<2>(fb[1][1]);
+            acc[0][1] = uc_mfma<F16>(fb[1][1], fa[0][0], acc[0][1]);
+            __builtin_amdgcn_sched_barrier(0);
+            uc_lds_wait<1>(fb[2][1]);
+            acc[0][2] = uc_mfma<F16>(fb[2][1], fa[0][0], acc[0][2]);
+            __builtin_amdgcn_sched_barrier(0);
+            uc_lds_wait<0>(fb[3][1]);
+            acc[0][3] = uc_mfma<F16>(fb[3][1], fa[0][0], acc[0][3]);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[1][n] = uc_mfma<F16>(fb[n][1], fa[1][0], acc[1][n]);
+#else
+            uc_lds_wait<0>(fa[0][0], fa[1][0]);
 #endif
             UC_PRODUCT(0, 0)
             __builtin_amdgcn_s_setprio(0);
