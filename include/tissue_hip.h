@@ -543,6 +543,24 @@ TIP_API int tip_piv_lookup_max3_i32_dev(const double *prev_plane, const double *
 TIP_API int tip_piv_sample_max3_i32_dev(const float *flow, const int32_t *labels, int y, int x, const double *cy_host,
                                         const double *cx_host, const uint8_t *present_host, int64_t n, int32_t *hit_host);
 
+/* ---- run-only deflate of a map (csrc/tip_deflate.hip; movie.save_seg's label and type maps) ------------------------------ */
+/* The most bytes the encoder below writes for nbytes of input -- the one place the bound is written: per chunk of 65536     */
+/* input bytes 3 + 9 n + 7 + 3 bits (headers, the longest literal for every byte, end of block), padded to a byte, + 4.      */
+/* Touches no device.                                                                                                         */
+TIP_API int tip_deflate_runs_bound(int64_t nbytes, int64_t *bound_out);
+/* A raw deflate stream (RFC 1951) of the nbytes at src_dev into dst_dev (DEVICE buffers; cap: dst's bytes, at least the      */
+/* bound) and the CRC-32 (zip / zlib) of the input; size and CRC arrive in host words after ONE wait for the stream.  The     */
+/* stream is a sequence of byte-aligned NON-final blocks: per chunk of 65536 input bytes one fixed-Huffman block of literals  */
+/* and matches of distance elem_bytes (1, 2 or 4; no match reaches before its chunk) and one empty stored block, so the caller*/
+/* may put a stored block in front and must put a final block behind (01 00 00 FF FF).  The token rule: tip_deflate.hip's     */
+/* head, restated in tests/deflate_restate.py.  TIP_ERR_ARG: a null pointer, another elem_bytes, nbytes not a multiple of it, */
+/* cap below the bound.  nbytes == 0 gives the empty stream and CRC 0.                                                        */
+TIP_API int tip_deflate_runs_dev(const void *src_dev, int64_t nbytes, int elem_bytes, void *dst_dev, int64_t cap,
+                                 int64_t *out_bytes_host, uint32_t *crc32_host);
+/* The same on host arrays, staged through the calling thread's workspaces.                                                   */
+TIP_API int tip_deflate_runs(const void *src, int64_t nbytes, int elem_bytes, void *dst, int64_t cap, int64_t *out_bytes,
+                             uint32_t *crc32);
+
 #ifdef __cplusplus
 }
 #endif

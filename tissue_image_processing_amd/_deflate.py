@@ -1,0 +1,97 @@
+"""The run-only deflate encoder of csrc/tip_deflate.hip from Python, and what turns its output into a `.npy` archive member:
+the CRC-32 of a concatenation from the parts' CRCs, and the member builder that puts the array header in front as a stored
+block and closes the stream.  Nothing here inflates or deflates on the host."""
+import ctypes
+import zlib
+
+import numpy as np
+
+from . import _lib
+
+CRC_POLY = 0xEDB88320            # the zip / zlib CRC-32's polynomial, reflected: bit 31 is x^0, bit 0 is x^31
+FINAL_BLOCK = b"\x01\x00\x00\xff\xff"      # an empty stored block with BFINAL set: closes a stream of non-final blocks
+
+
+def _gf_mul(a, b):
+    """a * b in GF(2)[x] / P, reflected representation: for every term x^i of a add b * x^i; b * x shifts towards bit 0 and
+    the x^32 that falls out is replaced by the polynomial's lower terms."""
+    p = 0
+    for i in range(32):
+        if (a >> (31 - i)) & 1:
+            p ^= b
+        b = (b >> 1) ^ (CRC_POLY if b & 1 else 0)
+    return p
+
+
+def _x_pow_8n(n):
+    """x^(8 n) by square and multiply"""
+    p, sq = 1 << 31, 1 << 30          # x^0, x^1
+    for _ in range(3):
+        sq = _gf_mul(sq, sq)          # x^8
+    while n:
+        if n & 1:
+            p = _gf_mul(sq, p)
+        sq = _gf_mul(sq, sq)
+        n >>= 1
+    return p
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """zlib.crc32(A + B) from zlib.crc32(A), zlib.crc32(B) and len(B).  From the definition, with J the all-ones word that is
+    both the register's initial value and the final XOR: crc(M) = M(x) x^32 + J x^(8 |M|) + J (mod P).  Then
+    crc(A) x^(8 |B|) + crc(B) = A(x) x^(32 + 8 |B|) + B(x) x^32 + J x^(8 |A| + 8 |B|) + J + (J + J) x^(8 |B|), and that is
+    crc(A + B): A's CRC extended by |B| zero bytes, plus B's -- the two J x^(8 |B|) cancel because the two constants are equal."""
+    return _gf_mul(int(crc_a) & 0xFFFFFFFF, _x_pow_8n(int(len_b))) ^ (int(crc_b) & 0xFFFFFFFF)
+
+
+def runs_bound(nbytes):
+    """tip_deflate_runs_bound: the most bytes the encoder writes for nbytes of input (no device needed)."""
+    out = ctypes.c_int64(0)
+    _lib.check(_lib.load().tip_deflate_runs_bound(int(nbytes), ctypes.byref(out)))
+    return int(out.value)
+
+
+def deflate_runs_dev(src_ptr, nbytes, elem_bytes, dst_ptr, cap):
+    """tip_deflate_runs_dev on device addresses -> (stream bytes written at dst_ptr, CRC-32 of the input); waits once."""
+    size, crc = ctypes.c_int64(0), ctypes.c_uint32(0)
+    _lib.check(_lib.lib().tip_deflate_runs_dev(src_ptr, int(nbytes), int(elem_bytes), dst_ptr, int(cap), ctypes.byref(size),
+                                               ctypes.byref(crc)))
+    return int(size.value), int(crc.value)
+
+
+def deflate_runs(data, elem_bytes):
+    """tip_deflate_runs on a host buffer (bytes or a C-contiguous array) -> (stream, CRC-32 of the input)."""
+    src = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).view(np.uint8).ravel()
+    cap = runs_bound(src.size)
+    dst = np.empty(max(cap, 1), np.uint8)
+    keep = src if src.size else np.zeros(1, np.uint8)      # (an empty array has no address to hand over)
+    size, crc = ctypes.c_int64(0), ctypes.c_uint32(0)
+    _lib.check(_lib.lib().tip_deflate_runs(_lib.ptr(keep), src.size, int(elem_bytes), _lib.ptr(dst), cap, ctypes.byref(size),
+                                           ctypes.byref(crc)))
+    return dst[:size.value].tobytes(), int(crc.value)
+
+
+def npy_header(shape, dtype):
+    """The bytes np.save writes in front of a C-contiguous array's data (format 1.0: magic, header length, dict, padding)."""
+    import io
+    buf = io.BytesIO()
+    np.lib.format.write_array_header_1_0(buf, dict(shape=tuple(int(s) for s in shape), fortran_order=False,
+                                                   descr=np.lib.format.dtype_to_descr(np.dtype(dtype))))
+    return buf.getvalue()
+
+
+def stored_block(payload):
+    """A non-final stored block (BFINAL 0, BTYPE 00, padding, LEN, NLEN, the bytes): byte-aligned, so it goes in front of any
+    byte-aligned stream."""
+    n = len(payload)
+    if n > 0xFFFF:
+        raise ValueError("a stored block holds at most 65535 bytes (got %d)" % n)
+    return b"\x00" + n.to_bytes(2, "little") + (n ^ 0xFFFF).to_bytes(2, "little") + bytes(payload)
+
+
+def npy_member(array_header_bytes, stream, crc, nbytes):
+    """A whole `.npy` archive member from the encoder's output: (raw deflate stream, CRC-32, uncompressed size) of
+    array_header_bytes + data, where `stream` is the encoder's stream of the nbytes of data and `crc` their CRC-32.  The header
+    goes in front as a stored block, the final empty block behind; the CRCs are combined, no byte of the data is touched."""
+    raw = stored_block(array_header_bytes) + bytes(stream) + FINAL_BLOCK
+    return raw, crc32_combine(zlib.crc32(array_header_bytes), crc, nbytes), len(array_header_bytes) + int(nbytes)

@@ -36,6 +36,10 @@ network and closing / watershed tail through FramePipeline.segment_unet, whose l
 frame orientation (Y, X) and are copied on the device into the buffers the classical segmentation fills, so that every stage
 above runs on them unchanged.  Each pipeline has its own predictor and each worker thread its own torch stream.
 
+With `GpuFrameBackend(archive=True)` the owner of frame t also deflates the frame's label map and type map on the device
+(tip_deflate_runs_dev) and keeps the streams and the frame's tables; `save_seg`, called on every rank after `process_movie`, turns
+them into the `.seg` archive Tissue.load reads -- the maps never reach the host uncompressed.
+
 `backend` supplies the per-frame compute so the same driver runs on GPUs (GpuFrameBackend) and, for the
 multi-process CPU tests, on a stand-in backend with the gloo process group.
 """
@@ -131,9 +135,24 @@ class GpuFrameBackend(object):
 
     def __init__(self, C, Z, Y, X, device=None, keep_planes=False, inflight=1, cell_types=None, segmentation="classical",
                  unet_weights=None, unet_channels=(1, 0), predictor_factory=None, keep_hc=False, neighbor_features=False,
-                 order_features=False, **kw):
+                 order_features=False, archive=False, **kw):
         from .pipeline import FramePipeline
         from . import _lib
+        # archive: False, True or dict(type_name="HC") -- every frame's label map (and, with cell_types, its type map) is deflated
+        # on its own GPU right after the frame's tables (tip_deflate_runs_dev on that frame's pipeline and stream, so it overlaps
+        # the other frames in flight) and the stream (about a sixth of the map) is kept on the host in archive_frames[t] together with
+        # what cell_tables() found -- area, bbox, coordinate sums, perimeter counts, neighbour pairs -- and the type rows: the
+        # parts save_seg turns into the frame's `.seg` members.  type_name: the archive's name of the type cell_types marks.
+        if archive is True:
+            archive = {}
+        if archive is not False and archive is not None and not isinstance(archive, dict):
+            raise ValueError("archive must be False, True or dict(type_name=...)")
+        self.archive = None if not isinstance(archive, dict) else dict({"type_name": "HC"}, **archive)
+        if self.archive is not None and set(self.archive) != {"type_name"}:
+            raise ValueError("archive: unknown key(s) %s (known: type_name)" % sorted(set(self.archive) - {"type_name"}))
+        if self.archive is not None and (cell_types or {}).get("type_index", 0) != 0:
+            raise ValueError("archive: the archive names one type, bit 0 of the type byte (cell_types' type_index must be 0)")
+        self.archive_frames = {}   # frame -> dict(labels=(stream, crc), types=(stream, crc) or None, area, bbox, ..., pairs, type rows)
         # segmentation: "classical" (FramePipeline.segment: threshold, blur, watershed on channel 0) or "unet", the GUI's "use
         # Unet?" path (FramePipeline.segment_unet_frame: network + closing / watershed tail on the (atoh, zo) planes
         # unet_channels, labels (Y, X) copied on the device into the pipeline's label buffer).  Every pipeline -- this one and each worker's -- then owns
@@ -304,7 +323,31 @@ class GpuFrameBackend(object):
             out.update(p.neighbor_features(n, valid, out.get("type"), type_index=(self.cell_types or {}).get("type_index", 0)))
         if self.order_features:
             out.update(p.order_features(n, valid, out["cy"], out["cx"]))
+        if self.archive is not None:
+            self.archive_frames[t] = self._archive_parts(p, t, tab, out)
         return out
+
+    def _archive_parts(self, p, t, tab, out):
+        """Frame t's archive parts on pipeline p's thread: the kept label map (int32) and type map (uint8) deflated on the device
+        into p's stream buffer, only the streams downloaded, plus the frame's tables as cell_tables() returned them."""
+        from . import _lib
+        from ._deflate import deflate_runs_dev, runs_bound
+        P = self.Y * self.X
+        if getattr(p, "_stream_buf", None) is None:
+            p._stream_buf = _lib.DeviceBuffer(max(runs_bound(P * 4), 1))
+        dst = p._stream_buf
+
+        def encode(src_ptr, nbytes, elem_bytes):
+            size, crc = deflate_runs_dev(src_ptr, nbytes, elem_bytes, dst.ptr, dst.nbytes)
+            return dst.download((size,), np.uint8).tobytes(), crc
+
+        parts = {k: np.array(tab[k]) for k in ("area", "bbox", "sumy", "sumx", "pc", "pairs")}
+        parts["labels"] = encode(self.labels[t].ptr, P * 4, 4)
+        parts["types"] = None
+        if self.cell_types is not None:
+            parts["types"] = encode(self.type_maps[t].ptr, P, 1)
+            parts.update({k: np.array(out[k]) for k in ("type", "valid", "mean_intensity")})
+        return parts
 
     def fetch_cell_types(self, t):
         """Frame t's type map (uint8 (Y, X): a valid cell's type, 255 on invalid cells and label 0), downloaded."""
@@ -713,3 +756,21 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
                 _agree_on_piv_failure(failed, error, rank, world, dist, device)
             lookups.update(_gather_lookups(hits, dist, rank, world, device))
     return _stitch(tables, lookups, stitcher) if rank == 0 else (None, None)
+
+
+def save_seg(path, n_frames, backend, tables, ids, rank=0, world=1, dist=None, device="cpu", channel_names=()):
+    """Writes a finished movie as `<path>.seg`, the archive Tissue.load and the unmodified GUI open.  Collective: EVERY rank calls
+    it after process_movie, with process_movie's results (rank 0: tables and ids per frame; the others: None, None) and the
+    backend that ran the movie with archive=True or dict(type_name=...) (GpuFrameBackend).  Returns the path on rank 0, None
+    elsewhere.
+
+    Rank 0 hands the owners the track ids of their frames.  Each owner wraps its frames' device-deflated label and type maps as
+    `.npy` members (the array header in front as a stored block, CRCs combined: _deflate.npy_member) and builds
+    frame_k_data.pkl from the tables it kept -- what set_labels, calculate_frame_cellinfo, calc_cell_types(plane, ..., type_name)
+    when the backend types cells, and `label` = ids[t] leave in a Tissue; no device pass runs again -- deflated with the host's
+    zlib, being small.  The members travel to rank 0 in one gather (_collectives.gather_varlen); rank 0 adds drifts.npy (the
+    tables[t]["drift"] rows), valid_frames.npy (ones), an empty events table, the type and channel names and
+    shape_fitting_data.json, and writes the zip itself (seg_archive.write_raw_zip: members and order of
+    Tissue._archive_members).  An archive that would need zip64 raises ValueError before anything is written."""
+    from .seg_archive import save_seg as _save_seg
+    return _save_seg(path, n_frames, backend, tables, ids, rank, world, dist, device, channel_names)
