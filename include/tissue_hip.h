@@ -71,6 +71,8 @@ TIP_API int tip_sync(void);                       /* wait for this thread's stre
 /*   TIP_PROJECT_DEBUG                                                                 projection kernel selection   */
 /*   TIP_UNET_TILE8 = -1|0|1, TIP_UNET_SPB = 1|3, TIP_UNET_XCD_MAP = 0|1               U-Net convolution schedule    */
 /*                                                  (TIP_UNET_SPB: every value above 1 means 3)                       */
+/*   TIP_UNET_MFMA = 32|16               K of the MFMA behind fp16 pieces on 16-row tiles with >= 4 taps: 32 (default)  */
+/*                                       = v_mfma_f32_16x16x32_f16 on pairs of steps, 16 = 32x32x16 as everywhere else   */
 /*   TIP_UNET_TAIL_UNFUSED                                                            tail morphology as separate launches */
 /*   TIP_UNET_FIRST = mfma | valu | n    mode f16x3's first layer: matrix cores (default) or the float32 vector kernel; */
 /*                                       n > 1: matrix cores with n workgroups per CU (measurements)                    */
@@ -205,7 +207,14 @@ TIP_API int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream);
 /*    4     <2, 16, 2, 2, 1>   two pieces, 16-row tiles, one or two taps                                                            */
 /*    6     <2, 16, 4, 1, 3>   two pieces, 16-row tiles, nine taps, and six taps with c0 + c1 >= 256                               */
 /* Every two-piece flavour exists with bf16 (format 0) and with fp16 pieces (format 1): the code does not depend on the format.   */
+/* With fp16 pieces, codes 2 and 6 run one kernel on 16x16x32 MFMAs in place of their own (tip_unet_conv_mfma_k below): a launch  */
+/* then computes the same bits whichever of the two codes the tuning gives it.                                                    */
 TIP_API int tip_unet_conv_flavour(const tip_unet_conv_desc *d);
+/* The MFMA shape is a second property of a launch and does not change the code: 16 = the flavour's own kernel                     */
+/* (v_mfma_f32_32x32x16), 32 = fp16 pieces (format 1) under flavours 2 and 6 run one kernel on v_mfma_f32_16x16x32_f16, K = 32     */
+/* formed from two consecutive (chunk, tap) steps, one such pair per barrier (TIP_UNET_MFMA=16 puts them back on 32x32x16).        */
+/* Returns 16 or 32, or the negative error the launch would return.                                                                */
+TIP_API int tip_unet_conv_mfma_k(const tip_unet_conv_desc *d);
 /* Conv2DTranspose folded into the next Conv2D: border pass on the float32 partial `part` (2h x 2w x cout) that four  */
 /* raw launches over the low-resolution tensor x (h x w x cin, split) left.  row_w / col_w: [5][cin][cout] float32 corrections of  */
 /* the last output row / column, taps (parity, offset) = (0,-1) (0,0) (1,-1) (1,0) (1,+1); corner_w: [cin][cout]; bias_tab:        */

@@ -176,6 +176,7 @@ bool tuning_assign(Tuning &t, const char *name, const char *value)
     else if (n == "TIP_UNET_TILE8") num(t.unet_tile8, def.unet_tile8);
     else if (n == "TIP_UF_ONE_LEVEL") flag(t.uf_one_level, 0);
     else if (n == "TIP_UNET_SPB") num(t.unet_spb, def.unet_spb);
+    else if (n == "TIP_UNET_MFMA") { num(t.unet_mfma, def.unet_mfma); if (t.unet_mfma != 32) t.unet_mfma = 16; }
     else if (n == "TIP_UNET_XCD_MAP") flag(t.unet_xcd_map, 1);
     else if (n == "TIP_UNET_FIRST") {
         if (unset || !strcmp(value, "mfma")) t.unet_first_mfma = def.unet_first_mfma;
@@ -190,7 +191,7 @@ bool tuning_assign(Tuning &t, const char *name, const char *value)
 
 const char *const TUNING_NAMES[] = {"TIP_WS_TIES", "TIP_WS_OPEN", "TIP_WS_NO_SKIP", "TIP_WS_DEBUG", "TIP_WS_NO_ENDGAME", "TIP_WS_NO_WIDE",
                                     "TIP_PROJECT_GENERIC", "TIP_PROJECT_UNFUSED_PREBLUR", "TIP_PROJECT_UNFUSED_MASK",
-                                    "TIP_PROJECT_EXACT_SCORE", "TIP_PROJECT_DEBUG", "TIP_UNET_TILE8", "TIP_UNET_TAIL_UNFUSED", "TIP_UNET_XCD_MAP", "TIP_UNET_SPB", "TIP_UNET_FIRST", "TIP_UF_ONE_LEVEL", "TIP_MB_SMALL", "TIP_MB_BATCH"};
+                                    "TIP_PROJECT_EXACT_SCORE", "TIP_PROJECT_DEBUG", "TIP_UNET_TILE8", "TIP_UNET_TAIL_UNFUSED", "TIP_UNET_XCD_MAP", "TIP_UNET_SPB", "TIP_UNET_MFMA", "TIP_UNET_FIRST", "TIP_UF_ONE_LEVEL", "TIP_MB_SMALL", "TIP_MB_BATCH"};
 
 void tuning_from_env()
 {

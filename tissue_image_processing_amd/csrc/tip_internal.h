@@ -120,6 +120,7 @@ struct Tuning {
     int unet_tail_unfused = 0;  // TIP_UNET_TAIL_UNFUSED: the tail's morphology as separate rank-filter launches (tests)
     int unet_xcd_map = 1;       // TIP_UNET_XCD_MAP: the channel blocks of one pixel tile side by side on one XCD (0: all workgroups in flight on one channel block)
     int unet_spb = 3;           // TIP_UNET_SPB: steps per barrier of the 3x3 16-row convolution kernel (1 or 3; above 1 means 3)
+    int unet_mfma = 32;         // TIP_UNET_MFMA: K of the MFMA of the f16x3 16-row convolutions with >= 4 taps (32: 16x16x32; anything else: 16 = 32x32x16)
     int unet_first_mfma = 1;    // TIP_UNET_FIRST: mode f16x3's first layer, 1 (mfma) = k_unet_conv_first_mfma, 0 (valu) = the float32 vector kernel; n > 1: mfma with n workgroups per CU
     int uf_one_level = 0;       // TIP_UF_ONE_LEVEL: the one-level union-find (global atomics only) instead of tiles in LDS + borders (tests)
     int mb_small = -1;          // TIP_MB_SMALL: generations of the two-valued flood of at most this many pixels run in one workgroup (0: never; -1: the built-in default)

@@ -9,6 +9,7 @@
 // Runs on the stream the caller names (torch's current stream), so no cross-stream synchronisation is needed.
 #include "tip_internal.h"
 #include "tip_unet_conv.h"
+#include "tip_unet_conv_k32.h"
 #include "tip_unet_first.h"
 #include "tip_unet_planes.h"
 #include <algorithm>
@@ -124,6 +125,7 @@ struct ConvPlan {
     int row;                       // index into CONV_FLAVOURS
     int ntiles, nblks, xcd_map;
     size_t lds;
+    int mfma_k;                    // 16: the flavour's own kernel (32x32x16 MFMAs); 32: k_unet_conv_k32 in its place (16x16x32, tip_unet_conv_k32.h)
 };
 
 // Validates the descriptor and chooses the flavour: TIP_OK and `pl`, or the error tip_unet_conv_dev returns.  Touches no device.
@@ -174,6 +176,11 @@ static int unet_conv_plan(const tip_unet_conv_desc *d, ConvPlan &pl)
     const bool three = d->ntaps == 9 || (d->ntaps == 6 && d->c0 + d->c1 >= 256);
     const int spb = (th == 16 && dist == 4 && three && tuning().unet_spb > 1) ? 3 : 1;
     pl.lds = (size_t)(da + 1) * a_per * threads * 16 + (size_t)(spb > 1 ? 3 * spb : dist + 1) * d->planes * 256 * 16;
+    // The MFMA shape is a second property of the launch: the codes below do not change with it.  Two fp16 pieces on 16-row tiles with
+    // four and more taps (flavours 2 and 6) run ONE K = 32 kernel, one pair step per barrier, unless TIP_UNET_MFMA=16 -- so
+    // TIP_UNET_SPB does not change a bit of what these launches compute.
+    pl.mfma_k = (d->format == 1 && d->planes == 2 && th == 16 && dist == 4 && tuning().unet_mfma == 32) ? 32 : 16;
+    if (pl.mfma_k == 32) pl.lds = UK_LDS;
     for (pl.row = 0; pl.row < N_CONV_FLAVOURS; ++pl.row) {
         const ConvFlavour &f = CONV_FLAVOURS[pl.row];
         if (f.npl == d->planes && f.th == th && f.d == dist && f.da == da && f.spb == spb) return TIP_OK;
@@ -186,6 +193,13 @@ int tip_unet_conv_flavour(const tip_unet_conv_desc *d)
     ConvPlan pl;
     const int rc = unet_conv_plan(d, pl);
     return rc ? rc : CONV_FLAVOURS[pl.row].code;
+}
+
+int tip_unet_conv_mfma_k(const tip_unet_conv_desc *d)
+{
+    ConvPlan pl;
+    const int rc = unet_conv_plan(d, pl);
+    return rc ? rc : pl.mfma_k;
 }
 
 int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
@@ -217,14 +231,14 @@ int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
     p.raw_out = d->raw_out; p.seed = d->seed;
     p.xcd_map = pl.xcd_map;
     const ConvFlavour &fl = CONV_FLAVOURS[pl.row];
-    const ConvKernel kernel = d->format == 1 ? fl.f16 : fl.bf16;
+    const ConvKernel kernel = pl.mfma_k == 32 ? k_unet_conv_k32 : d->format == 1 ? fl.f16 : fl.bf16;
     const int threads = fl.th * 32;
     const size_t lds = pl.lds;
     const dim3 grid = p.xcd_map ? dim3((unsigned)(pl.ntiles * pl.nblks)) : dim3(pl.ntiles, pl.nblks);
     hipStream_t s = (hipStream_t)stream;
     // the >64 KB dynamic LDS attribute is set once per (device, kernel): one atomic bit each
     static std::atomic<unsigned> attr_done[64];
-    const unsigned bit = 1u << (2 * pl.row + d->format);
+    const unsigned bit = pl.mfma_k == 32 ? 1u << 31 : 1u << (2 * pl.row + d->format);
     const int dev = c.device >= 0 && c.device < 64 ? c.device : 0;
     if (!(attr_done[dev].load(std::memory_order_acquire) & bit)) {
         TIP_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
