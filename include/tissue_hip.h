@@ -208,7 +208,9 @@ TIP_API int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream);
 /*    6     <2, 16, 4, 1, 3>   two pieces, 16-row tiles, nine taps, and six taps with c0 + c1 >= 256                               */
 /* Every two-piece flavour exists with bf16 (format 0) and with fp16 pieces (format 1): the code does not depend on the format.   */
 /* With fp16 pieces, codes 2 and 6 run one kernel on 16x16x32 MFMAs in place of their own (tip_unet_conv_mfma_k below): a launch  */
-/* then computes the same bits whichever of the two codes the tuning gives it.                                                    */
+/* then computes the same bits whichever of the two codes the tuning gives it.  The codes are the rows of one launch table         */
+/* (csrc/tip_unet.hip), which holds per code the kernel, threads and LDS size for bf16 pieces, fp16 pieces and fp16 pieces at      */
+/* K = 32; both queries and the launch read the one plan made from it.                                                             */
 TIP_API int tip_unet_conv_flavour(const tip_unet_conv_desc *d);
 /* The MFMA shape is a second property of a launch and does not change the code: 16 = the flavour's own kernel                     */
 /* (v_mfma_f32_32x32x16), 32 = fp16 pieces (format 1) under flavours 2 and 6 run one kernel on v_mfma_f32_16x16x32_f16, K = 32     */

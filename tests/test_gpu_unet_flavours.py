@@ -13,18 +13,14 @@ piece holds such a value), every product (a multiple of 2^-7) and every partial 
 float32 in any order, in all three modes, so the raw float32 output must EQUAL float64: a wrong tap, chunk, block, permutation or
 seam, or a tile read before its copy landed, cannot pass, and no tolerance is involved.  RANDOM: randn inputs, 0.1 randn weights,
 held to the per-layer bounds TOL of the existing layer tests on the whole tensor, every border region and every tile seam."""
-import functools
-
 import pytest
 
 import unet_layers as ul
-from unet_layers import HEAD_TOL, MODES, _assert_regions, _join, _split
+from unet_layers import HEAD_TOL, MODES, REGIONS, _assert_regions, _join, _split, bits, exact_case, random_case, run_case
 
 pytestmark = pytest.mark.gpu
 
 H, W, COUT = 32, 64, 256
-REGIONS = ["all", "interior", "first row", "last row", "first column", "last column", "top-left corner", "top-right corner",
-           "bottom-left corner", "bottom-right corner"]
 
 # flavour code -> [(ntaps, c0, c1, tuning under which the dispatcher must pick the flavour)]
 _T16, _SPB1 = {"TIP_UNET_TILE8": "0"}, {"TIP_UNET_SPB": "1"}
@@ -59,53 +55,6 @@ ALL_CASES = _params(_CASES)
 SHAPE_CASES = _params(_SHAPE_CASE)
 
 
-@functools.lru_cache(maxsize=None)
-def _exact(ntaps, c0, c1, cout=COUT, h=H, w=W):
-    """exact data of one case and its float64 results (shared by the tests; never modified)"""
-    import torch
-    g = torch.Generator().manual_seed(1000 * ntaps + c0 + 7 * c1 + cout + h * w)
-    dy, dx = ul.tap_offsets(ntaps)
-    a0 = torch.randint(0, 64, (h, w, c0), generator=g).float() / 16
-    a1 = torch.randint(0, 64, (h, w, c1), generator=g).float() / 16 if c1 else None
-    taps = 2.0 ** -torch.randint(0, 4, (ntaps, c0 + c1, cout), generator=g).float() * (torch.randint(0, 2, (ntaps, c0 + c1, cout), generator=g).float() * 2 - 1)
-    bias = torch.randint(-64, 64, (cout,), generator=g).float() / 16
-    scale = 2.0 ** torch.randint(-1, 2, (cout,), generator=g).float()
-    shift = torch.randint(-64, 64, (cout,), generator=g).float() / 16
-    seed = torch.randint(-1024, 1024, (h, w, cout), generator=g).float() / 128
-    ref = ul.reference(a0, a1, taps, dy, dx, bias, scale, shift)
-    seeded = ul.reference(a0, a1, taps, dy, dx, seed=seed)["sum"]
-    # the construction: every sum, seeded or not, is a float32 (a multiple of 2^-7 below 2^9 + 8), and so is the BatchNorm output
-    for t in (ref["sum"], seeded, ref["out"]):
-        assert torch.equal(t.float().double(), t)
-    assert float(ref["sum"].abs().max()) < 512 and float(ref["out"].abs().max()) < 2048
-    return dict(a0=a0, a1=a1, taps=taps, dy=dy, dx=dx, bias=bias, scale=scale, shift=shift, seed=seed, ref=ref, seeded=seeded)
-
-
-@functools.lru_cache(maxsize=None)
-def _random(ntaps, c0, c1, cout=COUT, h=H, w=W):
-    """randn data of one case, as test_gpu_unet_conv.py::test_single_layers_against_float64 draws it, and its float64 results"""
-    import torch
-    g = torch.Generator().manual_seed(2000 * ntaps + c0 + 7 * c1 + cout + h * w)
-    dy, dx = ul.tap_offsets(ntaps)
-    a0 = torch.randn((h, w, c0), generator=g)
-    a1 = torch.randn((h, w, c1), generator=g) if c1 else None
-    taps = torch.randn((ntaps, c0 + c1, cout), generator=g) * 0.1
-    bias, scale, shift = torch.randn(cout, generator=g), torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g)
-    hw, hb = torch.randn((2, cout), generator=g) * 0.05, torch.randn(2, generator=g) * 0.1
-    ref = ul.reference(a0, a1, taps, dy, dx, bias, scale, shift, head=(hw, hb) if cout == 128 else None)
-    return dict(a0=a0, a1=a1, taps=taps, dy=dy, dx=dx, bias=bias, scale=scale, shift=shift, hw=hw, hb=hb, ref=ref,
-                ref_bias=ref["sum"] + bias.double())
-
-
-def _layer(mode, code, c, **kw):
-    return ul.run_layer(mode, c["a0"], c["a1"], c["taps"], c["dy"], c["dx"], code, **kw)
-
-
-def _bits(t):
-    import torch
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
 def _xcd_active(code, h, w, cout):
     """whether a launch of this flavour on this grid uses the XCD workgroup order when TIP_UNET_XCD_MAP allows it (tip_unet.hip)"""
     return cout > 128 and ((h // ul.FLAVOURS[code][1]) * (w // 32)) % 8 == 0
@@ -125,30 +74,30 @@ def test_exact_data_equal_float64(code, ntaps, c0, c1, tune, mode):
     1024 x 2^-8 -- up to 11 bits for an 8-bit piece: not held in general, so the joined value is held to TOL instead."""
     import torch
     from tissue_image_processing_amd import _lib
-    c = _exact(ntaps, c0, c1)
+    c = exact_case(ntaps, c0, c1)
     planes, fmt = MODES[mode]
     th = ul.FLAVOURS[code][1]
     zero = torch.zeros((H, W, COUT))
     with _lib.tuning(**tune):
-        raw = _layer(mode, code, c, raw=True)["raw"]
-        again = _layer(mode, code, c, raw=True)["raw"]
-        seeded = _layer(mode, code, c, raw=True, seed=c["seed"])["raw"]
-        zero_seeded = _layer(mode, code, c, raw=True, seed=zero)["raw"]
-        stored = _layer(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])
+        raw = run_case(mode, code, c, raw=True)["raw"]
+        again = run_case(mode, code, c, raw=True)["raw"]
+        seeded = run_case(mode, code, c, raw=True, seed=c["seed"])["raw"]
+        zero_seeded = run_case(mode, code, c, raw=True, seed=zero)["raw"]
+        stored = run_case(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])
         with _lib.tuning(TIP_UNET_XCD_MAP="0"):
-            raw_plain = _layer(mode, code, c, raw=True)["raw"]
-            stored_plain = _layer(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
+            raw_plain = run_case(mode, code, c, raw=True)["raw"]
+            stored_plain = run_case(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
     wrong = raw.double() != c["ref"]["sum"]
     print("%s: %d of %d raw sums differ from float64 (XCD order %s)" % (mode, int(wrong.sum()), wrong.numel(), "on" if _xcd_active(code, H, W, COUT) else "not applicable"))
     assert not bool(wrong.any()), "raw output differs from float64 at (y, x, channel) %s ..." % wrong.nonzero()[:4].tolist()
-    assert torch.equal(_bits(again), _bits(raw)), "two identical launches differ"
-    assert torch.equal(_bits(raw_plain), _bits(raw)), "TIP_UNET_XCD_MAP=0 changes the raw output"
+    assert torch.equal(bits(again), bits(raw)), "two identical launches differ"
+    assert torch.equal(bits(raw_plain), bits(raw)), "TIP_UNET_XCD_MAP=0 changes the raw output"
     assert torch.equal(seeded.double(), c["seeded"]), "seeded raw output differs from float64's seed + sum"
-    assert torch.equal(_bits(zero_seeded), _bits(raw)), "a zero seed changes the raw output"
+    assert torch.equal(bits(zero_seeded), bits(raw)), "a zero seed changes the raw output"
     assert stored.get("status", 0) == 0
     want = _split(c["ref"]["out"].float(), planes, fmt)
-    assert torch.equal(_bits(stored["out"]), _bits(want)), "stored pieces differ from the split of the float64 result"
-    assert torch.equal(_bits(stored_plain), _bits(stored["out"])), "TIP_UNET_XCD_MAP=0 changes the stored planes"
+    assert torch.equal(bits(stored["out"]), bits(want)), "stored pieces differ from the split of the float64 result"
+    assert torch.equal(bits(stored_plain), bits(stored["out"])), "TIP_UNET_XCD_MAP=0 changes the stored planes"
     got = _join(stored["out"], fmt).double()
     if mode == "bf16x3":
         _assert_regions(mode, "exact data, stored", got, c["ref"]["out"], REGIONS)
@@ -163,15 +112,15 @@ def test_random_data_within_layer_bounds(code, ntaps, c0, c1, tune, mode):
     the interior and the rows and columns either side of every tile seam; the XCD workgroup order changes no bit."""
     import torch
     from tissue_image_processing_amd import _lib
-    c = _random(ntaps, c0, c1)
+    c = random_case(ntaps, c0, c1)
     fmt = MODES[mode][1]
     what = "<%d,%d,%d,%d,%d> %d taps %d+%d" % (ul.FLAVOURS[code] + (ntaps, c0, c1))
     with _lib.tuning(**tune):
-        res = _layer(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])
+        res = run_case(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])
         with _lib.tuning(TIP_UNET_XCD_MAP="0"):
-            plain = _layer(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
+            plain = run_case(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
     assert res.get("status", 0) == 0
-    assert torch.equal(_bits(plain), _bits(res["out"]))
+    assert torch.equal(bits(plain), bits(res["out"]))
     got = _join(res["out"], fmt).double()
     _assert_regions(mode, what, got, c["ref"]["out"], REGIONS)
     ul.assert_seams(mode, what, got, c["ref"]["out"], ul.FLAVOURS[code][1])
@@ -186,26 +135,26 @@ def test_xcd_order_on_sixteen_row_tiles(code, ntaps, c0, c1, tune, mode):
     from tissue_image_processing_amd import _lib
     h, w = 32, 128
     assert _xcd_active(code, h, w, COUT) and not _xcd_active(code, H, W, COUT)
-    c = _exact(ntaps, c0, c1, COUT, h, w)
+    c = exact_case(ntaps, c0, c1, COUT, h, w)
     planes, fmt = MODES[mode]
     with _lib.tuning(**tune):
-        raw = _layer(mode, code, c, raw=True)["raw"]
-        stored = _layer(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
+        raw = run_case(mode, code, c, raw=True)["raw"]
+        stored = run_case(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
         with _lib.tuning(TIP_UNET_XCD_MAP="0"):
-            raw_plain = _layer(mode, code, c, raw=True)["raw"]
-            stored_plain = _layer(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
+            raw_plain = run_case(mode, code, c, raw=True)["raw"]
+            stored_plain = run_case(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
     assert torch.equal(raw.double(), c["ref"]["sum"])
-    assert torch.equal(_bits(stored), _bits(_split(c["ref"]["out"].float(), planes, fmt)))
-    assert torch.equal(_bits(raw_plain), _bits(raw)) and torch.equal(_bits(stored_plain), _bits(stored))
+    assert torch.equal(bits(stored), bits(_split(c["ref"]["out"].float(), planes, fmt)))
+    assert torch.equal(bits(raw_plain), bits(raw)) and torch.equal(bits(stored_plain), bits(stored))
 
 
 @pytest.mark.parametrize("code,ntaps,c0,c1,tune,mode", SHAPE_CASES)
 def test_bias_only_epilogue(code, ntaps, c0, c1, tune, mode):
     """no scale / shift (the transposed convolution's layers): sum + bias, no ReLU -- negative values survive"""
     from tissue_image_processing_amd import _lib
-    c = _random(ntaps, c0, c1)
+    c = random_case(ntaps, c0, c1)
     with _lib.tuning(**tune):
-        res = _layer(mode, code, c, bias=c["bias"])
+        res = run_case(mode, code, c, bias=c["bias"])
     assert res.get("status", 0) == 0
     got = _join(res["out"], MODES[mode][1]).double()
     assert float(c["ref_bias"].min()) < -0.1 * float(c["ref_bias"].abs().max())
@@ -220,12 +169,12 @@ def test_pooled_output(code, ntaps, c0, c1, tune, mode):
     float64's"""
     import torch
     from tissue_image_processing_amd import _lib
-    c = _random(ntaps, c0, c1)
+    c = random_case(ntaps, c0, c1)
     fmt = MODES[mode][1]
     with _lib.tuning(**tune):
-        res = _layer(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"], pool=True)
-        alone = _layer(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
-    assert torch.equal(_bits(res["out"]), _bits(alone))
+        res = run_case(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"], pool=True)
+        alone = run_case(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
+    assert torch.equal(bits(res["out"]), bits(alone))
     assert torch.equal(_join(res["pool"]), torch.nn.functional.max_pool2d(_join(res["out"]).permute(2, 0, 1)[None], 2)[0].permute(1, 2, 0))
     _assert_regions(mode, "pooled output", _join(res["pool"], fmt).double(), c["ref"]["pool"], REGIONS)
     _assert_regions(mode, "output next to the pooled one", _join(res["out"], fmt).double(), c["ref"]["out"], ["all"])
@@ -238,10 +187,10 @@ def test_stride_two_mapping(code, ntaps, c0, c1, tune, mode, oy, ox):
     classes) and raw: the class is within TOL / equal to float64, the other three parity classes keep the sentinel (run_layer)"""
     import torch
     from tissue_image_processing_amd import _lib
-    c, e = _random(ntaps, c0, c1), _exact(ntaps, c0, c1)
+    c, e = random_case(ntaps, c0, c1), exact_case(ntaps, c0, c1)
     with _lib.tuning(**tune):
-        res = _layer(mode, code, c, bias=c["bias"], stride=2, oy=oy, ox=ox)
-        raw = _layer(mode, code, e, raw=True, stride=2, oy=oy, ox=ox)["raw"]
+        res = run_case(mode, code, c, bias=c["bias"], stride=2, oy=oy, ox=ox)
+        raw = run_case(mode, code, e, raw=True, stride=2, oy=oy, ox=ox)["raw"]
     got = _join(res["out"][:, oy::2, ox::2], MODES[mode][1]).double()
     _assert_regions(mode, "stride 2, class (%d, %d)" % (oy, ox), got, c["ref_bias"], REGIONS)
     assert torch.equal(raw[oy::2, ox::2].double(), e["ref"]["sum"])
@@ -252,10 +201,10 @@ def test_fused_head(code, ntaps, c0, c1, tune, mode):
     """head_out (128 output channels): class probabilities against float64's softmax at the network tests' bounds, and against
     tip_unet_head_dev on the same layer's stored planes at the same bound"""
     from tissue_image_processing_amd import _lib
-    c = _random(ntaps, c0, c1, 128)
+    c = random_case(ntaps, c0, c1, 128)
     with _lib.tuning(**tune):
-        fused = _layer(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"], head=(c["hw"], c["hb"]))
-        stored = _layer(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
+        fused = run_case(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"], head=(c["hw"], c["hb"]))
+        stored = run_case(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])["out"]
     assert fused.get("status", 0) == 0
     ref = c["ref"]["head"]
     assert float((ref * (1 - ref) > 0.05).double().mean()) > 0.9        # (the softmax is not saturated: errors are not hidden)

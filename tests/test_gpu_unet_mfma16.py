@@ -10,14 +10,14 @@ four to eight, of which four taps make the next chunk's activations due one pair
 a seam in y and in x) and 32 x 128 (the XCD workgroup order, on and off), 256 output channels (two channel blocks).
 
 The 8-row kernel (flavour 0) stays on 32x32x16, so the cases at h = 24 and under the default plan only assert that
-tip_unet_conv_mfma_k says so.  EXACT and RANDOM data are test_gpu_unet_flavours.py's (same generators, shared caches)."""
+tip_unet_conv_mfma_k says so.  EXACT and RANDOM data are unet_layers' exact_case and random_case: what test_gpu_unet_flavours.py
+runs on, drawn once per process."""
 import ctypes
 
 import pytest
 
 import unet_layers as ul
-from unet_layers import HEAD_TOL, TOL, _assert_regions, _join, _split
-from test_gpu_unet_flavours import REGIONS, _bits, _exact, _layer, _random
+from unet_layers import HEAD_TOL, REGIONS, TOL, _assert_regions, _join, _split, bits, exact_case, random_case, run_case
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +42,7 @@ def _mfma_k(ntaps, c0, c1, h, w, cout=COUT):
 def _run(c, ntaps, c0, c1, h, w, want_k=32, spb=3, **kw):
     """one launch; the flavour code (run_layer) and the MFMA shape are asserted first"""
     assert _mfma_k(ntaps, c0, c1, h, w, c["taps"].shape[2]) == want_k
-    return _layer(MODE, _code(ntaps, c0, c1, spb), c, **kw)
+    return run_case(MODE, _code(ntaps, c0, c1, spb), c, **kw)
 
 
 @pytest.mark.parametrize("h,w", GRIDS)
@@ -53,7 +53,7 @@ def test_exact_data_equal_float64(ntaps, c0, c1, h, w):
     float64 result"""
     import torch
     from tissue_image_processing_amd import _lib
-    c = _exact(ntaps, c0, c1, COUT, h, w)
+    c = exact_case(ntaps, c0, c1, COUT, h, w)
     bn = dict(bias=c["bias"], scale=c["scale"], shift=c["shift"])
     with _lib.tuning(**T16):
         raw = _run(c, ntaps, c0, c1, h, w, raw=True)["raw"]
@@ -70,13 +70,13 @@ def test_exact_data_equal_float64(ntaps, c0, c1, h, w):
     print("%d of %d raw sums differ from float64" % (int(wrong.sum()), wrong.numel()))
     assert not bool(wrong.any()), "raw output differs from float64 at (y, x, channel) %s ..." % wrong.nonzero()[:4].tolist()
     assert torch.equal(seeded.double(), c["seeded"]), "seeded raw output differs from float64's seed + sum"
-    assert torch.equal(_bits(again), _bits(raw)), "two identical launches differ"
-    assert torch.equal(_bits(raw_spb1), _bits(raw)), "TIP_UNET_SPB=1 changes the raw output"
-    assert torch.equal(_bits(raw_plain), _bits(raw)), "TIP_UNET_XCD_MAP=0 changes the raw output"
+    assert torch.equal(bits(again), bits(raw)), "two identical launches differ"
+    assert torch.equal(bits(raw_spb1), bits(raw)), "TIP_UNET_SPB=1 changes the raw output"
+    assert torch.equal(bits(raw_plain), bits(raw)), "TIP_UNET_XCD_MAP=0 changes the raw output"
     assert stored["status"] == 0
     want = _split(c["ref"]["out"].float(), 2, 1)
-    assert torch.equal(_bits(stored["out"]), _bits(want)), "stored pieces differ from the split of the float64 result"
-    assert torch.equal(_bits(stored_spb1), _bits(stored["out"])) and torch.equal(_bits(stored_plain), _bits(stored["out"]))
+    assert torch.equal(bits(stored["out"]), bits(want)), "stored pieces differ from the split of the float64 result"
+    assert torch.equal(bits(stored_spb1), bits(stored["out"])) and torch.equal(bits(stored_plain), bits(stored["out"]))
 
 
 @pytest.mark.parametrize("h,w", GRIDS)
@@ -85,7 +85,7 @@ def test_random_data_within_layer_bounds(ntaps, c0, c1, h, w):
     """RANDOM data: unet_layers' per-layer bound for f16x3 on the tensor, every border region and every tile seam; the 32x32x16
     kernels (TIP_UNET_MFMA=16) and the K = 32 kernel, each within that bound of float64, differ by at most twice the bound"""
     from tissue_image_processing_amd import _lib
-    c = _random(ntaps, c0, c1, COUT, h, w)
+    c = random_case(ntaps, c0, c1, COUT, h, w)
     bn = dict(bias=c["bias"], scale=c["scale"], shift=c["shift"])
     with _lib.tuning(**T16):
         res = _run(c, ntaps, c0, c1, h, w, **bn)
@@ -117,7 +117,7 @@ def test_eight_row_launches_keep_32x32x16():
 
 def test_bias_only_epilogue():
     from tissue_image_processing_amd import _lib
-    c = _random(*EPILOGUE_CASE)
+    c = random_case(*EPILOGUE_CASE)
     with _lib.tuning(**T16):
         res = _run(c, *EPILOGUE_CASE, 32, 64, bias=c["bias"])
     assert res["status"] == 0
@@ -131,12 +131,12 @@ def test_pooled_output():
     """the pooled planes are exactly max_pool2d of the joined stored output, which is the launch's without pool_out bit for bit"""
     import torch
     from tissue_image_processing_amd import _lib
-    c = _random(*EPILOGUE_CASE)
+    c = random_case(*EPILOGUE_CASE)
     bn = dict(bias=c["bias"], scale=c["scale"], shift=c["shift"])
     with _lib.tuning(**T16):
         res = _run(c, *EPILOGUE_CASE, 32, 64, pool=True, **bn)
         alone = _run(c, *EPILOGUE_CASE, 32, 64, **bn)["out"]
-    assert torch.equal(_bits(res["out"]), _bits(alone))
+    assert torch.equal(bits(res["out"]), bits(alone))
     assert torch.equal(_join(res["pool"]), torch.nn.functional.max_pool2d(_join(res["out"]).permute(2, 0, 1)[None], 2)[0].permute(1, 2, 0))
     _assert_regions(MODE, "pooled output", _join(res["pool"], 1).double(), c["ref"]["pool"], REGIONS)
     _assert_regions(MODE, "output next to the pooled one", _join(res["out"], 1).double(), c["ref"]["out"], ["all"])
@@ -148,7 +148,7 @@ def test_stride_two_mapping(oy, ox):
     parity classes keep the sentinel (run_layer)"""
     import torch
     from tissue_image_processing_amd import _lib
-    c, e = _random(*EPILOGUE_CASE), _exact(*EPILOGUE_CASE)
+    c, e = random_case(*EPILOGUE_CASE), exact_case(*EPILOGUE_CASE)
     with _lib.tuning(**T16):
         res = _run(c, *EPILOGUE_CASE, 32, 64, bias=c["bias"], stride=2, oy=oy, ox=ox)
         raw = _run(e, *EPILOGUE_CASE, 32, 64, raw=True, stride=2, oy=oy, ox=ox)["raw"]
@@ -160,7 +160,7 @@ def test_stride_two_mapping(oy, ox):
 def test_fused_head():
     """head_out (128 output channels) against float64's softmax and against tip_unet_head_dev on the same layer's stored planes"""
     from tissue_image_processing_amd import _lib
-    c = _random(*EPILOGUE_CASE, 128)
+    c = random_case(*EPILOGUE_CASE, 128)
     bn = dict(bias=c["bias"], scale=c["scale"], shift=c["shift"])
     with _lib.tuning(**T16):
         fused = _run(c, *EPILOGUE_CASE, 32, 64, head=(c["hw"], c["hb"]), **bn)
@@ -178,7 +178,7 @@ def test_range_flag_fires():
     """the fp16 range word (test_gpu_unet_range.py's mechanism): BatchNorm scales that push values past 4094 set bit 0 and the stored
     pieces saturate; the same layer with its own scales does not"""
     from tissue_image_processing_amd import _lib
-    c = _random(*EPILOGUE_CASE)
+    c = random_case(*EPILOGUE_CASE)
     big = c["scale"] * (2.0 * 4094 / float(c["ref"]["out"].abs().max()))
     assert float((ul.reference(c["a0"], c["a1"], c["taps"], c["dy"], c["dx"], c["bias"], big, c["shift"])["out"]).abs().max()) > 4094 * 1.5
     with _lib.tuning(**T16):

@@ -9,15 +9,14 @@ the second input from chunk 8 on, at a chunk boundary inside the loop; (6, 272, 
 in the activation buffer it began in); (6, 272, 16): a first input of an odd chunk count and a second input of one chunk;
 (6, 240, 0), one chunk below the threshold, keeps flavour 2.
 
-EXACT data (inputs multiples of 1/16 in [0, 4), weights signed powers of two in [2^-3, 1]: every product is a multiple of 2^-7 and
-every partial sum stays below 6 x 288 x 4 < 2^13, 20 significant bits): the raw float32 sum must EQUAL float64 -- no tolerance.
-RANDOM data: the per-layer bounds of the existing layer tests (unet_layers.TOL) on the tensor, its borders and every tile seam."""
-import functools
-
+EXACT data (unet_layers.exact_case, which asserts its construction: inputs multiples of 1/16 in [0, 4), weights signed powers of two
+in [2^-3, 1], every product a multiple of 2^-7 and every sum below 2^9): the raw float32 sum must EQUAL float64 -- no tolerance.
+RANDOM data (unet_layers.random_case): the per-layer bounds of the existing layer tests (unet_layers.TOL) on the tensor, its borders
+and every tile seam."""
 import pytest
 
 import unet_layers as ul
-from unet_layers import MODES, _assert_regions, _join
+from unet_layers import MODES, _assert_regions, _join, bits, exact_case, random_case, run_case
 
 pytestmark = pytest.mark.gpu
 
@@ -28,44 +27,6 @@ PARAMS = [pytest.param(t, c0, c1, code, mode, id="%dtaps-%d+%d-flavour%d-%s" % (
           for t, c0, c1, code in CASES for mode in ("f16x3", "bf16x3")]
 
 
-@functools.lru_cache(maxsize=None)
-def _exact(ntaps, c0, c1, h, w):
-    import torch
-    g = torch.Generator().manual_seed(5000 * ntaps + c0 + 7 * c1 + h * w)
-    dy, dx = ul.tap_offsets(ntaps)
-    cin = c0 + c1
-    a0 = torch.randint(0, 64, (h, w, c0), generator=g).float() / 16
-    a1 = torch.randint(0, 64, (h, w, c1), generator=g).float() / 16 if c1 else None
-    taps = 2.0 ** -torch.randint(0, 4, (ntaps, cin, COUT), generator=g).float() * (torch.randint(0, 2, (ntaps, cin, COUT), generator=g).float() * 2 - 1)
-    seed = torch.randint(-1024, 1024, (h, w, COUT), generator=g).float() / 128
-    ref = ul.reference(a0, a1, taps, dy, dx)["sum"]
-    seeded = ul.reference(a0, a1, taps, dy, dx, seed=seed)["sum"]
-    assert torch.equal(ref.float().double(), ref) and torch.equal(seeded.float().double(), seeded)
-    return dict(a0=a0, a1=a1, taps=taps, dy=dy, dx=dx, seed=seed, ref=ref, seeded=seeded)
-
-
-@functools.lru_cache(maxsize=None)
-def _random(ntaps, c0, c1, h, w):
-    import torch
-    g = torch.Generator().manual_seed(6000 * ntaps + c0 + 7 * c1 + h * w)
-    dy, dx = ul.tap_offsets(ntaps)
-    a0 = torch.randn((h, w, c0), generator=g)
-    a1 = torch.randn((h, w, c1), generator=g) if c1 else None
-    taps = torch.randn((ntaps, c0 + c1, COUT), generator=g) * 0.1
-    bias, scale, shift = torch.randn(COUT, generator=g), torch.rand(COUT, generator=g) + 0.5, torch.randn(COUT, generator=g)
-    ref = ul.reference(a0, a1, taps, dy, dx, bias, scale, shift)
-    return dict(a0=a0, a1=a1, taps=taps, dy=dy, dx=dx, bias=bias, scale=scale, shift=shift, ref=ref)
-
-
-def _layer(mode, code, c, **kw):
-    return ul.run_layer(mode, c["a0"], c["a1"], c["taps"], c["dy"], c["dx"], code, **kw)
-
-
-def _bits(t):
-    import torch
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
 @pytest.mark.parametrize("h,w", [(32, 64), (32, 128)])
 @pytest.mark.parametrize("ntaps,c0,c1,code,mode", PARAMS)
 def test_exact_data_equal_float64(ntaps, c0, c1, code, mode, h, w):
@@ -73,17 +34,17 @@ def test_exact_data_equal_float64(ntaps, c0, c1, code, mode, h, w):
     off and with one step per barrier (TIP_UNET_SPB=1: flavour 2, the schedule these launches ran on before)"""
     import torch
     from tissue_image_processing_amd import _lib
-    c = _exact(ntaps, c0, c1, h, w)
-    raw = _layer(mode, code, c, raw=True)["raw"]
-    again = _layer(mode, code, c, raw=True)["raw"]
-    seeded = _layer(mode, code, c, raw=True, seed=c["seed"])["raw"]
+    c = exact_case(ntaps, c0, c1, COUT, h, w)
+    raw = run_case(mode, code, c, raw=True)["raw"]
+    again = run_case(mode, code, c, raw=True)["raw"]
+    seeded = run_case(mode, code, c, raw=True, seed=c["seed"])["raw"]
     with _lib.tuning(TIP_UNET_XCD_MAP="0"):
-        plain = _layer(mode, code, c, raw=True)["raw"]
+        plain = run_case(mode, code, c, raw=True)["raw"]
     with _lib.tuning(TIP_UNET_SPB="1"):
-        one = _layer(mode, 2, c, raw=True)["raw"]
-    wrong = raw.double() != c["ref"]
+        one = run_case(mode, 2, c, raw=True)["raw"]
+    wrong = raw.double() != c["ref"]["sum"]
     assert not bool(wrong.any()), "raw output differs from float64 at (y, x, channel) %s ..." % wrong.nonzero()[:4].tolist()
-    assert torch.equal(_bits(again), _bits(raw)) and torch.equal(_bits(plain), _bits(raw)) and torch.equal(_bits(one), _bits(raw))
+    assert torch.equal(bits(again), bits(raw)) and torch.equal(bits(plain), bits(raw)) and torch.equal(bits(one), bits(raw))
     assert torch.equal(seeded.double(), c["seeded"])
 
 
@@ -93,12 +54,12 @@ def test_random_data_within_layer_bounds(ntaps, c0, c1, code, mode):
     are those of the one-step schedule bit for bit (the same products in the same order per accumulator)"""
     import torch
     from tissue_image_processing_amd import _lib
-    c = _random(ntaps, c0, c1, 32, 64)
-    res = _layer(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])
+    c = random_case(ntaps, c0, c1, COUT)
+    res = run_case(mode, code, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])
     with _lib.tuning(TIP_UNET_SPB="1"):
-        one = _layer(mode, 2, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])
+        one = run_case(mode, 2, c, bias=c["bias"], scale=c["scale"], shift=c["shift"])
     assert res.get("status", 0) == 0
-    assert torch.equal(_bits(res["out"]), _bits(one["out"]))
+    assert torch.equal(bits(res["out"]), bits(one["out"]))
     got = _join(res["out"], MODES[mode][1]).double()
     what = "flavour %d, %d taps %d+%d" % (code, ntaps, c0, c1)
     _assert_regions(mode, what, got, c["ref"]["out"], REGIONS)

@@ -1,7 +1,10 @@
-"""Shared by the layer-level U-Net tests (test_gpu_unet_conv.py, test_gpu_unet_compose.py, test_gpu_unet_flavours.py): the piece
-formats on the host, the per-layer error bounds, one launcher for tip_unet_conv_dev that names the kernel flavour it means to run and
-fences every output with sentinels, and the float64 evaluation of the same stencil on the unsplit values."""
+"""Shared by the layer-level U-Net tests (test_gpu_unet_conv.py, test_gpu_unet_compose.py, test_gpu_unet_flavours.py,
+test_gpu_unet_six_taps.py, test_gpu_unet_mfma16.py, test_unet_plan_host.py): the piece formats on the host, the per-layer error
+bounds, one launcher for tip_unet_conv_dev that names the kernel flavour it means to run and fences every output with sentinels, the
+float64 evaluation of the same stencil on the unsplit values, and the EXACT and RANDOM cases of the one-launch tests (exact_case,
+random_case: cached, so every test file of a process draws a case once; run_case, bits)."""
 import ctypes
+import functools
 import math
 
 MODES = {"f16x3": (2, 1), "bf16x3": (2, 0), "bf16x6": (3, 0)}     # mode -> (planes, piece format)
@@ -237,3 +240,57 @@ def reference(a0, a1, taps, dy, dx, bias=None, scale=None, shift=None, seed=None
             z = (o @ head[0].double().t() + head[1].double()).permute(2, 0, 1)
             r["logits"], r["head"] = z, torch.softmax(z, 0)
     return r
+
+
+# ---- the cases of the one-launch tests (test_gpu_unet_flavours.py has the argument for the two kinds of data) -----------------------
+
+REGIONS = ["all", "interior", "first row", "last row", "first column", "last column", "top-left corner", "top-right corner",
+           "bottom-left corner", "bottom-right corner"]
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(ntaps, c0, c1, cout=256, h=32, w=64):
+    """exact data of one case and its float64 results (shared by the tests; never modified)"""
+    import torch
+    g = torch.Generator().manual_seed(1000 * ntaps + c0 + 7 * c1 + cout + h * w)
+    dy, dx = tap_offsets(ntaps)
+    a0 = torch.randint(0, 64, (h, w, c0), generator=g).float() / 16
+    a1 = torch.randint(0, 64, (h, w, c1), generator=g).float() / 16 if c1 else None
+    taps = 2.0 ** -torch.randint(0, 4, (ntaps, c0 + c1, cout), generator=g).float() * (torch.randint(0, 2, (ntaps, c0 + c1, cout), generator=g).float() * 2 - 1)
+    bias = torch.randint(-64, 64, (cout,), generator=g).float() / 16
+    scale = 2.0 ** torch.randint(-1, 2, (cout,), generator=g).float()
+    shift = torch.randint(-64, 64, (cout,), generator=g).float() / 16
+    seed = torch.randint(-1024, 1024, (h, w, cout), generator=g).float() / 128
+    ref = reference(a0, a1, taps, dy, dx, bias, scale, shift)
+    seeded = reference(a0, a1, taps, dy, dx, seed=seed)["sum"]
+    # the construction: every sum, seeded or not, is a float32 (a multiple of 2^-7 below 2^9 + 8), and so is the BatchNorm output
+    for t in (ref["sum"], seeded, ref["out"]):
+        assert torch.equal(t.float().double(), t)
+    assert float(ref["sum"].abs().max()) < 512 and float(ref["out"].abs().max()) < 2048
+    return dict(a0=a0, a1=a1, taps=taps, dy=dy, dx=dx, bias=bias, scale=scale, shift=shift, seed=seed, ref=ref, seeded=seeded)
+
+
+@functools.lru_cache(maxsize=None)
+def random_case(ntaps, c0, c1, cout=256, h=32, w=64):
+    """randn data of one case, as test_gpu_unet_conv.py::test_single_layers_against_float64 draws it, and its float64 results"""
+    import torch
+    g = torch.Generator().manual_seed(2000 * ntaps + c0 + 7 * c1 + cout + h * w)
+    dy, dx = tap_offsets(ntaps)
+    a0 = torch.randn((h, w, c0), generator=g)
+    a1 = torch.randn((h, w, c1), generator=g) if c1 else None
+    taps = torch.randn((ntaps, c0 + c1, cout), generator=g) * 0.1
+    bias, scale, shift = torch.randn(cout, generator=g), torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g)
+    hw, hb = torch.randn((2, cout), generator=g) * 0.05, torch.randn(2, generator=g) * 0.1
+    ref = reference(a0, a1, taps, dy, dx, bias, scale, shift, head=(hw, hb) if cout == 128 else None)
+    return dict(a0=a0, a1=a1, taps=taps, dy=dy, dx=dx, bias=bias, scale=scale, shift=shift, hw=hw, hb=hb, ref=ref,
+                ref_bias=ref["sum"] + bias.double())
+
+
+def run_case(mode, code, c, **kw):
+    """run_layer on a case of exact_case / random_case"""
+    return run_layer(mode, c["a0"], c["a1"], c["taps"], c["dy"], c["dx"], code, **kw)
+
+
+def bits(t):
+    import torch
+    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)

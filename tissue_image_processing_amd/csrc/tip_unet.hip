@@ -1,5 +1,7 @@
 // tip_unet.hip -- the U-Net's layers: the launchers of the hand-written kernels on split planes (tip_unet_conv.h, tip_unet_first.h,
-// tip_unet_planes.h), the table of the convolution's flavours, the fp16 pieces' range word, and the torch path's epilogue.
+// tip_unet_planes.h), the convolutions' launch table (per flavour code: kernel, threads and LDS size of everything that can be launched,
+// taken from the kernels' own layout constants) and the one function that picks from it, the fp16 pieces' range word, and the torch
+// path's epilogue.
 //
 // The torch path (the convolutions left to PyTorch-ROCm / MIOpen): epilogue of the U-Net's convolutions (pl.py:31-37: Conv2D + bias
 // -> ReLU -> BatchNormalization at inference = per-channel scale and shift), fused into ONE in-place pass over the NHWC activation.
@@ -47,30 +49,49 @@ static int with_pieces(int planes, int format, Fn &&f)
 }
 static bool pieces_ok(int planes, int format) { return with_pieces(planes, format, [](auto, auto) { return TIP_OK; }) == TIP_OK; }
 
-// The flavours of k_unet_conv: the code tip_unet_conv_flavour returns (include/tissue_hip.h tabulates them), the template shape
-// <pieces, tile rows, weight steps ahead, activation chunks ahead, steps per barrier> and its kernel for either piece format
-// (fp16 pieces come in two planes only).
+// The launch table of the convolutions.  A row: the code tip_unet_conv_flavour returns (include/tissue_hip.h tabulates them), the
+// template shape <pieces, tile rows, weight steps ahead, activation chunks ahead, steps per barrier> of k_unet_conv, and what can be
+// LAUNCHED for the code -- kernel, threads per workgroup, dynamic LDS bytes -- with bf16 pieces, with fp16 pieces, and with fp16
+// pieces on 16x16x32 MFMAs (k_unet_conv_k32 in the shape's place: 16-row tiles with the four-step weight schedule, codes 2 and 6).
+// kernel == nullptr: there is none (fp16 pieces come in two planes only).  Threads and LDS bytes are the kernels' own constants
+// (UcLayout, UK_THREADS / UK_LDS): nothing about a launch is computed a second time.
 typedef void (*ConvKernel)(const ConvParams);
+struct ConvLaunch {
+    ConvKernel kernel;
+    int threads, lds;
+};
+enum { CONV_BF16, CONV_F16, CONV_F16_K32, N_CONV_LAUNCHES };
 struct ConvFlavour {
     int code, npl, th, d, da, spb;
-    ConvKernel bf16, f16;
+    ConvLaunch launch[N_CONV_LAUNCHES];
 };
+constexpr int CONV_LDS_MAX = 160 * 1024;       // a CU's LDS
+template <int NPL, int TH, int D, int DA, int SPB, bool F16>
+constexpr ConvLaunch conv_launch()
+{
+    using L = UcLayout<NPL, TH, D, DA, SPB>;
+    static_assert(L::LDS <= CONV_LDS_MAX, "the tile buffers fit a CU's LDS");
+    return {k_unet_conv<NPL, TH, D, DA, SPB, F16>, L::THREADS, L::LDS};
+}
+static_assert(UK_LDS <= CONV_LDS_MAX, "the tile buffers fit a CU's LDS");
 template <int CODE, int NPL, int TH, int D, int DA = 1, int SPB = 1>
 constexpr ConvFlavour conv_flavour()
 {
-    ConvKernel f16 = nullptr;
-    if constexpr (NPL == 2) f16 = k_unet_conv<NPL, TH, D, DA, SPB, true>;
-    return {CODE, NPL, TH, D, DA, SPB, k_unet_conv<NPL, TH, D, DA, SPB, false>, f16};
+    ConvLaunch f16 = {nullptr, 0, 0}, f16_k32 = {nullptr, 0, 0};
+    if constexpr (NPL == 2) f16 = conv_launch<NPL, TH, D, DA, SPB, true>();
+    if constexpr (NPL == 2 && TH == 16 && D == 4) f16_k32 = {k_unet_conv_k32, UK_THREADS, UK_LDS};
+    return {CODE, NPL, TH, D, DA, SPB, {conv_launch<NPL, TH, D, DA, SPB, false>(), f16, f16_k32}};
 }
-constexpr ConvFlavour CONV_FLAVOURS[] = {
-    conv_flavour<0, 2, 8, 2>(),              // 8-row tiles (two workgroups per CU)
-    conv_flavour<1, 2, 16, 2>(),             // 16-row tiles, three taps
-    conv_flavour<2, 2, 16, 4>(),             // ... four and more taps, one step per barrier
-    conv_flavour<3, 3, 8, 2>(),              // three pieces
-    conv_flavour<4, 2, 16, 2, 2>(),          // ... one and two taps
-    conv_flavour<6, 2, 16, 4, 1, 3>(),       // ... 3x3 stencils, three steps per barrier
+constexpr ConvFlavour CONV_FLAVOURS[] = {      //                                                     LDS bytes (K = 32: 131 072)
+    conv_flavour<0, 2, 8, 2>(),                // 8-row tiles (two workgroups per CU)                    73 728
+    conv_flavour<1, 2, 16, 2>(),               // 16-row tiles, three taps                              106 496
+    conv_flavour<2, 2, 16, 4>(),               // ... four and more taps, one step per barrier          122 880
+    conv_flavour<3, 3, 8, 2>(),                // three pieces                                          110 592
+    conv_flavour<4, 2, 16, 2, 2>(),            // ... one and two taps                                  147 456
+    conv_flavour<6, 2, 16, 4, 1, 3>(),         // ... 3x3 stencils, three steps per barrier             155 648
 };
 constexpr int N_CONV_FLAVOURS = sizeof(CONV_FLAVOURS) / sizeof(CONV_FLAVOURS[0]);
+static_assert(N_CONV_FLAVOURS * N_CONV_LAUNCHES <= 32, "one bit per table entry in the attribute's once-flag");
 
 }  // namespace tip
 
@@ -120,12 +141,13 @@ static unsigned *unet_status_word(Ctx &c, hipStream_t s)
     return w;
 }
 
-// The flavour of k_unet_conv a descriptor's launch runs, and everything else that follows from the descriptor and the tuning alone.
+// What a descriptor's launch runs, and everything else that follows from the descriptor and the tuning alone.
 struct ConvPlan {
-    int row;                       // index into CONV_FLAVOURS
-    int ntiles, nblks, xcd_map;
-    size_t lds;
+    const ConvFlavour *fl;         // the row of CONV_FLAVOURS: code and shape
+    ConvLaunch launch;             // ... and the entry of it that is launched
+    int entry;                     // the entry's position in the table (the bit of the attribute's once-flag)
     int mfma_k;                    // 16: the flavour's own kernel (32x32x16 MFMAs); 32: k_unet_conv_k32 in its place (16x16x32, tip_unet_conv_k32.h)
+    int ntiles, nblks, xcd_map;
 };
 
 // Validates the descriptor and chooses the flavour: TIP_OK and `pl`, or the error tip_unet_conv_dev returns.  Touches no device.
@@ -165,25 +187,24 @@ static int unet_conv_plan(const tip_unet_conv_desc *d, ConvPlan &pl)
     const int th = (d->planes == 2 && d->h % 16 == 0 && !want8) ? 16 : 8;
     const int dist = (th == 16 && d->ntaps >= 4) ? 4 : 2;
     const int da = (th == 16 && d->ntaps <= 2) ? 2 : 1;       // one- and two-tap stencils: activation tiles two chunks ahead
-    const int threads = th * 32, hp = UC_HW * (th + 2);
     pl.ntiles = (d->h / th) * (d->w / UC_TW); pl.nblks = d->cout / UC_BN;
     pl.xcd_map = (tuning().unet_xcd_map && pl.nblks > 1 && pl.ntiles % 8 == 0) ? 1 : 0;
-    const int a_per = (d->planes * ((hp * 2 + 63) / 64) * 64 + threads - 1) / threads;     // (a plane's halo tile padded to whole waves, as in the kernel)
     // three steps per barrier: 3x3 stencils on 16-row tiles (a chunk's nine taps in three iterations, nine weight buffers), and the
     // six-tap classes of a composed decoder level (two iterations per chunk) from 256 input channels on -- measured 3.5-6.5 % faster
     // there; shorter six-tap loops were not measured and keep one step per barrier.
     // TIP_UNET_SPB = 1 keeps one step per barrier everywhere, every larger value means three
     const bool three = d->ntaps == 9 || (d->ntaps == 6 && d->c0 + d->c1 >= 256);
     const int spb = (th == 16 && dist == 4 && three && tuning().unet_spb > 1) ? 3 : 1;
-    pl.lds = (size_t)(da + 1) * a_per * threads * 16 + (size_t)(spb > 1 ? 3 * spb : dist + 1) * d->planes * 256 * 16;
     // The MFMA shape is a second property of the launch: the codes below do not change with it.  Two fp16 pieces on 16-row tiles with
     // four and more taps (flavours 2 and 6) run ONE K = 32 kernel, one pair step per barrier, unless TIP_UNET_MFMA=16 -- so
     // TIP_UNET_SPB does not change a bit of what these launches compute.
     pl.mfma_k = (d->format == 1 && d->planes == 2 && th == 16 && dist == 4 && tuning().unet_mfma == 32) ? 32 : 16;
-    if (pl.mfma_k == 32) pl.lds = UK_LDS;
-    for (pl.row = 0; pl.row < N_CONV_FLAVOURS; ++pl.row) {
-        const ConvFlavour &f = CONV_FLAVOURS[pl.row];
-        if (f.npl == d->planes && f.th == th && f.d == dist && f.da == da && f.spb == spb) return TIP_OK;
+    const int which = pl.mfma_k == 32 ? CONV_F16_K32 : d->format == 1 ? CONV_F16 : CONV_BF16;
+    for (int row = 0; row < N_CONV_FLAVOURS; ++row) {
+        const ConvFlavour &f = CONV_FLAVOURS[row];
+        if (f.npl != d->planes || f.th != th || f.d != dist || f.da != da || f.spb != spb || !f.launch[which].kernel) continue;
+        pl.fl = &f; pl.launch = f.launch[which]; pl.entry = row * N_CONV_LAUNCHES + which;
+        return TIP_OK;
     }
     return fail(TIP_ERR_UNSUPPORTED, "tip_unet_conv_dev: no kernel flavour <%d, %d, %d, %d, %d>", d->planes, th, dist, da, spb);
 }
@@ -192,7 +213,7 @@ int tip_unet_conv_flavour(const tip_unet_conv_desc *d)
 {
     ConvPlan pl;
     const int rc = unet_conv_plan(d, pl);
-    return rc ? rc : CONV_FLAVOURS[pl.row].code;
+    return rc ? rc : pl.fl->code;
 }
 
 int tip_unet_conv_mfma_k(const tip_unet_conv_desc *d)
@@ -230,32 +251,29 @@ int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
     p.head_w = d->head_w; p.head_b = d->head_b; p.head_out = d->head_out;
     p.raw_out = d->raw_out; p.seed = d->seed;
     p.xcd_map = pl.xcd_map;
-    const ConvFlavour &fl = CONV_FLAVOURS[pl.row];
-    const ConvKernel kernel = pl.mfma_k == 32 ? k_unet_conv_k32 : d->format == 1 ? fl.f16 : fl.bf16;
-    const int threads = fl.th * 32;
-    const size_t lds = pl.lds;
+    const ConvLaunch &ln = pl.launch;
     const dim3 grid = p.xcd_map ? dim3((unsigned)(pl.ntiles * pl.nblks)) : dim3(pl.ntiles, pl.nblks);
     hipStream_t s = (hipStream_t)stream;
-    // the >64 KB dynamic LDS attribute is set once per (device, kernel): one atomic bit each
+    // the >64 KB dynamic LDS attribute is set once per (device, table entry): one atomic bit each
     static std::atomic<unsigned> attr_done[64];
-    const unsigned bit = pl.mfma_k == 32 ? 1u << 31 : 1u << (2 * pl.row + d->format);
+    const unsigned bit = 1u << pl.entry;
     const int dev = c.device >= 0 && c.device < 64 ? c.device : 0;
     if (!(attr_done[dev].load(std::memory_order_acquire) & bit)) {
-        TIP_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        TIP_HIP(hipFuncSetAttribute((const void *)ln.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ln.lds));
         attr_done[dev].fetch_or(bit, std::memory_order_release);
     }
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, p);
+    hipLaunchKernelGGL(ln.kernel, grid, dim3(ln.threads), (size_t)ln.lds, s, p);
 #ifdef UC_TRACE
     {
         unsigned long long tr[128];
         TIP_HIP(hipStreamSynchronize(s));
         TIP_HIP(hipMemcpy(tr, trace_dev, sizeof tr, hipMemcpyDeviceToHost));
-        for (int k = 0; k < fl.th / 2; ++k) {
+        for (int k = 0; k < pl.fl->th / 2; ++k) {
             const unsigned long long *t = tr + 16 * k;
             const double n = (double)t[4];
             fprintf(stderr, "UC_TRACE th %d spb %d taps %d cin %d cout %d grid %dx%d wave %d simd %d: per STEP (shader clocks; sums over the loop / steps): copies %.0f, products %.0f (first MFMA out after %.0f), "
                             "vmcnt wait %.0f, barrier %.0f, total %.0f; steps %.0f; whole loop %.0f, prologue %.0f, epilogue %.0f clocks\n",
-                    fl.th, fl.spb, d->ntaps, d->c0 + d->c1, d->cout, d->h, d->w, k, (int)((t[7] >> 4) & 3), t[0] / n, t[2] / n, t[1] / n, t[6] / n, (t[3] - t[6]) / n, t[5] / n, n, (double)t[5], (double)t[8], (double)t[9]);
+                    pl.fl->th, pl.fl->spb, d->ntaps, d->c0 + d->c1, d->cout, d->h, d->w, k, (int)((t[7] >> 4) & 3), t[0] / n, t[2] / n, t[1] / n, t[6] / n, (t[3] - t[6]) / n, t[5] / n, n, (double)t[5], (double)t[8], (double)t[9]);
         }
     }
 #endif

@@ -295,14 +295,33 @@ __device__ __forceinline__ void uc_lds_wait(u32x4 &a, u32x4 &b, u32x4 &c)
     asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(N));
 }
 
-// NPL = bf16 pieces per value (2 or 3).
-//
-// LDS image (one dynamic array; 16-byte slots):  two activation buffers of A_SLOTS slots -- slot (plane * 340 + pixel) * 2 + sh --
-// and D + 1 weight buffers of NPL * 256 slots -- slot (plane * 128 + n) * 2 + sh.  A row (one pixel / one output channel) is
+// LDS image (one dynamic array; 16-byte slots):  DA + 1 activation buffers of A_SLOTS slots -- slot (plane * 340 + pixel) * 2 + sh --
+// and NBBUF weight buffers of NPL * 256 slots -- slot (plane * 128 + n) * 2 + sh.  A row (one pixel / one output channel) is
 // 16 bf16 = 32 bytes = two slots; the two halves of row j are stored SWAPPED when bit 3 of j is set (sh = half ^ ((j >> 3) & 1)):
 // the 16-lane groups of ds_read_b128 ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} of consecutive rows, one half each) then hit 16
 // different bank quads with unpadded rows, which is what lets the tiles arrive by asynchronous ... lds copies (a wave's 64 x 16
 // bytes land in 64 consecutive slots; the swizzle is applied to the per-lane SOURCE offset).
+//
+// Declared ONCE, for the kernels (k_unet_conv's names are aliases of these members, k_unet_conv_k32 takes its tiles from
+// UcLayout<2, 16, 4>) and for the launcher (tip_unet.hip: a launch's threads and dynamic LDS size are THREADS and LDS).  The
+// template parameters are k_unet_conv's, described there.
+template <int NPL, int TH, int D, int DA = 1, int SPB = 1>
+struct UcLayout {
+    static constexpr int THREADS = TH * 32, HP = UC_HW * (TH + 2);
+    // a plane's halo tile is padded to whole waves of slots (A_PLANE): one copy instruction of one wave then serves ONE plane, and
+    // the plane picks the buffer resource (scalar) instead of adding a plane stride to the 32-bit per-lane offset
+    static constexpr int A_GPP = (HP * 2 + 63) / 64, A_PLANE = A_GPP * 64;    // wave-groups / slots per plane (20 / 1280 for 16 rows, 11 / 704 for 8)
+    static constexpr int A_PER = (NPL * A_PLANE + THREADS - 1) / THREADS;     // copy instructions per thread and chunk (5 / 6 / 9)
+    static constexpr int A_SLOTS = A_PER * THREADS;                           // padded: every wave issues the same number of copies
+    static constexpr int A_BYTES = A_SLOTS * 16;
+    static constexpr int B_PER = NPL * 256 / THREADS;                         // weight slots per thread (NPL * 256 slots)
+    static_assert(B_PER * THREADS == NPL * 256, "weight slots divide evenly");
+    static constexpr int B_BYTES = NPL * 256 * 16;
+    static constexpr int NBBUF = SPB > 1 ? 3 * SPB : D + 1;                   // weight buffers (see D and SPB below)
+    static constexpr int LDS = (DA + 1) * A_BYTES + NBBUF * B_BYTES;          // the launch's dynamic LDS size
+};
+
+// NPL = bf16 pieces per value (2 or 3).
 //
 // TH = tile rows = 2 per wave: 8 (256 threads, two workgroups per CU) or 16 (512 threads, one per CU).  The weight tile of a step
 // is shared by all the workgroup's waves, so the taller tile halves the weight bytes copied per MFMA -- and the copies are what
@@ -337,18 +356,10 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
     static_assert(DA == 1 || (DA == 2 && D == 2), "two-chunk activation prefetch: with the two-step weight schedule");
     static_assert(SPB == 1 || (SPB == 3 && D == 4 && DA == 1 && TH == 16), "several steps per barrier: the 16-row kernel with the four-step weight schedule");
     constexpr bool PAIR = SPB > 1;
-    constexpr int UC_NBBUF = PAIR ? 3 * SPB : D + 1;
-    constexpr int UC_THREADS = TH * 32, UC_HP = UC_HW * (TH + 2);
     static_assert(TH == 8 || (TH == 16 && NPL == 2), "16-row tiles: two pieces (LDS)");
-    // a plane's halo tile is padded to whole waves of slots (A_PLANE): one copy instruction of one wave then serves ONE plane, and
-    // the plane picks the buffer resource (scalar) instead of adding a plane stride to the 32-bit per-lane offset
-    constexpr int A_GPP = (UC_HP * 2 + 63) / 64, A_PLANE = A_GPP * 64;    // wave-groups / slots per plane (20 / 1280 for 16 rows, 11 / 704 for 8)
-    constexpr int A_PER = (NPL * A_PLANE + UC_THREADS - 1) / UC_THREADS;  // copy instructions per thread and chunk (5 / 6 / 9)
-    constexpr int A_SLOTS = A_PER * UC_THREADS;                           // padded: every wave issues the same number of copies
-    constexpr int A_BYTES = A_SLOTS * 16;
-    constexpr int B_PER = NPL * 256 / UC_THREADS;                         // weight slots per thread (NPL * 256 slots)
-    static_assert(B_PER * UC_THREADS == NPL * 256, "weight slots divide evenly");
-    constexpr int B_BYTES = NPL * 256 * 16;
+    using L = UcLayout<NPL, TH, D, DA, SPB>;         // the LDS image, shared with the launcher
+    constexpr int UC_NBBUF = L::NBBUF, UC_THREADS = L::THREADS, UC_HP = L::HP;
+    constexpr int A_GPP = L::A_GPP, A_PLANE = L::A_PLANE, A_PER = L::A_PER, A_BYTES = L::A_BYTES, B_PER = L::B_PER, B_BYTES = L::B_BYTES;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *sA = smem, *sB = smem + (DA + 1) * A_BYTES;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -683,7 +694,7 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
     // map goes out the same way first (max-then-split equals the pooled split map: the pieces are a monotone function of the value).
     // No barrier in front: every wave reads its last fragments and sees its last copies land BEFORE the final step's barrier, so a
     // wave that is past that barrier may overwrite the tile buffers.
-    static_assert(UC_THREADS / 64 * EP_BYTES <= (DA + 1) * A_BYTES + UC_NBBUF * B_BYTES, "the staging images fit the tile buffers");
+    static_assert(UC_THREADS / 64 * EP_BYTES <= L::LDS, "the staging images fit the tile buffers");
     int pxl = lane & 31, hf = lane >> 5;
     asm volatile("" : "+v"(pxl), "+v"(hf));           // (opaque: nothing of the epilogue's addressing is hoisted into the main loop's registers)
     unsigned char *ep = smem + wave * EP_BYTES;

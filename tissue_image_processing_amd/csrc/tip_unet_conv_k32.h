@@ -78,10 +78,12 @@ __device__ __forceinline__ void uc_lds_wait(u32x4 &a, u32x4 &b, u32x4 &c, u32x4 
     asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "n"(N));
 }
 
-constexpr int UK_THREADS = 512, UK_TH = 16, UK_HP = UC_HW * (UK_TH + 2);
-constexpr int UK_A_GPP = (UK_HP * 2 + 63) / 64, UK_A_PLANE = UK_A_GPP * 64;                 // 20 wave-groups / 1280 slots per plane
-constexpr int UK_A_PER = (2 * UK_A_PLANE + UK_THREADS - 1) / UK_THREADS;                    // 5 copy instructions per thread and chunk
-constexpr int UK_A_BYTES = UK_A_PER * UK_THREADS * 16, UK_B_BYTES = 2 * 256 * 16;           // 40 KB / 8 KB
+// The tiles are those of k_unet_conv<2, 16, 4> (tip_unet_conv.h: UcLayout); the weight ring and with it the LDS size are this kernel's.
+using UkTiles = UcLayout<2, 16, 4>;
+constexpr int UK_THREADS = UkTiles::THREADS, UK_TH = 16, UK_HP = UkTiles::HP;               // 512 threads
+constexpr int UK_A_GPP = UkTiles::A_GPP, UK_A_PLANE = UkTiles::A_PLANE;                     // 20 wave-groups / 1280 slots per plane
+constexpr int UK_A_PER = UkTiles::A_PER;                                                    // 5 copy instructions per thread and chunk
+constexpr int UK_A_BYTES = UkTiles::A_BYTES, UK_B_BYTES = UkTiles::B_BYTES;                 // 40 KB / 8 KB
 constexpr int UK_NB = 6;                                                                    // weight tiles: three pair steps
 constexpr int UK_LDS = 2 * UK_A_BYTES + UK_NB * UK_B_BYTES;                                 // 128 KB
 static_assert(UK_THREADS / 64 * EP_BYTES <= UK_LDS, "the staging images fit the tile buffers");
