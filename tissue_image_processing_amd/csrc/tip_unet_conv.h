@@ -40,6 +40,10 @@
 // correct the edges the cropped transposed convolution makes special, and the convolution itself runs over the skip tensor alone,
 // seeded.  The up-sampled tensor never exists and the 2 / 2 / 1-tap parity launches, the slowest of the pass, are not run.
 // The kernel body has the details next to the code; DESIGN.md 5.7 has the measurements (clock trace, power-limited MFMA ceiling).
+// What k_unet_conv_k32 (tip_unet_conv_k32.h) runs as well stands in front of the kernel, once: the LDS image's sizes (UcLayout), its
+// swizzle (uc_slot) with the compile-time checks of what fills and reads it, the workgroup map (uc_workgroup), the step order
+// (uc_next_step) and the tile copies -- plans, halo window, buffer resources, copy_a / copy_b (UcCopies).  Products, schedules,
+// seed loads and epilogues are each kernel's own: their lane maps differ.
 #pragma once
 #include "tip_internal.h"
 
@@ -75,7 +79,7 @@ struct ConvParams {
 #ifdef UC_TRACE
     unsigned long long *trace;     // diagnostic build: clock sums of block 0 / wave 0 (tools/unet_trace.py)
 #endif
-    int xcd_map;                   // workgroup -> (tile, channel block) mapping, see the kernel
+    int xcd_map;                   // workgroup -> (tile, channel block) mapping, see uc_workgroup
     float acc_scale;               // fp16 pieces: the accumulator is multiplied by this (1 / (activation scale x weight scale), a power of two) before the bias
     uint16_t *pool_out;            // nullptr, or [plane][outH / 2][outW / 2][cout]: MaxPool2D(2) of the output (needs sy = sx = 1)
     float *raw_out;                // nullptr, or float32 [outH][outW][cout]: accumulator x acc_scale through the output mapping, nothing else ("raw output")
@@ -297,17 +301,52 @@ __device__ __forceinline__ void uc_lds_wait(u32x4 &a, u32x4 &b, u32x4 &c)
 
 // LDS image (one dynamic array; 16-byte slots):  DA + 1 activation buffers of A_SLOTS slots -- slot (plane * 340 + pixel) * 2 + sh --
 // and NBBUF weight buffers of NPL * 256 slots -- slot (plane * 128 + n) * 2 + sh.  A row (one pixel / one output channel) is
-// 16 bf16 = 32 bytes = two slots; the two halves of row j are stored SWAPPED when bit 3 of j is set (sh = half ^ ((j >> 3) & 1)):
-// the 16-lane groups of ds_read_b128 ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} of consecutive rows, one half each) then hit 16
-// different bank quads with unpadded rows, which is what lets the tiles arrive by asynchronous ... lds copies (a wave's 64 x 16
-// bytes land in 64 consecutive slots; the swizzle is applied to the per-lane SOURCE offset).
-//
-// Declared ONCE, for the kernels (k_unet_conv's names are aliases of these members, k_unet_conv_k32 takes its tiles from
+// 16 bf16 = 32 bytes = two slots; the two halves of row j are stored SWAPPED when bit 3 of j is set (uc_slot, the one place that
+// says so): the 16-lane groups of ds_read_b128 ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} of consecutive rows, one half each) then
+// hit 16 different bank quads with unpadded rows, which is what lets the tiles arrive by asynchronous ... lds copies (a wave's
+// 64 x 16 bytes land in 64 consecutive slots; the swizzle is applied to the per-lane SOURCE offset: uc_slot_half).
+constexpr int uc_slot(int row, int half) { return row * 2 + (half ^ ((row >> 3) & 1)); }     // 16-byte slot of logical half `half` of row `row`
+constexpr int uc_slot_half(int s) { return uc_slot(s >> 1, s & 1) & 1; }                     // the logical half that stored slot s holds
+// What the kernels rely on, checked where it is declared.  The copies fill slot s with (row s >> 1, uc_slot_half(s)): that is the
+// slot uc_slot gives a reader of that row and half (n = a tile's slots) ...
+constexpr bool uc_copy_fills(int n)
+{
+    for (int s = 0; s < n; ++s)
+        if (uc_slot(s >> 1, uc_slot_half(s)) != s) return false;
+    return true;
+}
+// ... and a read is conflict-free: ds_read_b128 serves a wave in four groups of 16 lanes, {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}
+// and the same + 32 (uc_group_lane(g, i): lane i of group g), and the 16 lanes of a group hit 16 different bank quads (a quad = 16
+// bytes = a slot, 16 of them) whichever row a wave's window starts in.  READ: the kernel's lane -> (row inside the window, half).
+constexpr int uc_group_lane(int g, int i) { return (g & 1 ? (i < 8 ? 4 + i : i < 12 ? 8 + i : 16 + i) : (i < 4 ? i : i < 8 ? 8 + i : 12 + i)) + 32 * (g >> 1); }
+static_assert(uc_group_lane(0, 0) == 0 && uc_group_lane(0, 4) == 12 && uc_group_lane(0, 8) == 20 && uc_group_lane(1, 0) == 4 && uc_group_lane(1, 8) == 16 && uc_group_lane(1, 12) == 28, "lane groups");
+template <typename READ>
+constexpr bool uc_conflict_free()
+{
+    for (int align = 0; align < 64; ++align)
+        for (int g = 0; g < 4; ++g) {
+            unsigned seen = 0;
+            for (int i = 0; i < 16; ++i) {
+                const int lane = uc_group_lane(g, i), quad = uc_slot(align + READ::row(lane), READ::half(lane)) & 15;
+                if (seen & (1u << quad)) return false;
+                seen |= 1u << quad;
+            }
+        }
+    return true;
+}
+struct UcRead32 {                             // k_unet_conv, both operands of the 32x32x16 MFMAs: 32 consecutive rows, a half per half-wave
+    static constexpr int row(int lane) { return lane & 31; }
+    static constexpr int half(int lane) { return lane >> 5; }
+};
+static_assert(uc_conflict_free<UcRead32>(), "16 different bank quads per lane group of ds_read_b128, at every alignment");
+static_assert(uc_copy_fills(256), "weight tile: slot q of a plane holds what a reader of row q >> 1 expects");
+
+// The image's sizes, declared ONCE, for the kernels (k_unet_conv's names are aliases of these members, k_unet_conv_k32 takes its tiles from
 // UcLayout<2, 16, 4>) and for the launcher (tip_unet.hip: a launch's threads and dynamic LDS size are THREADS and LDS).  The
 // template parameters are k_unet_conv's, described there.
 template <int NPL, int TH, int D, int DA = 1, int SPB = 1>
 struct UcLayout {
-    static constexpr int THREADS = TH * 32, HP = UC_HW * (TH + 2);
+    static constexpr int ROWS = TH, THREADS = TH * 32, HP = UC_HW * (TH + 2);
     // a plane's halo tile is padded to whole waves of slots (A_PLANE): one copy instruction of one wave then serves ONE plane, and
     // the plane picks the buffer resource (scalar) instead of adding a plane stride to the 32-bit per-lane offset
     static constexpr int A_GPP = (HP * 2 + 63) / 64, A_PLANE = A_GPP * 64;    // wave-groups / slots per plane (20 / 1280 for 16 rows, 11 / 704 for 8)
@@ -319,7 +358,116 @@ struct UcLayout {
     static constexpr int B_BYTES = NPL * 256 * 16;
     static constexpr int NBBUF = SPB > 1 ? 3 * SPB : D + 1;                   // weight buffers (see D and SPB below)
     static constexpr int LDS = (DA + 1) * A_BYTES + NBBUF * B_BYTES;          // the launch's dynamic LDS size
+    static_assert(A_PLANE >= 2 * HP && A_PER * THREADS >= NPL * A_PLANE, "every plane's halo tile has its slots, every slot its copy");
+    static_assert(uc_copy_fills(2 * HP), "activation tile: slot rem of a plane holds what a reader of pixel rem >> 1 expects");
 };
+
+// Workgroup -> (pixel tile, block of 128 output channels).  Plain order: grid (tiles, blocks) -- every workgroup in flight works
+// on the SAME channel block (its weights stay in L2) but the input is streamed from HBM once per block (up to eight times).
+// XCD order (p.xcd_map; 1-D grid of tiles x blocks, tiles % 8 == 0): the hardware deals workgroup b to XCD b % 8, so with
+// j = b / 8 the workgroups j = 0 .. nblks - 1 of one XCD are the channel blocks of ONE pixel tile: they run side by side and
+// the tile's activations come out of that XCD's L2 for all but the first of them; the weights of all blocks then stream through
+// each L2 from the memory-side cache (a layer's packed weights are at most 38 MB).
+struct UcWorkgroup { int tile, nblk; };
+__device__ __forceinline__ UcWorkgroup uc_workgroup(const ConvParams &p)
+{
+    if (p.xcd_map) {
+        const int nblks = p.cout / UC_BN, b = blockIdx.x, xcd = b & 7, j = b >> 3;
+        return {(j / nblks) * 8 + xcd, j - (j / nblks) * nblks};
+    }
+    return {(int)blockIdx.x, (int)blockIdx.y};
+}
+// (chunk c, tap t) -> the next step of the linear step order
+__device__ __forceinline__ void uc_next_step(int &c, int &t, int ntaps) { if (++t == ntaps) { t = 0; ++c; } }
+
+#if defined(__HIP_DEVICE_COMPILE__)       // (the buffer-resource builtins exist in the device pass only)
+// ---- the tile copies of k_unet_conv and k_unet_conv_k32: plans (fixed per thread) and the copies themselves ---------------------
+// The tiles arrive by buffer_load_dwordx4 ... lds: a buffer resource (scalar registers: base, extent) + a per-lane byte offset
+// that is FIXED for the whole kernel + a scalar offset that moves with the chunk / step.  A step's copies are then a handful of
+// scalar instructions and the copy itself -- no vector arithmetic: clock counters inside the kernel (tools/unet_trace.sh)
+// showed every step opening with ~210 clocks of copy addressing in all waves, during which the matrix pipe had nothing to
+// issue, and vector instructions of one wave also delay its SIMD partner's MFMAs.  Halo pixels outside the image (and the
+// padding slots) carry an offset beyond the resource's extent: the hardware's range check returns zeros for them.
+// L: the kernel's UcLayout; sA / sB: its activation / weight buffers; wave: a readfirstlane SCALAR (the LDS bases of the copies go
+// to M0 without a waterfall loop); (ty0, tx0): the tile's first pixel; nblk: its channel block.
+template <int NPL, typename L>
+struct UcCopies {
+    static constexpr int RSRC_FLAGS = 0x00020000;       // raw buffer, 32-bit data format (gfx9 resource word 3)
+    const ConvParams &p;
+    unsigned char *const sA, *const sB;
+    const int lane, wave, ty0, tx0, nblk, nchunks, nblks;
+    const int rowbase, winrows;          // the halo window: its first image row, and its rows inside the image
+    unsigned a_off[L::A_PER];            // (only ever indexed by unrolled constants: registers)
+    bool a_second = false;               // the offsets are those of in1 (they depend on the channel count)
+    // the window's start in plane 0 of the CURRENT input, its plane stride and extent: scalars that switch once, when the chunks reach
+    // the second input (one copy path -- two branches with their own pointers made the compiler build a scratch table of them; no
+    // arrays either: a private array of pointers would live in scratch).  A copy instruction's plane follows from (u, wave), and
+    // its resource words are put together at the copy -- a few scalar moves.
+    unsigned long long a_win, a_plane_bytes;
+    int a_rec;
+    const __amdgpu_buffer_rsrc_t rs_b;   // the layer's packed weights
+    const unsigned b_off;                // weight slot q = u * THREADS + tid = (plane q / 256, n = (q % 256) / 2, stored half q & 1): byte offset inside the step's tile
+
+    __device__ __forceinline__ UcCopies(const ConvParams &p_, unsigned char *sA_, unsigned char *sB_, int tid, int wave_, int ty0_, int tx0_, int nblk_)
+        : p(p_), sA(sA_), sB(sB_), lane(tid & 63), wave(wave_), ty0(ty0_), tx0(tx0_), nblk(nblk_), nchunks((p_.c0 + p_.c1) / UC_KC),
+          nblks(p_.cout / UC_BN), rowbase(ty0_ > 0 ? ty0_ - 1 : 0), winrows(min(p_.H, ty0_ + L::ROWS + 1) - rowbase),
+          a_win((unsigned long long)(p_.in0 + (long)rowbase * p_.W * p_.c0)), a_plane_bytes((unsigned long long)((long)p_.H * p_.W * p_.c0) * 2),
+          a_rec((int)(unsigned)((long)winrows * p_.W * p_.c0 * 2)),
+          rs_b(__builtin_amdgcn_make_buffer_rsrc((void *)p_.w, 0, (int)0xffffffffu, RSRC_FLAGS)),
+          b_off((unsigned)(((tid >> 8) * (UC_BN * UC_KC) + ((tid & 255) >> 1) * UC_KC + uc_slot_half(tid & 255) * 8) * 2))
+    {
+        plan_a(p.c0);
+    }
+    // activation slot q = u * THREADS + tid = group g = u * (THREADS / 64) + wave (scalar), lane: plane g / A_GPP, slot inside the plane
+    // -> halo pixel, stored half -> image pixel and logical half.  The buffer resource of a copy covers ONE plane's halo WINDOW (the
+    // image rows rowbase .. rowbase + winrows - 1 of the input: <= (TH + 2) W C 2 bytes), so tensors of any size are addressed with
+    // 32-bit offsets relative to the window.  C: the channel count of the input the offsets are for.
+    __device__ __forceinline__ void plan_a(int C)
+    {
+#pragma unroll
+        for (int u = 0; u < L::A_PER; ++u) {
+            const int g = u * (L::THREADS / 64) + wave, pl = g / L::A_GPP;
+            const int rem = (g - pl * L::A_GPP) * 64 + lane, px = rem >> 1, half = uc_slot_half(rem);
+            const int hy = px / UC_HW, hx = px - hy * UC_HW;
+            const int gy = ty0 + hy - 1, gx = tx0 + hx - 1;
+            const bool inside = pl < NPL && rem < L::HP * 2 && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
+            a_off[u] = inside ? (unsigned)((((long)(gy - rowbase) * p.W + gx) * C + half * 8) * 2) : 0xffff0000u;     // (beyond any admissible extent -- the launcher keeps a window below 2^32 - 65536 bytes -- and the step's scalar offset cannot wrap it around)
+        }
+    }
+    // the halo tile of `chunk` into activation buffer `buf`
+    __device__ __forceinline__ void copy_a(int chunk, int buf)
+    {
+        const int cbase = chunk * UC_KC;
+        const bool second = cbase >= p.c0;
+        if (second && !a_second) {          // (once per kernel, and only when a second input exists)
+            a_second = true;
+            a_win = (unsigned long long)(p.in1 + (long)rowbase * p.W * p.c1);
+            a_plane_bytes = (unsigned long long)((long)p.H * p.W * p.c1) * 2;
+            a_rec = (int)(unsigned)((long)winrows * p.W * p.c1 * 2);
+            if (p.c1 != p.c0) plan_a(p.c1);
+        }
+        const int soff = (second ? cbase - p.c0 : cbase) * 2;
+        lds_byte *dst = (lds_byte *)(sA + buf * L::A_BYTES + wave * 64 * 16);
+#pragma unroll
+        for (int u = 0; u < L::A_PER; ++u) {
+            const int pl = min((u * (L::THREADS / 64) + wave) / L::A_GPP, NPL - 1);      // this wave's plane (padding groups: every lane carries the out-of-range offset)
+            const unsigned long long base = a_win + (unsigned long long)pl * a_plane_bytes;
+            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)base), hi = __builtin_amdgcn_readfirstlane((unsigned)(base >> 32));
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(a_rec), RSRC_FLAGS);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst + u * L::THREADS * 16, 16, a_off[u], soff, 0, 0);
+        }
+    }
+    // the weight tile of step (chunk, tap) into weight buffer `buf`
+    __device__ __forceinline__ void copy_b(int chunk, int tap, int buf)
+    {
+        const int soff = ((tap * nchunks + chunk) * nblks + nblk) * (NPL * UC_BN * UC_KC * 2);        // (a layer's packed weights stay below 2 GB)
+        lds_byte *dst = (lds_byte *)(sB + buf * L::B_BYTES + wave * 64 * 16);
+#pragma unroll
+        for (int u = 0; u < L::B_PER; ++u)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, dst + u * L::THREADS * 16, 16, b_off, soff + u * (L::THREADS / 256) * (UC_BN * UC_KC * 2), 0, 0);
+    }
+};
+#endif
 
 // NPL = bf16 pieces per value (2 or 3).
 //
@@ -358,99 +506,18 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
     constexpr bool PAIR = SPB > 1;
     static_assert(TH == 8 || (TH == 16 && NPL == 2), "16-row tiles: two pieces (LDS)");
     using L = UcLayout<NPL, TH, D, DA, SPB>;         // the LDS image, shared with the launcher
-    constexpr int UC_NBBUF = L::NBBUF, UC_THREADS = L::THREADS, UC_HP = L::HP;
-    constexpr int A_GPP = L::A_GPP, A_PLANE = L::A_PLANE, A_PER = L::A_PER, A_BYTES = L::A_BYTES, B_PER = L::B_PER, B_BYTES = L::B_BYTES;
+    constexpr int UC_NBBUF = L::NBBUF, UC_THREADS = L::THREADS;
+    constexpr int A_PLANE = L::A_PLANE, A_PER = L::A_PER, A_BYTES = L::A_BYTES, B_PER = L::B_PER, B_BYTES = L::B_BYTES;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *sA = smem, *sB = smem + (DA + 1) * A_BYTES;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // (scalar: LDS bases of the copies go to M0 without a waterfall loop)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // (scalar: see UcCopies)
     const int tilesX = p.W / UC_TW;
-    const int nblks = p.cout / UC_BN;
-    // Workgroup -> (pixel tile, block of 128 output channels).  Plain order: grid (tiles, blocks) -- every workgroup in flight works
-    // on the SAME channel block (its weights stay in L2) but the input is streamed from HBM once per block (up to eight times).
-    // XCD order (p.xcd_map; 1-D grid of tiles x blocks, tiles % 8 == 0): the hardware deals workgroup b to XCD b % 8, so with
-    // j = b / 8 the workgroups j = 0 .. nblks - 1 of one XCD are the channel blocks of ONE pixel tile: they run side by side and
-    // the tile's activations come out of that XCD's L2 for all but the first of them; the weights of all blocks then stream through
-    // each L2 from the memory-side cache (a layer's packed weights are at most 38 MB).
-    int tile, nblk;
-    if (p.xcd_map) {
-        const int b = blockIdx.x, xcd = b & 7, j = b >> 3;
-        tile = (j / nblks) * 8 + xcd;
-        nblk = j - (j / nblks) * nblks;
-    } else {
-        tile = blockIdx.x;
-        nblk = blockIdx.y;
-    }
-    const int ty0 = (tile / tilesX) * TH, tx0 = (tile % tilesX) * UC_TW;
+    const UcWorkgroup wg = uc_workgroup(p);
+    const int nblk = wg.nblk;
+    const int ty0 = (wg.tile / tilesX) * TH, tx0 = (wg.tile % tilesX) * UC_TW;
     const int cin = p.c0 + p.c1, nchunks = cin / UC_KC, nsteps = nchunks * p.ntaps;
-    const long in_plane0 = (long)p.H * p.W * p.c0, in_plane1 = (long)p.H * p.W * p.c1;
-    const int rowbase = ty0 > 0 ? ty0 - 1 : 0;                // first image row of the halo window
-    const int winrows = min(p.H, ty0 + TH + 1) - rowbase;     // ... and its rows inside the image
-
-    // ---- copy plans (fixed per thread) ------------------------------------------------------------------------------------
-    // The tiles arrive by buffer_load_dwordx4 ... lds: a buffer resource (scalar registers: base, extent) + a per-lane byte offset
-    // that is FIXED for the whole kernel + a scalar offset that moves with the chunk / step.  A step's copies are then a handful of
-    // scalar instructions and the copy itself -- no vector arithmetic: clock counters inside the kernel (tools/unet_trace.sh)
-    // showed every step opening with ~210 clocks of copy addressing in all waves, during which the matrix pipe had nothing to
-    // issue, and vector instructions of one wave also delay its SIMD partner's MFMAs.  Halo pixels outside the image (and the
-    // padding slots) carry an offset beyond the resource's extent: the hardware's range check returns zeros for them.
-    // activation slot q = u * THREADS + tid = group g = u * (THREADS / 64) + wave (scalar), lane: plane g / A_GPP, slot inside the plane
-    // -> halo pixel, stored half -> image pixel and logical half.  The buffer resource of a copy covers ONE plane's halo WINDOW (the
-    // image rows rowbase .. rowbase + winrows - 1 of the input: <= (TH + 2) W C 2 bytes), so tensors of any size are addressed with
-    // 32-bit offsets relative to the window.
-    unsigned a_off[A_PER];
-    auto plan_a = [&](int C) {
-#pragma unroll
-        for (int u = 0; u < A_PER; ++u) {
-            const int g = u * (UC_THREADS / 64) + wave, pl = g / A_GPP;
-            const int rem = (g - pl * A_GPP) * 64 + lane, px = rem >> 1, half = (rem & 1) ^ ((px >> 3) & 1);
-            const int hy = px / UC_HW, hx = px - hy * UC_HW;
-            const int gy = ty0 + hy - 1, gx = tx0 + hx - 1;
-            const bool inside = pl < NPL && rem < UC_HP * 2 && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
-            a_off[u] = inside ? (unsigned)((((long)(gy - rowbase) * p.W + gx) * C + half * 8) * 2) : 0xffff0000u;     // (beyond any admissible extent -- the launcher keeps a window below 2^32 - 65536 bytes -- and the step's scalar offset cannot wrap it around)
-        }
-    };
-    plan_a(p.c0);
-    bool a_second = false;                  // the offsets are those of in1 (they depend on the channel count)
-    constexpr int RSRC_FLAGS = 0x00020000;  // raw buffer, 32-bit data format (gfx9 resource word 3)
-    // the window's start in every plane of in0 / in1 (scalars, no arrays: a private array of pointers would live in scratch); a copy
-    // instruction's plane follows from (u, wave), and its resource words are put together at the copy -- a few scalar moves
-    // the window's start in plane 0 of the CURRENT input, its plane stride and extent: scalars that switch once, when the chunks reach
-    // the second input (one copy path -- two branches with their own pointers made the compiler build a scratch table of them)
-    unsigned long long a_win = (unsigned long long)(p.in0 + (long)rowbase * p.W * p.c0), a_plane_bytes = (unsigned long long)in_plane0 * 2;
-    int a_rec = (int)(unsigned)((long)winrows * p.W * p.c0 * 2);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void *)p.w, 0, (int)0xffffffffu, RSRC_FLAGS);
-    auto copy_a = [&](int chunk, int buf) {
-        const int cbase = chunk * UC_KC;
-        const bool second = cbase >= p.c0;
-        if (second && !a_second) {          // (once per kernel, and only when a second input exists)
-            a_second = true;
-            a_win = (unsigned long long)(p.in1 + (long)rowbase * p.W * p.c1);
-            a_plane_bytes = (unsigned long long)in_plane1 * 2;
-            a_rec = (int)(unsigned)((long)winrows * p.W * p.c1 * 2);
-            if (p.c1 != p.c0) plan_a(p.c1);
-        }
-        const int soff = (second ? cbase - p.c0 : cbase) * 2;
-        lds_byte *dst = (lds_byte *)(sA + buf * A_BYTES + wave * 64 * 16);
-#pragma unroll
-        for (int u = 0; u < A_PER; ++u) {
-            const int pl = min((u * (UC_THREADS / 64) + wave) / A_GPP, NPL - 1);      // this wave's plane (padding groups: every lane carries the out-of-range offset)
-            const unsigned long long base = a_win + (unsigned long long)pl * a_plane_bytes;
-            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)base), hi = __builtin_amdgcn_readfirstlane((unsigned)(base >> 32));
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(a_rec), RSRC_FLAGS);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst + u * UC_THREADS * 16, 16, a_off[u], soff, 0, 0);
-        }
-    };
-    // weight slot q = u * THREADS + tid = (plane q / 256, n = (q % 256) / 2, stored half q & 1)
-    const int bq = tid & 255;
-    const unsigned b_off = (unsigned)(((tid >> 8) * (UC_BN * UC_KC) + (bq >> 1) * UC_KC + (((bq & 1) ^ ((bq >> 4) & 1))) * 8) * 2);   // byte offset inside the step's tile
-    auto copy_b = [&](int chunk, int tap, int buf) {
-        const int soff = ((tap * nchunks + chunk) * nblks + nblk) * (NPL * UC_BN * UC_KC * 2);        // (a layer's packed weights stay below 2 GB)
-        lds_byte *dst = (lds_byte *)(sB + buf * B_BYTES + wave * 64 * 16);
-#pragma unroll
-        for (int u = 0; u < B_PER; ++u)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, dst + u * UC_THREADS * 16, 16, b_off, soff + u * (UC_THREADS / 256) * (UC_BN * UC_KC * 2), 0, 0);
-    };
+    UcCopies<NPL, L> cp(p, sA, sB, tid, wave, ty0, tx0, nblk);       // the tile copies: plans, resources, copy_a / copy_b
 
     // Accumulators: D = W^T X^T -- the WEIGHT fragment is the matrix core's A operand, so a lane holds ONE pixel (column lane & 31)
     // and sixteen output channels per 32-channel block: register i of half-wave hf is row 8 (i >> 2) + 4 hf + (i & 3), and the packed
@@ -465,9 +532,9 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
             for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.f;
 
     // prologue: activation chunk 0, weight steps 0 .. D-1
-    copy_a(0, 0);
-    if (DA == 2 && nchunks > 1) copy_a(1, 1);
-    for (int s0 = 0; s0 < (PAIR ? 2 * SPB : D) && s0 < nsteps; ++s0) copy_b(s0 / p.ntaps, s0 % p.ntaps, s0);
+    cp.copy_a(0, 0);
+    if (DA == 2 && nchunks > 1) cp.copy_a(1, 1);
+    for (int s0 = 0; s0 < (PAIR ? 2 * SPB : D) && s0 < nsteps; ++s0) cp.copy_b(s0 / p.ntaps, s0 % p.ntaps, s0);
     if (p.seed) {
         // accumulator seed: the lane's 2 x 4 x 16 values of a float32 [H][W][cout] tensor (its pixel's sixteen adjacent channels per
         // 32-channel block: 64 contiguous bytes), in the accumulator's units (1 / acc_scale is a power of two: exact).  The loads go
@@ -489,7 +556,7 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
     uc_wait_barrier<0>();
 
     const int r = lane & 31, h = lane >> 5;
-    const int b_row = r * 2 + (h ^ ((r >> 3) & 1));          // slot of this lane's weight fragment inside a plane's 32 rows
+    const int b_row = uc_slot(r, h);                         // slot of this lane's weight fragment inside a plane's 32 rows
     int step = 0;
     int nc = D / p.ntaps, nt = D % p.ntaps;                  // (chunk, tap) of step + D
     int buf0 = 0, buf2 = D;                                  // weight buffers of steps s and s + D (no division in the loop)
@@ -523,7 +590,7 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             const int px = (wave * 2 + m + 1 + dy) * UC_HW + (r + 1 + dx);
-            aslot[m] = px * 2 + (h ^ ((px >> 3) & 1));
+            aslot[m] = uc_slot(px, h);
         }
         auto read_a = [&](int m, int pl) { fa[m][pl] = *reinterpret_cast<const u32x4 *>(abuf + (pl * A_PLANE + aslot[m]) * 16); };
         auto read_b = [&](int n, int pl) { fb[n][pl] = *reinterpret_cast<const u32x4 *>(bbuf + (pl * 256 + n * 64 + b_row) * 16); };
@@ -551,7 +618,6 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
 #pragma unroll
             for (int n = 0; n < 4; ++n) acc[1][n] = uc_mfma<F16>(fb[n][0], fa[1][1], acc[1][n]);
             __builtin_amdgcn_sched_barrier(0);
-#ifndef UC_TWO_PRODUCTS        // (timing experiment of DESIGN 8: how the kernel's time follows the MFMA count; never part of the product)
             uc_lds_wait<3>(fa[0][0], fa[1][0], fb[0][1]);
             acc[0][0] = uc_mfma<F16>(fb[0][1], fa[0][0], acc[0][0]);
             __builtin_amdgcn_sched_barrier(0);
@@ -565,9 +631,6 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
             acc[0][3] = uc_mfma<F16>(fb[3][1], fa[0][0], acc[0][3]);
 #pragma unroll
             for (int n = 0; n < 4; ++n) acc[1][n] = uc_mfma<F16>(fb[n][1], fa[1][0], acc[1][n]);
-#else
-            uc_lds_wait<0>(fa[0][0], fa[1][0]);
-#endif
             UC_PRODUCT(0, 0)
             __builtin_amdgcn_s_setprio(0);
         } else {
@@ -591,7 +654,6 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
         int cb = (2 * SPB) / p.ntaps, tb = (2 * SPB) % p.ntaps;   // ... and of the next weight copy (2 SPB steps ahead)
         int bb = 0;                                          // weight buffer of the iteration's first step
         int a_issued = 0;                                    // highest chunk whose activations are on their way (chunk 0: prologue)
-        auto next = [&](int &c, int &t) { if (++t == p.ntaps) { t = 0; ++c; } };
         auto wrapb = [](int b) { return b >= UC_NBBUF ? b - UC_NBBUF : b; };
         for (int s = 0; s < nsteps; s += SPB) {
             UC_T(t_a);
@@ -608,9 +670,9 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
             for (int k = 0; k < SPB; ++k) {
                 buf0 = wrapb(bb + k);
                 step_products(c0, t0);
-                next(c0, t0);
-                if (k == 0 && issue_a) copy_a(ca, ca & 1);
-                if (issue_b) { copy_b(cb, tb, wrapb(bb + 2 * SPB + k)); next(cb, tb); }
+                uc_next_step(c0, t0, p.ntaps);
+                if (k == 0 && issue_a) cp.copy_a(ca, ca & 1);
+                if (issue_b) { cp.copy_b(cb, tb, wrapb(bb + 2 * SPB + k)); uc_next_step(cb, tb, p.ntaps); }
             }
             UC_T(t_c);
             // everything older than this iteration's copies has to be there: the weights of the next iteration's steps (issued an
@@ -633,9 +695,9 @@ __global__ void __launch_bounds__(TH * 32, (NPL == 2) ? 2 : 1) k_unet_conv(const
             UC_T(t_b);
             step_products(chunk, tap);
             // (behind the products: a copy blocks its wave at issue while the copy queue is full, see the loop above)
-            if (issue_a) copy_a(chunk + DA, (chunk + DA) % (DA + 1));
-            if (issue_b) copy_b(nc, nt, buf2);
-            if (++nt == p.ntaps) { nt = 0; ++nc; }
+            if (issue_a) cp.copy_a(chunk + DA, (chunk + DA) % (DA + 1));
+            if (issue_b) cp.copy_b(nc, nt, buf2);
+            uc_next_step(nc, nt, p.ntaps);
             UC_T(t_c);
             // Before the barrier the weights of step + 1 must have landed (issued one step ago, before everything issued in
             // this step) and, when the next step opens a new chunk, its activations too.  Issue order inside a step is

@@ -3,6 +3,10 @@
 // shape -- at this kernel's wave tile and LDS traffic the 16x16x32 loop runs 12 % faster by wall than the 32x32x16 one
 // (tools/ubench/mfma_f16_shape_lds.hip).  Everything around the products is tip_unet_conv.h's: the packed weights, the
 // LDS image (32-byte rows with the XOR swizzle, filled by asynchronous copies), the descriptor, the epilogue's five forms.
+// Shared as CODE, not as a copy: the tile layout (UcLayout<2, 16, 4>), the swizzle (uc_slot) and its conflict check
+// (uc_conflict_free, here under this kernel's read pattern), the copy plans and the copies (UcCopies), the workgroup map
+// (uc_workgroup) and the (chunk, tap) stepper (uc_next_step).  This file has what differs: the lane maps, the pair step's products
+// and schedule, the weight ring, and the epilogue and seed loads on this kernel's lane map.
 //
 // The K = 32 pair step.  The instruction contracts 32 K values, a chunk has 16 channels, and a 32-channel chunk does not fit LDS.
 // So K = 32 is formed from two CONSECUTIVE (chunk, tap) steps of the linear step order: lanes 0-31 (K-groups 0 / 1: the two
@@ -30,25 +34,14 @@ namespace tip {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int uk_map16(int i) { return i < 8 ? i : i ^ 4; }                          // stored row / pixel of MFMA row / column i
-constexpr int uk_slot(int row, int half) { return row * 2 + (half ^ ((row >> 3) & 1)); }   // tip_unet_conv.h's swizzle
 // first channel (inside a 32-channel block pair n >> 1, plus 8 (n & 1)) of the four a lane of K-group kq (lane >> 4) holds: MFMA
 // rows 4 kq .. 4 kq + 3 are stored rows 4 kq' .. with kq' = 0, 1, 3, 2, and stored row 8 g + 4 h + j holds channel 16 h + 4 g + j
 constexpr int uk_chan(int kq) { return 16 * ((kq < 2 ? kq : kq ^ 1) & 1) + 4 * ((kq < 2 ? kq : kq ^ 1) >> 1); }
-// ds_read_b128 serves a wave in four groups of 16 lanes: {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32
-constexpr int uk_group_lane(int g, int i) { return (g & 1 ? (i < 8 ? 4 + i : i < 12 ? 8 + i : 16 + i) : (i < 4 ? i : i < 8 ? 8 + i : 12 + i)) + 32 * (g >> 1); }
-constexpr bool uk_conflict_free()
-{
-    for (int align = 0; align < 64; ++align)            // first row / pixel of the 16 consecutive ones, any alignment
-        for (int g = 0; g < 4; ++g) {
-            unsigned seen = 0;
-            for (int i = 0; i < 16; ++i) {
-                const int lane = uk_group_lane(g, i), quad = uk_slot(align + uk_map16(lane & 15), (lane >> 4) & 1) & 15;
-                if (seen & (1u << quad)) return false;
-                seen |= 1u << quad;
-            }
-        }
-    return true;
-}
+struct UkRead16 {                             // both operands: 16 consecutive rows / pixels in uk_map16's order, a half per K-group parity
+    static constexpr int row(int lane) { return uk_map16(lane & 15); }
+    static constexpr int half(int lane) { return (lane >> 4) & 1; }
+};
+constexpr bool uk_conflict_free() { return uc_conflict_free<UkRead16>(); }      // (uc_slot's swizzle under this kernel's read pattern)
 constexpr bool uk_bijective()
 {
     unsigned rows = 0, chans = 0;
@@ -66,7 +59,6 @@ constexpr bool uk_bijective()
 }
 static_assert(uk_bijective(), "the row / pixel map is a permutation and a lane's channels are what the packed rows hold");
 static_assert(uk_conflict_free(), "16 different bank quads per lane group of ds_read_b128, at every alignment");
-static_assert(uk_group_lane(0, 0) == 0 && uk_group_lane(0, 4) == 12 && uk_group_lane(0, 8) == 20 && uk_group_lane(1, 0) == 4 && uk_group_lane(1, 8) == 16 && uk_group_lane(1, 12) == 28, "lane groups");
 
 __device__ __forceinline__ f32x4 uk_mfma(const u32x4 &a, const u32x4 &b, const f32x4 &c)
 {
@@ -80,87 +72,26 @@ __device__ __forceinline__ void uc_lds_wait(u32x4 &a, u32x4 &b, u32x4 &c, u32x4 
 
 // The tiles are those of k_unet_conv<2, 16, 4> (tip_unet_conv.h: UcLayout); the weight ring and with it the LDS size are this kernel's.
 using UkTiles = UcLayout<2, 16, 4>;
-constexpr int UK_THREADS = UkTiles::THREADS, UK_TH = 16, UK_HP = UkTiles::HP;               // 512 threads
-constexpr int UK_A_GPP = UkTiles::A_GPP, UK_A_PLANE = UkTiles::A_PLANE;                     // 20 wave-groups / 1280 slots per plane
-constexpr int UK_A_PER = UkTiles::A_PER;                                                    // 5 copy instructions per thread and chunk
-constexpr int UK_A_BYTES = UkTiles::A_BYTES, UK_B_BYTES = UkTiles::B_BYTES;                 // 40 KB / 8 KB
+constexpr int UK_THREADS = UkTiles::THREADS;                                                // 512 threads
 constexpr int UK_NB = 6;                                                                    // weight tiles: three pair steps
-constexpr int UK_LDS = 2 * UK_A_BYTES + UK_NB * UK_B_BYTES;                                 // 128 KB
+constexpr int UK_LDS = 2 * UkTiles::A_BYTES + UK_NB * UkTiles::B_BYTES;                     // 128 KB: two 40 KB activation buffers, six 8 KB tiles
 static_assert(UK_THREADS / 64 * EP_BYTES <= UK_LDS, "the staging images fit the tile buffers");
-static_assert(2 * 256 == UK_THREADS, "one weight copy instruction per thread and tile");
+static_assert(UkTiles::B_PER == 1, "one weight copy instruction per thread and tile");
 
 __global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParams p)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool F16 = true;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char *sA = smem, *sB = smem + 2 * UK_A_BYTES;
+    unsigned char *sA = smem, *sB = smem + 2 * UkTiles::A_BYTES;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tilesX = p.W / UC_TW;
-    const int nblks = p.cout / UC_BN;
-    int tile, nblk;                                     // workgroup -> (pixel tile, channel block): tip_unet_conv.h
-    if (p.xcd_map) {
-        const int b = blockIdx.x, xcd = b & 7, j = b >> 3;
-        tile = (j / nblks) * 8 + xcd;
-        nblk = j - (j / nblks) * nblks;
-    } else {
-        tile = blockIdx.x;
-        nblk = blockIdx.y;
-    }
-    const int ty0 = (tile / tilesX) * UK_TH, tx0 = (tile % tilesX) * UC_TW;
+    const UcWorkgroup wg = uc_workgroup(p);
+    const int nblk = wg.nblk;
+    const int ty0 = (wg.tile / tilesX) * UkTiles::ROWS, tx0 = (wg.tile % tilesX) * UC_TW;
     const int cin = p.c0 + p.c1, nchunks = cin / UC_KC, nsteps = nchunks * p.ntaps;
-    const long in_plane0 = (long)p.H * p.W * p.c0, in_plane1 = (long)p.H * p.W * p.c1;
-    const int rowbase = ty0 > 0 ? ty0 - 1 : 0;
-    const int winrows = min(p.H, ty0 + UK_TH + 1) - rowbase;
-
-    // ---- copy plans: tip_unet_conv.h's, for 512 threads and two planes ---------------------------------------------------------------
-    unsigned a_off[UK_A_PER];
-    auto plan_a = [&](int C) {
-#pragma unroll
-        for (int u = 0; u < UK_A_PER; ++u) {
-            const int g = u * (UK_THREADS / 64) + wave, pl = g / UK_A_GPP;
-            const int rem = (g - pl * UK_A_GPP) * 64 + lane, px = rem >> 1, half = (rem & 1) ^ ((px >> 3) & 1);
-            const int hy = px / UC_HW, hx = px - hy * UC_HW;
-            const int gy = ty0 + hy - 1, gx = tx0 + hx - 1;
-            const bool inside = pl < 2 && rem < UK_HP * 2 && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
-            a_off[u] = inside ? (unsigned)((((long)(gy - rowbase) * p.W + gx) * C + half * 8) * 2) : 0xffff0000u;
-        }
-    };
-    plan_a(p.c0);
-    bool a_second = false;
-    constexpr int RSRC_FLAGS = 0x00020000;
-    unsigned long long a_win = (unsigned long long)(p.in0 + (long)rowbase * p.W * p.c0), a_plane_bytes = (unsigned long long)in_plane0 * 2;
-    int a_rec = (int)(unsigned)((long)winrows * p.W * p.c0 * 2);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void *)p.w, 0, (int)0xffffffffu, RSRC_FLAGS);
-    auto copy_a = [&](int chunk, int buf) {
-        const int cbase = chunk * UC_KC;
-        const bool second = cbase >= p.c0;
-        if (second && !a_second) {
-            a_second = true;
-            a_win = (unsigned long long)(p.in1 + (long)rowbase * p.W * p.c1);
-            a_plane_bytes = (unsigned long long)in_plane1 * 2;
-            a_rec = (int)(unsigned)((long)winrows * p.W * p.c1 * 2);
-            if (p.c1 != p.c0) plan_a(p.c1);
-        }
-        const int soff = (second ? cbase - p.c0 : cbase) * 2;
-        lds_byte *dst = (lds_byte *)(sA + buf * UK_A_BYTES + wave * 64 * 16);
-#pragma unroll
-        for (int u = 0; u < UK_A_PER; ++u) {
-            const int pl = min((u * (UK_THREADS / 64) + wave) / UK_A_GPP, 1);
-            const unsigned long long base = a_win + (unsigned long long)pl * a_plane_bytes;
-            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)base), hi = __builtin_amdgcn_readfirstlane((unsigned)(base >> 32));
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(a_rec), RSRC_FLAGS);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst + u * UK_THREADS * 16, 16, a_off[u], soff, 0, 0);
-        }
-    };
-    const int bq = tid & 255;
-    const unsigned b_off = (unsigned)(((tid >> 8) * (UC_BN * UC_KC) + (bq >> 1) * UC_KC + (((bq & 1) ^ ((bq >> 4) & 1))) * 8) * 2);
-    auto copy_b = [&](int chunk, int tap, int buf) {     // one instruction per thread: the step's two planes of 128 rows
-        const int soff = ((tap * nchunks + chunk) * nblks + nblk) * (2 * UC_BN * UC_KC * 2);
-        lds_byte *dst = (lds_byte *)(sB + buf * UK_B_BYTES + wave * 64 * 16);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, dst, 16, b_off, soff, 0, 0);
-    };
+    UcCopies<2, UkTiles> cp(p, sA, sB, tid, wave, ty0, tx0, nblk);       // the tile copies (tip_unet_conv.h); one instruction per thread and weight tile
 
     // Accumulators: [pixel group g = 2 (tile row) + (16-pixel half)][16-row block n]; the lane's pixel and channels: see the top
     f32x4 acd[4][8];
@@ -177,10 +108,10 @@ __global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParam
 
     // prologue: activation chunk 0, the weight tiles of pair steps 0 and 1 (a step that does not exist: the last one again -- every
     // wave issues the same number of copies, and nothing reads the tile)
-    copy_a(0, 0);
+    cp.copy_a(0, 0);
     for (int s0 = 0; s0 < 4; ++s0) {
         const int st = min(s0, nsteps - 1);
-        copy_b(st / p.ntaps, st % p.ntaps, s0);
+        cp.copy_b(st / p.ntaps, st % p.ntaps, s0);
     }
     if (p.seed) {
         const float up = 1.f / p.acc_scale;
@@ -197,7 +128,7 @@ __global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParam
     uc_wait_barrier<0>();
 
     const unsigned sA_addr = uc_lds_addr(sA), sB_addr = uc_lds_addr(sB);
-    const unsigned b_lane = (unsigned)(uk_slot(c16, khalf) * 16);
+    const unsigned b_lane = (unsigned)(uc_slot(c16, khalf) * 16);
     u32x4 ga[4][2], gb[8][2];           // [pixel group][piece], [16-row block][piece]
     // products from the smallest magnitude class to the largest, per accumulator: lo x hi, hi x lo, hi x hi (as tip_unet_conv.h)
 #define UK_ROW(N_, PA, PB)                                                                                      \
@@ -209,10 +140,10 @@ __global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParam
         const int dya = p.dy[ta], dxa = p.dx[ta], dyb = p.dy[tb2], dxb = p.dx[tb2];
         const int dyl = odd ? dyb : dya, dxl = odd ? dxb : dxa, cl = odd ? cb2 : ca;
         const int px0 = (wave * 2 + 1 + dyl) * UC_HW + c16 + 1 + dxl, px1 = px0 + UC_HW;
-        const unsigned abase = sA_addr + (unsigned)((cl & 1) * UK_A_BYTES);
-        const unsigned ra0 = abase + (unsigned)(uk_slot(px0, khalf) * 16), ra1 = abase + (unsigned)(uk_slot(px1, khalf) * 16);
-        const unsigned rb = sB_addr + (unsigned)((wbuf + (TAIL ? 0 : odd)) * UK_B_BYTES) + b_lane;
-        constexpr int AP = UK_A_PLANE * 16, BP = 256 * 16, XH = 16 * 32, BN = 16 * 32;     // + 16 pixels / + 16 rows: the same swizzle bit
+        const unsigned abase = sA_addr + (unsigned)((cl & 1) * UkTiles::A_BYTES);
+        const unsigned ra0 = abase + (unsigned)(uc_slot(px0, khalf) * 16), ra1 = abase + (unsigned)(uc_slot(px1, khalf) * 16);
+        const unsigned rb = sB_addr + (unsigned)((wbuf + (TAIL ? 0 : odd)) * UkTiles::B_BYTES) + b_lane;
+        constexpr int AP = UkTiles::A_PLANE * 16, BP = 256 * 16, XH = 16 * 32, BN = 16 * 32;     // + 16 pixels / + 16 rows: the same swizzle bit
         // The eight 16-row blocks go in two halves, so that 64 registers of fragments are live: the four activation fragments of
         // both pieces stay, the weight fragments of a half are read as the registers of the half before fall free.  Reads return in
         // order; W(N, ...) waits until at most N are out (the unpaired last step: for all of them) and ties the fragments it names.
@@ -286,7 +217,6 @@ __global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParam
         int cw = 4 / p.ntaps, tw = 4 % p.ntaps;          // ... and of the next weight copy (two pair steps ahead)
         int pb = 0;                                      // the pair's place in the ring (tiles 2 pb, 2 pb + 1)
         int a_issued = 0;                                // highest chunk whose activations are on their way (chunk 0: prologue)
-        auto next = [&](int &c, int &t) { if (++t == p.ntaps) { t = 0; ++c; } };
         // The workgroup's barrier stands in the MIDDLE of a pair step, not between two: a wave that has issued the pair's last read
         // waits there until its copies of the next pair's tiles have landed (issued a pair step ago), and behind the barrier
         //   * every wave's copies of pair j + 1 have landed, so a wave goes from pair j's last product straight to pair j + 1's
@@ -297,26 +227,26 @@ __global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParam
         // or 1 where it is issued, and the stencils have four taps and more); a_due covers the case that is not.
         for (int s = 0; s + 1 < nsteps; s += 2) {
             int c1 = c0, t1 = t0;
-            next(c1, t1);
+            uc_next_step(c1, t1, p.ntaps);
             const bool issue_a = c0 + 1 < nchunks && c0 + 1 > a_issued;
             const bool a_due = issue_a && t0 + 3 >= p.ntaps;
             const int ca = c0 + 1;
             const bool issue_b = s + 4 < nsteps;
             pair_products(std::false_type{}, c0, t0, c1, t1, 2 * pb, [&]() {
                 asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-                if (issue_a) { a_issued = ca; copy_a(ca, ca & 1); }
+                if (issue_a) { a_issued = ca; cp.copy_a(ca, ca & 1); }
                 if (issue_b) {
                     const int wb = 2 * (pb == 0 ? 2 : pb - 1);       // pair j + 2 takes the place pair j - 1 had
                     const int cw0 = cw, tw0 = tw;
-                    copy_b(cw0, tw0, wb);
-                    next(cw, tw);
-                    if (s + 5 < nsteps) { copy_b(cw, tw, wb + 1); next(cw, tw); }
-                    else copy_b(cw0, tw0, wb + 1);       // (an odd step count: the unpaired step's tile twice, the second one unread)
+                    cp.copy_b(cw0, tw0, wb);
+                    uc_next_step(cw, tw, p.ntaps);
+                    if (s + 5 < nsteps) { cp.copy_b(cw, tw, wb + 1); uc_next_step(cw, tw, p.ntaps); }
+                    else cp.copy_b(cw0, tw0, wb + 1);       // (an odd step count: the unpaired step's tile twice, the second one unread)
                 }
             });
             if (a_due) uc_wait_barrier<0>();
             c0 = c1; t0 = t1;
-            next(c0, t0);
+            uc_next_step(c0, t0, p.ntaps);
             pb = pb == 2 ? 0 : pb + 1;
         }
         // an odd step count: the last step alone, behind the loop (inside it, a second product path makes the compiler spill the
