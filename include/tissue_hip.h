@@ -116,6 +116,8 @@ TIP_API int tip_build_manifold_f32(const float *score, int z, int y, int x, int6
 /* czyx: uint16 (C,Z,Y,X).  [zlo,zhi) is the z slice sp.py:30-31 takes when max_z>0 (else 0,Z).   */
 /* taps: scipy taps for sigma 0.5 (5), 1 (9), 2 (17), 30 (241); pass NULL to have them built with */
 /* libm.  proj: float64 (C,Y,X) (sp.py:74 np.zeros -> float64); zmap: int64 (Y,X) = min_z+argmax. */
+/* ref_ch in [-c, 0) counts from the end like numpy's index, and like the reference (sp.py:76      */
+/* compares the channel number with it) then gives EVERY channel the atoh_shift-ed mask.           */
 TIP_API int tip_project_u16(const uint16_t *czyx, int c, int z, int y, int x, int zlo, int zhi, int min_z,
                             int ref_ch, int airyscan, int atoh_shift,
                             const double *t05, const double *t1, const double *t2, const double *t30,

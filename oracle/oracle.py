@@ -63,6 +63,10 @@ def gaussian_kernel1d(sigma, truncate=4.0):
 def correlate1d(a, weights, axis, mode="nearest", cval=0.0):
     a = np.ascontiguousarray(a)
     assert a.dtype in (np.float32, np.float64)
+    if a.ndim > 3:      # the other extents are independent lines: the (leading, axis, trailing) view of the array
+        axis %= a.ndim
+        lead, trail = int(np.prod(a.shape[:axis], dtype=np.int64)), int(np.prod(a.shape[axis + 1:], dtype=np.int64))
+        return correlate1d(a.reshape(lead, a.shape[axis], trail), weights, 1, mode, cval).reshape(a.shape)
     out = np.empty_like(a)
     shape3 = (1,) * (3 - a.ndim) + a.shape
     dims = (ctypes.c_long * 3)(*shape3)

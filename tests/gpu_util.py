@@ -17,6 +17,106 @@ def taps_patch(monkeypatch, golden_taps):
     monkeypatch.setattr(bim, "_gaussian_kernel1d", patched)
 
 
+def radius_taps(r):
+    """Normalised Gaussian taps of sigma r / 4 cut at +-r (2 r + 1 of them, symmetric): the radius chosen directly, so that
+    a test can sit on either side of a dispatch threshold.  The same array goes to the device and to the oracle."""
+    x = np.arange(-r, r + 1, dtype=np.float64)
+    w = np.exp(-0.5 * (x / (r / 4.0)) ** 2)
+    w /= w.sum()
+    w = 0.5 * (w + w[::-1])             # exactly symmetric whatever the sum's rounding did
+    return np.ascontiguousarray(w)
+
+
+def wide_range_data(rng, shape, dtype):
+    """signed samples over six orders of magnitude: a tap sum in another order rounds differently almost everywhere"""
+    return (rng.standard_normal(shape) * 10.0 ** rng.uniform(-3, 3, shape)).astype(dtype)
+
+
+def nearest_tap_first_sum(vol, taps, axis):
+    """The same correlation ('nearest' edges, float64) summed with d running 1 .. r instead of scipy's r .. 1: what a kernel
+    with the wrong tap order would compute.  A float64 test is only worth its name where this differs from the oracle."""
+    r = taps.size // 2
+    n = vol.shape[axis]
+    idx = np.arange(n)
+
+    def at(i):
+        return np.take(vol, np.clip(i, 0, n - 1), axis=axis)
+
+    tmp = at(idx) * taps[r]
+    for d in range(1, r + 1):
+        tmp = tmp + (at(idx - d) + at(idx + d)) * taps[r - d]
+    return tmp
+
+
+def order_sensitive_share(vol, taps, axis, ref):
+    """share of the elements in which the nearest-tap-first sum differs from the oracle's result `ref`"""
+    return float((nearest_tap_first_sum(vol, taps, axis) != ref).mean())
+
+
+GUARD = 4096       # elements of NaN in front of and behind an array inside its device buffer
+
+
+class GuardedBuffer:
+    """An array's worth of device memory inside a larger allocation filled with NaN, GUARD elements on either side.  A
+    kernel that reads outside its input picks up NaN (and fails the equality); one that writes outside its output changes a
+    band, which bands_untouched() reports."""
+
+    def __init__(self, shape, dtype, data=None):
+        from tissue_image_processing_amd import _lib
+        self.shape, self.dtype = tuple(shape), np.dtype(dtype)
+        self.n = int(np.prod(self.shape))
+        host = np.full(self.n + 2 * GUARD, np.nan, self.dtype)
+        if data is not None:
+            host[GUARD:GUARD + self.n] = np.ascontiguousarray(data, self.dtype).ravel()
+        self.buf = _lib.DeviceBuffer(host.nbytes).upload(host)
+        self.ptr = self.buf.ptr + GUARD * self.dtype.itemsize
+
+    def download(self):
+        """(the array, True if both bands still hold nothing but NaN)"""
+        host = self.buf.download((self.n + 2 * GUARD,), self.dtype)
+        bands_ok = bool(np.isnan(host[:GUARD]).all() and np.isnan(host[GUARD + self.n:]).all())
+        return host[GUARD:GUARD + self.n].reshape(self.shape).copy(), bands_ok
+
+
+def correlate1d_guarded(vol, taps, axis_code):
+    """tip_correlate1d_dev on `vol` (rank 3, float32 / float64) with input and output inside NaN bands; axis_code is the axis,
+    + 100 for the forced generic kernel, + 200 for the forced long kernel.  Returns the output; asserts the bands."""
+    from tissue_image_processing_amd import _lib
+    lib = _lib.lib()
+    Z, Y, X = vol.shape
+    src = GuardedBuffer(vol.shape, vol.dtype, vol)
+    dst = GuardedBuffer(vol.shape, vol.dtype)
+    _lib.check(lib.tip_correlate1d_dev(_lib.dptr(src.ptr), _lib.dptr(dst.ptr), 0 if vol.dtype == np.float32 else 1, Z, Y, X,
+                                       axis_code, _lib.ptr(taps), taps.size))
+    _lib.check(lib.tip_sync())
+    out, bands_ok = dst.download()
+    assert bands_ok, "the kernel wrote outside its output (axis code %d, shape %s, %d taps)" % (axis_code, vol.shape, taps.size)
+    src.buf.free()
+    dst.buf.free()
+    return out
+
+
+class launches:
+    """with launches() as ran: ...   -> ran = {kernel name: launch count} of the library's launches inside the block (its
+    launch profiler, tip_prof_report): which kernels a dispatcher chose, seen from outside."""
+
+    def __enter__(self):
+        from tissue_image_processing_amd import _lib
+        _lib.prof_enable(True)
+        _lib.prof_reset()
+        self.ran = {}
+        return self.ran
+
+    def __exit__(self, *exc):
+        from tissue_image_processing_amd import _lib
+        try:
+            self.ran.update({name: count for name, (count, _) in _lib.prof_report().items()})
+        finally:
+            _lib.prof_reset()
+            _lib.prof_enable(False)
+        return False
+
+
 def integer_segmentation_reference(orc, image, imgthresh, stdeviation, blocksize):
     """What bim.py:446-476 does to an integer image, restated on the oracle (whose blur_image refuses integers): threshold,
     scipy's integer-dtype blur (float64 passes, truncated after every axis), serial flood."""

@@ -15,6 +15,7 @@ from . import _lib
 
 UINT8_MAXVAL = 255
 UINT16_MAXVAL = 65535
+_GRID_MAX = 65535      # the z and y extents of a launch are grid dimensions (correlate1d_dev refuses more)
 
 
 def _gaussian_kernel1d(sigma, radius):
@@ -60,6 +61,10 @@ def blur_image(image, std):
     float32 / float64 arrays of any rank run on the GPU with scipy's exact arithmetic (double accumulation in
     scipy's tap order, rounding to the array dtype after each axis).  Integer images follow scipy's rule
     "output dtype == input dtype": they are filtered in float64 and truncated on store, as scipy's C core does.
+
+    Sizes: any extents that fit host and device memory.  One launch takes at most 65535 planes and 65535 rows (they are
+    grid dimensions); an array with more of either -- a long movie folded into (leading, axis, trailing), a tall table --
+    is filtered axis after axis in launches refolded below that limit (_blur_axis_refolded), with the same bits.
     """
     image = np.asarray(image)
     if image.ndim < 1:
@@ -100,13 +105,62 @@ def blur_image(image, std):
     for ax in range(src.ndim):
         if sig[ax] > 1e-15:
             taps[ax + 3 - src.ndim] = gaussian_taps(sig[ax])
-    out = np.empty_like(src)
-    lib = _lib.lib()
+    vol = src.reshape(shape3)
+    if shape3[0] <= _GRID_MAX and shape3[1] <= _GRID_MAX:
+        return _gaussian3d(vol, taps, dtype).reshape(src.shape)
+    # a longer z or y extent does not fit one launch: axis after axis (the rounding to the array dtype in between is scipy's
+    # too), every pass refolded so that no launch sees more than _GRID_MAX planes or rows
+    cur = vol
+    for ax in range(3):
+        if taps[ax] is not None:
+            cur = _blur_axis_refolded(cur, ax, taps[ax], dtype)
+    return (cur.copy() if cur is vol else cur).reshape(src.shape)
+
+
+def _gaussian3d(vol, taps, dtype):
+    """one tip_gaussian3d_w call on a contiguous (z, y, x) array; taps: per axis, None for an axis that is not filtered"""
+    out = np.empty_like(vol)
     args = []
     for t in taps:
         args += [_lib.ptr(t), 0 if t is None else t.size]
-    _lib.check(lib.tip_gaussian3d_w(_lib.ptr(src), _lib.ptr(out), dtype, shape3[0], shape3[1], shape3[2], *args))
+    _lib.check(_lib.lib().tip_gaussian3d_w(_lib.ptr(vol), _lib.ptr(out), dtype, vol.shape[0], vol.shape[1], vol.shape[2], *args))
     return out
+
+
+def _blur_rows(rows, t, dtype):
+    """the x pass of any number of independent rows: planes of _GRID_MAX rows, and one more launch for the rest"""
+    n_rows, n = rows.shape
+    full = n_rows // _GRID_MAX
+    if full > _GRID_MAX:
+        raise ValueError("blur_image: %d independent lines (at most %d * %d)" % (n_rows, _GRID_MAX, _GRID_MAX))
+    out = np.empty_like(rows)
+    cut = full * _GRID_MAX
+    if full:
+        out[:cut] = _gaussian3d(rows[:cut].reshape(full, _GRID_MAX, n), (None, None, t), dtype).reshape(cut, n)
+    if cut < n_rows:
+        out[cut:] = _gaussian3d(rows[cut:].reshape(1, n_rows - cut, n), (None, None, t), dtype).reshape(n_rows - cut, n)
+    return out
+
+
+def _blur_axis_refolded(vol, ax, t, dtype):
+    """One axis pass of a contiguous rank-3 array as launches of at most _GRID_MAX planes and rows.  The unfiltered extents are
+    independent lines, so the array is the (leading, axis, trailing) view of itself: an x pass of leading rows when nothing
+    trails, else a y pass of trailing-wide rows, a stack of leading planes at a time; a filtered axis that is itself longer
+    than _GRID_MAX (and not the last) is moved to the end on the host, filtered as rows and moved back."""
+    lead = int(np.prod(vol.shape[:ax], dtype=np.int64))
+    n = vol.shape[ax]
+    trail = int(np.prod(vol.shape[ax + 1:], dtype=np.int64))
+    if trail == 1:
+        return _blur_rows(vol.reshape(lead, n), t, dtype).reshape(vol.shape)
+    v = vol.reshape(lead, n, trail)
+    if n > _GRID_MAX:
+        rows = np.ascontiguousarray(v.transpose(0, 2, 1)).reshape(lead * trail, n)
+        back = _blur_rows(rows, t, dtype).reshape(lead, trail, n).transpose(0, 2, 1)
+        return np.ascontiguousarray(back).reshape(vol.shape)
+    out = np.empty_like(v)
+    for a in range(0, lead, _GRID_MAX):
+        out[a:a + _GRID_MAX] = _gaussian3d(v[a:a + _GRID_MAX], (None, t, None), dtype)
+    return out.reshape(vol.shape)
 
 
 def watershed_segmentation(image, imgthresh, stdeviation, blocksize):

@@ -666,6 +666,7 @@ struct ProjJob {
     long P, V;                      // Y * X, Zs * P
     int min_z, ref_ch, method, bin, airyscan, atoh_shift;   // method: without the manifold flag
     bool manifold;                  // sp.py:56-57: the spiral z-map instead of the argmax
+    bool ref_unshifted;             // the reference channel takes the unshifted mask (false: ref_ch was given from the end)
     bool fast;                      // X % 4 == 0 and no TIP_PROJECT_GENERIC: the register-sliding / fused / fp16 kernels
     Taps k05, k1, k2, k30;
     WsGuard ws;                     // a tier takes the buffers only it uses from here
@@ -876,7 +877,8 @@ static int mask_and_project(ProjJob &s)
     const unsigned all = (1u << C) - 1u;
     for (int pass = 0; pass < (s.atoh_shift != 0 ? 2 : 1); ++pass) {
         const int32_t *sel = pass == 0 ? s.zsel : s.zsel_a;
-        const unsigned cm = s.atoh_shift == 0 ? all : (pass == 0 ? (1u << s.ref_ch) : (all & ~(1u << s.ref_ch)));
+        const unsigned refbit = s.ref_unshifted ? (1u << s.ref_ch) : 0u;
+        const unsigned cm = s.atoh_shift == 0 ? all : (pass == 0 ? refbit : (all & ~refbit));
         if (!cm) continue;
         if (fused) {
             rc = C <= 2 ? launch_mask_fused<2>(s, sel, cm) : C <= 4 ? launch_mask_fused<4>(s, sel, cm) : launch_mask_fused<8>(s, sel, cm);
@@ -917,6 +919,10 @@ int project_dev(const uint16_t *czyx, int C, int Z, int Y, int X, int zlo, int z
     if (!s.stream) return TIP_ERR_HIP;
     s.czyx = czyx; s.C = C; s.Z = Z; s.Y = Y; s.X = X; s.zlo = zlo; s.Zs = zhi - zlo;
     s.P = (long)Y * X; s.V = (long)s.Zs * s.P;
+    // ref_ch in [-C, 0) counts from the end, as numpy's image[reference_channel] does (sp.py:32) -- and sp.py:76 then compares
+    // the channel NUMBER with it, which never matches: every channel, the reference included, takes the shifted mask
+    s.ref_unshifted = ref_ch >= 0;
+    if (ref_ch < 0 && C > 0) ref_ch += C;
     s.min_z = min_z; s.ref_ch = ref_ch; s.bin = bin; s.airyscan = airyscan; s.atoh_shift = atoh_shift;
     s.manifold = (method & TIP_PROJECT_MANIFOLD) != 0;
     s.method = method & ~TIP_PROJECT_MANIFOLD;

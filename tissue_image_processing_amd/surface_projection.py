@@ -48,7 +48,8 @@ def time_point_surface_projection(time_point, axes, reference_channel, min_z=0, 
     C, Z, Y, X = image.shape
     if not (-C <= reference_channel < C):
         raise IndexError("index %d is out of bounds for axis 0 with size %d" % (reference_channel, C))
-    reference_channel %= C
+    # (a negative index goes down as it is: upstream reads image[reference_channel] but compares the channel NUMBER with it
+    #  (sp.py:76), so no channel, the reference included, then takes the unshifted mask -- project_dev does the same)
     zlo, zhi = (min_z, min(max_z, Z)) if max_z > 0 else (0, Z)
     if zlo < 0:
         zlo = max(0, Z + zlo)
