@@ -175,7 +175,7 @@ def mods(monkeypatch, golden_taps, oracle_with_golden_taps):
 @pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
 def test_255_taps_in_the_table_257_in_memory(mods, dtype):
     """sigma 31.8 -> r = 127, 255 taps: the last size the kernel-argument table holds; sigma 31.9 -> r = 128, 257 taps: the
-    device-tap kernel k_corr_big.  Both along y (40 < r) and x (300) of a (40, 300) image."""
+    generic kernel with device taps (corr_big).  Both along y (40 < r) and x (300) of a (40, 300) image."""
     bim, orc = mods
     img = wide_range_data(np.random.default_rng(31), (40, 300), dtype)
     assert bim.gaussian_taps(31.8).size == 255 and bim.gaussian_taps(31.9).size == 257
@@ -212,7 +212,7 @@ def test_gaussian3d_ping_pong_axis_subsets(mods, subset, dtype):
 @pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
 @pytest.mark.parametrize("sigma", [(1, 40, 2), (0, 3, 40)], ids=["big_in_the_middle", "big_at_the_end"])
 def test_gaussian3d_ping_pong_with_device_taps(mods, sigma, dtype):
-    """sigma 40 (321 taps) goes through k_corr_big, whose taps take a workspace slice of their own between the ping-pong's
+    """sigma 40 (321 taps) goes through the corr_big launch, whose taps take a workspace slice of their own between the ping-pong's
     passes: in the middle of three passes and at the end of two"""
     bim, orc = mods
     vol = wide_range_data(np.random.default_rng(60), (5, 37, 70), dtype)

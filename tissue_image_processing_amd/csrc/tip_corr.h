@@ -1,14 +1,7 @@
-// tip_corr.h -- exact scipy-order separable correlation kernels (device templates).
-//
-// Arithmetic contract (scipy/ndimage/src/ni_filters.c NI_Correlate1D, symmetric branch; called through
-// gaussian_filter at bim.py:389):
-//     tmp  = x[c] * w[r]
-//     tmp += (x[c-d] + x[c+d]) * w[r-d]      for d = r, r-1, ..., 1      (all in double, no FMA contraction)
-//     out  = (T) tmp
-// with mode='nearest' (index clamp).  The whole library is compiled with -ffp-contract=off so that the
-// multiply and the add round separately, as scipy's x86-64 builds do.
+// tip_corr.h -- exact scipy-order separable correlation kernels (device templates) and the one tap sum they all share.
 #pragma once
 #include "tip_internal.h"
+#include <type_traits>
 
 namespace tip {
 
@@ -21,10 +14,50 @@ struct LoadPlain {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// Generic kernel: one thread per output element, taps read through the cache hierarchy.
+// The arithmetic contract of every exact Gaussian pass (scipy/ndimage/src/ni_filters.c NI_Correlate1D, symmetric branch;
+// called through gaussian_filter at bim.py:389), spelled here and nowhere else:
+//     tmp  = x[c] * w[r]
+//     tmp += (x[c-d] + x[c+d]) * w[r-d]      for d = r, r-1, ..., 1      (all in double, no FMA contraction)
+//     out  = (T) tmp
+// with mode='nearest' (index clamp).  The whole library is compiled with -ffp-contract=off so that the
+// multiply and the add round separately, as scipy's x86-64 builds do.
+// at(j): window sample j = 0 .. 2r as double (centre at r; the clamp and the cast to double are the accessor's);
+// w: anything indexable that yields double.  Compile-time radius: fully unrolled, so ring indices inside at() fold.
+template <int R, typename At, typename W>
+__device__ __forceinline__ double tap_sum(At at, const W &w)
+{
+    double tmp = at(R) * w[R];
+#pragma unroll
+    for (int d = R; d >= 1; --d) tmp += (at(R - d) + at(R + d)) * w[R - d];
+    return tmp;
+}
+template <typename At, typename W>
+__device__ __forceinline__ double tap_sum(int r, At at, const W &w)
+{
+    double tmp = at(r) * w[r];
+    for (int d = r; d >= 1; --d) tmp += (at(r - d) + at(r + d)) * w[r - d];
+    return tmp;
+}
+
+struct TapsDev {   // taps in device memory: any odd, symmetric count, for radii beyond the table of a Taps
+    const double *w;
+    int n;
+};
+
+// run-time axis -> compile-time axis: f(std::integral_constant<int, A>) for A = axis; FIRST = 1 for in-plane-only kernels
+template <int FIRST = 0, typename F>
+static inline int with_axis(int axis, F &&f)
+{
+    if constexpr (FIRST == 0)
+        if (axis == 0) return f(std::integral_constant<int, 0>{});
+    if (axis == 1) return f(std::integral_constant<int, 1>{});
+    return f(std::integral_constant<int, 2>{});
+}
+
+// Generic kernel: one thread per output element, taps (a Taps by value or a TapsDev) read through the cache hierarchy.
 // AXIS: 0 = z, 1 = y, 2 = x of a (Z,Y,X) volume.  Good for short kernels (<= ~25 taps).
-template <typename T, int AXIS, typename Load>
-__global__ void __launch_bounds__(256) k_corr_generic(Load in, T *__restrict__ out, int Z, int Y, int X, Taps taps)
+template <typename T, int AXIS, typename Load, typename TapSrc = Taps>
+__global__ void __launch_bounds__(256) k_corr_generic(Load in, T *__restrict__ out, int Z, int Y, int X, TapSrc taps)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
@@ -33,13 +66,11 @@ __global__ void __launch_bounds__(256) k_corr_generic(Load in, T *__restrict__ o
     const int r = taps.n >> 1;
     const int len = AXIS == 0 ? Z : (AXIS == 1 ? Y : X);
     const int c = AXIS == 0 ? z : (AXIS == 1 ? y : x);
-    auto at = [&](int i) -> double {
-        i = clampi(i, 0, len - 1);
+    auto at = [&](int j) -> double {
+        const int i = clampi(c - r + j, 0, len - 1);
         return AXIS == 0 ? in(i, y, x) : (AXIS == 1 ? in(z, i, x) : in(z, y, i));
     };
-    double tmp = at(c) * taps.w[r];
-    for (int d = r; d >= 1; --d) tmp += (at(c - d) + at(c + d)) * taps.w[r - d];
-    out[((long)z * Y + y) * X + x] = (T)tmp;
+    out[((long)z * Y + y) * X + x] = (T)tap_sum(r, at, taps.w);
 }
 
 // Stage a (positions x 64 lines) float tile into LDS with 'nearest' clamping.  A block owns its CU's LDS alone, so
@@ -124,7 +155,7 @@ __global__ void __launch_bounds__(256) k_corr_long_f32(const float *__restrict__
             Rr[i] = (double)ctr[(i + r) * LS];
         }
 #pragma unroll 8
-        for (int d = r; d >= 1; --d) {
+        for (int d = r; d >= 1; --d) {   // tap_sum's contract for R outputs at once, the window shifts interleaved with the sum
             const double w = taps.w[r - d];
 #pragma unroll
             for (int i = 0; i < R; ++i) acc[i] += (L[i] + Rr[i]) * w;

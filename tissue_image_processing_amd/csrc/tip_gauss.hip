@@ -8,35 +8,31 @@ namespace tip {
 constexpr int LONG_TO = 256;  // outputs per line per block in the long-kernel variant
 constexpr int LONG_R = 8;     // outputs per register window
 
-template <typename T>
-static int corr_generic(const T *in, T *out, int Z, int Y, int X, int axis, const Taps &t)
+// name: the launch-profiler name.  TapSrc: Taps (the table, by value) or TapsDev
+template <typename T, typename TapSrc>
+static int corr_generic(const char *name, const T *in, T *out, int Z, int Y, int X, int axis, const TapSrc &t)
 {
     LoadPlain<T> ld{in, (long)Y * X, (long)X};
-    dim3 grid(cdiv(X, 256), Y, Z), block(256);
-    const bool f64 = sizeof(T) == 8;
-    if (axis == 0) TIP_LAUNCH(f64 ? "corr_generic_z_f64" : "corr_generic_z", (k_corr_generic<T, 0, LoadPlain<T>>), grid, block, 0, ld, out, Z, Y, X, t);
-    else if (axis == 1) TIP_LAUNCH(f64 ? "corr_generic_y_f64" : "corr_generic_y", (k_corr_generic<T, 1, LoadPlain<T>>), grid, block, 0, ld, out, Z, Y, X, t);
-    else TIP_LAUNCH(f64 ? "corr_generic_x_f64" : "corr_generic_x", (k_corr_generic<T, 2, LoadPlain<T>>), grid, block, 0, ld, out, Z, Y, X, t);
-    return TIP_OK;
+    return with_axis(axis, [&](auto A) -> int {
+        TIP_LAUNCH(name, (k_corr_generic<T, decltype(A)::value, LoadPlain<T>, TapSrc>), dim3(cdiv(X, 256), Y, Z), dim3(256), 0, ld, out, Z,
+                   Y, X, t);
+        return TIP_OK;
+    });
 }
+static const char *const GENERIC_NAME[2][3] = {{"corr_generic_z", "corr_generic_y", "corr_generic_x"},
+                                               {"corr_generic_z_f64", "corr_generic_y_f64", "corr_generic_x_f64"}};
 
 int corr_long_f32(const float *in, float *out, int Z, int Y, int X, int axis, const Taps &t)
 {
-    const int r = t.n >> 1;
-    if (axis == 1) {
-        size_t lds = (size_t)(LONG_TO + 2 * r) * 64 * sizeof(float);
-        auto k = k_corr_long_f32<1, LONG_TO, LONG_R>;
+    return with_axis<1>(axis, [&](auto A) -> int {
+        constexpr int AX = decltype(A)::value;      // lanes along x (AX 1, LDS[pos][64]) or along y (AX 2, LDS[pos][65])
+        const size_t lds = (size_t)(LONG_TO + 2 * (t.n >> 1)) * (AX == 1 ? 64 : 65) * sizeof(float);
+        auto k = k_corr_long_f32<AX, LONG_TO, LONG_R>;
         TIP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        dim3 grid(cdiv(X, 64), cdiv(Y, LONG_TO), Z), block(256);
-        TIP_LAUNCH("corr_long_y", k, grid, block, lds, in, out, Z, Y, X, t);
-    } else {
-        size_t lds = (size_t)(LONG_TO + 2 * r) * 65 * sizeof(float);
-        auto k = k_corr_long_f32<2, LONG_TO, LONG_R>;
-        TIP_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        dim3 grid(cdiv(Y, 64), cdiv(X, LONG_TO), Z), block(256);
-        TIP_LAUNCH("corr_long_x", k, grid, block, lds, in, out, Z, Y, X, t);
-    }
-    return TIP_OK;
+        const dim3 grid(cdiv(AX == 1 ? X : Y, 64), cdiv(AX == 1 ? Y : X, LONG_TO), Z);
+        TIP_LAUNCH(AX == 1 ? "corr_long_y" : "corr_long_x", k, grid, dim3(256), lds, in, out, Z, Y, X, t);
+        return TIP_OK;
+    });
 }
 
 // dtype 0 = f32, 1 = f64.  force: 0 auto, 1 generic, 2 long
@@ -54,7 +50,7 @@ int correlate1d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, i
         use_long = true;
     }
     if (use_long) return corr_long_f32((const float *)in, (float *)out, Z, Y, X, axis, t);
-    if (dtype == 0) return corr_generic<float>((const float *)in, (float *)out, Z, Y, X, axis, t);
+    if (dtype == 0) return corr_generic(GENERIC_NAME[0][axis], (const float *)in, (float *)out, Z, Y, X, axis, t);
     if (dtype == 1) {
         // radius 12 (sigma 3, the watershed's default blur, bim.py:474) along y / x: register-sliding kernels, each
         // input loaded once per thread instead of 25 times through the caches
@@ -68,27 +64,9 @@ int correlate1d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, i
                        (const double *)in, (double *)out, Y, X, t);
             return TIP_OK;
         }
-        return corr_generic<double>((const double *)in, (double *)out, Z, Y, X, axis, t);
+        return corr_generic(GENERIC_NAME[1][axis], (const double *)in, (double *)out, Z, Y, X, axis, t);
     }
     return fail(TIP_ERR_ARG, "correlate1d: dtype %d", dtype);
-}
-
-// taps in device memory (any odd, symmetric count): the generic kernel's arithmetic, for radii beyond the tap table
-template <typename T, int AXIS>
-__global__ void __launch_bounds__(256) k_corr_big(const T *__restrict__ in, T *__restrict__ out, int Z, int Y, int X,
-                                                  const double *__restrict__ w, int n)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, z = blockIdx.z;
-    if (x >= X) return;
-    const int r = n >> 1;
-    const int len = AXIS == 0 ? Z : (AXIS == 1 ? Y : X);
-    const int c = AXIS == 0 ? z : (AXIS == 1 ? y : x);
-    const long stride = AXIS == 0 ? (long)Y * X : (AXIS == 1 ? (long)X : 1L);
-    const T *line = in + ((long)z * Y + y) * X + x - (long)c * stride;      // element 0 of this output's line
-    auto at = [&](int i) -> double { return (double)line[(long)clampi(i, 0, len - 1) * stride]; };
-    double tmp = at(c) * w[r];
-    for (int d = r; d >= 1; --d) tmp += (at(c - d) + at(c + d)) * w[r - d];
-    out[((long)z * Y + y) * X + x] = (T)tmp;
 }
 
 // in -> out through up to three axis passes; `out` doubles as scratch together with one workspace.
@@ -121,7 +99,7 @@ int gaussian3d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, co
         int rc;
         if (np_[a] > 255) {
             // radius > 127 (sigma > 31.8): more taps than the kernel-argument tap table holds; they go to device memory and a
-            // plain one-thread-per-output kernel walks them in scipy's order (no reference call site is this wide: slow path)
+            // the generic kernel walks them there in scipy's order (no reference call site is this wide: slow path)
             const int n = np_[a];
             if (n % 2 == 0 || n > 8191) return fail(TIP_ERR_ARG, "gaussian: %d taps (odd, at most 8191)", n);
             for (int i = 0; i < n / 2; ++i)
@@ -130,16 +108,10 @@ int gaussian3d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, co
             if (!wd) return TIP_ERR_NOMEM;
             TIP_HIP(hipMemcpyAsync(wd, tp[a], (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx().stream));
             TIP_HIP(hipStreamSynchronize(ctx().stream));      // (the host tap array may be a temporary of the caller)
-            const dim3 grid(cdiv(X, 256), Y, Z);
-            if (dtype == 0) {
-                if (a == 0) { TIP_LAUNCH("corr_big", (k_corr_big<float, 0>), grid, dim3(256), 0, (const float *)cur, (float *)dst, Z, Y, X, (const double *)wd, n); }
-                else if (a == 1) { TIP_LAUNCH("corr_big", (k_corr_big<float, 1>), grid, dim3(256), 0, (const float *)cur, (float *)dst, Z, Y, X, (const double *)wd, n); }
-                else { TIP_LAUNCH("corr_big", (k_corr_big<float, 2>), grid, dim3(256), 0, (const float *)cur, (float *)dst, Z, Y, X, (const double *)wd, n); }
-            } else {
-                if (a == 0) { TIP_LAUNCH("corr_big", (k_corr_big<double, 0>), grid, dim3(256), 0, (const double *)cur, (double *)dst, Z, Y, X, (const double *)wd, n); }
-                else if (a == 1) { TIP_LAUNCH("corr_big", (k_corr_big<double, 1>), grid, dim3(256), 0, (const double *)cur, (double *)dst, Z, Y, X, (const double *)wd, n); }
-                else { TIP_LAUNCH("corr_big", (k_corr_big<double, 2>), grid, dim3(256), 0, (const double *)cur, (double *)dst, Z, Y, X, (const double *)wd, n); }
-            }
+            const TapsDev td{wd, n};
+            rc = dtype == 0 ? corr_generic("corr_big", (const float *)cur, (float *)dst, Z, Y, X, a, td)
+                            : corr_generic("corr_big", (const double *)cur, (double *)dst, Z, Y, X, a, td);
+            if (rc) return rc;
         } else {
             Taps t;
             rc = make_taps(t, tp[a], np_[a]);
@@ -185,18 +157,15 @@ int tip_gaussian3d_w(const void *in, void *out, int dtype, int z, int y, int x, 
     if (!in || !out) return fail(TIP_ERR_ARG, "tip_gaussian3d_w: null pointer");
     if (dtype != 0 && dtype != 1) return fail(TIP_ERR_ARG, "dtype must be 0 (f32) or 1 (f64)");
     if (z <= 0 || y <= 0 || x <= 0) return fail(TIP_ERR_ARG, "empty volume");
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
+    if (!ctx().stream) return TIP_ERR_HIP;
     const size_t bytes = (size_t)z * y * x * (dtype == 0 ? 4 : 8);
-    WsGuard ws;
-    char *din = ws.get<char>(bytes), *dout = ws.get<char>(bytes);
-    if (!din || !dout) return TIP_ERR_NOMEM;
-    TIP_HIP(hipMemcpyAsync(din, in, bytes, hipMemcpyHostToDevice, c.stream));
+    Staging st;
+    const char *din = st.in((const char *)in, bytes);
+    char *dout = st.out((char *)out, bytes);
+    if (st.rc) return st.rc;
     int rc = gaussian3d_dev(din, dout, dtype, z, y, x, tz, nz, ty, ny, tx, nx);
     if (rc) return rc;
-    TIP_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    return st.finish();
 }
 
 static int taps_for(double sigma, double truncate, double *buf, int *n)

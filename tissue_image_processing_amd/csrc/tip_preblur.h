@@ -9,7 +9,7 @@
 //     (first z pass, exactly k_zpass_r2_x4's arithmetic), writing the plane to LDS;
 //   * y pass and x pass run on that LDS plane (same tap order as k_ypass_slide / k_xpass_slide, each rounded to float32);
 //   * the x-pass outputs of the last 5 planes stay in registers and the second z pass streams the result to HBM.
-// Every pass accumulates in float64 in scipy's order and rounds to float32 exactly where the separate kernels do, so the
+// Every pass is a tap_sum (tip_corr.h) of float32 samples and rounds to float32 exactly where the separate kernels do, so the
 // output is bit-identical to them (tests compare the two paths).  The intermediate volume (the (0.5, 1, 1)-blurred
 // channel itself) is not produced: callers that need it (bin_size > 1) use the separate kernels.
 #pragma once
@@ -45,12 +45,7 @@ __global__ void __launch_bounds__(PB_T) k_preblur_fused(const uint16_t *__restri
         const int r = i / PB_WX, c = i - r * PB_WX;
         off[k] = i < PB_WY * PB_WX ? clampi(y0 - PB_H + r, 0, Y - 1) * X + clampi(x0 - PB_H + c, 0, X - 1) : -1;
     }
-    auto raw = [&](int z, int k) -> float {
-        float v = (float)src[(long)z * P + (long)off[k]];
-        if (airy) { v -= 10000.f; if (v < 0.f) v = 0.f; }
-        if (has && v > cp) v = cp;
-        return v;
-    };
+    auto raw = [&](int z, int k) -> float { return raw_sample(src[(long)z * P + (long)off[k]], airy, has, cp); };
     // Both z windows are RINGS indexed by plane % 5 and the plane loop is unrolled five-fold, so that every ring index is a
     // compile-time constant: no window shifting (the shifts were 142 of the loop's ~700 instructions, and the kernel is
     // bound by instruction issue).
@@ -77,10 +72,8 @@ __global__ void __launch_bounds__(PB_T) k_preblur_fused(const uint16_t *__restri
                 for (int k = 0; k < PB_OWN; ++k) {
                     if (off[k] < 0) continue;
                     const int i = t + k * PB_T;
-                    double tmp = (double)w[k][u] * k05.w[2];
-                    tmp += ((double)w[k][(u + 3) % 5] + (double)w[k][(u + 2) % 5]) * k05.w[0];
-                    tmp += ((double)w[k][(u + 4) % 5] + (double)w[k][(u + 1) % 5]) * k05.w[1];
-                    (&p1[0][0])[i] = (float)tmp;
+                    // window: planes zp-2 .. zp+2 = slots u+3, u+4, u, u+1, u+2
+                    (&p1[0][0])[i] = (float)tap_sum<2>([&](int j) { return (double)w[k][(u + 3 + j) % 5]; }, k05.w);
                     w[k][(u + 3) % 5] = raw(min(zp + 3, Z - 1), k);      // plane zp + 3 takes the slot of plane zp - 2
                 }
             }
@@ -95,12 +88,7 @@ __global__ void __launch_bounds__(PB_T) k_preblur_fused(const uint16_t *__restri
 #pragma unroll
                     for (int i = 0; i < 12; ++i) win[i] = (double)p1[yr + i][yc];
 #pragma unroll
-                    for (int o = 0; o < 4; ++o) {
-                        double tmp = win[o + 4] * k1.w[4];
-#pragma unroll
-                        for (int d = 4; d >= 1; --d) tmp += (win[o + 4 - d] + win[o + 4 + d]) * k1.w[4 - d];
-                        yb[yr + o][yc] = (float)tmp;
-                    }
+                    for (int o = 0; o < 4; ++o) yb[yr + o][yc] = (float)tap_sum<4>([&](int j) { return win[o + j]; }, k1.w);
                 }
                 if (t < (PB_YI - PB_T) * 4) {
                     const int item = PB_T + (t >> 2), o = t & 3;
@@ -108,10 +96,7 @@ __global__ void __launch_bounds__(PB_T) k_preblur_fused(const uint16_t *__restri
                     double win[9];
 #pragma unroll
                     for (int i = 0; i < 9; ++i) win[i] = (double)p1[yr + i][yc];
-                    double tmp = win[4] * k1.w[4];
-#pragma unroll
-                    for (int d = 4; d >= 1; --d) tmp += (win[4 - d] + win[4 + d]) * k1.w[4 - d];
-                    yb[yr][yc] = (float)tmp;
+                    yb[yr][yc] = (float)tap_sum<4>([&](int j) { return win[j]; }, k1.w);
                 }
             }
             __syncthreads();
@@ -123,12 +108,7 @@ __global__ void __launch_bounds__(PB_T) k_preblur_fused(const uint16_t *__restri
                     v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w;
                 }
 #pragma unroll
-                for (int k = 0; k < PB_O; ++k) {
-                    double tmp = (double)v[k + 4] * k1.w[4];
-#pragma unroll
-                    for (int d = 4; d >= 1; --d) tmp += ((double)v[k + 4 - d] + (double)v[k + 4 + d]) * k1.w[4 - d];
-                    last[k] = (float)tmp;
-                }
+                for (int k = 0; k < PB_O; ++k) last[k] = (float)tap_sum<4>([&](int j) { return (double)v[k + j]; }, k1.w);
             }   // (zp >= Z: `last` keeps the last plane: the window's far end is replicated)
 #pragma unroll
             for (int k = 0; k < PB_O; ++k) {
@@ -139,12 +119,8 @@ __global__ void __launch_bounds__(PB_T) k_preblur_fused(const uint16_t *__restri
             if (zo >= 0 && y0 + oy < Y && x0 + ox < X) {
                 float o[PB_O];
 #pragma unroll
-                for (int k = 0; k < PB_O; ++k) {                                // window: planes zo-2 .. zo+2 = slots u+1 .. u+4, u
-                    double tmp = (double)ring[(u + 3) % 5][k] * k05.w[2];
-                    tmp += ((double)ring[(u + 1) % 5][k] + (double)ring[u][k]) * k05.w[0];
-                    tmp += ((double)ring[(u + 2) % 5][k] + (double)ring[(u + 4) % 5][k]) * k05.w[1];
-                    o[k] = (float)tmp;
-                }
+                for (int k = 0; k < PB_O; ++k)                                  // window: planes zo-2 .. zo+2 = slots u+1 .. u+4, u
+                    o[k] = (float)tap_sum<2>([&](int j) { return (double)ring[(u + 1 + j) % 5][k]; }, k05.w);
                 float *dst = out + (long)zo * P + (long)(y0 + oy) * X + x0 + ox;
                 if (x0 + ox + PB_O <= X && (X & 3) == 0) {
                     *reinterpret_cast<float4 *>(dst) = make_float4(o[0], o[1], o[2], o[3]);

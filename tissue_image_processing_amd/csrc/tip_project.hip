@@ -26,31 +26,45 @@ struct ClipInfo {
     int has;
 };
 
-// ---- P1: the airyscan offset (sp.py:26-29), on the integer sample for the histograms and on the float for the readers ----
-__device__ __forceinline__ int airy_offset(int v, int airy)
+// inclusive prefix sum over the 64 lanes of a wave
+template <typename T>
+__device__ __forceinline__ T wave_inclusive_scan(T v, int lane)
 {
-    if (airy) { v -= 10000; if (v < 0) v = 0; }
-    return v;
-}
-__device__ __forceinline__ float airy_offset(float v, int airy)
-{
-    if (airy) { v -= 10000.f; if (v < 0.f) v = 0.f; }
+    for (int d = 1; d < 64; d <<= 1) {
+        const T o = __shfl_up(v, d, 64);
+        if (lane >= d) v += o;
+    }
     return v;
 }
 
-// ---- P2: histogram of the (offset-corrected) reference channel -----------------------------------------
+// ---- P2: histogram of the (offset-corrected, airy_offset) reference channel ------------------------------
 // One persistent 1024-thread block per CU with a private 65536-bin LDS histogram of 16-bit counters packed two per dword.
 // A block walks chunks of 57344 voxels; a chunk adds at most 57344 to a bin, so between chunks every bin that has reached
 // 8192 is moved to the global histogram (a handful per chunk) and no counter can overflow; the table is cleared once and
 // flushed once per block.  (One block per chunk -- 2196 clears, scans and full flushes of the 128 KB table, 6.6 M global
 // atomics on ~3000 addresses -- took 0.13 ms; the 252 MB read alone is 0.06 ms.)
 constexpr int HIST_PER_BLOCK = 57344;  // 7 trips of 1024 threads x 8 voxels; 57344 + 8191 < 65536
+// the packed table (32768 dwords, bin b in half b & 1 of dword b >> 1) of a 1024-thread block: clear, bump, flush all
+__device__ __forceinline__ void hist_clear(unsigned int *h)
+{
+    for (int i = threadIdx.x; i < 32768; i += 1024) h[i] = 0;
+    __syncthreads();
+}
+__device__ __forceinline__ void hist_bump(unsigned int *h, int val) { atomicAdd(&h[val >> 1], 1u << (16 * (val & 1))); }
+__device__ __forceinline__ void hist_flush_all(const unsigned int *h, unsigned long long *__restrict__ hist)
+{
+    for (int i = threadIdx.x; i < 32768; i += 1024) {
+        const unsigned int c = h[i];
+        if (c & 0xffffu) atomicAdd(&hist[2 * i], (unsigned long long)(c & 0xffffu));
+        if (c >> 16) atomicAdd(&hist[2 * i + 1], (unsigned long long)(c >> 16));
+    }
+}
+
 __global__ void __launch_bounds__(1024) k_hist_u16(const uint16_t *__restrict__ in, long n, int airy,
                                                    unsigned long long *__restrict__ hist)
 {
     __shared__ unsigned int h[32768];
-    for (int i = threadIdx.x; i < 32768; i += 1024) h[i] = 0;
-    __syncthreads();
+    hist_clear(h);
     const long nchunks = (n + HIST_PER_BLOCK - 1) / HIST_PER_BLOCK;
     for (long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
         const long base = chunk * HIST_PER_BLOCK;
@@ -67,21 +81,14 @@ __global__ void __launch_bounds__(1024) k_hist_u16(const uint16_t *__restrict__ 
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
 #pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        const int val = airy_offset((int)((w[j] >> (16 * s)) & 0xffffu), airy);
-                        atomicAdd(&h[val >> 1], 1u << (16 * (val & 1)));
-                    }
+                    for (int s = 0; s < 2; ++s) hist_bump(h, airy_offset((int)((w[j] >> (16 * s)) & 0xffffu), airy));
                 }
             }
         } else {
             for (int k = 0; k < TRIPS; ++k) {
                 const long i0 = base + ((long)k * 1024 + threadIdx.x) * 8;
-                for (int j = 0; j < 8; ++j) {
-                    if (i0 + j < n) {
-                        const int val = airy_offset((int)in[i0 + j], airy);
-                        atomicAdd(&h[val >> 1], 1u << (16 * (val & 1)));
-                    }
-                }
+                for (int j = 0; j < 8; ++j)
+                    if (i0 + j < n) hist_bump(h, airy_offset((int)in[i0 + j], airy));
             }
         }
         __syncthreads();
@@ -94,11 +101,7 @@ __global__ void __launch_bounds__(1024) k_hist_u16(const uint16_t *__restrict__ 
             __syncthreads();
         }
     }
-    for (int i = threadIdx.x; i < 32768; i += 1024) {
-        const unsigned int c = h[i];
-        if (c & 0xffffu) atomicAdd(&hist[2 * i], (unsigned long long)(c & 0xffffu));
-        if (c >> 16) atomicAdd(&hist[2 * i + 1], (unsigned long long)(c >> 16));
-    }
+    hist_flush_all(h, hist);
 }
 
 // The same histogram over a sub-box [z0,z1) x [y0,y1) x [x0,x1) of one channel plane stack (row length X, plane size
@@ -108,24 +111,18 @@ __global__ void __launch_bounds__(1024) k_hist_u16_box(const uint16_t *__restric
                                                        int by, int bx, int airy, unsigned long long *__restrict__ hist)
 {
     __shared__ unsigned int h[32768];
-    for (int i = threadIdx.x; i < 32768; i += 1024) h[i] = 0;
-    __syncthreads();
+    hist_clear(h);
     const long n = (long)bz * by * bx;
     const long base = (long)blockIdx.x * HIST_PER_BLOCK;
     for (int k = 0; k < HIST_PER_BLOCK / 1024; ++k) {
         const long i = base + (long)k * 1024 + threadIdx.x;
         if (i < n) {
             const int x = (int)(i % bx), y = (int)((i / bx) % by), z = (int)(i / ((long)bx * by));
-            const int val = airy_offset((int)in[((long)(z0 + z) * Y + (y0 + y)) * X + (x0 + x)], airy);
-            atomicAdd(&h[val >> 1], 1u << (16 * (val & 1)));
+            hist_bump(h, airy_offset((int)in[((long)(z0 + z) * Y + (y0 + y)) * X + (x0 + x)], airy));
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 32768; i += 1024) {
-        const unsigned int c = h[i];
-        if (c & 0xffffu) atomicAdd(&hist[2 * i], (unsigned long long)(c & 0xffffu));
-        if (c >> 16) atomicAdd(&hist[2 * i + 1], (unsigned long long)(c >> 16));
-    }
+    hist_flush_all(h, hist);
 }
 
 // np.percentile(nonzero, 95) with numpy 1.26 arithmetic (see oracle.percentile_linear): one block.
@@ -144,11 +141,7 @@ __global__ void __launch_bounds__(1024) k_percentile95(const unsigned long long 
     unsigned long long s = 0;
     for (int b = t * 64; b < t * 64 + 64; ++b)
         if (b > 0 || with_zero) s += hist[b];
-    unsigned long long inc = s;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
+    unsigned long long inc = wave_inclusive_scan(s, lane);
     if (lane == 63) wave_tot[wave] = inc;
     __syncthreads();
     unsigned long long base = 0;
@@ -179,11 +172,7 @@ __global__ void __launch_bounds__(1024) k_percentile95(const unsigned long long 
     if (wave < 2) {       // wave 0: value at rank prev, wave 1: at rank next
         const unsigned long long k = (unsigned long long)(wave == 0 ? prev : next) - s_before[wave];
         const int b = s_chunk[wave] * 64 + lane;
-        unsigned long long c = (b > 0 || with_zero) ? hist[b] : 0ULL, ci = c;
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long o = __shfl_up(ci, d, 64);
-            if (lane >= d) ci += o;
-        }
+        const unsigned long long ci = wave_inclusive_scan((b > 0 || with_zero) ? hist[b] : 0ULL, lane);
         // first bin whose inclusive count exceeds k
         const unsigned long long hit = __ballot(ci > k);
         if (lane == 0) s_val[wave] = hit ? s_chunk[wave] * 64 + (__ffsll((long long)hit) - 1) : 65535;
@@ -207,11 +196,30 @@ struct LoadU16Clip {
     const ClipInfo *clip;
     __device__ __forceinline__ double operator()(int z, int y, int x) const
     {
-        float f = airy_offset((float)p[z * sz + y * sy + x], airy);
-        if (clip->has && f > clip->p95) f = clip->p95;
-        return (double)f;
+        return (double)raw_sample(p[z * sz + y * sy + x], airy, clip->has != 0, clip->p95);
     }
 };
+
+// ---- the z-maps of pixel p from its chosen plane index (sp.py:61-62, 68-69) ----------------------------------------
+__device__ __forceinline__ void emit_zmaps(long p, int plane, int Z, int min_z, int atoh_shift, int32_t *__restrict__ zsel,
+                                           int32_t *__restrict__ zsel_atoh, int64_t *__restrict__ zmap, int *__restrict__ err)
+{
+    const int cz = min_z + plane;            // sp.py:61
+    if (zmap) zmap[p] = cz;
+    int ca = cz;
+    if (atoh_shift != 0) {                   // sp.py:62 np.clip(chosen_z + shift, 0, Z)  (upper bound Z, sic)
+        ca = cz + atoh_shift;
+        ca = ca < 0 ? 0 : (ca > Z ? Z : ca);
+    }
+    if (cz >= Z || ca >= Z) {                // the reference's fancy index would raise IndexError (sp.py:68-69)
+        atomicOr(err, 1);
+        zsel[p] = cz >= Z ? Z - 1 : cz;
+        zsel_atoh[p] = ca >= Z ? Z - 1 : ca;
+        return;
+    }
+    zsel[p] = cz;
+    zsel_atoh[p] = ca;
+}
 
 // ---- P5: first-maximum argmax over z ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_argmax_z(const float *__restrict__ score, int Z, long P, int min_z,
@@ -227,21 +235,7 @@ __global__ void __launch_bounds__(256) k_argmax_z(const float *__restrict__ scor
         const float s = score[(long)z * P + p];
         if (s > best) { best = s; bi = z; }
     }
-    const int cz = min_z + bi;               // sp.py:61
-    if (zmap) zmap[p] = cz;
-    int ca = cz;
-    if (atoh_shift != 0) {                   // sp.py:62 np.clip(chosen_z + shift, 0, Z)  (upper bound Z, sic)
-        ca = cz + atoh_shift;
-        ca = ca < 0 ? 0 : (ca > Z ? Z : ca);
-    }
-    if (cz >= Z || ca >= Z) {                // the reference's fancy index would raise IndexError (sp.py:68-69)
-        atomicOr(err, 1);
-        zsel[p] = cz >= Z ? Z - 1 : cz;
-        zsel_atoh[p] = ca >= Z ? Z - 1 : ca;
-        return;
-    }
-    zsel[p] = cz;
-    zsel_atoh[p] = ca;
+    emit_zmaps(p, bi, Z, min_z, atoh_shift, zsel, zsel_atoh, zmap, err);
 }
 
 __global__ void k_identity(float *out, int n)
@@ -281,12 +275,7 @@ __global__ void __launch_bounds__(256) k_xpass_wmax(const float *__restrict__ ym
     for (int c = 0; c < MAXC; ++c) mx[c] = 0.f;
     for (int z = 0; z < Zs; ++z) {
         const float *row = ymask + (long)z * P + (long)y * X;
-        double tmp = (double)row[x] * taps.w[r];
-        for (int d = r; d >= 1; --d) {
-            const float a = row[clampi(x - d, 0, X - 1)], b = row[clampi(x + d, 0, X - 1)];
-            tmp += ((double)a + (double)b) * taps.w[r - d];
-        }
-        const float m = (float)tmp;
+        const float m = (float)tap_sum(r, [&](int j) { return (double)row[clampi(x - r + j, 0, X - 1)]; }, taps.w);
 #pragma unroll
         for (int c = 0; c < MAXC; ++c) {
             if (c < C && ((chan_mask >> c) & 1u)) {
@@ -366,13 +355,8 @@ __global__ void __launch_bounds__(256) k_mask_wmax_fused(const float *__restrict
         for (int i = t; i < FT_Y * FT_W; i += 256) {     // y pass of plane z for the tile's columns
             const int r = i / FT_W, c = i - r * FT_W;
             float val = 0.f;
-            if (z >= (int)cmin[r][c] - MASK_ZR && z <= (int)cmax[r][c] + MASK_ZR) {
-                double tmp = (double)Tz[zs[r + MASK_R][c]] * taps.w[MASK_R];
-#pragma unroll
-                for (int d = MASK_R; d >= 1; --d)
-                    tmp += ((double)Tz[zs[r + MASK_R - d][c]] + (double)Tz[zs[r + MASK_R + d][c]]) * taps.w[MASK_R - d];
-                val = (float)tmp;
-            }
+            if (z >= (int)cmin[r][c] - MASK_ZR && z <= (int)cmax[r][c] + MASK_ZR)
+                val = (float)tap_sum<MASK_R>([&](int j) { return (double)Tz[zs[r + j][c]]; }, taps.w);
             yb[r][c] = val;
         }
         __syncthreads();        // (the buffer of plane z-1 is free again only after the NEXT barrier: two buffers, one barrier per plane)
@@ -385,13 +369,7 @@ __global__ void __launch_bounds__(256) k_mask_wmax_fused(const float *__restrict
             }
             float m[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                double tmp = (double)v[k + MASK_R] * taps.w[MASK_R];
-#pragma unroll
-                for (int d = MASK_R; d >= 1; --d)
-                    tmp += ((double)v[k + MASK_R - d] + (double)v[k + MASK_R + d]) * taps.w[MASK_R - d];
-                m[k] = (float)tmp;
-            }
+            for (int k = 0; k < 8; ++k) m[k] = (float)tap_sum<MASK_R>([&](int j) { return (double)v[k + j]; }, taps.w);
 #pragma unroll
             for (int c = 0; c < MAXC; ++c) {
                 if (c < C && ((chan_mask >> c) & 1u)) {
@@ -432,6 +410,15 @@ static int cu_count()
         cus = hipGetDeviceProperties(&prop, ctx().device) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     return cus;
+}
+
+// the float32 copy of n taps (a Taps' table or a caller's array) for the certified fast score passes; zero beyond n
+static TapsF taps_f32(const double *w, int n)
+{
+    TapsF f;
+    f.n = n;
+    for (int i = 0; i < 256; ++i) f.w[i] = i < n ? (float)w[i] : 0.f;
+    return f;
 }
 
 // The sigma-30 score pass of the certified argmax on the fp16 matrix cores with split operands (tip_corr_f16.h): radius 120
@@ -517,11 +504,7 @@ __global__ void __launch_bounds__(256) k_argmax_certify(const float *__restrict_
     // append with one atomic per block (not per pixel: same-address atomics serialise in L2)
     const int mine = __popc(unc);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = mine;   // inclusive prefix sum over the wave
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
+    const int incl = wave_inclusive_scan(mine, lane);
     if (lane == 63) s_cnt[wave] = incl;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -571,8 +554,8 @@ __global__ void __launch_bounds__(256) k_argmax_exact_fix(const float *__restric
             if (threadIdx.x < 2 * r + 1) {
                 const int xx = clampi(x + (int)threadIdx.x - r, 0, X - 1);
                 double tmp = (double)vol[(long)y * X + xx] * taps.w[r];
-                // the sum is serial (scipy's order) but the loads are not: 2 * FIX_UL per trip in flight (the kernel is bound by
-                // global-load latency, not by arithmetic)
+                // tap_sum's contract with the loads batched: the sum is serial (scipy's order) but the loads are not, 2 * FIX_UL per
+                // trip in flight (the kernel is bound by global-load latency, not by arithmetic)
                 for (int d0 = r; d0 >= 1; d0 -= FIX_UL) {
                     float a[FIX_UL], b[FIX_UL];
 #pragma unroll
@@ -588,11 +571,7 @@ __global__ void __launch_bounds__(256) k_argmax_exact_fix(const float *__restric
                 c[threadIdx.x] = (float)tmp;   // exact y pass, rounded to float32 like scipy's intermediate
             }
             __syncthreads();
-            if (threadIdx.x == 0) {
-                double tmp = (double)c[r] * taps.w[r];
-                for (int d = r; d >= 1; --d) tmp += ((double)c[r - d] + (double)c[r + d]) * taps.w[r - d];
-                sexact[z] = (float)tmp;
-            }
+            if (threadIdx.x == 0) sexact[z] = (float)tap_sum(r, [&](int j) { return (double)c[j]; }, taps.w);
             __syncthreads();
         }
         if (threadIdx.x == 0) {
@@ -612,18 +591,7 @@ __global__ void __launch_bounds__(256) k_emit_zmaps(const int *__restrict__ best
 {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
-    const int cz = min_z + best_z[p];
-    if (zmap) zmap[p] = cz;
-    int ca = cz;
-    if (atoh_shift != 0) { ca = cz + atoh_shift; ca = ca < 0 ? 0 : (ca > Z ? Z : ca); }
-    if (cz >= Z || ca >= Z) {
-        atomicOr(err, 1);
-        zsel[p] = cz >= Z ? Z - 1 : cz;
-        zsel_atoh[p] = ca >= Z ? Z - 1 : ca;
-        return;
-    }
-    zsel[p] = cz;
-    zsel_atoh[p] = ca;
+    emit_zmaps(p, best_z[p], Z, min_z, atoh_shift, zsel, zsel_atoh, zmap, err);
 }
 
 static int resolve_taps(const double *given, double sigma, int expect, Taps &t)
@@ -809,9 +777,7 @@ static int zmaps_certified(ProjJob &s)
     float *D = s.ws.get<float>(s.V);
     int *bestz = s.ws.get<int>(P), *unc = s.ws.get<int>(P), *uncn = s.ws.get<int>(1);
     if (!D || !bestz || !unc || !uncn) return TIP_ERR_NOMEM;
-    TapsF f30;
-    f30.n = s.k30.n;
-    for (int i = 0; i < 256; ++i) f30.w[i] = (float)s.k30.w[i];
+    const TapsF f30 = taps_f32(s.k30.w, s.k30.n);
     // fast y pass B -> A, fast x pass A -> D   (B, the exact z-passed volume, is kept for the exact fix-up).  The fp16 tiles
     // take the clip value: their samples are scaled into fp16's range by it, and the volume B -- convex combinations of
     // clipped voxels -- is bounded by it; err bit 8 would report a sample beyond that range.
@@ -954,23 +920,18 @@ static int project_host(const uint16_t *czyx, int c, int z, int y, int x, int zl
                         int bin, int airyscan, int atoh_shift, const double *t05, const double *t1, const double *t2,
                         const double *t30, double *proj, int64_t *zmap)
 {
-    Ctx &cx = ctx();
-    if (!cx.stream) return TIP_ERR_HIP;
+    if (!ctx().stream) return TIP_ERR_HIP;
     if (!czyx || !proj) return fail(TIP_ERR_ARG, "tip_project_u16: null pointer");
     if (c < 1 || z < 1 || y < 1 || x < 1) return fail(TIP_ERR_ARG, "tip_project_u16: empty stack");
     const size_t nin = (size_t)c * z * y * x, P = (size_t)y * x;
-    WsGuard ws;
-    uint16_t *din = ws.get<uint16_t>(nin);
-    double *dproj = ws.get<double>((size_t)c * P);
-    int64_t *dz = ws.get<int64_t>(P);
-    if (!din || !dproj || !dz) return TIP_ERR_NOMEM;
-    TIP_HIP(hipMemcpyAsync(din, czyx, nin * 2, hipMemcpyHostToDevice, cx.stream));
+    Staging st;
+    const uint16_t *din = st.in(czyx, nin);
+    double *dproj = st.out(proj, (size_t)c * P);
+    int64_t *dz = st.out(zmap, P);       // (no zmap asked for: none computed, none copied)
+    if (st.rc) return st.rc;
     int rc = project_dev(din, c, z, y, x, zlo, zhi, min_z, ref_ch, method, bin, airyscan, atoh_shift, t05, t1, t2, t30, dproj, dz);
     if (rc) return rc;
-    TIP_HIP(hipMemcpyAsync(proj, dproj, (size_t)c * P * 8, hipMemcpyDeviceToHost, cx.stream));
-    if (zmap) TIP_HIP(hipMemcpyAsync(zmap, dz, P * 8, hipMemcpyDeviceToHost, cx.stream));
-    TIP_HIP(hipStreamSynchronize(cx.stream));
-    return TIP_OK;
+    return st.finish();
 }
 
 static int check_binned(int method, int bin)
@@ -1043,28 +1004,21 @@ __global__ void k_set_clip(ClipInfo *c, float v) { c->has = 1; c->p95 = v; c->p9
 // weights (radius 120); clip = the bound of the data (the scaling follows from it).  flag: bit 8 = a sample beyond the range.
 int tip_score_pass_f16(const float *in, float *out, int z, int y, int x, int axis, const double *taps, int ntaps, float clip, int *flag)
 {
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
+    if (!ctx().stream) return TIP_ERR_HIP;
     if (!in || !out || !taps || !flag || z < 1 || y < 1 || x < 1 || (axis != 1 && axis != 2) || ntaps != 241 || !(clip > 0.f))
         return fail(TIP_ERR_ARG, "tip_score_pass_f16: bad arguments (radius 120 only)");
     const size_t V = (size_t)z * y * x;
-    WsGuard ws;
-    float *di = ws.get<float>(V), *dout = ws.get<float>(V);
-    ClipInfo *ci = ws.get<ClipInfo>(1);
-    int *df = ws.get<int>(1);
-    if (!di || !dout || !ci || !df) return TIP_ERR_NOMEM;
-    TapsF t;
-    t.n = ntaps;
-    for (int i = 0; i < 256; ++i) t.w[i] = i < ntaps ? (float)taps[i] : 0.f;
-    TIP_HIP(hipMemcpyAsync(di, in, V * 4, hipMemcpyHostToDevice, c.stream));
-    TIP_HIP(hipMemsetAsync(df, 0, sizeof(int), c.stream));
-    hipLaunchKernelGGL(k_set_clip, dim3(1), dim3(1), 0, c.stream, ci, clip);
-    int rc = axis == 1 ? launch_f16<1>(di, dout, z, y, x, t, ci, df) : launch_f16<2>(di, dout, z, y, x, t, ci, df);
+    Staging st;
+    const float *di = st.in(in, V);
+    float *dout = st.out(out, V);
+    ClipInfo *ci = st.scratch<ClipInfo>(1);
+    int *df = st.out(flag, 1, true);
+    if (st.rc) return st.rc;
+    const TapsF t = taps_f32(taps, ntaps);
+    hipLaunchKernelGGL(k_set_clip, dim3(1), dim3(1), 0, ctx().stream, ci, clip);
+    int rc = with_axis<1>(axis, [&](auto A) { return launch_f16<decltype(A)::value>(di, dout, z, y, x, t, ci, df); });
     if (rc) return rc;
-    TIP_HIP(hipMemcpyAsync(out, dout, V * 4, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipMemcpyAsync(flag, df, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    return st.finish();
 }
 
 // How v_mfma_f32_32x32x16_f16 rounds, on THIS device (the certified bound of tip_corr_f16.h counts two roundings per instruction:
@@ -1084,41 +1038,31 @@ __global__ void k_mfma_f16_probe(const float *a, const float *b, const float *c,
 }
 int tip_mfma_f16_probe(const float *a, const float *b, const float *cvals, float *out, int ncase)
 {
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
+    if (!ctx().stream) return TIP_ERR_HIP;
     if (!a || !b || !cvals || !out || ncase < 1 || ncase > 256) return fail(TIP_ERR_ARG, "tip_mfma_f16_probe: bad arguments");
-    WsGuard ws;
-    float *da = ws.get<float>((size_t)ncase * 16), *db = ws.get<float>((size_t)ncase * 16), *dc = ws.get<float>(ncase), *dout = ws.get<float>(ncase);
-    if (!da || !db || !dc || !dout) return TIP_ERR_NOMEM;
-    TIP_HIP(hipMemcpyAsync(da, a, (size_t)ncase * 64, hipMemcpyHostToDevice, c.stream));
-    TIP_HIP(hipMemcpyAsync(db, b, (size_t)ncase * 64, hipMemcpyHostToDevice, c.stream));
-    TIP_HIP(hipMemcpyAsync(dc, cvals, (size_t)ncase * 4, hipMemcpyHostToDevice, c.stream));
-    hipLaunchKernelGGL(k_mfma_f16_probe, dim3(1), dim3(64), 0, c.stream, (const float *)da, (const float *)db, (const float *)dc, dout, ncase);
-    TIP_HIP(hipMemcpyAsync(out, dout, (size_t)ncase * 4, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
-    return TIP_OK;
+    Staging st;
+    const float *da = st.in(a, (size_t)ncase * 16), *db = st.in(b, (size_t)ncase * 16), *dc = st.in(cvals, (size_t)ncase);
+    float *dout = st.out(out, (size_t)ncase);
+    if (st.rc) return st.rc;
+    hipLaunchKernelGGL(k_mfma_f16_probe, dim3(1), dim3(64), 0, ctx().stream, da, db, dc, dout, ncase);
+    return st.finish();
 }
 
 // sp.py:87-165 on its own: score float32 (z, y, x) host -> int64 (y, x) plane map
 int tip_build_manifold_f32(const float *score, int z, int y, int x, int64_t *chosen)
 {
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
+    if (!ctx().stream) return TIP_ERR_HIP;
     if (!score || !chosen || z < 1 || y < 1 || x < 1) return fail(TIP_ERR_ARG, "tip_build_manifold_f32: bad arguments");
     const size_t P = (size_t)y * x, V = P * z;
-    WsGuard ws;
-    float *ds = ws.get<float>(V);
-    int *bz = ws.get<int>(P), *err = ws.get<int>(1);
-    if (!ds || !bz || !err) return TIP_ERR_NOMEM;
-    TIP_HIP(hipMemcpyAsync(ds, score, V * 4, hipMemcpyHostToDevice, c.stream));
-    TIP_HIP(hipMemsetAsync(err, 0, sizeof(int), c.stream));
+    std::vector<int> hb(P);          // the int32 plane map and the error word come down first: `chosen` is written last
+    int herr = 0;
+    Staging st;
+    const float *ds = st.in(score, V);
+    int *bz = st.out(hb.data(), P), *err = st.out(&herr, 1, true);
+    if (st.rc) return st.rc;
     int rc = manifold_dev(ds, z, y, x, bz, err);
     if (rc) return rc;
-    std::vector<int> hb(P);
-    int herr = 0;
-    TIP_HIP(hipMemcpyAsync(hb.data(), bz, P * 4, hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    TIP_HIP(hipStreamSynchronize(c.stream));
+    if ((rc = st.finish())) return rc;
     if (herr) return fail(TIP_ERR_HIP, "build_manifold: a pixel without a visited neighbour (upstream raises TypeError here)");
     for (size_t i = 0; i < P; ++i) chosen[i] = hb[i];
     return TIP_OK;

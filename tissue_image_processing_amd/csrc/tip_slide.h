@@ -5,18 +5,27 @@
 
 namespace tip {
 
-// scipy-order symmetric tap sum over a compile-time window: win[0..2R], centre at R
-template <int R>
-__device__ __forceinline__ double tap_sum(const double (&win)[2 * R + 1], const Taps &taps)
+// ---- P1: the airyscan offset (sp.py:26-29), on the integer sample for the histograms and on the float for the readers ----
+__device__ __forceinline__ int airy_offset(int v, int airy)
 {
-    double tmp = win[R] * taps.w[R];
-#pragma unroll
-    for (int d = R; d >= 1; --d) tmp += (win[R - d] + win[R + d]) * taps.w[R - d];
-    return tmp;
+    if (airy) { v -= 10000; if (v < 0) v = 0; }
+    return v;
+}
+__device__ __forceinline__ float airy_offset(float v, int airy)
+{
+    if (airy) { v -= 10000.f; if (v < 0.f) v = 0.f; }
+    return v;
+}
+// P1 + P2, the one reader of a raw stack sample: uint16 -> float32, airyscan offset, clip at p95 if `has` (sp.py:26-36)
+__device__ __forceinline__ float raw_sample(uint16_t u, int airy, bool has, float p95)
+{
+    float v = airy_offset((float)u, airy);
+    if (has && v > p95) v = p95;
+    return v;
 }
 
 // ---- z pass, radius 2 (sigma 0.5), four x columns per thread ------------------------------------------------------------
-struct Src4U16Clip {       // uint16 stack reader with the airyscan offset and the percentile clip fused (sp.py:26-36)
+struct Src4U16Clip {       // uint16 stack reader (raw_sample)
     const uint16_t *p;
     int airy;
     const float *clip_p95;
@@ -24,14 +33,11 @@ struct Src4U16Clip {       // uint16 stack reader with the airyscan offset and t
     __device__ __forceinline__ void load(long idx, float (&v)[4]) const
     {
         const ushort4 u = *reinterpret_cast<const ushort4 *>(p + idx);
-        v[0] = (float)u.x; v[1] = (float)u.y; v[2] = (float)u.z; v[3] = (float)u.w;
+        const uint16_t s[4] = {u.x, u.y, u.z, u.w};
         const bool has = *clip_has != 0;
         const float c = *clip_p95;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (airy) { v[k] -= 10000.f; if (v[k] < 0.f) v[k] = 0.f; }
-            if (has && v[k] > c) v[k] = c;
-        }
+        for (int k = 0; k < 4; ++k) v[k] = raw_sample(s[k], airy, has, c);
     }
 };
 struct Src4F32 {
@@ -64,12 +70,7 @@ __global__ void __launch_bounds__(256) k_zpass_r2_x4(Src src, float *__restrict_
         float4 o;
         float *op = &o.x;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            double tmp = win[2][k] * taps.w[2];
-            tmp += (win[0][k] + win[4][k]) * taps.w[0];
-            tmp += (win[1][k] + win[3][k]) * taps.w[1];
-            op[k] = (float)tmp;
-        }
+        for (int k = 0; k < 4; ++k) op[k] = (float)tap_sum<2>([&](int j) { return win[j][k]; }, taps.w);
         *reinterpret_cast<float4 *>(out + (long)z * P + q) = o;
         src.load((long)min(z + 3, Z - 1) * P + q, v);
 #pragma unroll
@@ -98,9 +99,7 @@ __global__ void __launch_bounds__(256) k_ypass_slide(const T *__restrict__ in, T
         for (int o = 0; o < W; ++o) {
             const int y = y0 + s * W + o;
             // logical window element j lives in physical slot (o + j) % W
-            double tmp = win[(o + R) % W] * taps.w[R];
-#pragma unroll
-            for (int d = R; d >= 1; --d) tmp += (win[(o + R - d) % W] + win[(o + R + d) % W]) * taps.w[R - d];
+            const double tmp = tap_sum<R>([&](int j) { return win[(o + j) % W]; }, taps.w);
             if (y < Y) dst[(long)y * X] = (T)tmp;
             win[o % W] = (double)src[(long)clampi(y + R + 1, 0, Y - 1) * X];  // the slot that just left the window
         }
@@ -130,12 +129,7 @@ __global__ void __launch_bounds__(256) k_xpass_slide(const T *__restrict__ in, T
     }
     T o[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        double tmp = (double)v[k + R] * taps.w[R];
-#pragma unroll
-        for (int d = R; d >= 1; --d) tmp += ((double)v[k + R - d] + (double)v[k + R + d]) * taps.w[R - d];
-        o[k] = (T)tmp;
-    }
+    for (int k = 0; k < 8; ++k) o[k] = (T)tap_sum<R>([&](int j) { return (double)v[k + j]; }, taps.w);
     T *dst = out + row * X + x0;
     if (F32 && x0 + 8 <= X && (X & 3) == 0) {
         float *df = reinterpret_cast<float *>(dst);
