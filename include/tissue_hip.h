@@ -556,6 +556,30 @@ TIP_API int tip_piv_lookup_max3_i32_dev(const double *prev_plane, const double *
 TIP_API int tip_piv_sample_max3_i32_dev(const float *flow, const int32_t *labels, int y, int x, const double *cy_host,
                                         const double *cx_host, const uint8_t *present_host, int64_t n, int32_t *hit_host);
 
+/* ---- track linking: trackpy.link_df_iter's model for one frame (csrc/tip_link.hip; ti.py:1881-1938) ---------------------- */
+/* linking.link_candidates + _solve_subnet on the device.  track_pos (n_tracks, 3) and points (n, 3): row-major embedded      */
+/* features (cy, cx, sqrt(area / 2)), linking.embed.  A candidate link joins a track and a feature with                       */
+/* d = sqrt(dy dy + dx dx + da da) <= search_range (each operation rounded, left to right).  Tracks and features connected     */
+/* through live links form a subnet; one with at most max_subnet tracks and features is solved -- the links minimising          */
+/* sum(d^2) + range^2 per unlinked track and per unlinked feature, range = the current one -- and its links die; while         */
+/* larger ones remain, range *= adaptive_step (in double, repeatedly) and links longer than that die.  track_of_feature[j]:    */
+/* the track feature j continues, -1 when it starts a new one.  stats (6 entries, may be NULL): candidate links, rounds,        */
+/* subnets solved, the largest solved subnet's larger side, the last range as the BIT PATTERN of the double, oversize flag:     */
+/* 0 none; 1: a subnet exceeds max_subnet and adaptive_stop < 0 (no adaptive search); 2: the range fell below adaptive_stop   */
+/* (or reached 0) with a subnet still too large.  With the flag set the call still returns TIP_OK and track_of_feature is      */
+/* unspecified.  TIP_ERR_ARG: a null pointer, a negative count, more than 2^31 - 24 tracks + features, search_range <= 0 or    */
+/* not finite, adaptive_step outside (0, 1), adaptive_stop NaN, and in the host form a non-finite coordinate (the device form   */
+/* leaves such a row unlinked); TIP_ERR_UNSUPPORTED: max_subnet outside [1, 30] (the LDS budget of the solver);                */
+/* TIP_ERR_OVERFLOW: more than 2^31 - 1 candidate links.  n == 0 or n_tracks == 0: TIP_OK, all -1, nothing is read.  The _dev   */
+/* form takes device pointers (stats too) and, unlike most _dev entries, waits for the stream: once for the link count and      */
+/* once per round.                                                                                                              */
+TIP_API int tip_link_frame_f64(const double *track_pos, int64_t n_tracks, const double *points, int64_t n, double search_range,
+                               double adaptive_stop, double adaptive_step, int max_subnet, int32_t *track_of_feature,
+                               int64_t *stats);
+TIP_API int tip_link_frame_f64_dev(const double *track_pos, int64_t n_tracks, const double *points, int64_t n,
+                                   double search_range, double adaptive_stop, double adaptive_step, int max_subnet,
+                                   int32_t *track_of_feature, int64_t *stats);
+
 /* ---- run-only deflate of a map (csrc/tip_deflate.hip; movie.save_seg's label and type maps) ------------------------------ */
 /* The most bytes the encoder below writes for nbytes of input -- the one place the bound is written: per chunk of 65536     */
 /* input bytes 3 + 9 n + 7 + 3 bits (headers, the longest literal for every byte, end of block), padded to a byte, + 4.      */

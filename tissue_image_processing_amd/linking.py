@@ -17,8 +17,13 @@ trackpy's published linking model for exactly the parameters of that call site:
 * `memory`: a track that finds no feature stays linkable at its last position for that many further frames;
 * new tracks get consecutive particle numbers in feature order.
 
-The tables involved are a few thousand rows per frame: this is host work (numpy / scipy), not a GPU kernel; the dense
-array steps of tracking (drift, label lookup) are the HIP paths in `_registration.py` and `tip_lookup_max3_i32_dev`.
+Two linkers share the state handling (particle numbers, memory, track order) and differ in how they find the links of one
+frame: `FrameLinker` on the host (cKDTree candidates, scipy components, `linear_sum_assignment` per subnet) and
+`DeviceFrameLinker` in one call of the HIP library (`tip_link_frame_f64`, csrc/tip_link.hip: grid candidates, union-find
+subnets, one wavefront's shortest-augmenting-path assignment per subnet).  The host code below is the
+specification of the device path: same distances bit for bit, same ranges, and scipy's assignment step for step, so that
+even a subnet with several optimal assignments gets the host's.  `make_linker` picks one from
+the environment variable TISSUE_HIP_LINKER (host, the default, or device).
 """
 import numpy as np
 
@@ -105,19 +110,31 @@ class FrameLinker(object):
 
     def link(self, points):
         """points: (N, 3) embedded features of the next frame.  Returns (N,) int64 particle numbers."""
-        from scipy.spatial import cKDTree
         points = np.asarray(points, np.float64).reshape(-1, 3)
+        return self._advance(points, self._find_links(points))
+
+    def _find_links(self, points):
+        """(N,) int64: for every feature the index of the track (row of track_pos) it continues, -1 where it starts a new one."""
+        from scipy.spatial import cKDTree
         n = points.shape[0]
-        out_ids = np.full((n,), -1, np.int64)
-        links = []
+        track_of = np.full((n,), -1, np.int64)
         if n and self.track_id.size:
             pairs = cKDTree(self.track_pos).sparse_distance_matrix(cKDTree(points), self.search_range, output_type="coo_matrix")
             links = link_candidates(self.track_id.size, n, pairs.row, pairs.col, pairs.data, self.search_range,
                                     self.adaptive_stop, self.adaptive_step)
+            for s, d in links:
+                track_of[d] = s
+        return track_of
+
+    def _advance(self, points, track_of):
+        """The state after a frame whose feature j continues track track_of[j]: fresh particle numbers in feature order, then
+        the linkable tracks as `new points + kept`."""
+        n = points.shape[0]
+        out_ids = np.full((n,), -1, np.int64)
+        linked = np.flatnonzero(track_of >= 0)
+        out_ids[linked] = self.track_id[track_of[linked]]
         linked_src = np.zeros((self.track_id.size,), bool)
-        for s, d in links:
-            out_ids[d] = self.track_id[s]
-            linked_src[s] = True
+        linked_src[track_of[linked]] = True
         fresh = np.flatnonzero(out_ids < 0)
         out_ids[fresh] = self.next_particle + np.arange(fresh.size)
         self.next_particle += fresh.size
@@ -127,3 +144,46 @@ class FrameLinker(object):
         self.track_id = np.concatenate([out_ids, self.track_id[keep]])
         self.track_age = np.concatenate([np.zeros((n,), np.int64), self.track_age[keep] + 1])
         return out_ids
+
+
+STAT_NAMES = ("links", "rounds", "subnets", "largest_subnet", "final_range", "oversize")
+
+
+class DeviceFrameLinker(FrameLinker):
+    """FrameLinker whose link finding is one call of the HIP library (tip_link_frame_f64).  No CPU fallback: without the built
+    library or a GPU, `link` raises _lib.TissueHipError.  `last_stats`: the device call's statistics of the last frame
+    (STAT_NAMES; None for a frame that needed no call)."""
+
+    last_stats = None
+
+    def _find_links(self, points):
+        from . import _lib
+        n, n_tracks = points.shape[0], self.track_id.size
+        self.last_stats = None
+        if n == 0 or n_tracks == 0:
+            return np.full((n,), -1, np.int64)
+        lib = _lib.lib()
+        tracks, points = np.ascontiguousarray(self.track_pos, np.float64), np.ascontiguousarray(points, np.float64)
+        track_of = np.empty((n,), np.int32)
+        stats = np.zeros((6,), np.int64)
+        stop = -1.0 if self.adaptive_stop is None else float(self.adaptive_stop)
+        _lib.check(lib.tip_link_frame_f64(_lib.ptr(tracks), n_tracks, _lib.ptr(points), n, self.search_range, stop, self.adaptive_step,
+                                          MAX_SUBNET, _lib.ptr(track_of), _lib.ptr(stats)))
+        self.last_stats = dict(zip(STAT_NAMES, stats.tolist()))
+        self.last_stats["final_range"] = float(stats[4:5].view(np.float64)[0])
+        if stats[5] == 1:
+            raise SubnetOversizeError("a subnet exceeds %d particles at range %g" % (MAX_SUBNET, self.last_stats["final_range"]))
+        if stats[5]:
+            raise SubnetOversizeError("a subnet still exceeds %d particles at the adaptive_stop range %g"
+                                      % (MAX_SUBNET, self.adaptive_stop))
+        return track_of.astype(np.int64)
+
+
+def make_linker(**kw):
+    """The linker the environment asks for: TISSUE_HIP_LINKER=host (default) gives FrameLinker(**kw), device gives
+    DeviceFrameLinker(**kw); anything else is a ValueError."""
+    import os
+    which = os.environ.get("TISSUE_HIP_LINKER", "host")
+    if which not in ("host", "device"):
+        raise ValueError("TISSUE_HIP_LINKER must be 'host' or 'device', not %r" % (which,))
+    return (DeviceFrameLinker if which == "device" else FrameLinker)(**kw)

@@ -13,7 +13,9 @@ With `estimate_drift=True` the frame-to-frame drift (Tissue.update_drift, ti.py:
 sharded driver as well: the owner of frame t needs frame t-1's reference-channel projection, which lives on rank
 (t-1) % world -- one point-to-point transfer of a (Y, X) float64 plane per frame (33.5 MB at 2048^2, rank r -> r+1 over
 xGMI, all pairs at once) -- and runs the phase correlation next to its own plane.  `stitcher="linker"` replaces the
-label-lookup tracker by the trackpy-model linker (ti.py:1881-1933, linking.FrameLinker) on rank 0.
+label-lookup tracker by the trackpy-model linker (ti.py:1881-1933, linking.FrameLinker) on rank 0, after the last round;
+`stitcher="device_linker"` is that linker with its link finding on the GPU (linking.DeviceFrameLinker, tip_link_frame_f64), fed
+round by round while the next round computes.
 
 With `use_piv=True` the same plane exchange feeds the tracker's PIV mode (ti.py:2061-2106) instead: the owner of frame t
 runs the TV-L1 flow from frame t-1's plane to its own (both truncated to uint16 first, as the GUI loads the movie), samples
@@ -561,22 +563,38 @@ def exchange_planes(sends, recvs, backend, rank, world, dist):
     return prev
 
 
-def link_ids(tables, drifts):
-    """stitcher="linker": track ids from the trackpy-model linker (ti.py:1881-1933) on rank 0: features are the present
-    rows' (cy, cx, area) shifted by the cumulative drift; id = particle + 1, absent rows 0."""
-    from .linking import FrameLinker, embed
-    linker = FrameLinker(search_range=100, adaptive_stop=10, adaptive_step=0.95, memory=3)
-    total = np.zeros(2)
-    out = []
-    for t, tb in enumerate(tables):
-        if t > 0:
-            total = total + np.asarray(drifts[t], dtype=np.float64)
+LINKER_OPTIONS = dict(search_range=100, adaptive_stop=10, adaptive_step=0.95, memory=3)      # ti.py:1881-1933's call
+
+
+class _IdLinker(object):
+    """Track ids from the trackpy-model linker (ti.py:1881-1933), frame after frame: features are the present rows'
+    (cy, cx, area) shifted by the cumulative drift; id = particle + 1, absent rows 0."""
+
+    def __init__(self, linker):
+        self.linker = linker
+        self.total = np.zeros(2)
+        self.ids = []
+
+    def add(self, tb, drift):
+        """The next frame's table and the drift between the previous frame and it."""
+        from .linking import embed
+        if self.ids:
+            self.total = self.total + np.asarray(drift, dtype=np.float64)
         present = np.flatnonzero(tb["area"] > 0)
-        particles = linker.link(embed(tb["cy"][present] + total[0], tb["cx"][present] + total[1], tb["area"][present]))
+        particles = self.linker.link(embed(tb["cy"][present] + self.total[0], tb["cx"][present] + self.total[1], tb["area"][present]))
         ids = np.zeros(tb["area"].size, np.int64)
         ids[present] = np.asarray(particles, dtype=np.int64) + 1
-        out.append(ids)
-    return out
+        self.ids.append(ids)
+
+
+def link_ids(tables, drifts):
+    """stitcher="linker": the ids of _IdLinker over all tables on rank 0, with the linker of linking.make_linker (the host's
+    unless TISSUE_HIP_LINKER=device)."""
+    from .linking import make_linker
+    linked = _IdLinker(make_linker(**LINKER_OPTIONS))
+    for t, tb in enumerate(tables):
+        linked.add(tb, drifts[t])
+    return linked.ids
 
 
 DriftSource = collections.namedtuple("DriftSource", "kind planes local")
@@ -590,8 +608,8 @@ def _drift_source(stitcher, estimate_drift, use_piv, local_drifts, backend):
     chosen = [kind for kind, on in (("estimate", estimate_drift), ("piv", use_piv), ("local", local is not None)) if on]
     if len(chosen) > 1:
         raise ValueError("estimate_drift, use_piv and local_drifts are three drift sources: pass one of them")
-    if stitcher not in ("lookup", "linker"):
-        raise ValueError("stitcher must be 'lookup' or 'linker'")
+    if stitcher not in ("lookup", "linker", "device_linker"):
+        raise ValueError("stitcher must be 'lookup', 'linker' or 'device_linker'")
     kind = chosen[0] if chosen else "given"
     if kind in ("piv", "local"):      # the owner's look-up is the backend's own step
         flag, method = {"piv": ("use_piv", "piv_lookup"), "local": ("local_drifts", "local_drift_lookup")}[kind]
@@ -690,9 +708,19 @@ def _gather_lookups(hits, dist, rank, world, device):
     return {t: found for part in parts for t, found in unpack_lookups(part).items()}
 
 
-def _stitch(tables, lookups, stitcher):
-    """Rank 0's sequential part -> (tables per frame, track ids per frame)."""
+def _link_round(linked, tables):
+    """stitcher="device_linker" on rank 0: the frames that have arrived and are next in order go to the linker.  A round's
+    frames are one contiguous block, so after round k every frame below (k + 1) B W is linked."""
+    while len(linked.ids) in tables:
+        tb = tables[len(linked.ids)]
+        linked.add(tb, tb["drift"])
+
+
+def _stitch(tables, lookups, stitcher, linked=None):
+    """Rank 0's sequential part -> (tables per frame, track ids per frame).  linked: the _IdLinker that has seen every round."""
     tabs = [tables[t] for t in range(len(tables))]
+    if stitcher == "device_linker":
+        return tabs, linked.ids
     if stitcher == "linker":
         return tabs, link_ids(tabs, [tb["drift"] for tb in tabs])
     return tabs, propagate_ids(tabs, [None] + [lookups[t] for t in range(1, len(tabs))])
@@ -724,6 +752,11 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
     extents (Y, X) above window_size and the "lookup" stitcher, and excludes estimate_drift and use_piv (ValueError, before any
     frame is computed).
 
+    stitcher="device_linker": the linker of stitcher="linker" with its link finding on the GPU (linking.DeviceFrameLinker; the
+    same ids, the same exclusions: no use_piv, no local_drifts).  Rank 0 links a round's frames as soon as _exchange_tables has
+    delivered them, while the compute thread works on the next round, so with block_frames the linking is no tail after the
+    last frame either.  stitcher="linker" links all tables at the end, with the linker TISSUE_HIP_LINKER names (default host).
+
     The movie is worked off in ROUNDS of `block_frames` frames per rank (plan_rounds; None: the whole shard in one round, no
     overlap).  While a thread computes round k+1 (_compute_round), this one runs round k's exchange: planes to the neighbour rank
     (exchange_planes), drift (_drift_step), all-gather of the cell tables (_exchange_tables), owner-side look-ups (_owner_lookups;
@@ -738,6 +771,10 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
     rounds = plan_rounds(n_frames, rank, world, block_frames)
     upstream = plan_rounds(n_frames, (rank - 1) % world, world, block_frames)      # the neighbour whose planes arrive here
     tables, lookups, held_planes = {}, {}, {}
+    linked = None
+    if stitcher == "device_linker" and rank == 0:
+        from .linking import DeviceFrameLinker
+        linked = _IdLinker(DeviceFrameLinker(**LINKER_OPTIONS))
     with ThreadPoolExecutor(1) as pool:               # (left only when the compute thread is idle, also by an exception)
         pending = pool.submit(_compute_round, rounds[0], frame_source, backend)
         for k, mine in enumerate(rounds):
@@ -749,13 +786,15 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
                                                    [t for t in upstream[k] if t + 1 < n_frames], backend, rank, world, dist))
             _drift_step(mine, local, drifts, backend, held_planes, source)
             tables.update(_exchange_tables(mine, local, extra, dist, rank, world, device))
-            if stitcher == "linker":
+            if linked is not None:
+                _link_round(linked, tables)
+            if stitcher != "lookup":
                 continue
             hits, failed, error = _owner_lookups(mine, tables, backend, held_planes, source)
             if source.kind == "piv":
                 _agree_on_piv_failure(failed, error, rank, world, dist, device)
             lookups.update(_gather_lookups(hits, dist, rank, world, device))
-    return _stitch(tables, lookups, stitcher) if rank == 0 else (None, None)
+    return _stitch(tables, lookups, stitcher, linked) if rank == 0 else (None, None)
 
 
 def save_seg(path, n_frames, backend, tables, ids, rank=0, world=1, dist=None, device="cpu", channel_names=()):

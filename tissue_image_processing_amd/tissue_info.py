@@ -100,10 +100,10 @@ def _link_two_frames(f, search_range, adaptive_stop, pos_columns, t_column, memo
     """trackpy.link's call signature over linking.FrameLinker for a two-frame table (parity with trackpy unpinned, see
     linking.py): rows of the first frame get particles 0..n-1 in row order, rows of the second the particle of their
     partner or fresh numbers."""
-    from .linking import FrameLinker, embed
+    from .linking import make_linker, embed
     out = f.copy()
     frames = np.sort(f[t_column].unique())
-    linker = FrameLinker(search_range=search_range, adaptive_stop=adaptive_stop, memory=memory)
+    linker = make_linker(search_range=search_range, adaptive_stop=adaptive_stop, memory=memory)
     particle = np.zeros(len(f), np.int64)
     for t in frames:
         rows = np.flatnonzero(f[t_column].to_numpy() == t)
@@ -470,10 +470,10 @@ class TissueHipMixin(object):
         by the cumulative drift -- to trackpy.link_df_iter(search_range=100, adaptive_stop=10, memory=3) and writes
         `label = particle + 1`.  trackpy is a third-party package that is not part of the reference: the linking model
         is restated in linking.py for these parameters (PARITY UNPINNED, see there).  Generator yielding frame numbers."""
-        from .linking import FrameLinker, embed
+        from .linking import make_linker, embed
         last = self.number_of_frames if final_frame == -1 else final_frame
         reuse_drifts = bool((self.drifts > 0).any())
-        linker = FrameLinker(search_range=100, adaptive_stop=10, memory=3)
+        linker = make_linker(search_range=100, adaptive_stop=10, memory=3)      # TISSUE_HIP_LINKER: host (default) or device
         refresh_next = False
         total_dy = total_dx = 0.0
         previous_frame = 0
