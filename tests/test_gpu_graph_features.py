@@ -119,6 +119,22 @@ def test_empty_inputs_and_a_single_label():
     assert seg.contact_sums(*seg.contact_triples(one), off, adj, ones, 0 * ones, None).tolist() == [0]
 
 
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 2049])
+def test_chain_graph_offsets_at_the_scan_chunk_edges(n):
+    """A chain 1 - 2 - ... - n: the single-workgroup scan of the degrees walks n in chunks of 1024, and the total lands behind
+    the last one."""
+    i = np.arange(1, n, dtype=np.int32)
+    off, adj = _seg().neighbor_csr(np.stack([i + 1, i], axis=1), n)
+    deg = np.full(n, 2, np.int64)
+    deg[0] -= 1
+    deg[-1] -= 1
+    np.testing.assert_array_equal(off, np.concatenate([[0], np.cumsum(deg)]))
+    assert off.tolist()[:2] == ([0, 0] if n == 1 else [0, 1])
+    labels = np.arange(1, n + 1)
+    want = np.stack([labels - 1, labels + 1], axis=1).ravel()
+    np.testing.assert_array_equal(adj, want[(want >= 1) & (want <= n)])          # every row: its one or two neighbours, ascending
+
+
 def test_adj_capacity_one_short_is_an_overflow():
     from tissue_image_processing_amd import _lib
     f = gc.frame("H")

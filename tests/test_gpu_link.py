@@ -54,6 +54,27 @@ def test_shifted_coordinates():
     assert _same(_device_run(frames)[0], lc.run(linking.FrameLinker(), frames))
 
 
+def _grid_doublings(points, h):
+    """How often the grid kernel doubles the cell side h for these features (its own loop, on the CPU), and the final side."""
+    fin = points[np.isfinite(points).all(axis=1)]
+    H, W = np.ptp(fin[:, 0]), np.ptp(fin[:, 1])
+    doublings = 0
+    while (np.floor(H / h) + 1.0) * (np.floor(W / h) + 1.0) > points.shape[0] + 4:
+        h, doublings = 2.0 * h, doublings + 1
+    return doublings, h
+
+
+def test_far_apart_copies_double_the_grid_cell():
+    """Movie B next to a copy of itself 3.0e6 / 2.0e6 away: cells of side search_range would outnumber the features, so the grid
+    kernel doubles h twelve times (no other link test doubles it at all); the host linker is the reference as everywhere."""
+    frames = [np.concatenate([f, f + np.array([3.0e6, -2.0e6, 0.0])]) for f in lc.frames_of("B")]
+    assert all(_grid_doublings(f, 100.0) == (12, 409600.0) for f in frames)
+    assert all(_grid_doublings(f, 100.0)[0] == 0 for name in ("A", "B") for f in lc.frames_of(name))
+    ids, stats = _device_run(frames)
+    assert stats[0] is None and all(s is not None and s["oversize"] == 0 and s["links"] > 0 for s in stats[1:])
+    assert _same(ids, lc.run(linking.FrameLinker(), frames))
+
+
 # ---- edges -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("gap", [1, 4], ids=["inside_memory", "outside_memory"])
 def test_empty_frames_between_points(gap):
@@ -170,12 +191,10 @@ def _second_frame_of_a():
     return np.ascontiguousarray(lk.track_pos), np.ascontiguousarray(a[1])
 
 
-def test_device_pointer_form_equals_the_host_pointer_form():
+def _call_dev(tracks, points):
+    """The device-pointer entry on (n_tracks, 3) and (n, 3) arrays -> (track_of_feature, stats)."""
     from tissue_image_processing_amd import _lib
     lib = _lib.lib()
-    tracks, points = _second_frame_of_a()
-    rc, ref, ref_stats = _call(lib.tip_link_frame_f64, tracks, points)
-    assert rc == 0 and ref.max() >= 0 and ref.min() >= -1
     n = points.shape[0]
     d_t, d_p = _lib.DeviceBuffer(tracks.nbytes).upload(tracks), _lib.DeviceBuffer(points.nbytes).upload(points)
     d_out, d_stats = _lib.DeviceBuffer(n * 4), _lib.DeviceBuffer(6 * 8)
@@ -183,11 +202,38 @@ def test_device_pointer_form_equals_the_host_pointer_form():
         _lib.check(lib.tip_link_frame_f64_dev(_lib.dptr(d_t.ptr), tracks.shape[0], _lib.dptr(d_p.ptr), n, 100.0, 10.0, 0.95, 30,
                                               _lib.dptr(d_out.ptr), _lib.dptr(d_stats.ptr)))
         _lib.check(lib.tip_sync())
-        assert np.array_equal(d_out.download((n,), np.int32), ref)
-        assert np.array_equal(d_stats.download((6,), np.int64), ref_stats)
+        return d_out.download((n,), np.int32), d_stats.download((6,), np.int64)
     finally:
         for b in (d_t, d_p, d_out, d_stats):
             b.free()
+
+
+def test_device_pointer_form_equals_the_host_pointer_form():
+    from tissue_image_processing_amd import _lib
+    tracks, points = _second_frame_of_a()
+    rc, ref, ref_stats = _call(_lib.lib().tip_link_frame_f64, tracks, points)
+    assert rc == 0 and ref.max() >= 0 and ref.min() >= -1
+    out, stats = _call_dev(tracks, points)
+    assert np.array_equal(out, ref)
+    assert np.array_equal(stats, ref_stats)
+
+
+def test_device_pointer_form_leaves_non_finite_rows_out():
+    """The host form refuses non-finite rows; the device-pointer form cannot look, so its kernels skip them: a NaN feature gets
+    no track, a track at cx = +inf gets no feature, and everything else is the call without those two rows."""
+    tracks, points = _second_frame_of_a()
+    clean, _ = _call_dev(tracks, points)
+    linked = np.flatnonzero(clean >= 0)
+    bad_f, bad_t = int(linked[0]), int(clean[linked[1]])                       # (both rows take part in the untouched call)
+    bad_tracks, bad_points = tracks.copy(), points.copy()
+    bad_points[bad_f] = np.nan
+    bad_tracks[bad_t, 1] = np.inf
+    out, stats = _call_dev(bad_tracks, bad_points)
+    ref, ref_stats = _call_dev(np.delete(tracks, bad_t, axis=0), np.delete(points, bad_f, axis=0))
+    ref = np.where(ref >= bad_t, ref + 1, ref)                                 # track numbers of the full table
+    assert out[bad_f] == -1
+    assert np.array_equal(np.delete(out, bad_f), ref)
+    assert stats[0] == ref_stats[0] and stats[0] > 0
 
 
 def test_argument_errors_come_back_without_a_launch():

@@ -54,6 +54,41 @@ def test_collinear_points_give_the_chain():
         assert [r.tolist() for r in rows] == [[2, 3], [3, 5], [0, 4], [0, 1], [2], [1]]
 
 
+def _order_grid(py, px):
+    """The grid kernel's cell side and shape for these points (its own formula, on the CPU): (first h, doublings, gx, gy)."""
+    n = len(px)
+    W, H, target = float(np.ptp(px)), float(np.ptp(py)), float(max(n // 2, 1))
+    h0 = np.sqrt(W / target * H) if W > 0 and H > 0 else (max(W, H) / target if W > 0 or H > 0 else 1.0)
+    h, doublings = h0, 0
+    while (np.floor(W / h) + 1.0) * (np.floor(H / h) + 1.0) > n + 4:
+        h, doublings = 2.0 * h, doublings + 1
+    return h0, doublings, int(np.floor(W / h)) + 1, int(np.floor(H / h)) + 1
+
+
+def test_thin_box_doubles_the_grid_cell():
+    """1000 x 1 with 40 points: square cells of two points each would outnumber the points, so h doubles (twice, to a 35 x 1
+    grid); every other case's box is near-square or exactly degenerate."""
+    rng = np.random.default_rng(11)
+    px = rng.uniform(0, 1000, 40)
+    py = rng.uniform(0, 1, 40)
+    h0, doublings, gx, gy = _order_grid(py, px)
+    assert abs(h0 - 6.83) < 0.01 and (doublings, gx, gy) == (2, 35, 1)
+    want = orr.delaunay_neighbors(py, px)
+    assert max(len(r) for r in want) == 11
+    rows = device_rows(py, px)
+    assert_rows_equal(rows, want)
+    assert orr.edges_of(rows) == orr.voronoi_edges(py, px)
+
+
+def test_points_on_an_axis_parallel_line():
+    """W = 0 with distinct py, and its transpose (H = 0): one row or one column of cells of side max(W, H) / (n // 2)."""
+    line, const = np.asarray([0.0, 5.0, 1.0, 9.0, 2.5, 7.0, 4.0]), np.full(7, 3.0)
+    for py, px in ((line, const), (const, line)):
+        rows = device_rows(py, px)
+        assert_rows_equal(rows, orr.delaunay_neighbors(py, px))
+        assert [r.tolist() for r in rows] == [[2], [5, 6], [0, 4], [5], [2, 6], [1, 3], [1, 4]]
+
+
 def test_neighbours_equal_scipy_on_2000_points():
     rng = np.random.default_rng(72)
     py, px = rng.uniform(0, 512, 2000), rng.uniform(0, 512, 2000)

@@ -72,6 +72,32 @@ def test_label_large_vs_oracle(env):
     np.testing.assert_array_equal(out, ref)
 
 
+@pytest.mark.parametrize("side, many_blocks", [(64, False), (2900, True)])
+def test_label_numbering_on_both_sides_of_the_block_sum_threshold(env, side, many_blocks):
+    """The device-wide scan behind the raster-order numbering: up to 4096 scan blocks (8.4 M pixels) every block adds up the block
+    sums in front of it itself (scan_add_own); 2900 x 2900 pixels are 4107 blocks, whose sums one workgroup scans (scan_sums,
+    scan_add).  Small rectangles of distinct values that do not touch, so scipy's components of `image != 0` are the labels."""
+    from scipy import ndimage
+    from gpu_util import launches
+    _, seg, _, _ = env
+    rng = np.random.default_rng(side)
+    pitch = 16 if side == 64 else 100
+    per_row = side // pitch
+    cells = rng.choice(per_row * per_row, size=min(300, per_row * per_row // 2), replace=False)
+    values = rng.permutation(np.arange(1, 5000))[:cells.size]
+    a = np.zeros((side, side), np.int32)
+    for c, v in zip(cells, values):
+        y0, x0 = (c // per_row) * pitch + rng.integers(1, pitch // 2), (c % per_row) * pitch + rng.integers(1, pitch // 2)
+        a[y0:y0 + rng.integers(1, pitch // 2), x0:x0 + rng.integers(1, pitch // 2)] = v      # (stays inside its cell, off its edge)
+    ref, n_ref = ndimage.label(a != 0)
+    with launches() as ran:
+        out, n = seg.label(a, background=0, return_num=True, connectivity=1)
+    assert n == n_ref == cells.size
+    np.testing.assert_array_equal(out, ref)
+    assert ("scan_sums" in ran) == many_blocks and ("scan_add" in ran) == many_blocks and ("scan_add_own" in ran) != many_blocks
+    assert "scan_block" in ran
+
+
 @pytest.mark.parametrize("shape", [(64, 64), (65, 97), (300, 421), (700, 900), (2048, 2048)])
 def test_tiled_union_find_equals_one_level(env, shape):
     """Connected components by tiles in LDS + a border pass (the default from 64 x 64 pixels on) against the one-level union-find

@@ -13,14 +13,6 @@
 
 namespace tip {
 
-int regionprops_dev(const int32_t *labels, const double *intensity, int Y, int X, int n, int64_t *area, int64_t *bbox4,
-                    int64_t *sumy, int64_t *sumx, int64_t *pc3, double *isum);                          // tip_props.hip
-int order_stats_dev(const int32_t *labels, const double *img, long n, int nlab, long long *rank, const long long *rank0,
-                    double *lo, double *hi);                                                             // tip_select.hip
-int gaussian3d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, const double *tz, int nz, const double *ty,
-                   int ny, const double *tx, int nx);                                                    // tip_gauss.hip
-int rankfilter2d_dev(const void *in, void *out, int dtype, int Y, int X, int ky, int kx, int fp, int border, int is_max);   // tip_label.hip
-
 // _segmentation.percentile_per_label / percentile_frame: virt = (count - 1) * (q / 100), prev = clip(floor(virt), 0, count - 1)
 __device__ __forceinline__ long long ct_prev(long long count, double q, double *gamma)
 {
@@ -76,7 +68,7 @@ __global__ void __launch_bounds__(256) k_ct_ranks(const int64_t *__restrict__ ar
 }
 
 // has_peak[l] = 1 when a pixel of label l + 1 is a local maximum of the blurred marker; lanes of a wave that share a label
-// are combined first, so a cell's interior costs one store per wave instead of one per pixel
+// are combined first (wave_combine), so a cell's interior costs one store per wave instead of one per pixel
 __global__ void __launch_bounds__(256) k_ct_peak(const int32_t *__restrict__ labels, const double *__restrict__ blur,
                                                  const double *__restrict__ mx, long P, int n, unsigned int *__restrict__ has_peak)
 {
@@ -87,15 +79,7 @@ __global__ void __launch_bounds__(256) k_ct_peak(const int32_t *__restrict__ lab
         l = labels[i] - 1;
         active = l >= 0 && l < n && fabs(blur[i] - mx[i]) < 1e-6;
     }
-    unsigned long long todo = __ballot(active);
-    const int lane = threadIdx.x & 63;
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int ls = __shfl(l, leader, 64);
-        const unsigned long long same = __ballot(active && l == ls) & todo;
-        if (lane == leader) has_peak[ls] = 1u;
-        todo &= ~same;
-    }
+    wave_combine(active, l, [&](int ls, int) { has_peak[ls] = 1u; });
 }
 
 // per label: validity (ti.py:2360-2367), mean intensity, and the type bit (ti.py:2369-2391)

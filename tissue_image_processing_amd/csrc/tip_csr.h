@@ -1,7 +1,8 @@
 // tip_csr.h -- the CSR pieces shared by the neighbour-graph features (tip_graph.hip) and the Delaunay rows (tip_order.hip):
 // offsets int32[n + 1], adj int32[n_adj] of 1-based labels.  Device side: the label test, the clamped row read, the search in an
-// ascending row and the per-row rank sort.  Host side: the dimension check of both forms and the validation of a HOST CSR before
-// it is uploaded.
+// ascending row, the rank of an entry among its row (row_rank: also how the track linker, tip_link.hip, orders a subnet's members in
+// LDS) and the per-row rank sort.  Host side: the dimension check of both forms and the validation of a HOST CSR before it is
+// uploaded.
 #pragma once
 #include "tip_internal.h"
 
@@ -33,7 +34,20 @@ __device__ __forceinline__ int row_find(const int32_t *__restrict__ adj, int b, 
     return -1;
 }
 
-// one wavefront per row: entry a of raw goes to the slot numbered by the row's entries below it (ties by position), plus `add`.
+// the slot, counted from b, of entry a (of value v) of the row raw[b .. e) in ascending order: the number of entries below it,
+// ties by position
+template <typename Idx>
+__device__ __forceinline__ Idx row_rank(const int32_t *raw, Idx b, Idx e, int v, Idx a)
+{
+    Idx rank = 0;
+    for (Idx c = b; c < e; ++c) {
+        const int w = raw[c];
+        rank += (w < v || (w == v && c < a)) ? 1 : 0;
+    }
+    return rank;
+}
+
+// one wavefront per row: entry a of raw goes to the slot row_rank gives it, plus `add`.
 // Lanes stride over the row in chunks of 64, so a hub row longer than a wavefront takes several chunks.  The row starts at
 // offsets[row] and ends at offsets[row + 1], or row_len[row] entries later when row_len is given; a row that does not fit out
 // (cap) or raw (raw_cap) is left out (the entry point reports the overflow).
@@ -48,12 +62,7 @@ __global__ __launch_bounds__(CSR_BLOCK) void k_rank_sort(const OffT *__restrict_
     if (b < 0 || e < b || e > cap || e > raw_cap) return;
     for (long a = b + lane; a < e; a += CSR_WAVE) {
         const int v = raw[a];
-        long rank = 0;
-        for (long c = b; c < e; ++c) {
-            const int w = raw[c];
-            rank += (w < v || (w == v && c < a)) ? 1 : 0;
-        }
-        out[b + rank] = v + add;
+        out[b + row_rank(raw, b, e, v, a)] = v + add;
     }
 }
 

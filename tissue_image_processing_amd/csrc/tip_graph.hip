@@ -3,9 +3,9 @@
 // calculate_neighbors_correlation_function).  The reference answers every table row with pandas look-ups over Python sets; here
 // the graph is a CSR adjacency (offsets int32[n + 1], adj int32[...] of 1-based labels, ASCENDING within a row) and every feature
 // is one launch over the query rows.  tip_csr.h has the pieces shared with tip_order.hip: label_ok / row_of / row_find, the
-// rank-sort kernel and the host checks of a CSR.
+// rank rule and its sort kernel and the host checks of a CSR; the scan is scan_i32_dev (tip_label.hip, launched as "csr_scan").
 //
-//   k_csr_count / k_scan_i32 / k_csr_fill / k_rank_sort ("csr_sort")
+//   k_csr_count / (scan_i32_dev) / k_csr_fill / k_rank_sort ("csr_sort")
 //                    the CSR from the unique (hi, lo) pairs of tip_neighbor_pairs_i32: a pair gives both directions when
 //                    working[hi - 1] is set (or working is NULL) -- upstream's find_neighbors visits working cells only and finds
 //                    a pair from its larger label (ti.py:1827-1838).  Degrees with atomicAdd, one workgroup's exclusive scan,
@@ -49,38 +49,6 @@ __global__ void k_csr_count(const int32_t *__restrict__ pairs, long np, int n, c
     if (p >= np || !pair_takes_part(pairs, p, n, working, hi, lo)) return;
     atomicAdd(&deg[hi - 1], 1);
     atomicAdd(&deg[lo - 1], 1);
-}
-
-// out[i] = in[0] + ... + in[i - 1] for i = 0 .. n (out[n] = the total); one workgroup walks the array in chunks of 1024
-__global__ __launch_bounds__(1024) void k_scan_i32(const int32_t *__restrict__ in, int32_t *__restrict__ out, int n)
-{
-    __shared__ int s[1024];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + threadIdx.x, v = i < n ? in[i] : 0;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const int t = (int)threadIdx.x >= off ? s[threadIdx.x - off] : 0;
-            __syncthreads();
-            s[threadIdx.x] += t;
-            __syncthreads();
-        }
-        const int incl = s[threadIdx.x], c = carry;
-        if (i < n) out[i] = c + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = c + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[n] = carry;
-}
-
-int scan_i32_dev(const int32_t *in, int32_t *out, int n)
-{
-    TIP_LAUNCH("csr_scan", k_scan_i32, dim3(1), dim3(1024), 0, in, out, n);
-    return TIP_OK;
 }
 
 __global__ void k_csr_fill(const int32_t *__restrict__ pairs, long np, int n, const uint8_t *__restrict__ working,

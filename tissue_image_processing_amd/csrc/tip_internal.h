@@ -172,7 +172,36 @@ constexpr int OF_F64_AS_U16 = 5;
 int optical_flow_tvl1_dev(const void *ref, const void *mov, int dtype, int y, int x, float attachment, float tightness,
                           int num_warp, int num_iter, double tol, float *flow_out, int32_t *warps_host, int cap);
 
-// tip_graph.hip: out[i] = in[0] + ... + in[i - 1] for i = 0 .. n on device arrays (out has n + 1 entries), one workgroup, asynchronous
+// tip_label.hip: exclusive scans of int32 on device arrays, asynchronous.  exclusive_scan_i32: out[i] = in[0] + ... + in[i - 1] for
+// i < n device-wide, the sum to *total_dev (may be NULL).  scan_i32_dev: the same by one workgroup, for the small tables; out
+// has n + 1 entries and out[n] is the sum.
+int exclusive_scan_i32(const int *in, int *out, long n, int *total_dev);
 int scan_i32_dev(const int32_t *in, int32_t *out, int n);
+
+// the device forms one unit borrows from another (their arguments are described where they are defined)
+int regionprops_dev(const int32_t *labels, const double *intensity, int Y, int X, int n, int64_t *area, int64_t *bbox4, int64_t *sumy,
+                    int64_t *sumx, int64_t *pc3, double *isum);                                                          // tip_props.hip
+int order_stats_dev(const int32_t *labels, const double *img, long n, int nlab, long long *rank, const long long *rank0, double *lo,
+                    double *hi);                                                                                         // tip_select.hip
+int gaussian3d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, const double *tz, int nz, const double *ty, int ny,
+                   const double *tx, int nx);                                                                            // tip_gauss.hip
+int rankfilter2d_dev(const void *in, void *out, int dtype, int Y, int X, int ky, int kx, int fp, int border, int is_max);   // tip_label.hip
+int watershed_dev(const double *img, int32_t *labels, int Y, int X, int wsl, int32_t *flags_host);                          // tip_watershed.hip
+
+// Called by whole wavefronts of a 1-D workgroup: f(key, count) runs once for every distinct key among the active lanes, on the
+// first lane that holds it, with the number of lanes that do -- so a wave pays one atomic or one store per key, not per lane.
+template <typename Key, typename F>
+__device__ __forceinline__ void wave_combine(bool active, Key key, F f)
+{
+    unsigned long long todo = __ballot(active);
+    const int lane = threadIdx.x & 63;
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const Key lk = __shfl(key, leader, 64);
+        const unsigned long long same = __ballot(active && key == lk) & todo;
+        if (lane == leader) f(lk, __popcll(same));
+        todo &= ~same;
+    }
+}
 
 }  // namespace tip

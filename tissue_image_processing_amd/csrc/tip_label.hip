@@ -10,7 +10,8 @@
 namespace tip {
 
 // ---------------------------------------------------------------------------------------------------------
-// exclusive scan of int32 (three kernels: per-block scan, scan of block sums, add)
+// exclusive scan of int32 (three kernels: per-block scan, scan of block sums, add); the scan of the block sums alone is
+// scan_i32_dev, the scan of the neighbour graph, the Delaunay rows, the point grid and the track linker
 // ---------------------------------------------------------------------------------------------------------
 constexpr int SCAN_ITEMS = 8, SCAN_THREADS = 256, SCAN_BLOCK = SCAN_ITEMS * SCAN_THREADS;
 
@@ -46,26 +47,27 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_block(const int *__restri
     if (threadIdx.x == SCAN_THREADS - 1) bsum[blockIdx.x] = run;
 }
 
-__global__ void __launch_bounds__(1024) k_scan_sums(int *__restrict__ bsum, int nb, int *__restrict__ total)
+// out[i] = in[0] + ... + in[i - 1] for i = 0 .. n - 1 and *total = their sum (total may be NULL): one workgroup walks the array in
+// chunks of 1024 (Hillis-Steele in LDS) and carries the sum along.  in == out is allowed -- a thread reads its element before any
+// thread of the chunk writes -- so neither is __restrict__.  The scan of the block sums ("scan_sums") and scan_i32_dev.
+__global__ void __launch_bounds__(1024) k_scan_one(const int *in, int *out, int n, int *total)
 {
-    __shared__ int buf[1024];
+    __shared__ int s[1024];
     __shared__ int carry;
     if (threadIdx.x == 0) carry = 0;
     __syncthreads();
-    for (int base = 0; base < nb; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int v = i < nb ? bsum[i] : 0;
-        buf[threadIdx.x] = v;
+    for (int base = 0; base < n; base += 1024) {
+        const int i = base + threadIdx.x, v = i < n ? in[i] : 0;
+        s[threadIdx.x] = v;
         __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const int t = threadIdx.x >= d ? buf[threadIdx.x - d] : 0;
+        for (int off = 1; off < 1024; off <<= 1) {
+            const int t = (int)threadIdx.x >= off ? s[threadIdx.x - off] : 0;
             __syncthreads();
-            buf[threadIdx.x] += t;
+            s[threadIdx.x] += t;
             __syncthreads();
         }
-        const int incl = buf[threadIdx.x];
-        const int c = carry;
-        if (i < nb) bsum[i] = c + incl - v;
+        const int incl = s[threadIdx.x], c = carry;
+        if (i < n) out[i] = c + incl - v;
         __syncthreads();
         if (threadIdx.x == 1023) carry = c + incl;
         __syncthreads();
@@ -115,8 +117,15 @@ int exclusive_scan_i32(const int *in, int *out, long n, int *total_dev)
         TIP_LAUNCH("scan_add_own", k_scan_add_own, dim3(nb), dim3(SCAN_THREADS), 0, out, n, (const int *)bsum, nb, total_dev);
         return TIP_OK;
     }
-    TIP_LAUNCH("scan_sums", k_scan_sums, dim3(1), dim3(1024), 0, bsum, nb, total_dev);
+    TIP_LAUNCH("scan_sums", k_scan_one, dim3(1), dim3(1024), 0, (const int *)bsum, bsum, nb, total_dev);
     TIP_LAUNCH("scan_add", k_scan_add, dim3(nb), dim3(SCAN_THREADS), 0, out, n, (const int *)bsum);
+    return TIP_OK;
+}
+
+// the small tables (cell counts, degrees): the single workgroup alone, out[n] = the total
+int scan_i32_dev(const int32_t *in, int32_t *out, int n)
+{
+    TIP_LAUNCH("csr_scan", k_scan_one, dim3(1), dim3(1024), 0, in, out, n, out + n);
     return TIP_OK;
 }
 

@@ -2,10 +2,11 @@
 // ti.py:1881-1938, and movie.process_movie's linker stitchers).  The model is linking.link_candidates + _solve_subnet; DESIGN.md
 // 5.10 has the argument why the ids are the host's.
 //
-//   k_link_grid / k_link_cell_count / (scan_i32_dev) / k_link_cell_fill
-//                    a uniform grid over the (cy, cx) bounding box of the finite features, cells of side h >= search_range (h doubles
-//                    until the grid has at most n + 4 cells: coordinates may be far apart after cumulative drift); the features
-//                    (cy, cx, a, position) copied cell by cell, so the cells x0 .. x1 of one grid row are one contiguous range.
+//   point_grid_launch (tip_grid.h; launched as "link_grid" / "link_cell_count" / "csr_scan" / "link_cell_fill")
+//                    the uniform grid over the (cy, cx) bounding box of the finite features, cells of side h >= search_range (h
+//                    doubles until the grid has at most n + 4 cells: coordinates may be far apart after cumulative drift); the
+//                    features (cy, cx, a, position) copied cell by cell, so the cells x0 .. x1 of one grid row are one contiguous
+//                    range (rect_row).
 //   k_link_candidates<false / true> / (scan_i32_dev)
 //                    one thread per track: the features of the cells within one cell of the track's (h >= search_range, so nothing
 //                    in reach lies further; the cell range is taken with a 1e-6 cell margin against the rounding of the division),
@@ -22,13 +23,15 @@
 //   k_link_solve     the subnet's augmented cost matrix in LDS, exactly _solve_subnet's: rows = tracks + one row per feature,
 //                    columns = features + one column per track, d d on links, range^2 on "track lost" / "feature is new", 0 in the
 //                    dummy block, 1e18 elsewhere (60 x 60 doubles = 28.8 KB: five subnets per CU), members ranked into ascending
-//                    order first (np.unique's; the order in which the atomics handed out the slots leaves no trace).  The
+//                    order first (np.unique's, by row_rank of tip_csr.h; the order in which the atomics handed out the slots leaves no trace).  The
 //                    assignment is scipy's linear_sum_assignment step for step -- shortest augmenting paths with potentials, one
 //                    lane per column, the minimum by a wave reduction, scipy's arithmetic and scipy's choice among equal
 //                    candidates -- so that a subnet with several optimal assignments (cells on a lattice: exact ties do occur)
 //                    gets the one the host linker gets.
 // Every index read from memory is checked before it is used, every write is checked against its capacity.
 #include <cmath>
+#include "tip_csr.h"
+#include "tip_grid.h"
 #include "tip_uf.h"
 
 namespace tip {
@@ -37,83 +40,7 @@ constexpr int L_MAX = 30, L_N = 2 * L_MAX;          // linking.MAX_SUBNET and th
 constexpr double L_BIG = 1e18, L_INF = __builtin_huge_val();
 enum { LS_OVER = 0, LS_LIVE = 1, LS_SUBNETS = 2, LS_LARGEST = 3, LS_WORDS = 4 };
 
-struct LGrid {
-    double miny, minx, h;
-    int gy, gx;
-};
-
 __device__ __forceinline__ bool finite3(const double *__restrict__ p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
-
-__device__ __forceinline__ double cell_pos(double v, double lo, double h) { return __ddiv_rn(__dsub_rn(v, lo), h); }
-
-__device__ __forceinline__ int clamp_cell(double c, int g)
-{
-    c = floor(c);
-    if (!(c >= 0.0)) return 0;
-    return c > (double)(g - 1) ? g - 1 : (int)c;
-}
-
-__global__ __launch_bounds__(256) void k_link_grid(const double *__restrict__ pts, int n, double range, int cell_cap, LGrid *__restrict__ g)
-{
-    __shared__ double s[4][256];
-    double y0 = L_INF, y1 = -L_INF, x0 = L_INF, x1 = -L_INF;
-    for (int p = threadIdx.x; p < n; p += 256) {
-        const double *q = pts + 3 * (long)p;
-        if (!finite3(q)) continue;
-        y0 = fmin(y0, q[0]), y1 = fmax(y1, q[0]), x0 = fmin(x0, q[1]), x1 = fmax(x1, q[1]);
-    }
-    s[0][threadIdx.x] = y0, s[1][threadIdx.x] = y1, s[2][threadIdx.x] = x0, s[3][threadIdx.x] = x1;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            s[0][threadIdx.x] = fmin(s[0][threadIdx.x], s[0][threadIdx.x + off]);
-            s[1][threadIdx.x] = fmax(s[1][threadIdx.x], s[1][threadIdx.x + off]);
-            s[2][threadIdx.x] = fmin(s[2][threadIdx.x], s[2][threadIdx.x + off]);
-            s[3][threadIdx.x] = fmax(s[3][threadIdx.x], s[3][threadIdx.x + off]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-    y0 = s[0][0], y1 = s[1][0], x0 = s[2][0], x1 = s[3][0];
-    if (!(y0 <= y1)) y0 = y1 = x0 = x1 = 0.0;      // no finite feature
-    const double H = y1 - y0, W = x1 - x0;
-    double h = range, fy = 1.0, fx = 1.0;
-    bool ok = false;
-    for (int it = 0; it < 2200 && !ok; ++it) {     // (far-apart coordinates: cells of side range would outnumber the features; h doubles)
-        fy = floor(H / h) + 1.0, fx = floor(W / h) + 1.0;
-        ok = fy * fx <= (double)cell_cap;
-        if (!ok) h *= 2.0;
-    }
-    if (!ok) fy = fx = 1.0, h = L_INF;
-    g->miny = y0, g->minx = x0, g->h = h, g->gy = (int)fy, g->gx = (int)fx;
-}
-
-__global__ void k_link_cell_count(const double *__restrict__ pts, int n, const LGrid *__restrict__ gp, int cell_cap,
-                                  int32_t *__restrict__ cell_of, int32_t *__restrict__ cnt)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const LGrid g = *gp;
-    const double *q = pts + 3 * (long)p;
-    int c = -1;
-    if (finite3(q)) c = clamp_cell(cell_pos(q[0], g.miny, g.h), g.gy) * g.gx + clamp_cell(cell_pos(q[1], g.minx, g.h), g.gx);
-    if (c >= cell_cap) c = -1;
-    cell_of[p] = c;
-    if (c >= 0) atomicAdd(&cnt[c], 1);
-}
-
-__global__ void k_link_cell_fill(const double *__restrict__ pts, int n, const int32_t *__restrict__ cell_of, const int32_t *__restrict__ start,
-                                 int32_t *__restrict__ cursor, double *__restrict__ spt, int32_t *__restrict__ sidx)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int c = cell_of[p];
-    if (c < 0) return;
-    const long pos = (long)start[c] + atomicAdd(&cursor[c], 1);
-    if (pos < 0 || pos >= n) return;
-    const double *q = pts + 3 * (long)p;
-    spt[3 * pos] = q[0], spt[3 * pos + 1] = q[1], spt[3 * pos + 2] = q[2], sidx[pos] = p;
-}
 
 // the cells [lo, hi] of one axis that can hold a feature within one cell side of position c (in cells); false: none
 __device__ __forceinline__ bool cell_reach(double c, int g, int &lo, int &hi)
@@ -127,25 +54,25 @@ __device__ __forceinline__ bool cell_reach(double c, int g, int &lo, int &hi)
 
 // FILL false: deg[s] = the links of track s, *total += them.  FILL true: the links at lstart[s] ...
 template <bool FILL>
-__global__ void k_link_candidates(const double *__restrict__ trk, int nt, const LGrid *__restrict__ gp, const int32_t *__restrict__ start,
+__global__ void k_link_candidates(const double *__restrict__ trk, int nt, const PointGrid *__restrict__ gp, const int32_t *__restrict__ start,
                                   int cell_cap, const double *__restrict__ spt, const int32_t *__restrict__ sidx, int n, double range,
                                   int32_t *__restrict__ deg, unsigned long long *__restrict__ total, const int32_t *__restrict__ lstart,
                                   int32_t *__restrict__ les, int32_t *__restrict__ led, double *__restrict__ lev, long n_links)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nt) return;
-    const LGrid g = *gp;
+    const PointGrid g = *gp;
     const double *t = trk + 3 * (long)s;
     int n_fin = start[cell_cap];
     if (n_fin > n) n_fin = n;
     const long base = FILL ? (long)lstart[s] : 0;
-    int found = 0, y0, y1, x0, x1;
-    if (finite3(t) && g.gx >= 1 && g.gy >= 1 && (long)g.gx * g.gy <= cell_cap && cell_reach(cell_pos(t[0], g.miny, g.h), g.gy, y0, y1) &&
-        cell_reach(cell_pos(t[1], g.minx, g.h), g.gx, x0, x1)) {
-        for (int row = y0; row <= y1; ++row) {
-            int b = start[row * g.gx + x0], e = start[row * g.gx + x1 + 1];
-            if (b < 0) b = 0;
-            if (e > n_fin) e = n_fin;
+    int found = 0;
+    CellRect rc;
+    if (finite3(t) && g.gx >= 1 && g.gy >= 1 && (long)g.gx * g.gy <= cell_cap && cell_reach(cell_pos(t[0], g.miny, g.h), g.gy, rc.y0, rc.y1) &&
+        cell_reach(cell_pos(t[1], g.minx, g.h), g.gx, rc.x0, rc.x1)) {
+        for (int row = rc.y0; row <= rc.y1; ++row) {
+            int b, e;
+            rect_row(start, g, rc, row, n_fin, b, e);
             for (int j = b; j < e; ++j) {
                 const double dy = __dsub_rn(t[0], spt[3 * (long)j]), dx = __dsub_rn(t[1], spt[3 * (long)j + 1]);
                 const double da = __dsub_rn(t[2], spt[3 * (long)j + 2]);
@@ -224,16 +151,8 @@ __global__ __launch_bounds__(64) void k_link_solve(const int *__restrict__ paren
     if (lane < ct) raw_t[lane] = mt;
     if (lane < cf) raw_f[lane] = mf;
     __syncthreads();
-    if (lane < ct) {
-        int rank = 0;
-        for (int c = 0; c < ct; ++c) rank += (raw_t[c] < mt || (raw_t[c] == mt && c < lane)) ? 1 : 0;
-        st[rank] = mt;
-    }
-    if (lane < cf) {
-        int rank = 0;
-        for (int c = 0; c < cf; ++c) rank += (raw_f[c] < mf || (raw_f[c] == mf && c < lane)) ? 1 : 0;
-        sf[rank] = mf;
-    }
+    if (lane < ct) st[row_rank(raw_t, 0, ct, mt, lane)] = mt;
+    if (lane < cf) sf[row_rank(raw_f, 0, cf, mf, lane)] = mf;
     const int N = ct + cf;
     for (int e = lane; e < N * N; e += 64) {
         const int i = e / N, j = e - i * N;
@@ -361,24 +280,19 @@ static int link_frame_launch(const double *trk, int64_t nt, const double *pts, i
     if (n) TIP_HIP(hipMemsetAsync(track_of_feature, 0xff, (size_t)n * 4, c.stream));
     if (n == 0 || nt == 0) return TIP_OK;
     WsGuard ws;
-    const int cell_cap = (int)(n < 0x7ffffff0 - 4 ? n + 4 : 0x7ffffff0);
-    LGrid *g = ws.get<LGrid>(1);
-    int32_t *cell_of = ws.get<int32_t>((size_t)n), *cnt = ws.get<int32_t>((size_t)cell_cap), *start = ws.get<int32_t>((size_t)cell_cap + 1);
-    int32_t *sidx = ws.get<int32_t>((size_t)n), *deg = ws.get<int32_t>((size_t)nt), *lstart = ws.get<int32_t>((size_t)nt + 1);
-    double *spt = ws.get<double>((size_t)n * 3);
+    static const char *const names[3] = {"link_grid", "link_cell_count", "link_cell_fill"};
+    PointGridArrays gr;
+    if (int rc = point_grid_launch(ws, PointsRows3{pts}, n, SideGiven{search_range}, names, gr)) return rc;
+    const int cell_cap = gr.cell_cap;
+    const PointGrid *g = gr.g;
+    const int32_t *start = gr.start, *sidx = gr.sidx;
+    const double *spt = gr.payload;
+    int32_t *deg = ws.get<int32_t>((size_t)nt), *lstart = ws.get<int32_t>((size_t)nt + 1);
     unsigned long long *total = ws.get<unsigned long long>(1);
-    if (!g || !cell_of || !cnt || !start || !sidx || !deg || !lstart || !spt || !total) return TIP_ERR_NOMEM;
-    TIP_HIP(hipMemsetAsync(cnt, 0, (size_t)cell_cap * 4, c.stream));
+    if (!deg || !lstart || !total) return TIP_ERR_NOMEM;
     TIP_HIP(hipMemsetAsync(total, 0, 8, c.stream));
-    TIP_LAUNCH("link_grid", k_link_grid, dim3(1), dim3(256), 0, pts, (int)n, search_range, cell_cap, g);
-    TIP_LAUNCH("link_cell_count", k_link_cell_count, dim3(cdiv(n, 256)), dim3(256), 0, pts, (int)n, (const LGrid *)g, cell_cap, cell_of, cnt);
-    if (int rc = scan_i32_dev(cnt, start, cell_cap)) return rc;
-    TIP_HIP(hipMemsetAsync(cnt, 0, (size_t)cell_cap * 4, c.stream));
-    TIP_LAUNCH("link_cell_fill", k_link_cell_fill, dim3(cdiv(n, 256)), dim3(256), 0, pts, (int)n, (const int32_t *)cell_of, (const int32_t *)start,
-               cnt, spt, sidx);
-    TIP_LAUNCH("link_count", k_link_candidates<false>, dim3(cdiv(nt, 64)), dim3(64), 0, trk, (int)nt, (const LGrid *)g, (const int32_t *)start,
-               cell_cap, (const double *)spt, (const int32_t *)sidx, (int)n, search_range, deg, total, (const int32_t *)nullptr,
-               (int32_t *)nullptr, (int32_t *)nullptr, (double *)nullptr, 0L);
+    TIP_LAUNCH("link_count", k_link_candidates<false>, dim3(cdiv(nt, 64)), dim3(64), 0, trk, (int)nt, g, start, cell_cap, spt, sidx, (int)n,
+               search_range, deg, total, (const int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (double *)nullptr, 0L);
     if (int rc = scan_i32_dev(deg, lstart, (int)nt)) return rc;
     unsigned long long n_links_host = 0;
     TIP_HIP(hipMemcpyAsync(&n_links_host, total, 8, hipMemcpyDeviceToHost, c.stream));
@@ -401,9 +315,8 @@ static int link_frame_launch(const double *trk, int64_t nt, const double *pts, i
     TIP_HIP(hipMemsetAsync(lev, 0, (size_t)n_links * 8, c.stream));
     TIP_HIP(hipMemsetAsync(alive, 1, (size_t)n_links, c.stream));
     TIP_HIP(hipMemsetAsync(status, 0, LS_WORDS * 4, c.stream));
-    TIP_LAUNCH("link_fill", k_link_candidates<true>, dim3(cdiv(nt, 64)), dim3(64), 0, trk, (int)nt, (const LGrid *)g, (const int32_t *)start,
-               cell_cap, (const double *)spt, (const int32_t *)sidx, (int)n, search_range, (int32_t *)nullptr, (unsigned long long *)nullptr,
-               (const int32_t *)lstart, les, led, lev, n_links);
+    TIP_LAUNCH("link_fill", k_link_candidates<true>, dim3(cdiv(nt, 64)), dim3(64), 0, trk, (int)nt, g, start, cell_cap, spt, sidx, (int)n,
+               search_range, (int32_t *)nullptr, (unsigned long long *)nullptr, (const int32_t *)lstart, les, led, lev, n_links);
     double rng = search_range;
     volatile double two = 2.0;      // the null cost is Python's `rng ** 2`: libm's pow at run time, which is not always rng * rng
     for (;;) {

@@ -3,11 +3,10 @@
 // per-row columns behind calculate_neighbors_correlation_function (ti.py:803-843; their kernel, k_neighbor_state, walks the
 // neighbour CSR and lives in tip_graph.hip).  DESIGN.md 5.8 has the argument.
 //
-//   k_order_grid / k_order_count / (scan_i32_dev) / k_order_fill
-//                    a uniform grid over the bounding box of the finite points, about two points per square cell of side h:
-//                    bounding box and grid shape in one workgroup, points counted into cells with atomicAdd, the exclusive scan
-//                    of tip_graph.hip, then the points (x, y, position) copied cell by cell -- the points of the cells x0 .. x1
-//                    of one grid row are one contiguous range.  A point with a non-finite coordinate takes no part.
+//   point_grid_launch (tip_grid.h; launched as "order_grid" / "order_count" / "csr_scan" / "order_fill")
+//                    the uniform grid over the bounding box of the finite points, first cell side about two points per square
+//                    cell; the points (x, y, position) copied cell by cell -- the points of the cells x0 .. x1 of one grid row are
+//                    one contiguous range (rect_row).  A point with a non-finite coordinate takes no part.
 //   k_delaunay       one wavefront (one 64-thread workgroup) per point i.  Candidates are the points of the cells within r cells
 //                    of i's cell (r = 2, 4, 8, ...); the lanes stride over the candidates j, and for each j the interval test
 //                    runs over the candidates k:   a = p_j - p_i, b = p_k - p_i,   s = a.x b.y - a.y b.x,
@@ -21,96 +20,18 @@
 //                    point) ends with the whole grid.  A candidate list of at most O_CAP points is held in LDS; a longer one
 //                    streams from global memory, each j first against the last list that did fit (nearly every far j dies there).
 //                    The certified sweep is repeated to write the members (two-call convention: sizes, the caller's scan,
-//                    members), unsorted into a scratch row that k_rank_sort (tip_csr.h, launched as "order_row_sort") ranks into
-//                    ascending order.  No degree cap.
+//                    members), unsorted into a scratch row that k_rank_sort (tip_csr.h: row_rank; launched as "order_row_sort")
+//                    ranks into ascending order.  No degree cap.
 //   k_psin           one thread per query row: hypot(sum cos(n theta), sum sin(n theta)) / count over the row's members.
 // Every index read from memory is checked before it is used, every write is checked against its capacity.
 #include <cmath>
 #include "tip_csr.h"
+#include "tip_grid.h"
 
 namespace tip {
 
 constexpr int O_CAP = 512;          // candidates held in LDS per wavefront (20 bytes each)
 constexpr double O_INF = __builtin_huge_val();
-
-struct OGrid {
-    double minx, miny, h;
-    int gx, gy;
-};
-
-__device__ __forceinline__ bool finite2(double a, double b) { return isfinite(a) && isfinite(b); }
-
-__device__ __forceinline__ int cell_coord(double v, double lo, double h, int g)
-{
-    const double c = floor(__ddiv_rn(__dsub_rn(v, lo), h));
-    if (!(c >= 0.0)) return 0;
-    return c > (double)(g - 1) ? g - 1 : (int)c;
-}
-
-__global__ __launch_bounds__(256) void k_order_grid(const double *__restrict__ py, const double *__restrict__ px, int n, int cell_cap,
-                                                    OGrid *__restrict__ g)
-{
-    __shared__ double s[4][256];
-    double x0 = O_INF, x1 = -O_INF, y0 = O_INF, y1 = -O_INF;
-    for (int p = threadIdx.x; p < n; p += 256) {
-        const double x = px[p], y = py[p];
-        if (!finite2(x, y)) continue;
-        x0 = fmin(x0, x), x1 = fmax(x1, x), y0 = fmin(y0, y), y1 = fmax(y1, y);
-    }
-    s[0][threadIdx.x] = x0, s[1][threadIdx.x] = x1, s[2][threadIdx.x] = y0, s[3][threadIdx.x] = y1;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            s[0][threadIdx.x] = fmin(s[0][threadIdx.x], s[0][threadIdx.x + off]);
-            s[1][threadIdx.x] = fmax(s[1][threadIdx.x], s[1][threadIdx.x + off]);
-            s[2][threadIdx.x] = fmin(s[2][threadIdx.x], s[2][threadIdx.x + off]);
-            s[3][threadIdx.x] = fmax(s[3][threadIdx.x], s[3][threadIdx.x + off]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-    x0 = s[0][0], x1 = s[1][0], y0 = s[2][0], y1 = s[3][0];
-    if (!(x0 <= x1)) x0 = x1 = y0 = y1 = 0.0;      // no finite point
-    const double W = x1 - x0, H = y1 - y0, target = n / 2 > 1 ? (double)(n / 2) : 1.0;
-    double h = W > 0.0 && H > 0.0 ? sqrt(W / target * H) : (W > 0.0 || H > 0.0 ? fmax(W, H) / target : 1.0);
-    if (!(h > 0.0) || !isfinite(h)) h = 1.0;
-    double fx = 1.0, fy = 1.0;
-    bool ok = false;
-    for (int it = 0; it < 2200 && !ok; ++it) {     // (a thin box: cells of side h would outnumber the points; h doubles)
-        fx = floor(W / h) + 1.0, fy = floor(H / h) + 1.0;
-        ok = fx * fy <= (double)cell_cap;
-        if (!ok) h *= 2.0;
-    }
-    if (!ok) fx = fy = 1.0, h = O_INF;
-    g->minx = x0, g->miny = y0, g->h = h, g->gx = (int)fx, g->gy = (int)fy;
-}
-
-__global__ void k_order_count(const double *__restrict__ py, const double *__restrict__ px, int n, const OGrid *__restrict__ gp,
-                              int cell_cap, int32_t *__restrict__ cell_of, int32_t *__restrict__ cnt)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const OGrid g = *gp;
-    const double x = px[p], y = py[p];
-    int c = -1;
-    if (finite2(x, y)) c = cell_coord(y, g.miny, g.h, g.gy) * g.gx + cell_coord(x, g.minx, g.h, g.gx);
-    if (c >= cell_cap) c = -1;
-    cell_of[p] = c;
-    if (c >= 0) atomicAdd(&cnt[c], 1);
-}
-
-__global__ void k_order_fill(const double *__restrict__ py, const double *__restrict__ px, int n, const int32_t *__restrict__ cell_of,
-                             const int32_t *__restrict__ start, int32_t *__restrict__ cursor, double *__restrict__ sx,
-                             double *__restrict__ sy, int32_t *__restrict__ sidx)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int c = cell_of[p];
-    if (c < 0) return;
-    const long pos = (long)start[c] + atomicAdd(&cursor[c], 1);
-    if (pos < 0 || pos >= n) return;
-    sx[pos] = px[p], sy[pos] = py[p], sidx[pos] = p;
-}
 
 // the interval of pair (i, j), a = p_j - p_i, cut by one point b = p_k - p_i.  k = i (b = 0) and k = j (b = a) give s = 0 and
 // |b|^2 - a.b = 0 exactly and cut nothing, so the callers do not single them out.
@@ -126,17 +47,6 @@ __device__ __forceinline__ void cut(double ax, double ay, double bx, double by, 
         else lo = fmax(lo, t);
     }
     if (!(lo < hi)) alive = false;
-}
-
-struct ORect { int x0, x1, y0, y1; };
-
-__device__ __forceinline__ void rect_row(const int32_t *__restrict__ start, const OGrid &g, const ORect &rc, int row, int n_fin, int &b, int &e)
-{
-    b = start[row * g.gx + rc.x0];
-    e = start[row * g.gx + rc.x1 + 1];
-    if (b < 0) b = 0;
-    if (e > n_fin) e = n_fin;
-    if (e < b) e = b;
 }
 
 // squared distance from p_i to the farther end of a live pair's interval (the circle's centre is a / 2 + t perp(a))
@@ -156,7 +66,7 @@ struct OSweep {
 // they stream from the sorted arrays and the staged points are only the first filter.  raw != NULL: the edges' point positions
 // go to raw[raw_base ...] (bounded by raw_cap).
 __device__ OSweep sweep(const double *__restrict__ kx, const double *__restrict__ ky, const int *__restrict__ ki, int n_near, bool in_lds,
-                        const int32_t *__restrict__ start, const OGrid &g, const ORect &rc, int n_fin, const double *__restrict__ sx,
+                        const int32_t *__restrict__ start, const PointGrid &g, const CellRect &rc, int n_fin, const double *__restrict__ sx,
                         const double *__restrict__ sy, const int32_t *__restrict__ sidx, double xi, double yi, int i, int lane,
                         int32_t *__restrict__ raw, long raw_base, long raw_cap)
 {
@@ -200,7 +110,7 @@ __device__ OSweep sweep(const double *__restrict__ kx, const double *__restrict_
 }
 
 template <typename OffT>
-__global__ __launch_bounds__(64) void k_delaunay(const OGrid *__restrict__ gp, const int32_t *__restrict__ start, int cell_cap,
+__global__ __launch_bounds__(64) void k_delaunay(const PointGrid *__restrict__ gp, const int32_t *__restrict__ start, int cell_cap,
                                                  const double *__restrict__ sx, const double *__restrict__ sy,
                                                  const int32_t *__restrict__ sidx, int n, int64_t *__restrict__ sizes,
                                                  int32_t *__restrict__ deg32, const OffT *__restrict__ moff, int32_t *__restrict__ raw,
@@ -209,7 +119,7 @@ __global__ __launch_bounds__(64) void k_delaunay(const OGrid *__restrict__ gp, c
     __shared__ double kx[O_CAP], ky[O_CAP];
     __shared__ int ki[O_CAP];
     const int lane = threadIdx.x;
-    const OGrid g = *gp;
+    const PointGrid g = *gp;
     int n_fin = start[cell_cap];
     if (n_fin > n) n_fin = n;
     const int p = blockIdx.x;                       // the same for every lane: all control flow below is uniform
@@ -222,7 +132,7 @@ __global__ __launch_bounds__(64) void k_delaunay(const OGrid *__restrict__ gp, c
     int n_near = 0;
     long total = 0;
     for (long r = 2;; r *= 2) {
-        ORect rc;
+        CellRect rc;
         rc.x0 = (int)((long)cxi - r > 0 ? (long)cxi - r : 0), rc.x1 = (int)((long)cxi + r < g.gx - 1 ? (long)cxi + r : g.gx - 1);
         rc.y0 = (int)((long)cyi - r > 0 ? (long)cyi - r : 0), rc.y1 = (int)((long)cyi + r < g.gy - 1 ? (long)cyi + r : g.gy - 1);
         const bool whole = rc.x0 == 0 && rc.y0 == 0 && rc.x1 == g.gx - 1 && rc.y1 == g.gy - 1;
@@ -304,23 +214,15 @@ static int delaunay_launch(const double *py, const double *px, int64_t n, int64_
     if (deg32 && n) TIP_HIP(hipMemsetAsync(deg32, 0, (size_t)n * 4, c.stream));
     if (n < 2) return TIP_OK;
     WsGuard ws;
-    const int cell_cap = (int)(n < 0x7ffffff0 - 4 ? n + 4 : 0x7ffffff0);
-    OGrid *g = ws.get<OGrid>(1);
-    int32_t *cell_of = ws.get<int32_t>((size_t)n), *cnt = ws.get<int32_t>((size_t)cell_cap), *start = ws.get<int32_t>((size_t)cell_cap + 1);
-    int32_t *sidx = ws.get<int32_t>((size_t)n), *raw = members ? ws.get<int32_t>((size_t)members_cap) : nullptr;
-    int32_t *row_len = members ? ws.get<int32_t>((size_t)n) : nullptr;
-    double *sx = ws.get<double>((size_t)n), *sy = ws.get<double>((size_t)n);
-    if (!g || !cell_of || !cnt || !start || !sidx || !sx || !sy || (members && (!raw || !row_len))) return TIP_ERR_NOMEM;
-    TIP_HIP(hipMemsetAsync(cnt, 0, (size_t)cell_cap * 4, c.stream));
-    TIP_LAUNCH("order_grid", k_order_grid, dim3(1), dim3(256), 0, py, px, (int)n, cell_cap, g);
-    TIP_LAUNCH("order_count", k_order_count, dim3(cdiv(n, 256)), dim3(256), 0, py, px, (int)n, (const OGrid *)g, cell_cap, cell_of, cnt);
-    if (int rc = scan_i32_dev(cnt, start, cell_cap)) return rc;
-    TIP_HIP(hipMemsetAsync(cnt, 0, (size_t)cell_cap * 4, c.stream));
-    TIP_LAUNCH("order_fill", k_order_fill, dim3(cdiv(n, 256)), dim3(256), 0, py, px, (int)n, (const int32_t *)cell_of, (const int32_t *)start, cnt,
-               sx, sy, sidx);
+    static const char *const names[3] = {"order_grid", "order_count", "order_fill"};
+    PointGridArrays gr;
+    if (int rc = point_grid_launch(ws, PointsYX{py, px}, n, SideTwoPerCell{}, names, gr)) return rc;
+    int32_t *raw = members ? ws.get<int32_t>((size_t)members_cap) : nullptr, *row_len = members ? ws.get<int32_t>((size_t)n) : nullptr;
+    if (members && (!raw || !row_len)) return TIP_ERR_NOMEM;
     if (row_len) TIP_HIP(hipMemsetAsync(row_len, 0, (size_t)n * 4, c.stream));
-    TIP_LAUNCH("delaunay", k_delaunay<OffT>, dim3((unsigned)n), dim3(64), 0, (const OGrid *)g, (const int32_t *)start, cell_cap, (const double *)sx,
-               (const double *)sy, (const int32_t *)sidx, (int)n, sizes, deg32, moff, raw, row_len, (long)members_cap);
+    TIP_LAUNCH("delaunay", k_delaunay<OffT>, dim3((unsigned)n), dim3(64), 0, (const PointGrid *)gr.g, (const int32_t *)gr.start, gr.cell_cap,
+               (const double *)gr.payload, (const double *)gr.payload + plane_pitch(n), (const int32_t *)gr.sidx, (int)n, sizes, deg32, moff, raw, row_len,
+               (long)members_cap);
     if (members)
         TIP_LAUNCH("order_row_sort", k_rank_sort<OffT>, dim3(cdiv(n, CSR_WPB)), dim3(CSR_BLOCK), 0, moff, (const int32_t *)row_len,
                    (const int32_t *)raw, (long)members_cap, members, (int)n, (long)members_cap, add);

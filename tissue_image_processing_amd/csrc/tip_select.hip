@@ -23,22 +23,9 @@ __device__ __forceinline__ double sel_dec(unsigned long long e)
     return __longlong_as_double((long long)b);
 }
 
-// add 1 to hist[slot] for every active lane, lanes with equal slots combined into one atomic (neighbouring pixels mostly
-// share label and leading digits: a wave touches a handful of distinct slots)
-__device__ __forceinline__ void wave_hist_add(bool active, long slot, unsigned int *__restrict__ hist)
-{
-    unsigned long long todo = __ballot(active);
-    const int lane = threadIdx.x & 63;
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const long ls = __shfl(slot, leader, 64);
-        const unsigned long long same = __ballot(active && slot == ls) & todo;
-        if (lane == leader) atomicAdd(&hist[ls], (unsigned int)__popcll(same));
-        todo &= ~same;
-    }
-}
-
-// one digit: labels == nullptr -> a single pseudo-label 0 for every pixel (whole-frame statistic)
+// one digit: labels == nullptr -> a single pseudo-label 0 for every pixel (whole-frame statistic).  Per label, the lanes of a wave
+// with equal slots are combined into one atomic (wave_combine: neighbouring pixels mostly share label and leading digits, so a
+// wave touches a handful of distinct slots)
 __global__ void __launch_bounds__(256) k_sel_hist(const int32_t *__restrict__ labels, const double *__restrict__ img, long n, int nlab,
                                                   const unsigned long long *__restrict__ prefix, int shift,
                                                   unsigned int *__restrict__ hist)
@@ -60,7 +47,7 @@ __global__ void __launch_bounds__(256) k_sel_hist(const int32_t *__restrict__ la
         }
         const int bin = (int)((key >> shift) & 255ULL);
         if (whole) { if (active) atomicAdd(&sh[bin], 1u); }
-        else wave_hist_add(active, (long)l * 256 + bin, hist);
+        else wave_combine(active, (long)l * 256 + bin, [&](long slot, int count) { atomicAdd(&hist[slot], (unsigned int)count); });
     }
     if (whole) {
         __syncthreads();
@@ -117,8 +104,9 @@ __global__ void __launch_bounds__(256) k_sel_emit(const unsigned long long *__re
 }
 
 // The select on device-resident ranks, asynchronous on the context stream: rank[l] (consumed: it ends as the rank inside the
-// selected key) and rank0[l] (kept) hold the 0-based rank asked of label l + 1, < 0 for an absent label; lo / hi are device
-// arrays of nlab values (see label_order_stats_dev).  labels == nullptr: nlab must be 1 (the whole frame).
+// selected key) and rank0[l] (kept) hold the 0-based rank asked of label l + 1, < 0 for an absent label.  lo / hi are device
+// arrays of nlab values: lo[l] = the value of that rank among the pixels of label l + 1, hi[l] = the value of the next rank (= lo
+// when there is none).  labels == nullptr: nlab must be 1 (the whole frame).
 int order_stats_dev(const int32_t *labels, const double *img, long n, int nlab, long long *rank, const long long *rank0, double *lo,
                     double *hi)
 {
@@ -145,31 +133,6 @@ int order_stats_dev(const int32_t *labels, const double *img, long n, int nlab, 
     return TIP_OK;
 }
 
-// lo[l] = value of rank ranks[l] (0-based) among the pixels of label l + 1, hi[l] = value of rank ranks[l] + 1 (= lo when
-// there is none); ranks[l] < 0: label absent.  labels == nullptr: nlab must be 1 (the whole frame).  Host ranks in, host
-// values out (synchronises).
-int label_order_stats_dev(const int32_t *labels, const double *img, long n, int nlab, const long long *ranks_host, double *lo_host,
-                          double *hi_host)
-{
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
-    if (!img || !ranks_host || !lo_host || !hi_host || n < 1 || nlab < 1) return fail(TIP_ERR_ARG, "order_stats: bad arguments");
-    if (!labels && nlab != 1) return fail(TIP_ERR_ARG, "order_stats: whole-frame mode takes one rank");
-    WsGuard ws;
-    long long *rank = ws.get<long long>(nlab), *rank0 = ws.get<long long>(nlab);
-    double *lo = ws.get<double>(nlab), *hi = ws.get<double>(nlab);
-    if (!rank || !rank0 || !lo || !hi) return TIP_ERR_NOMEM;
-    hipStream_t s = c.stream;
-    TIP_HIP(hipMemcpyAsync(rank, ranks_host, (size_t)nlab * 8, hipMemcpyHostToDevice, s));
-    TIP_HIP(hipMemcpyAsync(rank0, ranks_host, (size_t)nlab * 8, hipMemcpyHostToDevice, s));
-    const int rc = order_stats_dev(labels, img, n, nlab, rank, rank0, lo, hi);
-    if (rc) return rc;
-    TIP_HIP(hipMemcpyAsync(lo_host, lo, (size_t)nlab * 8, hipMemcpyDeviceToHost, s));
-    TIP_HIP(hipMemcpyAsync(hi_host, hi, (size_t)nlab * 8, hipMemcpyDeviceToHost, s));
-    TIP_HIP(hipStreamSynchronize(s));
-    return TIP_OK;
-}
-
 }  // namespace tip
 
 using namespace tip;
@@ -183,13 +146,14 @@ int tip_label_order_stats_f64(const int32_t *labels, const double *img, int y, i
     if (!c.stream) return TIP_ERR_HIP;
     if (!img || y < 1 || x < 1 || nlab < 1 || !ranks || !lo || !hi) return fail(TIP_ERR_ARG, "tip_label_order_stats_f64: bad arguments");
     const size_t P = (size_t)y * x;
-    WsGuard ws;
-    int32_t *dl = labels ? ws.get<int32_t>(P) : nullptr;
-    double *di = ws.get<double>(P);
-    if ((labels && !dl) || !di) return TIP_ERR_NOMEM;
-    if (labels) TIP_HIP(hipMemcpyAsync(dl, labels, P * 4, hipMemcpyHostToDevice, c.stream));
-    TIP_HIP(hipMemcpyAsync(di, img, P * 8, hipMemcpyHostToDevice, c.stream));
-    return label_order_stats_dev(dl, di, (long)P, nlab, (const long long *)ranks, lo, hi);
+    Staging st;                                      // host ranks in, host values out
+    const int32_t *dl = st.in(labels, P);
+    const double *di = st.in(img, P);
+    long long *rank = st.in((const long long *)ranks, (size_t)nlab), *rank0 = st.in((const long long *)ranks, (size_t)nlab);
+    double *dlo = st.out(lo, (size_t)nlab), *dhi = st.out(hi, (size_t)nlab);
+    if (st.rc) return st.rc;
+    if (int rc = order_stats_dev(dl, di, (long)P, nlab, rank, rank0, dlo, dhi)) return rc;
+    return st.finish();
 }
 
 }  // extern "C"

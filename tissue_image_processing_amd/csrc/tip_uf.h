@@ -135,6 +135,4 @@ int uf_components(Same s, int *parent, int Y, int X)
     return TIP_OK;
 }
 
-int exclusive_scan_i32(const int *in, int *out, long n, int *total_dev);
-
 }  // namespace tip

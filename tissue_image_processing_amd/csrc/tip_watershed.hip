@@ -30,9 +30,6 @@
 
 namespace tip {
 
-int gaussian3d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, const double *tz, int nz, const double *ty,
-                   int ny, const double *tx, int nx);                                                    // tip_gauss.hip
-
 // Both reductions: 4 independent loads per thread and trip, one atomic per BLOCK (thousands of same-address 64-bit
 // atomics serialise in L2 and used to cost more than the 32 MB read itself).
 constexpr int WS_RED_BLOCKS = 512;
