@@ -580,7 +580,7 @@ TIP_API int tip_link_frame_f64_dev(const double *track_pos, int64_t n_tracks, co
                                    double search_range, double adaptive_stop, double adaptive_step, int max_subnet,
                                    int32_t *track_of_feature, int64_t *stats);
 
-/* ---- run-only deflate of a map (csrc/tip_deflate.hip; movie.save_seg's label and type maps) ------------------------------ */
+/* ---- deflate of a map: runs, or runs and row matches (csrc/tip_deflate.hip; movie.save_seg's label and type maps) -------- */
 /* The most bytes the encoder below writes for nbytes of input -- the one place the bound is written: per chunk of 65536     */
 /* input bytes 3 + 9 n + 7 + 3 bits (headers, the longest literal for every byte, end of block), padded to a byte, + 4.      */
 /* Touches no device.                                                                                                         */
@@ -597,6 +597,17 @@ TIP_API int tip_deflate_runs_dev(const void *src_dev, int64_t nbytes, int elem_b
 /* The same on host arrays, staged through the calling thread's workspaces.                                                   */
 TIP_API int tip_deflate_runs(const void *src, int64_t nbytes, int elem_bytes, void *dst, int64_t cap, int64_t *out_bytes,
                              uint32_t *crc32);
+/* The same stream framing, contracts and bound (tip_deflate_runs_bound) with matches to the ROW ABOVE beside the runs: the    */
+/* buffer is a map whose rows are row_bytes long (a positive multiple of elem_bytes; it need not divide nbytes), and an element */
+/* may also match the one row_bytes, row_bytes + elem_bytes or row_bytes - elem_bytes before it in the buffer -- each distance */
+/* used when it is above elem_bytes and at most 32768; such a match is at least 4 bytes long, may reach into an earlier chunk  */
+/* and never before the buffer.  The rule: tip_deflate.hip's head, restated in tests/deflate_rows_restate.py.  With no usable  */
+/* distance (row_bytes > 32768 + elem_bytes) the stream is tip_deflate_runs'.  TIP_ERR_ARG additionally: row_bytes <= 0 or not */
+/* a multiple of elem_bytes.                                                                                                    */
+TIP_API int tip_deflate_rows_dev(const void *src_dev, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst_dev, int64_t cap,
+                                 int64_t *out_bytes_host, uint32_t *crc32_host);
+TIP_API int tip_deflate_rows(const void *src, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst, int64_t cap,
+                             int64_t *out_bytes, uint32_t *crc32);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-// tip_deflate.hip -- run-only deflate (RFC 1951) and CRC-32 of a device buffer, so that a label map or a type map leaves its
+// tip_deflate.hip -- deflate (RFC 1951) by runs, or by runs and matches to the row above, and CRC-32 of a device buffer, so that a label map or a type map leaves its
 // GPU as the few kilobytes a `.seg` archive member holds instead of as 16 MB for the host's zlib (movie.save_seg).
 //
 // Stream (tests/deflate_restate.py is the same rule in Python, byte for byte).  The input is cut into chunks of 65536 bytes.
@@ -11,7 +11,18 @@
 // first element may repeat the last one of the segment before, so a long run is a chain of 256-byte matches; the chunk's
 // first element never repeats: no match reaches before its chunk.
 //
-// k_deflate_runs: one workgroup (256 threads) per chunk, one thread per segment.
+// The ROWS rule (tip_deflate_rows; tests/deflate_rows_restate.py) keeps stream, chunks and segments and adds matches to the row
+// above of a map whose rows are P = row_bytes long.  With e = elem_bytes and p a byte offset into the WHOLE buffer: R(p) is
+// "repeats" as above; M_d(p), for the candidate distances d = P, P + e, P - e in this order, each kept only when e < d <= 32768,
+// is p >= d and the element at p equals the one at p - d -- in an earlier chunk too, never before the buffer.  At p, with r and
+// u_d the bytes of consecutive elements from p on, up to the segment's end, with R and with M_d, and (u, d*) the longest u_d (a
+// tie goes to the earlier candidate): u >= max(4, e) and u > r gives one match (u, d*); else r >= max(3, e) one match (r, e);
+// else the element's e literals.  A match is the length code, the 5-bit distance code and its extra bits, at most 8 + 5 + 5 + 13
+// = 31 bits for at least 4 bytes: the bound is unchanged.  Without a kept candidate (P > 32768 + e) it is the run-only rule,
+// and the run-only kernel runs.
+//
+// k_deflate_runs, k_deflate_rows: one workgroup (256 threads) per chunk, one thread per segment; they differ in the token rule
+// alone (RunsRule: a byte walk with look-behind; RowsRule: bit masks of R and the M_d in registers, see there).
 //   stage    the chunk into LDS, segment t at dword 65 t: the threads then walk their segments in step, lane l reading dword
 //            65 l + w -- bank (l + w) mod 32, all distinct within a 32-lane half (ds_read_b32), where the plain layout (stride
 //            64 dwords) would put all 64 lanes on one bank.  The global reads are consecutive dwords.
@@ -100,7 +111,7 @@ struct WordSink {                           // appends at a bit position of zero
     int nacc;
     uint32_t word;
     __device__ WordSink(uint32_t *w, uint32_t bitpos) : words(w), nacc((int)(bitpos & 31u)), word(bitpos >> 5) {}
-    __device__ void put(uint32_t v, int n)  // n <= 18 and nacc < 32: the accumulator never passes 50 bits
+    __device__ void put(uint32_t v, int n)  // n <= 31 (a row match) and nacc < 32: the accumulator never passes 63 bits
     {
         acc |= (uint64_t)v << nacc;
         nacc += n;
@@ -123,17 +134,24 @@ template <class Sink> __device__ static inline void put_literal(Sink &s, uint32_
     else s.put(__brev(0x190u + (v - 144u)) >> 23, 9);
 }
 
-template <int E, class Sink> __device__ static inline void put_match(Sink &s, int len)      // 3 <= len <= 256, distance E
+// the length symbol of a match of 3 <= len <= 256 bytes and its extra bits; nb: their bit count (7 .. 13)
+__device__ static inline uint32_t length_code(int len, int &nb)
 {
     const uint32_t n = (uint32_t)len - 3u;
     const int eb = n < 8u ? 0 : (31 - __clz((int)n)) - 2;          // extra bits of the length symbol
     const uint32_t sym = n < 8u ? 257u + n : 261u + 4u * eb + ((n >> eb) & 3u);
     uint32_t v;
-    int nb;
     if (sym < 280u) { v = __brev(sym - 256u) >> 25; nb = 7; }
     else { v = __brev(0xC0u + (sym - 280u)) >> 24; nb = 8; }
     v |= (n & ((1u << eb) - 1u)) << nb;
     nb += eb;
+    return v;
+}
+
+template <int E, class Sink> __device__ static inline void put_match(Sink &s, int len)      // 3 <= len <= 256, distance E
+{
+    int nb;
+    uint32_t v = length_code(len, nb);
     constexpr uint32_t dist_rev5 = E == 1 ? 0u : E == 2 ? 16u : 24u;   // distance codes 0, 1, 3 (distances 1, 2, 4), five bits reversed
     v |= dist_rev5 << nb;
     s.put(v, nb + 5);
@@ -173,10 +191,193 @@ template <int E, class Sink> __device__ static inline void encode_segment(Sink &
     put_run<E>(s, run, prev);
 }
 
-template <int E>
-__global__ __launch_bounds__(DF_THREADS) void k_deflate_runs(const uint8_t *__restrict__ src, long nbytes, int aligned,
-                                                             uint32_t *__restrict__ slots, uint32_t *__restrict__ sizes,
-                                                             uint32_t *__restrict__ crc_out)
+template <int E> struct RunsRule {          // the run-only rule: nothing to prepare, the segment is walked byte by byte
+    __device__ void prepare(const uint8_t *, long, long, const uint32_t *, int, bool, uint32_t) {}
+    template <class Sink> __device__ void encode(Sink &s, const uint32_t *seg, int nb, bool has_prev, uint32_t prev) const
+    {
+        encode_segment<E>(s, seg, nb, has_prev, prev);
+    }
+};
+
+// ---- the rows rule ---------------------------------------------------------------------------------------------------------
+// A candidate distance: d bytes (0: not kept), its code -- five bits reversed, the extra bits behind them -- and the bit count.
+struct RowDist {
+    int d;
+    uint32_t code;
+    int nbits;
+};
+struct RowDists {                           // P, P + E, P - E in the rule's order, at least one kept (row_bytes 0 on the host: none)
+    RowDist c[3];
+    long row_bytes;
+};
+
+// one bit per element of the dword x: the element is zero (x: the XOR of two dwords -- their elements are equal)
+template <int E> __device__ static inline uint32_t zero_elems(uint32_t x)
+{
+    if constexpr (E == 4) return x == 0u ? 1u : 0u;
+    else if constexpr (E == 2) return ((x & 0xFFFFu) == 0u ? 1u : 0u) | ((x >> 16) == 0u ? 2u : 0u);
+    else {
+        // bit 7 of every byte that is not zero (the sum does not carry between bytes), inverted, then the four flags -- bits
+        // 0, 8, 16, 24 -- gathered in bits 28 .. 31 by one product whose sixteen terms land on distinct bits
+        const uint32_t nz = (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
+        return (((nz ^ 0x80808080u) >> 7) * 0x10204080u) >> 28;
+    }
+}
+
+// the dword that starts E bytes before hi's first byte (lo: the dword before hi) and the one that starts E bytes behind lo's
+template <int E> __device__ static inline uint32_t elem_before(uint32_t lo, uint32_t hi)
+{
+    if constexpr (E == 4) return lo;
+    else return (lo >> (32 - 8 * E)) | (hi << (8 * E));
+}
+template <int E> __device__ static inline uint32_t elem_behind(uint32_t lo, uint32_t hi)
+{
+    if constexpr (E == 4) return hi;
+    else return (lo >> (8 * E)) | (hi << (32 - 8 * E));
+}
+
+// the one bits of the mask m (W words, bit i: element i) in a row from bit pos on
+template <int W> __device__ static inline int ones_from(const uint64_t (&m)[W], int pos)
+{
+    int n = 0;
+    bool go = true;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const int b = pos - 64 * k;           // the first bit of word k that counts (below 0: all of it)
+        if (go && b < 64) {
+            const int from = b > 0 ? b : 0, room = 64 - from;
+            const uint64_t inv = ~m[k] >> from;      // (zeros enter at the top: the count is capped at the word's end)
+            int c = inv ? __builtin_ctzll(inv) : 64;
+            c = c < room ? c : room;
+            n += c;
+            go = c == room;
+        }
+    }
+    return n;
+}
+
+// clears the bits of m outside [lo, hi)
+template <int W> __device__ static inline void keep_bits(uint64_t (&m)[W], int lo, int hi)
+{
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const int l = lo - 64 * k, h = hi - 64 * k;
+        const uint64_t below_h = h >= 64 ? ~0ul : h <= 0 ? 0ul : (1ul << h) - 1ul;
+        const uint64_t below_l = l >= 64 ? ~0ul : l <= 0 ? 0ul : (1ul << l) - 1ul;
+        m[k] &= below_h & ~below_l;
+    }
+}
+
+// Eighteen dwords of the buffer from byte offset `off` on (any sign, any alignment); bytes outside the buffer read as zero.
+__device__ static inline void load_above(const uint8_t *src, long nbytes, long off, uint32_t (&a)[18])
+{
+    if (off >= 0 && off + 72 <= nbytes && (((uintptr_t)src + (uintptr_t)off) & 3u) == 0) {
+        const uint32_t *p = (const uint32_t *)(src + off);
+#pragma unroll
+        for (int i = 0; i < 18; ++i) a[i] = p[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 18; ++i) {
+            uint32_t d = 0;
+            for (int b = 0; b < 4; ++b) {
+                const long o = off + 4 * i + b;
+                if (o >= 0 && o < nbytes) d |= (uint32_t)src[o] << (8 * b);
+            }
+            a[i] = d;
+        }
+    }
+}
+
+// The rows rule (this file's head): per thread one bit per element of its segment for R -- the element repeats -- and for each
+// candidate distance -- the element equals the one d bytes before it in the BUFFER -- kept in registers (64 bits each for
+// int32, 256 for uint8); the walk is then count-the-ones arithmetic on the four masks, the same for both sinks.
+// The masks are built sixteen dwords at a time.  The three distances differ by one element, so ONE span of the row above --
+// the sixteen dwords at p - P and one dword either side -- serves all three: plain dword loads when the span lies inside the
+// buffer and is dword-aligned (an int32 map; a uint8 map whose row is a multiple of 4), byte loads otherwise.  The guard
+// p >= d is applied to the finished masks, so whatever the loads return before the buffer's first byte (zero) never counts.
+template <int E> struct RowsRule {
+    static constexpr int W = 4 / E;          // 64-bit words of a mask: 256 / E elements
+    static constexpr int NE = 4 / E;         // elements of a dword
+    RowDists dist;
+    uint64_t r[W], m[3][W];
+
+    __device__ __forceinline__ void prepare(const uint8_t *src, long nbytes, long at, const uint32_t *seg, int nb, bool has_prev, uint32_t prev)
+    {
+#pragma unroll
+        for (int j = 0; j < W; ++j) r[j] = m[0][j] = m[1][j] = m[2][j] = 0;
+        if (nb <= 0) return;
+        uint32_t before = prev << (32 - 8 * E);               // (a dword whose last element is the one before the segment)
+#pragma unroll 1
+        for (int g = 0; 64 * g < nb; ++g) {
+            uint32_t a[18];                                     // the row above: dwords -1 .. 16 of this group's
+            load_above(src, nbytes, at - dist.row_bytes + 64 * g - 4, a);
+            uint64_t br = 0, b0 = 0, b1 = 0, b2 = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const uint32_t x = seg[16 * g + i];
+                br |= (uint64_t)zero_elems<E>(x ^ elem_before<E>(before, x)) << (NE * i);
+                before = x;
+                b0 |= (uint64_t)zero_elems<E>(x ^ a[i + 1]) << (NE * i);
+                b1 |= (uint64_t)zero_elems<E>(x ^ elem_before<E>(a[i], a[i + 1])) << (NE * i);
+                b2 |= (uint64_t)zero_elems<E>(x ^ elem_behind<E>(a[i + 1], a[i + 2])) << (NE * i);
+            }
+            const int bit = 16 * NE * g;                        // the group's first element
+#pragma unroll
+            for (int j = 0; j < W; ++j)
+                if (j == (bit >> 6)) {
+                    r[j] |= br << (bit & 63);
+                    m[0][j] |= b0 << (bit & 63);
+                    m[1][j] |= b1 << (bit & 63);
+                    m[2][j] |= b2 << (bit & 63);
+                }
+        }
+        keep_bits(r, has_prev ? 0 : 1, nb / E);                 // the chunk's first element never repeats
+        keep_from(m[0], dist.c[0].d, at, nb);                   // M_d needs p >= d, and a distance that is kept
+        keep_from(m[1], dist.c[1].d, at, nb);
+        keep_from(m[2], dist.c[2].d, at, nb);
+    }
+
+    // clears, in the mask of distance d, the elements before byte d of the buffer (all when d is 0: not kept)
+    __device__ static __forceinline__ void keep_from(uint64_t (&mk)[W], int d, long at, int nb)
+    {
+        const long first = (long)d - at;                        // the segment's first byte with p >= d
+        keep_bits(mk, d == 0 || first >= nb ? nb / E : first > 0 ? (int)first / E : 0, nb / E);
+    }
+
+    template <class Sink> __device__ __forceinline__ void encode(Sink &s, const uint32_t *seg, int nb, bool, uint32_t) const
+    {
+        constexpr uint32_t mask = E == 4 ? 0xFFFFFFFFu : (1u << (8 * (E & 3))) - 1u;
+        const uint32_t code0 = dist.c[0].code, code1 = dist.c[1].code, code2 = dist.c[2].code;
+        const int nbits0 = dist.c[0].nbits, nbits1 = dist.c[1].nbits, nbits2 = dist.c[2].nbits;
+        for (int pos = 0; pos < nb / E;) {
+            const int run = ones_from(r, pos), u1 = ones_from(m[1], pos), u2 = ones_from(m[2], pos);
+            int u = ones_from(m[0], pos), k = 0;                // the longest; a tie stays with the earlier distance
+            if (u1 > u) { u = u1; k = 1; }
+            if (u2 > u) { u = u2; k = 2; }
+            if (u * E >= 4 && u > run) {
+                int nbits;
+                uint32_t v = length_code(u * E, nbits);
+                v |= (k == 0 ? code0 : k == 1 ? code1 : code2) << nbits;
+                s.put(v, nbits + (k == 0 ? nbits0 : k == 1 ? nbits1 : nbits2));      // at most 13 + 18
+                pos += u;
+            } else if (run * E >= (E > 3 ? E : 3)) {
+                put_match<E>(s, run * E);
+                pos += run;
+            } else {
+                const uint32_t x = (seg[(pos * E) >> 2] >> (8 * ((pos * E) & 3))) & mask;
+#pragma unroll
+                for (int b = 0; b < E; ++b) put_literal(s, (x >> (8 * b)) & 255u);
+                pos += 1;
+            }
+        }
+    }
+};
+
+// One chunk by one workgroup (this file's head): what both kernels are, but for the token rule.
+template <int E, class Rule>
+__device__ static __forceinline__ void deflate_chunk(Rule &rule, const uint8_t *__restrict__ src, long nbytes, int aligned,
+                                                     uint32_t *__restrict__ slots, uint32_t *__restrict__ sizes,
+                                                     uint32_t *__restrict__ crc_out)
 {
     extern __shared__ uint32_t df_lds[];
     uint32_t *in = df_lds, *out = df_lds + DF_IN_WORDS, *crctab = out + DF_OUT_WORDS, *misc = crctab + 256;
@@ -211,8 +412,9 @@ __global__ __launch_bounds__(DF_THREADS) void k_deflate_runs(const uint8_t *__re
     const bool has_prev = t > 0 && nb > 0;
     const uint32_t prev = has_prev ? in[(t - 1) * DF_SEG_LD + 63] >> (32 - 8 * E) : 0u;      // the segment before is full
 
+    rule.prepare(src, nbytes, base + first, seg, nb, has_prev, prev);
     CountSink cs;
-    encode_segment<E>(cs, seg, nb, has_prev, prev);
+    rule.encode(cs, seg, nb, has_prev, prev);
     // exclusive block scan of the bit counts: within the wave by shuffles, across the four waves through LDS
     const int lane = t & 63, wave = t >> 6;
     uint32_t incl = cs.bits;
@@ -231,7 +433,7 @@ __global__ __launch_bounds__(DF_THREADS) void k_deflate_runs(const uint8_t *__re
 
     WordSink ws(out, t == 0 ? 0u : bitpos);
     if (t == 0) ws.put(2u, 3);                // BFINAL 0, then BTYPE 01 least significant bit first
-    encode_segment<E>(ws, seg, nb, has_prev, prev);
+    rule.encode(ws, seg, nb, has_prev, prev);
     ws.flush();
     // end of block (seven zero bits) and the stored block's header (three) are zeros already; behind the padding LEN = 0, NLEN = FFFF
     const uint32_t body = (3u + total + 7u + 3u + 7u) / 8u, size = body + 4u;
@@ -259,6 +461,25 @@ __global__ __launch_bounds__(DF_THREADS) void k_deflate_runs(const uint8_t *__re
         sizes[blockIdx.x] = size;
         atomicXor(crc_out, misc[4]);
     }
+}
+
+template <int E>
+__global__ __launch_bounds__(DF_THREADS) void k_deflate_runs(const uint8_t *__restrict__ src, long nbytes, int aligned,
+                                                             uint32_t *__restrict__ slots, uint32_t *__restrict__ sizes,
+                                                             uint32_t *__restrict__ crc_out)
+{
+    RunsRule<E> rule;
+    deflate_chunk<E>(rule, src, nbytes, aligned, slots, sizes, crc_out);
+}
+
+template <int E>
+__global__ __launch_bounds__(DF_THREADS) void k_deflate_rows(const uint8_t *__restrict__ src, long nbytes, int aligned, RowDists dist,
+                                                             uint32_t *__restrict__ slots, uint32_t *__restrict__ sizes,
+                                                             uint32_t *__restrict__ crc_out)
+{
+    RowsRule<E> rule;
+    rule.dist = dist;
+    deflate_chunk<E>(rule, src, nbytes, aligned, slots, sizes, crc_out);
 }
 
 // offsets[c] = sizes[0] + ... + sizes[c - 1]; *total = the sum.  One workgroup, 256 chunks per step.
@@ -298,27 +519,62 @@ __global__ __launch_bounds__(256) void k_deflate_compact(const uint32_t *__restr
     for (uint32_t i = threadIdx.x; i < size; i += 256) to[i] = slot[i];
 }
 
-template <int E> static int launch_encode(const void *src, long nbytes, long chunks, uint32_t *slots, uint32_t *sizes, uint32_t *crc)
+// rows: the candidate distances of the rows rule, or null for the run-only rule
+template <int E>
+static int launch_encode(const void *src, long nbytes, long chunks, const RowDists *rows, uint32_t *slots, uint32_t *sizes, uint32_t *crc)
 {
     constexpr size_t lds = (size_t)DF_LDS_WORDS * 4;
+    const int aligned = (int)(((uintptr_t)src & 3u) == 0);
+    if (rows) {
+        TIP_HIP(hipFuncSetAttribute((const void *)k_deflate_rows<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        TIP_LAUNCH("deflate_rows", k_deflate_rows<E>, dim3((unsigned)chunks), dim3(DF_THREADS), lds, (const uint8_t *)src, nbytes, aligned,
+                   *rows, slots, sizes, crc);
+        return TIP_OK;
+    }
     TIP_HIP(hipFuncSetAttribute((const void *)k_deflate_runs<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    TIP_LAUNCH("deflate_runs", k_deflate_runs<E>, dim3((unsigned)chunks), dim3(DF_THREADS), lds, (const uint8_t *)src, nbytes,
-               (int)(((uintptr_t)src & 3u) == 0), slots, sizes, crc);
+    TIP_LAUNCH("deflate_runs", k_deflate_runs<E>, dim3((unsigned)chunks), dim3(DF_THREADS), lds, (const uint8_t *)src, nbytes, aligned,
+               slots, sizes, crc);
     return TIP_OK;
 }
 
-static int check_args(const char *who, const void *src, long nbytes, int elem_bytes, const void *dst, long cap, const void *out_bytes,
-                      const void *crc)
+// The rows rule's candidates P, P + e, P - e, each kept when e < d <= 32768, with their distance codes (RFC 1951 3.2.5): codes
+// 0 .. 3 are the distances 1 .. 4; from 5 on, with h the highest bit of d - 1, the code is 2 h + the bit below h, and the
+// h - 1 bits below that are the extra bits.
+static RowDists row_dists(int e, long row_bytes)
+{
+    RowDists r{};
+    if (row_bytes > 32768 + e) return r;      // none is kept: the run-only rule
+    const long cand[3] = {row_bytes, row_bytes + e, row_bytes - e};
+    for (int k = 0; k < 3; ++k) {
+        if (cand[k] <= e || cand[k] > 32768) continue;
+        const uint32_t t = (uint32_t)cand[k] - 1u;
+        int h = 31;
+        while (!(t >> h)) --h;
+        const int eb = t < 4u ? 0 : h - 1;
+        const uint32_t code = t < 4u ? t : 2u * h + ((t >> eb) & 1u);
+        uint32_t rev = 0;
+        for (int b = 0; b < 5; ++b) rev |= ((code >> b) & 1u) << (4 - b);
+        r.c[k] = {(int)cand[k], rev | ((t & ((1u << eb) - 1u)) << 5), 5 + eb};
+        r.row_bytes = row_bytes;
+    }
+    return r;
+}
+
+// row_bytes: the rows entries' row length (positive there), 0 from the runs entries
+static int check_args(const char *who, const void *src, long nbytes, int elem_bytes, long row_bytes, const void *dst, long cap,
+                      const void *out_bytes, const void *crc)
 {
     if (!src || !dst || !out_bytes || !crc) return fail(TIP_ERR_ARG, "%s: null pointer", who);
     if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4) return fail(TIP_ERR_ARG, "%s: elem_bytes %d (1, 2 or 4)", who, elem_bytes);
     if (nbytes < 0 || nbytes % elem_bytes) return fail(TIP_ERR_ARG, "%s: nbytes %ld is not a multiple of elem_bytes %d", who, nbytes, elem_bytes);
+    if (row_bytes % elem_bytes) return fail(TIP_ERR_ARG, "%s: row_bytes %ld is not a multiple of elem_bytes %d", who, row_bytes, elem_bytes);
     if (nbytes / DF_CHUNK >= (1L << 31)) return fail(TIP_ERR_ARG, "%s: nbytes %ld (at most 2^47)", who, nbytes);
     if (cap < stream_bound(nbytes)) return fail(TIP_ERR_ARG, "%s: cap %ld is below tip_deflate_runs_bound(%ld) = %ld", who, cap, nbytes, stream_bound(nbytes));
     return TIP_OK;
 }
 
-static int deflate_runs_dev(const void *src, long nbytes, int elem_bytes, void *dst, int64_t *out_bytes, uint32_t *crc32)
+// row_bytes 0: the run-only rule -- which the rows rule also is when its row is too long for any candidate distance
+static int deflate_dev(const void *src, long nbytes, int elem_bytes, long row_bytes, void *dst, int64_t *out_bytes, uint32_t *crc32)
 {
     *out_bytes = 0;
     *crc32 = 0;
@@ -331,9 +587,10 @@ static int deflate_runs_dev(const void *src, long nbytes, int elem_bytes, void *
     unsigned long *pin = (unsigned long *)pinned_scratch(16);
     if (!slots || !sizes || !offsets || !result || !pin) return TIP_ERR_NOMEM;
     TIP_HIP(hipMemsetAsync(result, 0, 16, c.stream));
-    int rc = elem_bytes == 1 ? launch_encode<1>(src, nbytes, chunks, slots, sizes, (uint32_t *)(result + 1))
-           : elem_bytes == 2 ? launch_encode<2>(src, nbytes, chunks, slots, sizes, (uint32_t *)(result + 1))
-                             : launch_encode<4>(src, nbytes, chunks, slots, sizes, (uint32_t *)(result + 1));
+    const RowDists dists = row_dists(elem_bytes, row_bytes), *rows = dists.row_bytes ? &dists : nullptr;
+    int rc = elem_bytes == 1 ? launch_encode<1>(src, nbytes, chunks, rows, slots, sizes, (uint32_t *)(result + 1))
+           : elem_bytes == 2 ? launch_encode<2>(src, nbytes, chunks, rows, slots, sizes, (uint32_t *)(result + 1))
+                             : launch_encode<4>(src, nbytes, chunks, rows, slots, sizes, (uint32_t *)(result + 1));
     if (rc) return rc;
     TIP_LAUNCH("deflate_offsets", k_deflate_offsets, dim3(1), dim3(256), 0, sizes, chunks, offsets, result);
     TIP_LAUNCH("deflate_compact", k_deflate_compact, dim3((unsigned)chunks), dim3(256), 0, slots, sizes, offsets, (uint8_t *)dst);
@@ -342,6 +599,31 @@ static int deflate_runs_dev(const void *src, long nbytes, int elem_bytes, void *
     *out_bytes = (int64_t)pin[0];
     *crc32 = (uint32_t)pin[1];
     return TIP_OK;
+}
+
+// the two entry forms of both rules (row_bytes 0: run-only)
+static int entry_dev(const char *who, const void *src, long nbytes, int elem_bytes, long row_bytes, void *dst, long cap, int64_t *out_bytes,
+                     uint32_t *crc32)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_args(who, src, nbytes, elem_bytes, row_bytes, dst, cap, out_bytes, crc32)) return rc;
+    return deflate_dev(src, nbytes, elem_bytes, row_bytes, dst, out_bytes, crc32);
+}
+
+static int entry_host(const char *who, const void *src, long nbytes, int elem_bytes, long row_bytes, void *dst, long cap, int64_t *out_bytes,
+                      uint32_t *crc32)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_args(who, src, nbytes, elem_bytes, row_bytes, dst, cap, out_bytes, crc32)) return rc;
+    Staging st;
+    const uint8_t *ds = st.in((const uint8_t *)src, (size_t)nbytes);
+    uint8_t *dd = st.out((uint8_t *)dst, (size_t)stream_bound(nbytes));
+    if (st.rc) return st.rc;
+    if (int rc = deflate_dev(ds, nbytes, elem_bytes, row_bytes, dd, out_bytes, crc32)) return rc;
+    st.set_count(dd, (size_t)*out_bytes);
+    return st.finish();
 }
 
 }  // namespace tip
@@ -360,24 +642,26 @@ int tip_deflate_runs_bound(int64_t nbytes, int64_t *bound_out)
 int tip_deflate_runs_dev(const void *src_dev, int64_t nbytes, int elem_bytes, void *dst_dev, int64_t cap, int64_t *out_bytes_host,
                          uint32_t *crc32_host)
 {
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
-    if (int rc = check_args("tip_deflate_runs_dev", src_dev, nbytes, elem_bytes, dst_dev, cap, out_bytes_host, crc32_host)) return rc;
-    return deflate_runs_dev(src_dev, nbytes, elem_bytes, dst_dev, out_bytes_host, crc32_host);
+    return entry_dev("tip_deflate_runs_dev", src_dev, nbytes, elem_bytes, 0, dst_dev, cap, out_bytes_host, crc32_host);
 }
 
 int tip_deflate_runs(const void *src, int64_t nbytes, int elem_bytes, void *dst, int64_t cap, int64_t *out_bytes, uint32_t *crc32)
 {
-    Ctx &c = ctx();
-    if (!c.stream) return TIP_ERR_HIP;
-    if (int rc = check_args("tip_deflate_runs", src, nbytes, elem_bytes, dst, cap, out_bytes, crc32)) return rc;
-    Staging st;
-    const uint8_t *ds = st.in((const uint8_t *)src, (size_t)nbytes);
-    uint8_t *dd = st.out((uint8_t *)dst, (size_t)stream_bound(nbytes));
-    if (st.rc) return st.rc;
-    if (int rc = deflate_runs_dev(ds, nbytes, elem_bytes, dd, out_bytes, crc32)) return rc;
-    st.set_count(dd, (size_t)*out_bytes);
-    return st.finish();
+    return entry_host("tip_deflate_runs", src, nbytes, elem_bytes, 0, dst, cap, out_bytes, crc32);
+}
+
+int tip_deflate_rows_dev(const void *src_dev, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst_dev, int64_t cap,
+                         int64_t *out_bytes_host, uint32_t *crc32_host)
+{
+    if (row_bytes <= 0) return fail(TIP_ERR_ARG, "tip_deflate_rows_dev: row_bytes %ld is not positive", (long)row_bytes);
+    return entry_dev("tip_deflate_rows_dev", src_dev, nbytes, elem_bytes, row_bytes, dst_dev, cap, out_bytes_host, crc32_host);
+}
+
+int tip_deflate_rows(const void *src, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst, int64_t cap, int64_t *out_bytes,
+                     uint32_t *crc32)
+{
+    if (row_bytes <= 0) return fail(TIP_ERR_ARG, "tip_deflate_rows: row_bytes %ld is not positive", (long)row_bytes);
+    return entry_host("tip_deflate_rows", src, nbytes, elem_bytes, row_bytes, dst, cap, out_bytes, crc32);
 }
 
 }  // extern "C"

@@ -1,8 +1,10 @@
-"""Two ways from a finished movie on one MI355X to a `.seg` archive, timed: N synthetic 2048^2 frames, cell types on.
+"""Ways from a finished movie on one MI355X to a `.seg` archive, timed: N synthetic 2048^2 frames, cell types on.
 
   (a) GpuFrameBackend(archive=...) + movie.save_seg: the label and type maps are deflated on the device inside process_movie
       (csrc/tip_deflate.hip), save_seg wraps the streams and builds the frame tables from what the driver kept.  Its cost is
       what `archive` adds to process_movie plus the save_seg call.
+  (a') the same with archive=dict(matches="rows"): matches to the row above beside the runs (tip_deflate_rows_dev), a smaller
+      archive from a slower deflate call.
   (b) what the driver offers without `archive`: download every frame's label and type map, put them into a Tissue with the
       frame's table (calculate_frame_cellinfo on the downloaded labels, the type columns from process_movie's tables, the
       track ids) and call Tissue.save, which deflates every member with the host's zlib.
@@ -76,9 +78,12 @@ def main():
     channels = ("zo", "atoh")
     plain = movie.GpuFrameBackend(2, Z, Y, X, device=0, inflight=args.inflight, cell_types=opts)
     arch = movie.GpuFrameBackend(2, Z, Y, X, device=0, inflight=args.inflight, cell_types=opts, archive=dict(type_name="HC"))
+    arch_rows = movie.GpuFrameBackend(2, Z, Y, X, device=0, inflight=args.inflight, cell_types=opts,
+                                      archive=dict(type_name="HC", matches="rows"))
     tmp = tempfile.mkdtemp()
-    path_a, path_b = os.path.join(tmp, "a"), os.path.join(tmp, "b")
-    rec = {k: [] for k in ("movie_plain", "movie_archive", "save_seg", "b_download", "b_tables", "b_save")}
+    path_a, path_b, path_r = os.path.join(tmp, "a"), os.path.join(tmp, "b"), os.path.join(tmp, "a_rows")
+    rec = {k: [] for k in ("movie_plain", "movie_archive", "save_seg", "b_download", "b_tables", "b_save", "movie_archive_rows",
+                           "save_seg_rows")}
 
     def run(backend):
         torch.cuda.synchronize()
@@ -94,28 +99,39 @@ def main():
         movie.save_seg(path_a, T, arch, tabs_a, ids_a, channel_names=channels)
         w_save = time.perf_counter() - t0
         b = tissue_route(path_b, plain, tabs_p, ids_p, T, Y, X, channels)
-        print("rep %d: movie %.3f / %.3f s, save_seg %.3f s, Tissue route %.3f + %.3f + %.3f s" % ((rep, w_plain, w_arch, w_save) + b),
-              file=sys.stderr, flush=True)
+        tabs_r, ids_r, w_rows = run(arch_rows)
+        t0 = time.perf_counter()
+        movie.save_seg(path_r, T, arch_rows, tabs_r, ids_r, channel_names=channels)
+        w_save_rows = time.perf_counter() - t0
+        print("rep %d: movie %.3f / %.3f / %.3f s (plain, runs, rows), save_seg %.3f / %.3f s, Tissue route %.3f + %.3f + %.3f s"
+              % ((rep, w_plain, w_arch, w_rows, w_save, w_save_rows) + b), file=sys.stderr, flush=True)
         if rep:
-            for k, v in zip(rec, (w_plain, w_arch, w_save) + b):
+            for k, v in zip(rec, (w_plain, w_arch, w_save) + b + (w_rows, w_save_rows)):
                 rec[k].append(v)
     n = args.reps
     a_total = [rec["movie_archive"][i] - rec["movie_plain"][i] + rec["save_seg"][i] for i in range(n)]
+    r_total = [rec["movie_archive_rows"][i] - rec["movie_plain"][i] + rec["save_seg_rows"][i] for i in range(n)]
+    streams_r = [(len(arch_rows.archive_frames[t]["labels"][0]), len(arch_rows.archive_frames[t]["types"][0])) for t in range(T)]
     b_total = [rec["b_download"][i] + rec["b_tables"][i] + rec["b_save"][i] for i in range(n)]
     streams = [(len(arch.archive_frames[t]["labels"][0]), len(arch.archive_frames[t]["types"][0])) for t in range(T)]
     out = {"frames": T, "size": [Y, X, Z], "inflight": args.inflight, "reps": n, "rows_per_frame": int(tabs_a[0]["area"].size),
            "seconds": {k: stats(v) for k, v in rec.items()},
-           "route_a_total_s": stats(a_total), "route_b_total_s": stats(b_total),
+           "route_a_total_s": stats(a_total), "route_a_rows_total_s": stats(r_total), "route_b_total_s": stats(b_total),
            "route_a_save_seg_only_s": stats(rec["save_seg"]),
            "process_movie_ms_per_frame": {"plain": round(1e3 * float(np.median(rec["movie_plain"])) / T, 3),
-                                          "archive": round(1e3 * float(np.median(rec["movie_archive"])) / T, 3)},
-           "archive_bytes": {"a": os.path.getsize(path_a + ".seg"), "b": os.path.getsize(path_b + ".seg")},
+                                          "archive": round(1e3 * float(np.median(rec["movie_archive"])) / T, 3),
+                                          "archive_rows": round(1e3 * float(np.median(rec["movie_archive_rows"])) / T, 3)},
+           "archive_bytes": {"a": os.path.getsize(path_a + ".seg"), "a_rows": os.path.getsize(path_r + ".seg"),
+                             "b": os.path.getsize(path_b + ".seg")},
            "device_stream_bytes_per_frame": {"labels": int(np.mean([s[0] for s in streams])), "types": int(np.mean([s[1] for s in streams])),
+                                             "labels_rows": int(np.mean([s[0] for s in streams_r])),
+                                             "types_rows": int(np.mean([s[1] for s in streams_r])),
                                              "raw_labels": Y * X * 4, "raw_types": Y * X}}
     out["a_below_b_by_more_than_bs_spread"] = bool(out["route_b_total_s"]["median"] - out["route_a_total_s"]["median"]
                                                    > out["route_b_total_s"]["spread"])
     plain.close()
     arch.close()
+    arch_rows.close()
     text = json.dumps(out, indent=1)
     print(text)
     if args.out:
