@@ -219,6 +219,17 @@ TIP_API int tip_unet_conv_flavour(const tip_unet_conv_desc *d);
 /* formed from two consecutive (chunk, tap) steps, one such pair per barrier (TIP_UNET_MFMA=16 puts them back on 32x32x16).        */
 /* Returns 16 or 32, or the negative error the launch would return.                                                                */
 TIP_API int tip_unet_conv_mfma_k(const tip_unet_conv_desc *d);
+/* The same three entries with the CALLER's per-call choices in `flags` (0: exactly the entries above, which call these with 0; an   */
+/* unknown bit: TIP_ERR_ARG).  A choice is the call's own -- stateless, nothing process-wide changes under other threads.           */
+/*   TIP_UNET_CONV_ROWS8_K32   fp16 pieces (format 1, two planes) on 8-row tiles with four and more taps run the K = 32 kernel on     */
+/*                             their own tiles: 256 threads, two workgroups per CU with 80 KB of LDS each, the workgroup's barrier   */
+/*                             between pair steps.  The code stays 0 and tip_unet_conv_mfma_k_ex answers 32 (TIP_UNET_MFMA=16: 16).  */
+/*                             K = 32 rounds two steps' sums together: within the mode's per-layer bound of float64 like the          */
+/*                             32x32x16 kernel, not bit-identical to it -- which is why it is a flag and not the default.             */
+#define TIP_UNET_CONV_ROWS8_K32 1
+TIP_API int tip_unet_conv_ex_dev(const tip_unet_conv_desc *d, int flags, void *stream);
+TIP_API int tip_unet_conv_flavour_ex(const tip_unet_conv_desc *d, int flags);
+TIP_API int tip_unet_conv_mfma_k_ex(const tip_unet_conv_desc *d, int flags);
 /* Conv2DTranspose folded into the next Conv2D: border pass on the float32 partial `part` (2h x 2w x cout) that four  */
 /* raw launches over the low-resolution tensor x (h x w x cin, split) left.  row_w / col_w: [5][cin][cout] float32 corrections of  */
 /* the last output row / column, taps (parity, offset) = (0,-1) (0,0) (1,-1) (1,0) (1,+1); corner_w: [cin][cout]; bias_tab:        */

@@ -20,6 +20,14 @@ _F16_ACT_SCALE = 16.0      # fp16 pieces: activations are stored times 2^4 (satu
 _RANGE_F16 = 1             # TIP_UNET_RANGE_F16: bit 0 of the thread's status word
 _RANGE_POLICIES = ("fallback", "raise", "off")
 _RANGE_FALLBACK_MODE = "bf16x6"      # float32's exponent range at float32-equivalent precision
+CONV_ROWS8_K32 = 1         # TIP_UNET_CONV_ROWS8_K32: flag of tip_unet_conv_ex_dev and its two queries
+
+
+def conv_flags(mode):
+    """The per-call flags a forward pass in `mode` hands tip_unet_conv_ex_dev.  Mode f16x3 runs its 8-row launches of four and more
+    taps (the 128-channel 3x3 layers) on the K = 32 kernel; TISSUE_HIP_UNET_ROWS8_K32=0 restores the 32x32x16 launches.
+    Read per pass and handed over per call: nothing process-wide changes under the worker threads."""
+    return CONV_ROWS8_K32 if mode == "f16x3" and os.environ.get("TISSUE_HIP_UNET_ROWS8_K32", "1") != "0" else 0
 
 
 class UNetRangeError(_lib.TissueHipError):
@@ -173,11 +181,11 @@ def compose_layers(tw, bt, w1, b1, planes, fmt):
     return st
 
 
-def composed_up(st, planes, fmt, src, h, w, stream, name="", launch=None):
+def composed_up(st, planes, fmt, src, h, w, stream, name="", launch=None, flags=0):
     """The launches of compose_layers' `st` over the split low-resolution tensor src (planes, h, w, cin): four composed stencils leave
     the next convolution's sum over its up-sampled half as float32 (2h, 2w, cout), the border pass corrects its edges.  That
     convolution then runs over the skip tensor alone with st["bias"] and seed = the returned tensor.  launch(name, flop, fn): the
-    caller's per-launch timing hook."""
+    caller's per-launch timing hook; flags: tip_unet_conv_ex_dev's, for the four stencils."""
     import torch
     lib = _lib.lib()
     launch = launch or (lambda name, flop, fn: fn())
@@ -188,7 +196,7 @@ def composed_up(st, planes, fmt, src, h, w, stream, name="", launch=None):
             layer = st["x%d%d" % (py, px)]
             d = _conv_desc(layer, planes, fmt, src, None, h, w, None, raw=part, out_h=2 * h, out_w=2 * w, stride=2, oy=py, ox=px)
             launch("%sx.%d%d %dx%d %d+0->%d x%d taps" % (name, py, px, h, w, cin, cout, d.ntaps), 2.0 * h * w * d.ntaps * cout * cin,
-                   lambda: _lib.check(lib.tip_unet_conv_dev(ctypes.byref(d), stream)))
+                   lambda: _lib.check(lib.tip_unet_conv_ex_dev(ctypes.byref(d), flags, stream)))
     row_w, col_w, corner_w, bias_tab = st["border"]
     launch("%sborder %dx%d %d->%d" % (name, 2 * h, 2 * w, cin, cout), 2.0 * 2.5 * (h + w) * cin * cout,
            lambda: _lib.check(lib.tip_unet_compose_border_dev(src.data_ptr(), planes, fmt, h, w, cin, cout, row_w.data_ptr(),
@@ -372,6 +380,7 @@ def _launch(net, x, mode, logits):
     net.last_mode = mode                  # (bench.py / tests: which arithmetic the last forward pass really used)
     net.last_compose = tuple("u%d" % i for i in levels)      # ... and which decoder levels ran composed (empty: none)
     lib = _lib.lib()
+    flags = conv_flags(mode)
     stream = torch.cuda.current_stream(x.device).cuda_stream
     H, W = int(x.shape[2]), int(x.shape[3])
     x = x.to(torch.float32).contiguous()
@@ -392,7 +401,7 @@ def _launch(net, x, mode, logits):
 
     def launch_conv(name, d):
         timed("%s %dx%d %d+%d->%d x%d taps" % (name, d.h, d.w, d.c0, d.c1, d.cout, d.ntaps), 2.0 * d.h * d.w * d.ntaps * d.cout * (d.c0 + d.c1),
-              lambda: _lib.check(lib.tip_unet_conv_dev(ctypes.byref(d), stream)))
+              lambda: _lib.check(lib.tip_unet_conv_ex_dev(ctypes.byref(d), flags, stream)))
 
     def conv3(name, bn, src, skip, h, w, pooled=None, head=None, seed=None):
         """Conv2D(3x3) -> ReLU -> BatchNormalization `bn`; head: the probabilities' tensor when the head rides in the epilogue;
@@ -443,7 +452,7 @@ def _launch(net, x, mode, logits):
             cur, h, w = pooled, h // 2, w // 2
         cur = double("mid", cur, None, h, w)  # bottleneck
         for i in range(3):                    # decoder: the convolution reads [up-sampled, skip] as one concatenated tensor
-            part = composed_up(hw["u%d.x" % i], planes, fmt, cur, h, w, stream, "u%d." % i, timed) if i in levels else None
+            part = composed_up(hw["u%d.x" % i], planes, fmt, cur, h, w, stream, "u%d." % i, timed, flags) if i in levels else None
             up = conv_t("u%d.t" % i, cur, h, w) if part is None else None
             h, w = 2 * h, 2 * w
             # the last convolution's epilogue computes the head: softmax probabilities instead of the layer's own output

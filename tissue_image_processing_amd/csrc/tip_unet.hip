@@ -52,9 +52,10 @@ static bool pieces_ok(int planes, int format) { return with_pieces(planes, forma
 // The launch table of the convolutions.  A row: the code tip_unet_conv_flavour returns (include/tissue_hip.h tabulates them), the
 // template shape <pieces, tile rows, weight steps ahead, activation chunks ahead, steps per barrier> of k_unet_conv, and what can be
 // LAUNCHED for the code -- kernel, threads per workgroup, dynamic LDS bytes -- with bf16 pieces, with fp16 pieces, and with fp16
-// pieces on 16x16x32 MFMAs (k_unet_conv_k32 in the shape's place: 16-row tiles with the four-step weight schedule, codes 2 and 6).
+// pieces on 16x16x32 MFMAs (k_unet_conv_k32 on the shape's tiles in its place: 16-row tiles with the four-step weight schedule, codes
+// 2 and 6, and the two-piece 8-row tiles, code 0, which only TIP_UNET_CONV_ROWS8_K32 selects).
 // kernel == nullptr: there is none (fp16 pieces come in two planes only).  Threads and LDS bytes are the kernels' own constants
-// (UcLayout, UK_THREADS / UK_LDS): nothing about a launch is computed a second time.
+// (UcLayout, UkLaunch): nothing about a launch is computed a second time.
 typedef void (*ConvKernel)(const ConvParams);
 struct ConvLaunch {
     ConvKernel kernel;
@@ -73,16 +74,22 @@ constexpr ConvLaunch conv_launch()
     static_assert(L::LDS <= CONV_LDS_MAX, "the tile buffers fit a CU's LDS");
     return {k_unet_conv<NPL, TH, D, DA, SPB, F16>, L::THREADS, L::LDS};
 }
-static_assert(UK_LDS <= CONV_LDS_MAX, "the tile buffers fit a CU's LDS");
+template <typename L>
+constexpr ConvLaunch conv_launch_k32()
+{
+    static_assert(UkLaunch<L>::LDS <= CONV_LDS_MAX, "the tile buffers fit a CU's LDS");
+    return {k_unet_conv_k32<L>, UkLaunch<L>::THREADS, UkLaunch<L>::LDS};
+}
 template <int CODE, int NPL, int TH, int D, int DA = 1, int SPB = 1>
 constexpr ConvFlavour conv_flavour()
 {
     ConvLaunch f16 = {nullptr, 0, 0}, f16_k32 = {nullptr, 0, 0};
     if constexpr (NPL == 2) f16 = conv_launch<NPL, TH, D, DA, SPB, true>();
-    if constexpr (NPL == 2 && TH == 16 && D == 4) f16_k32 = {k_unet_conv_k32, UK_THREADS, UK_LDS};
+    if constexpr (NPL == 2 && TH == 16 && D == 4) f16_k32 = conv_launch_k32<UkTiles16>();
+    if constexpr (NPL == 2 && TH == 8) f16_k32 = conv_launch_k32<UkTiles8>();
     return {CODE, NPL, TH, D, DA, SPB, {conv_launch<NPL, TH, D, DA, SPB, false>(), f16, f16_k32}};
 }
-constexpr ConvFlavour CONV_FLAVOURS[] = {      //                                                     LDS bytes (K = 32: 131 072)
+constexpr ConvFlavour CONV_FLAVOURS[] = {      //                                                     LDS bytes (K = 32: 131 072; code 0: 81 920)
     conv_flavour<0, 2, 8, 2>(),                // 8-row tiles (two workgroups per CU)                    73 728
     conv_flavour<1, 2, 16, 2>(),               // 16-row tiles, three taps                              106 496
     conv_flavour<2, 2, 16, 4>(),               // ... four and more taps, one step per barrier          122 880
@@ -151,8 +158,10 @@ struct ConvPlan {
 };
 
 // Validates the descriptor and chooses the flavour: TIP_OK and `pl`, or the error tip_unet_conv_dev returns.  Touches no device.
-static int unet_conv_plan(const tip_unet_conv_desc *d, ConvPlan &pl)
+// flags: the caller's per-call choices (TIP_UNET_CONV_*, include/tissue_hip.h); 0 is what the entries without flags ask for.
+static int unet_conv_plan(const tip_unet_conv_desc *d, int flags, ConvPlan &pl)
 {
+    if (flags & ~TIP_UNET_CONV_ROWS8_K32) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: unknown flags 0x%x", flags);
     if (!d || !d->in0 || !d->weights || (!d->bias && !d->raw_out) || (!d->out && !d->head_out && !d->raw_out)) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: null pointer");
     if (!pieces_ok(d->planes, d->format)) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: pieces are 2 or 3 planes of bf16 (format 0) or 2 planes of fp16 (format 1)");
     if (d->format == 1 && !(d->acc_scale > 0.f)) return fail(TIP_ERR_ARG, "tip_unet_conv_dev: fp16 pieces come with a positive acc_scale");
@@ -197,8 +206,11 @@ static int unet_conv_plan(const tip_unet_conv_desc *d, ConvPlan &pl)
     const int spb = (th == 16 && dist == 4 && three && tuning().unet_spb > 1) ? 3 : 1;
     // The MFMA shape is a second property of the launch: the codes below do not change with it.  Two fp16 pieces on 16-row tiles with
     // four and more taps (flavours 2 and 6) run ONE K = 32 kernel, one pair step per barrier, unless TIP_UNET_MFMA=16 -- so
-    // TIP_UNET_SPB does not change a bit of what these launches compute.
-    pl.mfma_k = (d->format == 1 && d->planes == 2 && th == 16 && dist == 4 && tuning().unet_mfma == 32) ? 32 : 16;
+    // TIP_UNET_SPB does not change a bit of what these launches compute.  The 8-row launches with four and more taps (flavour 0) run
+    // that kernel on their own tiles only where the CALLER asks for it (TIP_UNET_CONV_ROWS8_K32): K = 32 rounds two steps' sums
+    // together, so its bits are not the 32x32x16 kernel's, and what a call without the flag computes does not change.
+    const bool k32_tiles = (th == 16 && dist == 4) || (th == 8 && d->ntaps >= 4 && (flags & TIP_UNET_CONV_ROWS8_K32));
+    pl.mfma_k = (d->format == 1 && d->planes == 2 && k32_tiles && tuning().unet_mfma == 32) ? 32 : 16;
     const int which = pl.mfma_k == 32 ? CONV_F16_K32 : d->format == 1 ? CONV_F16 : CONV_BF16;
     for (int row = 0; row < N_CONV_FLAVOURS; ++row) {
         const ConvFlavour &f = CONV_FLAVOURS[row];
@@ -209,26 +221,30 @@ static int unet_conv_plan(const tip_unet_conv_desc *d, ConvPlan &pl)
     return fail(TIP_ERR_UNSUPPORTED, "tip_unet_conv_dev: no kernel flavour <%d, %d, %d, %d, %d>", d->planes, th, dist, da, spb);
 }
 
-int tip_unet_conv_flavour(const tip_unet_conv_desc *d)
+int tip_unet_conv_flavour_ex(const tip_unet_conv_desc *d, int flags)
 {
     ConvPlan pl;
-    const int rc = unet_conv_plan(d, pl);
+    const int rc = unet_conv_plan(d, flags, pl);
     return rc ? rc : pl.fl->code;
 }
+int tip_unet_conv_flavour(const tip_unet_conv_desc *d) { return tip_unet_conv_flavour_ex(d, 0); }
 
-int tip_unet_conv_mfma_k(const tip_unet_conv_desc *d)
+int tip_unet_conv_mfma_k_ex(const tip_unet_conv_desc *d, int flags)
 {
     ConvPlan pl;
-    const int rc = unet_conv_plan(d, pl);
+    const int rc = unet_conv_plan(d, flags, pl);
     return rc ? rc : pl.mfma_k;
 }
+int tip_unet_conv_mfma_k(const tip_unet_conv_desc *d) { return tip_unet_conv_mfma_k_ex(d, 0); }
 
-int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream)
+int tip_unet_conv_dev(const tip_unet_conv_desc *d, void *stream) { return tip_unet_conv_ex_dev(d, 0, stream); }
+
+int tip_unet_conv_ex_dev(const tip_unet_conv_desc *d, int flags, void *stream)
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
     ConvPlan pl;
-    if (const int rc = unet_conv_plan(d, pl)) return rc;
+    if (const int rc = unet_conv_plan(d, flags, pl)) return rc;
     ConvParams p;
     p.in0 = (const uint16_t *)d->in0; p.in1 = (const uint16_t *)(d->c1 > 0 ? d->in1 : d->in0);
     p.c0 = d->c0; p.c1 = d->c1; p.H = d->h; p.W = d->w;

@@ -342,7 +342,7 @@ static_assert(uc_conflict_free<UcRead32>(), "16 different bank quads per lane gr
 static_assert(uc_copy_fills(256), "weight tile: slot q of a plane holds what a reader of row q >> 1 expects");
 
 // The image's sizes, declared ONCE, for the kernels (k_unet_conv's names are aliases of these members, k_unet_conv_k32 takes its tiles from
-// UcLayout<2, 16, 4>) and for the launcher (tip_unet.hip: a launch's threads and dynamic LDS size are THREADS and LDS).  The
+// UcLayout<2, 16, 4> or UcLayout<2, 8, 2>) and for the launcher (tip_unet.hip: a launch's threads and dynamic LDS size are THREADS and LDS).  The
 // template parameters are k_unet_conv's, described there.
 template <int NPL, int TH, int D, int DA = 1, int SPB = 1>
 struct UcLayout {

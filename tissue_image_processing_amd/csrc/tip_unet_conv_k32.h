@@ -1,9 +1,9 @@
-// tip_unet_conv_k32.h -- k_unet_conv's two-piece fp16 arithmetic (f16x3) on v_mfma_f32_16x16x32_f16, for 16-row tiles and stencils
-// of four and more taps.  Why: the pass runs at the board's power limit, and the clock the chip holds there depends on the MFMA
+// tip_unet_conv_k32.h -- k_unet_conv's two-piece fp16 arithmetic (f16x3) on v_mfma_f32_16x16x32_f16, for stencils of four and more
+// taps: on 16-row tiles (512 threads, one workgroup per CU) and, asked for by flag, on 8-row tiles (256 threads, two per CU).  Why: the pass runs at the board's power limit, and the clock the chip holds there depends on the MFMA
 // shape -- at this kernel's wave tile and LDS traffic the 16x16x32 loop runs 12 % faster by wall than the 32x32x16 one
 // (tools/ubench/mfma_f16_shape_lds.hip).  Everything around the products is tip_unet_conv.h's: the packed weights, the
 // LDS image (32-byte rows with the XOR swizzle, filled by asynchronous copies), the descriptor, the epilogue's five forms.
-// Shared as CODE, not as a copy: the tile layout (UcLayout<2, 16, 4>), the swizzle (uc_slot) and its conflict check
+// Shared as CODE, not as a copy: the tile layout (UcLayout<2, 16, 4> / UcLayout<2, 8, 2>: the kernel's template parameter), the swizzle (uc_slot) and its conflict check
 // (uc_conflict_free, here under this kernel's read pattern), the copy plans and the copies (UcCopies), the workgroup map
 // (uc_workgroup) and the (chunk, tap) stepper (uc_next_step).  This file has what differs: the lane maps, the pair step's products
 // and schedule, the weight ring, and the epilogue and seed loads on this kernel's lane map.
@@ -17,9 +17,13 @@
 //     buffers.
 //   * An odd step count: the last step is alone.  Lanes 32-63 then read the same step as lanes 0-31 (finite values, not whatever
 //     the ring holds) and their activation fragments are zeroed in registers: once per workgroup.
-//   * Weight ring: three pair steps = six 8 KB tiles.  With the two 40 KB activation buffers: 128 KB.
-//   * The workgroup's barrier stands in the MIDDLE of a pair step; the copies of pair j + 2 and of the next chunk go out right behind
+//   * 16-row tiles.  Weight ring: three pair steps = six 8 KB tiles.  With the two 40 KB activation buffers: 128 KB.  The
+//     workgroup's barrier stands in the MIDDLE of a pair step; the copies of pair j + 2 and of the next chunk go out right behind
 //     it (the main loop has the ordering argument).
+//   * 8-row tiles.  Two workgroups share a CU, so a workgroup has 80 KB: two 24 KB activation buffers and a ring of TWO pair steps
+//     (four tiles).  A ring of two cannot carry the middle barrier -- pair j + 1 would land in the slots pair j - 1's second half
+//     still reads -- so the barrier stands BETWEEN pair steps and the copies of pair j + 1 go out behind the one that opens pair j.
+// Everything per wave is the same in both: lane maps, reads, products and their order, the epilogue.
 // Lane maps.  Weights stay the A operand (M = output channels).  MFMA row rho of a 16-row block reads stored weight row
 // uk_map16(rho), MFMA column j reads pixel uk_map16(j) of a 16-pixel group: 8-11 <-> 12-15.  With ds_read_b128's lane groups and the
 // swizzle the identity order conflicts two-way; this order is conflict-free for 16 consecutive rows or pixels at any alignment
@@ -70,18 +74,29 @@ __device__ __forceinline__ void uc_lds_wait(u32x4 &a, u32x4 &b, u32x4 &c, u32x4 
     asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "n"(N));
 }
 
-// The tiles are those of k_unet_conv<2, 16, 4> (tip_unet_conv.h: UcLayout); the weight ring and with it the LDS size are this kernel's.
-using UkTiles = UcLayout<2, 16, 4>;
-constexpr int UK_THREADS = UkTiles::THREADS;                                                // 512 threads
-constexpr int UK_NB = 6;                                                                    // weight tiles: three pair steps
-constexpr int UK_LDS = 2 * UkTiles::A_BYTES + UK_NB * UkTiles::B_BYTES;                     // 128 KB: two 40 KB activation buffers, six 8 KB tiles
-static_assert(UK_THREADS / 64 * EP_BYTES <= UK_LDS, "the staging images fit the tile buffers");
-static_assert(UkTiles::B_PER == 1, "one weight copy instruction per thread and tile");
+// What a K = 32 launch adds to its tile layout L (tip_unet_conv.h: UcLayout; the tiles are those of k_unet_conv<2, 16, 4> resp.
+// <2, 8, 2>): where the workgroup's barrier stands, the weight ring, and with it the LDS size.  The launch table reads THREADS and LDS.
+template <typename L>
+struct UkLaunch {
+    static constexpr bool MID = L::ROWS == 16;                         // the barrier in the middle of a pair step (else: between two)
+    static constexpr int AHEAD = MID ? 2 : 1;                          // pair steps the weight copies run ahead
+    static constexpr int NB = 2 * (AHEAD + 1);                         // weight tiles: three pair steps / two
+    static constexpr int THREADS = L::THREADS;
+    static constexpr int LDS = 2 * L::A_BYTES + NB * L::B_BYTES;       // two activation buffers and the ring
+    static_assert(L::ROWS == 16 || L::ROWS == 8, "two tile rows per wave, eight waves or four");
+    static_assert(THREADS / 64 * EP_BYTES <= LDS, "the staging images fit the tile buffers");
+};
+using UkTiles16 = UcLayout<2, 16, 4>;         // 512 threads; 128 KB: two 40 KB activation buffers, six 8 KB tiles
+using UkTiles8 = UcLayout<2, 8, 2>;           // 256 threads;  80 KB: two 24 KB activation buffers, four 8 KB tiles
+static_assert(UkLaunch<UkTiles16>::LDS == 128 * 1024, "one 16-row workgroup per CU");
+static_assert(2 * UkLaunch<UkTiles8>::LDS == 160 * 1024, "two 8-row workgroups are resident: each has exactly half a CU's LDS");
 
-__global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParams p)
+template <typename UkTiles>
+__global__ void __launch_bounds__(UkTiles::THREADS, 2) k_unet_conv_k32(const ConvParams p)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool F16 = true;
+    using K = UkLaunch<UkTiles>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *sA = smem, *sB = smem + 2 * UkTiles::A_BYTES;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -91,7 +106,7 @@ __global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParam
     const int nblk = wg.nblk;
     const int ty0 = (wg.tile / tilesX) * UkTiles::ROWS, tx0 = (wg.tile % tilesX) * UC_TW;
     const int cin = p.c0 + p.c1, nchunks = cin / UC_KC, nsteps = nchunks * p.ntaps;
-    UcCopies<2, UkTiles> cp(p, sA, sB, tid, wave, ty0, tx0, nblk);       // the tile copies (tip_unet_conv.h); one instruction per thread and weight tile
+    UcCopies<2, UkTiles> cp(p, sA, sB, tid, wave, ty0, tx0, nblk);       // the tile copies (tip_unet_conv.h)
 
     // Accumulators: [pixel group g = 2 (tile row) + (16-pixel half)][16-row block n]; the lane's pixel and channels: see the top
     f32x4 acd[4][8];
@@ -106,10 +121,10 @@ __global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParam
     const int c16 = uk_map16(lane & 15);                 // the lane's pixel inside a 16-pixel group, and its weight row inside a 16-row block
     const int cbch = uk_chan(kq);
 
-    // prologue: activation chunk 0, the weight tiles of pair steps 0 and 1 (a step that does not exist: the last one again -- every
-    // wave issues the same number of copies, and nothing reads the tile)
+    // prologue: activation chunk 0, the weight tiles of the first AHEAD pair steps (a step that does not exist: the last one again --
+    // every wave issues the same number of copies, and nothing reads the tile)
     cp.copy_a(0, 0);
-    for (int s0 = 0; s0 < 4; ++s0) {
+    for (int s0 = 0; s0 < 2 * K::AHEAD; ++s0) {
         const int st = min(s0, nsteps - 1);
         cp.copy_b(st / p.ntaps, st % p.ntaps, s0);
     }
@@ -134,8 +149,8 @@ __global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParam
 #define UK_ROW(N_, PA, PB)                                                                                      \
     _Pragma("unroll") for (int g = 0; g < 4; ++g) acd[g][N_] = uk_mfma(gb[N_][PB], ga[g][PA], acd[g][N_]);
     // One pair step.  (ca, ta) / (cb, tb): (chunk, tap) of the lanes' steps 2j / 2j + 1; wbuf: the ring tile of step 2j.
-    // `mid` runs between the two halves: the loop's barrier and copies (see there).
-    auto pair_products = [&](auto tail_c, int ca, int ta, int cb2, int tb2, int wbuf, auto &&mid) {
+    // `head` runs behind the first reads' issue, `mid` between the two halves: the loop's copies and barrier (see there).
+    auto pair_products = [&](auto tail_c, int ca, int ta, int cb2, int tb2, int wbuf, auto &&head, auto &&mid) {
         constexpr bool TAIL = decltype(tail_c)::value;
         const int dya = p.dy[ta], dxa = p.dx[ta], dyb = p.dy[tb2], dxb = p.dx[tb2];
         const int dyl = odd ? dyb : dya, dxl = odd ? dxb : dxa, cl = odd ? cb2 : ca;
@@ -156,6 +171,8 @@ __global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParam
         };
         uc_lds_read<AP>(ga[0][1], ra0); uc_lds_read<AP + XH>(ga[1][1], ra0); uc_lds_read<AP>(ga[2][1], ra1); uc_lds_read<AP + XH>(ga[3][1], ra1);
         uc_lds_read<0>(gb[0][0], rb); uc_lds_read<BN>(gb[1][0], rb); uc_lds_read<2 * BN>(gb[2][0], rb); uc_lds_read<3 * BN>(gb[3][0], rb);
+        __builtin_amdgcn_sched_barrier(0);
+        head();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         UK_W(3, ga[0][1], ga[1][1], ga[2][1], ga[3][1], gb[0][0]);
@@ -214,45 +231,60 @@ __global__ void __launch_bounds__(UK_THREADS, 2) k_unet_conv_k32(const ConvParam
 
     {
         int c0 = 0, t0 = 0;                              // (chunk, tap) of the pair's first step
-        int cw = 4 / p.ntaps, tw = 4 % p.ntaps;          // ... and of the next weight copy (two pair steps ahead)
+        int cw = 2 * K::AHEAD / p.ntaps, tw = 2 * K::AHEAD % p.ntaps;      // ... and of the next weight copy (AHEAD pair steps ahead)
         int pb = 0;                                      // the pair's place in the ring (tiles 2 pb, 2 pb + 1)
         int a_issued = 0;                                // highest chunk whose activations are on their way (chunk 0: prologue)
-        // The workgroup's barrier stands in the MIDDLE of a pair step, not between two: a wave that has issued the pair's last read
-        // waits there until its copies of the next pair's tiles have landed (issued a pair step ago), and behind the barrier
+        // 16-row tiles.  The workgroup's barrier stands in the MIDDLE of a pair step, not between two: a wave that has issued the
+        // pair's last read waits there until its copies of the next pair's tiles have landed (issued a pair step ago), and behind the barrier
         //   * every wave's copies of pair j + 1 have landed, so a wave goes from pair j's last product straight to pair j + 1's
         //     reads -- no barrier, no first-operand latency with an empty matrix pipe between two pair steps;
         //   * every wave has read all of pair j - 1, so the copies of pair j + 2 (its place in the ring) and, when pair j BEGINS
         //     inside chunk c, of chunk c + 1 (the buffer of chunk c - 1) go out right there, in front of the second half's products.
         // The next chunk is then waited for at the next middle barrier, a pair step before its first read at the earliest (t0 is 0
         // or 1 where it is issued, and the stencils have four taps and more); a_due covers the case that is not.
+        // 8-row tiles.  The barrier stands BETWEEN pair steps (the ring of two, see the top).  Behind the barrier that opens pair j
+        // every wave has read all of pair j - 1, so the copies of pair j + 1 (pair j - 1's place) and of chunk c + 1 (as above:
+        // the buffer of chunk c - 1, which pair j, beginning in chunk c, does not read) go out there -- behind the issue of the
+        // pair's first reads, which do not wait for them.  In front of the barrier that closes pair j a wave waits for its own
+        // copies: a whole pair step of flight.  A chunk issued where t0 is 0 or 1 is first read by a LATER pair (four taps and
+        // more), so it has landed and been waited for: no a_due here.
         for (int s = 0; s + 1 < nsteps; s += 2) {
             int c1 = c0, t1 = t0;
             uc_next_step(c1, t1, p.ntaps);
             const bool issue_a = c0 + 1 < nchunks && c0 + 1 > a_issued;
-            const bool a_due = issue_a && t0 + 3 >= p.ntaps;
             const int ca = c0 + 1;
-            const bool issue_b = s + 4 < nsteps;
-            pair_products(std::false_type{}, c0, t0, c1, t1, 2 * pb, [&]() {
-                asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+            const bool issue_b = s + 2 * K::AHEAD < nsteps;
+            auto copies = [&]() {
                 if (issue_a) { a_issued = ca; cp.copy_a(ca, ca & 1); }
                 if (issue_b) {
-                    const int wb = 2 * (pb == 0 ? 2 : pb - 1);       // pair j + 2 takes the place pair j - 1 had
+                    const int wb = 2 * (K::MID ? (pb == 0 ? 2 : pb - 1) : pb ^ 1);       // pair j + AHEAD takes the place pair j - 1 had
                     const int cw0 = cw, tw0 = tw;
                     cp.copy_b(cw0, tw0, wb);
                     uc_next_step(cw, tw, p.ntaps);
-                    if (s + 5 < nsteps) { cp.copy_b(cw, tw, wb + 1); uc_next_step(cw, tw, p.ntaps); }
+                    if (s + 2 * K::AHEAD + 1 < nsteps) { cp.copy_b(cw, tw, wb + 1); uc_next_step(cw, tw, p.ntaps); }
                     else cp.copy_b(cw0, tw0, wb + 1);       // (an odd step count: the unpaired step's tile twice, the second one unread)
                 }
-            });
-            if (a_due) uc_wait_barrier<0>();
+            };
+            if constexpr (K::MID) {
+                const bool a_due = issue_a && t0 + 3 >= p.ntaps;
+                pair_products(std::false_type{}, c0, t0, c1, t1, 2 * pb, []() {}, [&]() {
+                    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+                    copies();
+                });
+                if (a_due) uc_wait_barrier<0>();
+            } else {
+                pair_products(std::false_type{}, c0, t0, c1, t1, 2 * pb, copies, []() {});
+                uc_wait_barrier<0>();
+            }
             c0 = c1; t0 = t1;
             uc_next_step(c0, t0, p.ntaps);
-            pb = pb == 2 ? 0 : pb + 1;
+            pb = pb == K::AHEAD ? 0 : pb + 1;
         }
         // an odd step count: the last step alone, behind the loop (inside it, a second product path makes the compiler spill the
-        // accumulators); its tile landed in front of the last middle barrier
-        if (nsteps & 1) pair_products(std::true_type{}, c0, t0, c0, t0, 2 * pb, []() {});
-        uc_wait_barrier<0>();                            // the epilogue writes its staging images over the tile buffers
+        // accumulators); its tile landed in front of the last barrier
+        if (nsteps & 1) pair_products(std::true_type{}, c0, t0, c0, t0, 2 * pb, []() {}, []() {});
+        // the epilogue writes its staging images over the tile buffers (8-row tiles, even step count: the loop's last barrier was that one)
+        if (K::MID || (nsteps & 1)) uc_wait_barrier<0>();
     }
 #undef UK_ROW
 
