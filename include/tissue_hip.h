@@ -619,6 +619,16 @@ TIP_API int tip_deflate_rows_dev(const void *src_dev, int64_t nbytes, int elem_b
                                  int64_t *out_bytes_host, uint32_t *crc32_host);
 TIP_API int tip_deflate_rows(const void *src, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst, int64_t cap,
                              int64_t *out_bytes, uint32_t *crc32);
+/* The same tokens, framing, contracts, error codes and bound with DYNAMIC Huffman codes: per chunk the tokens become either the */
+/* fixed-Huffman block of the entries above or one dynamic-Huffman block with the chunk's own literal/length and distance codes   */
+/* (optimal lengths limited to 15 bits, a constant code-length code), whichever is fewer bytes -- a tie gives the fixed form --,  */
+/* so no chunk is longer than the entries above write it.  row_bytes == 0 selects the run-only token rule (tip_deflate_runs'),    */
+/* row_bytes > 0 the rows rule (tip_deflate_rows'); TIP_ERR_ARG for a negative row_bytes or one that is no multiple of elem_bytes.*/
+/* The stream: tip_deflate.hip's dynamic section, specified in tests/deflate_dynamic_restate.py.                                  */
+TIP_API int tip_deflate_dynamic_dev(const void *src_dev, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst_dev, int64_t cap,
+                                    int64_t *out_bytes_host, uint32_t *crc32_host);
+TIP_API int tip_deflate_dynamic(const void *src, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst, int64_t cap,
+                                int64_t *out_bytes, uint32_t *crc32);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-"""The deflate encoder of csrc/tip_deflate.hip (runs, or runs and matches to the row above) from Python, and what turns its output into a `.npy` archive member:
+"""The deflate encoder of csrc/tip_deflate.hip (runs, or runs and matches to the row above; fixed or per-chunk dynamic codes) from Python, and what turns its output into a `.npy` archive member:
 the CRC-32 of a concatenation from the parts' CRCs, and the member builder that puts the array header in front as a stored
 block and closes the stream.  Nothing here inflates or deflates on the host."""
 import ctypes
@@ -67,13 +67,25 @@ def deflate_rows_dev(src_ptr, nbytes, elem_bytes, row_bytes, dst_ptr, cap):
     return int(size.value), int(crc.value)
 
 
-def _deflate_host(data, elem_bytes, row_bytes):
+def deflate_dynamic_dev(src_ptr, nbytes, elem_bytes, row_bytes, dst_ptr, cap):
+    """tip_deflate_dynamic_dev on device addresses: the tokens of deflate_rows_dev (row_bytes > 0) or deflate_runs_dev (row_bytes 0 or
+    None), every chunk in a dynamic-Huffman block of its own codes where that is fewer bytes than the fixed block."""
+    size, crc = ctypes.c_int64(0), ctypes.c_uint32(0)
+    _lib.check(_lib.lib().tip_deflate_dynamic_dev(src_ptr, int(nbytes), int(elem_bytes), int(row_bytes or 0), dst_ptr, int(cap),
+                                                  ctypes.byref(size), ctypes.byref(crc)))
+    return int(size.value), int(crc.value)
+
+
+def _deflate_host(data, elem_bytes, row_bytes, dynamic=False):
     src = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).view(np.uint8).ravel()
     cap = runs_bound(src.size)
     dst = np.empty(max(cap, 1), np.uint8)
     keep = src if src.size else np.zeros(1, np.uint8)      # (an empty array has no address to hand over)
     size, crc = ctypes.c_int64(0), ctypes.c_uint32(0)
-    if row_bytes is None:
+    if dynamic:
+        rc = _lib.lib().tip_deflate_dynamic(_lib.ptr(keep), src.size, int(elem_bytes), int(row_bytes or 0), _lib.ptr(dst), cap,
+                                            ctypes.byref(size), ctypes.byref(crc))
+    elif row_bytes is None:
         rc = _lib.lib().tip_deflate_runs(_lib.ptr(keep), src.size, int(elem_bytes), _lib.ptr(dst), cap, ctypes.byref(size), ctypes.byref(crc))
     else:
         rc = _lib.lib().tip_deflate_rows(_lib.ptr(keep), src.size, int(elem_bytes), int(row_bytes), _lib.ptr(dst), cap, ctypes.byref(size),
@@ -90,6 +102,11 @@ def deflate_runs(data, elem_bytes):
 def deflate_rows(data, elem_bytes, row_bytes):
     """tip_deflate_rows on a host buffer: deflate_runs with matches to the row above, row_bytes the map's row length."""
     return _deflate_host(data, elem_bytes, row_bytes)
+
+
+def deflate_dynamic(data, elem_bytes, row_bytes=None):
+    """tip_deflate_dynamic on a host buffer: deflate_rows' tokens (deflate_runs' with row_bytes None or 0) under per-chunk dynamic codes."""
+    return _deflate_host(data, elem_bytes, row_bytes, dynamic=True)
 
 
 def npy_header(shape, dtype):

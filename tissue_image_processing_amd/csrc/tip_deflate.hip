@@ -23,6 +23,8 @@
 //
 // k_deflate_runs, k_deflate_rows: one workgroup (256 threads) per chunk, one thread per segment; they differ in the token rule
 // alone (RunsRule: a byte walk with look-behind; RowsRule: bit masks of R and the M_d in registers, see there).
+// k_deflate_dynamic (tip_deflate_dynamic) is either rule with another CODING of its tokens: per chunk a dynamic-Huffman block of
+// the chunk's own codes where that is fewer bytes ("the dynamic coding", below); the steps here are shared.
 //   stage    the chunk into LDS, segment t at dword 65 t: the threads then walk their segments in step, lane l reading dword
 //            65 l + w -- bank (l + w) mod 32, all distinct within a 32-lane half (ds_read_b32), where the plain layout (stride
 //            64 dwords) would put all 64 lanes on one bank.  The global reads are consecutive dwords.
@@ -134,38 +136,72 @@ template <class Sink> __device__ static inline void put_literal(Sink &s, uint32_
     else s.put(__brev(0x190u + (v - 144u)) >> 23, 9);
 }
 
-// the length symbol of a match of 3 <= len <= 256 bytes and its extra bits; nb: their bit count (7 .. 13)
-__device__ static inline uint32_t length_code(int len, int &nb)
+// the length symbol of a match of 3 <= len <= 256 bytes; eb, extra: its extra bits' count and value
+__device__ static inline uint32_t length_symbol(int len, int &eb, uint32_t &extra)
 {
     const uint32_t n = (uint32_t)len - 3u;
-    const int eb = n < 8u ? 0 : (31 - __clz((int)n)) - 2;          // extra bits of the length symbol
-    const uint32_t sym = n < 8u ? 257u + n : 261u + 4u * eb + ((n >> eb) & 3u);
-    uint32_t v;
+    eb = n < 8u ? 0 : (31 - __clz((int)n)) - 2;
+    extra = n & ((1u << eb) - 1u);
+    return n < 8u ? 257u + n : 261u + 4u * eb + ((n >> eb) & 3u);
+}
+
+// the length symbol in the fixed code and its extra bits; nb: their bit count (7 .. 13)
+__device__ static inline uint32_t length_code(int len, int &nb)
+{
+    int eb;
+    uint32_t extra, v;
+    const uint32_t sym = length_symbol(len, eb, extra);
     if (sym < 280u) { v = __brev(sym - 256u) >> 25; nb = 7; }
     else { v = __brev(0xC0u + (sym - 280u)) >> 24; nb = 8; }
-    v |= (n & ((1u << eb) - 1u)) << nb;
+    v |= extra << nb;
     nb += eb;
     return v;
 }
 
-template <int E, class Sink> __device__ static inline void put_match(Sink &s, int len)      // 3 <= len <= 256, distance E
-{
-    int nb;
-    uint32_t v = length_code(len, nb);
-    constexpr uint32_t dist_rev5 = E == 1 ? 0u : E == 2 ? 16u : 24u;   // distance codes 0, 1, 3 (distances 1, 2, 4), five bits reversed
-    v |= dist_rev5 << nb;
-    s.put(v, nb + 5);
-}
+// ---- codings: what a token becomes.  A token rule hands its tokens to a coding: literal(sink, byte) and match(sink, len, k), k the
+// match's distance -- 0, 1, 2: the rows rule's candidates in its order; 3: elem_bytes (a run).
+// A candidate distance: d bytes (0: not kept), its fixed code -- five bits reversed, the extra bits behind them --, the bit count,
+// and its distance symbol.
+struct RowDist {
+    int d;
+    uint32_t code;
+    int nbits;
+    int sym;
+};
+struct RowDists {                           // P, P + E, P - E in the rule's order, at least one kept (row_bytes 0 on the host: none)
+    RowDist c[3];
+    long row_bytes;
+};
 
-template <int E, class Sink> __device__ static inline void put_run(Sink &s, int run, uint32_t elem)
+template <int E> struct FixedCode {         // RFC 1951's fixed code: what the run-only and the rows kernel write
+    const RowDists *dist = nullptr;           // the rows rule's candidates (k = 0, 1, 2); the run-only rule has none
+    template <class Sink> __device__ __forceinline__ void literal(Sink &s, uint32_t v) const { put_literal(s, v); }
+    template <class Sink> __device__ __forceinline__ void match(Sink &s, int len, int k) const
+    {
+        int nb;
+        uint32_t v = length_code(len, nb);
+        if (k == 3) {
+            constexpr uint32_t dist_rev5 = E == 1 ? 0u : E == 2 ? 16u : 24u;   // distance codes 0, 1, 3 (distances 1, 2, 4), five bits reversed
+            s.put(v | (dist_rev5 << nb), nb + 5);
+        } else {
+            const uint32_t code0 = dist->c[0].code, code1 = dist->c[1].code, code2 = dist->c[2].code;
+            const int nbits0 = dist->c[0].nbits, nbits1 = dist->c[1].nbits, nbits2 = dist->c[2].nbits;
+            v |= (k == 0 ? code0 : k == 1 ? code1 : code2) << nb;
+            s.put(v, nb + (k == 0 ? nbits0 : k == 1 ? nbits1 : nbits2));      // at most 13 + 18
+        }
+    }
+};
+
+template <int E, class Code, class Sink> __device__ static inline void put_run(const Code &code, Sink &s, int run, uint32_t elem)
 {
     if (run == 0) return;
-    if (run >= (E > 3 ? E : 3)) { put_match<E>(s, run); return; }
-    for (int i = 0; i < run; ++i) put_literal(s, (elem >> (8 * (i % E))) & 255u);      // (E = 1: run 1, 2; E = 2: run 2)
+    if (run >= (E > 3 ? E : 3)) { code.match(s, run, 3); return; }
+    for (int i = 0; i < run; ++i) code.literal(s, (elem >> (8 * (i % E))) & 255u);      // (E = 1: run 1, 2; E = 2: run 2)
 }
 
 // one thread's segment: nb valid bytes (a multiple of E) at seg[0 ..]; prev: the element before it, when has_prev
-template <int E, class Sink> __device__ static inline void encode_segment(Sink &s, const uint32_t *seg, int nb, bool has_prev, uint32_t prev)
+template <int E, class Code, class Sink>
+__device__ static inline void encode_segment(const Code &code, Sink &s, const uint32_t *seg, int nb, bool has_prev, uint32_t prev)
 {
     constexpr uint32_t mask = E == 4 ? 0xFFFFFFFFu : (1u << (8 * (E & 3))) - 1u;
     int run = 0;
@@ -178,39 +214,31 @@ template <int E, class Sink> __device__ static inline void encode_segment(Sink &
                 if (has_prev && x == prev) {
                     run += E;
                 } else {
-                    put_run<E>(s, run, prev);
+                    put_run<E>(code, s, run, prev);
                     run = 0;
 #pragma unroll
-                    for (int b = 0; b < E; ++b) put_literal(s, (x >> (8 * b)) & 255u);
+                    for (int b = 0; b < E; ++b) code.literal(s, (x >> (8 * b)) & 255u);
                 }
                 prev = x;
                 has_prev = true;
             }
         }
     }
-    put_run<E>(s, run, prev);
+    put_run<E>(code, s, run, prev);
 }
 
 template <int E> struct RunsRule {          // the run-only rule: nothing to prepare, the segment is walked byte by byte
+    __device__ void set(const RowDists &) {}
+    __device__ FixedCode<E> fixed_code() const { return FixedCode<E>(); }
     __device__ void prepare(const uint8_t *, long, long, const uint32_t *, int, bool, uint32_t) {}
-    template <class Sink> __device__ void encode(Sink &s, const uint32_t *seg, int nb, bool has_prev, uint32_t prev) const
+    template <class Code, class Sink>
+    __device__ void encode(const Code &code, Sink &s, const uint32_t *seg, int nb, bool has_prev, uint32_t prev) const
     {
-        encode_segment<E>(s, seg, nb, has_prev, prev);
+        encode_segment<E>(code, s, seg, nb, has_prev, prev);
     }
 };
 
 // ---- the rows rule ---------------------------------------------------------------------------------------------------------
-// A candidate distance: d bytes (0: not kept), its code -- five bits reversed, the extra bits behind them -- and the bit count.
-struct RowDist {
-    int d;
-    uint32_t code;
-    int nbits;
-};
-struct RowDists {                           // P, P + E, P - E in the rule's order, at least one kept (row_bytes 0 on the host: none)
-    RowDist c[3];
-    long row_bytes;
-};
-
 // one bit per element of the dword x: the element is zero (x: the XOR of two dwords -- their elements are equal)
 template <int E> __device__ static inline uint32_t zero_elems(uint32_t x)
 {
@@ -301,6 +329,14 @@ template <int E> struct RowsRule {
     RowDists dist;
     uint64_t r[W], m[3][W];
 
+    __device__ void set(const RowDists &d) { dist = d; }
+    __device__ FixedCode<E> fixed_code() const
+    {
+        FixedCode<E> f;
+        f.dist = &dist;
+        return f;
+    }
+
     __device__ __forceinline__ void prepare(const uint8_t *src, long nbytes, long at, const uint32_t *seg, int nb, bool has_prev, uint32_t prev)
     {
 #pragma unroll
@@ -344,43 +380,254 @@ template <int E> struct RowsRule {
         keep_bits(mk, d == 0 || first >= nb ? nb / E : first > 0 ? (int)first / E : 0, nb / E);
     }
 
-    template <class Sink> __device__ __forceinline__ void encode(Sink &s, const uint32_t *seg, int nb, bool, uint32_t) const
+    template <class Code, class Sink>
+    __device__ __forceinline__ void encode(const Code &code, Sink &s, const uint32_t *seg, int nb, bool, uint32_t) const
     {
         constexpr uint32_t mask = E == 4 ? 0xFFFFFFFFu : (1u << (8 * (E & 3))) - 1u;
-        const uint32_t code0 = dist.c[0].code, code1 = dist.c[1].code, code2 = dist.c[2].code;
-        const int nbits0 = dist.c[0].nbits, nbits1 = dist.c[1].nbits, nbits2 = dist.c[2].nbits;
         for (int pos = 0; pos < nb / E;) {
             const int run = ones_from(r, pos), u1 = ones_from(m[1], pos), u2 = ones_from(m[2], pos);
             int u = ones_from(m[0], pos), k = 0;                // the longest; a tie stays with the earlier distance
             if (u1 > u) { u = u1; k = 1; }
             if (u2 > u) { u = u2; k = 2; }
             if (u * E >= 4 && u > run) {
-                int nbits;
-                uint32_t v = length_code(u * E, nbits);
-                v |= (k == 0 ? code0 : k == 1 ? code1 : code2) << nbits;
-                s.put(v, nbits + (k == 0 ? nbits0 : k == 1 ? nbits1 : nbits2));      // at most 13 + 18
+                code.match(s, u * E, k);
                 pos += u;
             } else if (run * E >= (E > 3 ? E : 3)) {
-                put_match<E>(s, run * E);
+                code.match(s, run * E, 3);
                 pos += run;
             } else {
                 const uint32_t x = (seg[(pos * E) >> 2] >> (8 * ((pos * E) & 3))) & mask;
 #pragma unroll
-                for (int b = 0; b < E; ++b) put_literal(s, (x >> (8 * b)) & 255u);
+                for (int b = 0; b < E; ++b) code.literal(s, (x >> (8 * b)) & 255u);
                 pos += 1;
             }
         }
     }
 };
 
-// One chunk by one workgroup (this file's head): what both kernels are, but for the token rule.
-template <int E, class Rule>
-__device__ static __forceinline__ void deflate_chunk(Rule &rule, const uint8_t *__restrict__ src, long nbytes, int aligned,
+// ---- the dynamic coding (tip_deflate_dynamic; tests/deflate_dynamic_restate.py is its specification) -------------------------
+// Per chunk the tokens -- the rule's, unchanged -- are written either as above or as one dynamic-Huffman block (BTYPE 10) with the
+// chunk's own literal/length and distance codes, whichever gives fewer bytes (a tie: the fixed form), so no chunk grows and the
+// bound stays.  Code lengths: the used symbols ranked by (count, symbol); Huffman's tree by two queues (leaves in rank order,
+// internal nodes as made; the leaf on equal weights); the leaves counted per depth, depths above 15 at 15 and then repaired
+// (bl[15] -= 1, the deepest d < 15 with leaves: bl[d] -= 1, bl[d + 1] += 2, until Kraft's sum is 1); lengths handed out by rank,
+// longest first; one used symbol gets length 1; canonical codes.  Header: HLIT, HDIST trimmed, the lengths as one sequence, zero
+// runs as symbols 18 (while 11 or more remain) and 17 (3 .. 10), never 16, under a CONSTANT code-length code (4 bits for 0 .. 11,
+// 17, 18; 5 bits for 12 .. 15), so HCLEN is 19 and the first 17 + 57 bits differ between blocks in HLIT and HDIST alone.
+// Steps of k_deflate_dynamic behind the staging: walk 1 counts every thread's symbols into LDS and its fixed bits; the counters
+// add up; lengths, codes, header and both sizes; the choice; then the fixed kernels' scan and emitting walk -- with, for a
+// dynamic chunk, one more counting walk in between, whose bits and the emitting walk's come from the code table.
+// Histogram: a map's few dominant symbols would put a wave's lanes on one LDS counter (same-address atomics serialise), so there
+// are 32 copies of the 316 counters, copy (lane mod 32) at word 32 symbol + copy: the lanes of a 32-lane half hit 32 distinct
+// banks whatever their symbols, and a counter is shared by two lanes of each wave.  The copies, the sort and the tree live in the
+// output words, which are zeroed again before anything is emitted; only the code table (288 words), the four distances' codes,
+// the header (64 words) and a few counters are kept beside them: 1.5 KB more LDS than the fixed kernels.
+// The tree's merge (at most 285 steps), the repair and the header's run-length walk (at most 316 steps) are one lane's work.
+constexpr int DY_LIT = 286, DY_SYMS = DY_LIT + 30, DY_REPS = 32;
+constexpr int DY_CNT = DY_SYMS * DY_REPS, DY_LEN = DY_CNT + 320, DY_SORT = DY_LEN + 320;      // scratch, in the output words
+constexpr int DY_SORT_WORDS = 288 + 288 + 288 + 576 + 64;                                       // sw, ssym, iw, parent, bl
+constexpr int DY_DTAB = DY_SORT + DY_SORT_WORDS, DY_SCRATCH = DY_DTAB + 32;
+static_assert(DY_SCRATCH <= DF_OUT_WORDS, "the dynamic coding's scratch lies in the output words");
+constexpr int DY_TAB = 0, DY_DIST = 288, DY_HDR = 296, DY_MISC = 360, DY_WORDS = 376;         // kept, behind misc
+enum { DM_HLIT = 0, DM_HDIST, DM_BITS, DM_HDR_BITS, DM_LIMITED };
+
+// the code-length code's constant table: symbol -> code, reversed, in bits 0 .. 4, its length in bits 8 ..
+__device__ static inline uint32_t cl_code(uint32_t sym)
+{
+    if (sym < 12u) return (__brev(sym) >> 28) | (4u << 8);
+    if (sym < 16u) return (__brev(28u + (sym - 12u)) >> 27) | (5u << 8);
+    return (__brev(sym - 5u) >> 28) | (4u << 8);                 // 17, 18: the 4-bit codes 12, 13
+}
+
+// The lengths of one alphabet from its counts (this section's head), and its table: tab[s] = the canonical code, reversed, with
+// the length in bits 16 ..; 0 for an unused symbol.  All 256 threads call it; scr: DY_SORT_WORDS of scratch.
+__device__ static void code_lengths(const uint32_t *cnt, int nsym, uint32_t *len, uint32_t *tab, uint32_t *scr, uint32_t *limited)
+{
+    uint32_t *sw = scr, *ssym = scr + 288, *iw = scr + 576, *parent = scr + 864, *bl = scr + 1440, *lstart = bl + 16, *first = bl + 32,
+             *over = bl + 48;
+    const int t = threadIdx.x;
+    int n = 0;
+    for (int s = t; s == t || s < nsym; s += DF_THREADS) {      // (every thread runs the first round: it learns n)
+        const uint32_t c = s < nsym ? cnt[s] : 0u;
+        int r = 0, used = 0;
+        for (int j = 0; j < nsym; ++j) {
+            const uint32_t cj = cnt[j];
+            used += cj != 0u;
+            r += cj != 0u && (cj < c || (cj == c && j < s));
+        }
+        n = used;
+        if (s < nsym) {
+            len[s] = 0;
+            if (c) { sw[r] = c; ssym[r] = (uint32_t)s; }
+        }
+    }
+    if (t < 64) bl[t] = 0;
+    __syncthreads();
+    if (n == 1 && t == 0) bl[1] = 1;
+    if (n >= 2) {
+        if (t == 0) {                         // two queues: A the leaves 0 .. n - 1, B the internal nodes n .. as they are made
+            int a = 0, b = 0;
+            uint32_t wa = sw[0], wb = ~0u;
+            for (int made = 0; made < n - 1; ++made) {
+                uint32_t sum = 0;
+                for (int k = 0; k < 2; ++k) {
+                    if (wa <= wb) {
+                        sum += wa;
+                        parent[a] = (uint32_t)(n + made);
+                        ++a;
+                        wa = a < n ? sw[a] : ~0u;
+                    } else {
+                        sum += wb;
+                        parent[n + b] = (uint32_t)(n + made);
+                        ++b;
+                        wb = b < made ? iw[b] : ~0u;
+                    }
+                }
+                iw[made] = sum;
+                if (b == made) wb = sum;      // (B was empty: the new node is its head)
+            }
+        }
+        __syncthreads();
+        for (int r = t; r < n; r += DF_THREADS) {
+            int d = 0;
+            for (uint32_t x = (uint32_t)r; x != (uint32_t)(2 * n - 2); x = parent[x]) ++d;
+            if (d > 15) { *over = 1u; d = 15; }
+            atomicAdd(&bl[d], 1u);
+        }
+        __syncthreads();
+        if (t == 0 && *over) {
+            *limited = 1u;
+            uint32_t kraft = 0;
+            for (int d = 1; d <= 15; ++d) kraft += bl[d] << (15 - d);
+            for (; kraft > (1u << 15); --kraft) {
+                bl[15] -= 1u;
+                for (int d = 14; d >= 1; --d)
+                    if (bl[d]) { bl[d] -= 1u; bl[d + 1] += 2u; break; }
+            }
+        }
+    }
+    if (t == 0) {
+        uint32_t rank = 0, code = 0;
+        for (int d = 15; d >= 1; --d) { lstart[d] = rank; rank += bl[d]; }
+        for (int d = 1; d <= 15; ++d) { code = (code + bl[d - 1]) << 1; first[d] = code; }      // (bl[0] is 0)
+    }
+    __syncthreads();
+    for (int r = t; r < n; r += DF_THREADS)
+        for (int d = 15; d >= 1; --d)
+            if ((uint32_t)r - lstart[d] < bl[d]) len[ssym[r]] = (uint32_t)d;
+    __syncthreads();
+    for (int s = t; s < nsym; s += DF_THREADS) {
+        const uint32_t l = len[s];
+        uint32_t e = 0;
+        if (l) {
+            uint32_t k = 0;
+            for (int j = 0; j < s; ++j) k += len[j] == l;
+            e = (__brev(first[l] + k) >> (32 - l)) | (l << 16);
+        }
+        tab[s] = e;
+    }
+    __syncthreads();
+}
+
+// the header of a dynamic block into the zeroed words hdr; returns its bits.  One lane's work.
+__device__ static uint32_t dynamic_header(uint32_t *hdr, const uint32_t *len, int hlit, int hdist)
+{
+    // the code-length code's lengths in the order 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 -- 0, eleven
+    // times 4, then 5, 4, 5, 4, 5, 4, 5 --, three bits each, the first in the lowest bits: octal, read from the right
+    constexpr uint32_t order_lo = 04444444440u, order_hi = 0545454544u;      // ten and nine of them
+    WordSink s(hdr, 0u);
+    uint32_t bits = 0;
+    auto put = [&](uint32_t v, int n) { s.put(v, n); bits += (uint32_t)n; };
+    put(4u, 3);                               // BFINAL 0, then BTYPE 10 least significant bit first
+    put((uint32_t)(hlit - 257), 5);
+    put((uint32_t)(hdist - 1), 5);
+    put(19u - 4u, 4);
+    put(order_lo, 30);
+    put(order_hi, 27);
+    const int total = hlit + hdist;
+    auto at = [&](int i) { return i < hlit ? len[i] : len[DY_LIT + (i - hlit)]; };
+    for (int i = 0; i < total;) {
+        const uint32_t l = at(i);
+        if (l) {
+            const uint32_t c = cl_code(l);
+            put(c & 31u, (int)(c >> 8));
+            ++i;
+            continue;
+        }
+        int n = 1;
+        while (i + n < total && at(i + n) == 0u) ++n;
+        i += n;
+        while (n >= 11) {
+            const int m = n < 138 ? n : 138;
+            put((cl_code(18u) & 31u) | ((uint32_t)(m - 11) << 4), 4 + 7);
+            n -= m;
+        }
+        if (n >= 3) {
+            put((cl_code(17u) & 31u) | ((uint32_t)(n - 3) << 4), 4 + 3);
+        } else {
+            for (; n > 0; --n) put(cl_code(0u) & 31u, 4);
+        }
+    }
+    s.flush();
+    return bits;
+}
+
+// the extra bits of a literal/length symbol (s < DY_LIT) or of the distance symbol s - DY_LIT
+__device__ static inline uint32_t symbol_extra_bits(int s)
+{
+    if (s < DY_LIT) return s < 265 || s == 285 ? 0u : (uint32_t)(s - 261) >> 2;
+    const int d = s - DY_LIT;
+    return d < 4 ? 0u : (uint32_t)(d >> 1) - 1u;
+}
+
+template <int E> struct HistCode {          // walk 1: counts the symbols in this lane's copy, and the fixed form's bits
+    FixedCode<E> fixed;
+    uint32_t *hist;                           // this lane's copy: symbol s at hist[DY_REPS s]
+    const RowDists *dist;                     // the candidates: their distance symbols
+    template <class Sink> __device__ __forceinline__ void literal(Sink &s, uint32_t v) const
+    {
+        atomicAdd(&hist[DY_REPS * v], 1u);
+        fixed.literal(s, v);
+    }
+    template <class Sink> __device__ __forceinline__ void match(Sink &s, int len, int k) const
+    {
+        int eb;
+        uint32_t extra;
+        atomicAdd(&hist[DY_REPS * length_symbol(len, eb, extra)], 1u);
+        const int sym0 = dist->c[0].sym, sym1 = dist->c[1].sym, sym2 = dist->c[2].sym;
+        atomicAdd(&hist[DY_REPS * (DY_LIT + (k == 0 ? sym0 : k == 1 ? sym1 : k == 2 ? sym2 : E - 1))], 1u);
+        fixed.match(s, len, k);
+    }
+};
+
+struct DynCode {                            // the chunk's own codes, in LDS
+    const uint32_t *tab;                      // symbol -> code, reversed, and its length in bits 16 ..
+    const uint32_t *dist;                     // [k]: distance k's code, reversed, with its extra bits behind it; [4 + k]: the bit count
+    template <class Sink> __device__ __forceinline__ void literal(Sink &s, uint32_t v) const
+    {
+        const uint32_t e = tab[v];
+        s.put(e & 0xFFFFu, (int)(e >> 16));
+    }
+    template <class Sink> __device__ __forceinline__ void match(Sink &s, int len, int k) const
+    {
+        int eb;
+        uint32_t extra;
+        const uint32_t e = tab[length_symbol(len, eb, extra)];
+        s.put((e & 0xFFFFu) | (extra << (e >> 16)), (int)(e >> 16) + eb);                      // at most 15 + 5
+        s.put(dist[k], (int)dist[4 + k]);                                                      // at most 15 + 13
+    }
+};
+
+// One chunk by one workgroup (this file's head): what all the kernels are, but for the token rule and the coding (DYN: the
+// dynamic coding's section above; dists: the rule's candidates once more, or zeros).
+template <int E, bool DYN, class Rule>
+__device__ static __forceinline__ void deflate_chunk(Rule &rule, const RowDists &dists, const uint8_t *__restrict__ src, long nbytes, int aligned,
                                                      uint32_t *__restrict__ slots, uint32_t *__restrict__ sizes,
                                                      uint32_t *__restrict__ crc_out)
 {
     extern __shared__ uint32_t df_lds[];
     uint32_t *in = df_lds, *out = df_lds + DF_IN_WORDS, *crctab = out + DF_OUT_WORDS, *misc = crctab + 256;
+    [[maybe_unused]] uint32_t *kept = misc + 8, *dm = kept + DY_MISC;      // (DYN only: DY_WORDS more)
     const int t = threadIdx.x;
     const long base = (long)blockIdx.x * DF_CHUNK;
     const int L = (int)(nbytes - base < DF_CHUNK ? nbytes - base : DF_CHUNK);      // 1 .. 65536, a multiple of E
@@ -397,13 +644,17 @@ __device__ static __forceinline__ void deflate_chunk(Rule &rule, const uint8_t *
         in[(i >> 6) * DF_SEG_LD + (i & 63)] = d;
     }
     const int out_words = (int)((chunk_bound(L) + 3) / 4) + 1;
-    for (int i = t; i < out_words; i += DF_THREADS) out[i] = 0;
+    const int zero_words = DYN && out_words < DY_SCRATCH ? DY_SCRATCH : out_words;      // (DYN: its scratch starts from zeros too)
+    for (int i = t; i < zero_words; i += DF_THREADS) out[i] = 0;
     {
         uint32_t c = (uint32_t)t;             // the CRC of the one byte t: eight steps of the bitwise definition
         for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? DF_POLY : 0u);
         crctab[t] = c;
     }
     if (t < 8) misc[t] = 0;                   // [0..3] the waves' bit totals, [4] the workgroup's CRC
+    if constexpr (DYN) {
+        for (int i = t; i < DY_WORDS; i += DF_THREADS) kept[i] = 0;
+    }
     __syncthreads();
 
     const int first = t * DF_SEG;
@@ -411,32 +662,101 @@ __device__ static __forceinline__ void deflate_chunk(Rule &rule, const uint8_t *
     const uint32_t *seg = in + t * DF_SEG_LD;
     const bool has_prev = t > 0 && nb > 0;
     const uint32_t prev = has_prev ? in[(t - 1) * DF_SEG_LD + 63] >> (32 - 8 * E) : 0u;      // the segment before is full
+    const int lane = t & 63, wave = t >> 6;
+    // exclusive block scan of the bit counts: within the wave by shuffles, across the four waves through LDS
+    auto scan = [&](uint32_t bits, uint32_t &before, uint32_t &total) {
+        uint32_t incl = bits;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) misc[wave] = incl;
+        __syncthreads();
+        before = incl - bits;
+        total = 0;
+        for (int w = 0; w < DF_THREADS / 64; ++w) {
+            if (w < wave) before += misc[w];
+            total += misc[w];
+        }
+    };
 
     rule.prepare(src, nbytes, base + first, seg, nb, has_prev, prev);
     CountSink cs;
-    rule.encode(cs, seg, nb, has_prev, prev);
-    // exclusive block scan of the bit counts: within the wave by shuffles, across the four waves through LDS
-    const int lane = t & 63, wave = t >> 6;
-    uint32_t incl = cs.bits;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
+    uint32_t before, total, head = 3u, eob_bits = 7u;      // head: the bits in front of the first token; the fixed end of block: seven zeros
+    bool dynamic = false;
+    DynCode dyn{};
+    if constexpr (DYN) {
+        HistCode<E> hc{rule.fixed_code(), out + (t & (DY_REPS - 1)), &dists};
+        rule.encode(hc, cs, seg, nb, has_prev, prev);
+        scan(cs.bits, before, total);         // (its barrier: the counters are complete)
+        uint32_t *cnt = out + DY_CNT, *len = out + DY_LEN, *dtab = out + DY_DTAB;
+        for (int s = t; s < DY_SYMS; s += DF_THREADS) {
+            uint32_t c = 0;
+            for (int j = 0; j < DY_REPS; ++j) c += out[DY_REPS * s + ((j + s) & (DY_REPS - 1))];      // (rotated: distinct banks)
+            cnt[s] = s == 256 ? 1u : c;       // the end of block, once
+        }
+        __syncthreads();
+#ifndef DF_TIME_SKIP_CODES                    // (a timing build leaves the construction and the header out: tools/deflate_dynamic_time.py --lib)
+        code_lengths(cnt, DY_LIT, len, kept + DY_TAB, out + DY_SORT, &dm[DM_LIMITED]);
+        code_lengths(cnt + DY_LIT, DY_SYMS - DY_LIT, len + DY_LIT, dtab, out + DY_SORT, &dm[DM_LIMITED]);
+#endif
+        uint32_t bits = 0;
+        for (int s = t; s < DY_SYMS; s += DF_THREADS) {
+            if (len[s]) atomicMax(&dm[s < DY_LIT ? DM_HLIT : DM_HDIST], (uint32_t)(s < DY_LIT ? s : s - DY_LIT) + 1u);
+            bits += cnt[s] * (len[s] + symbol_extra_bits(s));
+        }
+        for (int d = 32; d >= 1; d >>= 1) bits += __shfl_xor(bits, d, 64);
+        if (lane == 0) atomicAdd(&dm[DM_BITS], bits);
+        if (t < 4) {                          // the four distances' codes: the rule's candidates, then elem_bytes
+            const RowDist rd = t < 3 ? dists.c[t] : RowDist{E, 0u, 5, E - 1};
+            const uint32_t e = rd.d ? dtab[rd.sym] : 0u;
+            kept[DY_DIST + t] = (e & 0xFFFFu) | ((rd.code >> 5) << (e >> 16));
+            kept[DY_DIST + 4 + t] = (e >> 16) + (uint32_t)(rd.nbits - 5);
+        }
+        __syncthreads();
+#ifndef DF_TIME_SKIP_CODES
+        if (t == 0) {
+            const uint32_t hlit = dm[DM_HLIT] < 257u ? 257u : dm[DM_HLIT], hdist = dm[DM_HDIST] < 1u ? 1u : dm[DM_HDIST];
+            dm[DM_HDR_BITS] = dynamic_header(kept + DY_HDR, len, (int)hlit, (int)hdist);
+        }
+#endif
+        __syncthreads();
+        // both forms' bytes, the stored block included (DM_BITS counts the end-of-block code too); a tie goes to the fixed form
+        const uint32_t fixed_bytes = (3u + total + 7u + 3u + 7u) / 8u + 4u, dynamic_bytes = (dm[DM_HDR_BITS] + dm[DM_BITS] + 3u + 7u) / 8u + 4u;
+        dynamic = dynamic_bytes < fixed_bytes;
+        dyn = DynCode{kept + DY_TAB, kept + DY_DIST};
+        __syncthreads();                      // (everyone has read the scratch)
+        for (int i = t; i < (out_words < DY_SCRATCH ? out_words : DY_SCRATCH); i += DF_THREADS) out[i] = 0;
+        if (dynamic) {
+            cs.bits = 0;
+            rule.encode(dyn, cs, seg, nb, has_prev, prev);
+            scan(cs.bits, before, total);
+            head = dm[DM_HDR_BITS];
+            eob_bits = kept[DY_TAB + 256] >> 16;
+        } else {
+            __syncthreads();                  // the output words are zero again
+        }
+    } else {
+        rule.encode(rule.fixed_code(), cs, seg, nb, has_prev, prev);
+        scan(cs.bits, before, total);
     }
-    if (lane == 63) misc[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (int w = 0; w < DF_THREADS / 64; ++w) {
-        if (w < wave) before += misc[w];
-        total += misc[w];
-    }
-    const uint32_t bitpos = 3u + before + (incl - cs.bits);
 
-    WordSink ws(out, t == 0 ? 0u : bitpos);
-    if (t == 0) ws.put(2u, 3);                // BFINAL 0, then BTYPE 01 least significant bit first
-    rule.encode(ws, seg, nb, has_prev, prev);
+    WordSink ws(out, dynamic || t > 0 ? head + before : 0u);
+    if (dynamic) {
+        if (t < 64 && kept[DY_HDR + t]) atomicOr(&out[t], kept[DY_HDR + t]);
+        rule.encode(dyn, ws, seg, nb, has_prev, prev);
+        if (t == 0) {
+            ws.flush();
+            ws = WordSink(out, head + total);
+            ws.put(kept[DY_TAB + 256] & 0xFFFFu, (int)eob_bits);
+        }
+    } else {
+        if (t == 0) ws.put(2u, 3);            // BFINAL 0, then BTYPE 01 least significant bit first
+        rule.encode(rule.fixed_code(), ws, seg, nb, has_prev, prev);
+    }
     ws.flush();
-    // end of block (seven zero bits) and the stored block's header (three) are zeros already; behind the padding LEN = 0, NLEN = FFFF
-    const uint32_t body = (3u + total + 7u + 3u + 7u) / 8u, size = body + 4u;
+    // the fixed end of block (seven zero bits) and the stored block's header (three) are zeros already; behind the padding LEN = 0, NLEN = FFFF
+    const uint32_t body = (head + total + eob_bits + 3u + 7u) / 8u, size = body + 4u;
     if (t == 0) {
         atomicOr(&out[(body + 2u) >> 2], 0xFFu << (8u * ((body + 2u) & 3u)));
         atomicOr(&out[(body + 3u) >> 2], 0xFFu << (8u * ((body + 3u) & 3u)));
@@ -469,7 +789,7 @@ __global__ __launch_bounds__(DF_THREADS) void k_deflate_runs(const uint8_t *__re
                                                              uint32_t *__restrict__ crc_out)
 {
     RunsRule<E> rule;
-    deflate_chunk<E>(rule, src, nbytes, aligned, slots, sizes, crc_out);
+    deflate_chunk<E, false>(rule, RowDists{}, src, nbytes, aligned, slots, sizes, crc_out);
 }
 
 template <int E>
@@ -478,8 +798,19 @@ __global__ __launch_bounds__(DF_THREADS) void k_deflate_rows(const uint8_t *__re
                                                              uint32_t *__restrict__ crc_out)
 {
     RowsRule<E> rule;
-    rule.dist = dist;
-    deflate_chunk<E>(rule, src, nbytes, aligned, slots, sizes, crc_out);
+    rule.set(dist);
+    deflate_chunk<E, false>(rule, dist, src, nbytes, aligned, slots, sizes, crc_out);
+}
+
+// either rule with the dynamic coding (dist: all zero with RunsRule)
+template <int E, class Rule>
+__global__ __launch_bounds__(DF_THREADS) void k_deflate_dynamic(const uint8_t *__restrict__ src, long nbytes, int aligned, RowDists dist,
+                                                                uint32_t *__restrict__ slots, uint32_t *__restrict__ sizes,
+                                                                uint32_t *__restrict__ crc_out)
+{
+    Rule rule;
+    rule.set(dist);
+    deflate_chunk<E, true>(rule, dist, src, nbytes, aligned, slots, sizes, crc_out);
 }
 
 // offsets[c] = sizes[0] + ... + sizes[c - 1]; *total = the sum.  One workgroup, 256 chunks per step.
@@ -519,12 +850,26 @@ __global__ __launch_bounds__(256) void k_deflate_compact(const uint32_t *__restr
     for (uint32_t i = threadIdx.x; i < size; i += 256) to[i] = slot[i];
 }
 
-// rows: the candidate distances of the rows rule, or null for the run-only rule
+// rows: the candidate distances of the rows rule, or null for the run-only rule; dynamic: the dynamic coding
 template <int E>
-static int launch_encode(const void *src, long nbytes, long chunks, const RowDists *rows, uint32_t *slots, uint32_t *sizes, uint32_t *crc)
+static int launch_encode(const void *src, long nbytes, long chunks, const RowDists *rows, bool dynamic, uint32_t *slots, uint32_t *sizes,
+                         uint32_t *crc)
 {
     constexpr size_t lds = (size_t)DF_LDS_WORDS * 4;
     const int aligned = (int)(((uintptr_t)src & 3u) == 0);
+    if (dynamic) {
+        constexpr size_t dlds = lds + (size_t)DY_WORDS * 4;
+        if (rows) {
+            TIP_HIP(hipFuncSetAttribute((const void *)k_deflate_dynamic<E, RowsRule<E>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));
+            TIP_LAUNCH("deflate_dynamic_rows", (k_deflate_dynamic<E, RowsRule<E>>), dim3((unsigned)chunks), dim3(DF_THREADS), dlds,
+                       (const uint8_t *)src, nbytes, aligned, *rows, slots, sizes, crc);
+            return TIP_OK;
+        }
+        TIP_HIP(hipFuncSetAttribute((const void *)k_deflate_dynamic<E, RunsRule<E>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));
+        TIP_LAUNCH("deflate_dynamic_runs", (k_deflate_dynamic<E, RunsRule<E>>), dim3((unsigned)chunks), dim3(DF_THREADS), dlds,
+                   (const uint8_t *)src, nbytes, aligned, RowDists{}, slots, sizes, crc);
+        return TIP_OK;
+    }
     if (rows) {
         TIP_HIP(hipFuncSetAttribute((const void *)k_deflate_rows<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         TIP_LAUNCH("deflate_rows", k_deflate_rows<E>, dim3((unsigned)chunks), dim3(DF_THREADS), lds, (const uint8_t *)src, nbytes, aligned,
@@ -554,7 +899,7 @@ static RowDists row_dists(int e, long row_bytes)
         const uint32_t code = t < 4u ? t : 2u * h + ((t >> eb) & 1u);
         uint32_t rev = 0;
         for (int b = 0; b < 5; ++b) rev |= ((code >> b) & 1u) << (4 - b);
-        r.c[k] = {(int)cand[k], rev | ((t & ((1u << eb) - 1u)) << 5), 5 + eb};
+        r.c[k] = {(int)cand[k], rev | ((t & ((1u << eb) - 1u)) << 5), 5 + eb, (int)code};
         r.row_bytes = row_bytes;
     }
     return r;
@@ -574,7 +919,8 @@ static int check_args(const char *who, const void *src, long nbytes, int elem_by
 }
 
 // row_bytes 0: the run-only rule -- which the rows rule also is when its row is too long for any candidate distance
-static int deflate_dev(const void *src, long nbytes, int elem_bytes, long row_bytes, void *dst, int64_t *out_bytes, uint32_t *crc32)
+static int deflate_dev(const void *src, long nbytes, int elem_bytes, long row_bytes, bool dynamic, void *dst, int64_t *out_bytes,
+                       uint32_t *crc32)
 {
     *out_bytes = 0;
     *crc32 = 0;
@@ -588,9 +934,9 @@ static int deflate_dev(const void *src, long nbytes, int elem_bytes, long row_by
     if (!slots || !sizes || !offsets || !result || !pin) return TIP_ERR_NOMEM;
     TIP_HIP(hipMemsetAsync(result, 0, 16, c.stream));
     const RowDists dists = row_dists(elem_bytes, row_bytes), *rows = dists.row_bytes ? &dists : nullptr;
-    int rc = elem_bytes == 1 ? launch_encode<1>(src, nbytes, chunks, rows, slots, sizes, (uint32_t *)(result + 1))
-           : elem_bytes == 2 ? launch_encode<2>(src, nbytes, chunks, rows, slots, sizes, (uint32_t *)(result + 1))
-                             : launch_encode<4>(src, nbytes, chunks, rows, slots, sizes, (uint32_t *)(result + 1));
+    int rc = elem_bytes == 1 ? launch_encode<1>(src, nbytes, chunks, rows, dynamic, slots, sizes, (uint32_t *)(result + 1))
+           : elem_bytes == 2 ? launch_encode<2>(src, nbytes, chunks, rows, dynamic, slots, sizes, (uint32_t *)(result + 1))
+                             : launch_encode<4>(src, nbytes, chunks, rows, dynamic, slots, sizes, (uint32_t *)(result + 1));
     if (rc) return rc;
     TIP_LAUNCH("deflate_offsets", k_deflate_offsets, dim3(1), dim3(256), 0, sizes, chunks, offsets, result);
     TIP_LAUNCH("deflate_compact", k_deflate_compact, dim3((unsigned)chunks), dim3(256), 0, slots, sizes, offsets, (uint8_t *)dst);
@@ -601,18 +947,18 @@ static int deflate_dev(const void *src, long nbytes, int elem_bytes, long row_by
     return TIP_OK;
 }
 
-// the two entry forms of both rules (row_bytes 0: run-only)
-static int entry_dev(const char *who, const void *src, long nbytes, int elem_bytes, long row_bytes, void *dst, long cap, int64_t *out_bytes,
-                     uint32_t *crc32)
+// the two entry forms of both rules (row_bytes 0: run-only) and both codings
+static int entry_dev(const char *who, const void *src, long nbytes, int elem_bytes, long row_bytes, bool dynamic, void *dst, long cap,
+                     int64_t *out_bytes, uint32_t *crc32)
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
     if (int rc = check_args(who, src, nbytes, elem_bytes, row_bytes, dst, cap, out_bytes, crc32)) return rc;
-    return deflate_dev(src, nbytes, elem_bytes, row_bytes, dst, out_bytes, crc32);
+    return deflate_dev(src, nbytes, elem_bytes, row_bytes, dynamic, dst, out_bytes, crc32);
 }
 
-static int entry_host(const char *who, const void *src, long nbytes, int elem_bytes, long row_bytes, void *dst, long cap, int64_t *out_bytes,
-                      uint32_t *crc32)
+static int entry_host(const char *who, const void *src, long nbytes, int elem_bytes, long row_bytes, bool dynamic, void *dst, long cap,
+                      int64_t *out_bytes, uint32_t *crc32)
 {
     Ctx &c = ctx();
     if (!c.stream) return TIP_ERR_HIP;
@@ -621,7 +967,7 @@ static int entry_host(const char *who, const void *src, long nbytes, int elem_by
     const uint8_t *ds = st.in((const uint8_t *)src, (size_t)nbytes);
     uint8_t *dd = st.out((uint8_t *)dst, (size_t)stream_bound(nbytes));
     if (st.rc) return st.rc;
-    if (int rc = deflate_dev(ds, nbytes, elem_bytes, row_bytes, dd, out_bytes, crc32)) return rc;
+    if (int rc = deflate_dev(ds, nbytes, elem_bytes, row_bytes, dynamic, dd, out_bytes, crc32)) return rc;
     st.set_count(dd, (size_t)*out_bytes);
     return st.finish();
 }
@@ -642,26 +988,40 @@ int tip_deflate_runs_bound(int64_t nbytes, int64_t *bound_out)
 int tip_deflate_runs_dev(const void *src_dev, int64_t nbytes, int elem_bytes, void *dst_dev, int64_t cap, int64_t *out_bytes_host,
                          uint32_t *crc32_host)
 {
-    return entry_dev("tip_deflate_runs_dev", src_dev, nbytes, elem_bytes, 0, dst_dev, cap, out_bytes_host, crc32_host);
+    return entry_dev("tip_deflate_runs_dev", src_dev, nbytes, elem_bytes, 0, false, dst_dev, cap, out_bytes_host, crc32_host);
 }
 
 int tip_deflate_runs(const void *src, int64_t nbytes, int elem_bytes, void *dst, int64_t cap, int64_t *out_bytes, uint32_t *crc32)
 {
-    return entry_host("tip_deflate_runs", src, nbytes, elem_bytes, 0, dst, cap, out_bytes, crc32);
+    return entry_host("tip_deflate_runs", src, nbytes, elem_bytes, 0, false, dst, cap, out_bytes, crc32);
 }
 
 int tip_deflate_rows_dev(const void *src_dev, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst_dev, int64_t cap,
                          int64_t *out_bytes_host, uint32_t *crc32_host)
 {
     if (row_bytes <= 0) return fail(TIP_ERR_ARG, "tip_deflate_rows_dev: row_bytes %ld is not positive", (long)row_bytes);
-    return entry_dev("tip_deflate_rows_dev", src_dev, nbytes, elem_bytes, row_bytes, dst_dev, cap, out_bytes_host, crc32_host);
+    return entry_dev("tip_deflate_rows_dev", src_dev, nbytes, elem_bytes, row_bytes, false, dst_dev, cap, out_bytes_host, crc32_host);
 }
 
 int tip_deflate_rows(const void *src, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst, int64_t cap, int64_t *out_bytes,
                      uint32_t *crc32)
 {
     if (row_bytes <= 0) return fail(TIP_ERR_ARG, "tip_deflate_rows: row_bytes %ld is not positive", (long)row_bytes);
-    return entry_host("tip_deflate_rows", src, nbytes, elem_bytes, row_bytes, dst, cap, out_bytes, crc32);
+    return entry_host("tip_deflate_rows", src, nbytes, elem_bytes, row_bytes, false, dst, cap, out_bytes, crc32);
+}
+
+int tip_deflate_dynamic_dev(const void *src_dev, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst_dev, int64_t cap,
+                            int64_t *out_bytes_host, uint32_t *crc32_host)
+{
+    if (row_bytes < 0) return fail(TIP_ERR_ARG, "tip_deflate_dynamic_dev: row_bytes %ld is negative", (long)row_bytes);
+    return entry_dev("tip_deflate_dynamic_dev", src_dev, nbytes, elem_bytes, row_bytes, true, dst_dev, cap, out_bytes_host, crc32_host);
+}
+
+int tip_deflate_dynamic(const void *src, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst, int64_t cap, int64_t *out_bytes,
+                        uint32_t *crc32)
+{
+    if (row_bytes < 0) return fail(TIP_ERR_ARG, "tip_deflate_dynamic: row_bytes %ld is negative", (long)row_bytes);
+    return entry_host("tip_deflate_dynamic", src, nbytes, elem_bytes, row_bytes, true, dst, cap, out_bytes, crc32);
 }
 
 }  // extern "C"

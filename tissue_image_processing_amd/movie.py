@@ -39,7 +39,7 @@ frame orientation (Y, X) and are copied on the device into the buffers the class
 above runs on them unchanged.  Each pipeline has its own predictor and each worker thread its own torch stream.
 
 With `GpuFrameBackend(archive=True)` the owner of frame t also deflates the frame's label map and type map on the device
-(tip_deflate_runs_dev, or tip_deflate_rows_dev with archive=dict(matches="rows")) and keeps the streams and the frame's tables; `save_seg`, called on every rank after `process_movie`, turns
+(tip_deflate_runs_dev, tip_deflate_rows_dev with archive=dict(matches="rows"), tip_deflate_dynamic_dev with codes="dynamic") and keeps the streams and the frame's tables; `save_seg`, called on every rank after `process_movie`, turns
 them into the `.seg` archive Tissue.load reads -- the maps never reach the host uncompressed.
 
 `backend` supplies the per-frame compute so the same driver runs on GPUs (GpuFrameBackend) and, for the
@@ -135,6 +135,7 @@ class GpuFrameBackend(object):
 
     SEGMENTATIONS = ("classical", "unet")
     ARCHIVE_MATCHES = ("runs", "rows")
+    ARCHIVE_CODES = ("fixed", "dynamic")
 
     def __init__(self, C, Z, Y, X, device=None, keep_planes=False, inflight=1, cell_types=None, segmentation="classical",
                  unet_weights=None, unet_channels=(1, 0), predictor_factory=None, keep_hc=False, neighbor_features=False,
@@ -147,14 +148,21 @@ class GpuFrameBackend(object):
         # together with what cell_tables() found -- area, bbox, coordinate sums, perimeter counts, neighbour pairs -- and the type
         # rows: the parts save_seg turns into the frame's `.seg` members.  type_name: the archive's name of the type cell_types
         # marks.  matches: "runs", or "rows" for matches to the row above as well (tip_deflate_rows_dev with the map's row length:
-        # a smaller stream from a slower call).
+        # a smaller stream from a slower call).  codes: "fixed", or "dynamic" for per-chunk Huffman codes under either
+        # `matches` (tip_deflate_dynamic_dev: a smaller stream again); it is kept beside the dict, in archive_codes.
         if archive is True:
             archive = {}
         if archive is not False and archive is not None and not isinstance(archive, dict):
-            raise ValueError("archive must be False, True or dict(type_name=..., matches=...)")
+            raise ValueError("archive must be False, True or dict(type_name=..., matches=..., codes=...)")
+        self.archive_codes = "fixed"
+        if isinstance(archive, dict):
+            archive = dict(archive)
+            self.archive_codes = archive.pop("codes", "fixed")
+            if self.archive_codes not in self.ARCHIVE_CODES:
+                raise ValueError("archive: codes must be one of %s, not %r" % (", ".join(repr(c) for c in self.ARCHIVE_CODES), self.archive_codes))
         self.archive = None if not isinstance(archive, dict) else dict({"type_name": "HC", "matches": "runs"}, **archive)
         if self.archive is not None and set(self.archive) != {"type_name", "matches"}:
-            raise ValueError("archive: unknown key(s) %s (known: type_name, matches)" % sorted(set(self.archive) - {"type_name", "matches"}))
+            raise ValueError("archive: unknown key(s) %s (known: type_name, matches, codes)" % sorted(set(self.archive) - {"type_name", "matches"}))
         if self.archive is not None and self.archive["matches"] not in self.ARCHIVE_MATCHES:
             raise ValueError("archive: matches must be one of %s, not %r" % (", ".join(repr(m) for m in self.ARCHIVE_MATCHES), self.archive["matches"]))
         if self.archive is not None and (cell_types or {}).get("type_index", 0) != 0:
@@ -338,15 +346,17 @@ class GpuFrameBackend(object):
         """Frame t's archive parts on pipeline p's thread: the kept label map (int32) and type map (uint8) deflated on the device
         into p's stream buffer, only the streams downloaded, plus the frame's tables as cell_tables() returned them."""
         from . import _lib
-        from ._deflate import deflate_rows_dev, deflate_runs_dev, runs_bound
+        from ._deflate import deflate_dynamic_dev, deflate_rows_dev, deflate_runs_dev, runs_bound
         P = self.Y * self.X
-        rows = self.archive["matches"] == "rows"
+        rows, dynamic = self.archive["matches"] == "rows", self.archive_codes == "dynamic"
         if getattr(p, "_stream_buf", None) is None:
             p._stream_buf = _lib.DeviceBuffer(max(runs_bound(P * 4), 1))
         dst = p._stream_buf
 
         def encode(src_ptr, nbytes, elem_bytes):
-            if rows:
+            if dynamic:
+                size, crc = deflate_dynamic_dev(src_ptr, nbytes, elem_bytes, self.X * elem_bytes if rows else 0, dst.ptr, dst.nbytes)
+            elif rows:
                 size, crc = deflate_rows_dev(src_ptr, nbytes, elem_bytes, self.X * elem_bytes, dst.ptr, dst.nbytes)
             else:
                 size, crc = deflate_runs_dev(src_ptr, nbytes, elem_bytes, dst.ptr, dst.nbytes)
