@@ -483,6 +483,42 @@ TIP_API int tip_lookup_max3_i32_dev(const int32_t *labels, int y, int x, const i
 /* Tissue.get_trackking_labels (ti.py:4021-4028): out[p] = lut[labels[p]] (lut[0] = 0)              */
 TIP_API int tip_lut_gather_i32(const int32_t *labels, const int64_t *lut, int64_t n_lut, int64_t *out, int64_t n);
 
+/* ---- event detection of one frame pair (ti.py:609-789: detect_edge_cells, find_events_iterator; csrc/tip_events.hip) --------- */
+/* detect_edge_cells as row flags: flags[r] = 1 when label r + 1 occurs in the first or last row or column of the (y, x) map, 0      */
+/* otherwise (uint8[n]; a label above n takes no part).  Only the 2 (y + x) border pixels are read.                                 */
+TIP_API int tip_border_rows_i32(const int32_t *labels, int y, int x, int64_t n, uint8_t *flags);
+TIP_API int tip_border_rows_i32_dev(const int32_t *labels, int y, int x, int64_t n, uint8_t *flags);
+/* The exact-pixel sibling of tip_lookup_max3_i32_dev: out[i] = labels[qy[i], qx[i]], -1 for points outside the frame (the events  */
+/* code reads the raw previous map, ti.py:745-760).  labels is a DEVICE pointer, the queries and out are host arrays.              */
+TIP_API int tip_lookup_i32_dev(const int32_t *labels, int y, int x, const int64_t *qy_host, const int64_t *qx_host, int64_t n,
+                               int32_t *out_host);
+/* find_events_iterator's three tests for one frame pair, over ROWS.  Per frame: id (the track label of each row), sel (valid == 1  */
+/* and empty_cell == 0), pos (positive for the differentiation type; read on sel rows only) and the neighbour sets as a CSR (offsets */
+/* int32[n + 1], adj int32[n_adj]; tip_neighbor_csr_i32's layout).  For the current frame also edge (tip_border_rows_i32 of its map)  */
+/* and under (the PREVIOUS map's label under the row's drift-shifted centroid, -1 outside the frame); first_edge_ids: the ids of the  */
+/* movie's FIRST frame's border rows.  P / C = the ids of the previous / current frame's sel rows; ids are unique among a frame's    */
+/* sel rows (the caller's to ensure; INT64_MIN is reserved).  A neighbour label n is used as a ROW INDEX, without a minus one, as     */
+/* upstream does: the row test is 0 <= n < rows and sel[n], and the neighbour's id is then id[n].                                    */
+/*   delam[r]    previous row r: id in P \ C and not in first_edge_ids, and every neighbour passes the row test with an id that is   */
+/*               neither in P \ C nor in first_edge_ids (an empty row passes).                                                        */
+/*   diff[r]     previous row r: id in P and C, positive in the current frame and not in the previous one, same neighbourhood test.  */
+/*   division[r] current row r: id in C \ P and no id of an edge row, under[r] != -1, every neighbour passes the row test in the       */
+/*               current frame, and at least one matches: its id in P and C and no edge id, under[n] != -1 and under[n] == under[r]  */
+/*               (label 0, a watershed line under both, compares equal).  n_match[r] = the matches, mother_row[r] = the matching      */
+/*               row with the largest index; 0 and -1 on rows without a division.                                                     */
+TIP_API int tip_event_flags_i32(const int64_t *id_prev, const uint8_t *sel_prev, const uint8_t *pos_prev, const int32_t *off_prev,
+                                const int32_t *adj_prev, int64_t n_prev, int64_t n_adj_prev, const int64_t *id_cur,
+                                const uint8_t *sel_cur, const uint8_t *pos_cur, const int32_t *off_cur, const int32_t *adj_cur,
+                                int64_t n_cur, int64_t n_adj_cur, const uint8_t *edge_cur, const int32_t *under_cur,
+                                const int64_t *first_edge_ids, int64_t n_first_edge, uint8_t *delam, uint8_t *diff, uint8_t *division,
+                                int32_t *n_match, int32_t *mother_row);
+TIP_API int tip_event_flags_i32_dev(const int64_t *id_prev, const uint8_t *sel_prev, const uint8_t *pos_prev, const int32_t *off_prev,
+                                    const int32_t *adj_prev, int64_t n_prev, int64_t n_adj_prev, const int64_t *id_cur,
+                                    const uint8_t *sel_cur, const uint8_t *pos_cur, const int32_t *off_cur, const int32_t *adj_cur,
+                                    int64_t n_cur, int64_t n_adj_cur, const uint8_t *edge_cur, const int32_t *under_cur,
+                                    const int64_t *first_edge_ids, int64_t n_first_edge, uint8_t *delam, uint8_t *diff,
+                                    uint8_t *division, int32_t *n_match, int32_t *mother_row);
+
 /* ---- window statistics and spatial feature maps (ti.py:1200-1266: calculate_spatial_data, the windows of get_frame_data) ---- */
 /* For each of m centres (qy, qx) and a table of n rows (cy, cx float64, area int64, type uint8, feat float64 or NULL = zeros):   */
 /* n_in = rows with (cx - qx)^2 + (cy - qy)^2 < r2 -- two subtractions, two squarings, one addition, each rounded to float64, a  */

@@ -534,3 +534,76 @@ def graph_neighbor_state_dev(offsets_ptr, adj_ptr, n, n_adj, member_ptr, state_p
 def order_features_dev(py_ptr, px_ptr, n, order, psi_ptr, degree_ptr):
     """tip_order_features_f64_dev: Delaunay degree (int64) and psi_order (float64) of n device points, left in device buffers."""
     _lib.check(_lib.lib().tip_order_features_f64_dev(py_ptr, px_ptr, n, int(order), psi_ptr, degree_ptr))
+
+
+# ---- event detection of one frame pair (csrc/tip_events.hip) ------------------------------------------------------------------------
+def border_rows(labels, n=None):
+    """tip_border_rows_i32: uint8[n], 1 where label r + 1 touches the map's border (Tissue.detect_edge_cells as row flags)."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    if labels.ndim != 2:
+        raise ValueError("border_rows takes a 2-D label map")
+    if n is None:
+        n = int(labels.max()) if labels.size else 0
+    flags = np.zeros(int(n), np.uint8)
+    _lib.check(_lib.lib().tip_border_rows_i32(_lib.ptr(labels), labels.shape[0], labels.shape[1], int(n), _lib.ptr(flags)))
+    return flags
+
+
+def border_rows_dev(labels_ptr, y, x, n, flags_ptr):
+    """tip_border_rows_i32_dev: device addresses, asynchronous on the calling thread's stream."""
+    _lib.check(_lib.lib().tip_border_rows_i32_dev(labels_ptr, y, x, int(n), flags_ptr))
+
+
+def lookup_exact_dev(labels_ptr, y, x, qy, qx):
+    """tip_lookup_i32_dev: int32 labels[qy, qx] of a DEVICE label map at host query points, -1 outside the frame."""
+    qy = np.ascontiguousarray(qy, dtype=np.int64).reshape(-1)
+    qx = np.ascontiguousarray(qx, dtype=np.int64).reshape(-1)
+    if qy.size != qx.size:
+        raise ValueError("qy and qx differ in length")
+    out = np.empty(qy.size, np.int32)
+    _lib.check(_lib.lib().tip_lookup_i32_dev(labels_ptr, y, x, _lib.ptr(qy), _lib.ptr(qx), qy.size, _lib.ptr(out)))
+    return out
+
+
+EVENT_OUTPUTS = (("delam", np.uint8), ("diff", np.uint8), ("division", np.uint8), ("n_match", np.int32), ("mother_row", np.int32))
+
+
+def _event_frame(frame, more=()):
+    """one frame's rows as the C-ABI takes them: id int64, sel / pos uint8, the CSR int32, then the columns named in `more`"""
+    ids = np.ascontiguousarray(frame["id"], dtype=np.int64).reshape(-1)
+    n = ids.size
+    offsets = np.ascontiguousarray(frame["offsets"], dtype=np.int32).reshape(-1)
+    adj = np.ascontiguousarray(frame["adj"], dtype=np.int32).reshape(-1)
+    if offsets.size != n + 1:
+        raise ValueError("offsets has %d entries for %d rows" % (offsets.size, n))
+    out = dict(id=ids, sel=_bytes_column(frame["sel"], n, "sel"), pos=_bytes_column(frame["pos"], n, "pos"), offsets=offsets, adj=adj)
+    for name, dtype in more:
+        out[name] = np.ascontiguousarray(frame[name], dtype=dtype).reshape(-1)
+        if out[name].size != n:
+            raise ValueError("%s has %d entries for %d rows" % (name, out[name].size, n))
+    sel_ids = ids[out["sel"] != 0]
+    if np.unique(sel_ids).size != sel_ids.size:
+        raise ValueError("event_flags: an id occurs twice among a frame's valid, non-empty rows")
+    return out
+
+
+def event_flags(prev, cur, first_edge_ids):
+    """tip_event_flags_i32 for one frame pair.  prev: dict(id, sel, pos, offsets, adj); cur: the same plus edge and under; ->
+    dict(delam, diff uint8 over the previous rows; division uint8, n_match, mother_row int32 over the current rows).  An id that
+    occurs twice among a frame's sel rows is a ValueError."""
+    p, c = _event_frame(prev), _event_frame(cur, (("edge", np.uint8), ("under", np.int32)))
+    first = np.ascontiguousarray(first_edge_ids, dtype=np.int64).reshape(-1)
+    sizes = {"delam": p["id"].size, "diff": p["id"].size}
+    out = {name: np.zeros(sizes.get(name, c["id"].size), dtype) for name, dtype in EVENT_OUTPUTS}
+    _lib.check(_lib.lib().tip_event_flags_i32(
+        *[_lib.ptr(p[k]) for k in ("id", "sel", "pos", "offsets", "adj")], p["id"].size, p["adj"].size,
+        *[_lib.ptr(c[k]) for k in ("id", "sel", "pos", "offsets", "adj")], c["id"].size, c["adj"].size,
+        _lib.ptr(c["edge"]), _lib.ptr(c["under"]), _lib.ptr(first), first.size, *[_lib.ptr(out[name]) for name, _ in EVENT_OUTPUTS]))
+    return out
+
+
+def event_flags_dev(prev_ptrs, n_prev, n_adj_prev, cur_ptrs, n_cur, n_adj_cur, edge_ptr, under_ptr, first_edge_ids_ptr, n_first_edge, out_ptrs):
+    """tip_event_flags_i32_dev: device addresses -- prev_ptrs / cur_ptrs = (id, sel, pos, offsets, adj), out_ptrs = (delam, diff,
+    division, n_match, mother_row) -- asynchronous on the calling thread's stream; no uniqueness check."""
+    _lib.check(_lib.lib().tip_event_flags_i32_dev(*prev_ptrs, n_prev, n_adj_prev, *cur_ptrs, n_cur, n_adj_cur, edge_ptr, under_ptr,
+                                                  first_edge_ids_ptr, n_first_edge, *out_ptrs))

@@ -42,6 +42,11 @@ With `GpuFrameBackend(archive=True)` the owner of frame t also deflates the fram
 (tip_deflate_runs_dev, tip_deflate_rows_dev with archive=dict(matches="rows"), tip_deflate_dynamic_dev with codes="dynamic") and keeps the streams and the frame's tables; `save_seg`, called on every rank after `process_movie`, turns
 them into the `.seg` archive Tissue.load reads -- the maps never reach the host uncompressed.
 
+`find_events`, called on every rank after `process_movie` like `save_seg`, detects the cell events -- delaminations, divisions,
+differentiations (Tissue.find_events_iterator, ti.py:636-789) -- with the label-map reads on the owners' GPUs (tip_border_rows_i32_dev,
+tip_lookup_i32_dev) and one device pass per frame pair over the table rows (tip_event_flags_i32); rank 0 gets the events table, which
+`save_seg(..., events=...)` writes into the archive (events.py).
+
 `backend` supplies the per-frame compute so the same driver runs on GPUs (GpuFrameBackend) and, for the
 multi-process CPU tests, on a stand-in backend with the gloo process group.
 """
@@ -223,6 +228,7 @@ class GpuFrameBackend(object):
         self.type_maps = {}   # frame -> DeviceBuffer (uint8 type map), with cell_types
         self.local_drifts = {}   # frame -> [(window, row shift, column shift)] of local_drift_lookup
         self._workers = []  # persistent worker threads (process_frames)
+        self._event_sets = {}   # frame -> its rows' neighbour sets as the archive's reader iterates them (event_rows)
 
     def process_frame(self, t, stack_u16):
         return self._process_with(self.pipe, t, stack_u16)
@@ -382,6 +388,52 @@ class GpuFrameBackend(object):
         _lib.check(self.pipe.lib.tip_lookup_max3_i32_dev(self.labels[t].ptr, self.Y, self.X, _lib.ptr(qy), _lib.ptr(qx),
                                                           qy.size, _lib.ptr(out)))
         return out
+
+    # -- events (find_events) ---------------------------------------------------------------------------------
+    def lookup_exact(self, t, qy, qx):
+        """Frame t's label map at (qy, qx), -1 outside the frame: lookup without the 3x3 maximum (tip_lookup_i32_dev)."""
+        from ._segmentation import lookup_exact_dev
+        return lookup_exact_dev(self.labels[t].ptr, self.Y, self.X, qy, qx)
+
+    def border_rows(self, t):
+        """uint8 per row of frame t: its cell touches the border of the resident label map (tip_border_rows_i32_dev reads the
+        2 (Y + X) border pixels; only the flags come to the host)."""
+        from . import _lib
+        from ._segmentation import border_rows_dev
+        n = self._kept(t)["area"].size
+        d_flags = _lib.DeviceBuffer(max(n, 1))
+        border_rows_dev(self.labels[t].ptr, self.Y, self.X, n, d_flags.ptr)
+        flags = d_flags.download((n,), np.uint8)
+        d_flags.free()
+        return flags
+
+    def _kept(self, t):
+        if self.archive is None:
+            raise ValueError("the event pass needs the frames' archive parts: GpuFrameBackend(..., archive=True)")
+        return self.archive_frames[t]
+
+    def event_rows(self, t):
+        """Frame t's rows for the event pass, from its kept parts: sel (valid in the end: by the area rule, or the typing's), pos
+        (positive for the archive's type; zeros untyped) and the CSR of exactly the neighbour sets frame_table writes
+        (seg_archive.neighbor_sets: with the typing's second pass, which clears the newly valid rows' sets -- built from the sets,
+        not from one working mask).  The sets stay with the backend, in the order a reader of the archive iterates them."""
+        from .events import as_archived, positive_rows, sets_to_csr
+        from .seg_archive import neighbor_sets
+        kept = self._kept(t)
+        typed = kept.get("types") is not None
+        sets, _, _, valid = neighbor_sets(kept, typed)
+        self._event_sets[t] = as_archived(sets)
+        offsets, adj = sets_to_csr(sets)
+        pos = positive_rows(kept["type"]) if typed else np.zeros(valid.size, np.uint8)
+        return dict(sel=valid.astype(np.uint8), pos=pos, offsets=offsets, adj=adj)
+
+    def classify_pair(self, t, prev, cur, first_edge_ids):
+        """The frame pair (t - 1, t) on this GPU (tip_event_flags_i32): prev / cur are the two frames' rows (id, sel, pos, offsets,
+        adj; cur also edge and under), first_edge_ids the first frame's border ids -> the row lists of events.found_rows; a
+        division with several matching neighbours takes its mother from frame t's own sets (event_rows(t) came first)."""
+        from ._segmentation import event_flags
+        from .events import found_rows
+        return found_rows(event_flags(prev, cur, first_edge_ids), prev, cur, self._event_sets[t])
 
     # -- drift (T2) ------------------------------------------------------------------------------------------
     def plane(self, t):
@@ -816,7 +868,29 @@ def process_movie(n_frames, frame_source, backend, rank=0, world=1, dist=None, d
     return _stitch(tables, lookups, stitcher, linked) if rank == 0 else (None, None)
 
 
-def save_seg(path, n_frames, backend, tables, ids, rank=0, world=1, dist=None, device="cpu", channel_names=()):
+def find_events(n_frames, backend, tables, ids, rank=0, world=1, dist=None, device="cpu", drifts=None):
+    """Detects the movie's cell events -- delaminations, divisions, differentiations -- as Tissue.find_events_iterator(1, n_frames,
+    differentiation_type_name=<the archive's type>) would on the saved archive, without a label map leaving its GPU.  Collective
+    like save_seg: EVERY rank calls it after process_movie with process_movie's results (rank 0: tables and ids per frame; the
+    others: None, None) and the backend that ran the movie with archive=... (its kept parts hold the neighbour pairs; ValueError
+    otherwise).  Returns the events DataFrame on rank 0 -- what save_seg(..., events=...) writes as events_data.pkl -- and None
+    elsewhere.  An untyped movie has no differentiations.
+
+    Rank 0 hands out ids, centroids and drift rows (drifts: None = tables[t]["drift"], the rows drifts.npy will hold).  Every
+    owner publishes its frames' rows -- sel, pos, the CSR of the table's neighbour sets (backend.event_rows), the border flags of
+    its map (backend.border_rows) -- and the labels of its map under the NEXT frame's rows at int(round(c)) + int(drift), the drift
+    truncated first (backend.lookup_exact); the owner of frame t then classifies the pair (t - 1, t) on its GPU
+    (backend.classify_pair) and the flagged rows travel to rank 0, which builds the table through Tissue.add_event
+    (events.events_table).  Six collectives per call whatever n_frames is -- two broadcasts, an all-gather and a gather with their
+    size exchanges -- with empty payloads from ranks that own nothing, so any n_frames works, including fewer frames than ranks.
+
+    ValueError, on every rank, when a frame has no table or a drift row is not finite; on the owner (the other ranks then raise
+    RuntimeError instead of waiting) when an id occurs twice among a frame's valid, non-empty rows."""
+    from .events import find_events as _find_events
+    return _find_events(n_frames, backend, tables, ids, rank, world, dist, device, drifts)
+
+
+def save_seg(path, n_frames, backend, tables, ids, rank=0, world=1, dist=None, device="cpu", channel_names=(), events=None):
     """Writes a finished movie as `<path>.seg`, the archive Tissue.load and the unmodified GUI open.  Collective: EVERY rank calls
     it after process_movie, with process_movie's results (rank 0: tables and ids per frame; the others: None, None) and the
     backend that ran the movie with archive=True or dict(type_name=...) (GpuFrameBackend).  Returns the path on rank 0, None
@@ -827,8 +901,8 @@ def save_seg(path, n_frames, backend, tables, ids, rank=0, world=1, dist=None, d
     frame_k_data.pkl from the tables it kept -- what set_labels, calculate_frame_cellinfo, calc_cell_types(plane, ..., type_name)
     when the backend types cells, and `label` = ids[t] leave in a Tissue; no device pass runs again -- deflated with the host's
     zlib, being small.  The members travel to rank 0 in one gather (_collectives.gather_varlen); rank 0 adds drifts.npy (the
-    tables[t]["drift"] rows), valid_frames.npy (ones), an empty events table, the type and channel names and
-    shape_fitting_data.json, and writes the zip itself (seg_archive.write_raw_zip: members and order of
+    tables[t]["drift"] rows), valid_frames.npy (ones), the events table (`events`, rank 0's DataFrame from find_events; None: an empty
+    one, the archive as it was before there were events), the type and channel names and shape_fitting_data.json, and writes the zip itself (seg_archive.write_raw_zip: members and order of
     Tissue._archive_members).  An archive that would need zip64 raises ValueError before anything is written."""
     from .seg_archive import save_seg as _save_seg
-    return _save_seg(path, n_frames, backend, tables, ids, rank, world, dist, device, channel_names)
+    return _save_seg(path, n_frames, backend, tables, ids, rank, world, dist, device, channel_names, events)

@@ -73,6 +73,33 @@ def _find_neighbors(neighbors, n_neighbors, by_hi, working_indices):
         n_neighbors[cell_index] = len(neighbors[cell_index])
 
 
+def neighbor_sets(kept, typed, min_cell_area=0.1, max_cell_area=10):
+    """The neighbour sets of one frame's rows as the Tissue route leaves them, from the kept parts (area, pairs and, typed, the row
+    `valid`): calculate_frame_cellinfo's find_neighbors over the rows valid by the area rule, then -- typed -- calc_cell_types'
+    second pass over the newly valid rows, which CLEARS their sets first.  -> (neighbors: object array of sets of 1-based labels,
+    n_neighbors int64, valid by the area rule, valid in the end), what frame_table writes and movie.find_events classifies."""
+    area = np.asarray(kept["area"], np.int64)
+    n = area.size
+    smallest, largest = min_cell_area * area.mean(), max_cell_area * area.mean()
+    first_valid = (area > smallest) & (area < largest)
+    pairs = np.asarray(kept["pairs"]).astype(np.int64).reshape(-1, 2)
+    if pairs.size:
+        pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]      # _segmentation.neighbor_pairs' order
+    by_hi = {}
+    for hi, lo in pairs:
+        by_hi.setdefault(int(hi), []).append(int(lo))
+    neighbors = np.empty(n, object)
+    for i in range(n):
+        neighbors[i] = set()
+    n_neighbors = np.zeros(n, np.int64)
+    _find_neighbors(neighbors, n_neighbors, by_hi, np.flatnonzero(first_valid))
+    valid = first_valid
+    if typed:
+        valid = np.asarray(kept["valid"]) != 0
+        _find_neighbors(neighbors, n_neighbors, by_hi, np.flatnonzero(valid & ~first_valid))
+    return neighbors, n_neighbors, first_valid, valid
+
+
 def frame_table(kept, ids, type_name=None, min_cell_area=0.1, max_cell_area=10):
     """The cells_info table of one frame as the Tissue route leaves it -- set_labels, calculate_frame_cellinfo, then
     calc_cell_types(plane, ..., type_name) when the frame was typed, then `label` set to the track ids -- from what the movie
@@ -100,24 +127,12 @@ def frame_table(kept, ids, type_name=None, min_cell_area=0.1, max_cell_area=10):
         full = np.zeros(n, dtype=np.float64 if name in ("perimeter", "cx", "cy") else np.int64)
         full[present] = np.asarray(values)[present]
         info[name] = full
-    smallest, largest = min_cell_area * area.mean(), max_cell_area * area.mean()
-    valid = (area > smallest) & (area < largest)
-    info["valid"] = valid.astype(int)
-    pairs = np.asarray(kept["pairs"]).astype(np.int64).reshape(-1, 2)
-    if pairs.size:
-        pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]      # _segmentation.neighbor_pairs' order
-    by_hi = {}
-    for hi, lo in pairs:
-        by_hi.setdefault(int(hi), []).append(int(lo))
-    neighbors = info["neighbors"].to_numpy()
-    n_neighbors = info["n_neighbors"].to_numpy().copy()
-    _find_neighbors(neighbors, n_neighbors, by_hi, np.flatnonzero(valid))
+    neighbors, n_neighbors, first_valid, valid = neighbor_sets(kept, type_name is not None, min_cell_area, max_cell_area)
+    info["valid"] = first_valid.astype(int)
     if type_name is not None:             # calc_cell_types on a fresh table: the new type is bit 0
         rows = np.flatnonzero(present)
         info.loc[rows, "mean_intensity_" + type_name] = np.asarray(kept["mean_intensity"], np.float64)[rows]
-        now_valid = np.asarray(kept["valid"]) != 0
-        _find_neighbors(neighbors, n_neighbors, by_hi, np.flatnonzero(now_valid & ~valid))
-        info.loc[:, "valid"] = now_valid.astype(int)
+        info.loc[:, "valid"] = valid.astype(int)
         info.loc[:, "type"] = np.asarray(kept["type"]).astype(np.int64)
     info["neighbors"] = list(neighbors)
     info["n_neighbors"] = n_neighbors
@@ -186,7 +201,7 @@ def frame_members(t, kept, ids, shape, type_name):
     return members
 
 
-def save_seg(path, n_frames, backend, tables, ids, rank=0, world=1, dist=None, device="cpu", channel_names=()):
+def save_seg(path, n_frames, backend, tables, ids, rank=0, world=1, dist=None, device="cpu", channel_names=(), events=None):
     """See movie.save_seg."""
     import io
     import json
@@ -216,7 +231,7 @@ def save_seg(path, n_frames, backend, tables, ids, rank=0, world=1, dist=None, d
         ordered.append((name,) + deflate_small(buf.getvalue()))
 
     # the movie-wide members, in Tissue._archive_members' order
-    small("events_data.pkl", lambda fh: make_df(0, EVENTS_INFO_SPEC).to_pickle(fh, compression=None))
+    small("events_data.pkl", lambda fh: (make_df(0, EVENTS_INFO_SPEC) if events is None else events).to_pickle(fh, compression=None))
     small("drifts.npy", lambda fh: np.save(fh, np.array([tables[t]["drift"] for t in range(n_frames)], np.float64).reshape(n_frames, 2)))
     small("valid_frames.npy", lambda fh: np.save(fh, np.ones((n_frames,)).astype(int)))
     small("shape_fitting_data.json", lambda fh: fh.write(json.dumps([dict() for _ in range(n_frames)]).encode()))
