@@ -154,13 +154,6 @@ def test_frame_table_without_types_has_no_type_columns():
     assert seg_archive.frame_table(dict(kept, area=np.zeros(0, np.int64)), np.zeros(0)) is None
 
 
-def test_member_wire_format_round_trip():
-    from tissue_image_processing_amd import seg_archive
-    members = [("a.npy", b"\x01\x02\x03", 0xFFFFFFFF, 3), ("frame_10_data.pkl", b"", 0, 0), ("b", bytes(range(17)), 5, 1 << 33)]
-    assert seg_archive.unpack_members(seg_archive.pack_members(members)) == members
-    assert seg_archive.unpack_members(seg_archive.pack_members([])) == []
-
-
 def test_zip64_is_refused_before_anything_is_written(tmp_path):
     from tissue_image_processing_amd import seg_archive
     path = str(tmp_path / "big.seg")

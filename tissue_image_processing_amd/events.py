@@ -6,15 +6,20 @@ A frame's rows, as the kernels take them (csrc/tip_events.hip, _segmentation.eve
 == 1 and empty_cell == 0), pos (positive for the differentiation type), the neighbour sets as a CSR, edge (the row's cell touches
 the border of its own map) and under (the PREVIOUS map's label under the row's drift-shifted centroid).  This module holds what is
 neither kernel nor backend: the CSR of the table's sets, the shifted positions, the choice of a division's mother where several
-neighbours match, the wire formats of the three exchanges and rank 0's assembly of the events table through Tissue.add_event."""
+neighbours match, the field tuples of the three exchanges and rank 0's assembly of the events table through Tissue.add_event."""
 import pickle
 
 import numpy as np
 
-from ._collectives import gather_varlen
+from ._collectives import broadcast_varlen, gather_varlen, pack_records, unpack_records
 
 BACKEND_METHODS = ("event_rows", "border_rows", "lookup_exact", "classify_pair")
-_FAILED = -1      # first word of a rank's payload when its owner step raised
+# the three exchanges, as _collectives' records keyed by frame
+MOVIE_FIELDS = (("drift", np.float64), ("id", np.int64), ("cy", np.float64), ("cx", np.float64))      # rank 0's hand-out
+ROW_FIELDS = (("sel", np.uint8), ("pos", np.uint8), ("edge", np.uint8), ("offsets", np.int32), ("adj", np.int32),
+              ("under_next", np.int32))      # an owner's frames; under_next: the frame's map under the NEXT frame's rows
+FOUND_FIELDS = (("delam", np.int64), ("diff", np.int64), ("division", np.int64), ("mother", np.int64))      # an owner's pairs
+_FAILED = -1      # key of the one record, its fields empty, that a rank sends when its owner step raised
 
 
 def sets_to_csr(sets):
@@ -81,113 +86,23 @@ def found_rows(flags, prev, cur, sets):
                 division=division, mother=mother[division])
 
 
-# ---- wire formats: flat int64 arrays, float64 values as their bit patterns -----------------------------------------------------
-def _bits(a):
-    return np.ascontiguousarray(a, np.float64).reshape(-1).view(np.int64)
-
-
-def pack_movie(n_frames, tables, ids, drifts):
-    """Rank 0's hand-out: per frame [t, n, drift row, drift column, ids (n), cy (n), cx (n)]."""
-    parts = []
-    for t in range(n_frames):
-        tb = tables[t]
-        drift = tb["drift"] if drifts is None else drifts[t]
-        frame_ids = np.asarray(ids[t], np.int64).reshape(-1)
-        n = frame_ids.size if frame_ids.size == np.asarray(tb["cy"]).size == np.asarray(tb["cx"]).size else -1      # -1: ids and table disagree
-        parts += [np.array([t, n], np.int64), _bits(drift)[:2]]
-        if n > 0:
-            parts += [frame_ids, _bits(tb["cy"]), _bits(tb["cx"])]
-    return np.concatenate(parts) if parts else np.zeros(0, np.int64)
-
-
-def unpack_movie(flat):
-    movie, pos = {}, 0
-    while pos < flat.size:
-        t, n, rows = int(flat[pos]), max(int(flat[pos + 1]), 0), int(flat[pos + 1])
-        body = flat[pos + 4:pos + 4 + 3 * n]
-        movie[t] = dict(rows=rows, drift=flat[pos + 2:pos + 4].copy().view(np.float64), id=body[:n].copy(), cy=body[n:2 * n].copy().view(np.float64),
-                        cx=body[2 * n:].copy().view(np.float64))
-        pos += 4 + 3 * n
-    return movie
-
-
-def pack_rows(rows):
-    """An owner's frames: per frame [t, n, n_adj, n_under, sel, pos, edge (n each), offsets (n + 1), adj (n_adj), under_next
-    (n_under: the frame's map under the NEXT frame's rows)]."""
-    parts = []
-    for t, r in rows.items():
-        parts += [np.array([t, r["sel"].size, r["adj"].size, r["under_next"].size], np.int64)]
-        parts += [np.asarray(r[k], np.int64).reshape(-1) for k in ("sel", "pos", "edge", "offsets", "adj", "under_next")]
-    return np.concatenate(parts) if parts else np.zeros(0, np.int64)
-
-
-def unpack_rows(flat):
-    rows, pos = {}, 0
-    while pos < flat.size:
-        t, n, n_adj, n_under = (int(v) for v in flat[pos:pos + 4])
-        pos += 4
-        r = {}
-        for name, count, dtype in (("sel", n, np.uint8), ("pos", n, np.uint8), ("edge", n, np.uint8), ("offsets", n + 1, np.int32),
-                                   ("adj", n_adj, np.int32), ("under_next", n_under, np.int32)):
-            r[name] = flat[pos:pos + count].astype(dtype)
-            pos += count
-        rows[t] = r
-    return rows
-
-
-FOUND_LISTS = ("delam", "diff", "division", "mother")
-
-
-def pack_found(found):
-    """An owner's pairs: per current frame t [t, three counts, delamination rows, differentiation rows, division rows, mother rows]."""
-    parts = []
-    for t, f in found.items():
-        parts += [np.array([t, f["delam"].size, f["diff"].size, f["division"].size], np.int64)]
-        parts += [np.asarray(f[k], np.int64).reshape(-1) for k in FOUND_LISTS]
-    return np.concatenate(parts) if parts else np.zeros(0, np.int64)
-
-
-def unpack_found(flat):
-    found, pos = {}, 0
-    while pos < flat.size:
-        t, a, b, c = (int(v) for v in flat[pos:pos + 4])
-        pos += 4
-        f = {}
-        for name, count in zip(FOUND_LISTS, (a, b, c, c)):
-            f[name] = flat[pos:pos + count].copy()
-            pos += count
-        found[t] = f
-    return found
-
-
-def _broadcast(flat, rank, world, dist, device):
-    """rank 0's int64 array on every rank: its size, then the array"""
-    if world == 1:
-        return flat
-    import torch
-    size = torch.tensor([flat.size if rank == 0 else 0], dtype=torch.int64, device=device)
-    dist.broadcast(size, src=0)
-    buf = torch.from_numpy(flat).to(device) if rank == 0 else torch.zeros(int(size.item()), dtype=torch.int64, device=device)
-    dist.broadcast(buf, src=0)
-    return buf.cpu().numpy()
-
-
-def _collect(step, what, rank, world, dist, device, root=None):
-    """Runs an owner step (-> flat int64 payload) and the gather of every rank's payload.  A step that raises still joins the
-    gather, with the failure mark, and raises afterwards; the ranks that see another rank's mark raise RuntimeError -- no rank is
-    left waiting in a collective."""
+def _collect(step, fields, what, rank, world, dist, device, root=None):
+    """Runs an owner step (-> {t: record of `fields`}) and the gather of every rank's records -> all of them in one dict ({} on a
+    rank that receives nothing).  A step that raises still joins the gather, with the failure mark, and raises afterwards; the
+    ranks that see another rank's mark raise RuntimeError -- no rank is left waiting in a collective."""
     error = None
     try:
-        flat = step()
+        records = step()
     except Exception as e:
-        error, flat = e, np.array([_FAILED], np.int64)
-    parts = [flat] if world == 1 else gather_varlen(flat, np.int64, dist, rank, world, device, root=root)
+        error, records = e, {_FAILED: {name: () for name, _ in fields}}
+    parts = gather_varlen(pack_records(records, fields), dist, rank, world, device, root=root)
     if error is not None:
         raise error
-    bad = [r for r, part in enumerate(parts or ()) if part.size and part[0] == _FAILED]
+    parts = [unpack_records(part, fields) for part in parts or ()]
+    bad = [r for r, part in enumerate(parts) if _FAILED in part]
     if bad:
         raise RuntimeError("find_events: %s failed on rank %d" % (what, bad[0]))
-    return parts
+    return {t: record for part in parts for t, record in part.items()}
 
 
 # ---- the collective -----------------------------------------------------------------------------------------------------------------
@@ -200,11 +115,16 @@ def find_events(n_frames, backend, tables, ids, rank=0, world=1, dist=None, devi
     if lacking:
         raise ValueError("find_events needs a backend with %s" % ", ".join(lacking))
     # 1. rank 0 hands out ids, centroids and drift rows; every rank checks the same numbers
-    movie = unpack_movie(_broadcast(pack_movie(n_frames, tables, ids, drifts) if rank == 0 else np.zeros(0, np.int64), rank, world, dist, device))
+    movie = {}
+    if rank == 0:
+        movie = {t: dict(drift=tables[t]["drift"] if drifts is None else drifts[t], id=ids[t], cy=tables[t]["cy"], cx=tables[t]["cx"])
+                 for t in range(n_frames)}
+    movie = unpack_records(broadcast_varlen(pack_records(movie, MOVIE_FIELDS), dist, rank, world, device), MOVIE_FIELDS)
     for t in range(n_frames):
-        if t not in movie or movie[t]["rows"] == 0:
+        sizes = set(movie[t][k].size for k in ("id", "cy", "cx")) if t in movie else {0}
+        if sizes == {0}:
             raise ValueError("find_events: frame %d has no table" % t)
-        if movie[t]["rows"] < 0:
+        if len(sizes) > 1:
             raise ValueError("find_events: frame %d's ids and table differ in length" % t)
         if not np.isfinite(movie[t]["drift"]).all():
             raise ValueError("find_events: the drift row of frame %d is not finite" % t)
@@ -225,9 +145,9 @@ def find_events(n_frames, backend, tables, ids, rank=0, world=1, dist=None, devi
                 nxt = movie[t + 1]
                 r["under_next"] = backend.lookup_exact(t, *shifted_positions(nxt["cy"], nxt["cx"], nxt["drift"]))
             rows[t] = r
-        return pack_rows(rows)
+        return rows
 
-    rows = {t: r for part in _collect(publish, "a frame's rows", rank, world, dist, device) for t, r in unpack_rows(part).items()}
+    rows = _collect(publish, ROW_FIELDS, "a frame's rows", rank, world, dist, device)
 
     # 3. the owner of frame t classifies the pair (t - 1, t); the row lists travel to rank 0
     def classify():
@@ -238,12 +158,11 @@ def find_events(n_frames, backend, tables, ids, rank=0, world=1, dist=None, devi
                 prev = dict(rows[t - 1], id=movie[t - 1]["id"])
                 cur = dict(rows[t], id=movie[t]["id"], under=rows[t - 1]["under_next"])
                 found[t] = backend.classify_pair(t, prev, cur, first_edge_ids)
-        return pack_found(found)
+        return found
 
-    parts = _collect(classify, "a pair's classification", rank, world, dist, device, root=0)
+    found = _collect(classify, FOUND_FIELDS, "a pair's classification", rank, world, dist, device, root=0)
     if rank != 0:
         return None
-    found = {t: f for part in parts for t, f in unpack_found(part).items()}
     return events_table(n_frames, tables, ids, [rows[t]["sel"] for t in range(n_frames)], found)
 
 

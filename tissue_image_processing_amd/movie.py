@@ -55,7 +55,7 @@ import collections
 
 import numpy as np
 
-from ._collectives import gather_varlen
+from ._collectives import gather_varlen, pack_records, unpack_records
 
 
 class _Job(object):
@@ -528,45 +528,6 @@ def local_drift_options(local_drifts):
     return opts
 
 
-def pack_tables(tables, extra=()):
-    """Wire format of a round's cell tables ({t: dict}) -> one float64 array: per frame the header [t, n, drift row, drift
-    column], then area, cy, cx and every column named in `extra` ((name, dtype) pairs), n values each."""
-    parts = []
-    for t, tb in tables.items():
-        parts += [np.array([t, tb["area"].size, tb["drift"][0], tb["drift"][1]], np.float64), tb["area"], tb["cy"], tb["cx"]]
-        parts += [tb[name] for name, _ in extra]
-    return np.concatenate([np.asarray(a, np.float64).ravel() for a in parts]) if parts else np.zeros(0)
-
-
-def unpack_tables(flat, extra=()):
-    """pack_tables undone -> {t: dict}: area int64, extra columns in their dtype, drift its own pair."""
-    tables, pos = {}, 0
-    while pos < flat.size:
-        t, n = int(flat[pos]), int(flat[pos + 1])
-        cols = flat[pos + 4:pos + 4 + (3 + len(extra)) * n].reshape(3 + len(extra), n)
-        tables[t] = dict(area=cols[0].astype(np.int64), cy=cols[1], cx=cols[2], drift=flat[pos + 2:pos + 4].copy())
-        for (name, dtype), col in zip(extra, cols[3:]):
-            tables[t][name] = col.astype(dtype)
-        pos += 4 + cols.size
-    return tables
-
-
-def pack_lookups(lookups):
-    """Wire format of a round's look-ups ({t: hits}) -> one int64 array: per frame [t, n], then the n hits."""
-    parts = [np.concatenate([[t, r.size], r]).astype(np.int64) for t, r in lookups.items()]
-    return np.concatenate(parts) if parts else np.zeros(0, np.int64)
-
-
-def unpack_lookups(flat):
-    """pack_lookups undone -> {t: int64 hits}."""
-    lookups, pos = {}, 0
-    while pos < flat.size:
-        t, n = int(flat[pos]), int(flat[pos + 1])
-        lookups[t] = flat[pos + 2:pos + 2 + n]
-        pos += 2 + n
-    return lookups
-
-
 def assign_track_ids(prev_ids, hit, n_cur, start_ids=None):
     """One step of the label-lookup tracker's id bookkeeping (ti.py:2041-2046, 2092-2106).
 
@@ -722,12 +683,18 @@ def _drift_step(mine, local, drifts, backend, held_planes, source):
         local[t]["drift"] = drifts[t].copy()
 
 
+TABLE_FIELDS = (("area", np.int64), ("cy", np.float64), ("cx", np.float64), ("drift", np.float64))      # then the backend's extra_columns
+LOOKUP_FIELDS = (("hits", np.int64),)
+
+
 def _exchange_tables(mine, local, extra, dist, rank, world, device):
-    """The round's cell tables on every rank, {t: dict}.  One process: the backend's own dicts, as they are."""
+    """The round's cell tables on every rank, {t: dict} (_collectives' records of TABLE_FIELDS + extra, all-gathered).  One
+    process: the backend's own dicts, as they are."""
     if world == 1:
         return {t: local[t] for t in mine}
-    parts = gather_varlen(pack_tables({t: local[t] for t in mine}, extra), np.float64, dist, rank, world, device)
-    return {t: tb for part in parts for t, tb in unpack_tables(part, extra).items()}
+    fields = TABLE_FIELDS + tuple(extra)
+    parts = gather_varlen(pack_records({t: local[t] for t in mine}, fields), dist, rank, world, device)
+    return {t: tb for part in parts for t, tb in unpack_records(part, fields).items()}
 
 
 def _owner_lookups(mine, tables, backend, held_planes, source):
@@ -772,11 +739,13 @@ def _agree_on_piv_failure(failed, error, rank, world, dist, device):
 
 
 def _gather_lookups(hits, dist, rank, world, device):
-    """The round's look-ups on rank 0, {t: hits}; {} on the other ranks."""
+    """The round's look-ups on rank 0, {t: int64 hits} (records of LOOKUP_FIELDS, gathered); {} on the other ranks.  One process:
+    `hits` as it is."""
     if world == 1:
         return hits
-    parts = gather_varlen(pack_lookups(hits), np.int64, dist, rank, world, device, root=0) or ()
-    return {t: found for part in parts for t, found in unpack_lookups(part).items()}
+    flat = pack_records({t: dict(hits=h) for t, h in hits.items()}, LOOKUP_FIELDS)
+    parts = gather_varlen(flat, dist, rank, world, device, root=0) or ()
+    return {t: r["hits"] for part in parts for t, r in unpack_records(part, LOOKUP_FIELDS).items()}
 
 
 def _link_round(linked, tables):
@@ -881,8 +850,9 @@ def find_events(n_frames, backend, tables, ids, rank=0, world=1, dist=None, devi
     its map (backend.border_rows) -- and the labels of its map under the NEXT frame's rows at int(round(c)) + int(drift), the drift
     truncated first (backend.lookup_exact); the owner of frame t then classifies the pair (t - 1, t) on its GPU
     (backend.classify_pair) and the flagged rows travel to rank 0, which builds the table through Tissue.add_event
-    (events.events_table).  Six collectives per call whatever n_frames is -- two broadcasts, an all-gather and a gather with their
-    size exchanges -- with empty payloads from ranks that own nothing, so any n_frames works, including fewer frames than ranks.
+    (events.events_table).  Six collectives per call whatever n_frames is -- a broadcast, an all-gather and a gather, each after
+    its size exchange (_collectives.broadcast_varlen, gather_varlen) -- with empty payloads from ranks that own nothing, so any
+    n_frames works, including fewer frames than ranks.
 
     ValueError, on every rank, when a frame has no table or a drift row is not finite; on the owner (the other ranks then raise
     RuntimeError instead of waiting) when an id occurs twice among a frame's valid, non-empty rows."""
@@ -900,7 +870,7 @@ def save_seg(path, n_frames, backend, tables, ids, rank=0, world=1, dist=None, d
     `.npy` members (the array header in front as a stored block, CRCs combined: _deflate.npy_member) and builds
     frame_k_data.pkl from the tables it kept -- what set_labels, calculate_frame_cellinfo, calc_cell_types(plane, ..., type_name)
     when the backend types cells, and `label` = ids[t] leave in a Tissue; no device pass runs again -- deflated with the host's
-    zlib, being small.  The members travel to rank 0 in one gather (_collectives.gather_varlen); rank 0 adds drifts.npy (the
+    zlib, being small.  The members travel to rank 0 as records in one gather (_collectives.gather_varlen); rank 0 adds drifts.npy (the
     tables[t]["drift"] rows), valid_frames.npy (ones), the events table (`events`, rank 0's DataFrame from find_events; None: an empty
     one, the archive as it was before there were events), the type and channel names and shape_fitting_data.json, and writes the zip itself (seg_archive.write_raw_zip: members and order of
     Tissue._archive_members).  An archive that would need zip64 raises ValueError before anything is written."""

@@ -9,7 +9,7 @@ import zlib
 
 import numpy as np
 
-from ._collectives import gather_varlen
+from ._collectives import broadcast_varlen, gather_varlen, pack_records, unpack_records
 from ._deflate import npy_header, npy_member
 
 ZIP32_MAX = 0xFFFFFFFF          # a size or an offset of this value or above needs zip64
@@ -141,46 +141,27 @@ def frame_table(kept, ids, type_name=None, min_cell_area=0.1, max_cell_area=10):
 
 
 # ---- members and their way to rank 0 -------------------------------------------------------------------------------------
-def pack_members(members):
-    """Wire format of a rank's members -> one int64 array: the byte count, then per member [name length, stream length, CRC,
-    size] (four int64) + name + stream, the whole padded to a multiple of eight bytes."""
-    blob = bytearray()
-    for name, raw, crc, size in members:
-        name = name.encode("utf-8")
-        blob += struct.pack("<qqqq", len(name), len(raw), crc, size) + name + raw
-    n = len(blob)
-    blob += b"\0" * (-n % 8)
-    return np.concatenate([np.array([n], np.int64), np.frombuffer(bytes(blob), np.int64)])
+ID_FIELDS = (("ids", np.int64),)      # rank 0's hand-out, keyed by frame
+MEMBER_FIELDS = (("name", np.uint8), ("stream", np.uint8), ("crc", np.int64), ("size", np.int64))      # keyed by the member's index
 
 
-def unpack_members(flat):
-    """pack_members undone -> [(name, stream, CRC, size)]."""
-    flat = np.ascontiguousarray(flat, np.int64)
-    if flat.size == 0:
-        return []
-    blob, pos, out = flat[1:].tobytes()[:int(flat[0])], 0, []
-    while pos < len(blob):
-        ln, lr, crc, size = struct.unpack_from("<qqqq", blob, pos)
-        pos += 32
-        out.append((blob[pos:pos + ln].decode("utf-8"), blob[pos + ln:pos + ln + lr], crc, size))
-        pos += ln + lr
-    return out
+def members_as_records(members):
+    """[(name, stream, CRC, size)] -> {index: record of MEMBER_FIELDS}, name and stream as their bytes."""
+    return {k: dict(name=np.frombuffer(name.encode("utf-8"), np.uint8), stream=np.frombuffer(raw, np.uint8), crc=crc, size=size)
+            for k, (name, raw, crc, size) in enumerate(members)}
+
+
+def records_as_members(records):
+    """members_as_records undone, `str` names and `bytes` streams."""
+    return [(r["name"].tobytes().decode("utf-8"), r["stream"].tobytes(), int(r["crc"][0]), int(r["size"][0])) for r in records.values()]
 
 
 def _ids_to_owners(ids, n_frames, rank, world, dist, device):
-    """Rank 0 hands out the track ids: one broadcast of [t, n, ids...] per frame (kilobytes); every rank keeps its own frames'."""
-    from .movie import pack_lookups, unpack_lookups
+    """Rank 0 hands out the track ids in one broadcast (kilobytes per frame); every rank keeps its own frames'."""
     from .pipeline import frames_for_rank
-    if world == 1:
-        return {t: np.asarray(ids[t], np.int64) for t in range(n_frames)}
-    import torch
-    flat = pack_lookups({t: np.asarray(ids[t], np.int64) for t in range(n_frames)}) if rank == 0 else np.zeros(0, np.int64)
-    size = torch.tensor([flat.size], dtype=torch.int64, device=device)
-    dist.broadcast(size, src=0)
-    buf = torch.from_numpy(flat).to(device) if rank == 0 else torch.zeros(int(size.item()), dtype=torch.int64, device=device)
-    dist.broadcast(buf, src=0)
-    every = unpack_lookups(buf.cpu().numpy())
-    return {t: every[t] for t in frames_for_rank(n_frames, rank, world)}
+    flat = pack_records({t: dict(ids=ids[t]) for t in range(n_frames)} if rank == 0 else {}, ID_FIELDS)
+    every = unpack_records(broadcast_varlen(flat, dist, rank, world, device), ID_FIELDS)
+    return {t: every[t]["ids"] for t in frames_for_rank(n_frames, rank, world)}
 
 
 def frame_members(t, kept, ids, shape, type_name):
@@ -216,11 +197,10 @@ def save_seg(path, n_frames, backend, tables, ids, rank=0, world=1, dist=None, d
     if missing:
         raise ValueError("save_seg: frames %s were not processed by this backend" % missing)
     members = [m for t in sorted(mine) for m in frame_members(t, kept[t], mine[t], (backend.Y, backend.X), type_name)]
-    if world > 1:
-        parts = gather_varlen(pack_members(members), np.int64, dist, rank, world, device, root=0)
-        if rank != 0:
-            return None
-        members = [m for part in parts for m in unpack_members(part)]
+    parts = gather_varlen(pack_records(members_as_records(members), MEMBER_FIELDS), dist, rank, world, device, root=0)
+    if rank != 0:
+        return None
+    members = [m for part in parts for m in records_as_members(unpack_records(part, MEMBER_FIELDS))]
     by_name = {m[0]: m for m in members}
     ordered = [by_name[name] for k in range(1, n_frames + 1)
                for name in ("frame_%d_labels.npy" % k, "frame_%d_types.npy" % k, "frame_%d_data.pkl" % k) if name in by_name]

@@ -18,9 +18,10 @@ CPU tests, on a stand-in with the gloo process group.
 
 import numpy as np
 
-from ._collectives import gather_varlen
+from ._collectives import gather_varlen, pack_records, unpack_records
 
 HALO = 4 + 120 + 8   # radius of sigma 1 (4 * 1) + sigma 30 (4 * 30) + sigma 2 (4 * 2): support of one projected pixel
+TILE_FIELDS = (("proj", np.float64), ("zmap", np.int64))      # a tile's interior on its way to rank 0, keyed by the tile's index
 
 
 def tile_boxes(Y, X, ny, nx, halo=HALO):
@@ -95,27 +96,22 @@ def project_tiled(tile_source, C, Y, X, grid, backend, rank=0, world=1, dist=Non
         t = torch.from_numpy(hist.astype(np.int64)).to(device)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)          # the frame's histogram on every rank
         hist = t.cpu().numpy().astype(np.uint64)
-    payload = []
+    tiles = {}
     for k in mine:
         (y0, y1, x0, x1), (py0, py1, px0, px1) = boxes[k]
         proj, zmap = backend.project(k, hist)
         sy, sx = slice(y0 - py0, y1 - py0), slice(x0 - px0, x1 - px0)
-        payload += [np.array([k], np.float64), proj[:, sy, sx].ravel(), zmap[sy, sx].astype(np.float64).ravel()]
-    flat = np.concatenate(payload) if payload else np.zeros(0)
-    parts = gather_varlen(flat, np.float64, dist, rank, world, device, root=0) if world > 1 else [flat]
+        tiles[k] = dict(proj=proj[:, sy, sx], zmap=zmap[sy, sx])
+    parts = gather_varlen(pack_records(tiles, TILE_FIELDS), dist, rank, world, device, root=0)
     if rank != 0:
         return None, None
     proj = np.empty((C, Y, X), np.float64)
     zmap = np.empty((Y, X), np.int64)
     for part in parts:
-        pos = 0
-        while pos < part.size:
-            k = int(part[pos])
+        for k, tile in unpack_records(part, TILE_FIELDS).items():
             (y0, y1, x0, x1), _ = boxes[k]
-            n = (y1 - y0) * (x1 - x0)
-            proj[:, y0:y1, x0:x1] = part[pos + 1:pos + 1 + C * n].reshape(C, y1 - y0, x1 - x0)
-            zmap[y0:y1, x0:x1] = part[pos + 1 + C * n:pos + 1 + (C + 1) * n].reshape(y1 - y0, x1 - x0).astype(np.int64)
-            pos += 1 + (C + 1) * n
+            proj[:, y0:y1, x0:x1] = tile["proj"].reshape(C, y1 - y0, x1 - x0)
+            zmap[y0:y1, x0:x1] = tile["zmap"].reshape(y1 - y0, x1 - x0)
     return proj, zmap
 
 
