@@ -666,6 +666,46 @@ TIP_API int tip_deflate_dynamic_dev(const void *src_dev, int64_t nbytes, int ele
 TIP_API int tip_deflate_dynamic(const void *src, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst, int64_t cap,
                                 int64_t *out_bytes, uint32_t *crc32);
 
+/* ---- inflate of many deflate streams, and the 16-bit TIFF row pass (csrc/tip_inflate.hip, csrc/tip_inflate_core.h; the     */
+/* ---- strips of a deflate-compressed TIFF: movie.tiff_frame_source) --------------------------------------------------------- */
+/* One status word per strip.  A strip that fails is not an error of the call: the call returns TIP_OK and counts it.          */
+enum tip_inflate_status {
+    TIP_INFLATE_OK = 0,
+    TIP_INFLATE_BAD_HEADER = 1,      /* zlib wrapper: CM != 8, CINFO > 7, FCHECK fails, or FDICT set */
+    TIP_INFLATE_BAD_BLOCK_TYPE = 2,  /* BTYPE 3 */
+    TIP_INFLATE_BAD_STORED = 3,      /* a stored block's LEN and NLEN are not complements */
+    TIP_INFLATE_BAD_LENGTHS = 4,     /* code lengths over-subscribed, or incomplete other than the one-distance-code (or no-distance-code) */
+                                     /* set zlib accepts; repeat code 16 first; a repeat past HLIT + HDIST; no end-of-block code;         */
+                                     /* HLIT > 286 or HDIST > 30                                                                          */
+    TIP_INFLATE_BAD_SYMBOL = 5,      /* literal/length 286 or 287, distance 30 or 31, or bits that are no code of an incomplete set */
+    TIP_INFLATE_BAD_DISTANCE = 6,    /* a match reaches before the start of this strip's output */
+    TIP_INFLATE_INPUT_END = 7,       /* the strip's bytes end inside the stream */
+    TIP_INFLATE_OUTPUT_FULL = 8,     /* the stream holds more than dst_len bytes (nothing beyond dst_len is written) */
+    TIP_INFLATE_OUTPUT_SHORT = 9,    /* the final block ends before dst_len bytes */
+    TIP_INFLATE_BAD_ADLER = 10       /* zlib wrapper: the Adler-32 of the output is not the stream's */
+};
+/* n_strips independent streams, RFC 1951 (wrapper 0) or RFC 1950 (wrapper 1: zlib header and Adler-32), from one source buffer */
+/* into one destination buffer.  strips: four int64 per strip -- src_off, src_len, dst_off, dst_len; a strip's window is its    */
+/* own output, so no match reaches before dst_off, and dst_len is the exact size the stream must give.  Every read stays inside */
+/* [src_off, src_off + src_len) and every write inside [dst_off, dst_off + dst_len), whatever the bytes; destination bytes      */
+/* outside every strip are left as they are.  status: one int32 per strip (tip_inflate_status); *n_bad: how many are non-zero,  */
+/* in a host word after one wait for the stream.  Before anything is launched the table is checked on the host (the _dev form   */
+/* downloads it: 32 bytes a strip): a range outside src_bytes / dst_bytes, or two non-empty destinations that overlap, give      */
+/* TIP_ERR_ARG and no device memory is written; so do a null pointer, a negative size and another wrapper.  _dev: src, strips,  */
+/* dst and status are DEVICE buffers, on the calling thread's stream.  _host: the same decoder (tip_inflate_core.h) compiled    */
+/* for the CPU, no device touched -- the reference the device form is tested against.                                           */
+TIP_API int tip_inflate_strips_dev(const void *src_dev, int64_t src_bytes, const int64_t *strips_dev, int64_t n_strips, int wrapper,
+                                   void *dst_dev, int64_t dst_bytes, int32_t *status_dev, int32_t *n_bad_host);
+TIP_API int tip_inflate_strips(const void *src, int64_t src_bytes, const int64_t *strips, int64_t n_strips, int wrapper, void *dst,
+                               int64_t dst_bytes, int32_t *status, int32_t *n_bad);
+TIP_API int tip_inflate_strips_host(const void *src, int64_t src_bytes, const int64_t *strips, int64_t n_strips, int wrapper, void *dst,
+                                    int64_t dst_bytes, int32_t *status, int32_t *n_bad);
+/* In place on a DEVICE buffer of n_rows rows of row_elems 16-bit samples, asynchronous: with swap_bytes the two bytes of every */
+/* sample change places (the file's byte order is not the host's), then with predictor 2 every row becomes its running sum      */
+/* modulo 2^16 (TIFF horizontal differencing undone; libtiff's order: swap, then accumulate).  Rows are independent.  predictor */
+/* 1: no sum; another predictor: TIP_ERR_UNSUPPORTED.                                                                            */
+TIP_API int tip_tiff_finish_u16_dev(void *stack_dev, int64_t n_rows, int64_t row_elems, int predictor, int swap_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,221 @@
+"""CPU: deflate-compressed TIFF stacks as image sources.  The fixtures under tests/golden/tiff were written by tifffile and
+expected.npz holds what the reference's own read_tiff returned for each (tools/make_goldens_tiff.py): read_tiff, the lazy
+source behind open_image / read_image_in_chunks, the cases that must keep raising, and save_tiff's opt-in zlib form."""
+import os
+import struct
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TIFF = os.path.join(ROOT, "tests", "golden", "tiff")
+READABLE = ["zlib_rps7", "zlib_rps7_bigtiff", "zlib_predictor_bigendian", "zlib_one_strip", "zlib_imagej", "zlib_u8", "plain_rps7"]
+
+
+@pytest.fixture(scope="module")
+def expected():
+    return np.load(os.path.join(TIFF, "expected.npz"), allow_pickle=False)
+
+
+def _path(name):
+    return os.path.join(TIFF, name + ".tif")
+
+
+@pytest.mark.parametrize("name", READABLE)
+def test_read_tiff_is_the_reference(name, expected):
+    """The first of these (compression 8) raised "compressed or multi-sample pages are not read here" before the reader inflated."""
+    from tissue_image_processing_amd import basic_image_manipulations as bim
+    image, axes, shape, _ = bim.read_tiff(_path(name))
+    want = expected[name + "__image"]
+    assert axes == str(expected[name + "__axes"])
+    assert tuple(shape) == tuple(expected[name + "__shape"]) == image.shape
+    assert image.dtype == want.dtype and image.dtype.isnative
+    assert np.array_equal(image, want)
+
+
+def test_page_table_reads_no_pixels():
+    from tissue_image_processing_amd import basic_image_manipulations as bim
+    for name, order, big, predictor, strips in (("zlib_rps7", "<", False, 1, 6), ("zlib_rps7_bigtiff", "<", True, 1, 6),
+                                                 ("zlib_predictor_bigendian", ">", False, 2, 6), ("zlib_one_strip", "<", False, 1, 1)):
+        table = bim.tiff_page_table(_path(name))
+        assert (table.byte_order, table.big, len(table.pages)) == (order, big, 12)
+        for pg in table.pages:
+            assert (pg.cols, pg.rows, pg.bits, pg.sample_format, pg.samples) == (48, 40, 16, 1, 1)
+            assert (pg.compression, pg.predictor, pg.strips) == (8, predictor, strips)
+            assert len(pg.offsets) == len(pg.counts) == strips
+            assert [pg.strip_rows(k) for k in range(strips)] == ([7, 7, 7, 7, 7, 5] if strips == 6 else [40])
+    assert bim.tiff_page_table(_path("lzw")).pages[0].compression == 5
+
+
+@pytest.mark.parametrize("name", READABLE)
+def test_lazy_source_dims_and_ragged_block(name, expected):
+    from tissue_image_processing_amd import basic_image_manipulations as bim
+    axes = str(expected[name + "__axes"])
+    tczyx = bim._as_tczyx(expected[name + "__image"], axes)
+    src = bim.open_image(_path(name))
+    assert tuple(src.dims) == tczyx.shape == (2, 2, 3, 40, 48)
+    box = (slice(1, 2), slice(0, 2), slice(1, 3), slice(5, 38), slice(7, 48))
+    got = src.block(*box)
+    assert got.dtype == tczyx.dtype and np.array_equal(got, tczyx[box])
+    assert sorted(src._decoded) == sorted(src.page_index(1, c, z) for c in range(2) for z in (1, 2))      # only those pages were decoded
+
+
+def test_chunks_of_the_compressed_file_are_its_twin_s():
+    from tissue_image_processing_amd import basic_image_manipulations as bim
+    kw = dict(dx=20, dy=16, dz=2, dt=1)
+    a = list(bim.read_image_in_chunks(_path("zlib_rps7"), **kw))
+    b = list(bim.read_image_in_chunks(_path("plain_rps7"), **kw))
+    assert len(a) == len(b) == 2 * 2 * 3 * 3
+    for x, y in zip(a, b):
+        assert x.shape == y.shape and x.dtype == y.dtype and np.array_equal(x, y)
+    assert tuple(bim.get_image_dimensions(_path("zlib_imagej"))) == (2, 2, 3, 40, 48)
+
+
+def test_what_keeps_raising(tmp_path):
+    from tissue_image_processing_amd import basic_image_manipulations as bim
+    with pytest.raises(ValueError, match=r"compression 5\b"):
+        bim.read_tiff(_path("lzw"))
+    with pytest.raises(ValueError, match=r"compression 5\b"):
+        bim.open_image(_path("lzw"))
+    blob = open(_path("zlib_rps7"), "rb").read()
+
+    def patched(tag, value, name):
+        """the fixture with `tag`'s SHORT value replaced in every IFD"""
+        assert struct.pack("<HHI", tag, 3, 1) in blob
+        out, at = bytearray(blob), struct.unpack("<I", blob[4:8])[0]
+        while at:
+            n, = struct.unpack("<H", out[at:at + 2])
+            for k in range(n):
+                e = at + 2 + 12 * k
+                if struct.unpack("<H", out[e:e + 2])[0] == tag:
+                    out[e + 8:e + 12] = struct.pack("<HH", value, 0)
+            at, = struct.unpack("<I", out[at + 2 + 12 * n:at + 6 + 12 * n])
+        p = str(tmp_path / name)
+        open(p, "wb").write(bytes(out))
+        return p
+
+    for tag, value, pattern in ((259, 32773, r"compression 32773\b"), (259, 7, r"compression 7\b"), (277, 3, r"SamplesPerPixel 3\b")):
+        with pytest.raises(ValueError, match=pattern):
+            bim.read_tiff(patched(tag, value, "t%d_%d.tif" % (tag, value)))
+    # predictor 3 and tiles: tags the fixture with the predictor carries / can carry in place of another
+    pred = open(_path("zlib_predictor_bigendian"), "rb").read()
+    out, at = bytearray(pred), struct.unpack(">I", pred[4:8])[0]
+    n, = struct.unpack(">H", out[at:at + 2])
+    for k in range(n):
+        e = at + 2 + 12 * k
+        if struct.unpack(">H", out[e:e + 2])[0] == 317:
+            out[e + 8:e + 12] = struct.pack(">HH", 3, 0)
+    open(str(tmp_path / "p3.tif"), "wb").write(bytes(out))
+    with pytest.raises(ValueError, match=r"predictor 3\b"):
+        bim.read_tiff(str(tmp_path / "p3.tif"))
+    out = bytearray(pred)
+    for k in range(n):
+        e = at + 2 + 12 * k
+        if struct.unpack(">H", out[e:e + 2])[0] == 317:
+            out[e:e + 2] = struct.pack(">H", 322)            # Predictor's entry becomes TileWidth (tags stay sorted: 317 < 322 < 339)
+    open(str(tmp_path / "tiled.tif"), "wb").write(bytes(out))
+    with pytest.raises(ValueError, match=r"tiled"):
+        bim.read_tiff(str(tmp_path / "tiled.tif"))
+    # a strip that does not inflate names its page and strip
+    table = bim.tiff_page_table(_path("zlib_rps7"))
+    bad = bytearray(blob)
+    bad[table.pages[3].offsets[2] + 9] ^= 0x55
+    open(str(tmp_path / "bad.tif"), "wb").write(bytes(bad))
+    with pytest.raises(ValueError, match=r"page 3 strip 2\b"):
+        bim.read_tiff(str(tmp_path / "bad.tif"))
+
+
+@pytest.mark.parametrize("predictor", [1, 2])
+@pytest.mark.parametrize("rowsperstrip", [None, 7, 64])
+def test_save_tiff_zlib_round_trip(tmp_path, predictor, rowsperstrip):
+    from tissue_image_processing_amd import basic_image_manipulations as bim
+    rng = np.random.default_rng(5)
+    for dtype, axes, shape in ((np.uint16, "TCZYX", (2, 2, 3, 45, 70)), (np.uint8, "ZYX", (3, 45, 71))):
+        a = (rng.random(shape) * 250).astype(dtype)
+        a[..., 10:20, :] = 65535 if dtype == np.uint16 else 255          # differences wrap modulo 2^bits at the edges of the band
+        p = str(tmp_path / "z.tif")
+        bim.save_tiff(p, a, axes=axes, compression="zlib", predictor=predictor, rowsperstrip=rowsperstrip)
+        image, ax, sh, _ = bim.read_tiff(p)
+        assert ax == axes and sh == shape and image.dtype == dtype and np.array_equal(image, a)
+        pg = bim.tiff_page_table(p).pages[0]
+        assert (pg.compression, pg.predictor) == (8, predictor)
+        assert pg.rows_per_strip == (45 if rowsperstrip in (None, 64) else 7)           # 64 KB of raw rows hold the 45; 7 leaves 3 ragged
+        assert pg.strips == (1 if rowsperstrip in (None, 64) else 7)
+    tall = (rng.random((300, 200)) * 60000).astype(np.uint16)
+    bim.save_tiff(str(tmp_path / "tall.tif"), tall, axes="YX", compression="zlib")
+    assert bim.tiff_page_table(str(tmp_path / "tall.tif")).pages[0].rows_per_strip == 163      # 65536 // (200 * 2)
+    assert np.array_equal(bim.read_tiff(str(tmp_path / "tall.tif"))[0], tall)
+    with pytest.raises(ValueError):
+        bim.save_tiff(str(tmp_path / "x.tif"), tall, compression="lzw")
+    with pytest.raises(ValueError):
+        bim.save_tiff(str(tmp_path / "x.tif"), tall, predictor=2)
+    with pytest.raises(TypeError):
+        bim.save_tiff(str(tmp_path / "x.tif"), tall.astype(np.float32), compression="zlib")
+
+
+def _baseline_layout(image, axes):
+    """The uncompressed file save_tiff has always written, from its documented layout: an 8-byte little-endian header; per
+    (Y, X) plane an IFD of the sorted entries 256, 257, 258, 259, 262, (270 on the first page,) 273, 277, 278, 279, 339 as
+    (tag, type, count, value), the next IFD's offset, the first page's description "axes=... shape=..." (NUL-terminated, padded
+    to a word), the plane's little-endian samples as one strip, and a pad byte after an odd-sized plane."""
+    planes = image.reshape((-1,) + image.shape[-2:]).astype(image.dtype.newbyteorder("<"))
+    rows, cols = planes.shape[1:]
+    item = planes.dtype.itemsize
+    fmt = {"u": 1, "i": 2, "f": 3}[planes.dtype.kind]
+    desc = ("axes=%s shape=%s" % (axes, "x".join(str(v) for v in image.shape))).encode() + b"\0"
+    desc += b"\0" * (len(desc) & 1)
+    out, at = struct.pack("<2sHI", b"II", 42, 8), 8
+    for k in range(len(planes)):
+        extra = desc if k == 0 else b""
+        n = 11 if extra else 10
+        data_at = at + 2 + 12 * n + 4 + len(extra)
+        size = rows * cols * item
+        ent = [(256, 4, 1, cols), (257, 4, 1, rows), (258, 3, 1, item * 8), (259, 3, 1, 1), (262, 3, 1, 1)]
+        ent += [(270, 2, len(extra), at + 2 + 12 * n + 4)] if extra else []
+        ent += [(273, 4, 1, data_at), (277, 3, 1, 1), (278, 4, 1, rows), (279, 4, 1, size), (339, 3, 1, fmt)]
+        nxt = data_at + size + (size & 1) if k + 1 < len(planes) else 0
+        out += struct.pack("<H", n) + b"".join(struct.pack("<HHII", *e) for e in ent) + struct.pack("<I", nxt)
+        out += extra + planes[k].tobytes() + b"\0" * (size & 1)
+        at = nxt
+    return out
+
+
+def test_save_tiff_default_bytes_are_unchanged(tmp_path):
+    from tissue_image_processing_amd import basic_image_manipulations as bim
+    rng = np.random.default_rng(6)
+    for dtype, axes, shape in ((np.uint16, "TCZYX", (2, 2, 3, 9, 11)), (np.uint8, "ZYX", (3, 5, 7)), (np.float32, "YX", (4, 6))):
+        a = (rng.random(shape) * 200).astype(dtype)
+        p = str(tmp_path / "plain.tif")
+        bim.save_tiff(p, a, axes=axes)
+        assert open(p, "rb").read() == _baseline_layout(a, axes)
+
+
+@pytest.mark.parametrize("name", ["zlib_rps7", "zlib_rps7_bigtiff", "zlib_predictor_bigendian", "zlib_one_strip", "zlib_imagej"])
+def test_frame_source_tables_on_the_cpu(name, expected):
+    """movie.tiff_frame_source without a device: decode="host" gives the frames; decode="device" gives the compressed strips and
+    a table whose destinations are the strips' places in the (C, Z, Y, X) stack whatever the page order -- inflated here by the
+    host form of the device's decoder, then byte order and predictor undone in numpy."""
+    from tissue_image_processing_amd import _inflate, movie
+    from tissue_image_processing_amd import basic_image_manipulations as bim
+    want = bim._as_tczyx(expected[name + "__image"], str(expected[name + "__axes"]))
+    host = movie.tiff_frame_source(_path(name), decode="host")
+    dev = movie.tiff_frame_source(_path(name), decode="device")
+    assert tuple(host.dims) == tuple(dev.dims) == want.shape and host.n_frames == 2
+    for t in range(2):
+        assert np.array_equal(host(t), want[t])
+        f = dev(t)
+        raw = f.buffer.numpy() if hasattr(f.buffer, "numpy") else f.buffer
+        dst = np.zeros(want[t].nbytes, np.uint8)
+        status, n_bad = _inflate.inflate_strips_host(raw[:f.src_bytes], f.strips(), 1, dst)
+        assert n_bad == 0 and f.n_strips == len(status) == (6 if name == "zlib_one_strip" else 36)
+        a = dst.view(np.uint16)
+        a = (a.byteswap() if f.swap_bytes else a).reshape(-1, want.shape[-1])
+        a = np.cumsum(a, axis=1, dtype=np.uint16) if f.predictor == 2 else a
+        assert np.array_equal(a.reshape(want[t].shape), want[t])
+        f.release()
+    assert (f.predictor, f.swap_bytes) == ((2, True) if name == "zlib_predictor_bigendian" else (1, False))
+    assert movie.tiff_frame_source(_path(name)).decode == "host"          # 36 strips a frame: below AUTO_DEVICE_MIN_STRIPS
+    with pytest.raises(ValueError):
+        movie.tiff_frame_source(_path("zlib_u8"), decode="device")
+    with pytest.raises(ValueError):
+        movie.tiff_frame_source(_path(name), decode="gpu")

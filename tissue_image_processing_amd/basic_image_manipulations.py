@@ -291,13 +291,23 @@ def tiff_normalise(image, data_type=""):
     return image
 
 
-def save_tiff(path, image, metadata=None, axes="", data_type=""):
+def save_tiff(path, image, metadata=None, axes="", data_type="", compression=None, predictor=1, rowsperstrip=None):
     """bim.py:160-188.  Upstream hands the array to aicsimageio's OME-TIFF writer; here a self-contained baseline TIFF
     writer stores every (Y, X) plane of the normalised array as one page (little-endian, uncompressed, min-is-black) with
     the axes string and shape in the first page's ImageDescription -- what ImageJ / tifffile / the reference's read_tiff
     open as a stack.  `metadata` with a to_xml() method (or a string) is appended to that description; other objects are
-    reported once as not written."""
+    reported once as not written.
+
+    compression="zlib" (opt-in; uint8 / uint16 only) writes every page as deflate strips instead (Compression 8, host zlib, one
+    stream per strip of `rowsperstrip` rows -- by default about 64 KB of raw data) with predictor 1 or 2 (horizontal
+    differencing).  Without these arguments the file is byte for byte what it always was."""
     import struct
+    if compression not in (None, "zlib"):
+        raise ValueError("save_tiff: compression %r (None or 'zlib')" % (compression,))
+    if compression is None and (predictor != 1 or rowsperstrip is not None):
+        raise ValueError("save_tiff: predictor and rowsperstrip belong to compression='zlib'")
+    if predictor not in (1, 2):
+        raise ValueError("save_tiff: predictor %r (1: none, 2: horizontal differencing)" % (predictor,))
     image = tiff_normalise(image, data_type)
     if image.dtype == np.float64:
         image = image.astype(np.float32)
@@ -319,6 +329,8 @@ def save_tiff(path, image, metadata=None, axes="", data_type=""):
         else:
             desc = desc[:-1] + b"\n" + (xml if isinstance(xml, bytes) else xml.encode("utf-8", "replace")) + b"\0"
     desc += b"\0" * (len(desc) & 1)                       # TIFF 6.0: every IFD starts on a word boundary
+    if compression == "zlib":
+        return _save_tiff_zlib(path, planes, desc, predictor, rowsperstrip)
     plane_bytes = rows * cols * planes.dtype.itemsize
     pad = plane_bytes & 1                                   # (odd-sized uint8 planes)
     if planes.nbytes + planes.shape[0] * 256 + len(desc) >= 2 ** 32:
@@ -348,12 +360,83 @@ def save_tiff(path, image, metadata=None, axes="", data_type=""):
     return
 
 
+def _save_tiff_zlib(path, planes, desc, predictor, rowsperstrip):
+    """save_tiff's deflate form: per page the strip offsets and byte counts follow the IFD, then the strips (zlib streams)."""
+    import os
+    import struct
+    import zlib
+    if planes.dtype not in (np.uint8, np.uint16):
+        raise TypeError("save_tiff: compression='zlib' writes uint8 / uint16 pages (got %s)" % planes.dtype)
+    n_pages, rows, cols = planes.shape
+    item = planes.dtype.itemsize
+    if rowsperstrip is None:
+        rowsperstrip = max(1, min(rows, 65536 // max(1, cols * item)))
+    rowsperstrip = int(rowsperstrip)
+    if rowsperstrip < 1:
+        raise ValueError("save_tiff: rowsperstrip %d" % rowsperstrip)
+    rowsperstrip = min(rowsperstrip, rows)
+    n_strips = -(-rows // rowsperstrip)
+    from concurrent.futures import ThreadPoolExecutor
+    threads = max(1, min(16, os.cpu_count() or 1))
+
+    def page_strips(k):
+        plane = planes[k]
+        if predictor == 2:
+            plane = np.concatenate([plane[:, :1], np.diff(plane, axis=1)], axis=1).astype(planes.dtype)      # modulo 2^bits
+        return [plane[r:r + rowsperstrip] for r in range(0, rows, rowsperstrip)]
+
+    # (zlib releases the interpreter lock: the strips of a few pages are compressed side by side; the file does not depend on it)
+    with open(path, "wb") as fh, ThreadPoolExecutor(threads) as pool:
+        fh.write(struct.pack("<2sHI", b"II", 42, 8))
+        offset = 8
+        done = {}
+        for k in range(n_pages):
+            if k not in done:
+                ahead = range(k, min(n_pages, k + max(1, threads // n_strips)))
+                raw = [part for j in ahead for part in page_strips(j)]
+                out = list(pool.map(lambda part: zlib.compress(part.tobytes(), 6), raw))
+                done = {j: out[i * n_strips:(i + 1) * n_strips] for i, j in enumerate(ahead)}
+            strips = done[k]
+            sizes = [len(s) for s in strips]
+            strips = [s + b"\0" * (len(s) & 1) for s in strips]           # (every strip starts on a word boundary)
+            extra = desc if k == 0 else b""
+            entries = [(256, 4, 1, cols), (257, 4, 1, rows), (258, 3, 1, item * 8), (259, 3, 1, 8), (262, 3, 1, 1), (277, 3, 1, 1),
+                       (278, 4, 1, rowsperstrip), (339, 3, 1, 1)]
+            if predictor == 2:
+                entries.append((317, 3, 1, 2))
+            ifd_size = 2 + 12 * (len(entries) + 2 + (1 if extra else 0)) + 4
+            tables_at = offset + ifd_size                                   # offsets, then byte counts: LONGs (inline when one strip)
+            table_bytes = 8 * n_strips if n_strips > 1 else 0
+            extra_at = tables_at + table_bytes
+            data_at = extra_at + len(extra)
+            starts = [data_at + sum(len(s) for s in strips[:i]) for i in range(n_strips)]
+            end = data_at + sum(len(s) for s in strips)
+            if end >= 2 ** 32:
+                raise ValueError("save_tiff: classic TIFF holds less than 4 GiB; split the movie")
+            entries.append((273, 4, n_strips, tables_at if n_strips > 1 else starts[0]))
+            entries.append((279, 4, n_strips, tables_at + 4 * n_strips if n_strips > 1 else sizes[0]))
+            if extra:
+                entries.append((270, 2, len(extra), extra_at))
+            entries.sort()
+            nxt = end if k + 1 < n_pages else 0
+            fh.write(struct.pack("<H", len(entries)))
+            for tag, typ, cnt, val in entries:
+                fh.write(struct.pack("<HHII", tag, typ, cnt, val))
+            fh.write(struct.pack("<I", nxt))
+            if n_strips > 1:
+                fh.write(struct.pack("<%dI" % n_strips, *starts) + struct.pack("<%dI" % n_strips, *sizes))
+            fh.write(extra)
+            fh.write(b"".join(strips))
+            offset = nxt
+    return
+
+
 # ---- image sources and the chunk iterator (bim.py:28-159, 478-495) -------------------------------------------------------
 # The reference opens everything through aicsimageio (absent in this image).  Here an image source is anything that can
 # say its (T, C, Z, Y, X) extents and hand out 5-D sub-blocks:
 #   * a numpy array / memmap of rank 5 (TCZYX), or a list / tuple of them (one per scene = microscope position);
-#   * a path to a .npy file (memory-mapped) or to an uncompressed TIFF stack (the reader below; axes from save_tiff's
-#     or ImageJ's ImageDescription);
+#   * a path to a .npy file (memory-mapped) or to a TIFF stack of uncompressed or deflate strips (the reader below, lazy:
+#     only the pages a block needs are decoded; axes from save_tiff's, tifffile's or ImageJ's ImageDescription);
 #   * an object with aicsimageio's interface (set_scene, dims, get_image_dask_data) -- a real AICSImage where that
 #     package is installed; any other path is handed to aicsimageio and fails loudly without it.
 class ImageDims(tuple):
@@ -446,8 +529,7 @@ def open_image(source, series=0):
             arr = np.load(path, mmap_mode="r")
             src = _ArraySource([_as_tczyx(arr, "TCZYX"[5 - arr.ndim:])])
         elif ext in (".tif", ".tiff"):
-            image, axes, _, _ = read_tiff(path)
-            src = _ArraySource([_as_tczyx(image, axes if axes else "TCZYX"[5 - image.ndim:])])
+            src = _TiffSource(path)
         else:
             try:
                 from aicsimageio import AICSImage
@@ -504,9 +586,21 @@ def read_image_in_chunks(path, series=0, dx=0, dy=0, dz=0, dc=0, dt=0, apply_fun
 
 
 def _tiff_axes_from_description(desc, npages, rows, cols):
-    """(axes, shape) from the first page's ImageDescription: save_tiff's "axes=... shape=...", ImageJ's hyperstack
-    keys, else a plain page stack."""
+    """(axes, shape) from the first page's ImageDescription: save_tiff's "axes=... shape=...", tifffile's own JSON
+    {"shape": [...], "axes": "..."}, ImageJ's hyperstack keys, else a plain page stack."""
     import re
+    if desc.startswith("{"):
+        import json
+        try:
+            meta = json.loads(desc)
+        except ValueError:
+            meta = None
+        if isinstance(meta, dict) and isinstance(meta.get("shape"), list) and all(isinstance(v, int) for v in meta["shape"]):
+            shape, axes = tuple(meta["shape"]), meta.get("axes")
+            if int(np.prod(shape)) == npages * rows * cols and shape[-2:] == (rows, cols):
+                if not (isinstance(axes, str) and len(axes) == len(shape)):
+                    axes = "Q" * (len(shape) - 2) + "YX"      # (tifffile's name for axes it was not told)
+                return axes.upper(), shape
     m = re.search(r"axes=([A-Za-z]*) shape=([0-9x]+)", desc)
     if m and m.group(2):
         shape = tuple(int(v) for v in m.group(2).split("x"))
@@ -527,13 +621,44 @@ def _tiff_axes_from_description(desc, npages, rows, cols):
     return "YX", (rows, cols)
 
 
-def read_tiff(path):
-    """bim.py:28-51: (image, axes, shape, metadata) of a TIFF file.  Self-contained reader for what this package and
-    ImageJ write -- classic TIFF and BigTIFF, either byte order, uncompressed strips, one sample per pixel, 8 / 16 / 32-bit
-    unsigned, signed or float pages of one size; anything else raises."""
+TIFF_DEFLATE = (8, 32946)          # Compression: Adobe deflate and the legacy code; both are zlib streams (RFC 1950), one per strip
+
+
+class TiffPage(object):
+    """One IFD of a strip-organised TIFF, as tiff_page_table reads it: no pixel data."""
+    __slots__ = ("index", "cols", "rows", "bits", "sample_format", "samples", "compression", "predictor", "rows_per_strip",
+                 "offsets", "counts", "tiled", "description")
+
+    @property
+    def strips(self):
+        return -(-self.rows // self.rows_per_strip)
+
+    def strip_rows(self, k):
+        return min(self.rows_per_strip, self.rows - k * self.rows_per_strip)
+
+
+class TiffTable(object):
+    """tiff_page_table's result: the pages, the file's byte order ("<" or ">"), classic or BigTIFF, and the memory map the
+    offsets point into."""
+
+    def __init__(self, path, buf, byte_order, big, pages):
+        self.path, self.buf, self.byte_order, self.big, self.pages = path, buf, byte_order, big, pages
+
+    @property
+    def description(self):
+        return self.pages[0].description if self.pages else ""
+
+
+def tiff_page_table(path):
+    """The IFDs of a TIFF / BigTIFF file through a memory map -- extents, bits, sample format, compression, predictor, rows per
+    strip, strip offsets and byte counts per page; the file's byte order and flavour -- without touching pixel data."""
+    import mmap
     import struct
     with open(path, "rb") as fh:
-        buf = fh.read()
+        try:
+            buf = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
+        except ValueError:
+            buf = b""                         # (an empty file cannot be mapped)
     if len(buf) < 8 or buf[:2] not in (b"II", b"MM"):
         raise ValueError("%s is not a TIFF file" % path)
     bo = "<" if buf[:2] == b"II" else ">"
@@ -547,7 +672,7 @@ def read_tiff(path):
     sizes = {1: 1, 2: 1, 3: 2, 4: 4, 6: 1, 8: 2, 9: 4, 16: 8, 17: 8}
     codes = {1: "B", 3: "H", 4: "I", 6: "b", 8: "h", 9: "i", 16: "Q", 17: "q"}
     cnt_fmt, ent_size, inline, off_fmt = ("Q", 20, 8, "Q") if big else ("H", 12, 4, "I")
-    pages, desc = [], ""
+    pages = []
     while ifd:
         hdr = struct.calcsize(cnt_fmt)
         n, = struct.unpack(bo + cnt_fmt, buf[ifd:ifd + hdr])
@@ -560,28 +685,156 @@ def read_tiff(path):
             if typ not in sizes:
                 continue
             nbytes = sizes[typ] * cnt
-            data = raw[:nbytes] if nbytes <= inline else buf[struct.unpack(bo + off_fmt, raw)[0]:][:nbytes]
-            tags[tag] = data if typ == 2 else struct.unpack(bo + "%d%s" % (cnt, codes[typ]), data)
+            at = struct.unpack(bo + off_fmt, raw)[0] if nbytes > inline else 0
+            data = raw[:nbytes] if nbytes <= inline else buf[at:at + nbytes]
+            tags[tag] = bytes(data) if typ == 2 else struct.unpack(bo + "%d%s" % (cnt, codes[typ]), data)
         ifd, = struct.unpack(bo + off_fmt, buf[ifd + hdr + ent_size * n: ifd + hdr + ent_size * n + inline])
-        if tags.get(259, (1,))[0] != 1 or tags.get(277, (1,))[0] != 1:
-            raise ValueError("%s: compressed or multi-sample pages are not read here" % path)
-        cols, rows, bits = tags[256][0], tags[257][0], tags.get(258, (1,))[0]
-        kind = {1: "u", 2: "i", 3: "f"}[tags.get(339, (1,))[0]]
-        dtype = np.dtype("%s%s%d" % (bo, kind, bits // 8))
-        offs, counts = tags[273], tags.get(279, (rows * cols * dtype.itemsize,))
-        raw = b"".join(buf[o:o + c] for o, c in zip(offs, counts))
-        pages.append(np.frombuffer(raw, dtype=dtype, count=rows * cols).reshape(rows, cols))
-        if not desc and 270 in tags:
-            desc = tags[270].split(b"\0")[0].decode("latin-1")
-    if not pages:
+        pg = TiffPage()
+        pg.index = len(pages)
+        pg.cols, pg.rows, pg.bits = tags[256][0], tags[257][0], tags.get(258, (1,))[0]
+        pg.sample_format, pg.samples = tags.get(339, (1,))[0], tags.get(277, (1,))[0]
+        pg.compression, pg.predictor = tags.get(259, (1,))[0], tags.get(317, (1,))[0]
+        pg.tiled = 322 in tags or 324 in tags
+        pg.rows_per_strip = max(1, min(tags.get(278, (pg.rows,))[0], pg.rows))
+        pg.offsets = tags.get(273, ())
+        pg.counts = tags.get(279, (pg.rows * pg.cols * (pg.bits // 8),) if len(pg.offsets) == 1 else ())
+        pg.description = tags[270].split(b"\0")[0].decode("latin-1") if 270 in tags else ""
+        pages.append(pg)
+    return TiffTable(path, buf, bo, big, pages)
+
+
+def _tiff_check_page(path, pg):
+    """What is read here: strips of one sample per pixel, uncompressed (any 8 / 16 / 32 / 64-bit type) or deflate (8- and 16-bit
+    unsigned), predictor 1, or 2 on 8- and 16-bit unsigned.  Anything else raises with the tag value met."""
+    where = "%s: page %d" % (path, pg.index)
+    if pg.tiled:
+        raise ValueError("%s is tiled (TileWidth / TileLength present); only strips are read here" % where)
+    if pg.samples != 1:
+        raise ValueError("%s: SamplesPerPixel %d; multi-sample pages are not read here" % (where, pg.samples))
+    if pg.compression != 1 and pg.compression not in TIFF_DEFLATE:
+        names = {5: "LZW", 6: "old JPEG", 7: "JPEG", 32773: "PackBits", 50000: "zstd", 34925: "LZMA"}
+        raise ValueError("%s: compression %d%s; only uncompressed (1) and deflate (8, 32946) strips are read here"
+                         % (where, pg.compression, " (%s)" % names[pg.compression] if pg.compression in names else ""))
+    if pg.predictor not in (1, 2):
+        raise ValueError("%s: predictor %d%s; only 1 (none) and 2 (horizontal differencing) are read here"
+                         % (where, pg.predictor, " (floating point)" if pg.predictor == 3 else ""))
+    plain = pg.compression == 1 and pg.predictor == 1
+    if not plain and not (pg.sample_format == 1 and pg.bits in (8, 16)):
+        raise ValueError("%s: compressed or differenced pages are read as 8- or 16-bit unsigned only (BitsPerSample %d, SampleFormat %d)"
+                         % (where, pg.bits, pg.sample_format))
+    if pg.sample_format not in (1, 2, 3) or pg.bits not in (8, 16, 32, 64):
+        raise ValueError("%s: BitsPerSample %d, SampleFormat %d are not read here" % (where, pg.bits, pg.sample_format))
+    if not plain and (len(pg.offsets) != pg.strips or len(pg.counts) != pg.strips):
+        raise ValueError("%s: %d strip offsets and %d byte counts for %d strips" % (where, len(pg.offsets), len(pg.counts), pg.strips))
+
+
+def _tiff_page_dtype(table, pg):
+    return np.dtype("%s%s%d" % (table.byte_order, {1: "u", 2: "i", 3: "f"}[pg.sample_format], pg.bits // 8))
+
+
+def _tiff_decode_page(table, pg):
+    """Page pg as a (rows, cols) array in the FILE's byte order: strips joined (uncompressed) or inflated by zlib one by one, then
+    the horizontal predictor undone on native-order samples (libtiff's order: byte swap, then accumulate)."""
+    import zlib
+    dtype, buf = _tiff_page_dtype(table, pg), table.buf
+    if pg.compression == 1:
+        raw = b"".join(buf[o:o + c] for o, c in zip(pg.offsets, pg.counts))
+    else:
+        parts = []
+        for k, (o, c) in enumerate(zip(pg.offsets, pg.counts)):
+            want = pg.strip_rows(k) * pg.cols * dtype.itemsize
+            try:
+                part = zlib.decompress(buf[o:o + c])
+            except zlib.error as e:
+                raise ValueError("%s: page %d strip %d does not inflate: %s" % (table.path, pg.index, k, e))
+            if len(part) != want:
+                raise ValueError("%s: page %d strip %d inflates to %d bytes, not %d" % (table.path, pg.index, k, len(part), want))
+            parts.append(part)
+        raw = b"".join(parts)
+    plane = np.frombuffer(raw, dtype=dtype, count=pg.rows * pg.cols).reshape(pg.rows, pg.cols)
+    if pg.predictor == 2:
+        native = dtype.newbyteorder("=")
+        plane = np.cumsum(plane.astype(native), axis=1, dtype=native).astype(dtype)
+    return plane
+
+
+def _tiff_checked_table(path):
+    table = tiff_page_table(path)
+    if not table.pages:
         raise ValueError("%s holds no image" % path)
-    if any(p.shape != pages[0].shape or p.dtype != pages[0].dtype for p in pages):
-        raise ValueError("%s: pages of different size or type" % path)
+    first = table.pages[0]
+    for pg in table.pages:
+        _tiff_check_page(path, pg)
+        if (pg.rows, pg.cols, pg.bits, pg.sample_format) != (first.rows, first.cols, first.bits, first.sample_format):
+            raise ValueError("%s: pages of different size or type" % path)
+    return table
+
+
+def read_tiff(path):
+    """bim.py:28-51: (image, axes, shape, metadata) of a TIFF file.  Self-contained reader for what this package, ImageJ and
+    tifffile's defaults write -- classic TIFF and BigTIFF, either byte order, strips of one sample per pixel: uncompressed 8 / 16 /
+    32-bit unsigned, signed or float pages, or deflate (compression 8 / 32946, inflated with the standard library's zlib) 8- and
+    16-bit unsigned pages, with predictor 1 or 2; pages of one size.  Anything else raises ValueError naming the tag value met."""
+    table = _tiff_checked_table(path)
+    pages = [_tiff_decode_page(table, pg) for pg in table.pages]
     rows, cols = pages[0].shape
+    desc = table.description
     axes, shape = _tiff_axes_from_description(desc, len(pages), rows, cols)
     image = np.stack(pages).astype(pages[0].dtype.newbyteorder("=")).reshape(shape)
     metadata = dict(line.split("=", 1) for line in desc.splitlines() if "=" in line) if desc.startswith("ImageJ=") else None
     return image, axes, image.shape, metadata
+
+
+class _TiffSource(object):
+    """A TIFF stack as a lazy image source: dims from the page table, block() decodes only the pages it is asked for.  The
+    description's axes say which page holds which (t, c, z) -- TCZ, ImageJ's TZC or any other order of the page axes."""
+
+    def __init__(self, path):
+        self.table = _tiff_checked_table(path)
+        first = self.table.pages[0]
+        axes, shape = _tiff_axes_from_description(self.table.description, len(self.table.pages), first.rows, first.cols)
+        axes = axes if axes else "TCZYX"[5 - len(shape):]
+        if (len(axes) != len(shape) or any(a not in "TCZYX" for a in axes) or len(set(axes)) != len(axes) or axes[-2:] != "YX"):
+            raise ValueError("axes %r do not describe an array of rank %d" % (axes, len(shape)))
+        self.axes, self.shape = axes, tuple(int(v) for v in shape)
+        self.page_axes, self.page_shape = axes[:-2], self.shape[:-2]
+        self.dtype = _tiff_page_dtype(self.table, first).newbyteorder("=")
+        self._decoded = {}            # the pages of the last block(): the chunk iterator asks for the same pages x by x, y by y
+
+    def set_scene(self, series):
+        if series != 0:
+            raise IndexError("scene %d of 1" % series)
+
+    @property
+    def dims(self):
+        ext = dict(zip(self.axes, self.shape))
+        return ImageDims(*[ext.get(a, 1) for a in "TCZYX"])
+
+    def page_index(self, t, c, z):
+        """the page that holds plane (t, c, z)"""
+        at = dict(T=t, C=c, Z=z)
+        k = 0
+        for a, n in zip(self.page_axes, self.page_shape):
+            k = k * n + at[a]
+        return k
+
+    def block(self, t, c, z, y, x):
+        d = self.dims
+        ts, cs, zs = (range(*s.indices(n)) if isinstance(s, slice) else [s] for s, n in zip((t, c, z), d[:3]))
+        last, self._decoded = self._decoded, {}
+
+        def plane(ti, ci, zi):
+            k = self.page_index(ti, ci, zi)
+            if k not in self._decoded:
+                self._decoded[k] = last[k] if k in last else _tiff_decode_page(self.table, self.table.pages[k])
+            return self._decoded[k]
+
+        planes = [[[plane(ti, ci, zi)[y, x] for zi in zs] for ci in cs] for ti in ts]
+        out = np.array(planes, dtype=self.dtype)
+        for axis, s in reversed(list(enumerate((t, c, z)))):
+            if not isinstance(s, slice):
+                out = out.squeeze(axis)           # an integer index drops its axis, as on an array
+        return out
 
 
 def concatenate_time_points(files):

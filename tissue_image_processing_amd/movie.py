@@ -47,6 +47,11 @@ differentiations (Tissue.find_events_iterator, ti.py:636-789) -- with the label-
 tip_lookup_i32_dev) and one device pass per frame pair over the table rows (tip_event_flags_i32); rank 0 gets the events table, which
 `save_seg(..., events=...)` writes into the archive (events.py).
 
+`tiff_frame_source(path, decode=...)` is a frame_source over a TIFF stack, deflate-compressed ones included: with
+decode="device" a frame arrives as its compressed strips (CompressedFrame) and the owner inflates them on its GPU into the stack
+the projection reads (FramePipeline.inflate_stack: tip_inflate_strips_dev, tip_tiff_finish_u16_dev) -- the upload moves the
+compressed bytes; a strip that does not inflate raises ValueError on the owner before the frame is projected.
+
 `backend` supplies the per-frame compute so the same driver runs on GPUs (GpuFrameBackend) and, for the
 multi-process CPU tests, on a stand-in backend with the gloo process group.
 """
@@ -56,6 +61,118 @@ import collections
 import numpy as np
 
 from ._collectives import gather_varlen, pack_records, unpack_records
+
+
+class CompressedFrame(object):
+    """One time point of a deflate-compressed TIFF as tiff_frame_source(decode="device") hands it to GpuFrameBackend: `buffer`, one
+    (pinned where a GPU is there) host array holding the frame's compressed strips one after another and, from `table_at` on, the
+    strip table -- four int64 per strip: src_off, src_len, dst_off, dst_len, the destinations being the strips' places in the
+    (C, Z, Y, X) uint16 stack, whatever the file's page order; `pages` / `strip_of_page`: which page and strip each row is (for
+    the error text); `shape`, `predictor` (1 or 2) and `swap_bytes` (the file's byte order is not the host's)."""
+
+    def __init__(self, path, t, buffer, src_bytes, table_at, n_strips, pages, strip_of_page, shape, predictor, swap_bytes, release=None):
+        self.path, self.t, self.buffer, self.src_bytes, self.table_at, self.n_strips = path, t, buffer, src_bytes, table_at, n_strips
+        self.pages, self.strip_of_page, self.shape, self.predictor, self.swap_bytes = pages, strip_of_page, shape, predictor, swap_bytes
+        self._release = release
+
+    @property
+    def nbytes(self):
+        return self.table_at + 32 * self.n_strips
+
+    def host_ptr(self):
+        return self.buffer.data_ptr() if hasattr(self.buffer, "data_ptr") else self.buffer.ctypes.data
+
+    def strips(self):
+        """the strip table as an (n, 4) int64 array (a view of the buffer)"""
+        raw = self.buffer.numpy() if hasattr(self.buffer, "numpy") else self.buffer
+        return raw[self.table_at:self.table_at + 32 * self.n_strips].view(np.int64).reshape(-1, 4)
+
+    def release(self):
+        """the buffer goes back to its source (after the upload)"""
+        if self._release is not None:
+            self._release(self.buffer)
+            self._release, self.buffer = None, None
+
+
+# decode="auto" inflates on the device when a frame has at least this many strips' worth of parallel work (frame bytes over the
+# largest strip's bytes; the strip count when strips are equal).  Measured on one MI355X at 2048^2 x 30 x 2 (profiles/
+# tiff_inflate_time.json): 7 680 strips of 64 KB -- device 0.065 s a frame against 0.39-0.59 s for zlib on 16 host threads; 60
+# strips of 8 MB (one per page) -- device 1.81 s against 0.40 s.  One wave decodes one strip, so the device's time falls as
+# 1 / strips and meets the host's at about 60 * 1.81 / 0.40 = 272 strips; the threshold is the next power of two.
+AUTO_DEVICE_MIN_STRIPS = 512
+
+
+def tiff_frame_source(path, series=0, decode="auto", backend="gpu"):
+    """A frame_source for process_movie over a TIFF stack: source(t) is time point t as a (C, Z, Y, X) uint16 array
+    (decode="host": the strips inflated by zlib on the calling thread) or as a CompressedFrame (decode="device": the compressed
+    strips and their table, which GpuFrameBackend uploads and inflates on its GPU, tip_inflate_strips_dev).  decode="auto" is
+    "device" when a GPU backend consumes the frames (backend="gpu"), the file is 16-bit deflate strips and a frame holds at
+    least AUTO_DEVICE_MIN_STRIPS strips' worth of parallel work, else "host"; 8-bit files are converted on the host.  The source carries `dims` (T, C, Z, Y, X), `decode` and `n_frames`."""
+    import threading
+    from . import basic_image_manipulations as bim
+    if decode not in ("auto", "host", "device"):
+        raise ValueError("decode must be 'auto', 'host' or 'device', not %r" % (decode,))
+    src = bim.open_image(path, series)
+    if not isinstance(src, bim._TiffSource):
+        raise ValueError("tiff_frame_source: %r is not a TIFF stack" % (path,))
+    T, C, Z, Y, X = src.dims
+    table = src.table
+    first = table.pages[0]
+    device_ok = first.bits == 16 and first.sample_format == 1 and all(pg.compression in bim.TIFF_DEFLATE for pg in table.pages)
+    if decode == "device" and not device_ok:
+        raise ValueError("tiff_frame_source: decode='device' needs 16-bit unsigned deflate strips (%s has BitsPerSample %d, compression %d)"
+                         % (path, first.bits, first.compression))
+    if decode == "auto":
+        largest = max(pg.strip_rows(0) for pg in table.pages) * X * 2
+        parallel = (C * Z * Y * X * 2) // max(1, largest)
+        decode = "device" if (device_ok and backend == "gpu" and parallel >= AUTO_DEVICE_MIN_STRIPS) else "host"
+    import sys
+    swap = (table.byte_order == "<") != (sys.byteorder == "little")
+    lock, spare = threading.Lock(), []
+
+    def take(nbytes):
+        with lock:
+            for k, b in enumerate(spare):
+                if b.shape[0] >= nbytes:
+                    return spare.pop(k)
+        try:
+            import torch
+            return torch.empty(nbytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        except ImportError:
+            return np.empty(nbytes, np.uint8)
+
+    def give_back(buf):
+        with lock:
+            if len(spare) < 8:
+                spare.append(buf)
+
+    def host_frame(t):
+        return np.ascontiguousarray(src.block(slice(t, t + 1), slice(0, C), slice(0, Z), slice(0, Y), slice(0, X))[0], dtype=np.uint16)
+
+    def device_frame(t):
+        rows, at = [], 0
+        for c in range(C):
+            for z in range(Z):
+                pg = table.pages[src.page_index(t, c, z)]
+                if pg.predictor != first.predictor:
+                    raise ValueError("%s: pages with different predictors" % path)
+                base = (c * Z + z) * Y * X * 2
+                for k, (o, n) in enumerate(zip(pg.offsets, pg.counts)):
+                    rows.append((at, n, base + k * pg.rows_per_strip * X * 2, pg.strip_rows(k) * X * 2, pg.index, k, o))
+                    at += n
+        table_at = (at + 7) & ~7
+        buf = take(table_at + 32 * len(rows))
+        raw = buf.numpy() if hasattr(buf, "numpy") else buf
+        for s_off, n, _, _, _, _, o in rows:
+            raw[s_off:s_off + n] = np.frombuffer(table.buf, np.uint8, n, o)
+        strips = np.array([r[:4] for r in rows], np.int64).reshape(-1, 4)
+        raw[table_at:table_at + strips.nbytes] = strips.view(np.uint8).ravel()
+        return CompressedFrame(path, t, buf, at, table_at, len(rows), np.array([r[4] for r in rows]), np.array([r[5] for r in rows]),
+                               (C, Z, Y, X), first.predictor, swap, release=give_back)
+
+    source = device_frame if decode == "device" else host_frame
+    source.dims, source.decode, source.n_frames = src.dims, decode, T
+    return source
 
 
 class _Job(object):
@@ -309,7 +426,9 @@ class GpuFrameBackend(object):
 
     def _process_with(self, p, t, stack_u16):
         from . import _lib
-        if hasattr(stack_u16, "data_ptr"):        # a (pinned) torch tensor: copied straight from its storage
+        if isinstance(stack_u16, CompressedFrame):      # a compressed TIFF time point: inflated on this pipeline's stream
+            d_stack = p.inflate_stack(stack_u16)
+        elif hasattr(stack_u16, "data_ptr"):        # a (pinned) torch tensor: copied straight from its storage
             nbytes = stack_u16.numel() * stack_u16.element_size()
             d_stack = _lib.DeviceBuffer(nbytes)
             _lib.check(p.lib.tip_memcpy_h2d(d_stack.ptr, stack_u16.data_ptr(), nbytes))

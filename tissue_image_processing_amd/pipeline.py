@@ -51,6 +51,32 @@ class FramePipeline:
         buf.upload(stack_u16)
         return buf
 
+    def inflate_stack(self, frame):
+        """A movie.CompressedFrame -> the resident (C, Z, Y, X) uint16 stack project() reads: one upload of the compressed strips and
+        their table, tip_inflate_strips_dev straight into the stack buffer, tip_tiff_finish_u16_dev (byte order, predictor) in
+        place -- all on this thread's stream.  A strip that does not inflate raises ValueError naming its page, strip and status
+        before anything is projected."""
+        from . import _inflate
+        assert tuple(frame.shape) == (self.C, self.Z, self.Y, self.X)
+        nbytes = self.C * self.Z * self.Y * self.X * 2
+        packed, status = _lib.DeviceBuffer(frame.nbytes), _lib.DeviceBuffer(4 * max(frame.n_strips, 1))
+        _lib.check(self.lib.tip_memcpy_h2d(packed.ptr, frame.host_ptr(), frame.nbytes))
+        pages, strip_of_page, path, t = frame.pages, frame.strip_of_page, frame.path, frame.t
+        stack = _lib.DeviceBuffer(nbytes)
+        n_bad = _inflate.inflate_strips_dev(packed.ptr, frame.src_bytes, packed.ptr + frame.table_at, frame.n_strips, 1, stack.ptr, nbytes,
+                                            status.ptr)
+        frame.release()
+        if n_bad:
+            st = status.download((frame.n_strips,), np.int32)
+            k = int(np.flatnonzero(st)[0])
+            stack.free()
+            raise ValueError("%s: frame %d, page %d strip %d does not inflate: status %d (%s); %d strip(s) of the frame failed"
+                             % (path, t, pages[k], strip_of_page[k], st[k], _inflate.STATUS_TEXT.get(int(st[k]), "?"), n_bad))
+        _inflate.tiff_finish_u16_dev(stack.ptr, self.C * self.Z * self.Y, self.X, frame.predictor, frame.swap_bytes)
+        packed.free()
+        status.free()
+        return stack
+
     def project(self, d_stack):
         """P0-P9 (sp.py:17-85) on a resident uint16 stack; asynchronous."""
         _lib.check(self.lib.tip_project_u16_dev(
