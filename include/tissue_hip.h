@@ -665,6 +665,23 @@ TIP_API int tip_deflate_dynamic_dev(const void *src_dev, int64_t nbytes, int ele
                                     int64_t *out_bytes_host, uint32_t *crc32_host);
 TIP_API int tip_deflate_dynamic(const void *src, int64_t nbytes, int elem_bytes, int64_t row_bytes, void *dst, int64_t cap,
                                 int64_t *out_bytes, uint32_t *crc32);
+/* STRIPS: n_pages planes of rows x row_bytes, each cut into strips of rows_per_strip rows (the last one of a page may be shorter), */
+/* every strip a zlib stream of its own (RFC 1950) -- what a TIFF with Compression 8 holds per strip: 78 01, the body, the final    */
+/* empty stored block 01 00 00 FF FF and the strip's Adler-32, most significant byte first.  The body is byte for byte what          */
+/* tip_deflate_rows (codes 0) or tip_deflate_dynamic with this row_bytes (codes 1) writes for THAT STRIP AS A WHOLE BUFFER, so no     */
+/* match reaches before the strip; tests/deflate_strips_restate.py is the framing.  The streams are compacted into dst in            */
+/* page-major order, every one at an even offset (one zero byte behind a stream of odd size); table: (offset, size) per strip as     */
+/* int64 pairs, size without the pad byte; *out_bytes: the bytes written, pad bytes included.  Sizes, table and total arrive in host */
+/* memory after ONE wait for the stream.  _bound: the most bytes written (per strip of n bytes 2 + the chunk bound of n + 9, made    */
+/* even); touches no device.  TIP_ERR_UNSUPPORTED: rows_per_strip * row_bytes > 65536 (a strip is one chunk).  TIP_ERR_ARG: a null   */
+/* pointer, elem_bytes not 1 or 2, row_bytes not a positive multiple of it, rows_per_strip < 1, another codes, a negative extent, cap */
+/* below the bound.  n_pages == 0 or rows == 0: TIP_OK, zero bytes, nothing is read.                                                  */
+TIP_API int tip_deflate_strips_bound(int64_t n_pages, int64_t rows, int64_t row_bytes, int64_t rows_per_strip, int64_t *bound_out);
+TIP_API int tip_deflate_strips_dev(const void *src_dev, int64_t n_pages, int64_t rows, int64_t row_bytes, int elem_bytes,
+                                   int64_t rows_per_strip, int codes, void *dst_dev, int64_t cap, int64_t *table_host,
+                                   int64_t *out_bytes_host);
+TIP_API int tip_deflate_strips(const void *src, int64_t n_pages, int64_t rows, int64_t row_bytes, int elem_bytes, int64_t rows_per_strip,
+                               int codes, void *dst, int64_t cap, int64_t *table, int64_t *out_bytes);
 
 /* ---- inflate of many deflate streams, and the 16-bit TIFF row pass (csrc/tip_inflate.hip, csrc/tip_inflate_core.h; the     */
 /* ---- strips of a deflate-compressed TIFF: movie.tiff_frame_source) --------------------------------------------------------- */
@@ -705,6 +722,15 @@ TIP_API int tip_inflate_strips_host(const void *src, int64_t src_bytes, const in
 /* modulo 2^16 (TIFF horizontal differencing undone; libtiff's order: swap, then accumulate).  Rows are independent.  predictor */
 /* 1: no sum; another predictor: TIP_ERR_UNSUPPORTED.                                                                            */
 TIP_API int tip_tiff_finish_u16_dev(void *stack_dev, int64_t n_rows, int64_t row_elems, int predictor, int swap_bytes);
+
+/* ---- a frame's maps as uint16 TIFF pages (csrc/tip_export.hip; movie.export_tiff) ------------------------------------------- */
+/* Plane 0 of out_dev (n_pix uint16): ids_host[labels - 1], 0 on label 0 -- Tissue.get_trackking_labels cast to uint16; plane 1,    */
+/* only when types_dev is given (out_dev then holds 2 n_pix): the type byte with 0 -> 2, 255 -> 0, others as they are              */
+/* (export_segmentation_and_cell_types_to_tiff's map).  labels_dev, types_dev, out_dev are DEVICE buffers; ids_host is n_ids int64   */
+/* on the host.  A label outside [0, n_ids] is written as 0 and counted in *n_bad_host (a host word, after one wait).  TIP_ERR_ARG:   */
+/* a null pointer, a negative count, or an id outside [0, 65535] -- checked before anything is launched.                             */
+TIP_API int tip_export_maps_u16_dev(const int32_t *labels_dev, const uint8_t *types_dev, int64_t n_pix, const int64_t *ids_host,
+                                    int64_t n_ids, uint16_t *out_dev, int32_t *n_bad_host);
 
 #ifdef __cplusplus
 }

@@ -109,6 +109,77 @@ def deflate_dynamic(data, elem_bytes, row_bytes=None):
     return _deflate_host(data, elem_bytes, row_bytes, dynamic=True)
 
 
+STRIP_CODES = {"fixed": 0, "dynamic": 1}      # tip_deflate_strips' `codes`
+
+
+def strip_codes(codes):
+    """"fixed" / "dynamic" (or 0 / 1) -> tip_deflate_strips' `codes`"""
+    if codes in STRIP_CODES:
+        return STRIP_CODES[codes]
+    if codes in (0, 1) and not isinstance(codes, bool):
+        return int(codes)
+    raise ValueError("codes must be 'fixed' or 'dynamic', not %r" % (codes,))
+
+
+def default_rows_per_strip(rows, row_bytes):
+    """The strip height the exports use: as many rows as 65536 bytes hold -- the most tip_deflate_strips takes --, at least 1."""
+    return max(1, min(int(rows), 65536 // max(1, int(row_bytes))))
+
+
+def strips_bound(n_pages, rows, row_bytes, rows_per_strip):
+    """tip_deflate_strips_bound: the most bytes the strip encoder writes for these pages (no device needed)."""
+    out = ctypes.c_int64(0)
+    _lib.check(_lib.load().tip_deflate_strips_bound(int(n_pages), int(rows), int(row_bytes), int(rows_per_strip), ctypes.byref(out)))
+    return int(out.value)
+
+
+def deflate_strips_dev(src_ptr, n_pages, rows, row_bytes, elem_bytes, rows_per_strip, codes, dst_ptr, cap):
+    """tip_deflate_strips_dev on device addresses: every strip of every page as a zlib stream of its own, compacted at dst_ptr ->
+    (table: int64 (strips, 2) of (offset, size) in page-major order, bytes written); waits once."""
+    n_strips = int(n_pages) * -(-int(rows) // max(1, int(rows_per_strip)))
+    table, total = np.zeros((max(n_strips, 1), 2), np.int64), ctypes.c_int64(0)
+    _lib.check(_lib.lib().tip_deflate_strips_dev(src_ptr, int(n_pages), int(rows), int(row_bytes), int(elem_bytes), int(rows_per_strip),
+                                                 strip_codes(codes), dst_ptr, int(cap), _lib.ptr(table), ctypes.byref(total)))
+    return table[:n_strips], int(total.value)
+
+
+def deflate_strips(pages, rows_per_strip, codes="dynamic"):
+    """tip_deflate_strips on a host array of uint8 or uint16 pages (..., rows, cols) -> per page the list of its strips' zlib streams."""
+    pages = np.ascontiguousarray(pages)
+    if pages.ndim < 2 or pages.dtype.itemsize not in (1, 2):
+        raise ValueError("deflate_strips takes 8- or 16-bit pages (..., rows, cols), not %s %s" % (pages.dtype, pages.shape))
+    rows, cols = pages.shape[-2:]
+    n_pages = int(np.prod(pages.shape[:-2], dtype=np.int64))
+    item = pages.dtype.itemsize
+    cap = strips_bound(n_pages, rows, cols * item, rows_per_strip)
+    n_strips = n_pages * -(-rows // int(rows_per_strip))
+    dst, table, total = np.empty(max(cap, 1), np.uint8), np.zeros((max(n_strips, 1), 2), np.int64), ctypes.c_int64(0)
+    keep = pages if pages.size else np.zeros(1, np.uint8)      # (an empty array has no address to hand over)
+    _lib.check(_lib.lib().tip_deflate_strips(_lib.ptr(keep), n_pages, rows, cols * item, item, int(rows_per_strip), strip_codes(codes),
+                                             _lib.ptr(dst), cap, _lib.ptr(table), ctypes.byref(total)))
+    return split_strips(dst[:total.value], table[:n_strips], n_pages)
+
+
+def split_strips(stream, table, n_pages):
+    """The compacted streams of deflate_strips_dev cut by its table -> per page the list of its strips' bytes."""
+    per_page = len(table) // n_pages if n_pages else 0
+    buf = memoryview(np.ascontiguousarray(stream, np.uint8)).cast("B")
+    return [[bytes(buf[int(o):int(o) + int(n)]) for o, n in table[k * per_page:(k + 1) * per_page]] for k in range(n_pages)]
+
+
+def export_maps_u16_dev(labels_ptr, types_ptr, n_pix, ids, out_ptr):
+    """tip_export_maps_u16_dev on device addresses: the uint16 page of tracking labels ids[labels - 1] (0 on label 0) at out_ptr and,
+    with types_ptr, the page of remapped types (0 -> 2, 255 -> 0) behind it.  ValueError for an id outside [0, 65535] and for a
+    label outside [0, len(ids)]."""
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    n_bad = ctypes.c_int32(0)
+    keep = ids if ids.size else np.zeros(1, np.int64)
+    _lib.check(_lib.lib().tip_export_maps_u16_dev(labels_ptr, types_ptr, int(n_pix), _lib.ptr(keep), ids.size, out_ptr, ctypes.byref(n_bad)))
+    if n_bad.value:
+        raise ValueError("%d pixels hold a label outside [0, %d]: the ids do not belong to this label map" % (n_bad.value, ids.size))
+    return out_ptr
+
+
 def npy_header(shape, dtype):
     """The bytes np.save writes in front of a C-contiguous array's data (format 1.0: magic, header length, dict, padding)."""
     import io

@@ -18,7 +18,7 @@ _lib = None
 _lock = threading.Lock()
 _tls = threading.local()
 
-TIP_ERR_ARG, TIP_ERR_INDEX, TIP_ERR_OVERFLOW = -2, -4, -6
+TIP_ERR_ARG, TIP_ERR_INDEX, TIP_ERR_UNSUPPORTED, TIP_ERR_OVERFLOW = -2, -4, -5, -6
 
 
 class TissueHipError(RuntimeError):

@@ -431,6 +431,90 @@ def _save_tiff_zlib(path, planes, desc, predictor, rowsperstrip):
     return
 
 
+def write_tiff_strips(path, shape, axes, dtype, rowsperstrip, pages, bigtiff=None):
+    """A deflate-strip TIFF from strips that are compressed ALREADY (movie.export_tiff: zlib streams made on the GPUs).  shape: the
+    whole array's, (..., Y, X), every leading index one page in C order; dtype uint8 or uint16; `pages` yields, per page, the list
+    of its finished strip streams (one per `rowsperstrip` rows, the last strip the rows that are left).  Pages are written as they
+    arrive; nothing but the current page is held.
+
+    The layout is save_tiff(compression="zlib")'s: little-endian, Compression 8, no Predictor tag, per page the strip offsets and
+    byte counts behind the IFD (inline for one strip), then the strips on word boundaries; "axes=... shape=..." in page 0's
+    ImageDescription.  bigtiff=True writes BigTIFF (magic 43, 8-byte offsets and counts); None chooses it when the classic form
+    would reach 4 GiB -- from the strips themselves when `pages` is a list, otherwise, the sizes not being known before the first
+    page is written, from the uncompressed size.  A classic file that reaches 4 GiB after all raises ValueError."""
+    import struct
+    dtype = np.dtype(dtype)
+    if dtype not in (np.uint8, np.uint16):
+        raise TypeError("write_tiff_strips writes uint8 / uint16 pages (got %s)" % dtype)
+    shape = tuple(int(v) for v in shape)
+    if len(shape) < 2 or min(shape) < 1:
+        raise ValueError("write_tiff_strips needs a shape (..., Y, X) of positive extents, not %r" % (shape,))
+    rows, cols = shape[-2:]
+    n_pages = int(np.prod(shape[:-2], dtype=np.int64))
+    rowsperstrip = int(rowsperstrip)
+    if rowsperstrip < 1:
+        raise ValueError("write_tiff_strips: rowsperstrip %d" % rowsperstrip)
+    rowsperstrip = min(rowsperstrip, rows)
+    n_strips = -(-rows // rowsperstrip)
+    desc = ("axes=%s shape=%s" % (axes, "x".join(str(v) for v in shape))).encode("ascii") + b"\0"
+    desc += b"\0" * (len(desc) & 1)
+    if bigtiff is None:
+        if isinstance(pages, (list, tuple)):
+            payload = sum(len(s) + (len(s) & 1) for page in pages for s in page)
+        else:
+            payload = n_pages * rows * cols * dtype.itemsize
+        bigtiff = payload + len(desc) + 16 + n_pages * (16 + 20 * 11 + 16 * n_strips) >= 2 ** 32      # (the larger form's tables)
+    big = bool(bigtiff)
+    # classic: 2-byte entry count, 12-byte entries, LONG (4) offsets; BigTIFF: 8-byte count, 20-byte entries, LONG8 (16) offsets
+    cnt_fmt, ent_fmt, off_fmt, off_type, word = ("<Q", "<HHQQ", "Q", 16, 8) if big else ("<H", "<HHII", "I", 4, 4)
+    written = 0
+    with open(path, "wb") as fh:
+        fh.write(struct.pack("<2sHHHQ", b"II", 43, 8, 0, 16) if big else struct.pack("<2sHI", b"II", 42, 8))
+        offset = 16 if big else 8
+        for k, strips in enumerate(pages):
+            if k >= n_pages:
+                raise ValueError("write_tiff_strips: more than the %d pages of shape %r" % (n_pages, shape))
+            strips = [bytes(s) for s in strips]
+            if len(strips) != n_strips:
+                raise ValueError("write_tiff_strips: page %d came with %d strips, not %d" % (k, len(strips), n_strips))
+            sizes = [len(s) for s in strips]
+            extra = desc if k == 0 else b""
+            entries = [(256, 4, 1, cols), (257, 4, 1, rows), (258, 3, 1, dtype.itemsize * 8), (259, 3, 1, 8), (262, 3, 1, 1), (277, 3, 1, 1),
+                       (278, 4, 1, rowsperstrip), (339, 3, 1, 1)]
+            ifd_size = struct.calcsize(cnt_fmt) + struct.calcsize(ent_fmt) * (len(entries) + 2 + (1 if extra else 0)) + word
+            tables_at = offset + ifd_size                                   # offsets, then byte counts (inline when one strip)
+            table_bytes = 2 * word * n_strips if n_strips > 1 else 0
+            extra_at = tables_at + table_bytes
+            data_at = extra_at + len(extra)
+            starts, at = [], data_at
+            for n in sizes:
+                starts.append(at)
+                at += n + (n & 1)                                           # (every strip starts on a word boundary)
+            end = at
+            if not big and end >= 2 ** 32:
+                raise ValueError("write_tiff_strips: classic TIFF holds less than 4 GiB; pass bigtiff=True")
+            entries.append((273, off_type, n_strips, tables_at if n_strips > 1 else starts[0]))
+            entries.append((279, off_type, n_strips, tables_at + word * n_strips if n_strips > 1 else sizes[0]))
+            if extra:
+                entries.append((270, 2, len(extra), extra_at))
+            entries.sort()
+            nxt = end if k + 1 < n_pages else 0
+            fh.write(struct.pack(cnt_fmt, len(entries)))
+            for entry in entries:
+                fh.write(struct.pack(ent_fmt, *entry))
+            fh.write(struct.pack("<" + off_fmt, nxt))
+            if n_strips > 1:
+                fh.write(struct.pack("<%d%s" % (n_strips, off_fmt), *starts) + struct.pack("<%d%s" % (n_strips, off_fmt), *sizes))
+            fh.write(extra)
+            for s in strips:
+                fh.write(s + b"\0" * (len(s) & 1))
+            offset = end
+            written += 1
+    if written != n_pages:
+        raise ValueError("write_tiff_strips: %d pages arrived for shape %r (%d pages)" % (written, shape, n_pages))
+    return path
+
+
 # ---- image sources and the chunk iterator (bim.py:28-159, 478-495) -------------------------------------------------------
 # The reference opens everything through aicsimageio (absent in this image).  Here an image source is anything that can
 # say its (T, C, Z, Y, X) extents and hand out 5-D sub-blocks:

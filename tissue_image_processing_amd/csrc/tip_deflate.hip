@@ -44,6 +44,8 @@
 // k_deflate_offsets: one workgroup scans the chunk sizes (exclusive, 64-bit) and leaves the total next to the CRC.
 // k_deflate_compact: workgroup c copies chunk c's bytes from its slot to dst + offset[c] (byte offsets: byte copies).
 // The entry then copies {total, crc} to pinned memory and waits for the stream once.
+// k_deflate_strips (tip_deflate_strips; the strips section below): the same chunk encoder on every strip of a TIFF page as a
+// buffer of its own, framed as a zlib stream with the strip's Adler-32 in place of the CRC (movie.export_tiff).
 #include "tip_internal.h"
 
 namespace tip {
@@ -57,7 +59,11 @@ constexpr uint32_t DF_POLY = 0xEDB88320u;
 // stored block, the padding, LEN and NLEN.
 __host__ __device__ constexpr long chunk_bound(long n) { return (3 + 9 * n + 7 + 3 + 7) / 8 + 4; }
 
-constexpr int DF_OUT_WORDS = (int)((chunk_bound(DF_CHUNK) + 3) / 4) + 1;      // LDS output words (+1: the accumulator's last flush)
+// A strip's zlib stream (the strips section below) is a chunk with 78 01 in front and the final block and the Adler-32 behind.
+constexpr int ZL_LEAD = 2, ZL_TAIL = 5 + 4;
+__host__ __device__ constexpr long strip_bound(long n) { return (ZL_LEAD + chunk_bound(n) + ZL_TAIL + 1) & ~1L; }      // (even: strips start on words)
+
+constexpr int DF_OUT_WORDS = (int)((ZL_LEAD + chunk_bound(DF_CHUNK) + ZL_TAIL + 3) / 4) + 1;      // LDS output words (+1: the accumulator's last flush)
 constexpr int DF_IN_WORDS = DF_THREADS * DF_SEG_LD;
 constexpr int DF_LDS_WORDS = DF_IN_WORDS + DF_OUT_WORDS + 256 + 8;
 
@@ -619,19 +625,23 @@ struct DynCode {                            // the chunk's own codes, in LDS
 };
 
 // One chunk by one workgroup (this file's head): what all the kernels are, but for the token rule and the coding (DYN: the
-// dynamic coding's section above; dists: the rule's candidates once more, or zeros).
-template <int E, bool DYN, class Rule>
-__device__ static __forceinline__ void deflate_chunk(Rule &rule, const RowDists &dists, const uint8_t *__restrict__ src, long nbytes, int aligned,
-                                                     uint32_t *__restrict__ slots, uint32_t *__restrict__ sizes,
-                                                     uint32_t *__restrict__ crc_out)
+// dynamic coding's section above; dists: the rule's candidates once more, or zeros).  The chunk is the DF_CHUNK bytes from
+// `base` on of the buffer (src, nbytes) -- the bytes the rule's matches may reach into; its stream goes to `slot`, the stream's size
+// to *size_out.  ZLIB false: the buffer's CRC-32 is folded into *sum_out.  ZLIB true (the strips section below: the buffer IS the
+// chunk): the stream is a whole zlib stream -- 78 01 in front, which shifts every bit by ZL_LEAD bytes, the final empty stored block
+// and the chunk's Adler-32 behind -- and sum_out is not used.
+template <int E, bool DYN, bool ZLIB, class Rule>
+__device__ static __forceinline__ void deflate_chunk(Rule &rule, const RowDists &dists, const uint8_t *__restrict__ src, long nbytes, long base,
+                                                     int aligned, uint32_t *__restrict__ slot, uint32_t *__restrict__ size_out,
+                                                     uint32_t *__restrict__ sum_out)
 {
     extern __shared__ uint32_t df_lds[];
     uint32_t *in = df_lds, *out = df_lds + DF_IN_WORDS, *crctab = out + DF_OUT_WORDS, *misc = crctab + 256;
     [[maybe_unused]] uint32_t *kept = misc + 8, *dm = kept + DY_MISC;      // (DYN only: DY_WORDS more)
     const int t = threadIdx.x;
-    const long base = (long)blockIdx.x * DF_CHUNK;
     const int L = (int)(nbytes - base < DF_CHUNK ? nbytes - base : DF_CHUNK);      // 1 .. 65536, a multiple of E
     const uint8_t *chunk = src + base;
+    constexpr uint32_t lead = ZLIB ? 8u * ZL_LEAD : 0u;      // the bits in front of the first block
 
     for (int i = t; 4 * i < L; i += DF_THREADS) {
         uint32_t d;
@@ -643,15 +653,15 @@ __device__ static __forceinline__ void deflate_chunk(Rule &rule, const RowDists 
         }
         in[(i >> 6) * DF_SEG_LD + (i & 63)] = d;
     }
-    const int out_words = (int)((chunk_bound(L) + 3) / 4) + 1;
+    const int out_words = (int)((chunk_bound(L) + (ZLIB ? ZL_LEAD + ZL_TAIL : 0) + 3) / 4) + 1;
     const int zero_words = DYN && out_words < DY_SCRATCH ? DY_SCRATCH : out_words;      // (DYN: its scratch starts from zeros too)
     for (int i = t; i < zero_words; i += DF_THREADS) out[i] = 0;
-    {
+    if constexpr (!ZLIB) {
         uint32_t c = (uint32_t)t;             // the CRC of the one byte t: eight steps of the bitwise definition
         for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? DF_POLY : 0u);
         crctab[t] = c;
     }
-    if (t < 8) misc[t] = 0;                   // [0..3] the waves' bit totals, [4] the workgroup's CRC
+    if (t < 8) misc[t] = 0;                   // [0..3] the waves' bit totals, [4] the workgroup's CRC (ZLIB: [4], [5] the Adler sums)
     if constexpr (DYN) {
         for (int i = t; i < DY_WORDS; i += DF_THREADS) kept[i] = 0;
     }
@@ -682,7 +692,7 @@ __device__ static __forceinline__ void deflate_chunk(Rule &rule, const RowDists 
 
     rule.prepare(src, nbytes, base + first, seg, nb, has_prev, prev);
     CountSink cs;
-    uint32_t before, total, head = 3u, eob_bits = 7u;      // head: the bits in front of the first token; the fixed end of block: seven zeros
+    uint32_t before, total, head = lead + 3u, eob_bits = 7u;      // head: the bits in front of the first token; the fixed end of block: seven zeros
     bool dynamic = false;
     DynCode dyn{};
     if constexpr (DYN) {
@@ -731,7 +741,7 @@ __device__ static __forceinline__ void deflate_chunk(Rule &rule, const RowDists 
             cs.bits = 0;
             rule.encode(dyn, cs, seg, nb, has_prev, prev);
             scan(cs.bits, before, total);
-            head = dm[DM_HDR_BITS];
+            head = lead + dm[DM_HDR_BITS];
             eob_bits = kept[DY_TAB + 256] >> 16;
         } else {
             __syncthreads();                  // the output words are zero again
@@ -741,9 +751,16 @@ __device__ static __forceinline__ void deflate_chunk(Rule &rule, const RowDists 
         scan(cs.bits, before, total);
     }
 
-    WordSink ws(out, dynamic || t > 0 ? head + before : 0u);
+    WordSink ws(out, dynamic || t > 0 ? head + before : lead);
+    if constexpr (ZLIB) {
+        if (t == 0) atomicOr(&out[0], 0x0178u);      // CMF 78: deflate, a 32 KB window; FLG 01: no dictionary, level 0, and 0x7801 a multiple of 31
+    }
     if (dynamic) {
-        if (t < 64 && kept[DY_HDR + t]) atomicOr(&out[t], kept[DY_HDR + t]);
+        if (t < 64 && kept[DY_HDR + t]) {
+            const uint64_t h = (uint64_t)kept[DY_HDR + t] << lead;      // (the header's words, moved behind the lead)
+            atomicOr(&out[t], (uint32_t)h);
+            if (lead && (uint32_t)(h >> 32)) atomicOr(&out[t + 1], (uint32_t)(h >> 32));
+        }
         rule.encode(dyn, ws, seg, nb, has_prev, prev);
         if (t == 0) {
             ws.flush();
@@ -762,25 +779,70 @@ __device__ static __forceinline__ void deflate_chunk(Rule &rule, const RowDists 
         atomicOr(&out[(body + 3u) >> 2], 0xFFu << (8u * ((body + 3u) & 3u)));
     }
 
-    uint32_t part = 0;
-    if (nb > 0) {
-        uint32_t c = 0xFFFFFFFFu;
+    if constexpr (ZLIB) {
+        // Adler-32 (RFC 1950) of the L bytes x_0 ..: s1 = 1 + sum x_i, s2 = L + sum (L - i) x_i, both modulo 65521.  A thread's
+        // share is its segment's two sums with the weights counted from the segment's end, moved to the chunk's end by
+        // (bytes behind the segment) * (its plain sum); one add per wave into LDS.
+        uint32_t s1 = 0;
+        uint64_t s2 = 0;
         for (int w = 0; 4 * w < nb; ++w) {
             const uint32_t d = seg[w];
-            for (int b = 0; b < 4 && 4 * w + b < nb; ++b) c = crctab[(c ^ (d >> (8 * b))) & 255u] ^ (c >> 8);
+            for (int b = 0; b < 4 && 4 * w + b < nb; ++b) {
+                const uint32_t x = (d >> (8 * b)) & 255u;
+                s1 += x;
+                s2 += (uint32_t)(nb - (4 * w + b)) * x;
+            }
         }
-        part = gf_mul(~c, gf_x_pow_8n((unsigned long)(nbytes - (base + first + nb))));
-    }
-    for (int d = 32; d >= 1; d >>= 1) part ^= __shfl_xor(part, d, 64);
-    if (lane == 0) atomicXor(&misc[4], part);
-    __syncthreads();                          // the output words and the CRC are complete
+        if (nb > 0) s2 += (uint64_t)(uint32_t)(L - (first + nb)) * s1;      // below 2^33
+        uint32_t a = s1 % 65521u, b = (uint32_t)(s2 % 65521u);
+        for (int d = 32; d >= 1; d >>= 1) {
+            a += __shfl_xor(a, d, 64);
+            b += __shfl_xor(b, d, 64);
+        }
+        if (lane == 0) {
+            atomicAdd(&misc[4], a);
+            atomicAdd(&misc[5], b);
+        }
+        __syncthreads();                      // the output words and the sums are complete
+        if (t == 0) {                         // the final block 01 00 00 FF FF and the Adler-32, most significant byte first
+            const uint32_t adler = (((uint32_t)L + misc[5]) % 65521u) << 16 | ((1u + misc[4]) % 65521u);
+            const uint32_t tail[ZL_TAIL] = {1u, 0u, 0u, 0xFFu, 0xFFu, adler >> 24, (adler >> 16) & 255u, (adler >> 8) & 255u, adler & 255u};
+            for (uint32_t i = 0; i < (uint32_t)ZL_TAIL; ++i) out[(size + i) >> 2] |= tail[i] << (8u * ((size + i) & 3u));
+        }
+        __syncthreads();
+        const uint32_t whole = size + (uint32_t)ZL_TAIL;
+        for (uint32_t i = t; 4u * i < whole; i += DF_THREADS) slot[i] = out[i];
+        if (t == 0) *size_out = whole;
+    } else {
+        uint32_t part = 0;
+        if (nb > 0) {
+            uint32_t c = 0xFFFFFFFFu;
+            for (int w = 0; 4 * w < nb; ++w) {
+                const uint32_t d = seg[w];
+                for (int b = 0; b < 4 && 4 * w + b < nb; ++b) c = crctab[(c ^ (d >> (8 * b))) & 255u] ^ (c >> 8);
+            }
+            part = gf_mul(~c, gf_x_pow_8n((unsigned long)(nbytes - (base + first + nb))));
+        }
+        for (int d = 32; d >= 1; d >>= 1) part ^= __shfl_xor(part, d, 64);
+        if (lane == 0) atomicXor(&misc[4], part);
+        __syncthreads();                      // the output words and the CRC are complete
 
-    uint32_t *slot = slots + (size_t)blockIdx.x * DF_OUT_WORDS;
-    for (uint32_t i = t; 4u * i < size; i += DF_THREADS) slot[i] = out[i];
-    if (t == 0) {
-        sizes[blockIdx.x] = size;
-        atomicXor(crc_out, misc[4]);
+        for (uint32_t i = t; 4u * i < size; i += DF_THREADS) slot[i] = out[i];
+        if (t == 0) {
+            *size_out = size;
+            atomicXor(sum_out, misc[4]);
+        }
     }
+}
+
+// the chunk of workgroup blockIdx.x of a whole buffer, into its slot of the chunk-strided workspace
+template <int E, bool DYN, class Rule>
+__device__ static __forceinline__ void deflate_own_chunk(Rule &rule, const RowDists &dists, const uint8_t *__restrict__ src, long nbytes, int aligned,
+                                                         uint32_t *__restrict__ slots, uint32_t *__restrict__ sizes,
+                                                         uint32_t *__restrict__ crc_out)
+{
+    deflate_chunk<E, DYN, false>(rule, dists, src, nbytes, (long)blockIdx.x * DF_CHUNK, aligned, slots + (size_t)blockIdx.x * DF_OUT_WORDS,
+                                 sizes + blockIdx.x, crc_out);
 }
 
 template <int E>
@@ -789,7 +851,7 @@ __global__ __launch_bounds__(DF_THREADS) void k_deflate_runs(const uint8_t *__re
                                                              uint32_t *__restrict__ crc_out)
 {
     RunsRule<E> rule;
-    deflate_chunk<E, false>(rule, RowDists{}, src, nbytes, aligned, slots, sizes, crc_out);
+    deflate_own_chunk<E, false>(rule, RowDists{}, src, nbytes, aligned, slots, sizes, crc_out);
 }
 
 template <int E>
@@ -799,7 +861,7 @@ __global__ __launch_bounds__(DF_THREADS) void k_deflate_rows(const uint8_t *__re
 {
     RowsRule<E> rule;
     rule.set(dist);
-    deflate_chunk<E, false>(rule, dist, src, nbytes, aligned, slots, sizes, crc_out);
+    deflate_own_chunk<E, false>(rule, dist, src, nbytes, aligned, slots, sizes, crc_out);
 }
 
 // either rule with the dynamic coding (dist: all zero with RunsRule)
@@ -810,18 +872,47 @@ __global__ __launch_bounds__(DF_THREADS) void k_deflate_dynamic(const uint8_t *_
 {
     Rule rule;
     rule.set(dist);
-    deflate_chunk<E, true>(rule, dist, src, nbytes, aligned, slots, sizes, crc_out);
+    deflate_own_chunk<E, true>(rule, dist, src, nbytes, aligned, slots, sizes, crc_out);
 }
 
-// offsets[c] = sizes[0] + ... + sizes[c - 1]; *total = the sum.  One workgroup, 256 chunks per step.
+// ---- strips (tip_deflate_strips; tests/deflate_strips_restate.py) -----------------------------------------------------------------
+// The pages of a TIFF are cut into strips of rows_per_strip rows, every strip a zlib stream of its own (RFC 1950) that a reader
+// inflates without any other: 78 01, the body, the final empty stored block 01 00 00 FF FF, the strip's Adler-32.  The body is what
+// the rows entry (codes 0) or the dynamic entry (codes 1) writes for the strip as a WHOLE BUFFER, so a strip is one chunk -- at
+// most 65536 bytes -- and no match reaches before it: deflate_chunk with the strip as its buffer (ZLIB).  Strips are handed out
+// like the inflate kernel's: workgroup g of G takes strips g, g + G, ... -- the trip count comes from the block number alone.
+struct StripPlan {
+    long rows, row_bytes, rows_per_strip, strips_per_page, n_strips;
+    int slot_words;                           // words between two strips' slots: the longest strip's bound
+};
+
+template <int E, bool DYN, class Rule>
+__global__ __launch_bounds__(DF_THREADS) void k_deflate_strips(const uint8_t *__restrict__ src, StripPlan plan, RowDists dist,
+                                                               uint32_t *__restrict__ slots, uint32_t *__restrict__ sizes)
+{
+    Rule rule;
+    rule.set(dist);
+    for (long s = blockIdx.x; s < plan.n_strips; s += gridDim.x) {
+        const long page = s / plan.strips_per_page, row0 = (s % plan.strips_per_page) * plan.rows_per_strip;
+        const long nrows = plan.rows - row0 < plan.rows_per_strip ? plan.rows - row0 : plan.rows_per_strip;
+        const uint8_t *strip = src + (page * plan.rows + row0) * plan.row_bytes;
+        deflate_chunk<E, DYN, true>(rule, dist, strip, nrows * plan.row_bytes, 0, (int)(((uintptr_t)strip & 3u) == 0),
+                                    slots + (size_t)s * plan.slot_words, sizes + s, nullptr);
+        __syncthreads();                      // (the next strip is staged over this one's words)
+    }
+}
+
+// offsets[c] = sizes[0] + ... + sizes[c - 1]; *total = the sum.  One workgroup, 256 chunks per step.  even: every size counts
+// rounded up to an even number (strips start on word boundaries).  table, when given: (offset, size) per chunk as int64 pairs,
+// the total behind them.
 __global__ __launch_bounds__(256) void k_deflate_offsets(const uint32_t *__restrict__ sizes, long n, unsigned long *__restrict__ offsets,
-                                                         unsigned long *__restrict__ total)
+                                                         unsigned long *__restrict__ total, int even, long *__restrict__ table)
 {
     __shared__ unsigned long wave_sum[4];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     unsigned long carry = 0;
     for (long c0 = 0; c0 < n; c0 += 256) {
-        const unsigned long v = c0 + t < n ? sizes[c0 + t] : 0ul;
+        const unsigned long v = c0 + t < n ? (sizes[c0 + t] + (even ? 1ul : 0ul)) & ~(even ? 1ul : 0ul) : 0ul;
         unsigned long incl = v;
         for (int d = 1; d < 64; d <<= 1) {
             const unsigned long up = __shfl_up(incl, d, 64);
@@ -834,20 +925,31 @@ __global__ __launch_bounds__(256) void k_deflate_offsets(const uint32_t *__restr
             if (w < wave) before += wave_sum[w];
             all += wave_sum[w];
         }
-        if (c0 + t < n) offsets[c0 + t] = carry + before + incl - v;
+        if (c0 + t < n) {
+            offsets[c0 + t] = carry + before + incl - v;
+            if (table) {
+                table[2 * (c0 + t)] = (long)(carry + before + incl - v);
+                table[2 * (c0 + t) + 1] = (long)sizes[c0 + t];
+            }
+        }
         carry += all;
         __syncthreads();                      // (the next step overwrites wave_sum)
     }
-    if (t == 0) *total = carry;
+    if (t == 0) {
+        *total = carry;
+        if (table) table[2 * n] = (long)carry;
+    }
 }
 
-__global__ __launch_bounds__(256) void k_deflate_compact(const uint32_t *__restrict__ slots, const uint32_t *__restrict__ sizes,
-                                                         const unsigned long *__restrict__ offsets, uint8_t *__restrict__ dst)
+// slot_words: the words between two slots.  even: a stream of odd size is followed by one zero byte.
+__global__ __launch_bounds__(256) void k_deflate_compact(const uint32_t *__restrict__ slots, int slot_words, const uint32_t *__restrict__ sizes,
+                                                         const unsigned long *__restrict__ offsets, int even, uint8_t *__restrict__ dst)
 {
-    const uint8_t *slot = (const uint8_t *)(slots + (size_t)blockIdx.x * DF_OUT_WORDS);
+    const uint8_t *slot = (const uint8_t *)(slots + (size_t)blockIdx.x * slot_words);
     uint8_t *to = dst + offsets[blockIdx.x];
     const uint32_t size = sizes[blockIdx.x];
     for (uint32_t i = threadIdx.x; i < size; i += 256) to[i] = slot[i];
+    if (even && (size & 1u) && threadIdx.x == 0) to[size] = 0;
 }
 
 // rows: the candidate distances of the rows rule, or null for the run-only rule; dynamic: the dynamic coding
@@ -938,8 +1040,8 @@ static int deflate_dev(const void *src, long nbytes, int elem_bytes, long row_by
            : elem_bytes == 2 ? launch_encode<2>(src, nbytes, chunks, rows, dynamic, slots, sizes, (uint32_t *)(result + 1))
                              : launch_encode<4>(src, nbytes, chunks, rows, dynamic, slots, sizes, (uint32_t *)(result + 1));
     if (rc) return rc;
-    TIP_LAUNCH("deflate_offsets", k_deflate_offsets, dim3(1), dim3(256), 0, sizes, chunks, offsets, result);
-    TIP_LAUNCH("deflate_compact", k_deflate_compact, dim3((unsigned)chunks), dim3(256), 0, slots, sizes, offsets, (uint8_t *)dst);
+    TIP_LAUNCH("deflate_offsets", k_deflate_offsets, dim3(1), dim3(256), 0, sizes, chunks, offsets, result, 0, (long *)nullptr);
+    TIP_LAUNCH("deflate_compact", k_deflate_compact, dim3((unsigned)chunks), dim3(256), 0, slots, DF_OUT_WORDS, sizes, offsets, 0, (uint8_t *)dst);
     TIP_HIP(hipMemcpyAsync(pin, result, 16, hipMemcpyDeviceToHost, c.stream));
     TIP_HIP(hipStreamSynchronize(c.stream));
     *out_bytes = (int64_t)pin[0];
@@ -972,11 +1074,149 @@ static int entry_host(const char *who, const void *src, long nbytes, int elem_by
     return st.finish();
 }
 
+// ---- the strips entries ------------------------------------------------------------------------------------------------------
+static StripPlan strip_plan(long n_pages, long rows, long row_bytes, long rps)
+{
+    StripPlan p{};
+    p.rows = rows;
+    p.row_bytes = row_bytes;
+    p.rows_per_strip = rps;
+    p.strips_per_page = (rows + rps - 1) / rps;
+    p.n_strips = n_pages * p.strips_per_page;
+    p.slot_words = (int)((strip_bound((rows < rps ? rows : rps) * row_bytes) + 3) / 4);
+    return p;
+}
+
+static long strips_bound(long n_pages, long rows, long row_bytes, long rps)
+{
+    const long full = rows / rps, rest = rows % rps;
+    return n_pages * (full * strip_bound(rps * row_bytes) + (rest ? strip_bound(rest * row_bytes) : 0));
+}
+
+static int check_strip_shape(const char *who, long n_pages, long rows, long row_bytes, long rps)
+{
+    if (n_pages < 0 || rows < 0) return fail(TIP_ERR_ARG, "%s: %ld pages of %ld rows", who, n_pages, rows);
+    if (row_bytes < 1) return fail(TIP_ERR_ARG, "%s: row_bytes %ld is not positive", who, row_bytes);
+    if (rps < 1) return fail(TIP_ERR_ARG, "%s: rows_per_strip %ld is not positive", who, rps);
+    return TIP_OK;
+}
+
+static int check_strip_args(const char *who, const void *src, long n_pages, long rows, long row_bytes, int elem_bytes, long rps, int codes,
+                            const void *dst, long cap, const void *table, const void *out_bytes)
+{
+    if (!src || !dst || !table || !out_bytes) return fail(TIP_ERR_ARG, "%s: null pointer", who);
+    if (elem_bytes != 1 && elem_bytes != 2) return fail(TIP_ERR_ARG, "%s: elem_bytes %d (1 or 2)", who, elem_bytes);
+    if (codes != 0 && codes != 1) return fail(TIP_ERR_ARG, "%s: codes %d (0 fixed, 1 dynamic)", who, codes);
+    if (int rc = check_strip_shape(who, n_pages, rows, row_bytes, rps)) return rc;
+    if (row_bytes % elem_bytes) return fail(TIP_ERR_ARG, "%s: row_bytes %ld is not a multiple of elem_bytes %d", who, row_bytes, elem_bytes);
+    if (rps > DF_CHUNK || rps * row_bytes > DF_CHUNK)
+        return fail(TIP_ERR_UNSUPPORTED, "%s: a strip of %ld rows of %ld bytes is more than %d bytes", who, rps, row_bytes, DF_CHUNK);
+    if (n_pages && (rows + rps - 1) / rps > 0x7FFFFFFFL / n_pages) return fail(TIP_ERR_ARG, "%s: more than 2^31 - 1 strips", who);
+    if (cap < strips_bound(n_pages, rows, row_bytes, rps))
+        return fail(TIP_ERR_ARG, "%s: cap %ld is below tip_deflate_strips_bound = %ld", who, cap, strips_bound(n_pages, rows, row_bytes, rps));
+    return TIP_OK;
+}
+
+template <int E>
+static int launch_strips(const uint8_t *src, const StripPlan &plan, const RowDists *rows, bool dynamic, unsigned groups, uint32_t *slots,
+                         uint32_t *sizes)
+{
+    constexpr size_t lds = (size_t)DF_LDS_WORDS * 4, dlds = lds + (size_t)DY_WORDS * 4;
+    if (dynamic && rows) {
+        TIP_HIP(hipFuncSetAttribute((const void *)k_deflate_strips<E, true, RowsRule<E>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));
+        TIP_LAUNCH("deflate_strips_dynamic_rows", (k_deflate_strips<E, true, RowsRule<E>>), dim3(groups), dim3(DF_THREADS), dlds, src, plan, *rows,
+                   slots, sizes);
+    } else if (dynamic) {
+        TIP_HIP(hipFuncSetAttribute((const void *)k_deflate_strips<E, true, RunsRule<E>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));
+        TIP_LAUNCH("deflate_strips_dynamic_runs", (k_deflate_strips<E, true, RunsRule<E>>), dim3(groups), dim3(DF_THREADS), dlds, src, plan,
+                   RowDists{}, slots, sizes);
+    } else if (rows) {
+        TIP_HIP(hipFuncSetAttribute((const void *)k_deflate_strips<E, false, RowsRule<E>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        TIP_LAUNCH("deflate_strips_rows", (k_deflate_strips<E, false, RowsRule<E>>), dim3(groups), dim3(DF_THREADS), lds, src, plan, *rows, slots,
+                   sizes);
+    } else {
+        TIP_HIP(hipFuncSetAttribute((const void *)k_deflate_strips<E, false, RunsRule<E>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        TIP_LAUNCH("deflate_strips_runs", (k_deflate_strips<E, false, RunsRule<E>>), dim3(groups), dim3(DF_THREADS), lds, src, plan, RowDists{},
+                   slots, sizes);
+    }
+    return TIP_OK;
+}
+
+// all device addresses but table_host and out_bytes; the arguments are checked
+static int deflate_strips_dev(const void *src, long n_pages, long rows, long row_bytes, int elem_bytes, long rps, bool dynamic, void *dst,
+                              int64_t *table_host, int64_t *out_bytes)
+{
+    *out_bytes = 0;
+    if (n_pages == 0 || rows == 0) return TIP_OK;
+    Ctx &c = ctx();
+    const StripPlan plan = strip_plan(n_pages, rows, row_bytes, rps);
+    const long n = plan.n_strips;
+    WsGuard ws;
+    uint32_t *slots = ws.get<uint32_t>((size_t)n * plan.slot_words), *sizes = ws.get<uint32_t>(n);
+    unsigned long *offsets = ws.get<unsigned long>(n), *total = ws.get<unsigned long>(1);
+    long *table = ws.get<long>(2 * n + 1);
+    long *pin = (long *)pinned_scratch((size_t)(2 * n + 1) * 8);
+    if (!slots || !sizes || !offsets || !total || !table || !pin) return TIP_ERR_NOMEM;
+    static int cus = 0;          // (same device model on every GPU of a node; a benign race writes the same value)
+    if (!cus) {
+        hipDeviceProp_t prop;
+        cus = hipGetDeviceProperties(&prop, c.device) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    const unsigned groups = (unsigned)(n < cus ? n : cus);      // one workgroup's LDS fills a CU
+    const RowDists dists = row_dists(elem_bytes, row_bytes), *rd = dists.row_bytes ? &dists : nullptr;
+    if (int rc = elem_bytes == 1 ? launch_strips<1>((const uint8_t *)src, plan, rd, dynamic, groups, slots, sizes)
+                                 : launch_strips<2>((const uint8_t *)src, plan, rd, dynamic, groups, slots, sizes))
+        return rc;
+    TIP_LAUNCH("deflate_offsets", k_deflate_offsets, dim3(1), dim3(256), 0, sizes, n, offsets, total, 1, table);
+    TIP_LAUNCH("deflate_compact", k_deflate_compact, dim3((unsigned)n), dim3(256), 0, slots, plan.slot_words, sizes, offsets, 1, (uint8_t *)dst);
+    TIP_HIP(hipMemcpyAsync(pin, table, (size_t)(2 * n + 1) * 8, hipMemcpyDeviceToHost, c.stream));
+    TIP_HIP(hipStreamSynchronize(c.stream));
+    memcpy(table_host, pin, (size_t)n * 16);
+    *out_bytes = pin[2 * n];
+    return TIP_OK;
+}
+
 }  // namespace tip
 
 using namespace tip;
 
 extern "C" {
+
+int tip_deflate_strips_bound(int64_t n_pages, int64_t rows, int64_t row_bytes, int64_t rows_per_strip, int64_t *bound_out)
+{
+    if (!bound_out) return fail(TIP_ERR_ARG, "tip_deflate_strips_bound: null pointer");
+    if (int rc = check_strip_shape("tip_deflate_strips_bound", n_pages, rows, row_bytes, rows_per_strip)) return rc;
+    *bound_out = strips_bound(n_pages, rows, row_bytes, rows_per_strip);
+    return TIP_OK;
+}
+
+int tip_deflate_strips_dev(const void *src_dev, int64_t n_pages, int64_t rows, int64_t row_bytes, int elem_bytes, int64_t rows_per_strip,
+                           int codes, void *dst_dev, int64_t cap, int64_t *table_host, int64_t *out_bytes_host)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_strip_args("tip_deflate_strips_dev", src_dev, n_pages, rows, row_bytes, elem_bytes, rows_per_strip, codes, dst_dev, cap,
+                                  table_host, out_bytes_host))
+        return rc;
+    return deflate_strips_dev(src_dev, n_pages, rows, row_bytes, elem_bytes, rows_per_strip, codes == 1, dst_dev, table_host, out_bytes_host);
+}
+
+int tip_deflate_strips(const void *src, int64_t n_pages, int64_t rows, int64_t row_bytes, int elem_bytes, int64_t rows_per_strip, int codes,
+                       void *dst, int64_t cap, int64_t *table, int64_t *out_bytes)
+{
+    Ctx &c = ctx();
+    if (!c.stream) return TIP_ERR_HIP;
+    if (int rc = check_strip_args("tip_deflate_strips", src, n_pages, rows, row_bytes, elem_bytes, rows_per_strip, codes, dst, cap, table,
+                                  out_bytes))
+        return rc;
+    Staging st;
+    const uint8_t *ds = st.in((const uint8_t *)src, (size_t)(n_pages * rows * row_bytes));
+    uint8_t *dd = st.out((uint8_t *)dst, (size_t)strips_bound(n_pages, rows, row_bytes, rows_per_strip));
+    if (st.rc) return st.rc;
+    if (int rc = deflate_strips_dev(ds, n_pages, rows, row_bytes, elem_bytes, rows_per_strip, codes == 1, dd, table, out_bytes)) return rc;
+    st.set_count(dd, (size_t)*out_bytes);
+    return st.finish();
+}
 
 int tip_deflate_runs_bound(int64_t nbytes, int64_t *bound_out)
 {

@@ -499,6 +499,17 @@ class GpuFrameBackend(object):
         """Frame t's type map (uint8 (Y, X): a valid cell's type, 255 on invalid cells and label 0), downloaded."""
         return self.type_maps[t].download((self.Y, self.X), np.uint8)
 
+    def export_page_strips(self, t, ids, rowsperstrip, codes="dynamic"):
+        """Frame t's export pages as TIFF strips (export_tiff): the resident label map becomes the uint16 page of track ids
+        ids[label - 1] and, when the frame was typed, its type map the page with 0 -> 2 and 255 -> 0 (tip_export_maps_u16_dev); both
+        are deflated strip by strip where they are (tip_deflate_strips_dev) and only the streams come to the host -> per page the
+        list of its strips' zlib streams.  Called on the thread that owns this backend's pipeline."""
+        from .tiff_export import PageEncoder
+        if getattr(self, "_page_encoder", None) is None:
+            self._page_encoder = PageEncoder(self.Y, self.X)
+        types = self.type_maps[t].ptr if self.cell_types is not None else None
+        return self._page_encoder.encode(self.labels[t].ptr, types, ids, rowsperstrip, codes)
+
     def lookup(self, t, qy, qx):
         from . import _lib
         qy = np.ascontiguousarray(qy, dtype=np.int64)
@@ -995,3 +1006,26 @@ def save_seg(path, n_frames, backend, tables, ids, rank=0, world=1, dist=None, d
     Tissue._archive_members).  An archive that would need zip64 raises ValueError before anything is written."""
     from .seg_archive import save_seg as _save_seg
     return _save_seg(path, n_frames, backend, tables, ids, rank, world, dist, device, channel_names, events)
+
+
+def export_tiff(path, n_frames, backend, ids, rank=0, world=1, dist=None, device="cpu", rowsperstrip=None, codes="dynamic", bigtiff=None):
+    """Writes a finished movie's tracked labels and cell types as the TIFF of the GUI's "Export segmentation"
+    (Tissue.export_segmentation_and_cell_types_to_tiff): T x C x 1 x Y x X uint16 with deflate strips, channel 0 the tracking labels
+    ids[t][label - 1] (0 on label 0), channel 1 -- only when the backend typed its cells (C = 2, else 1) -- the type map with 0 -> 2
+    and 255 -> 0.  Collective like save_seg: EVERY rank calls it after process_movie, with process_movie's ids on rank 0 (None
+    elsewhere); it needs no archive=, the maps are resident either way.  Returns the path on rank 0, None elsewhere.
+
+    Rank 0 hands the owners the track ids of their frames (one broadcast).  Each owner turns its frames' resident maps into uint16
+    pages and those into one zlib stream per strip on its GPU (backend.export_page_strips: tip_export_maps_u16_dev, then
+    tip_deflate_strips_dev) -- no map reaches the host uncompressed.  The strips travel to rank 0 as records in one gather
+    (_collectives.gather_varlen), and rank 0 writes them with basic_image_manipulations.write_tiff_strips, which it tells every
+    strip's size, so bigtiff=None gives BigTIFF exactly when the classic file would reach 4 GiB.  Rank 0 holds the movie's
+    compressed strips once.
+
+    rowsperstrip: None = as many rows as 65536 bytes hold, max(1, min(Y, 65536 // (2 X))) -- the most the strip encoder takes;
+    codes: "dynamic" (per-strip Huffman codes where they are shorter) or "fixed".  The file does not depend on the world size.
+    ValueError on EVERY rank, before anything is written, when a frame was not processed by its owner's backend or holds a track
+    id outside [0, 65535] (the owners all-gather what they found first); ValueError on the owner when ids do not cover a frame's
+    labels."""
+    from .tiff_export import export_tiff as _export_tiff
+    return _export_tiff(path, n_frames, backend, ids, rank, world, dist, device, rowsperstrip, codes, bigtiff)

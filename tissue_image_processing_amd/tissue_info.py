@@ -12,6 +12,8 @@ reference's state / cache / persistence code (ti.py:193-353, 3462-3823) stays th
     calc_neighbors_contact_matrix(frame)                   ti.py:4073-4094 -> tip_rankfilter2d (cross footprint)
     track_cells_iterator(...)                              ti.py:2037-2113 -> tip_rankfilter2d + host table logic
     get_trackking_labels(frame)                            ti.py:4021-4028 -> tip_lut_gather_i32
+    export_segmentation[_and_cell_types]_to_tiff(...,      ti.py:4040-4062 -> tip_export_maps_u16_dev + tip_deflate_strips_dev
+        compression="device")
     calculate_spatial_data(...), get_frame_data(...),      ti.py:1035-1134, 1194-1266 -> tip_spatial_map_f64, tip_window_stats_f64
     calculate_data_around_a_given_point / _cell
     calculate_n_neighbors_from_type / _by_type,            ti.py:1752-1799, 2513-2543, 1844-1872, 1065-1096 -> tip_graph_counts_i32,
@@ -695,6 +697,103 @@ class TissueHipMixin(object):
         _lib.check(_lib.lib().tip_lut_gather_i32(_lib.ptr(lab32), _lib.ptr(cell_ids), cell_ids.size, _lib.ptr(out),
                                                  lab32.size))
         return out
+
+    # ---- exports (ti.py:4040-4062) ----------------------------------------------------------------------------------------------
+    def _export_frame_shape(self):
+        """(Y, X) of the movie's maps: upstream's self.labels.shape where the host class keeps a current label map."""
+        current = getattr(self, "labels", None)
+        if current is not None:
+            return tuple(current.shape[:2])
+        for frame in range(1, self.number_of_frames + 1):
+            if self.get_labels(frame) is not None:
+                return tuple(self.get_labels(frame).shape[:2])
+        raise ValueError("no frame has a label map to export")
+
+    def _export_device_tiff(self, path, channels, frame_maps):
+        """The export's compression="device": frame_maps(frame) -> (labels, ids, types or None) of a valid frame.  Every valid
+        frame's maps go to the device as they are, become uint16 pages and zlib strips there (tiff_export.PageEncoder) and
+        basic_image_manipulations.write_tiff_strips appends them page by page; an invalid frame's pages are zeros, as upstream
+        leaves them."""
+        import zlib
+        from . import tiff_export
+        from ._deflate import default_rows_per_strip
+        from .basic_image_manipulations import write_tiff_strips
+        Y, X = self._export_frame_shape()
+        rps = default_rows_per_strip(Y, 2 * X)
+        encoder = tiff_export.PageEncoder(Y, X)
+        d_labels, d_types = _lib.DeviceBuffer(Y * X * 4), _lib.DeviceBuffer(Y * X)
+        zero_page = [zlib.compress(bytes(min(rps, Y - r) * X * 2), 6) for r in range(0, Y, rps)]
+
+        def pages():
+            for frame in range(1, self.number_of_frames + 1):
+                if not self.is_frame_valid(frame):
+                    for _ in range(channels):
+                        yield zero_page
+                    continue
+                labels, ids, types = frame_maps(frame)
+                if labels is None or labels.shape != (Y, X):
+                    raise ValueError("frame %d has no label map of shape %s" % (frame, (Y, X)))
+                d_labels.upload(np.ascontiguousarray(labels, dtype=np.int32))
+                if types is not None:
+                    d_types.upload(np.ascontiguousarray(types, dtype=np.uint8))
+                for page in encoder.encode(d_labels.ptr, d_types.ptr if types is not None else None, ids, rps, "dynamic"):
+                    yield page
+
+        try:
+            write_tiff_strips(path, (self.number_of_frames, channels, 1, Y, X), "TCZYX", np.uint16, rps, pages())
+        finally:
+            d_labels.free()
+            d_types.free()
+        return 0
+
+    @staticmethod
+    def _check_export_compression(compression):
+        if compression not in (None, "device"):
+            raise ValueError("compression %r (None: upstream's uncompressed file; 'device': deflate strips made on the GPU)" % (compression,))
+
+    def export_segmentation_and_cell_types_to_tiff(self, outfolder, filename, compression=None):
+        """ti.py:4040-4052: T x 2 x 1 x Y x X uint16 -- the tracking labels, and the type map with 0 -> 2 and 255 -> 0; invalid
+        frames stay zero.  compression=None writes it through save_tiff as upstream does; "device" writes the same array with
+        deflate strips, pages and strips made on the GPU (tip_export_maps_u16_dev, tip_deflate_strips_dev)."""
+        import os
+        from .basic_image_manipulations import save_tiff
+        self._check_export_compression(compression)
+        path = os.path.join(outfolder, filename + '.tif')
+        if compression == "device":
+            return self._export_device_tiff(path, 2, lambda frame: (self.get_labels(frame), self.get_cells_info(frame).label.to_numpy(),
+                                                                   self.get_cell_types(frame)))
+        Y, X = self._export_frame_shape()
+        out = np.zeros((self.number_of_frames, 2, 1, Y, X), dtype="uint16")
+        for frame in range(1, self.number_of_frames + 1):
+            if self.is_frame_valid(frame):
+                labels = self.get_trackking_labels(frame)
+                out[frame - 1, 0, 0, :, :] = labels.astype("uint16")
+                cell_types = np.copy(self.get_cell_types(frame))
+                cell_types[cell_types == 0] = 2
+                cell_types[cell_types == 255] = 0
+                out[frame - 1, 1, 0, :, :] = cell_types.astype("uint16")
+        save_tiff(path, out, axes="TCZYX", data_type="uint16")
+        return 0
+
+    def export_segmentation_to_tiff(self, outfolder, filename, compression=None):
+        """ti.py:4054-4062: T x 1 x 1 x Y x X uint16 of the frames' label maps (not the tracking labels); invalid frames stay zero.
+        compression as in export_segmentation_and_cell_types_to_tiff; "device" takes labels up to 65535 (ValueError above)."""
+        import os
+        from .basic_image_manipulations import save_tiff
+        self._check_export_compression(compression)
+        path = os.path.join(outfolder, filename + '.tif')
+        if compression == "device":
+            def maps(frame):
+                labels = self.get_labels(frame)
+                return labels, np.arange(1, (int(labels.max()) if labels is not None and labels.size else 0) + 1, dtype=np.int64), None
+            return self._export_device_tiff(path, 1, maps)
+        Y, X = self._export_frame_shape()
+        out = np.zeros((self.number_of_frames, 1, 1, Y, X), dtype="uint16")
+        for frame in range(1, self.number_of_frames + 1):
+            if self.is_frame_valid(frame):
+                out[frame - 1, 0, 0, :, :] = self.get_labels(frame).astype("uint16")
+        save_tiff(path, out, axes="TCZYX", data_type="uint16")
+        return 0
 
 
     # ---- overlays (SURVEY 8f rank 4; ti.py:584-607, 2585-2645) and event detection (ti.py:609-789) ---------------------------
