@@ -3,11 +3,17 @@ expected.npz holds what the reference's own read_tiff returned for each (tools/m
 source behind open_image / read_image_in_chunks, the cases that must keep raising, and save_tiff's opt-in zlib form."""
 import os
 import struct
+import sys
+import zlib
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from tiff_layout_restate import baseline_file, strip_file  # noqa: E402
+
 TIFF = os.path.join(ROOT, "tests", "golden", "tiff")
 READABLE = ["zlib_rps7", "zlib_rps7_bigtiff", "zlib_predictor_bigendian", "zlib_one_strip", "zlib_imagej", "zlib_u8", "plain_rps7"]
 
@@ -153,31 +159,29 @@ def test_save_tiff_zlib_round_trip(tmp_path, predictor, rowsperstrip):
         bim.save_tiff(str(tmp_path / "x.tif"), tall.astype(np.float32), compression="zlib")
 
 
-def _baseline_layout(image, axes):
-    """The uncompressed file save_tiff has always written, from its documented layout: an 8-byte little-endian header; per
-    (Y, X) plane an IFD of the sorted entries 256, 257, 258, 259, 262, (270 on the first page,) 273, 277, 278, 279, 339 as
-    (tag, type, count, value), the next IFD's offset, the first page's description "axes=... shape=..." (NUL-terminated, padded
-    to a word), the plane's little-endian samples as one strip, and a pad byte after an odd-sized plane."""
-    planes = image.reshape((-1,) + image.shape[-2:]).astype(image.dtype.newbyteorder("<"))
-    rows, cols = planes.shape[1:]
-    item = planes.dtype.itemsize
-    fmt = {"u": 1, "i": 2, "f": 3}[planes.dtype.kind]
-    desc = ("axes=%s shape=%s" % (axes, "x".join(str(v) for v in image.shape))).encode() + b"\0"
-    desc += b"\0" * (len(desc) & 1)
-    out, at = struct.pack("<2sHI", b"II", 42, 8), 8
-    for k in range(len(planes)):
-        extra = desc if k == 0 else b""
-        n = 11 if extra else 10
-        data_at = at + 2 + 12 * n + 4 + len(extra)
-        size = rows * cols * item
-        ent = [(256, 4, 1, cols), (257, 4, 1, rows), (258, 3, 1, item * 8), (259, 3, 1, 1), (262, 3, 1, 1)]
-        ent += [(270, 2, len(extra), at + 2 + 12 * n + 4)] if extra else []
-        ent += [(273, 4, 1, data_at), (277, 3, 1, 1), (278, 4, 1, rows), (279, 4, 1, size), (339, 3, 1, fmt)]
-        nxt = data_at + size + (size & 1) if k + 1 < len(planes) else 0
-        out += struct.pack("<H", n) + b"".join(struct.pack("<HHII", *e) for e in ent) + struct.pack("<I", nxt)
-        out += extra + planes[k].tobytes() + b"\0" * (size & 1)
-        at = nxt
-    return out
+def _differenced_zlib_strips(array, rps):
+    """per page the strips save_tiff(compression="zlib", predictor=2) makes: every row's differences modulo 2^bits, the rows cut
+    into strips of rps rows, each strip a zlib stream of level 6"""
+    planes = array.reshape((-1,) + array.shape[-2:])
+    diff = planes.copy()
+    diff[:, :, 1:] = planes[:, :, 1:] - planes[:, :, :-1]          # (unsigned arithmetic wraps)
+    return [[zlib.compress(p[r:r + rps].astype(p.dtype.newbyteorder("<")).tobytes(), 6) for r in range(0, p.shape[0], rps)] for p in diff]
+
+
+@pytest.mark.parametrize("dtype,shape,rowsperstrip", [(np.uint16, (2, 23, 31), 7), (np.uint8, (3, 9, 13), None)])
+def test_save_tiff_zlib_predictor_2_is_the_restated_file(tmp_path, dtype, shape, rowsperstrip):
+    """Several ragged strips with their offset and count tables, and one strip a page (the default: 64 KB hold the 9 rows)."""
+    from tissue_image_processing_amd import basic_image_manipulations as bim
+    rng = np.random.default_rng(7)
+    a = (rng.integers(0, 4, shape) * rng.integers(0, 60, shape[-1])).astype(dtype)
+    a[:, 3:5, ::2] = np.iinfo(dtype).max                            # differences that wrap
+    rps = shape[-2] if rowsperstrip is None else rowsperstrip
+    pages = _differenced_zlib_strips(a, rps)
+    assert len(pages[0]) == (4 if rowsperstrip else 1)
+    p = str(tmp_path / "p2.tif")
+    bim.save_tiff(p, a, axes="ZYX", compression="zlib", predictor=2, rowsperstrip=rowsperstrip)
+    assert open(p, "rb").read() == strip_file(shape, "ZYX", np.dtype(dtype), rps, pages, predictor=2)
+    assert np.array_equal(bim.read_tiff(p)[0], a)
 
 
 def test_save_tiff_default_bytes_are_unchanged(tmp_path):
@@ -187,7 +191,7 @@ def test_save_tiff_default_bytes_are_unchanged(tmp_path):
         a = (rng.random(shape) * 200).astype(dtype)
         p = str(tmp_path / "plain.tif")
         bim.save_tiff(p, a, axes=axes)
-        assert open(p, "rb").read() == _baseline_layout(a, axes)
+        assert open(p, "rb").read() == baseline_file(a, axes)
 
 
 @pytest.mark.parametrize("name", ["zlib_rps7", "zlib_rps7_bigtiff", "zlib_predictor_bigendian", "zlib_one_strip", "zlib_imagej"])

@@ -121,11 +121,6 @@ def strip_codes(codes):
     raise ValueError("codes must be 'fixed' or 'dynamic', not %r" % (codes,))
 
 
-def default_rows_per_strip(rows, row_bytes):
-    """The strip height the exports use: as many rows as 65536 bytes hold -- the most tip_deflate_strips takes --, at least 1."""
-    return max(1, min(int(rows), 65536 // max(1, int(row_bytes))))
-
-
 def strips_bound(n_pages, rows, row_bytes, rows_per_strip):
     """tip_deflate_strips_bound: the most bytes the strip encoder writes for these pages (no device needed)."""
     out = ctypes.c_int64(0)

@@ -4,14 +4,18 @@ Same function names, argument meaning, return dtypes and error behaviour as the 
     put_channel_axis_first(image, axes)                              bim.py:199-231   (pure view logic, host)
     blur_image(image, std)                                           bim.py:373-390   -> tip_gaussian3d_w
     watershed_segmentation(image, imgthresh, stdeviation, blocksize) bim.py:446-476   -> tip_watershed_segmentation
-    read_image_in_chunks / get_image_dimensions / concatenate_time_points / read_tiff / save_tiff
-                                                                     bim.py:28-188, 478-495 (host I/O around the GPU path;
+    read_image_in_chunks / get_image_dimensions / concatenate_time_points
+                                                                     bim.py:54-159, 478-495 (host I/O around the GPU path;
                                                                      image sources: arrays, .npy, TIFF stacks, aicsimageio objects)
+    read_tiff / save_tiff / tiff_page_table / write_tiff_strips      bim.py:28-51, 160-188   (re-exported from tiff.py, which holds
+                                                                     the TIFF container: reader, lazy source, writers)
 """
 
 import numpy as np
 
 from . import _lib
+from .tiff import (TIFF_DEFLATE, BigTiffAppender, TiffPage, TiffSource, TiffTable, read_tiff, save_tiff,  # noqa: F401
+                   tiff_normalise, tiff_page_table, write_tiff_strips)
 
 UINT8_MAXVAL = 255
 UINT16_MAXVAL = 65535
@@ -281,245 +285,11 @@ def stretch_for_display(disp_img, min_percent, max_percent):
     return out
 
 
-def tiff_normalise(image, data_type=""):
-    """The conversion save_tiff applies before writing (bim.py:183-186): images that are not already of the requested
-    unsigned type are scaled so that their maximum becomes the type's maximum, and rounded."""
-    image = np.asarray(image)
-    if data_type and image.dtype != data_type and data_type in ('uint8', 'uint16'):
-        top = 255 if data_type == 'uint8' else 65535
-        image = np.round((image / np.max(image)) * top).astype(data_type)
-    return image
-
-
-def save_tiff(path, image, metadata=None, axes="", data_type="", compression=None, predictor=1, rowsperstrip=None):
-    """bim.py:160-188.  Upstream hands the array to aicsimageio's OME-TIFF writer; here a self-contained baseline TIFF
-    writer stores every (Y, X) plane of the normalised array as one page (little-endian, uncompressed, min-is-black) with
-    the axes string and shape in the first page's ImageDescription -- what ImageJ / tifffile / the reference's read_tiff
-    open as a stack.  `metadata` with a to_xml() method (or a string) is appended to that description; other objects are
-    reported once as not written.
-
-    compression="zlib" (opt-in; uint8 / uint16 only) writes every page as deflate strips instead (Compression 8, host zlib, one
-    stream per strip of `rowsperstrip` rows -- by default about 64 KB of raw data) with predictor 1 or 2 (horizontal
-    differencing).  Without these arguments the file is byte for byte what it always was."""
-    import struct
-    if compression not in (None, "zlib"):
-        raise ValueError("save_tiff: compression %r (None or 'zlib')" % (compression,))
-    if compression is None and (predictor != 1 or rowsperstrip is not None):
-        raise ValueError("save_tiff: predictor and rowsperstrip belong to compression='zlib'")
-    if predictor not in (1, 2):
-        raise ValueError("save_tiff: predictor %r (1: none, 2: horizontal differencing)" % (predictor,))
-    image = tiff_normalise(image, data_type)
-    if image.dtype == np.float64:
-        image = image.astype(np.float32)
-    if image.dtype not in (np.uint8, np.uint16, np.float32, np.int32):
-        raise TypeError("save_tiff writes uint8 / uint16 / int32 / float32 pages (got %s)" % image.dtype)
-    if image.ndim < 2:
-        raise ValueError("save_tiff needs at least a 2-D image")
-    planes = np.ascontiguousarray(image).reshape((-1,) + image.shape[-2:]).astype(image.dtype.newbyteorder("<"))
-    rows, cols = planes.shape[1:]
-    bits = planes.dtype.itemsize * 8
-    fmt = 3 if planes.dtype.kind == "f" else (2 if planes.dtype.kind == "i" else 1)
-    desc = ("axes=%s shape=%s" % (axes, "x".join(str(v) for v in image.shape))).encode("ascii") + b"\0"
-    if metadata is not None:
-        # upstream hands the OME metadata to aicsimageio's writer; here its XML (if it has one) rides in the description
-        xml = metadata.to_xml() if hasattr(metadata, "to_xml") else (metadata if isinstance(metadata, (str, bytes)) else None)
-        if xml is None:
-            import warnings
-            warnings.warn("save_tiff: metadata of type %s is not written (no OME-XML writer here)" % type(metadata).__name__)
-        else:
-            desc = desc[:-1] + b"\n" + (xml if isinstance(xml, bytes) else xml.encode("utf-8", "replace")) + b"\0"
-    desc += b"\0" * (len(desc) & 1)                       # TIFF 6.0: every IFD starts on a word boundary
-    if compression == "zlib":
-        return _save_tiff_zlib(path, planes, desc, predictor, rowsperstrip)
-    plane_bytes = rows * cols * planes.dtype.itemsize
-    pad = plane_bytes & 1                                   # (odd-sized uint8 planes)
-    if planes.nbytes + planes.shape[0] * 256 + len(desc) >= 2 ** 32:
-        raise ValueError("save_tiff: classic TIFF holds less than 4 GiB; split the movie")
-    with open(path, "wb") as fh:
-        fh.write(struct.pack("<2sHI", b"II", 42, 8))
-        offset = 8
-        for k in range(planes.shape[0]):
-            entries = [(256, 4, 1, cols), (257, 4, 1, rows), (258, 3, 1, bits), (259, 3, 1, 1), (262, 3, 1, 1),
-                       (277, 3, 1, 1), (278, 4, 1, rows), (279, 4, 1, rows * cols * planes.dtype.itemsize), (339, 3, 1, fmt)]
-            extra = desc if k == 0 else b""
-            ifd_size = 2 + 12 * (len(entries) + 1 + (1 if extra else 0)) + 4
-            data_at = offset + ifd_size + len(extra)
-            entries.append((273, 4, 1, data_at))
-            if extra:
-                entries.append((270, 2, len(extra), offset + ifd_size))
-            entries.sort()
-            nxt = data_at + plane_bytes + pad if k + 1 < planes.shape[0] else 0
-            fh.write(struct.pack("<H", len(entries)))
-            for tag, typ, cnt, val in entries:
-                fh.write(struct.pack("<HHII", tag, typ, cnt, val))
-            fh.write(struct.pack("<I", nxt))
-            fh.write(extra)
-            fh.write(planes[k].tobytes())
-            fh.write(b"\0" * pad)
-            offset = nxt
-    return
-
-
-def _save_tiff_zlib(path, planes, desc, predictor, rowsperstrip):
-    """save_tiff's deflate form: per page the strip offsets and byte counts follow the IFD, then the strips (zlib streams)."""
-    import os
-    import struct
-    import zlib
-    if planes.dtype not in (np.uint8, np.uint16):
-        raise TypeError("save_tiff: compression='zlib' writes uint8 / uint16 pages (got %s)" % planes.dtype)
-    n_pages, rows, cols = planes.shape
-    item = planes.dtype.itemsize
-    if rowsperstrip is None:
-        rowsperstrip = max(1, min(rows, 65536 // max(1, cols * item)))
-    rowsperstrip = int(rowsperstrip)
-    if rowsperstrip < 1:
-        raise ValueError("save_tiff: rowsperstrip %d" % rowsperstrip)
-    rowsperstrip = min(rowsperstrip, rows)
-    n_strips = -(-rows // rowsperstrip)
-    from concurrent.futures import ThreadPoolExecutor
-    threads = max(1, min(16, os.cpu_count() or 1))
-
-    def page_strips(k):
-        plane = planes[k]
-        if predictor == 2:
-            plane = np.concatenate([plane[:, :1], np.diff(plane, axis=1)], axis=1).astype(planes.dtype)      # modulo 2^bits
-        return [plane[r:r + rowsperstrip] for r in range(0, rows, rowsperstrip)]
-
-    # (zlib releases the interpreter lock: the strips of a few pages are compressed side by side; the file does not depend on it)
-    with open(path, "wb") as fh, ThreadPoolExecutor(threads) as pool:
-        fh.write(struct.pack("<2sHI", b"II", 42, 8))
-        offset = 8
-        done = {}
-        for k in range(n_pages):
-            if k not in done:
-                ahead = range(k, min(n_pages, k + max(1, threads // n_strips)))
-                raw = [part for j in ahead for part in page_strips(j)]
-                out = list(pool.map(lambda part: zlib.compress(part.tobytes(), 6), raw))
-                done = {j: out[i * n_strips:(i + 1) * n_strips] for i, j in enumerate(ahead)}
-            strips = done[k]
-            sizes = [len(s) for s in strips]
-            strips = [s + b"\0" * (len(s) & 1) for s in strips]           # (every strip starts on a word boundary)
-            extra = desc if k == 0 else b""
-            entries = [(256, 4, 1, cols), (257, 4, 1, rows), (258, 3, 1, item * 8), (259, 3, 1, 8), (262, 3, 1, 1), (277, 3, 1, 1),
-                       (278, 4, 1, rowsperstrip), (339, 3, 1, 1)]
-            if predictor == 2:
-                entries.append((317, 3, 1, 2))
-            ifd_size = 2 + 12 * (len(entries) + 2 + (1 if extra else 0)) + 4
-            tables_at = offset + ifd_size                                   # offsets, then byte counts: LONGs (inline when one strip)
-            table_bytes = 8 * n_strips if n_strips > 1 else 0
-            extra_at = tables_at + table_bytes
-            data_at = extra_at + len(extra)
-            starts = [data_at + sum(len(s) for s in strips[:i]) for i in range(n_strips)]
-            end = data_at + sum(len(s) for s in strips)
-            if end >= 2 ** 32:
-                raise ValueError("save_tiff: classic TIFF holds less than 4 GiB; split the movie")
-            entries.append((273, 4, n_strips, tables_at if n_strips > 1 else starts[0]))
-            entries.append((279, 4, n_strips, tables_at + 4 * n_strips if n_strips > 1 else sizes[0]))
-            if extra:
-                entries.append((270, 2, len(extra), extra_at))
-            entries.sort()
-            nxt = end if k + 1 < n_pages else 0
-            fh.write(struct.pack("<H", len(entries)))
-            for tag, typ, cnt, val in entries:
-                fh.write(struct.pack("<HHII", tag, typ, cnt, val))
-            fh.write(struct.pack("<I", nxt))
-            if n_strips > 1:
-                fh.write(struct.pack("<%dI" % n_strips, *starts) + struct.pack("<%dI" % n_strips, *sizes))
-            fh.write(extra)
-            fh.write(b"".join(strips))
-            offset = nxt
-    return
-
-
-def write_tiff_strips(path, shape, axes, dtype, rowsperstrip, pages, bigtiff=None):
-    """A deflate-strip TIFF from strips that are compressed ALREADY (movie.export_tiff: zlib streams made on the GPUs).  shape: the
-    whole array's, (..., Y, X), every leading index one page in C order; dtype uint8 or uint16; `pages` yields, per page, the list
-    of its finished strip streams (one per `rowsperstrip` rows, the last strip the rows that are left).  Pages are written as they
-    arrive; nothing but the current page is held.
-
-    The layout is save_tiff(compression="zlib")'s: little-endian, Compression 8, no Predictor tag, per page the strip offsets and
-    byte counts behind the IFD (inline for one strip), then the strips on word boundaries; "axes=... shape=..." in page 0's
-    ImageDescription.  bigtiff=True writes BigTIFF (magic 43, 8-byte offsets and counts); None chooses it when the classic form
-    would reach 4 GiB -- from the strips themselves when `pages` is a list, otherwise, the sizes not being known before the first
-    page is written, from the uncompressed size.  A classic file that reaches 4 GiB after all raises ValueError."""
-    import struct
-    dtype = np.dtype(dtype)
-    if dtype not in (np.uint8, np.uint16):
-        raise TypeError("write_tiff_strips writes uint8 / uint16 pages (got %s)" % dtype)
-    shape = tuple(int(v) for v in shape)
-    if len(shape) < 2 or min(shape) < 1:
-        raise ValueError("write_tiff_strips needs a shape (..., Y, X) of positive extents, not %r" % (shape,))
-    rows, cols = shape[-2:]
-    n_pages = int(np.prod(shape[:-2], dtype=np.int64))
-    rowsperstrip = int(rowsperstrip)
-    if rowsperstrip < 1:
-        raise ValueError("write_tiff_strips: rowsperstrip %d" % rowsperstrip)
-    rowsperstrip = min(rowsperstrip, rows)
-    n_strips = -(-rows // rowsperstrip)
-    desc = ("axes=%s shape=%s" % (axes, "x".join(str(v) for v in shape))).encode("ascii") + b"\0"
-    desc += b"\0" * (len(desc) & 1)
-    if bigtiff is None:
-        if isinstance(pages, (list, tuple)):
-            payload = sum(len(s) + (len(s) & 1) for page in pages for s in page)
-        else:
-            payload = n_pages * rows * cols * dtype.itemsize
-        bigtiff = payload + len(desc) + 16 + n_pages * (16 + 20 * 11 + 16 * n_strips) >= 2 ** 32      # (the larger form's tables)
-    big = bool(bigtiff)
-    # classic: 2-byte entry count, 12-byte entries, LONG (4) offsets; BigTIFF: 8-byte count, 20-byte entries, LONG8 (16) offsets
-    cnt_fmt, ent_fmt, off_fmt, off_type, word = ("<Q", "<HHQQ", "Q", 16, 8) if big else ("<H", "<HHII", "I", 4, 4)
-    written = 0
-    with open(path, "wb") as fh:
-        fh.write(struct.pack("<2sHHHQ", b"II", 43, 8, 0, 16) if big else struct.pack("<2sHI", b"II", 42, 8))
-        offset = 16 if big else 8
-        for k, strips in enumerate(pages):
-            if k >= n_pages:
-                raise ValueError("write_tiff_strips: more than the %d pages of shape %r" % (n_pages, shape))
-            strips = [bytes(s) for s in strips]
-            if len(strips) != n_strips:
-                raise ValueError("write_tiff_strips: page %d came with %d strips, not %d" % (k, len(strips), n_strips))
-            sizes = [len(s) for s in strips]
-            extra = desc if k == 0 else b""
-            entries = [(256, 4, 1, cols), (257, 4, 1, rows), (258, 3, 1, dtype.itemsize * 8), (259, 3, 1, 8), (262, 3, 1, 1), (277, 3, 1, 1),
-                       (278, 4, 1, rowsperstrip), (339, 3, 1, 1)]
-            ifd_size = struct.calcsize(cnt_fmt) + struct.calcsize(ent_fmt) * (len(entries) + 2 + (1 if extra else 0)) + word
-            tables_at = offset + ifd_size                                   # offsets, then byte counts (inline when one strip)
-            table_bytes = 2 * word * n_strips if n_strips > 1 else 0
-            extra_at = tables_at + table_bytes
-            data_at = extra_at + len(extra)
-            starts, at = [], data_at
-            for n in sizes:
-                starts.append(at)
-                at += n + (n & 1)                                           # (every strip starts on a word boundary)
-            end = at
-            if not big and end >= 2 ** 32:
-                raise ValueError("write_tiff_strips: classic TIFF holds less than 4 GiB; pass bigtiff=True")
-            entries.append((273, off_type, n_strips, tables_at if n_strips > 1 else starts[0]))
-            entries.append((279, off_type, n_strips, tables_at + word * n_strips if n_strips > 1 else sizes[0]))
-            if extra:
-                entries.append((270, 2, len(extra), extra_at))
-            entries.sort()
-            nxt = end if k + 1 < n_pages else 0
-            fh.write(struct.pack(cnt_fmt, len(entries)))
-            for entry in entries:
-                fh.write(struct.pack(ent_fmt, *entry))
-            fh.write(struct.pack("<" + off_fmt, nxt))
-            if n_strips > 1:
-                fh.write(struct.pack("<%d%s" % (n_strips, off_fmt), *starts) + struct.pack("<%d%s" % (n_strips, off_fmt), *sizes))
-            fh.write(extra)
-            for s in strips:
-                fh.write(s + b"\0" * (len(s) & 1))
-            offset = end
-            written += 1
-    if written != n_pages:
-        raise ValueError("write_tiff_strips: %d pages arrived for shape %r (%d pages)" % (written, shape, n_pages))
-    return path
-
-
 # ---- image sources and the chunk iterator (bim.py:28-159, 478-495) -------------------------------------------------------
 # The reference opens everything through aicsimageio (absent in this image).  Here an image source is anything that can
 # say its (T, C, Z, Y, X) extents and hand out 5-D sub-blocks:
 #   * a numpy array / memmap of rank 5 (TCZYX), or a list / tuple of them (one per scene = microscope position);
-#   * a path to a .npy file (memory-mapped) or to a TIFF stack of uncompressed or deflate strips (the reader below, lazy:
+#   * a path to a .npy file (memory-mapped) or to a TIFF stack of uncompressed or deflate strips (tiff.TiffSource, lazy:
 #     only the pages a block needs are decoded; axes from save_tiff's, tifffile's or ImageJ's ImageDescription);
 #   * an object with aicsimageio's interface (set_scene, dims, get_image_dask_data) -- a real AICSImage where that
 #     package is installed; any other path is handed to aicsimageio and fails loudly without it.
@@ -613,7 +383,7 @@ def open_image(source, series=0):
             arr = np.load(path, mmap_mode="r")
             src = _ArraySource([_as_tczyx(arr, "TCZYX"[5 - arr.ndim:])])
         elif ext in (".tif", ".tiff"):
-            src = _TiffSource(path)
+            src = TiffSource(path)
         else:
             try:
                 from aicsimageio import AICSImage
@@ -667,258 +437,6 @@ def read_image_in_chunks(path, series=0, dx=0, dy=0, dz=0, dc=0, dt=0, apply_fun
                             box = tuple(slice(p, q) for p, q in zip(a, b))
                             out[box] = np.reshape(res, [q - p for p, q in zip(a, b)])
                         yield result
-
-
-def _tiff_axes_from_description(desc, npages, rows, cols):
-    """(axes, shape) from the first page's ImageDescription: save_tiff's "axes=... shape=...", tifffile's own JSON
-    {"shape": [...], "axes": "..."}, ImageJ's hyperstack keys, else a plain page stack."""
-    import re
-    if desc.startswith("{"):
-        import json
-        try:
-            meta = json.loads(desc)
-        except ValueError:
-            meta = None
-        if isinstance(meta, dict) and isinstance(meta.get("shape"), list) and all(isinstance(v, int) for v in meta["shape"]):
-            shape, axes = tuple(meta["shape"]), meta.get("axes")
-            if int(np.prod(shape)) == npages * rows * cols and shape[-2:] == (rows, cols):
-                if not (isinstance(axes, str) and len(axes) == len(shape)):
-                    axes = "Q" * (len(shape) - 2) + "YX"      # (tifffile's name for axes it was not told)
-                return axes.upper(), shape
-    m = re.search(r"axes=([A-Za-z]*) shape=([0-9x]+)", desc)
-    if m and m.group(2):
-        shape = tuple(int(v) for v in m.group(2).split("x"))
-        if int(np.prod(shape)) == npages * rows * cols:
-            return m.group(1).upper(), shape
-    if desc.startswith("ImageJ="):
-        keys = dict(line.split("=", 1) for line in desc.splitlines() if "=" in line)
-        t, z, c = int(keys.get("frames", 1)), int(keys.get("slices", 1)), int(keys.get("channels", 1))
-        if t * z * c == npages:
-            axes, shape = "", ()
-            for name, n in (("T", t), ("Z", z), ("C", c)):
-                if n > 1:
-                    axes += name
-                    shape += (n,)
-            return axes + "YX", shape + (rows, cols)
-    if npages > 1:
-        return "QYX", (npages, rows, cols)           # (tifffile's name for an unknown page axis)
-    return "YX", (rows, cols)
-
-
-TIFF_DEFLATE = (8, 32946)          # Compression: Adobe deflate and the legacy code; both are zlib streams (RFC 1950), one per strip
-
-
-class TiffPage(object):
-    """One IFD of a strip-organised TIFF, as tiff_page_table reads it: no pixel data."""
-    __slots__ = ("index", "cols", "rows", "bits", "sample_format", "samples", "compression", "predictor", "rows_per_strip",
-                 "offsets", "counts", "tiled", "description")
-
-    @property
-    def strips(self):
-        return -(-self.rows // self.rows_per_strip)
-
-    def strip_rows(self, k):
-        return min(self.rows_per_strip, self.rows - k * self.rows_per_strip)
-
-
-class TiffTable(object):
-    """tiff_page_table's result: the pages, the file's byte order ("<" or ">"), classic or BigTIFF, and the memory map the
-    offsets point into."""
-
-    def __init__(self, path, buf, byte_order, big, pages):
-        self.path, self.buf, self.byte_order, self.big, self.pages = path, buf, byte_order, big, pages
-
-    @property
-    def description(self):
-        return self.pages[0].description if self.pages else ""
-
-
-def tiff_page_table(path):
-    """The IFDs of a TIFF / BigTIFF file through a memory map -- extents, bits, sample format, compression, predictor, rows per
-    strip, strip offsets and byte counts per page; the file's byte order and flavour -- without touching pixel data."""
-    import mmap
-    import struct
-    with open(path, "rb") as fh:
-        try:
-            buf = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
-        except ValueError:
-            buf = b""                         # (an empty file cannot be mapped)
-    if len(buf) < 8 or buf[:2] not in (b"II", b"MM"):
-        raise ValueError("%s is not a TIFF file" % path)
-    bo = "<" if buf[:2] == b"II" else ">"
-    magic, = struct.unpack(bo + "H", buf[2:4])
-    if magic == 42:                       # classic: 4-byte offsets, 12-byte entries, 2-byte entry count
-        big, ifd = False, struct.unpack(bo + "I", buf[4:8])[0]
-    elif magic == 43:                     # BigTIFF: 8-byte offsets, 20-byte entries, 8-byte entry count
-        big, ifd = True, struct.unpack(bo + "Q", buf[8:16])[0]
-    else:
-        raise ValueError("%s: not a TIFF / BigTIFF file (magic %d)" % (path, magic))
-    sizes = {1: 1, 2: 1, 3: 2, 4: 4, 6: 1, 8: 2, 9: 4, 16: 8, 17: 8}
-    codes = {1: "B", 3: "H", 4: "I", 6: "b", 8: "h", 9: "i", 16: "Q", 17: "q"}
-    cnt_fmt, ent_size, inline, off_fmt = ("Q", 20, 8, "Q") if big else ("H", 12, 4, "I")
-    pages = []
-    while ifd:
-        hdr = struct.calcsize(cnt_fmt)
-        n, = struct.unpack(bo + cnt_fmt, buf[ifd:ifd + hdr])
-        tags = {}
-        for k in range(n):
-            e = buf[ifd + hdr + ent_size * k: ifd + hdr + ent_size * (k + 1)]
-            tag, typ = struct.unpack(bo + "HH", e[:4])
-            cnt, = struct.unpack(bo + off_fmt, e[4:4 + inline])
-            raw = e[4 + inline:]
-            if typ not in sizes:
-                continue
-            nbytes = sizes[typ] * cnt
-            at = struct.unpack(bo + off_fmt, raw)[0] if nbytes > inline else 0
-            data = raw[:nbytes] if nbytes <= inline else buf[at:at + nbytes]
-            tags[tag] = bytes(data) if typ == 2 else struct.unpack(bo + "%d%s" % (cnt, codes[typ]), data)
-        ifd, = struct.unpack(bo + off_fmt, buf[ifd + hdr + ent_size * n: ifd + hdr + ent_size * n + inline])
-        pg = TiffPage()
-        pg.index = len(pages)
-        pg.cols, pg.rows, pg.bits = tags[256][0], tags[257][0], tags.get(258, (1,))[0]
-        pg.sample_format, pg.samples = tags.get(339, (1,))[0], tags.get(277, (1,))[0]
-        pg.compression, pg.predictor = tags.get(259, (1,))[0], tags.get(317, (1,))[0]
-        pg.tiled = 322 in tags or 324 in tags
-        pg.rows_per_strip = max(1, min(tags.get(278, (pg.rows,))[0], pg.rows))
-        pg.offsets = tags.get(273, ())
-        pg.counts = tags.get(279, (pg.rows * pg.cols * (pg.bits // 8),) if len(pg.offsets) == 1 else ())
-        pg.description = tags[270].split(b"\0")[0].decode("latin-1") if 270 in tags else ""
-        pages.append(pg)
-    return TiffTable(path, buf, bo, big, pages)
-
-
-def _tiff_check_page(path, pg):
-    """What is read here: strips of one sample per pixel, uncompressed (any 8 / 16 / 32 / 64-bit type) or deflate (8- and 16-bit
-    unsigned), predictor 1, or 2 on 8- and 16-bit unsigned.  Anything else raises with the tag value met."""
-    where = "%s: page %d" % (path, pg.index)
-    if pg.tiled:
-        raise ValueError("%s is tiled (TileWidth / TileLength present); only strips are read here" % where)
-    if pg.samples != 1:
-        raise ValueError("%s: SamplesPerPixel %d; multi-sample pages are not read here" % (where, pg.samples))
-    if pg.compression != 1 and pg.compression not in TIFF_DEFLATE:
-        names = {5: "LZW", 6: "old JPEG", 7: "JPEG", 32773: "PackBits", 50000: "zstd", 34925: "LZMA"}
-        raise ValueError("%s: compression %d%s; only uncompressed (1) and deflate (8, 32946) strips are read here"
-                         % (where, pg.compression, " (%s)" % names[pg.compression] if pg.compression in names else ""))
-    if pg.predictor not in (1, 2):
-        raise ValueError("%s: predictor %d%s; only 1 (none) and 2 (horizontal differencing) are read here"
-                         % (where, pg.predictor, " (floating point)" if pg.predictor == 3 else ""))
-    plain = pg.compression == 1 and pg.predictor == 1
-    if not plain and not (pg.sample_format == 1 and pg.bits in (8, 16)):
-        raise ValueError("%s: compressed or differenced pages are read as 8- or 16-bit unsigned only (BitsPerSample %d, SampleFormat %d)"
-                         % (where, pg.bits, pg.sample_format))
-    if pg.sample_format not in (1, 2, 3) or pg.bits not in (8, 16, 32, 64):
-        raise ValueError("%s: BitsPerSample %d, SampleFormat %d are not read here" % (where, pg.bits, pg.sample_format))
-    if not plain and (len(pg.offsets) != pg.strips or len(pg.counts) != pg.strips):
-        raise ValueError("%s: %d strip offsets and %d byte counts for %d strips" % (where, len(pg.offsets), len(pg.counts), pg.strips))
-
-
-def _tiff_page_dtype(table, pg):
-    return np.dtype("%s%s%d" % (table.byte_order, {1: "u", 2: "i", 3: "f"}[pg.sample_format], pg.bits // 8))
-
-
-def _tiff_decode_page(table, pg):
-    """Page pg as a (rows, cols) array in the FILE's byte order: strips joined (uncompressed) or inflated by zlib one by one, then
-    the horizontal predictor undone on native-order samples (libtiff's order: byte swap, then accumulate)."""
-    import zlib
-    dtype, buf = _tiff_page_dtype(table, pg), table.buf
-    if pg.compression == 1:
-        raw = b"".join(buf[o:o + c] for o, c in zip(pg.offsets, pg.counts))
-    else:
-        parts = []
-        for k, (o, c) in enumerate(zip(pg.offsets, pg.counts)):
-            want = pg.strip_rows(k) * pg.cols * dtype.itemsize
-            try:
-                part = zlib.decompress(buf[o:o + c])
-            except zlib.error as e:
-                raise ValueError("%s: page %d strip %d does not inflate: %s" % (table.path, pg.index, k, e))
-            if len(part) != want:
-                raise ValueError("%s: page %d strip %d inflates to %d bytes, not %d" % (table.path, pg.index, k, len(part), want))
-            parts.append(part)
-        raw = b"".join(parts)
-    plane = np.frombuffer(raw, dtype=dtype, count=pg.rows * pg.cols).reshape(pg.rows, pg.cols)
-    if pg.predictor == 2:
-        native = dtype.newbyteorder("=")
-        plane = np.cumsum(plane.astype(native), axis=1, dtype=native).astype(dtype)
-    return plane
-
-
-def _tiff_checked_table(path):
-    table = tiff_page_table(path)
-    if not table.pages:
-        raise ValueError("%s holds no image" % path)
-    first = table.pages[0]
-    for pg in table.pages:
-        _tiff_check_page(path, pg)
-        if (pg.rows, pg.cols, pg.bits, pg.sample_format) != (first.rows, first.cols, first.bits, first.sample_format):
-            raise ValueError("%s: pages of different size or type" % path)
-    return table
-
-
-def read_tiff(path):
-    """bim.py:28-51: (image, axes, shape, metadata) of a TIFF file.  Self-contained reader for what this package, ImageJ and
-    tifffile's defaults write -- classic TIFF and BigTIFF, either byte order, strips of one sample per pixel: uncompressed 8 / 16 /
-    32-bit unsigned, signed or float pages, or deflate (compression 8 / 32946, inflated with the standard library's zlib) 8- and
-    16-bit unsigned pages, with predictor 1 or 2; pages of one size.  Anything else raises ValueError naming the tag value met."""
-    table = _tiff_checked_table(path)
-    pages = [_tiff_decode_page(table, pg) for pg in table.pages]
-    rows, cols = pages[0].shape
-    desc = table.description
-    axes, shape = _tiff_axes_from_description(desc, len(pages), rows, cols)
-    image = np.stack(pages).astype(pages[0].dtype.newbyteorder("=")).reshape(shape)
-    metadata = dict(line.split("=", 1) for line in desc.splitlines() if "=" in line) if desc.startswith("ImageJ=") else None
-    return image, axes, image.shape, metadata
-
-
-class _TiffSource(object):
-    """A TIFF stack as a lazy image source: dims from the page table, block() decodes only the pages it is asked for.  The
-    description's axes say which page holds which (t, c, z) -- TCZ, ImageJ's TZC or any other order of the page axes."""
-
-    def __init__(self, path):
-        self.table = _tiff_checked_table(path)
-        first = self.table.pages[0]
-        axes, shape = _tiff_axes_from_description(self.table.description, len(self.table.pages), first.rows, first.cols)
-        axes = axes if axes else "TCZYX"[5 - len(shape):]
-        if (len(axes) != len(shape) or any(a not in "TCZYX" for a in axes) or len(set(axes)) != len(axes) or axes[-2:] != "YX"):
-            raise ValueError("axes %r do not describe an array of rank %d" % (axes, len(shape)))
-        self.axes, self.shape = axes, tuple(int(v) for v in shape)
-        self.page_axes, self.page_shape = axes[:-2], self.shape[:-2]
-        self.dtype = _tiff_page_dtype(self.table, first).newbyteorder("=")
-        self._decoded = {}            # the pages of the last block(): the chunk iterator asks for the same pages x by x, y by y
-
-    def set_scene(self, series):
-        if series != 0:
-            raise IndexError("scene %d of 1" % series)
-
-    @property
-    def dims(self):
-        ext = dict(zip(self.axes, self.shape))
-        return ImageDims(*[ext.get(a, 1) for a in "TCZYX"])
-
-    def page_index(self, t, c, z):
-        """the page that holds plane (t, c, z)"""
-        at = dict(T=t, C=c, Z=z)
-        k = 0
-        for a, n in zip(self.page_axes, self.page_shape):
-            k = k * n + at[a]
-        return k
-
-    def block(self, t, c, z, y, x):
-        d = self.dims
-        ts, cs, zs = (range(*s.indices(n)) if isinstance(s, slice) else [s] for s, n in zip((t, c, z), d[:3]))
-        last, self._decoded = self._decoded, {}
-
-        def plane(ti, ci, zi):
-            k = self.page_index(ti, ci, zi)
-            if k not in self._decoded:
-                self._decoded[k] = last[k] if k in last else _tiff_decode_page(self.table, self.table.pages[k])
-            return self._decoded[k]
-
-        planes = [[[plane(ti, ci, zi)[y, x] for zi in zs] for ci in cs] for ti in ts]
-        out = np.array(planes, dtype=self.dtype)
-        for axis, s in reversed(list(enumerate((t, c, z)))):
-            if not isinstance(s, slice):
-                out = out.squeeze(axis)           # an integer index drops its axis, as on an array
-        return out
 
 
 def concatenate_time_points(files):
@@ -1007,52 +525,11 @@ def extract_all_frames_from_a_scene(path, scene_index, max_frames=None):
     return 0
 
 
-class _BigTiffAppender(object):
-    """Streaming BigTIFF writer (magic 43, 8-byte offsets): every (Y, X) plane appended becomes one page -- uncompressed,
-    min-is-black, one strip -- so a movie larger than memory (or than classic TIFF's 4 GiB) can be written frame by frame."""
-
-    def __init__(self, path):
-        import struct
-        self._s = struct
-        self.fh = open(path, "wb")
-        self.fh.write(struct.pack("<2sHHHQ", b"II", 43, 8, 0, 0))       # the first-IFD offset (bytes 8..15) is patched later
-        self.link = 8                                                  # file position of the pointer to the next IFD
-
-    def write_plane(self, plane):
-        s = self._s
-        plane = np.ascontiguousarray(plane)
-        if plane.ndim != 2 or plane.dtype not in (np.uint8, np.uint16, np.float32, np.int32):
-            raise TypeError("BigTIFF pages are 2-D uint8 / uint16 / int32 / float32 planes (got %s %s)" % (plane.dtype, plane.shape))
-        rows, cols = plane.shape
-        raw = plane.astype(plane.dtype.newbyteorder("<")).tobytes()
-        at = self.fh.seek(0, 2)
-        at += (-at) % 8
-        self.fh.seek(at)
-        self.fh.write(raw)
-        ifd = at + len(raw)
-        ifd += (-ifd) % 8
-        fmt = 3 if plane.dtype.kind == "f" else (2 if plane.dtype.kind == "i" else 1)
-        entries = [(256, 4, 1, cols), (257, 4, 1, rows), (258, 3, 1, plane.dtype.itemsize * 8), (259, 3, 1, 1), (262, 3, 1, 1),
-                   (273, 16, 1, at), (277, 3, 1, 1), (278, 4, 1, rows), (279, 16, 1, len(raw)), (339, 3, 1, fmt)]
-        self.fh.seek(ifd)
-        self.fh.write(s.pack("<Q", len(entries)))
-        for tag, typ, cnt, val in entries:
-            self.fh.write(s.pack("<HHQQ", tag, typ, cnt, val))
-        nxt = self.fh.tell()
-        self.fh.write(s.pack("<Q", 0))
-        self.fh.seek(self.link)
-        self.fh.write(s.pack("<Q", ifd))
-        self.link = nxt
-
-    def close(self):
-        self.fh.close()
-
-
 def virtually_concatenate_time_points(files, position_indices, output_path="output.tif"):
     """bim.py:511-520: stream every time point of scene `position_indices[i] - 1` of `files[i]` into one BigTIFF, one
     (Z, C, Y, X) frame at a time (upstream: tifffile.TiffWriter(bigtiff=True).write per frame): pages in frame, z, channel
     order."""
-    out = _BigTiffAppender(output_path)
+    out = BigTiffAppender(output_path)
     try:
         for path, scene in zip(files, position_indices):
             for frame in extract_all_frames_from_a_scene(path, scene - 1):

@@ -109,16 +109,17 @@ def tiff_frame_source(path, series=0, decode="auto", backend="gpu"):
     "device" when a GPU backend consumes the frames (backend="gpu"), the file is 16-bit deflate strips and a frame holds at
     least AUTO_DEVICE_MIN_STRIPS strips' worth of parallel work, else "host"; 8-bit files are converted on the host.  The source carries `dims` (T, C, Z, Y, X), `decode` and `n_frames`."""
     import threading
-    from . import basic_image_manipulations as bim
+    from . import tiff
+    from .basic_image_manipulations import open_image
     if decode not in ("auto", "host", "device"):
         raise ValueError("decode must be 'auto', 'host' or 'device', not %r" % (decode,))
-    src = bim.open_image(path, series)
-    if not isinstance(src, bim._TiffSource):
+    src = open_image(path, series)
+    if not isinstance(src, tiff.TiffSource):
         raise ValueError("tiff_frame_source: %r is not a TIFF stack" % (path,))
     T, C, Z, Y, X = src.dims
     table = src.table
     first = table.pages[0]
-    device_ok = first.bits == 16 and first.sample_format == 1 and all(pg.compression in bim.TIFF_DEFLATE for pg in table.pages)
+    device_ok = first.bits == 16 and first.sample_format == 1 and all(pg.compression in tiff.TIFF_DEFLATE for pg in table.pages)
     if decode == "device" and not device_ok:
         raise ValueError("tiff_frame_source: decode='device' needs 16-bit unsigned deflate strips (%s has BitsPerSample %d, compression %d)"
                          % (path, first.bits, first.compression))
@@ -1018,11 +1019,11 @@ def export_tiff(path, n_frames, backend, ids, rank=0, world=1, dist=None, device
     Rank 0 hands the owners the track ids of their frames (one broadcast).  Each owner turns its frames' resident maps into uint16
     pages and those into one zlib stream per strip on its GPU (backend.export_page_strips: tip_export_maps_u16_dev, then
     tip_deflate_strips_dev) -- no map reaches the host uncompressed.  The strips travel to rank 0 as records in one gather
-    (_collectives.gather_varlen), and rank 0 writes them with basic_image_manipulations.write_tiff_strips, which it tells every
+    (_collectives.gather_varlen), and rank 0 writes them with tiff.write_tiff_strips, which it tells every
     strip's size, so bigtiff=None gives BigTIFF exactly when the classic file would reach 4 GiB.  Rank 0 holds the movie's
     compressed strips once.
 
-    rowsperstrip: None = as many rows as 65536 bytes hold, max(1, min(Y, 65536 // (2 X))) -- the most the strip encoder takes;
+    rowsperstrip: None = tiff.default_rows_per_strip(Y, 2 X), as many rows as 64 KB hold -- the most the strip encoder takes;
     codes: "dynamic" (per-strip Huffman codes where they are shorter) or "fixed".  The file does not depend on the world size.
     ValueError on EVERY rank, before anything is written, when a frame was not processed by its owner's backend or holds a track
     id outside [0, 65535] (the owners all-gather what they found first); ValueError on the owner when ids do not cover a frame's

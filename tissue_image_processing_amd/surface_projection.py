@@ -163,7 +163,8 @@ def movie_surface_projection(files, reference_channel, position_final_movie, ini
     scene numbers of the ones behind it, as upstream.  rank / world: shard the time points over processes (one per GPU);
     rank 0 writes the outputs."""
     import os
-    from .basic_image_manipulations import get_image_dimensions, concatenate_time_points, save_tiff
+    from .basic_image_manipulations import get_image_dimensions, concatenate_time_points
+    from .tiff import save_tiff
     positions = list(range(initial_positions_number))
     time_points_number = np.zeros((initial_positions_number, len(files)))
     projection_files = [[] for _ in range(initial_positions_number)]
@@ -258,7 +259,8 @@ def large_image_projection(input_dir, output_dir, input_file_name, position=1, r
     halo-less tiler: every block is projected on its own -- and write `<name>[_positionN]_projection.tif` (uint16) and
     `<name>[_positionN]_zmap.npy`.  Returns 0 when the input does not exist, as upstream."""
     import os
-    from .basic_image_manipulations import get_image_dimensions, save_tiff
+    from .basic_image_manipulations import get_image_dimensions
+    from .tiff import save_tiff
     several = hasattr(position, "__len__")
     path = os.path.join(input_dir, input_file_name)
     if not os.path.exists(path):

@@ -2,7 +2,7 @@
 channel 0 the tracking labels, channel 1 the type map with 0 -> 2 and 255 -> 0 -- written from maps that never leave their GPU
 uncompressed: csrc/tip_export.hip turns a frame's resident label and type map into uint16 pages, csrc/tip_deflate.hip's strip
 entry turns the pages into one zlib stream per TIFF strip, only the streams are downloaded, and
-basic_image_manipulations.write_tiff_strips puts them behind their IFDs (movie.export_tiff, and the Tissue mixin's
+tiff.write_tiff_strips puts them behind their IFDs (movie.export_tiff, and the Tissue mixin's
 compression="device")."""
 import numpy as np
 
@@ -26,9 +26,10 @@ class PageEncoder(object):
         holds and for a label the ids do not cover."""
         from . import _lib
         from ._deflate import deflate_strips_dev, export_maps_u16_dev, split_strips, strips_bound
+        from .tiff import StripGeometry
         Y, X = self.Y, self.X
         n_pages = 1 if types_ptr is None else 2
-        rps = min(int(rowsperstrip), Y)
+        rps = StripGeometry(Y, rowsperstrip).rows_per_strip
         cap = strips_bound(2, Y, 2 * X, rps)
         if self._pages is None:
             self._pages = _lib.DeviceBuffer(2 * Y * X * 2)
@@ -60,15 +61,15 @@ def record_as_strips(record, n_pages):
 
 def export_tiff(path, n_frames, backend, ids, rank=0, world=1, dist=None, device="cpu", rowsperstrip=None, codes="dynamic", bigtiff=None):
     """See movie.export_tiff."""
-    from .basic_image_manipulations import write_tiff_strips
-    from ._deflate import default_rows_per_strip, strip_codes
+    from ._deflate import strip_codes
+    from .tiff import StripGeometry, default_rows_per_strip, write_tiff_strips
     from .seg_archive import _ids_to_owners
     Y, X = int(backend.Y), int(backend.X)
     channels = 2 if getattr(backend, "cell_types", None) is not None else 1
     rps = default_rows_per_strip(Y, 2 * X) if rowsperstrip is None else int(rowsperstrip)
     if rps < 1:
         raise ValueError("export_tiff: rowsperstrip %d" % rps)
-    rps = min(rps, Y)
+    rps = StripGeometry(Y, rps).rows_per_strip
     strip_codes(codes)
     mine = _ids_to_owners(ids, n_frames, rank, world, dist, device)
     # a frame without its maps is every rank's error: the owners say which they lack before any of them encodes

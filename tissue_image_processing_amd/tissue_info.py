@@ -712,17 +712,17 @@ class TissueHipMixin(object):
     def _export_device_tiff(self, path, channels, frame_maps):
         """The export's compression="device": frame_maps(frame) -> (labels, ids, types or None) of a valid frame.  Every valid
         frame's maps go to the device as they are, become uint16 pages and zlib strips there (tiff_export.PageEncoder) and
-        basic_image_manipulations.write_tiff_strips appends them page by page; an invalid frame's pages are zeros, as upstream
+        tiff.write_tiff_strips appends them page by page; an invalid frame's pages are zeros, as upstream
         leaves them."""
         import zlib
         from . import tiff_export
-        from ._deflate import default_rows_per_strip
-        from .basic_image_manipulations import write_tiff_strips
+        from .tiff import StripGeometry, default_rows_per_strip, write_tiff_strips
         Y, X = self._export_frame_shape()
-        rps = default_rows_per_strip(Y, 2 * X)
+        strips = StripGeometry(Y, default_rows_per_strip(Y, 2 * X))
+        rps = strips.rows_per_strip
         encoder = tiff_export.PageEncoder(Y, X)
         d_labels, d_types = _lib.DeviceBuffer(Y * X * 4), _lib.DeviceBuffer(Y * X)
-        zero_page = [zlib.compress(bytes(min(rps, Y - r) * X * 2), 6) for r in range(0, Y, rps)]
+        zero_page = [zlib.compress(bytes(strips.strip_rows(k) * X * 2), 6) for k in range(strips.strips)]
 
         def pages():
             for frame in range(1, self.number_of_frames + 1):
@@ -756,7 +756,7 @@ class TissueHipMixin(object):
         frames stay zero.  compression=None writes it through save_tiff as upstream does; "device" writes the same array with
         deflate strips, pages and strips made on the GPU (tip_export_maps_u16_dev, tip_deflate_strips_dev)."""
         import os
-        from .basic_image_manipulations import save_tiff
+        from .tiff import save_tiff
         self._check_export_compression(compression)
         path = os.path.join(outfolder, filename + '.tif')
         if compression == "device":
@@ -779,7 +779,7 @@ class TissueHipMixin(object):
         """ti.py:4054-4062: T x 1 x 1 x Y x X uint16 of the frames' label maps (not the tracking labels); invalid frames stay zero.
         compression as in export_segmentation_and_cell_types_to_tiff; "device" takes labels up to 65535 (ValueError above)."""
         import os
-        from .basic_image_manipulations import save_tiff
+        from .tiff import save_tiff
         self._check_export_compression(compression)
         path = os.path.join(outfolder, filename + '.tif')
         if compression == "device":

@@ -52,8 +52,7 @@ def main():
     ap.add_argument("--host-json", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    from tissue_image_processing_amd import _lib, movie, synthetic
-    from tissue_image_processing_amd import basic_image_manipulations as bim
+    from tissue_image_processing_amd import _lib, movie, synthetic, tiff
     Y = X = args.size
     T, Z = args.frames, args.z
     sites_t, is_hc = synthetic.make_movie_sites(Y, X, T, seed=5)
@@ -68,7 +67,7 @@ def main():
             path, walls = os.path.join(tmp, name + ".tif"), []
             for rep in range(args.reps + 1):             # rep 0 is the warm-up
                 t0 = time.perf_counter()
-                bim.save_tiff(path, host_array(backend, ids, T, Y, X), axes="TCZYX", data_type="uint16", **kw)
+                tiff.save_tiff(path, host_array(backend, ids, T, Y, X), axes="TCZYX", data_type="uint16", **kw)
                 walls.append(time.perf_counter() - t0)
                 print("host %s rep %d: %.3f s" % (name, rep, walls[-1]), file=sys.stderr, flush=True)
             out["fetch_and_save_tiff_" + name] = {"wall_s": stats(walls[1:]), "file_bytes": os.path.getsize(path)}
@@ -92,15 +91,15 @@ def main():
             out["export_tiff_" + codes] = {"wall_s": stats(walls[codes][1:]), "file_bytes": os.path.getsize(path),
                                            "kernel_ms_per_movie": {k: stats(v[1:]) for k, v in kernels[codes].items()}}
         _lib.prof_enable(False)
-        image = bim.read_tiff(path)[0]
+        image = tiff.read_tiff(path)[0]
         np.testing.assert_array_equal(image, host_array(backend, ids, T, Y, X))      # (the timed file is the right one)
-        table = bim.tiff_page_table(path)
+        table = tiff.tiff_page_table(path)
         rps = table.pages[0].rows_per_strip
         planes = image.reshape(-1, Y, X)
         out["rows_per_strip"] = int(rps)
         out["zlib6_strip_bytes"] = int(sum(len(zlib.compress(p[r:r + rps].tobytes(), 6)) for p in planes for r in range(0, Y, rps)))
         for codes in ("fixed", "dynamic"):
-            strips = sum(sum(pg.counts) for pg in bim.tiff_page_table(os.path.join(tmp, codes + ".tif")).pages)
+            strips = sum(sum(pg.counts) for pg in tiff.tiff_page_table(os.path.join(tmp, codes + ".tif")).pages)
             out["export_tiff_" + codes]["strip_bytes"] = int(strips)
             out["export_tiff_" + codes]["strip_bytes_over_zlib6"] = round(strips / out["zlib6_strip_bytes"], 3)
             out["export_tiff_" + codes]["raw_over_strip_bytes"] = round(out["raw_bytes"] / strips, 2)

@@ -117,7 +117,7 @@ def main():
 
     # ---- this interpreter's tifffile on a file of write_tiff_strips ------------------------------------------------------------
     import tifffile
-    from tissue_image_processing_amd.basic_image_manipulations import write_tiff_strips
+    from tissue_image_processing_amd.tiff import write_tiff_strips
     planes = both["image"].reshape(-1, NY, NX)
     rps = 9
     pages = [[zlib.compress(p[r:r + rps].tobytes(), 6) for r in range(0, NY, rps)] for p in planes]

@@ -89,8 +89,7 @@ def main():
         print(json.dumps(result["auto_threshold"]))
         return
     import torch
-    from tissue_image_processing_amd import _inflate, _lib, movie, synthetic
-    from tissue_image_processing_amd import basic_image_manipulations as bim
+    from tissue_image_processing_amd import _inflate, _lib, movie, synthetic, tiff
     T, Y, X, Z, C = args.frames, args.size, args.size, args.z, 2
     sites_t, is_hc = synthetic.make_movie_sites(Y, X, T, seed=5)
     t0 = time.perf_counter()
@@ -103,7 +102,7 @@ def main():
                                ("one_strip_per_page_predictor2", 2, Y, min(args.distinct, T))):
         path = os.path.join(tmp, name + ".tif")
         t0 = time.perf_counter()
-        bim.save_tiff(path, np.stack(frames[:n]), axes="TCZYX", compression="zlib", predictor=pred, rowsperstrip=rps)
+        tiff.save_tiff(path, np.stack(frames[:n]), axes="TCZYX", compression="zlib", predictor=pred, rowsperstrip=rps)
         files[name] = (path, n)
         print("%s: %d frames, %.1f MB, written in %.1f s" % (name, n, os.path.getsize(path) / 1e6, time.perf_counter() - t0), flush=True)
     raw_bytes = C * Z * Y * X * 2
@@ -116,7 +115,7 @@ def main():
     d_raw = _lib.DeviceBuffer(raw_bytes)
     for name, (path, n) in files.items():
         src = movie.tiff_frame_source(path, decode="device")
-        table = bim.tiff_page_table(path)
+        table = tiff.tiff_page_table(path)
         rows = []
         for rep in range(2):                                   # the first pass over the file is the warm-up
             rows = []
