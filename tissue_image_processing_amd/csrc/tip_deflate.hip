@@ -673,7 +673,9 @@ __device__ static __forceinline__ void deflate_chunk(Rule &rule, const RowDists 
     const bool has_prev = t > 0 && nb > 0;
     const uint32_t prev = has_prev ? in[(t - 1) * DF_SEG_LD + 63] >> (32 - 8 * E) : 0u;      // the segment before is full
     const int lane = t & 63, wave = t >> 6;
-    // exclusive block scan of the bit counts: within the wave by shuffles, across the four waves through LDS
+    // exclusive block scan of the bit counts: within the wave by shuffles, across the four waves through LDS.  (This function keeps
+    // its scan and its three reductions by hand: with tip_wave.h's block_exclusive_scan and wave_reduce the compiler orders the
+    // code of the kernels around it differently, and these kernels are the archive's time.)
     auto scan = [&](uint32_t bits, uint32_t &before, uint32_t &total) {
         uint32_t incl = bits;
         for (int d = 1; d < 64; d <<= 1) {
@@ -908,32 +910,22 @@ __global__ __launch_bounds__(DF_THREADS) void k_deflate_strips(const uint8_t *__
 __global__ __launch_bounds__(256) void k_deflate_offsets(const uint32_t *__restrict__ sizes, long n, unsigned long *__restrict__ offsets,
                                                          unsigned long *__restrict__ total, int even, long *__restrict__ table)
 {
-    __shared__ unsigned long wave_sum[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    __shared__ unsigned long wave_sums[4];
+    const int t = threadIdx.x;
     unsigned long carry = 0;
     for (long c0 = 0; c0 < n; c0 += 256) {
         const unsigned long v = c0 + t < n ? (sizes[c0 + t] + (even ? 1ul : 0ul)) & ~(even ? 1ul : 0ul) : 0ul;
-        unsigned long incl = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long up = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        unsigned long before = 0, all = 0;
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) before += wave_sum[w];
-            all += wave_sum[w];
-        }
+        unsigned long all;
+        const unsigned long at = carry + block_exclusive_scan<4>(v, wave_sums, all);
         if (c0 + t < n) {
-            offsets[c0 + t] = carry + before + incl - v;
+            offsets[c0 + t] = at;
             if (table) {
-                table[2 * (c0 + t)] = (long)(carry + before + incl - v);
+                table[2 * (c0 + t)] = (long)at;
                 table[2 * (c0 + t) + 1] = (long)sizes[c0 + t];
             }
         }
         carry += all;
-        __syncthreads();                      // (the next step overwrites wave_sum)
+        __syncthreads();                      // (the next step overwrites wave_sums)
     }
     if (t == 0) {
         *total = carry;

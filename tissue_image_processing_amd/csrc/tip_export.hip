@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void k_export_maps_u16(const int32_t *__restri
             if (types) out[n + i] = (uint16_t)export_type(types[i]);
         }
     }
-    for (int d = 32; d >= 1; d >>= 1) bad += __shfl_xor(bad, d, 64);
+    bad = wave_sum(bad);
     if (bad && (threadIdx.x & 63u) == 0) atomicAdd(n_bad, (unsigned)bad);
 }
 

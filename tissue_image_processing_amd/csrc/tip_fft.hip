@@ -194,8 +194,7 @@ __global__ void __launch_bounds__(256) k_absargmax(const cplx *__restrict__ z, l
         const double m = hypot(z[i].x, z[i].y);   // np.abs of complex128 is hypot
         key = (unsigned long long)__double_as_longlong(m);
     }
-    unsigned long long wmax = key;
-    for (int d = 32; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(wmax, d, 64); wmax = o > wmax ? o : wmax; }
+    const unsigned long long wmax = wave_max(key);
     if ((threadIdx.x & 63) == 0) atomicMax(best_v, wmax);
     (void)best_i;
 }
@@ -274,7 +273,7 @@ __global__ void __launch_bounds__(64) k_updft2(const cplx *__restrict__ Ky, cons
         ax += w.x * d.x - w.y * d.y;
         ay += w.x * d.y + w.y * d.x;
     }
-    for (int d = 32; d >= 1; d >>= 1) { ax += __shfl_xor(ax, d, 64); ay += __shfl_xor(ay, d, 64); }
+    ax = wave_sum(ax); ay = wave_sum(ay);
     if (threadIdx.x == 0) out[(long)v * region + u] = make_double2(ax, -ay);
 }
 

@@ -80,11 +80,7 @@ struct WaveOut {
             w -= 64;
             if (w < 0) w += 65521;
         }
-        uint32_t a = (uint32_t)(s1 % 65521u), b = (uint32_t)(s2 % 65521u);
-        for (int m = 32; m; m >>= 1) {
-            a += (uint32_t)__shfl_xor((int)a, m, 64);
-            b += (uint32_t)__shfl_xor((int)b, m, 64);
-        }
+        const uint32_t a = wave_sum((uint32_t)(s1 % 65521u)), b = wave_sum((uint32_t)(s2 % 65521u));
         return tip_inflate::adler_from_sums(a % 65521u, b % 65521u, n);
     }
 };
@@ -122,10 +118,8 @@ __global__ __launch_bounds__(256) void k_inflate_count_bad(const int32_t *__rest
     __shared__ unsigned part[4];
     unsigned mine = 0;
     for (int i = (int)threadIdx.x; i < n_strips; i += 256) mine += status[i] != 0;
-    for (int m = 32; m; m >>= 1) mine += (unsigned)__shfl_xor((int)mine, m, 64);
-    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) *n_bad = part[0] + part[1] + part[2] + part[3];
+    mine = block_sum<4>(mine, part);
+    if (threadIdx.x == 0) *n_bad = mine;
 }
 
 // One wave per row, in place: each 16-bit sample's bytes swapped when the file's order is not the host's, then (predictor 2)
@@ -142,11 +136,7 @@ __global__ __launch_bounds__(256) void k_tiff_finish_u16(uint16_t *stack, long n
         uint32_t v = i < row_elems ? p[i] : 0u;
         if (swap) v = ((v & 0xFFu) << 8) | (v >> 8);
         if (predictor == 2) {
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t up = (uint32_t)__shfl_up((int)v, d, 64);
-                if (lane >= d) v += up;
-            }
-            v += carry;
+            v = wave_inclusive_scan(v) + carry;
             carry = (uint32_t)__shfl((int)v, 63, 64);
         }
         if (i < row_elems) p[i] = (uint16_t)v;

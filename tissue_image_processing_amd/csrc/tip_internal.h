@@ -188,20 +188,6 @@ int gaussian3d_dev(const void *in, void *out, int dtype, int Z, int Y, int X, co
 int rankfilter2d_dev(const void *in, void *out, int dtype, int Y, int X, int ky, int kx, int fp, int border, int is_max);   // tip_label.hip
 int watershed_dev(const double *img, int32_t *labels, int Y, int X, int wsl, int32_t *flags_host);                          // tip_watershed.hip
 
-// Called by whole wavefronts of a 1-D workgroup: f(key, count) runs once for every distinct key among the active lanes, on the
-// first lane that holds it, with the number of lanes that do -- so a wave pays one atomic or one store per key, not per lane.
-template <typename Key, typename F>
-__device__ __forceinline__ void wave_combine(bool active, Key key, F f)
-{
-    unsigned long long todo = __ballot(active);
-    const int lane = threadIdx.x & 63;
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const Key lk = __shfl(key, leader, 64);
-        const unsigned long long same = __ballot(active && key == lk) & todo;
-        if (lane == leader) f(lk, __popcll(same));
-        todo &= ~same;
-    }
-}
-
 }  // namespace tip
+
+#include "tip_wave.h"   // wave_combine, wave_reduce, wave_inclusive_scan, block_exclusive_scan, block_reduce: the device primitives

@@ -10,67 +10,32 @@
 namespace tip {
 
 // ---------------------------------------------------------------------------------------------------------
-// exclusive scan of int32 (three kernels: per-block scan, scan of block sums, add); the scan of the block sums alone is
-// scan_i32_dev, the scan of the neighbour graph, the Delaunay rows, the point grid and the track linker
+// exclusive scan of int32 (three kernels: per-block scan, scan of block sums, add), all on the block scan of tip_wave.h; the scan
+// of the block sums alone is scan_i32_dev, the scan of the neighbour graph, the Delaunay rows, the point grid and the track linker
 // ---------------------------------------------------------------------------------------------------------
-constexpr int SCAN_ITEMS = 8, SCAN_THREADS = 256, SCAN_BLOCK = SCAN_ITEMS * SCAN_THREADS;
-
 __global__ void __launch_bounds__(SCAN_THREADS) k_scan_block(const int *__restrict__ in, int *__restrict__ out, long n,
                                                              int *__restrict__ bsum)
 {
     __shared__ int wsum[SCAN_THREADS / 64];
-    const long base = (long)blockIdx.x * SCAN_BLOCK + (long)threadIdx.x * SCAN_ITEMS;
-    int v[SCAN_ITEMS], s = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        v[i] = base + i < n ? in[base + i] : 0;
-        s += v[i];
-    }
-    // wave inclusive scan of s
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
-    int run = woff + inc - s;
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        if (base + i < n) out[base + i] = run;
-        run += v[i];
-    }
-    if (threadIdx.x == SCAN_THREADS - 1) bsum[blockIdx.x] = run;
+    const int total = scan_tile_i32(in, out, (long)blockIdx.x * SCAN_BLOCK + (long)threadIdx.x * SCAN_ITEMS, n, wsum);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
 // out[i] = in[0] + ... + in[i - 1] for i = 0 .. n - 1 and *total = their sum (total may be NULL): one workgroup walks the array in
-// chunks of 1024 (Hillis-Steele in LDS) and carries the sum along.  in == out is allowed -- a thread reads its element before any
-// thread of the chunk writes -- so neither is __restrict__.  The scan of the block sums ("scan_sums") and scan_i32_dev.
+// chunks of 1024, one block scan per chunk, and every thread carries the sum along.  in == out is allowed -- a thread reads its
+// element before the scan's barrier and any thread of the chunk writes behind it -- so neither is __restrict__.  The scan of the
+// block sums ("scan_sums") and scan_i32_dev.
 __global__ void __launch_bounds__(1024) k_scan_one(const int *in, int *out, int n, int *total)
 {
-    __shared__ int s[1024];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
+    __shared__ int wsum[16];
+    int carry = 0;
     for (int base = 0; base < n; base += 1024) {
         const int i = base + threadIdx.x, v = i < n ? in[i] : 0;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const int t = (int)threadIdx.x >= off ? s[threadIdx.x - off] : 0;
-            __syncthreads();
-            s[threadIdx.x] += t;
-            __syncthreads();
-        }
-        const int incl = s[threadIdx.x], c = carry;
-        if (i < n) out[i] = c + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = c + incl;
-        __syncthreads();
+        int sum;
+        const int before = block_exclusive_scan<16>(v, wsum, sum);
+        if (i < n) out[i] = carry + before;
+        carry += sum;
+        __syncthreads();                            // (the next chunk writes wsum)
     }
     if (threadIdx.x == 0 && total) *total = carry;
 }
@@ -83,13 +48,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_add_own(int *__restrict__
     __shared__ int wsum[SCAN_THREADS / 64];
     int s = 0;
     for (int j = threadIdx.x; j < (int)blockIdx.x; j += SCAN_THREADS) s += bsum[j];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    int off = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN_THREADS / 64; ++w) off += wsum[w];
+    const int off = block_sum<SCAN_THREADS / 64>(s, wsum);
     if (total && (int)blockIdx.x == nb - 1 && threadIdx.x == 0) *total = off + bsum[nb - 1];
     const long base = (long)blockIdx.x * SCAN_BLOCK + (long)threadIdx.x * SCAN_ITEMS;
 #pragma unroll

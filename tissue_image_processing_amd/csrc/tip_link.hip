@@ -197,16 +197,11 @@ __global__ __launch_bounds__(64) void k_link_solve(const int *__restrict__ paren
                 const double c = __dsub_rn(__dsub_rn(__dadd_rn(min_val, cost[i * L_N + lane]), ui), vl);
                 if (c < spc) path = i, spc = c;
             }
-            double lowest = rem ? spc : L_INF;
-            for (int off = 32; off > 0; off >>= 1) lowest = fmin(lowest, __shfl_xor(lowest, off));
+            const double lowest = wave_reduce(rem ? spc : L_INF, [](double a, double b) { return fmin(a, b); });
             if (!(lowest < L_INF)) return;          // (an infeasible matrix: every row here has a finite entry)
             const bool tie = rem && spc == lowest;
             const bool any_free = __any(tie && row4col < 0);
-            int key = tie && (!any_free || row4col < 0) ? (any_free ? pos : -pos) : -0x7fffffff;
-            for (int off = 32; off > 0; off >>= 1) {
-                const int other = __shfl_xor(key, off);
-                key = other > key ? other : key;
-            }
+            const int key = wave_max(tie && (!any_free || row4col < 0) ? (any_free ? pos : -pos) : -0x7fffffff);
             const int index = any_free ? key : -key;
             const unsigned long long pick = __ballot(rem && pos == index);
             if (!pick) return;

@@ -31,10 +31,7 @@ __global__ void __launch_bounds__(256) k_argmax_first_f32(const float *__restric
         const unsigned long long k = ((unsigned long long)b << 32) | (unsigned long long)(0xffffffffu - (unsigned int)i);
         best = k > best ? k : best;
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(best, d, 64);
-        best = o > best ? o : best;
-    }
+    best = wave_max(best);
     if ((threadIdx.x & 63) == 0 && best) atomicMax(key, best);
 }
 

@@ -274,10 +274,8 @@ __global__ void __launch_bounds__(256) k_of_diff(const float *__restrict__ snap,
         const float d0 = snap[i] - u[i], d1 = snap[n + i] - u[n + i];
         s += (double)(d0 * d0) + (double)(d1 * d1);
     }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(acc, part[0] + part[1] + part[2] + part[3]);
+    s = block_sum<4>(s, part);                   // (the order of the additions is block_reduce's)
+    if (threadIdx.x == 0) atomicAdd(acc, s);
 }
 
 __global__ void k_of_check(const double *__restrict__ acc, double tol, int *__restrict__ done)

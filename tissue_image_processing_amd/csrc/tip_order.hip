@@ -159,8 +159,7 @@ __global__ __launch_bounds__(64) void k_delaunay(const PointGrid *__restrict__ g
             __syncthreads();
         }
         OSweep sw = sweep(kx, ky, ki, n_near, fits, start, g, rc, n_fin, sx, sy, sidx, xi, yi, i, lane, nullptr, 0, 0);
-        double reach = sw.reach;
-        for (int off = 32; off > 0; off >>= 1) reach = fmax(reach, __shfl_xor(reach, off));
+        double reach = wave_reduce(sw.reach, [](double a, double b) { return fmax(a, b); });
         if (sw.total == 0) reach = O_INF;
         const double span = (double)r * g.h;
         if (whole || 4.0 * reach * (1.0 + 1e-9) <= span * span) {

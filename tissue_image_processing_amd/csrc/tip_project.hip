@@ -26,17 +26,6 @@ struct ClipInfo {
     int has;
 };
 
-// inclusive prefix sum over the 64 lanes of a wave
-template <typename T>
-__device__ __forceinline__ T wave_inclusive_scan(T v, int lane)
-{
-    for (int d = 1; d < 64; d <<= 1) {
-        const T o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
 // ---- P2: histogram of the (offset-corrected, airy_offset) reference channel ------------------------------
 // One persistent 1024-thread block per CU with a private 65536-bin LDS histogram of 16-bit counters packed two per dword.
 // A block walks chunks of 57344 voxels; a chunk adds at most 57344 to a bin, so between chunks every bin that has reached
@@ -129,27 +118,18 @@ __global__ void __launch_bounds__(1024) k_hist_u16_box(const uint16_t *__restric
 // (with_zero: over all voxels, zeros included -- the second channel of method 'multi_channel', sp.py:46)
 __global__ void __launch_bounds__(1024) k_percentile95(const unsigned long long *__restrict__ hist, ClipInfo *out, int with_zero)
 {
-    // 1024 threads x 64 bins.  Chunk sums -> block-wide inclusive scan (wave shuffles + 16 wave totals) -> the chunk that
-    // holds a rank is the one thread whose [exclusive, inclusive) range contains it -> one wave scans that chunk's 64 bins.
+    // 1024 threads x 64 bins.  Chunk sums -> block-wide scan -> the chunk that holds a rank is the one thread whose
+    // [exclusive, inclusive) range contains it -> one wave scans that chunk's 64 bins.
     // (A single thread walking the 1024 chunk sums and the bins took 35 us: the whole projection waits for this value.)
     __shared__ unsigned long long wave_tot[16];
-    __shared__ unsigned long long s_n;
     __shared__ int s_chunk[2];
     __shared__ unsigned long long s_before[2];
     __shared__ int s_val[2];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    unsigned long long s = 0;
+    unsigned long long s = 0, n;
     for (int b = t * 64; b < t * 64 + 64; ++b)
         if (b > 0 || with_zero) s += hist[b];
-    unsigned long long inc = wave_inclusive_scan(s, lane);
-    if (lane == 63) wave_tot[wave] = inc;
-    __syncthreads();
-    unsigned long long base = 0;
-    for (int w = 0; w < wave; ++w) base += wave_tot[w];
-    inc += base;
-    if (t == 1023) s_n = inc;
-    __syncthreads();
-    const unsigned long long n = s_n;
+    const unsigned long long exc = block_exclusive_scan<16>(s, wave_tot, n), inc = exc + s;
     if (n == 0) {
         if (t == 0) { out->has = 0; out->p95 = 0.f; out->p95d = 0.0; }
         return;
@@ -163,7 +143,6 @@ __global__ void __launch_bounds__(1024) k_percentile95(const unsigned long long 
     if (prev > (long long)n - 1) prev = (long long)n - 1;
     long long next = prev + 1;
     if (next > (long long)n - 1) next = (long long)n - 1;
-    const unsigned long long exc = inc - s;
     if (s > 0) {          // the chunk whose cumulative range holds the rank (exactly one thread per rank)
         if (exc <= (unsigned long long)prev && (unsigned long long)prev < inc) { s_chunk[0] = t; s_before[0] = exc; }
         if (exc <= (unsigned long long)next && (unsigned long long)next < inc) { s_chunk[1] = t; s_before[1] = exc; }
@@ -172,7 +151,7 @@ __global__ void __launch_bounds__(1024) k_percentile95(const unsigned long long 
     if (wave < 2) {       // wave 0: value at rank prev, wave 1: at rank next
         const unsigned long long k = (unsigned long long)(wave == 0 ? prev : next) - s_before[wave];
         const int b = s_chunk[wave] * 64 + lane;
-        const unsigned long long ci = wave_inclusive_scan((b > 0 || with_zero) ? hist[b] : 0ULL, lane);
+        const unsigned long long ci = wave_inclusive_scan((b > 0 || with_zero) ? hist[b] : 0ULL);
         // first bin whose inclusive count exceeds k
         const unsigned long long hit = __ballot(ci > k);
         if (lane == 0) s_val[wave] = hit ? s_chunk[wave] * 64 + (__ffsll((long long)hit) - 1) : 65535;
@@ -331,7 +310,7 @@ __global__ void __launch_bounds__(256) k_mask_wmax_fused(const float *__restrict
         cmin[r][c] = (unsigned char)a; cmax[r][c] = (unsigned char)b;
         lo = min(lo, a); hi = max(hi, b);
     }
-    for (int d = 32; d >= 1; d >>= 1) { lo = min(lo, __shfl_xor(lo, d, 64)); hi = max(hi, __shfl_xor(hi, d, 64)); }
+    lo = wave_min(lo); hi = wave_max(hi);
     if ((t & 63) == 0) { atomicMin(&s_lo, lo); atomicMax(&s_hi, hi); }
     __syncthreads();
     const int zaB = max(s_lo - MASK_ZR, 0), zbB = min(s_hi + MASK_ZR, Zs - 1);
@@ -504,7 +483,7 @@ __global__ void __launch_bounds__(256) k_argmax_certify(const float *__restrict_
     // append with one atomic per block (not per pixel: same-address atomics serialise in L2)
     const int mine = __popc(unc);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int incl = wave_inclusive_scan(mine, lane);
+    const int incl = wave_inclusive_scan(mine);
     if (lane == 63) s_cnt[wave] = incl;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -128,12 +128,7 @@ __global__ void __launch_bounds__(PREP_T) k_prep_digit(const double *__restrict_
         }
     }
     if (MODE == 2) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const unsigned long long o0 = __shfl_xor(a0, d, 64), o1 = __shfl_xor(a1, d, 64);
-            a0 = o0 < a0 ? o0 : a0;
-            a1 = o1 < a1 ? o1 : a1;
-        }
+        a0 = wave_min(a0); a1 = wave_min(a1);
         if (lane == 0) { s_min[0][wave] = a0; s_min[1][wave] = a1; }
     }
     __syncthreads();
@@ -169,30 +164,17 @@ __global__ void __launch_bounds__(PREP_T) k_prep_digit(const double *__restrict_
     }
     if (tid < 2) { s_pick[tid] = (int)mask; s_cum[tid] = 0; s_nb[tid] = PREP_BINS; }
     __syncthreads();
-    // both ranks side by side: every thread sums PREP_PER bins, a scan over the waves and then over the wave sums finds the thread
-    // whose bins hold the rank
+    // both ranks: every thread sums PREP_PER bins, a block scan of the sums finds the thread whose bins hold the rank
     const unsigned int *h[2] = {sh[0], sh[one ? 0 : 1]};
-    long long r[2], sum[2], incl[2];
+    long long r[2];
 #pragma unroll
     for (int w = 0; w < 2; ++w) {
         r[w] = st->rank[c][w];
-        sum[w] = 0;
+        long long sum = 0, all;
 #pragma unroll
-        for (int k = 0; k < PREP_PER; ++k) sum[w] += h[w][tid * PREP_PER + k];
-        incl[w] = sum[w];
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long o = __shfl_up(incl[w], d, 64);
-            if (lane >= d) incl[w] += o;
-        }
-        if (lane == 63) s_wsum[w][wave] = incl[w];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < 2; ++w) {
-        long long cum = incl[w] - sum[w];
-        for (int k = 0; k < wave; ++k) cum += s_wsum[w][k];
-        if (cum <= r[w] && r[w] < cum + sum[w]) {                // (one thread)
+        for (int k = 0; k < PREP_PER; ++k) sum += h[w][tid * PREP_PER + k];
+        long long cum = block_exclusive_scan<PREP_W>(sum, s_wsum[w], all);
+        if (cum <= r[w] && r[w] < cum + sum) {                   // (one thread)
             int b = tid * PREP_PER;
             while (cum + (long long)h[w][b] <= r[w]) cum += h[w][b++];
             s_pick[w] = b; s_cum[w] = cum;

@@ -49,18 +49,9 @@ __global__ void __launch_bounds__(256) k_ws_minmax(const double *__restrict__ v,
             hi = e[u] > hi ? e[u] : hi;
         }
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long l2 = __shfl_xor(lo, d, 64), h2 = __shfl_xor(hi, d, 64);
-        lo = l2 < lo ? l2 : lo;
-        hi = h2 > hi ? h2 : hi;
-    }
-    if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
-    __syncthreads();
+    lo = block_reduce<4>(lo, slo, [](unsigned long long a, unsigned long long b) { return b < a ? b : a; });
+    hi = block_reduce<4>(hi, shi, [](unsigned long long a, unsigned long long b) { return b > a ? b : a; });
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) {
-            lo = slo[w] < lo ? slo[w] : lo;
-            hi = shi[w] > hi ? shi[w] : hi;
-        }
         atomicMin(&info->emin, lo);
         atomicMax(&info->emax, hi);
     }
@@ -79,13 +70,8 @@ __global__ void __launch_bounds__(256) k_ws_count_other(const double *__restrict
 #pragma unroll
         for (int u = 0; u < 4; ++u) c += (e[u] != emin && e[u] != emax);
     }
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
-    if ((threadIdx.x & 63) == 0) sc[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        c = sc[0] + sc[1] + sc[2] + sc[3];
-        if (c) atomicAdd(&info->n_other, c);
-    }
+    c = block_sum<4>(c, sc);
+    if (threadIdx.x == 0 && c) atomicAdd(&info->n_other, c);
 }
 
 // ---- markers: label(local_minima(image)) ---------------------------------------------------------------------------

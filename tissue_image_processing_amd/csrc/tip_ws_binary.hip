@@ -206,56 +206,26 @@ __global__ void __launch_bounds__(256) k_mb_flag_keys_dn(const unsigned long lon
 
 // exclusive scan of the key flags, length on the device: a fixed grid walks the 2048-element chunks; a block first needs the sum of all
 // chunks in front of its own, which it accumulates as it goes (its chunks are gridDim.x apart)
-constexpr int MBS_ITEMS = 8, MBS_CHUNK = 256 * MBS_ITEMS;
-__global__ void __launch_bounds__(256) k_mb_scan_chunks(const int *__restrict__ in, int *__restrict__ out, const MbState *S, int *__restrict__ csum)
+constexpr int MBS_ITEMS = SCAN_ITEMS, MBS_CHUNK = SCAN_BLOCK;      // (the tile of scan_tile_i32, tip_wave.h)
+__global__ void __launch_bounds__(SCAN_THREADS) k_mb_scan_chunks(const int *__restrict__ in, int *__restrict__ out, const MbState *S, int *__restrict__ csum)
 {
-    __shared__ int wsum[4];
+    __shared__ int wsum[SCAN_THREADS / 64];
     const int n = S->nnext > 0 ? S->keyspace : 0;
     for (int c0 = blockIdx.x; (long)c0 * MBS_CHUNK < n; c0 += gridDim.x) {
-        const long base = (long)c0 * MBS_CHUNK + (long)threadIdx.x * MBS_ITEMS;
-        int v[MBS_ITEMS], sum = 0;
-#pragma unroll
-        for (int i = 0; i < MBS_ITEMS; ++i) {
-            v[i] = base + i < n ? in[base + i] : 0;
-            sum += v[i];
-        }
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        int inc = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wsum[w];
-        int run = woff + inc - sum;
-#pragma unroll
-        for (int i = 0; i < MBS_ITEMS; ++i) {
-            if (base + i < n) out[base + i] = run;
-            run += v[i];
-        }
-        if (threadIdx.x == 255) csum[c0] = run;
-        __syncthreads();
+        const int total = scan_tile_i32(in, out, (long)c0 * MBS_CHUNK + (long)threadIdx.x * MBS_ITEMS, n, wsum);
+        if (threadIdx.x == 0) csum[c0] = total;
+        __syncthreads();                            // (the next chunk writes wsum)
     }
 }
 __global__ void __launch_bounds__(256) k_mb_scan_add(int *__restrict__ out, const MbState *S, const int *__restrict__ csum)
 {
     __shared__ int wsum[4];
-    __shared__ int s_off;
     const int n = S->nnext > 0 ? S->keyspace : 0;
     int off = 0, done_to = 0;                    // sum of csum[0 .. done_to)
     for (int c0 = blockIdx.x; (long)c0 * MBS_CHUNK < n; c0 += gridDim.x) {
         int part = 0;
         for (int j = done_to + threadIdx.x; j < c0; j += 256) part += csum[j];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = part;
-        __syncthreads();
-        if (threadIdx.x == 0) s_off = off + wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
-        off = s_off;
+        off += block_sum<4>(part, wsum);
         done_to = c0;
         const long base = (long)c0 * MBS_CHUNK + (long)threadIdx.x * MBS_ITEMS;
 #pragma unroll
@@ -360,7 +330,7 @@ __global__ void __launch_bounds__(MBG_THREADS) k_mb_small_gens(unsigned long lon
     __shared__ int s_nnext;
     int ncur = S->ncur, flip = S->flip, gen = S->gen;
     if (ncur <= 0 || ncur > small) return;                    // (uniform)
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     int unfinished = 0, done = 0;
     for (;;) {
         int *cur = flip ? listB : listA, *nxt = flip ? listA : listB;
@@ -398,22 +368,9 @@ __global__ void __launch_bounds__(MBG_THREADS) k_mb_small_gens(unsigned long lon
             for (int base = 0; base < nwords; base += MBG_THREADS) {
                 const int w = base + t;
                 const int c = w < nwords ? __popc(bits[w]) : 0;
-                int inc = c;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const int o = __shfl_up(inc, d, 64);
-                    if (lane >= d) inc += o;
-                }
-                if (lane == 63) wsum[wave] = inc;
-                __syncthreads();
-                int woff = 0, total = 0;
-#pragma unroll
-                for (int q = 0; q < MBG_THREADS / 64; ++q) {
-                    const int v = wsum[q];
-                    woff += q < wave ? v : 0;
-                    total += v;
-                }
-                if (w < nwords) pre[w] = carry + woff + inc - c;
+                int total;
+                const int before = block_exclusive_scan<MBG_THREADS / 64>(c, wsum, total);
+                if (w < nwords) pre[w] = carry + before;
                 carry += total;
                 __syncthreads();
             }

@@ -237,7 +237,7 @@ __global__ void __launch_bounds__(WS_THREADS) k_ws_tiles(const double *__restric
         if (WS_THREADS == 64 && tile_wst != nullptr) {
 #pragma unroll
             for (int u = 0; u < NLOAD; ++u) wcount += st_lab(ls[u]) == 0 ? 1 : 0;
-            for (int d = 32; d >= 1; d >>= 1) wcount += __shfl_xor(wcount, d, 64);
+            for (int d = 32; d >= 1; d >>= 1) wcount += __shfl_xor(wcount, d, 64);   // (by hand: wave_sum changes this kernel's code)
             if (!first && tile_wst[tile] == (wcount | WST_STUCK)) {
                 if (threadIdx.x == 0) changed_cur[tile] = 0;
                 return;
@@ -557,7 +557,7 @@ __global__ void __launch_bounds__(64) k_end_resolve(const double *__restrict__ v
         for (int u = 1; u < EPL; ++u)
             if (ch[u] < bh || (ch[u] == bh && cl[u] < bl)) { bh = ch[u]; bl = cl[u]; bu = u; }
         const unsigned long long mh = bh, ml = bl;
-        for (int d = 32; d >= 1; d >>= 1) {
+        for (int d = 32; d >= 1; d >>= 1) {     // (by hand: wave_reduce over the pair changes this kernel's code)
             const unsigned long long oh = __shfl_xor(bh, d, 64), ol = __shfl_xor(bl, d, 64);
             if (oh < bh || (oh == bh && ol < bl)) { bh = oh; bl = ol; }
         }
@@ -637,7 +637,9 @@ __global__ void __launch_bounds__(256) k_ws_tile_totals(const int *__restrict__ 
         u += a;
         if (a) f += tile_front[t];
     }
-    for (int d = 32; d >= 1; d >>= 1) { u += __shfl_xor(u, d, 64); f += __shfl_xor(f, d, 64); }
+    struct UF { int u, f; };
+    const UF s = wave_reduce(UF{u, f}, [](UF a, UF b) { return UF{a.u + b.u, a.f + b.f}; });
+    u = s.u; f = s.f;
     if ((threadIdx.x & 63) == 0 && (u | f)) { atomicAdd(&su, u); atomicAdd(&sf, f); }
     __syncthreads();
     if (threadIdx.x == 0 && (su | sf)) { atomicAdd(&info->und_total, su); atomicAdd(&info->front_total, sf); }
