@@ -732,6 +732,30 @@ TIP_API int tip_tiff_finish_u16_dev(void *stack_dev, int64_t n_rows, int64_t row
 TIP_API int tip_export_maps_u16_dev(const int32_t *labels_dev, const uint8_t *types_dev, int64_t n_pix, const int64_t *ids_host,
                                     int64_t n_ids, uint16_t *out_dev, int32_t *n_bad_host);
 
+/* ---- the projected movie as uint16 TIFF pages and its z-maps (csrc/tip_export.hip; movie.export_projection) ----------------- */
+/* Every _dev entry takes DEVICE buffers on the calling thread's stream; its twin without the suffix takes host arrays, touches no   */
+/* device and is compiled from the same per-sample function (the reference the device form is tested against).                      */
+/* tip_max_f64: the maximum of n doubles -- a frame's part of the normalisation save_tiff applies to the whole movie.  A NaN is       */
+/* never taken (numpy's max would return it); all NaN gives -inf.  _dev waits ONCE, *max_host is a host word.  TIP_ERR_ARG: a null   */
+/* pointer, n < 1.                                                                                                                 */
+TIP_API int tip_max_f64_dev(const double *src_dev, int64_t n, double *max_host);
+TIP_API int tip_max_f64(const double *src, int64_t n, double *max_out);
+/* n_pages pages of rows x cols float64 samples as uint16: u = (uint16) rint((v / scale_max) * 65535), the division and the product  */
+/* each rounded to nearest, no reciprocal and no fused step -- np.round((image / np.max(image)) * 65535).astype("uint16") of         */
+/* bim.py:183-186 when scale_max is the image's maximum.  predictor 1 stores u; predictor 2 (TIFF horizontal differencing) stores     */
+/* u[x] - u[x - 1] modulo 2^16 for x > 0 and u[0] at every row start.  scale_max == 0, an all-zero movie, writes zeros: what numpy's  */
+/* 0 / 0 -> NaN -> cast gives on x86-64.  A sample outside [0, scale_max] wraps modulo 2^16 as numpy's cast does there, a NaN gives   */
+/* 0.  _dev is asynchronous.  TIP_ERR_ARG: a null pointer, a negative extent, cols above 2^31 - 1, more than 10^12 samples,           */
+/* scale_max negative or not finite.  TIP_ERR_UNSUPPORTED: another predictor.  No samples: TIP_OK, nothing is read.                  */
+TIP_API int tip_projection_pages_u16_dev(const double *src_dev, int64_t n_pages, int64_t rows, int64_t cols, double scale_max,
+                                         int predictor, uint16_t *out_dev);
+TIP_API int tip_projection_pages_u16(const double *src, int64_t n_pages, int64_t rows, int64_t cols, double scale_max, int predictor,
+                                     uint16_t *out);
+/* astype("uint16") of n int64 (the z-map as sp.py:229-230 saves it): modulo 2^16.  _dev is asynchronous.  TIP_ERR_ARG: a null       */
+/* pointer, n negative (or above 10^12 for _dev).                                                                                   */
+TIP_API int tip_zmap_u16_dev(const int64_t *src_dev, int64_t n, uint16_t *out_dev);
+TIP_API int tip_zmap_u16(const int64_t *src, int64_t n, uint16_t *out);
+
 #ifdef __cplusplus
 }
 #endif

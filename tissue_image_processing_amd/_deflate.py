@@ -175,6 +175,57 @@ def export_maps_u16_dev(labels_ptr, types_ptr, n_pix, ids, out_ptr):
     return out_ptr
 
 
+def max_f64_dev(src_ptr, n):
+    """tip_max_f64_dev: the maximum of n float64 at a device address (waits once); a NaN is never taken."""
+    out = ctypes.c_double(0.0)
+    _lib.check(_lib.lib().tip_max_f64_dev(src_ptr, int(n), ctypes.byref(out)))
+    return float(out.value)
+
+
+def max_f64(values):
+    """tip_max_f64, the host twin of max_f64_dev (no device needed)."""
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    out = ctypes.c_double(0.0)
+    keep = values if values.size else np.zeros(1)
+    _lib.check(_lib.load().tip_max_f64(_lib.ptr(keep), values.size, ctypes.byref(out)))
+    return float(out.value)
+
+
+def projection_pages_u16_dev(src_ptr, n_pages, rows, cols, scale_max, predictor, out_ptr):
+    """tip_projection_pages_u16_dev on device addresses, asynchronous: float64 pages as the uint16 pages of
+    tiff.tiff_normalise(movie, "uint16") when scale_max is the movie's maximum, differenced along x for predictor 2."""
+    _lib.check(_lib.lib().tip_projection_pages_u16_dev(src_ptr, int(n_pages), int(rows), int(cols), float(scale_max), int(predictor), out_ptr))
+    return out_ptr
+
+
+def projection_pages_u16(planes, scale_max, predictor=1):
+    """tip_projection_pages_u16, the host twin (no device needed), on a float64 array (..., rows, cols) -> uint16 of its shape."""
+    planes = np.ascontiguousarray(planes, dtype=np.float64)
+    if planes.ndim < 2:
+        raise ValueError("projection_pages_u16 takes pages (..., rows, cols), not %s" % (planes.shape,))
+    rows, cols = planes.shape[-2:]
+    out = np.zeros(planes.shape, np.uint16)
+    keep, keep_out = (planes, out) if planes.size else (np.zeros(1), np.zeros(1, np.uint16))
+    _lib.check(_lib.load().tip_projection_pages_u16(_lib.ptr(keep), int(np.prod(planes.shape[:-2], dtype=np.int64)), rows, cols,
+                                                    float(scale_max), int(predictor), _lib.ptr(keep_out)))
+    return out
+
+
+def zmap_u16_dev(src_ptr, n, out_ptr):
+    """tip_zmap_u16_dev on device addresses, asynchronous: n int64 as uint16, modulo 2^16."""
+    _lib.check(_lib.lib().tip_zmap_u16_dev(src_ptr, int(n), out_ptr))
+    return out_ptr
+
+
+def zmap_u16(zmap):
+    """tip_zmap_u16, the host twin (no device needed): an int64 array -> uint16 of its shape."""
+    zmap = np.ascontiguousarray(zmap, dtype=np.int64)
+    out = np.zeros(zmap.shape, np.uint16)
+    if zmap.size:
+        _lib.check(_lib.load().tip_zmap_u16(_lib.ptr(zmap), zmap.size, _lib.ptr(out)))
+    return out
+
+
 def npy_header(shape, dtype):
     """The bytes np.save writes in front of a C-contiguous array's data (format 1.0: magic, header length, dict, padding)."""
     import io

@@ -250,7 +250,12 @@ class GpuFrameBackend(object):
     frame: the int32 label map (tracker look-ups) and, when drift is estimated, the reference channel's projection plane
     -- both kept with device-to-device copies.  The planes are torch tensors so that RCCL can send them as they are.
     close() is what releases process_frames' worker threads and their library contexts: each worker holds its backend, so a
-    backend dropped without close() keeps them for the life of the process."""
+    backend dropped without close() keeps them for the life of the process.
+
+    keep_projection=True also keeps, per owned frame, all C projection planes (float64 (C, Y, X)) and the int64 z-map -- what
+    export_projection writes as the projected movie and its z-maps.  That is 8 C Y X + 8 Y X bytes of device memory a frame: 100 MB
+    at 2048 x 2048 with C = 2, so a rank's share of a long movie has to fit its GPU (a float32 copy would halve it and is not
+    built).  close() frees them."""
 
     CELL_TYPE_COLUMNS = (("type", np.uint8), ("valid", np.uint8), ("mean_intensity", np.float64))
     CELL_TYPE_OPTIONS = ("atoh_channel", "threshold", "percentage_above_threshold", "peak_window_size", "type_index",
@@ -262,7 +267,7 @@ class GpuFrameBackend(object):
 
     def __init__(self, C, Z, Y, X, device=None, keep_planes=False, inflight=1, cell_types=None, segmentation="classical",
                  unet_weights=None, unet_channels=(1, 0), predictor_factory=None, keep_hc=False, neighbor_features=False,
-                 order_features=False, archive=False, **kw):
+                 order_features=False, archive=False, keep_projection=False, **kw):
         from .pipeline import FramePipeline
         from . import _lib
         # archive: False, True or dict(type_name="HC", matches="runs") -- every frame's label map (and, with cell_types, its type
@@ -338,8 +343,11 @@ class GpuFrameBackend(object):
         self.pipe = FramePipeline(C, Z, Y, X, device=device, **kw)
         if device is None:
             self.device = _lib.device_for_thread()
-        self.Y, self.X = Y, X
+        self.C, self.Y, self.X = C, Y, X
         self.keep_planes = keep_planes
+        self.keep_projection = bool(keep_projection)
+        self.projections = {}   # frame -> DeviceBuffer (float64 projection planes (C, Y, X)), with keep_projection
+        self.zmaps = {}         # frame -> DeviceBuffer (int64 z-map (Y, X)), with keep_projection
         self.inflight = max(1, int(inflight))
         self.labels = {}   # frame -> DeviceBuffer (int32 label map)
         self.planes = {}   # frame -> torch tensor (Y, X) float64 on this GPU
@@ -379,13 +387,19 @@ class GpuFrameBackend(object):
     def close(self):
         """Ends the worker threads; each releases its pipeline buffers and its library context (tip_shutdown) on the way out --
         in U-Net mode its predictor and its torch stream too; this pipeline's predictor goes as well (a later frame builds
-        a new one)."""
+        a new one).  The projections and z-maps of keep_projection are freed."""
         workers, self._workers = self._workers, []
         for w in workers:
             w.jobs.put(None)
         for w in workers:
             w.join()
         self._predictors.clear()
+        for kept in (self.projections, self.zmaps):
+            for buf in kept.values():
+                buf.free()
+            kept.clear()
+        for name in ("_projection_encoder", "_zmap_pages"):
+            setattr(self, name, None)
 
     def _predictor_for(self, p):
         """Pipeline p's own predictor, built on the thread that first segments with p."""
@@ -408,11 +422,12 @@ class GpuFrameBackend(object):
         if self.keep_hc:
             self.hc_maps[t] = self._keep(p, p.d_hc.ptr, 8)
 
-    def _keep(self, p, src_ptr, itemsize, dst=None):
-        """A device copy of a (Y, X) map of pipeline p, on p's stream: into the tensor dst, or a new DeviceBuffer."""
+    def _keep(self, p, src_ptr, itemsize, dst=None, planes=1):
+        """A device copy of `planes` (Y, X) maps of pipeline p, on p's stream: into the tensor dst, or a new DeviceBuffer."""
         from . import _lib
-        keep = _lib.DeviceBuffer(self.Y * self.X * itemsize) if dst is None else dst
-        _lib.check(p.lib.tip_memcpy_d2d(keep.ptr if dst is None else dst.data_ptr(), src_ptr, self.Y * self.X * itemsize))
+        nbytes = planes * self.Y * self.X * itemsize
+        keep = _lib.DeviceBuffer(nbytes) if dst is None else dst
+        _lib.check(p.lib.tip_memcpy_d2d(keep.ptr if dst is None else dst.data_ptr(), src_ptr, nbytes))
         return keep
 
     @staticmethod
@@ -436,6 +451,9 @@ class GpuFrameBackend(object):
         else:
             d_stack = p.upload_stack(stack_u16)
         p.project(d_stack)
+        if self.keep_projection:      # (d_proj may be the U-Net mode's torch view: its address is all the copy needs)
+            self.projections[t] = self._keep(p, p.d_proj.ptr, 8, planes=self.C)
+            self.zmaps[t] = self._keep(p, p.d_zmap.ptr, 8)
         if self.segmentation == "unet":
             self._segment_unet(p, t)
         else:
@@ -510,6 +528,38 @@ class GpuFrameBackend(object):
             self._page_encoder = PageEncoder(self.Y, self.X)
         types = self.type_maps[t].ptr if self.cell_types is not None else None
         return self._page_encoder.encode(self.labels[t].ptr, types, ids, rowsperstrip, codes)
+
+    def fetch_projection(self, t):
+        """Frame t's projection planes (float64 (C, Y, X)), downloaded; needs keep_projection."""
+        return self.projections[t].download((self.C, self.Y, self.X), np.float64)
+
+    def fetch_zmap(self, t):
+        """Frame t's z-map (int64 (Y, X)), downloaded; needs keep_projection."""
+        return self.zmaps[t].download((self.Y, self.X), np.int64)
+
+    def projection_max(self, t):
+        """The maximum of frame t's resident projection planes (tip_max_f64_dev): its part of the movie's normalisation."""
+        from ._deflate import max_f64_dev
+        return max_f64_dev(self.projections[t].ptr, self.C * self.Y * self.X)
+
+    def projection_page_strips(self, t, scale_max, rowsperstrip, codes="dynamic", predictor=1):
+        """Frame t's projection planes as TIFF strips (export_projection): the uint16 pages save_tiff(..., data_type="uint16") writes
+        for a movie whose maximum is scale_max (tip_projection_pages_u16_dev; differenced along x for predictor 2), deflated strip
+        by strip where they are (tip_deflate_strips_dev) -> per channel the list of its strips' zlib streams.  Called on the
+        thread that owns this backend's pipeline."""
+        from .tiff_export import ProjectionEncoder
+        if getattr(self, "_projection_encoder", None) is None:
+            self._projection_encoder = ProjectionEncoder(self.C, self.Y, self.X)
+        return self._projection_encoder.encode(self.projections[t].ptr, scale_max, rowsperstrip, codes, predictor)
+
+    def zmap_u16(self, t):
+        """Frame t's z-map as export_projection saves it: astype("uint16") on the device (tip_zmap_u16_dev), then downloaded."""
+        from . import _lib
+        from ._deflate import zmap_u16_dev
+        if getattr(self, "_zmap_pages", None) is None:
+            self._zmap_pages = _lib.DeviceBuffer(self.Y * self.X * 2)
+        zmap_u16_dev(self.zmaps[t].ptr, self.Y * self.X, self._zmap_pages.ptr)
+        return self._zmap_pages.download((self.Y, self.X), np.uint16)
 
     def lookup(self, t, qy, qx):
         from . import _lib
@@ -1030,3 +1080,27 @@ def export_tiff(path, n_frames, backend, ids, rank=0, world=1, dist=None, device
     labels."""
     from .tiff_export import export_tiff as _export_tiff
     return _export_tiff(path, n_frames, backend, ids, rank, world, dist, device, rowsperstrip, codes, bigtiff)
+
+
+def export_projection(path, n_frames, backend, rank=0, world=1, dist=None, device="cpu", rowsperstrip=None, codes="dynamic", predictor=1,
+                      bigtiff=None, zmap=True, metadata=None):
+    """Writes a finished movie's projection as the `positionN.tif` of movie_surface_projection -- T x C x Y x X uint16 with deflate
+    strips, what save_tiff(path, movie, axes="TCYX", data_type="uint16") stores: every sample scaled by the WHOLE movie's maximum
+    to 65535 and rounded (tiff.tiff_normalise) -- and, with zmap=True, `zmap_<name>.npy` beside it (`name`: path's basename
+    without ".tif"), uint16 (T, 1, 1, Y, X), where Tissue.load_height_map looks for it.  Collective like export_tiff: EVERY rank
+    calls it after process_movie with the backend that ran the movie with keep_projection=True.  Returns (path, the z-map's path or
+    None) on rank 0, None elsewhere.
+
+    The owners all-gather their frames' maxima (tip_max_f64_dev, 8 bytes a frame) and every rank takes the largest.  Each owner
+    turns its frames' resident float64 planes into uint16 pages and those into one zlib stream per strip on its GPU
+    (backend.projection_page_strips: tip_projection_pages_u16_dev, then tip_deflate_strips_dev); the strips travel to rank 0 in one
+    gather and rank 0 writes them with tiff.write_tiff_strips.  The uint16 z-maps (tip_zmap_u16_dev) travel raw in a second gather.
+
+    rowsperstrip: None = tiff.default_rows_per_strip(Y, 2 X); codes: "dynamic" or "fixed"; predictor: 1, or 2 for horizontal
+    differencing (tag 317; on synthetic data it did not pay, which is why it is not the default); bigtiff as in export_tiff;
+    metadata: an object with to_xml() or a string, written into the description as save_tiff does.  The file does not depend on the
+    world size.  ValueError on EVERY rank, before anything is written: a frame whose owner kept no projection (the owners
+    all-gather what they lack first), a row over 64 KB (X > 32768: a strip is one chunk of the encoder), a maximum that is
+    negative or not finite."""
+    from .tiff_export import export_projection as _export_projection
+    return _export_projection(path, n_frames, backend, rank, world, dist, device, rowsperstrip, codes, predictor, bigtiff, zmap, metadata)

@@ -155,16 +155,22 @@ def _project_scene(source, series, out_shape_t, rank, world, part_prefix, **para
 
 def movie_surface_projection(files, reference_channel, position_final_movie, initial_positions_number, output_dir,
                              method, bin_size, build_manifold, only_position, zmin, zmax, airyscan, output_name="",
-                             rank=0, world=1):
+                             rank=0, world=1, compression=None):
     """sp.py:168-236: project every time point of every position of a movie split over several files (image sources of
     basic_image_manipulations.open_image; scene = position) and write, per position, `positionN.tif` (uint16, TCYX),
     `zmap_positionN.npy` and -- when the sources carry OME stage metadata -- `stage_locations_positionN.pkl`.
     A position leaves the scene list after its final movie (position_final_movie, 1-based file numbers), which shifts the
     scene numbers of the ones behind it, as upstream.  rank / world: shard the time points over processes (one per GPU);
-    rank 0 writes the outputs."""
+    rank 0 writes the outputs.
+
+    compression (opt-in; None writes the file as it always was): "zlib" -- `positionN.tif` in deflate strips from the host's zlib
+    (save_tiff(compression="zlib")); "device" -- the same pages, every frame uploaded and deflated strip by strip on rank 0's
+    GPU (tiff_export.save_projection_tiff)."""
     import os
     from .basic_image_manipulations import get_image_dimensions, concatenate_time_points
     from .tiff import save_tiff
+    if compression not in (None, "zlib", "device"):
+        raise ValueError("movie_surface_projection: compression %r (None, 'zlib' or 'device')" % (compression,))
     positions = list(range(initial_positions_number))
     time_points_number = np.zeros((initial_positions_number, len(files)))
     projection_files = [[] for _ in range(initial_positions_number)]
@@ -203,8 +209,14 @@ def movie_surface_projection(files, reference_channel, position_final_movie, ini
             metadata = update_projection_metadata(get_image_metadata(files[0], series=position),
                                                   np.sum(time_points_number[position, :]), series=position)
             movie = concatenate_time_points(projection_files[position])
-            save_tiff(os.path.join(output_dir, output_name + "position%d.tif" % (position + 1)), movie, metadata=metadata,
-                      axes="TCYX", data_type="uint16")
+            movie_path = os.path.join(output_dir, output_name + "position%d.tif" % (position + 1))
+            if compression == "device":
+                from .tiff_export import save_projection_tiff
+                save_projection_tiff(movie_path, movie, metadata=metadata)
+            elif compression == "zlib":
+                save_tiff(movie_path, movie, metadata=metadata, axes="TCYX", data_type="uint16", compression="zlib")
+            else:
+                save_tiff(movie_path, movie, metadata=metadata, axes="TCYX", data_type="uint16")
             zmaps = np.concatenate([np.load(f).astype("uint16") for f in zmap_files[position]], axis=0)
             np.save(os.path.join(output_dir, output_name + "zmap_position%d.npy" % (position + 1)), zmaps)
         save_stage_positions(files, position_final_movie, initial_positions_number, output_dir, only_position=only_position,

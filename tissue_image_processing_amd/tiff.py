@@ -373,6 +373,18 @@ def tiff_normalise(image, data_type=""):
     return image
 
 
+def metadata_xml(metadata, who="save_tiff"):
+    """What of `metadata` rides in the description: upstream hands the OME metadata to aicsimageio's writer; here its XML (if it
+    has one) or the string itself; other objects are reported once as not written."""
+    if metadata is None:
+        return None
+    xml = metadata.to_xml() if hasattr(metadata, "to_xml") else (metadata if isinstance(metadata, (str, bytes)) else None)
+    if xml is None:
+        import warnings
+        warnings.warn("%s: metadata of type %s is not written (no OME-XML writer here)" % (who, type(metadata).__name__))
+    return xml
+
+
 def save_tiff(path, image, metadata=None, axes="", data_type="", compression=None, predictor=1, rowsperstrip=None):
     """bim.py:160-188.  Upstream hands the array to aicsimageio's OME-TIFF writer; here a self-contained baseline TIFF
     writer stores every (Y, X) plane of the normalised array as one page (little-endian, uncompressed, min-is-black) with
@@ -398,14 +410,7 @@ def save_tiff(path, image, metadata=None, axes="", data_type="", compression=Non
         raise ValueError("save_tiff needs at least a 2-D image")
     planes = np.ascontiguousarray(image).reshape((-1,) + image.shape[-2:]).astype(image.dtype.newbyteorder("<"))
     n_pages, rows, cols = planes.shape
-    xml = None
-    if metadata is not None:
-        # upstream hands the OME metadata to aicsimageio's writer; here its XML (if it has one) rides in the description
-        xml = metadata.to_xml() if hasattr(metadata, "to_xml") else (metadata if isinstance(metadata, (str, bytes)) else None)
-        if xml is None:
-            import warnings
-            warnings.warn("save_tiff: metadata of type %s is not written (no OME-XML writer here)" % type(metadata).__name__)
-    desc = _description(axes, image.shape, xml)
+    desc = _description(axes, image.shape, metadata_xml(metadata))
     too_large = "save_tiff: classic TIFF holds less than 4 GiB; split the movie"
     if compression == "zlib":
         if planes.dtype not in (np.uint8, np.uint16):
@@ -448,7 +453,7 @@ def _zlib_pages(planes, predictor, geometry):
                 yield out[i:i + n_strips]
 
 
-def write_tiff_strips(path, shape, axes, dtype, rowsperstrip, pages, bigtiff=None):
+def write_tiff_strips(path, shape, axes, dtype, rowsperstrip, pages, bigtiff=None, predictor=1, xml=None):
     """A deflate-strip TIFF from strips that are compressed ALREADY (movie.export_tiff: zlib streams made on the GPUs).  shape: the
     whole array's, (..., Y, X), every leading index one page in C order; dtype uint8 or uint16; `pages` yields, per page, the list
     of its finished strip streams (one per `rowsperstrip` rows, the last strip the rows that are left).  Pages are written as they
@@ -456,8 +461,9 @@ def write_tiff_strips(path, shape, axes, dtype, rowsperstrip, pages, bigtiff=Non
 
     The layout is save_tiff(compression="zlib")'s: little-endian, Compression 8, no Predictor tag, per page the strip offsets and
     byte counts behind the IFD (inline for one strip), then the strips on word boundaries; "axes=... shape=..." in page 0's
-    ImageDescription.  bigtiff=True writes BigTIFF (magic 43, 8-byte offsets and counts); None chooses it when the classic form
-    would reach 4 GiB -- from the strips themselves when `pages` is a list, otherwise, the sizes not being known before the first
+    ImageDescription.  predictor=2: the strips hold rows differenced along x modulo 2^bits (the caller's work) and every page says so
+    in tag 317; xml: a string that follows the description's first line, as save_tiff's metadata does.  bigtiff=True writes BigTIFF
+    (magic 43, 8-byte offsets and counts); None chooses it when the classic form would reach 4 GiB -- from the strips themselves when `pages` is a list, otherwise, the sizes not being known before the first
     page is written, from the uncompressed size.  A classic file that reaches 4 GiB after all raises ValueError."""
     dtype = np.dtype(dtype)
     if dtype not in (np.uint8, np.uint16):
@@ -469,15 +475,17 @@ def write_tiff_strips(path, shape, axes, dtype, rowsperstrip, pages, bigtiff=Non
     n_pages = int(np.prod(shape[:-2], dtype=np.int64))
     if int(rowsperstrip) < 1:
         raise ValueError("write_tiff_strips: rowsperstrip %d" % rowsperstrip)
+    if predictor not in (1, 2):
+        raise ValueError("write_tiff_strips: predictor %r (1: none, 2: horizontal differencing)" % (predictor,))
     geometry = StripGeometry(rows, rowsperstrip)
     n_strips = geometry.strips
-    desc = _description(axes, shape)
+    desc = _description(axes, shape, xml)
     if bigtiff is None:
         if isinstance(pages, (list, tuple)):
             payload = sum(len(s) + (len(s) & 1) for page in pages for s in page)
         else:
             payload = n_pages * rows * cols * dtype.itemsize
-        bigtiff = payload + len(desc) + 16 + n_pages * (16 + 20 * 11 + 16 * n_strips) >= 2 ** 32      # (the larger form's tables)
+        bigtiff = payload + len(desc) + 16 + n_pages * (16 + 20 * (11 if predictor == 1 else 12) + 16 * n_strips) >= 2 ** 32      # (the larger form's tables)
 
     def checked():
         written = 0
@@ -492,7 +500,7 @@ def write_tiff_strips(path, shape, axes, dtype, rowsperstrip, pages, bigtiff=Non
         if written != n_pages:
             raise ValueError("write_tiff_strips: %d pages arrived for shape %r (%d pages)" % (written, shape, n_pages))
 
-    _write_pages(path, bool(bigtiff), _page_tags(rows, cols, dtype, 8, geometry.rows_per_strip),
+    _write_pages(path, bool(bigtiff), _page_tags(rows, cols, dtype, 8, geometry.rows_per_strip, predictor),
                  "write_tiff_strips: classic TIFF holds less than 4 GiB; pass bigtiff=True", desc, n_pages, checked())
     return path
 
