@@ -38,7 +38,8 @@ typedef enum {
     TIP_ERR_NOMEM = -3,
     TIP_ERR_INDEX = -4,      /* the reference would raise IndexError (sp.py:62,68 clip upper bound) */
     TIP_ERR_UNSUPPORTED = -5,
-    TIP_ERR_OVERFLOW = -6    /* caller-provided capacity too small */
+    TIP_ERR_OVERFLOW = -6,   /* caller-provided capacity too small */
+    TIP_ERR_DEGENERATE = -7  /* no convex hull: fewer than three distinct points, or all on one line (ValueError in the mirror) */
 } tip_status;
 
 /* ---- lifecycle / plumbing ------------------------------------------------------------------- */
@@ -755,6 +756,50 @@ TIP_API int tip_projection_pages_u16(const double *src, int64_t n_pages, int64_t
 /* pointer, n negative (or above 10^12 for _dev).                                                                                   */
 TIP_API int tip_zmap_u16_dev(const int64_t *src_dev, int64_t n, uint16_t *out_dev);
 TIP_API int tip_zmap_u16(const int64_t *src, int64_t n, uint16_t *out);
+
+/* ---- the sensory-region filter (ti.py:614-620 detect_non_sensory_region_cells, 2781-2792                                          */
+/* remove_cells_outside_of_sensory_region; csrc/tip_hull.hip) ---------------------------------------------------- */
+/* Every geometric decision below is the exact sign of (b - a) x (p - a) on the float64 coordinates (csrc/tip_orient.h: a floating     */
+/* filter, then error-free transformations), on the device and on the host alike: no tolerance enters a hull or an outside flag.       */
+/* The convex hull of n planar points (px, py float64): the 0-based positions of its vertices, counter-clockwise in the (x, y) plane    */
+/* from the lexicographically smallest (x, then y) vertex.  A point on an edge between two vertices is no vertex; among coincident      */
+/* points the lowest position stands for all.  hull has room for cap entries; *n_hull = the vertices found, TIP_ERR_OVERFLOW when that   */
+/* exceeds cap (nothing is written to hull then), TIP_ERR_DEGENERATE when there are fewer than three -- fewer than three distinct        */
+/* points, or all on one line (*n_hull is then 0, 1 or 2).  n up to 2^30, of which at most 65 536 may SURVIVE the octagon filter --    */
+/* the points not strictly inside the octagon of the eight extremes of x, y, x + y, x - y: a few hundred of 10^6 uniform points, but     */
+/* all points of a circle --, because the vertex test is quadratic in them; more give TIP_ERR_UNSUPPORTED and nothing is written       */
+/* (tip_sensory_region_i32_dev alike; tip_sensory_region_host has no such limit).  The host form rejects a non-finite coordinate (ARG);  */
+/* in the _dev form such a point takes no part.  _dev: px, py, hull are DEVICE arrays, *n_hull_host a host word; the call waits for      */
+/* the stream (once to size its sort, once for the count).                                                                              */
+TIP_API int tip_convex_hull_f64(const double *px, const double *py, int64_t n, int32_t *hull, int64_t cap, int64_t *n_hull);
+TIP_API int tip_convex_hull_f64_dev(const double *px, const double *py, int64_t n, int32_t *hull, int64_t cap, int64_t *n_hull_host);
+/* outside[q] = 1 when query (qx[q], qy[q]) lies STRICTLY outside the convex polygon hull[0 .. h) (positions into px, py; counter-      */
+/* clockwise, strictly convex, h >= 3: what tip_convex_hull_f64 returns), 0 on its boundary and inside.  m = 0 is valid.  The host form  */
+/* checks the positions and rejects non-finite coordinates; the _dev form (device arrays, asynchronous) answers 0 for a query whose     */
+/* search meets a position outside 0 .. n - 1, and its answer for a non-finite query is unspecified.                                    */
+TIP_API int tip_points_outside_hull_f64(const double *px, const double *py, int64_t n, const int32_t *hull, int64_t h, const double *qx,
+                                        const double *qy, int64_t m, uint8_t *outside);
+TIP_API int tip_points_outside_hull_f64_dev(const double *px, const double *py, int64_t n, const int32_t *hull, int64_t h,
+                                            const double *qx, const double *qy, int64_t m, uint8_t *outside);
+/* types[p] = 255 where 1 <= labels[p] <= n and outside[labels[p] - 1] != 0; every other byte is left as it is -- the np.isin write of    */
+/* ti.py:2791.  labels (int32), types (uint8), outside (uint8[n]) are DEVICE arrays; asynchronous.                                      */
+TIP_API int tip_invalidate_cells_u8_dev(const int32_t *labels, uint8_t *types, int64_t n_pix, const uint8_t *outside_dev, int64_t n);
+/* The movie driver's one call per frame.  Host rows over labels 1..n: centroids cx, cy, and the bytes type, valid, empty (empty NULL:   */
+/* no empty row).  The hull points are the rows with type == 1, valid == 1 and empty == 0 -- equalities, not bit tests; type and valid  */
+/* both NULL: every row.  outside[r] (host, uint8[n]) = 1 where row r lies strictly outside their hull -- EVERY row is tested, also the  */
+/* invalid and empty ones --, hull (host, capacity hull_cap) = the hull's row positions as tip_convex_hull_f64 orders them, *n_hull      */
+/* their number; with labels / types (DEVICE maps of n_pix pixels, both or neither) the type map gets 255 on the outside rows' pixels.   */
+/* One upload of the rows, one download of flags and hull, on the calling thread's stream; returns when both are in place.              */
+/* TIP_ERR_DEGENERATE (no hull) and TIP_ERR_OVERFLOW leave outside, hull and the map untouched; TIP_ERR_ARG: a non-finite centroid, a    */
+/* null pointer, a negative count.                                                                                                    */
+TIP_API int tip_sensory_region_i32_dev(const int32_t *labels, uint8_t *types, int64_t n_pix, const double *cx, const double *cy,
+                                       const uint8_t *type, const uint8_t *valid, const uint8_t *empty, int64_t n, uint8_t *outside,
+                                       int32_t *hull, int64_t hull_cap, int64_t *n_hull);
+/* The same selection, hull and test on plain host arrays: touches no device, has no map, shares the predicate with the kernels but not  */
+/* their algorithms (monotone chain; edge-by-edge test) -- the reference the device forms are tested against.  outside NULL: the hull     */
+/* alone.                                                                                                                             */
+TIP_API int tip_sensory_region_host(const double *cx, const double *cy, const uint8_t *type, const uint8_t *valid, const uint8_t *empty,
+                                    int64_t n, uint8_t *outside, int32_t *hull, int64_t hull_cap, int64_t *n_hull);
 
 #ifdef __cplusplus
 }

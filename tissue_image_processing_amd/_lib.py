@@ -18,11 +18,15 @@ _lib = None
 _lock = threading.Lock()
 _tls = threading.local()
 
-TIP_ERR_ARG, TIP_ERR_INDEX, TIP_ERR_UNSUPPORTED, TIP_ERR_OVERFLOW = -2, -4, -5, -6
+TIP_ERR_ARG, TIP_ERR_INDEX, TIP_ERR_UNSUPPORTED, TIP_ERR_OVERFLOW, TIP_ERR_DEGENERATE = -2, -4, -5, -6, -7
 
 
 class TissueHipError(RuntimeError):
     pass
+
+
+class NoHullError(ValueError):
+    """TIP_ERR_DEGENERATE: the points have no convex hull -- fewer than three distinct ones, or all on one line."""
 
 
 def load():
@@ -112,6 +116,8 @@ def check(rc):
     msg = last_error()
     if rc == TIP_ERR_ARG:
         raise ValueError(msg)
+    if rc == TIP_ERR_DEGENERATE:
+        raise NoHullError(msg)
     if rc == TIP_ERR_INDEX:
         raise IndexError(msg)
     raise TissueHipError("tissue_hip error %d: %s" % (rc, msg))

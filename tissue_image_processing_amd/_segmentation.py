@@ -536,6 +536,82 @@ def order_features_dev(py_ptr, px_ptr, n, order, psi_ptr, degree_ptr):
     _lib.check(_lib.lib().tip_order_features_f64_dev(py_ptr, px_ptr, n, int(order), psi_ptr, degree_ptr))
 
 
+# ---- the sensory-region filter (csrc/tip_hull.hip) ------------------------------------------------------------------------------------
+NoHullError = _lib.NoHullError      # a ValueError: fewer than three distinct points, or all on one line
+
+
+def _hull_result(rc, hull, n_hull):
+    if rc == _lib.TIP_ERR_OVERFLOW:
+        raise _lib.TissueHipError("the hull has %d vertices, capacity %d" % (n_hull.value, hull.size))
+    _lib.check(rc)
+    return hull[:int(n_hull.value)].copy()
+
+
+def convex_hull(px, py, cap=None):
+    """tip_convex_hull_f64: int32 positions of the hull's vertices, counter-clockwise in the (x, y) plane from the lexicographically
+    smallest; a point on an edge is no vertex, the lowest position stands for coincident points.  NoHullError (a ValueError) for
+    fewer than three distinct points or all on one line, ValueError for a non-finite coordinate.  cap: the list's capacity (the
+    number of points by default); a smaller hull list raises TissueHipError naming the size needed."""
+    px, py = _points(px, py)
+    hull = np.zeros(max(px.size if cap is None else int(cap), 1), np.int32)
+    n_hull = ctypes.c_int64(0)
+    rc = _lib.lib().tip_convex_hull_f64(_lib.ptr(px), _lib.ptr(py), px.size, _lib.ptr(hull), hull.size if cap is None else int(cap),
+                                        ctypes.byref(n_hull))
+    return _hull_result(rc, hull, n_hull)
+
+
+def points_outside_hull(px, py, hull, qx, qy):
+    """tip_points_outside_hull_f64: uint8[m], 1 where query (qx, qy) lies strictly outside the convex polygon hull (positions into
+    px, py as convex_hull returns them), 0 on its boundary and inside."""
+    px, py = _points(px, py)
+    qx, qy = _points(qx, qy)
+    hull = np.ascontiguousarray(hull, dtype=np.int32).reshape(-1)
+    out = np.zeros(qx.size, np.uint8)
+    _lib.check(_lib.lib().tip_points_outside_hull_f64(_lib.ptr(px), _lib.ptr(py), px.size, _lib.ptr(hull), hull.size, _lib.ptr(qx),
+                                                      _lib.ptr(qy), qx.size, _lib.ptr(out)))
+    return out
+
+
+def invalidate_cells_dev(labels_ptr, types_ptr, n_pix, outside_ptr, n):
+    """tip_invalidate_cells_u8_dev on device addresses: types[p] = 255 where outside[labels[p] - 1]; asynchronous."""
+    _lib.check(_lib.lib().tip_invalidate_cells_u8_dev(labels_ptr, types_ptr, int(n_pix), outside_ptr, int(n)))
+
+
+def _sensory_rows(cx, cy, type, valid, empty):
+    cx, cy = _points(cx, cy)
+    rows = [None if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1) for a in (type, valid, empty)]
+    if (rows[0] is None) != (rows[1] is None):
+        raise ValueError("type and valid come together")
+    if any(a is not None and a.size != cx.size for a in rows):
+        raise ValueError("the rows' columns differ in length")
+    return (cx, cy, *rows)
+
+
+def _sensory_call(entry, head, cx, cy, type, valid, empty):
+    n = cx.size
+    outside = np.zeros(n, np.uint8)
+    hull = np.zeros(max(n, 1), np.int32)
+    n_hull = ctypes.c_int64(0)
+    rc = entry(*head, _lib.ptr(cx), _lib.ptr(cy), _lib.ptr(type), _lib.ptr(valid), _lib.ptr(empty), n, _lib.ptr(outside),
+               _lib.ptr(hull), n, ctypes.byref(n_hull))
+    return outside, _hull_result(rc, hull, n_hull)
+
+
+def sensory_region_dev(labels_ptr, types_ptr, n_pix, cx, cy, type, valid, empty=None):
+    """tip_sensory_region_i32_dev: the rows with type == 1, valid == 1 and empty == 0 (host uint8 rows; type and valid None: every
+    row) span the hull; -> (outside uint8[n], hull int32[h] of row positions), every row tested, and with labels_ptr / types_ptr
+    (DEVICE maps of n_pix pixels; both None: no map) 255 painted on the outside rows' pixels.  NoHullError when there is no hull --
+    nothing is painted then --, ValueError for a non-finite centroid."""
+    rows = _sensory_rows(cx, cy, type, valid, empty)
+    return _sensory_call(_lib.lib().tip_sensory_region_i32_dev, (labels_ptr, types_ptr, int(n_pix)), *rows)
+
+
+def sensory_region_host(cx, cy, type, valid, empty=None):
+    """tip_sensory_region_host: the same selection, hull and test on the CPU (no device), the device forms' checker."""
+    rows = _sensory_rows(cx, cy, type, valid, empty)
+    return _sensory_call(_lib.load().tip_sensory_region_host, (), *rows)
+
+
 # ---- event detection of one frame pair (csrc/tip_events.hip) ------------------------------------------------------------------------
 def border_rows(labels, n=None):
     """tip_border_rows_i32: uint8[n], 1 where label r + 1 touches the map's border (Tissue.detect_edge_cells as row flags)."""

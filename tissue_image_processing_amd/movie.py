@@ -33,6 +33,14 @@ on the resident labels and Atoh-channel projection (one device call, tip_cell_ty
 and mean_intensity, named in the backend's `extra_columns`, travel with the centroid tables, and the type map stays on the
 owner GPU next to the label map.
 
+With `GpuFrameBackend(cell_types=..., sensory_region=True)` the owner then applies the GUI's "remove non-sensory cells" step
+(Tissue.remove_cells_outside_of_sensory_region, ti.py:2781-2792) to the frame, right after its typing and before everything that
+reads `valid` or the type map: the convex hull of the hair cells' centroids is built on the device, every row outside it gets
+valid = 0 and its pixels 255 in the resident type map (one device call, tip_sensory_region_i32_dev).  The frame's dict gains the
+column `in_sensory_region`, `backend.sensory_hulls[t]` the hull's rows; a frame whose hair cells span no hull stays unfiltered and
+is listed in `backend.sensory_skipped`.  Neighbour and order columns, the archive, events and the exported TIFF follow from the
+filtered `valid` and map with no change of their own.
+
 With `GpuFrameBackend(segmentation="unet")` every frame is segmented as the GUI's "use Unet?" path does (gui.py:2059-2063):
 network and closing / watershed tail through FramePipeline.segment_unet, whose labels (and, with keep_hc, HC map) come back in
 frame orientation (Y, X) and are copied on the device into the buffers the classical segmentation fills, so that every stage
@@ -57,6 +65,7 @@ multi-process CPU tests, on a stand-in backend with the gloo process group.
 """
 
 import collections
+import threading
 
 import numpy as np
 
@@ -267,7 +276,7 @@ class GpuFrameBackend(object):
 
     def __init__(self, C, Z, Y, X, device=None, keep_planes=False, inflight=1, cell_types=None, segmentation="classical",
                  unet_weights=None, unet_channels=(1, 0), predictor_factory=None, keep_hc=False, neighbor_features=False,
-                 order_features=False, archive=False, keep_projection=False, **kw):
+                 order_features=False, archive=False, keep_projection=False, sensory_region=False, **kw):
         from .pipeline import FramePipeline
         from . import _lib
         # archive: False, True or dict(type_name="HC", matches="runs") -- every frame's label map (and, with cell_types, its type
@@ -326,6 +335,22 @@ class GpuFrameBackend(object):
         if unknown:
             raise ValueError("cell_types: unknown option(s) %s (known: %s)" % (sorted(unknown), ", ".join(self.CELL_TYPE_OPTIONS)))
         self.extra_columns = self.CELL_TYPE_COLUMNS if cell_types is not None else ()
+        # sensory_region: every typed frame is then filtered as Tissue.remove_cells_outside_of_sensory_region does (FramePipeline.
+        # sensory_region, right after the type call): rows outside the hull of the hair cells -- type == 1, valid == 1, area > 0 --
+        # get valid = 0 and 255 on their pixels of the resident type map; the frame's dict gains in_sensory_region (uint8) and
+        # sensory_hulls[t] the hull's row positions.  A frame without a hull (fewer than three hair cells, or all on one line) stays
+        # unfiltered, its column all ones, and is listed in sensory_skipped; the backend warns once (RuntimeWarning).
+        self.sensory_region = bool(sensory_region)
+        if self.sensory_region:
+            if cell_types is None:
+                raise ValueError("sensory_region: the filter needs the frames' cell types (cell_types=...)")
+            if self.cell_types.get("type_index", 0) != 0:
+                raise ValueError("sensory_region: hair cells are the rows with type == 1, bit 0 alone (cell_types' type_index must be 0)")
+            self.extra_columns = tuple(self.extra_columns) + (("in_sensory_region", np.uint8),)
+        self.sensory_hulls = {}     # frame -> int32 row positions of its hull's vertices, counter-clockwise
+        self.sensory_skipped = []   # frames left unfiltered: their hair cells span no hull; kept in ascending order
+        self._sensory_warned = False
+        self._sensory_lock = threading.Lock()      # (frames in flight finish on worker threads)
         # neighbor_features: every frame's dict also gains the neighbour-graph columns of FramePipeline.neighbor_features (int64
         # per row), computed after the frame's type call; the hc_* / sc_* columns only together with cell_types.  Without
         # cell_types a row is valid as calculate_frame_cellinfo has it: its area strictly between 0.1 and 10 mean areas.
@@ -477,6 +502,8 @@ class GpuFrameBackend(object):
             out.update(p.cell_types(n=tab["area"].size, type_map_ptr=tmap.ptr, **self.cell_types))   # (synchronises)
             self.type_maps[t] = tmap
         n = tab["area"].size
+        if self.sensory_region:
+            self._filter_sensory_region(p, t, n, out)
         valid = out["valid"] if self.cell_types is not None else self._valid_by_area(tab["area"])
         if self.neighbor_features:      # (untyped without cell_types: no "type" column)
             out.update(p.neighbor_features(n, valid, out.get("type"), type_index=(self.cell_types or {}).get("type_index", 0)))
@@ -485,6 +512,27 @@ class GpuFrameBackend(object):
         if self.archive is not None:
             self.archive_frames[t] = self._archive_parts(p, t, tab, out)
         return out
+
+    def _filter_sensory_region(self, p, t, n, out):
+        """Frame t's sensory-region filter on pipeline p's thread: out's valid becomes the filtered one, out gains
+        in_sensory_region, the frame's resident type map is repainted.  No hull: the frame stays as it is, with one warning."""
+        from . import _lib
+        try:
+            res = p.sensory_region(n, out["cy"], out["cx"], out["type"], out["valid"], type_map_ptr=self.type_maps[t].ptr)
+        except _lib.NoHullError as e:
+            import bisect
+            out["in_sensory_region"] = np.ones(n, np.uint8)
+            with self._sensory_lock:
+                bisect.insort(self.sensory_skipped, t)
+                first, self._sensory_warned = not self._sensory_warned, True
+            if first:
+                import warnings
+                warnings.warn("frame %d is left unfiltered, its hair cells span no sensory region (%s); further such frames are "
+                              "listed in sensory_skipped without a warning" % (t, e), RuntimeWarning)
+            return
+        out["in_sensory_region"] = (1 - res["outside"]).astype(np.uint8)
+        out["valid"] = (out["valid"] * out["in_sensory_region"]).astype(np.uint8)
+        self.sensory_hulls[t] = res["hull"]
 
     def _archive_parts(self, p, t, tab, out):
         """Frame t's archive parts on pipeline p's thread: the kept label map (int32) and type map (uint8) deflated on the device

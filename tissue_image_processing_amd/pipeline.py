@@ -289,6 +289,25 @@ class FramePipeline:
         out["voronoi_neighbors"][rows] = blob[8 * m:].view(np.int64)
         return out
 
+    def sensory_region(self, n, cy, cx, type, valid, type_map_ptr=None):
+        """The sensory-region filter of the n table rows (Tissue.remove_cells_outside_of_sensory_region, ti.py:2781-2792; csrc/
+        tip_hull.hip) next to the resident label map: the hull of the hair cells' centroids -- rows with type == 1, valid == 1 and
+        area > 0 (the areas cell_tables() left) --, every row tested against it, and 255 painted on the outside rows' pixels of the
+        type map at type_map_ptr (self.d_types by default).  One device call (tip_sensory_region_i32_dev): the rows go up in one
+        copy, outside (uint8, 1 = strictly outside) and hull (int32 row positions, counter-clockwise) come back in one.  Raises
+        _lib.NoHullError, the map untouched, when the hair cells span no hull.  cy, cx, type, valid: host arrays of n rows."""
+        from . import _segmentation as seg
+        n = int(n)
+        if getattr(self, "tables", None) is None or self.tables["area"].size != n:
+            raise RuntimeError("sensory_region(n=%d) follows cell_tables() of the same frame" % n)
+        if type_map_ptr is None:
+            if getattr(self, "d_types", None) is None:
+                raise RuntimeError("sensory_region follows cell_types() of the same frame")
+            type_map_ptr = self.d_types.ptr
+        outside, hull = seg.sensory_region_dev(self.d_labels.ptr, type_map_ptr, self.Y * self.X, cx, cy, type, valid,
+                                               (self.tables["area"] <= 0).astype(np.uint8))
+        return dict(outside=outside, hull=hull)
+
     def fetch_cell_types(self):
         return self.d_types.download((self.Y, self.X), np.uint8)
 

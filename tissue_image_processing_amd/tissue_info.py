@@ -19,6 +19,8 @@ reference's state / cache / persistence code (ti.py:193-353, 3462-3823) stays th
     calculate_n_neighbors_from_type / _by_type,            ti.py:1752-1799, 2513-2543, 1844-1872, 1065-1096 -> tip_graph_counts_i32,
     find_second_order_neighbors, calculate_contact_length,     tip_graph_second_i32, tip_contact_pairs_i32 + tip_contact_sums_i32
     calculate_contact_lengths
+    detect_non_sensory_region_cells(cells_info),           ti.py:614-620, 2781-2792 -> tip_sensory_region_i32_dev,
+    remove_cells_outside_of_sensory_region(frame)              tip_invalidate_cells_u8_dev
 """
 
 import numpy as np
@@ -370,6 +372,47 @@ class TissueHipMixin(object):
         invalid_cells_labels = cells_info.label.to_numpy()[~valid]
         cell_types[np.isin(lab, invalid_cells_labels)] = INVALID_TYPE_INDEX
         self.set_cell_types(frame, cell_types)
+        return 0
+
+    # ---- the sensory-region filter (csrc/tip_hull.hip) ------------------------------------------------------
+    @staticmethod
+    def detect_non_sensory_region_cells(cells_info):
+        """ti.py:614-620: the index values of the rows whose centroid (cx, cy) lies strictly outside the convex hull of the hair
+        cells' centroids -- the rows with type == 1 and empty_cell == 0 and valid == 1 (equalities, as upstream's query).  EVERY
+        row of the table is tested, invalid and empty ones at (0, 0) included.  One device call (tip_sensory_region_i32_dev): exact
+        predicates, a row on the hull's boundary is inside.  Deviations, see DESIGN.md 5.13: fewer than three hair cells, or all of
+        them on one line, raise ValueError (upstream: QhullError); a non-finite centroid raises ValueError."""
+        hair = lambda name, value: (cells_info[name].to_numpy() == value).astype(np.uint8)      # noqa: E731
+        outside, _ = seg.sensory_region_dev(None, None, 0, cells_info["cx"].to_numpy(dtype=np.float64),
+                                            cells_info["cy"].to_numpy(dtype=np.float64), hair("type", 1), hair("valid", 1),
+                                            1 - hair("empty_cell", 0))
+        return cells_info.index.to_numpy()[outside != 0]
+
+    def remove_cells_outside_of_sensory_region(self, frame):
+        """ti.py:2781-2792: valid = 0 on the rows detect_non_sensory_region_cells returns and, when the frame has a type map, 255
+        on their pixels (tip_invalidate_cells_u8_dev; every other byte stays).  Returns 0, also without labels; does nothing
+        without a table."""
+        labels = self.get_labels(frame)
+        if labels is None:
+            return 0
+        cells_info = self.get_cells_info(frame)
+        if cells_info is not None:
+            outside_cells_indices = self.detect_non_sensory_region_cells(cells_info)
+            cells_info.loc[outside_cells_indices, "valid"] = 0
+            cell_types = self.get_cell_types(frame)
+            if cell_types is not None and outside_cells_indices.size:
+                n = int(outside_cells_indices.max()) + 1
+                flags = np.zeros(n, np.uint8)
+                flags[outside_cells_indices] = 1
+                lab = np.ascontiguousarray(labels, dtype=np.int32)
+                painted = np.ascontiguousarray(cell_types).astype(np.uint8)
+                if not np.array_equal(painted, cell_types):
+                    raise ValueError("remove_cells_outside_of_sensory_region: the type map does not hold bytes")
+                d_lab, d_types, d_flags = (_lib.DeviceBuffer(a.nbytes).upload(a) for a in (lab, painted, flags))
+                seg.invalidate_cells_dev(d_lab.ptr, d_types.ptr, lab.size, d_flags.ptr, n)
+                cell_types[...] = d_types.download(painted.shape, np.uint8)
+                for buf in (d_lab, d_types, d_flags):
+                    buf.free()
         return 0
 
     # ---- C6 -------------------------------------------------------------------------------------------------
